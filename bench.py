@@ -12,12 +12,19 @@ n_neighbors=10, sample_size=256 -- the graph BASELINE.json quotes its target on.
 resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
 Order of a run: engine + positions; the device is brought to its steady power state (spin_up: the same iterations, untimed,
-for 150 ms -- `spinup_steps` in the JSON line -- after which the starting positions are put back); W untimed warm-up steps;
+for 150 ms, on a second engine over the same graph -- `spinup_steps` in the JSON line); SETTLE_STEPS iterations of the
+measured engine, after which the starting positions are put back (`settle_steps`); W untimed warm-up steps;
 `--repeats` timed passes of EXACTLY K steps each, barrier + synchronize on both sides, the median reported (`value`,
 `ms_per_step`; every pass in `ms_per_step_passes`); then a pass with HIP-event timers for the per-kernel table, the
 parity-mode record and the CPU baseline.
+
+--dump-outputs DIR writes what the timed passes computed, as a caller of the timed path receives it after their last
+step: DIR/positions.npy (float32, n x D; a fixed seeded sample of rows when that exceeds 64 MB).  The inputs -- graph,
+start, sample draws -- follow from the arguments alone, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -50,26 +57,24 @@ HBM_PEAK = 8.0e12       # B/s  (MI355X_MICROARCH.md: HBM3E peak, spec)
 FP32_PEAK = 157.3e12    # FLOP/s (fp32 vector peak = dense fp32 MFMA peak)
 
 
-def make_workload(name, seed=0):
+@functools.lru_cache(maxsize=2)
+def workload_edges(name, seed):
+    """Generated from the seed in every process, never read back from a file: the inputs are this build's, whatever ran
+    before (the big graphs take a minute or more: public_api asks for the bench workload's again)."""
     import graphem_rapids_amd as gra
-    kind, n, prm, D, k, S = WORKLOADS[name]
-    # (the big graphs take minutes to generate: kept in /tmp for the later passes of a profiling job on the same box)
-    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"graphem_bench_{name}_seed{seed}.npy")
-    if n >= 4_000_000 and os.path.exists(cache):
-        edges = np.load(cache)
+    kind, n, prm = WORKLOADS[name][:3]
+    if kind == "rr":
+        edges = gra.random_regular_edges(n, prm, seed=seed)
+    elif kind == "pp":
+        edges = gra.planted_partition_edges(n, *prm[:3], seed=seed, shuffle=(prm[4] if len(prm) > 4 else True))
     else:
-        if kind == "rr":
-            edges = gra.random_regular_edges(n, prm, seed=seed)
-        elif kind == "pp":
-            edges = gra.planted_partition_edges(n, *prm[:3], seed=seed, shuffle=(prm[4] if len(prm) > 4 else True))
-        else:
-            edges = gra.erdos_renyi_edges(n, prm, seed=12345)
-        edges = np.ascontiguousarray(edges, dtype=np.int32)
-        if n >= 4_000_000:
-            try:
-                np.save(cache, edges)
-            except OSError:
-                pass
+        edges = gra.erdos_renyi_edges(n, prm, seed=12345)
+    return np.ascontiguousarray(edges, dtype=np.int32)
+
+
+def make_workload(name, seed=0):
+    _, n, _, D, k, S = WORKLOADS[name]
+    edges = workload_edges(name, seed)
     rng = np.random.default_rng(seed)
     pos = (rng.standard_normal((n, D)) * 0.1).astype(np.float32)  # the reference's own random start (pt.py:369)
     return n, D, k, S, edges, pos
@@ -334,6 +339,12 @@ def public_api(args, device_id):
 
 
 SPINUP_MS = 150.0
+# Iterations of the measured engine between the spin-up (on another engine) and the W warm-up steps, in whole rounds of
+# K.  A fixed number, so that its sample draws do not depend on the clock.  rr1m, alternating runs on one MI355X, ms per
+# timed step: 0.1660 with none of these, 0.1670 after 100, 0.1646 after 1000, and 0.1648 when the spin-up itself ran on
+# the measured engine.  So the iterations right before the timed ones must be the measured engine's own, about as many
+# as a spin-up.
+SETTLE_STEPS = 1000
 
 
 def spin_up(run, sync, steps, reset, agree=None):
@@ -342,7 +353,8 @@ def spin_up(run, sync, steps, reset, agree=None):
     against 164 back to back on a busy device, the SAME layout either way -- tools/warm_probe.py, profiles/r04/final/warm_probe.log).  So the same iterations
     run untimed for SPINUP_MS first, then `reset` puts the starting positions back: the W warm-up steps and the K timed
     steps that follow start from the layout they would have started from without this, on a device in its steady state
-    (the engine's iteration counter, which keys the device sampler, is not put back: same layout, other sample draws).
+    (the engine's iteration counter, which keys the device sampler, is not put back: same layout, other sample draws --
+    so main() spins up a second engine over the same graph, not the measured one; see SETTLE_STEPS).
     The pass BEFORE this is reported as `ms_per_step_cold`."""
     # (every rank must run the SAME number of iterations -- they contain collectives: one timed round, the slowest rank's
     # time agreed on, the number of further rounds derived from that)
@@ -358,6 +370,24 @@ def spin_up(run, sync, steps, reset, agree=None):
     sync()
     reset()
     return (2 + rounds) * steps
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pos):
+    """--dump-outputs: the positions after the last timed step, every row, or -- when they exceed DUMP_MAX_BYTES -- the
+    rows of a fixed seeded sample in ascending order (the same rows in every run of the same workload)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = pos.shape[0]
+    max_rows = (DUMP_MAX_BYTES - 4096) // pos[0].nbytes   # (room for the .npy header)
+    rows = "all"
+    if n > max_rows:
+        idx = np.sort(np.random.default_rng(0).choice(n, max_rows, replace=False))
+        pos = pos[idx]
+        rows = f"{max_rows} of {n}: np.sort(np.random.default_rng(0).choice({n}, {max_rows}, replace=False))"
+    np.save(os.path.join(out_dir, "positions.npy"), np.ascontiguousarray(pos, dtype=np.float32))
+    return {"dir": out_dir, "positions": {"shape": list(pos.shape), "dtype": "float32", "rows": rows}}
 
 
 def self_launch(args):
@@ -431,7 +461,11 @@ def main():
                          "select -> keys -> merge -> statistics; every rank normalises all n rows.  own = form C (round 4): three "
                          "collectives in a row, the rows last.  gathered = form B")
     ap.add_argument("--repeats", type=int, default=3, help="timed passes of --steps iterations; the median is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the positions after the last timed step to DIR/positions.npy (float32; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_baseline_only:   # child of cpu_baseline_pinned(): no GPU, no torch.distributed; one JSON line
         n, D, k, S, edges, pos = make_workload(args.workload)
@@ -486,28 +520,27 @@ def main():
             dist.init_process_group("gloo", rank=rank, world_size=world)
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        lay = PartitionedLayout(n, D, edges, 1.0, 0.2, 0.5, k, S, seed=0, rank=rank, world=world,
-                                device_id=local_rank, native=args.loop == "native", knn_distance=args.knn_distance, finish=args.finish)
-        lay.set_positions(pos)
-        run = lay.run
-        sync = lay.sync
+        def make():   # -> (layout, its engine, run, sync)
+            lay = PartitionedLayout(n, D, edges, 1.0, 0.2, 0.5, k, S, seed=0, rank=rank, world=world, device_id=local_rank,
+                                    native=args.loop == "native", knn_distance=args.knn_distance, finish=args.finish)
+            lay.set_positions(pos)
+            return lay, lay.engine.eng, lay.run, lay.sync
         barrier = dist.barrier
-        eng = lay.engine.eng
     else:
-        eng = _native.Engine(n, D, edges, 1.0, 0.2, 0.5, k, S, seed=0, device_id=local_rank, knn_method=args.knn,
-                             knn_distance=args.knn_distance, ivf_lists=args.ivf_lists, ivf_probes=args.ivf_probes)
-        eng.set_positions(pos)
         stream = None
         if args.sampler == "host":  # ids drawn on the host before the timed region (parity-style stream)
             rng = np.random.default_rng(3)
             stream = np.stack([rng.permutation(E)[:S] for _ in range(max(args.steps, args.warmup))]).astype(np.int32)
 
-        def run(iters):
-            eng.run(iters, None if stream is None else stream[:iters])
-        sync = eng.sync
+        def make():   # -> (layout, its engine, run, sync)
+            eng = _native.Engine(n, D, edges, 1.0, 0.2, 0.5, k, S, seed=0, device_id=local_rank, knn_method=args.knn,
+                                 knn_distance=args.knn_distance, ivf_lists=args.ivf_lists, ivf_probes=args.ivf_probes)
+            eng.set_positions(pos)
+            return None, eng, (lambda iters: eng.run(iters, None if stream is None else stream[:iters])), eng.sync
 
         def barrier():
             return None
+    lay, eng, run, sync = make()
 
     def agree(dt_local):   # the slowest rank's time, the same number on every rank
         if not use_dist:
@@ -518,7 +551,18 @@ def main():
     reset = (lambda: lay.set_positions(pos)) if use_dist else (lambda: eng.set_positions(pos))
     cold_ms = agree(cold_pass(run, sync, args))
     reset()
-    spinup_steps = spin_up(run, sync, max(1, args.steps), reset, agree)
+    # the spin-up runs on a second engine over the same graph: its length follows the clock, and the measured engine's
+    # iteration counter (which keys the device sampler) must not -- so the timed steps draw the same samples in every run.
+    # The measured engine then runs SETTLE_STEPS of its own, and its starting positions are put back.
+    _, spin_eng, spin_run, spin_sync = make()
+    spinup_steps = spin_up(spin_run, spin_sync, max(1, args.steps), lambda: None, agree)
+    spin_eng.close()
+    settle_steps = 0
+    while settle_steps < SETTLE_STEPS:   # (in rounds of K, as the spin-up: a host-drawn stream holds K rows)
+        run(args.steps)
+        settle_steps += args.steps
+    sync()
+    reset()
     run(args.warmup)
     passes = []
     for _ in range(max(1, args.repeats)):   # median of 3 repeats; every pass is exactly --steps iterations
@@ -538,6 +582,11 @@ def main():
             dt = float(t.item())
         passes.append(dt)
     dt = sorted(passes)[len(passes) // 2]
+    # (the file is written at the end; the download idles the device, so it is brought back to its steady state before
+    # the evented pass -- after a bare download the per-kernel times read ~3 % higher)
+    last_pos = (lay if use_dist else eng).get_positions() if args.dump_outputs and rank == 0 else None
+    if args.dump_outputs:
+        spin_up(run, sync, max(1, args.steps), lambda: None, agree)
 
     # per-kernel durations with HIP events on the launching stream: a second pass of the same K steps
     eng.timing_enable(True)
@@ -578,7 +627,8 @@ def main():
         hbm = iter_roofline(ms, E, n, D)
         out = {
             "metric": "layout iterations/s", "value": args.steps / dt, "unit": "iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_steps": spinup_steps, "ms_per_step": ms,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_steps": spinup_steps, "settle_steps": settle_steps,
+            "ms_per_step": ms,
             "ms_per_step_cold": cold_ms,
             "repeats": len(passes), "ms_per_step_passes": [1e3 * p / args.steps for p in passes],
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
@@ -625,6 +675,8 @@ def main():
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_pinned(args)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
+        if last_pos is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last_pos)
         print(json.dumps(out))
     if use_dist:
         import faulthandler

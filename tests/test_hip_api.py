@@ -487,3 +487,41 @@ def test_bench_line_contract_on_a_small_workload():
     for case in d["public_api"]["cases"].values():
         assert case["torch"]["reference_identical"] is True and case["device"]["reference_identical"] is False
         assert case["torch"]["ms_per_iteration"] > 0 and case["device"]["ms_per_iteration"] > 0
+
+
+def test_bench_dump_outputs_are_the_timed_paths_last_positions(tmp_path):
+    """bench.py --dump-outputs DIR: DIR/positions.npy holds the positions after the last timed step, and those follow
+    from the arguments alone -- an engine built from the same workload and driven through the same calls (the cold
+    pass, the settling rounds, each followed by the start put back, the warm-up, three timed passes; the spin-up runs on
+    an engine of its own) ends there."""
+    import json
+    import subprocess
+    import sys
+    from graphem_rapids_amd import _native
+    import bench   # (the repository root is on sys.path: tests/conftest.py)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 5, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                          str(warmup), "--workload", "rr20k", "--no-cpu-baseline", "--no-parity-mode", "--no-public-api",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == steps and d["repeats"] == 3 and d["dump_outputs"]["positions"]["rows"] == "all"
+    got = np.load(tmp_path / "out" / "positions.npy")
+    n, D, k, S, edges, pos = bench.make_workload("rr20k")
+    assert got.dtype == np.float32 and got.shape == (n, D)
+    eng = _native.Engine(n, D, edges, 1.0, 0.2, 0.5, k, S, seed=0)
+    eng.set_positions(pos)
+    eng.run(warmup)
+    eng.run(steps)
+    eng.set_positions(pos)
+    assert d["settle_steps"] >= bench.SETTLE_STEPS and d["settle_steps"] % steps == 0
+    for _ in range(d["settle_steps"] // steps):
+        eng.run(steps)
+    eng.set_positions(pos)
+    eng.run(warmup)
+    for _ in range(3):
+        eng.run(steps)
+    want = eng.get_positions()
+    eng.close()
+    assert np.abs(got - want).max() <= 1e-5   # (other sample draws move the layout by orders of magnitude more)

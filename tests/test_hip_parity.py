@@ -404,8 +404,12 @@ def test_rccl_driver_single_rank():
     ref_eng.run(2)           # device sampler, iterations 3 and 4
     ref = ref_eng.get_positions()
     ref_eng.close()
+    import socket
+    with socket.socket() as s:   # a free port: another job on a shared machine may hold any fixed one
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
     os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = "29577"
+    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
