@@ -104,20 +104,21 @@ static void free_all(gh_engine *h) {
 }
 
 // ---- lifetime ----------------------------------------------------------------------
-extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges,
-                               const gh_params *params, const gh_partition *part) {
-    if (!out) return GH_ERR_INVALID;
-    *out = nullptr;
+gh_status gh_check_create_args(int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges, const gh_params *params,
+                               int f64_max_D, double f64_k_attr) {
     auto fail = [&](gh_status st, const std::string &msg) { g_create_error = msg; return st; };
+    const bool f64 = f64_max_D > 0;
     if (n <= 0) return fail(GH_ERR_INVALID, "Adjacency matrix cannot be empty");
     if (D <= 0) return fail(GH_ERR_INVALID, "Number of components must be positive, got " + std::to_string(D));
+    if (f64 && D > f64_max_D) return fail(GH_ERR_INVALID, "the float64 engine takes up to " + std::to_string(f64_max_D) + " components");
     if (!params) return fail(GH_ERR_INVALID, "params is NULL");
-    if (params->k_attr < 0) return fail(GH_ERR_INVALID, "Attractive force constant k_attr must be non-negative");
+    if ((f64 ? f64_k_attr : params->k_attr) < 0) return fail(GH_ERR_INVALID, "Attractive force constant k_attr must be non-negative");
     if (E < 0 || (E > 0 && !edges)) return fail(GH_ERR_INVALID, "edges is NULL");
     if (params->n_neighbors < 0 || params->sample_size < 0) return fail(GH_ERR_INVALID, "negative n_neighbors / sample_size");
+    const int64_t K = (int64_t)params->n_neighbors + 1;
+    if (f64 && K > 256) return fail(GH_ERR_INVALID, "the float64 engine takes up to 255 neighbours");   // (before the size check)
     if (E >= ((int64_t)1 << 30) || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "graph too large for int32 ids");
-    if ((int64_t)params->n_neighbors + 1 > GH_SEL_BUF - GH_SEL_CHUNK)
-        return fail(GH_ERR_INVALID, "n_neighbors too large for the HIP backend (max 2047)");
+    if (!f64 && K > GH_SEL_BUF - GH_SEL_CHUNK) return fail(GH_ERR_INVALID, "n_neighbors too large for the HIP backend (max 2047)");
     for (int64_t e = 0; e < E; ++e) {
         const int32_t u = edges[2 * e], v = edges[2 * e + 1];
         if (u < 0 || v < 0 || u >= n || v >= n) return fail(GH_ERR_INVALID, "edge endpoint out of range");
@@ -125,285 +126,36 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GH_ERR_HIP, "no HIP device available");
     if (device_id < 0 || device_id >= ndev) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
+    return GH_OK;
+}
 
-    gh_engine *h = new (std::nothrow) gh_engine();
-    if (!h) return fail(GH_ERR_NOMEM, "out of host memory");
-    h->device = device_id;
-    h->n = n; h->E = E; h->D = D; h->LD = gh_ld(D);
-    h->prm = *params;
-    h->k = params->n_neighbors; h->K = h->k + 1;
-    h->S = std::min<int64_t>(params->sample_size, E);
-    const bool auto_method = h->prm.knn_method != GH_KNN_SCAN && h->prm.knn_method != GH_KNN_GRID && h->prm.knn_method != GH_KNN_IVF;
-    if (h->prm.knn_method != GH_KNN_SCAN && h->prm.knn_method != GH_KNN_GRID && h->prm.knn_method != GH_KNN_IVF) {   // AUTO (and anything unknown)
-        // exact methods only.  Whole graph, up to 8 components, thousands of queries: the inverted file in its exact mode
-        // (rr1m, scan / exact IVF us per iteration: D = 3 S = 4096 1063 / 591, 16384 3691 / 766 (grid 1926); D = 6 S = 16384
-        // 5059 / 1401; D = 8 5264 / 2135; 100 K vertices D = 3 S = 4096 384 / 191; profiles/r03/knn_method_sweep.log); else the
-        // grid for <= 3 components from 12288 queries on; else the scan
-        const bool ivf = !part && params->knn_distance == GH_DIST_EXACT && D >= 2 && D <= 8 && h->S >= (D <= 4 ? 4096 : 8192) && E >= 262144;
-        h->prm.knn_method = ivf ? GH_KNN_IVF : (D <= 3 && h->S >= 12288) ? GH_KNN_GRID : GH_KNN_SCAN;
-        if (ivf) { h->prm.ivf_probes = -1; h->prm.ivf_lists = 0; }
-    }
-    if (params->knn_distance != GH_DIST_EXACT && params->knn_distance != GH_DIST_CDIST) { delete h; return fail(GH_ERR_INVALID, "unknown knn_distance"); }
-    h->cdist = params->knn_distance == GH_DIST_CDIST;
-    h->cd_part = h->cdist && part != nullptr;
-    if (h->cdist && !auto_method && params->knn_method != GH_KNN_SCAN) {   // (an explicit request must not be dropped silently)
-        delete h;
-        return fail(GH_ERR_INVALID, "knn_distance = GH_DIST_CDIST re-values the candidates of GH_KNN_SCAN: it cannot be combined with GH_KNN_GRID / GH_KNN_IVF");
-    }
-    if (h->cdist) h->prm.knn_method = GH_KNN_SCAN;   // AUTO: the other searches know exact distances only
-    h->Ksel = h->K + (h->cdist ? 1 : 0);
-    if (part) h->part = *part;
-    else h->part = gh_partition{0, n, 0, E, GH_EDGES_RANGE};
-    if (h->part.edge_rule == GH_EDGES_HASHED) h->part.edge_lo = h->part.edge_hi = 0;  // not used by this rule
-    if (h->part.row_lo < 0 || h->part.row_hi > n || h->part.row_lo > h->part.row_hi || h->part.edge_lo < 0 ||
-        h->part.edge_hi > E || h->part.edge_lo > h->part.edge_hi ||
-        (h->part.edge_rule != GH_EDGES_RANGE && h->part.edge_rule != GH_EDGES_HASHED)) {
-        delete h;
-        return fail(GH_ERR_INVALID, "partition out of range");
-    }
-    h->rows = h->part.row_hi - h->part.row_lo;
+// Environment switches of an engine, read once at creation (include/graphem_hip.h lists them).
+struct create_switches {
+    bool no_presetup = false;   // GRAPHEM_HIP_NO_PRESETUP: keep the next iteration's KNN set-up out of the normalise launch
+                                // (so that per-query flags survive a step for inspection)
+    bool graph = false;         // GRAPHEM_HIP_GRAPH=1: replay iterations from a hipGraph
+    const char *reorder = nullptr;   // GRAPHEM_HIP_REORDER=1 | 2 overrides gh_params.reorder (tests / A-B runs: off, breadth-first)
+    int tau_separate = -1;      // GRAPHEM_HIP_TAU_SEPARATE=1 | 0: thresholds in a launch of their own | in the fused one; -1: by size
+    bool stamps = false;        // GRAPHEM_HIP_STAMPS: wall-clock stamps of the fused launch's workgroups
+};
+static create_switches read_switches() {
+    create_switches sw;
+    sw.no_presetup = getenv("GRAPHEM_HIP_NO_PRESETUP") != nullptr;
+    if (const char *e = getenv("GRAPHEM_HIP_GRAPH")) sw.graph = atoi(e) != 0;
+    sw.reorder = getenv("GRAPHEM_HIP_REORDER");
+    if (const char *e = getenv("GRAPHEM_HIP_TAU_SEPARATE")) sw.tau_separate = atoi(e) != 0;
+    sw.stamps = getenv("GRAPHEM_HIP_STAMPS") != nullptr;
+    return sw;
+}
 
-    auto bail = [&](gh_status st) { g_create_error = h->err; free_all(h); delete h; return st; };
-    if (hipSetDevice(device_id) != hipSuccess) return bail(GH_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(GH_ERR_HIP); }
-    h->stream = h->own_stream;
-    h->pos_rows = n + GH_POS_PAD_ROWS;
-    // Diagnostic switches, read once here (include/graphem_hip.h lists them): GRAPHEM_HIP_NO_PRESETUP keeps the next
-    // iteration's KNN set-up out of the normalise launch (so that per-query flags survive a step for inspection),
-    // GRAPHEM_HIP_GRAPH=1 replays iterations from a hipGraph.
-    h->opt_no_presetup = getenv("GRAPHEM_HIP_NO_PRESETUP") != nullptr;
-    { const char *e = getenv("GRAPHEM_HIP_GRAPH"); h->opt_graph = e && atoi(e) != 0; }
-
-    // Internal vertex order (include/graphem_hip.h GH_REORDER_*): breadth-first numbers, components in
-    // order of their smallest vertex, children in pull-list (= edge id) order.
-    {
-        const bool l2_miss = (double)n * h->LD * sizeof(float) > 3.0 * 1024 * 1024;
-        const bool hashed_ok = !part || part->edge_rule == GH_EDGES_HASHED;
-        int mode = params->reorder;
-        if (const char *e = getenv("GRAPHEM_HIP_REORDER")) mode = atoi(e);  // tests / A-B runs: 1 off, 2 BFS
-        const bool reorder = hashed_ok && E > 0 && (mode == GH_REORDER_BFS || (mode == GH_REORDER_AUTO && l2_miss));
-        if (reorder) {
-            std::vector<int64_t> off((size_t)n + 1, 0);
-            for (int64_t e = 0; e < E; ++e) { off[(size_t)edges[2 * e] + 1]++; off[(size_t)edges[2 * e + 1] + 1]++; }
-            for (int64_t i = 0; i < n; ++i) off[(size_t)i + 1] += off[(size_t)i];
-            std::vector<int32_t> nb((size_t)off[(size_t)n]);
-            {
-                std::vector<int64_t> cur(off.begin(), off.end() - 1);
-                for (int64_t e = 0; e < E; ++e) {
-                    const int32_t u = edges[2 * e], v = edges[2 * e + 1];
-                    nb[(size_t)cur[(size_t)u]++] = v;
-                    nb[(size_t)cur[(size_t)v]++] = u;
-                }
-            }
-            h->order_host.assign((size_t)n, -1);
-            std::vector<int32_t> queue((size_t)n);
-            int64_t head = 0, tail = 0, next = 0;
-            for (int64_t root = 0; root < n; ++root) {
-                if (h->order_host[(size_t)root] >= 0) continue;
-                h->order_host[(size_t)root] = (int32_t)next++;
-                queue[(size_t)tail++] = (int32_t)root;
-                while (head < tail) {
-                    const int32_t x = queue[(size_t)head++];
-                    for (int64_t j = off[(size_t)x]; j < off[(size_t)x + 1]; ++j) {
-                        const int32_t y = nb[(size_t)j];
-                        if (h->order_host[(size_t)y] < 0) { h->order_host[(size_t)y] = (int32_t)next++; queue[(size_t)tail++] = y; }
-                    }
-                }
-            }
-            // Within blocks of 16384 consecutive breadth-first numbers, rows in order of falling degree: the lanes of a wave
-            // walk their pull lists in lock-step, so a wave costs its LONGEST list.  G(n, p) at 1 M vertices (Poisson
-            // degrees, mean 10): fused kernel 172.5 -> 163 us with blocks of 8 K - 32 K rows, 168 with 256, 170 - 172 with
-            // 256 K or the whole graph (the breadth-first locality is gone); a regular graph is left as it is (stable sort).
-            {
-                const int64_t B = 16384;
-                {
-                    std::vector<int32_t> inv((size_t)n);
-                    for (int64_t v = 0; v < n; ++v) inv[(size_t)h->order_host[(size_t)v]] = (int32_t)v;
-                    for (int64_t b0 = 0; b0 < n; b0 += B) {
-                        const int64_t b1 = std::min(n, b0 + B);
-                        std::stable_sort(inv.begin() + b0, inv.begin() + b1, [&](int32_t a, int32_t c) {
-                            return off[(size_t)a + 1] - off[(size_t)a] > off[(size_t)c + 1] - off[(size_t)c];
-                        });
-                    }
-                    for (int64_t i = 0; i < n; ++i) h->order_host[(size_t)inv[(size_t)i]] = (int32_t)i;
-                }
-            }
-            h->edges_internal.resize((size_t)E * 2);
-            for (int64_t i = 0; i < 2 * E; ++i) h->edges_internal[(size_t)i] = h->order_host[(size_t)edges[i]];
-            edges = h->edges_internal.data();  // everything below works on internal vertex numbers
-            if (!part) h->part = gh_partition{0, n, 0, 0, GH_EDGES_HASHED};
-        }
-    }
-
-    // Hubs (common.h GH_LONG_DEG): degrees over the WHOLE graph, so that every rank sees the same set.
-    // A graph that has any takes the flagged ownership rule (it lets the short endpoint of a hub's
-    // edge own it, so that no row owns more than a workgroup's tile).
-    std::vector<int32_t> deg((size_t)n, 0);
-    for (int64_t i = 0; i < 2 * E; ++i) deg[(size_t)edges[i]]++;
-    bool has_long = false;
-    h->long_deg = gh_long_degree(n, E);
-    const int long_deg = h->long_deg;
-    for (int64_t i = 0; i < n && !has_long; ++i) has_long = deg[(size_t)i] > long_deg;
-    if (has_long && part && part->edge_rule != GH_EDGES_HASHED) has_long = false;  // range partitions: as before
-    // A whole-graph engine always takes the hashed rule: under "endpoint 0 owns" vertex i of a u < v edge list owns its
-    // edges to higher-numbered neighbours only -- 8 for the first vertices of an 8-regular graph, 0 for the last -- so the
-    // fused workgroups at the end of the vertex range held 1024 rows for a few hundred owned edges and took 31 us where the
-    // median workgroup took 18 (tools/stamp_probe.py, 100 K vertices): they were the length of the kernel.
-    if (!part) h->part = gh_partition{0, n, 0, 0, GH_EDGES_HASHED};
-
-    // Pull lists of the own rows in the reference's summation order (pt.py:633-634):
-    // first the edges where the vertex is endpoint 0, then those where it is endpoint 1,
-    // each in edge-list order.  Bit 31 of an entry marks the edges this row OWNS (emits the
-    // midpoint of, and searches in the KNN phase).  Ownership rule GH_EDGES_RANGE: the edges
-    // [edge_lo, edge_hi), each owned by its endpoint 0.  GH_EDGES_HASHED (partitioned engines):
-    // a hash of the edge id picks the owning endpoint, so every rank owns ~E/world edges
-    // whatever the vertex numbering (with endpoint-0 ownership the low-numbered ranks of a
-    // u<v edge list hold most of the edges); an edge between a hub and a short row always belongs to
-    // the short row.
+// Device buffers of the engine, in the order they have always been allocated, and the plan's arrays on them.
+static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const create_switches &sw) {
+    const int64_t n = h->n, E = h->E;
+    const int D = h->D;
     const bool hashed = h->part.edge_rule == GH_EDGES_HASHED;
-    auto owner_is_v = [&](int64_t e) {
-        if (has_long) {
-            const int32_t du = deg[(size_t)edges[2 * e]], dv = deg[(size_t)edges[2 * e + 1]];
-            const bool lu = du > long_deg, lv = dv > long_deg;
-            if (lu != lv) return lu;
-            // between two long rows the one with FEWER neighbours owns the edge (equal degrees: the hash): a hub then owns
-            // edges to bigger hubs only, and no row owns more than a fused workgroup's tile (a 1045-degree hub of a graph whose
-            // rows are all long owned 520 edges by the hash alone and forced the whole engine onto its unfused kernels)
-            if (lu && du != dv) return du > dv;
-        }
-        uint32_t x = (uint32_t)e * 0x9E3779B1u;
-        x ^= x >> 15; x *= 0x85EBCA6Bu; x ^= x >> 13;
-        return (x >> 31) != 0;
-    };
-    std::vector<int32_t> rowptr((size_t)h->rows + 1, 0);
-    const int64_t lo = h->part.row_lo, hi = h->part.row_hi;
-    for (int64_t e = 0; e < E; ++e) {
-        const int32_t u = edges[2 * e], v = edges[2 * e + 1];
-        if (u >= lo && u < hi) rowptr[(size_t)(u - lo) + 1]++;
-        if (v >= lo && v < hi) rowptr[(size_t)(v - lo) + 1]++;
-    }
-    for (int64_t i = 0; i < h->rows; ++i) rowptr[(size_t)i + 1] += rowptr[(size_t)i];
-    h->adj_len = rowptr[(size_t)h->rows];
-    std::vector<int32_t> adj((size_t)std::max<int64_t>(h->adj_len, 1));
-    std::vector<int32_t> adj_eid(hashed ? (size_t)std::max<int64_t>(h->adj_len, 1) : 0);
-    {
-        std::vector<int32_t> cur(rowptr.begin(), rowptr.end() - 1);
-        for (int64_t e = 0; e < E; ++e) {
-            const int32_t u = edges[2 * e], v = edges[2 * e + 1];
-            if (u >= lo && u < hi) {
-                const size_t at = (size_t)cur[(size_t)(u - lo)]++;
-                const bool own = hashed ? !owner_is_v(e) : (e >= h->part.edge_lo && e < h->part.edge_hi);
-                adj[at] = (int32_t)((uint32_t)v | (own ? 0x80000000u : 0u));
-                if (hashed) adj_eid[at] = (int32_t)e;
-            }
-        }
-        for (int64_t e = 0; e < E; ++e) {
-            const int32_t u = edges[2 * e], v = edges[2 * e + 1];
-            if (v >= lo && v < hi) {
-                const size_t at = (size_t)cur[(size_t)(v - lo)]++;
-                const bool own = hashed && owner_is_v(e);
-                adj[at] = (int32_t)((uint32_t)u | (own ? 0x80000000u : 0u));
-                if (hashed) adj_eid[at] = (int32_t)e;
-            }
-        }
-    }
-
-    // d_first_edge[i]: where the midpoints of row i's owned edges go.  Range rule, edges sorted by
-    // first endpoint (always true for the reference's CSR-order edge list): the owned edges of a
-    // row are consecutive ids and the offset is the first of them.  Hashed rule: a prefix count
-    // into the list own_eids of owned edge ids in (row, pull list) order.
-    std::vector<int32_t> first_edge((size_t)h->rows + 1, 0);
-    std::vector<int32_t> own_eids, long_rows, long_ownptr, long_ownadj, long_eptr, long_erow;
-    std::vector<uint8_t> own_long;
-    if (hashed) {
-        own_eids.reserve((size_t)(E / std::max<int64_t>(1, n / std::max<int64_t>(h->rows, 1)) + 16));
-        for (int64_t i = 0; i < h->rows; ++i) {
-            first_edge[(size_t)i] = (int32_t)own_eids.size();
-            for (int32_t j = rowptr[(size_t)i]; j < rowptr[(size_t)i + 1]; ++j)
-                if ((uint32_t)adj[(size_t)j] >> 31) own_eids.push_back(adj_eid[(size_t)j]);
-        }
-        first_edge[(size_t)h->rows] = (int32_t)own_eids.size();
-        h->own_count = (int64_t)own_eids.size();
-        if (has_long) {  // the own hub rows and the (hub-hub) edges they own, for spring_long_kernel / spring_row
-            long_ownptr.push_back(0);
-            long_eptr.push_back(0);
-            for (int64_t i = 0; i < h->rows; ++i) {
-                if (rowptr[(size_t)i + 1] - rowptr[(size_t)i] <= long_deg) continue;
-                long_rows.push_back((int32_t)i);
-                long_eptr.push_back(long_eptr.back() + (rowptr[(size_t)i + 1] - rowptr[(size_t)i]));
-                for (int32_t j = rowptr[(size_t)i]; j < rowptr[(size_t)i + 1]; ++j)
-                    if ((uint32_t)adj[(size_t)j] >> 31) long_ownadj.push_back((int32_t)((uint32_t)adj[(size_t)j] & 0x7FFFFFFFu));
-                long_ownptr.push_back((int32_t)long_ownadj.size());
-            }
-            h->nlong = (int)long_rows.size();
-            h->long_entries = long_eptr.back();
-            for (size_t r = 0; r + 1 < long_eptr.size(); ++r) h->long_max_deg = std::max(h->long_max_deg, (int)(long_eptr[r + 1] - long_eptr[r]));
-            long_erow.resize((size_t)h->long_entries);   // list entry -> index of its long row (spares long_terms_kernel a binary search)
-            for (size_t r = 0; r + 1 < long_eptr.size(); ++r)
-                for (int32_t t = long_eptr[r]; t < long_eptr[r + 1]; ++t) long_erow[(size_t)t] = (int32_t)r;
-            own_long.assign(own_eids.size() + 1, 0);   // owned-edge slots of the long rows
-            for (int64_t i = 0; i < h->rows; ++i)
-                if (rowptr[(size_t)i + 1] - rowptr[(size_t)i] > long_deg)
-                    for (int32_t sl = first_edge[(size_t)i]; sl < (i + 1 < h->rows ? first_edge[(size_t)i + 1] : (int32_t)own_eids.size()); ++sl)
-                        own_long[(size_t)sl] = 1;
-        }
-        h->mid_base = 0;
-        h->fused_mid = true;
-        std::vector<int32_t>().swap(adj_eid);
-    } else {
-        bool sorted = true;
-        for (int64_t e = 1; e < E && sorted; ++e) sorted = edges[2 * e] >= edges[2 * (e - 1)];
-        if (sorted) {
-            int64_t e = 0;
-            for (int64_t i = 0; i <= h->rows; ++i) {
-                const int64_t x = lo + i;
-                while (e < E && edges[2 * e] < x) ++e;
-                first_edge[(size_t)i] = (int32_t)e;
-            }
-            h->fused_mid = first_edge[0] == h->part.edge_lo && first_edge[(size_t)h->rows] == h->part.edge_hi;
-        }
-        h->own_count = h->part.edge_hi - h->part.edge_lo;
-        h->mid_base = h->part.edge_lo;
-    }
-    // AUTO on a partitioned engine: the same rule with the edges this rank owns (known only now)
-    if (auto_method && part && !h->cdist && D >= 2 && D <= 8 && h->S >= (D <= 4 ? 4096 : 8192) && h->own_count >= 262144) {
-        h->prm.knn_method = GH_KNN_IVF;
-        h->prm.ivf_probes = -1;
-        h->prm.ivf_lists = 0;
-    }
-    // Vertex ranges of the fused spring+scan workgroups: as many consecutive own rows as hold at
-    // most TILE owned edges (and at most 1024 rows, 4 per thread).
-    std::vector<int32_t> vblock;
-    {
-        const int tile = gh_fused_tile(h);
-        const bool dim_ok = gh_dim_templated(D);
-        bool ok = h->fused_mid && dim_ok;
-        if (ok) {
-            vblock.push_back(0);
-            int64_t i = 0;
-            while (i < h->rows && ok) {
-                int64_t j = i, cnt = 0;
-                while (j < h->rows && j - i < 1024) {
-                    const int64_t own = first_edge[(size_t)j + 1] - first_edge[(size_t)j];
-                    if (own > tile) { ok = false; break; }  // a single row owns more than a tile: unfused path
-                    if (cnt + own > tile) break;
-                    cnt += own;
-                    ++j;
-                }
-                if (!ok) break;
-                vblock.push_back((int32_t)j);
-                i = j;
-            }
-        }
-        h->fused_scan = ok;
-        if (!ok) vblock.assign(1, 0);
-        h->n_vblocks = (int)vblock.size() - 1;
-    }
-
     const size_t nLD = (size_t)n * h->LD, S = (size_t)h->S;
     gh_status st;
-#define GH_A(p, count, zero) if ((st = dev_alloc(h, &h->p, (count), (zero))) != GH_OK) return bail(st)
-#define GH_A2(p, count) if ((st = dev_alloc(h, &h->p, (count), true)) != GH_OK) return bail(st)
+#define GH_A(p, count, zero) GH_TRY(dev_alloc(h, &h->p, (count), (zero)))
     GH_A(d_edges, (size_t)E * 2, false);
     GH_A(d_rowptr, (size_t)h->rows + 1, false);
     GH_A(d_adj, (size_t)h->adj_len, false);
@@ -412,19 +164,19 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     GH_A(d_Fs, (size_t)h->rows * h->LD, true);
     // candidate lists and the threshold subset exist only for the filtered scan (64 KiB per query)
     const bool scan_path = gh_knn_scan_path(h);
-    GH_A(d_gmin, (size_t)gh_gmin_floats(h), true);  // also fixes the threshold subset (thr_stride, thr_M1)
+    GH_A(d_gmin, (size_t)gh_gmin_floats(h), true);
     GH_A(d_sub_uv, (size_t)h->thr_M1 * 2, false);
-    if (hashed) GH_A(d_own_eids, own_eids.size() + 1, true);
+    if (hashed) GH_A(d_own_eids, g.own_eids.size() + 1, true);
     if (h->nlong) {
-        GH_A(d_long_rows, long_rows.size(), false);
-        GH_A(d_long_ownptr, long_ownptr.size(), false);
-        GH_A(d_long_ownadj, long_ownadj.size() + 1, true);
-        GH_A(d_long_eptr, long_eptr.size(), false);
-        GH_A(d_long_erow, long_erow.size() + 1, false);
+        GH_A(d_long_rows, g.long_rows.size(), false);
+        GH_A(d_long_ownptr, g.long_ownptr.size(), false);
+        GH_A(d_long_ownadj, g.long_ownadj.size() + 1, true);
+        GH_A(d_long_eptr, g.long_eptr.size(), false);
+        GH_A(d_long_erow, g.long_erow.size() + 1, false);
         GH_A(d_long_terms, (size_t)h->long_entries * D, false);
-        GH_A(d_own_long, own_long.size(), false);
+        GH_A(d_own_long, g.own_long.size(), false);
     }
-    GH_A(d_vblock, vblock.size(), false);
+    GH_A(d_vblock, g.vblock.size(), false);
     GH_A(d_pos, (size_t)h->pos_rows * h->LD, true);
     GH_A(d_new, (size_t)h->rows * h->LD, true);
     GH_A(d_tmpF, nLD, true);
@@ -442,7 +194,7 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     if ((st = dev_alloc(h, &h->d_cand, scan_path ? S * GH_CAND_CAP : 1, false)) != GH_OK) {
         h->err = "hipMalloc of the KNN candidate lists failed: sample_size = " + std::to_string(h->S) + " needs " +
                  std::to_string((S * GH_CAND_CAP * sizeof(uint64_t)) >> 20) + " MiB (128 KiB per sampled midpoint)";
-        return bail(st);
+        return st;
     }
     GH_A(d_cnt, S * GH_CNT_STRIDE, true);
     GH_A(d_ovf, S, true);
@@ -457,62 +209,95 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     h->nblocks_update = (int)((h->rows + 255) / 256);
     GH_A(d_blockstats, (size_t)std::max(std::max(h->nblocks_update, h->n_vblocks), 1) * 2 * h->LD, true);
     GH_A(d_stats, (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD, true);
-#undef GH_A
     h->d_sampled_cur = h->d_sampled;
     auto up = [&](void *dst, const void *src, size_t bytes) {
         return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
     };
-    if (!up(h->d_edges, edges, sizeof(int32_t) * 2 * (size_t)E) ||
-        !up(h->d_rowptr, rowptr.data(), sizeof(int32_t) * rowptr.size()) ||
-        !up(h->d_adj, adj.data(), sizeof(int32_t) * (size_t)h->adj_len) ||
-        !up(h->d_first_edge, first_edge.data(), sizeof(int32_t) * first_edge.size()) ||
-        !up(h->d_vblock, vblock.data(), sizeof(int32_t) * vblock.size()) ||
-        (hashed && !up(h->d_own_eids, own_eids.data(), sizeof(int32_t) * own_eids.size())) ||
-        (h->nlong && (!up(h->d_long_rows, long_rows.data(), sizeof(int32_t) * long_rows.size()) ||
-                      !up(h->d_long_ownptr, long_ownptr.data(), sizeof(int32_t) * long_ownptr.size()) ||
-                      !up(h->d_long_eptr, long_eptr.data(), sizeof(int32_t) * long_eptr.size()) ||
-                      !up(h->d_long_erow, long_erow.data(), sizeof(int32_t) * long_erow.size()) ||
-                      !up(h->d_long_ownadj, long_ownadj.data(), sizeof(int32_t) * long_ownadj.size()) ||
-                      !up(h->d_own_long, own_long.data(), own_long.size()))) ||
+    auto up32 = [&](void *dst, const std::vector<int32_t> &v) { return up(dst, v.data(), sizeof(int32_t) * v.size()); };
+    if (!up(h->d_edges, g.edges, sizeof(int32_t) * 2 * (size_t)E) || !up32(h->d_rowptr, g.rowptr) ||
+        !up(h->d_adj, g.adj.data(), sizeof(int32_t) * (size_t)h->adj_len) || !up32(h->d_first_edge, g.first_edge) ||
+        !up32(h->d_vblock, g.vblock) || (hashed && !up32(h->d_own_eids, g.own_eids)) ||
+        (h->nlong && (!up32(h->d_long_rows, g.long_rows) || !up32(h->d_long_ownptr, g.long_ownptr) ||
+                      !up32(h->d_long_eptr, g.long_eptr) || !up32(h->d_long_erow, g.long_erow) ||
+                      !up32(h->d_long_ownadj, g.long_ownadj) || !up(h->d_own_long, g.own_long.data(), g.own_long.size()))) ||
         hipStreamSynchronize(h->stream) != hipSuccess) {
         h->err = "upload of the graph failed";
-        return bail(GH_ERR_HIP);
+        return GH_ERR_HIP;
     }
-    if ((st = gh_grid_alloc(h)) != GH_OK) return bail(st);
-    if ((st = gh_ivf_alloc(h)) != GH_OK) return bail(st);
-    if ((st = gh_cdist_alloc(h)) != GH_OK) return bail(st);
-    GH_A2(d_tau_flag, 1);
-    GH_A2(d_iter, 1);
-    GH_A2(d_wait_failed, 1);
+    GH_TRY(gh_grid_alloc(h));
+    GH_TRY(gh_ivf_alloc(h));
+    GH_TRY(gh_cdist_alloc(h));
+    GH_A(d_tau_flag, 1, true);
+    GH_A(d_iter, 1, true);
+    GH_A(d_wait_failed, 1, true);
+    if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
+#undef GH_A
+    if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        h->err = "upload of the threshold subset failed";
+        return GH_ERR_HIP;
+    }
+    if (!h->order_host.empty()) {
+        GH_TRY(dev_alloc(h, &h->d_order, (size_t)n, false));
+        if (hipMemcpy(h->d_order, h->order_host.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+            h->err = "upload of the vertex order failed";
+            return GH_ERR_HIP;
+        }
+    }
+    return GH_OK;
+}
+
+extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges,
+                               const gh_params *params, const gh_partition *part) {
+    if (!out) return GH_ERR_INVALID;
+    *out = nullptr;
+    GH_TRY(gh_check_create_args(device_id, n, D, E, edges, params));
+    auto fail = [&](gh_status st, const std::string &msg) { g_create_error = msg; return st; };
+    gh_engine *h = new (std::nothrow) gh_engine();
+    if (!h) return fail(GH_ERR_NOMEM, "out of host memory");
+    auto refuse = [&](const char *msg) { delete h; return fail(GH_ERR_INVALID, msg); };
+    h->device = device_id;
+    h->n = n; h->E = E; h->D = D; h->LD = gh_ld(D);
+    h->prm = *params;
+    h->k = params->n_neighbors; h->K = h->k + 1;
+    h->S = std::min<int64_t>(params->sample_size, E);
+    const bool auto_method = params->knn_method != GH_KNN_SCAN && params->knn_method != GH_KNN_GRID && params->knn_method != GH_KNN_IVF;
+    if (params->knn_distance != GH_DIST_EXACT && params->knn_distance != GH_DIST_CDIST) return refuse("unknown knn_distance");
+    h->cdist = params->knn_distance == GH_DIST_CDIST;
+    h->cd_part = h->cdist && part != nullptr;
+    if (h->cdist && !auto_method && params->knn_method != GH_KNN_SCAN)   // (an explicit request must not be dropped silently)
+        return refuse("knn_distance = GH_DIST_CDIST re-values the candidates of GH_KNN_SCAN: it cannot be combined with GH_KNN_GRID / GH_KNN_IVF");
+    h->Ksel = h->K + (h->cdist ? 1 : 0);
+    if (part) h->part = *part;
+    else h->part = gh_partition{0, n, 0, E, GH_EDGES_RANGE};
+    if (h->part.edge_rule == GH_EDGES_HASHED) h->part.edge_lo = h->part.edge_hi = 0;  // not used by this rule
+    if (h->part.row_lo < 0 || h->part.row_hi > n || h->part.row_lo > h->part.row_hi || h->part.edge_lo < 0 ||
+        h->part.edge_hi > E || h->part.edge_lo > h->part.edge_hi ||
+        (h->part.edge_rule != GH_EDGES_RANGE && h->part.edge_rule != GH_EDGES_HASHED))
+        return refuse("partition out of range");
+    h->rows = h->part.row_hi - h->part.row_lo;
+
+    auto bail = [&](gh_status st) { g_create_error = h->err; free_all(h); delete h; return st; };
+    if (hipSetDevice(device_id) != hipSuccess) return bail(GH_ERR_HIP);
+    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(GH_ERR_HIP); }
+    h->stream = h->own_stream;
+    h->pos_rows = n + GH_POS_PAD_ROWS;
+    const create_switches sw = read_switches();
+    h->opt_no_presetup = sw.no_presetup;
+    h->opt_graph = sw.graph;
+
+    gh_graph_plan g;   // vertex order, ownership, pull lists, owned edges, fused blocks (graph_plan.hip)
+    gh_plan_graph(h, edges, part != nullptr, sw.reorder ? atoi(sw.reorder) : params->reorder, &g);
+    if (auto_method) gh_auto_knn_method(h);   // on the edges this engine searches: known only now
+    gh_choose_threshold_subset(h);            // (knn.hip) the method, own_count, fused_scan, Ksel and S are final here
+    gh_plan_threshold_subset(h, &g);
     // Thresholds by the first workgroups of the fused launch (tau_core.h) where that launch is a single round of
     // workgroups or little more: there the iteration is a chain of launch latencies and this removes one (100 K vertices:
     // 64.9 -> 60.6 us).  A large graph gains nothing (1 M vertices: 175.7 -> 176.7 us, the first round of workgroups waits
     // ~3 us for producers that share their CUs with gathers) and keeps the launch of its own.
-    // GRAPHEM_HIP_TAU_SEPARATE=1 / 0 forces either form.
-    h->tau_embedded = h->n_vblocks <= 2048;
-    if (const char *e = getenv("GRAPHEM_HIP_TAU_SEPARATE")) h->tau_embedded = atoi(e) == 0;
-    if (getenv("GRAPHEM_HIP_STAMPS")) GH_A2(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8);
-    if (h->thr_M1 > 0) {  // endpoints of the threshold subset: every thr_stride-th own edge
-        std::vector<int32_t> sub((size_t)h->thr_M1 * 2);
-        for (int64_t j = 0; j < h->thr_M1; ++j) {
-            const int64_t e = hashed ? (int64_t)own_eids[(size_t)(j * h->thr_stride)] : h->part.edge_lo + j * h->thr_stride;
-            sub[(size_t)(2 * j)] = edges[2 * e];
-            sub[(size_t)(2 * j + 1)] = edges[2 * e + 1];
-        }
-        if (hipMemcpy(h->d_sub_uv, sub.data(), sizeof(int32_t) * sub.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            h->err = "upload of the threshold subset failed";
-            return bail(GH_ERR_HIP);
-        }
-    }
-    if (!h->order_host.empty()) {
-        st = dev_alloc(h, &h->d_order, (size_t)n, false);
-        if (st != GH_OK) return bail(st);
-        if (hipMemcpy(h->d_order, h->order_host.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
-            h->err = "upload of the vertex order failed";
-            return bail(GH_ERR_HIP);
-        }
-    }
-    std::vector<int32_t>().swap(h->edges_internal);
+    h->tau_embedded = sw.tau_separate >= 0 ? sw.tau_separate == 0 : h->n_vblocks <= 2048;
+
+    const gh_status st = allocate_and_upload(h, g, sw);
+    if (st != GH_OK) return bail(st);
     *out = h;
     return GH_OK;
 }
@@ -1052,15 +837,23 @@ extern "C" gh_status gh_step_finish(gh_handle h) {
     return step_finish(h);
 }
 
-extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
+// Checks of the layout calls (name: the call, what: its layout in the message): world blocks of chunk rows, block `rank`
+// the engine's row partition, the blocks within d_pos if within_pos; no layout set yet.
+static gh_status check_layout(gh_engine *h, const char *name, const char *what, int32_t world, int32_t rank, int64_t chunk,
+                              bool within_pos = false) {
     GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_gather_layout"));
-    if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n ||
+    GH_TRY(reject_f64(h, name));
+    if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n || (within_pos && chunk * world > h->pos_rows) ||
         h->part.row_lo != std::min<int64_t>(h->n, rank * chunk) || h->part.row_hi != std::min<int64_t>(h->n, (rank + 1) * chunk)) {
-        h->err = "gather layout does not match the engine's row partition";
+        h->err = std::string(what) + " does not match the engine's row partition";
         return GH_ERR_INVALID;
     }
     if (h->d_gbuf || h->g_world) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
+    return GH_OK;
+}
+
+extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
+    GH_TRY(check_layout(h, "gh_gather_layout", "gather layout", world, rank, chunk));
     const int64_t stats_bytes = (int64_t)sizeof(double) * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
     const int64_t slot = (chunk * h->LD * (int64_t)sizeof(float) + stats_bytes + 15) / 16 * 16;
     GH_HIP(hipStreamSynchronize(h->stream));
@@ -1073,14 +866,7 @@ extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, 
     return GH_OK;
 }
 extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_rank_layout"));
-    if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n || chunk * world > h->pos_rows ||
-        h->part.row_lo != std::min<int64_t>(h->n, rank * chunk) || h->part.row_hi != std::min<int64_t>(h->n, (rank + 1) * chunk)) {
-        h->err = "rank layout does not match the engine's row partition";
-        return GH_ERR_INVALID;
-    }
-    if (h->d_gbuf || h->g_world) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
+    GH_TRY(check_layout(h, "gh_rank_layout", "rank layout", world, rank, chunk, true));
     GH_TRY(dev_alloc(h, &h->d_stats_comb, (size_t)2 * h->LD, true));
     // fewer components than the row stride (3 of 4, 5..7 of 8, 9..15 of 16): the finished blocks travel unpadded
     if (h->D < h->LD && world > 1) {
@@ -1093,14 +879,7 @@ extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, in
 // Form D: form B's finish (every rank normalises all n rows from the gathered un-normalised rows) with the big collective
 // moved to the front of the KNN tail -- see include/graphem_hip.h.
 extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_overlap_layout"));
-    if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n ||
-        h->part.row_lo != std::min<int64_t>(h->n, rank * chunk) || h->part.row_hi != std::min<int64_t>(h->n, (rank + 1) * chunk)) {
-        h->err = "overlap layout does not match the engine's row partition";
-        return GH_ERR_INVALID;
-    }
-    if (h->d_gbuf || h->g_world) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
+    GH_TRY(check_layout(h, "gh_overlap_layout", "overlap layout", world, rank, chunk));
     if (h->LD > 16) { h->err = "gh_overlap_layout: up to 16 components (use gh_rank_layout / gh_gather_layout beyond)"; return GH_ERR_INVALID; }
     const size_t R = (size_t)(2 + 2 * gh_fix_blocks(h->LD));
     // a rank's block of the late all-gather: statistics rows, 16 bytes for the patch count, the patch records

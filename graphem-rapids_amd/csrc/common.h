@@ -222,7 +222,7 @@ __host__ __device__ inline bool gh_dim_templated(int D) {
 // their spring force from spring_long_kernel (forces.hip) beforehand: one wave per row, 64
 // neighbours gathered and their force terms computed in parallel, then ADDED IN LIST ORDER through
 // v_readlane -- the reference's summation order, bit for bit.  Such rows own no edge whose other
-// endpoint is short (api.hip: the short endpoint owns it); the few they do own (hub-hub edges) are
+// endpoint is short (graph_plan.hip: the short endpoint owns it); the few they do own (hub-hub edges) are
 // listed apart so that their midpoints can still be emitted by the row's thread.
 #define GH_LONG_DEG 128
 // Small dense graphs (a SNAP social graph at 16 components: 4 K vertices of mean degree 44) leave a fused workgroup with

@@ -76,7 +76,7 @@ struct gh_engine {
     float *d_Fs = nullptr;        // (rows, LD) spring forces of the own rows
     float *d_gmin = nullptr;      // (S, Gpad) group minima of the threshold subset (setup_core.h), float bits
     int32_t *d_sub_uv = nullptr;  // (thr_M1, 2) endpoints of the subset edges
-    int64_t thr_stride = 0, thr_M1 = 0;  // the subset: every thr_stride-th own edge, thr_M1 of them (0: not chosen yet)
+    int64_t thr_stride = 0, thr_M1 = 0;  // the subset: every thr_stride-th own edge, thr_M1 of them (gh_choose_threshold_subset)
     int32_t *d_vblock = nullptr;  // (n_vblocks + 1) vertex ranges of the fused spring+scan workgroups
     int n_vblocks = 0;
     bool opt_no_presetup = false, opt_graph = false;   // GRAPHEM_HIP_NO_PRESETUP / GRAPHEM_HIP_GRAPH (read at gh_create)
@@ -125,7 +125,6 @@ struct gh_engine {
     uint16_t *d_qA = nullptr;     // (S, 16) f16 A-operand rows of the split-f16 MFMA pre-filter (D <= 3), same kernel
     int32_t *d_order = nullptr;       // internal row of every vertex (BFS reordering), or null: identity
     std::vector<int32_t> order_host;  // the same on the host (empty: identity)
-    std::vector<int32_t> edges_internal;  // gh_create scratch: the edge list in internal vertex numbers
     unsigned char *d_gbuf = nullptr;  // gather buffer of the one-collective finish (gh_gather_layout), or null
     float *d_new_own = nullptr;       // allocations behind d_new / d_stats while they point into d_gbuf
     double *d_stats_own = nullptr;
@@ -212,6 +211,23 @@ struct gh_scope {
     ~gh_scope();
 };
 
+// graph_plan.hip: what gh_create uploads about the graph, computed on the host.  gh_plan_graph also sets the engine's graph
+// scalars (part, order_host, adj_len, own_count, mid_base, fused_mid, the long-row counts, fused_scan, n_vblocks), which the
+// policy functions below read.
+struct gh_graph_plan {
+    const int32_t *edges = nullptr;   // (E, 2) the edge list in internal vertex numbers: `internal` or the caller's
+    std::vector<int32_t> internal;    // ... renumbered by the vertex order (empty: identity)
+    std::vector<int32_t> rowptr, adj; // pull lists of the own rows, bit 31 of an entry: the row owns the edge
+    std::vector<int32_t> first_edge, own_eids, vblock;
+    std::vector<int32_t> long_rows, long_ownptr, long_ownadj, long_eptr, long_erow;
+    std::vector<uint8_t> own_long;
+    std::vector<int32_t> sub_uv;      // (thr_M1, 2) endpoints of the threshold subset
+};
+void gh_plan_graph(gh_engine *h, const int32_t *edges, bool partitioned, int reorder, gh_graph_plan *g);
+void gh_auto_knn_method(gh_engine *h);   // GH_KNN_AUTO -> prm.knn_method (and the IVF parameters): needs own_count
+void gh_plan_threshold_subset(const gh_engine *h, gh_graph_plan *g);   // needs thr_stride / thr_M1
+// pull lists of all n rows without ownership bits (the float64 engine)
+void gh_pull_lists(int64_t n, int64_t E, const int32_t *edges, std::vector<int32_t> &rowptr, std::vector<int32_t> &adj);
 // api.hip / comm.hip
 extern "C" float *gh_rows_all_device(gh_handle h);
 extern "C" int32_t gh_rows_all_row_floats(gh_handle h);
@@ -222,6 +238,9 @@ gh_status gh_step_begin_device_ids(gh_engine *h, const int32_t *dev_ids);
 void gh_comm_free(gh_engine *h);
 // f64.hip
 void gh_set_create_error(const std::string &msg);   // (api.hip) message gh_last_error(NULL) returns
+// (api.hip) argument and device checks of gh_create / gh_create_f64; f64_max_D > 0: the float64 engine's, with its k_attr
+gh_status gh_check_create_args(int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges, const gh_params *params,
+                               int f64_max_D = 0, double f64_k_attr = 0.0);
 void gh_f64_free(gh_engine *h);
 gh_status gh_f64_set_positions_f32(gh_engine *h, const float *pos);
 gh_status gh_f64_get_positions_f32(gh_engine *h, float *pos);
@@ -232,7 +251,8 @@ gh_status gh_f64_knn_midpoints(gh_engine *h, const int32_t *sampled, int32_t *kn
 gh_status gh_knn_local(gh_engine *h, bool fuse_intersect);  // d_sampled, d_mid -> d_partial (unfused)
 bool gh_knn_scan_path(const gh_engine *h);
 struct gh_setup_args;
-gh_setup_args gh_make_setup_args(gh_engine *h, int mode, int32_t *sampled, uint64_t iter);  // setup_core.h
+void gh_choose_threshold_subset(gh_engine *h);   // thr_stride, thr_M1: once knn_method, own_count, fused_scan, Ksel and S are final
+gh_setup_args gh_make_setup_args(const gh_engine *h, int mode, int32_t *sampled, uint64_t iter);  // setup_core.h
 unsigned gh_setup_blocks(const gh_setup_args &a);
 int64_t gh_gmin_floats(const gh_engine *h);   // size of d_gmin
 gh_status gh_knn_prepare(gh_engine *h);

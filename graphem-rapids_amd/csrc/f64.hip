@@ -863,21 +863,8 @@ extern "C" gh_status gh_create_f64(gh_handle *out, int device_id, int64_t n, int
                                    double L_min, double k_attr, double k_inter) {
     if (!out) return GH_ERR_INVALID;
     *out = nullptr;
+    GH_TRY_ST(gh_check_create_args(device_id, n, D, E, edges, params, F64_MAXD, k_attr));
     auto fail = [&](gh_status st, const std::string &msg) { gh_set_create_error(msg); return st; };
-    if (n <= 0) return fail(GH_ERR_INVALID, "Adjacency matrix cannot be empty");
-    if (D <= 0) return fail(GH_ERR_INVALID, "Number of components must be positive, got " + std::to_string(D));
-    if (D > F64_MAXD) return fail(GH_ERR_INVALID, "the float64 engine takes up to 32 components");
-    if (!params) return fail(GH_ERR_INVALID, "params is NULL");
-    if (k_attr < 0) return fail(GH_ERR_INVALID, "Attractive force constant k_attr must be non-negative");
-    if (E < 0 || (E > 0 && !edges)) return fail(GH_ERR_INVALID, "edges is NULL");
-    if (params->n_neighbors < 0 || params->sample_size < 0) return fail(GH_ERR_INVALID, "negative n_neighbors / sample_size");
-    if (params->n_neighbors + 1 > 256) return fail(GH_ERR_INVALID, "the float64 engine takes up to 255 neighbours");
-    if (E >= ((int64_t)1 << 30) || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "graph too large for int32 ids");
-    for (int64_t e = 0; e < E; ++e)
-        if (edges[2 * e] < 0 || edges[2 * e + 1] < 0 || edges[2 * e] >= n || edges[2 * e + 1] >= n) return fail(GH_ERR_INVALID, "edge endpoint out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GH_ERR_HIP, "no HIP device available");
-    if (device_id < 0 || device_id >= ndev) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
     gh_engine *h = new (std::nothrow) gh_engine();
     if (!h) return fail(GH_ERR_NOMEM, "out of host memory");
     h->device = device_id;
@@ -895,15 +882,8 @@ extern "C" gh_status gh_create_f64(gh_handle *out, int device_id, int64_t n, int
     if (!h->f64) { h->err = "out of host memory"; return bail(GH_ERR_NOMEM); }
     gh_f64 *f = h->f64;
     f->L_min = L_min; f->k_attr = k_attr; f->k_inter = k_inter;
-    // pull lists in the reference's summation order (pt.py:633-634): edges where the vertex is endpoint 0, then endpoint 1
-    std::vector<int32_t> rowptr((size_t)n + 1, 0), adj((size_t)std::max<int64_t>(2 * E, 1));
-    for (int64_t e = 0; e < E; ++e) { rowptr[(size_t)edges[2 * e] + 1]++; rowptr[(size_t)edges[2 * e + 1] + 1]++; }
-    for (int64_t i = 0; i < n; ++i) rowptr[(size_t)i + 1] += rowptr[(size_t)i];
-    {
-        std::vector<int32_t> cur(rowptr.begin(), rowptr.end() - 1);
-        for (int64_t e = 0; e < E; ++e) adj[(size_t)cur[(size_t)edges[2 * e]]++] = edges[2 * e + 1];
-        for (int64_t e = 0; e < E; ++e) adj[(size_t)cur[(size_t)edges[2 * e + 1]]++] = edges[2 * e];
-    }
+    std::vector<int32_t> rowptr, adj;
+    gh_pull_lists(n, E, edges, rowptr, adj);   // the reference's summation order (graph_plan.hip)
     const size_t nD = (size_t)n * D;
     {   // update launches: T = nblocks * 256 threads with T a multiple of D (a thread then stays in one column)
         int64_t g = 256, dd = D;

@@ -7,7 +7,7 @@
 //   <  0  EXACT: a query probes every list that can hold one of its k + 1 nearest (ivf_probe_kernel<.., true>: centroid
 //         within sqrt(tau) + min(list radius, sqrt(tau) + distance to the query's nearest centroid), f16 errors on the safe
 //         side), so the rows are those of the scan, id for id.  What GH_KNN_AUTO takes for 2-8 components and thousands of
-//         queries (api.hip).
+//         queries (graph_plan.hip).
 //
 // What makes it an MI355X design rather than a port of a query-major IVF search:
 //  * the coarse quantiser is a flat argmin over C centroids on the MATRIX pipe: one v_mfma_f32_32x32x16_f16 gives

@@ -560,15 +560,17 @@ bool gh_knn_scan_path(const gh_engine *h) {
     return Mtot >= GH_SCAN_MIN_EDGES && h->LD <= 16 && h->D >= 2 && h->Ksel <= GH_EXTRACT_MAX_K && h->S <= 0x7FFFFFFF;
 }
 
+// The threshold subset of the filtered scan: every thr_stride-th own edge, thr_M1 of them (none on the other paths).
+void gh_choose_threshold_subset(gh_engine *h) {
+    const int64_t Mtot = own_edges(h);
+    const bool scan = gh_knn_scan_path(h) && !gh_grid_path(h) && !gh_ivf_path(h);   // the grid / IVF searches take their thresholds from their own structures
+    h->thr_stride = scan ? subset_stride(Mtot, h->Ksel, h->S, gh_fused_tile(h), gh_fused_uses_mfma(h)) : 1;
+    h->thr_M1 = scan ? (Mtot + h->thr_stride - 1) / h->thr_stride : 0;
+}
+
 // Sample ids (if still pending), query records, list reset and -- on the scan path -- the compact
 // threshold subset: one launch.
-gh_setup_args gh_make_setup_args(gh_engine *h, int mode, int32_t *sampled, uint64_t iter) {
-    if (h->thr_stride == 0) {  // fixed at the first use: d_gmin is sized from it
-        const int64_t Mtot = own_edges(h);
-        const bool scan = gh_knn_scan_path(h) && !gh_grid_path(h) && !gh_ivf_path(h);   // the grid / IVF searches take their thresholds from their own structures
-        h->thr_stride = scan ? subset_stride(Mtot, h->Ksel, h->S, gh_fused_tile(h), gh_fused_uses_mfma(h)) : 1;
-        h->thr_M1 = scan ? (Mtot + h->thr_stride - 1) / h->thr_stride : 0;
-    }
+gh_setup_args gh_make_setup_args(const gh_engine *h, int mode, int32_t *sampled, uint64_t iter) {
     const int tiles = (int)((h->thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
     // replayed iterations: the number of the iteration being set up = device counter + (iter - h->iter - 1): the counter
     // was moved to "this iteration + 1" by stats_fix_kernel before the normalise launch that carries the set-up
@@ -583,7 +585,7 @@ unsigned gh_setup_blocks(const gh_setup_args &a) {
     return a.tiles > 0 ? (unsigned)a.tiles : (unsigned)((a.S + 255) / 256);
 }
 int64_t gh_gmin_floats(const gh_engine *h) {
-    const gh_setup_args a = gh_make_setup_args(const_cast<gh_engine *>(h), 0, nullptr, 0);
+    const gh_setup_args a = gh_make_setup_args(h, 0, nullptr, 0);
     if (gh_ivf_path(h)) return h->S * 256 + 4;   // GH_IVF_GROUPS minima per query, written by ivf_probe_kernel
     if (a.tiles == 0) return 4;
     return h->S * a.Gpad + 4;

@@ -67,7 +67,7 @@ def partition_edges(edges, row_lo, row_hi):
 
 
 def edge_owner_is_second(edge_ids):
-    """The hash of the C library's GH_EDGES_HASHED rule (csrc/api.hip, gh_create): True where an
+    """The hash of the C library's GH_EDGES_HASHED rule (csrc/graph_plan.hip, edge_owner): True where an
     edge is owned by its second endpoint."""
     x = (np.asarray(edge_ids, dtype=np.uint64) * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)
     x ^= x >> np.uint64(15)

@@ -149,7 +149,7 @@ class GraphEmbedderHIP:
         # knn_distance='cdist' (the parity mode) ranks the candidates of the fused brute-force scan: it cannot be combined with
         # another search.  An explicit 'grid' / 'ivf' therefore excludes it (ValueError when both are explicit), and 'auto'
         # resolves to 'cdist' only where knn_method='auto' / 'scan' keeps the engine on the scan anyway -- the same size
-        # rule as GH_KNN_AUTO in csrc/api.hip (thousands of sampled midpoints go to the exact inverted file / the grid).
+        # rule as GH_KNN_AUTO in csrc/graph_plan.hip (thousands of sampled midpoints go to the exact inverted file / the grid).
         big_s_ivf = (2 <= n_components <= 8 and self.sample_size >= (4096 if n_components <= 4 else 8192)
                      and self.n_edges >= 262144)
         big_s_grid = n_components <= 3 and self.sample_size >= 12288
