@@ -10,6 +10,8 @@ from .memory_management import (MemoryManager, cleanup_gpu_memory, get_gpu_memor
                                 monitor_memory_usage)
 from .generators import (erdos_renyi_graph, generate_random_regular, erdos_renyi_edges, random_regular_edges, planted_partition_edges,
                          edges_to_adjacency, load_snap_edge_list)
+from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influence, greedy_seed_selection,
+                        run_influence_benchmark)
 
 __version__ = "0.1.0"
 
@@ -52,4 +54,5 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "check_hip_availability", "estimate_memory_usage", "erdos_renyi_graph", "generate_random_regular",
            "erdos_renyi_edges", "random_regular_edges", "planted_partition_edges", "edges_to_adjacency", "load_snap_edge_list",
            "graphem_seed_selection", "MemoryManager", "cleanup_gpu_memory", "get_gpu_memory_info",
-           "get_optimal_chunk_size", "monitor_memory_usage"]
+           "get_optimal_chunk_size", "monitor_memory_usage", "InfluenceGraph", "influence_spread",
+           "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark"]

@@ -31,6 +31,7 @@ SYMBOLS = [
     "gh_torch_randperm_prefix", "gh_torch_randperm_isa", "gh_run_torch_sampled", "gh_set_cdist_replay", "gh_sampler_stats",
     "gh_overlap_layout", "gh_rows_all_device", "gh_rows_all_row_floats", "gh_stats_all_device", "gh_stats_all_block_doubles", "gh_step_rows_early",
     "gh_step_pack_rows", "gh_step_finish_overlap",
+    "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
 ]
 
 
@@ -219,6 +220,18 @@ def load():
     L.gh_device_count.restype = i32
     L.gh_version.argtypes = []
     L.gh_version.restype = ctypes.c_char_p
+    L.gh_ic_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i64, vp, i32]
+    L.gh_ic_create.restype = ctypes.c_int
+    L.gh_ic_destroy.argtypes = [vp]
+    L.gh_ic_destroy.restype = None
+    L.gh_ic_last_error.argtypes = [vp]
+    L.gh_ic_last_error.restype = ctypes.c_char_p
+    L.gh_ic_arc_count.argtypes = [vp]
+    L.gh_ic_arc_count.restype = i64
+    L.gh_ic_set_memory_budget.argtypes = [vp, i64]
+    L.gh_ic_set_memory_budget.restype = ctypes.c_int
+    L.gh_ic_spread.argtypes = [vp, ctypes.c_double, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, i64, vp, vp]
+    L.gh_ic_spread.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -544,6 +557,58 @@ class Engine:
             self._chk(self.lib.gh_timing_get(self.handle, i, ctypes.byref(name), ctypes.byref(ms), ctypes.byref(cnt)))
             out[name.value.decode()] = (ms.value, cnt.value)
         return out
+
+
+class ICGraph:
+    """Thin RAII wrapper over a gh_ic_handle: Monte Carlo Independent Cascade on one graph (include/graphem_hip.h)."""
+
+    def __init__(self, n, arcs, directed=False, device_id=0):
+        self.lib = load()
+        self.handle = ctypes.c_void_p()
+        self.n, self.directed = int(n), bool(directed)
+        arcs = np.ascontiguousarray(arcs, dtype=np.int32).reshape(-1, 2)
+        st = self.lib.gh_ic_create(ctypes.byref(self.handle), int(device_id), self.n, arcs.shape[0], ptr(arcs),
+                                   1 if self.directed else 0)
+        if st != GH_OK:
+            self.handle = ctypes.c_void_p()
+            self._raise(st)
+        self.arcs = int(self.lib.gh_ic_arc_count(self.handle))
+
+    def _raise(self, st):
+        if st == GH_OK:
+            return
+        msg = self.lib.gh_ic_last_error(self.handle if self.handle.value else None)
+        msg = msg.decode() if msg else f"gh_status {st}"
+        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self.lib.gh_ic_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-exception-caught
+            pass
+
+    def set_memory_budget(self, nbytes):
+        """Device bytes of chunk state a spread call may hold (0: the default, 1 GiB)."""
+        self._raise(self.lib.gh_ic_set_memory_budget(self.handle, int(nbytes)))
+
+    def spread(self, sets, p, n_trials, seed=0, max_hops=-1, base=None, per_trial=False):
+        """sets: a list of vertex-id sequences.  Returns totals (n_sets,) int64 and, with per_trial, the (n_sets, n_trials)
+        int32 counts; with a base set both are marginal over it (gh_ic_spread)."""
+        sets = [np.asarray(s, dtype=np.int64).ravel() for s in sets]
+        offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([len(s) for s in sets])
+        verts = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), dtype=np.int32)
+        base = np.ascontiguousarray(np.zeros(0) if base is None else np.asarray(base).ravel(), dtype=np.int32)
+        totals = np.zeros(len(sets), dtype=np.int64)
+        trials = np.zeros((len(sets), int(n_trials)), dtype=np.int32) if per_trial else None
+        self._raise(self.lib.gh_ic_spread(self.handle, float(p), int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          len(sets), ptr(offsets), ptr(verts), ptr(base), len(base), ptr(totals), ptr(trials)))
+        return (totals, trials) if per_trial else totals
 
 
 def knn_points(query, reference, k, device_id=0):

@@ -1,0 +1,532 @@
+// Monte Carlo Independent Cascade on the GPU (include/graphem_hip.h "influence"; graphem-rapids_amd/influence.py).
+//
+// Trials are bit-sliced: word w of a (set, vertex) entry holds trials 64w .. 64w+63, and lane t of a wave evaluates the coin
+// of trial 64w + t, so one __ballot gives the live mask of an arc for 64 trials.  Coins are never stored: they are
+// recomputed from the counter-based hash (header), with mix(seed + t * G) computed once per lane and work item.
+//
+// A BFS level (round r, from the frontier of round r - 1) is two launches:
+//   ic_push_kernel / ic_pull_kernel  next words.  Both are launched; each reads the frontier's entry count on the device
+//                                    and only one does work (pull from `pull_min` entries on, Beamer-style), so the host
+//                                    never waits for a level.  push: a wave per frontier (entry, word), out-arcs in order,
+//                                    ONE 8-byte atomicOr per arc that reaches a new trial (the ballot aggregates the wave;
+//                                    lane q does arc q's memory work, 64 arcs at once).
+//                                    pull: a wave per unvisited (entry, word) of the whole state, in-arcs in order until
+//                                    every unvisited trial is reached, one plain store.  An entry that gains a bit is
+//                                    appended to the next frontier list once (per-entry round stamp).
+//   ic_advance_kernel                visited |= next over the new list (each entry joins the `touched` list the first time),
+//                                    clears the old frontier's words, zeroes the third counter of the ring of three.
+// The host reads the frontier count back every IC_CHECK_EVERY levels only.  Counting (ic_count_kernel) and clearing
+// (ic_reset_kernel) walk the touched list, never the dense state, so a chunk costs what its cascades reach.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/graphem_hip.h"
+
+#define IC_GOLDEN 0x9E3779B97F4A7C15ull
+#define IC_BLOCK 256
+#define IC_MAX_BLOCKS 2048
+#define IC_CHECK_EVERY 4            // levels between two host reads of the frontier count
+#define IC_PULL_DIV 16              // pull from (sets in chunk * n) / IC_PULL_DIV frontier entries on
+#define IC_DEFAULT_BUDGET (1ll << 30)
+
+namespace {
+
+__host__ __device__ __forceinline__ uint64_t ic_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint64_t ic_key(int32_t u, int32_t v, int directed) {
+    const uint32_t a = directed ? (uint32_t)u : (uint32_t)min(u, v);
+    const uint32_t b = directed ? (uint32_t)v : (uint32_t)max(u, v);
+    return ((uint64_t)a << 32) | b;
+}
+
+__device__ __forceinline__ uint64_t ic_valid(int w, int W, int T) {
+    const int r = T - 64 * w;
+    return (w < W - 1 || r >= 64) ? ~0ull : ((1ull << r) - 1);
+}
+
+__device__ __forceinline__ int32_t uni(int32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t uni64(uint64_t x) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+struct IcLevel {
+    const int64_t *out_ptr; const int32_t *out_adj;   // push: arcs u -> v by u
+    const int64_t *in_ptr; const int32_t *in_adj;     // pull: arcs u -> v by v
+    uint64_t *vis, *cur, *nxt;                        // (sets * n, W) words
+    int32_t *mark;                                    // (sets * n) round stamp of the last append
+    uint8_t *touched;                                 // (sets * n) entry is in the touched list
+    const int32_t *cur_list; int32_t *nxt_list; int32_t *touch_list;
+    const int32_t *cur_cnt; int32_t *nxt_cnt; int32_t *zero_cnt; int32_t *touch_cnt;
+    int64_t n, pull_min, dense;                       // dense = sets * n * W
+    uint64_t seed;
+    uint32_t thr;
+    int32_t W, T, directed, round;
+};
+
+__device__ __forceinline__ void ic_append(const IcLevel &a, int32_t e) {   // one lane
+    if (__hip_atomic_load(&a.mark[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.round) return;
+    if (atomicExch(&a.mark[e], a.round) != a.round) a.nxt_list[atomicAdd(a.nxt_cnt, 1)] = e;
+}
+
+__global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
+    const int64_t cnt = *a.cur_cnt;
+    if (cnt == 0 || cnt >= a.pull_min) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t items = cnt * a.W;
+    const int64_t nwaves = (int64_t)gridDim.x * (IC_BLOCK / 64);
+    for (int64_t i0 = ((int64_t)blockIdx.x * (IC_BLOCK / 64) + (threadIdx.x >> 6)) * 64; i0 < items; i0 += nwaves * 64) {
+        const int64_t i = i0 + lane;
+        int32_t e = 0, w = 0;
+        uint64_t f = 0;
+        if (i < items) {
+            e = a.cur_list[i / a.W];
+            w = (int32_t)(i % a.W);
+            f = a.cur[(int64_t)e * a.W + w];
+        }
+        uint64_t todo = __ballot(f != 0);
+        while (todo) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const int32_t ej = uni(__shfl(e, j)), wj = uni(__shfl(w, j));
+            const uint64_t fj = uni64(__shfl(f, j));
+            const int64_t s = ej / a.n;
+            const int32_t u = (int32_t)(ej - s * a.n);
+            const uint64_t h = ic_mix(a.seed + (uint64_t)(64 * wj + lane) * IC_GOLDEN);
+            const int64_t beg = a.out_ptr[u], end = a.out_ptr[u + 1];
+            // 64 arcs at a time: the coins of arc q go to lane q as one live mask, then every lane does its arc's
+            // memory work (visited load, atomicOr, append) in parallel instead of one lane arc after arc
+            for (int64_t k0 = beg; k0 < end; k0 += 64) {
+                const int32_t vk = k0 + lane < end ? a.out_adj[k0 + lane] : 0;
+                const int m = (int)min((int64_t)64, end - k0);
+                uint64_t mine = 0;
+                for (int q = 0; q < m; ++q) {
+                    const int32_t v = __builtin_amdgcn_readlane(vk, q);
+                    const uint64_t live = __ballot((uint32_t)(ic_mix(h ^ ic_key(u, v, a.directed)) >> 40) < a.thr) & fj;
+                    if (lane == q) mine = live;
+                }
+                if (mine) {
+                    const int64_t ev = s * a.n + vk;
+                    const uint64_t nw = mine & ~a.vis[ev * a.W + wj];
+                    if (nw) {
+                        atomicOr((unsigned long long *)&a.nxt[ev * a.W + wj], (unsigned long long)nw);
+                        ic_append(a, (int32_t)ev);
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
+    const int64_t cnt = *a.cur_cnt;
+    if (cnt == 0 || cnt < a.pull_min) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * (IC_BLOCK / 64);
+    for (int64_t i0 = ((int64_t)blockIdx.x * (IC_BLOCK / 64) + (threadIdx.x >> 6)) * 64; i0 < a.dense; i0 += nwaves * 64) {
+        const int64_t i = i0 + lane;   // word index: entry i / W, word i % W
+        uint64_t unv = 0;
+        if (i < a.dense) unv = ~a.vis[i] & ic_valid((int)(i % a.W), a.W, a.T);
+        uint64_t todo = __ballot(unv != 0);
+        while (todo) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const int64_t ij = (int64_t)uni64((uint64_t)(i0 + j));
+            const uint64_t uj = uni64(__shfl(unv, j));
+            const int32_t e = uni((int32_t)(ij / a.W)), wj = uni((int32_t)(ij % a.W));
+            const int64_t s = e / a.n;
+            const int32_t v = (int32_t)(e - s * a.n);
+            const uint64_t *cw = a.cur + s * a.n * a.W + wj;
+            uint64_t acc = 0, h = 0;
+            bool have_h = false;
+            const int64_t beg = a.in_ptr[v], end = a.in_ptr[v + 1];
+            // 64 in-arcs at a time: lane q loads the frontier word of arc q's source, coins only for the nonzero ones
+            for (int64_t k0 = beg; k0 < end && acc != uj; k0 += 64) {
+                int32_t uk = 0;
+                uint64_t fk = 0;
+                if (k0 + lane < end) {
+                    uk = a.in_adj[k0 + lane];
+                    fk = cw[(int64_t)uk * a.W] & uj;
+                }
+                uint64_t arcs = __ballot(fk != 0);
+                while (arcs && acc != uj) {
+                    const int q = __ffsll((unsigned long long)arcs) - 1;
+                    arcs &= arcs - 1;
+                    const int32_t u = __builtin_amdgcn_readlane(uk, q);
+                    const uint64_t f = uni64(__shfl(fk, q)) & ~acc;
+                    if (f == 0) continue;
+                    if (!have_h) { h = ic_mix(a.seed + (uint64_t)(64 * wj + lane) * IC_GOLDEN); have_h = true; }
+                    acc |= __ballot((uint32_t)(ic_mix(h ^ ic_key(u, v, a.directed)) >> 40) < a.thr) & f;
+                }
+            }
+            if (acc && lane == 0) {
+                a.nxt[ij] = acc;
+                ic_append(a, e);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(IC_BLOCK) void ic_advance_kernel(IcLevel a) {
+    const int64_t ncur = (int64_t)*a.cur_cnt * a.W, nnew = (int64_t)*a.nxt_cnt * a.W;
+    const int64_t stride = (int64_t)gridDim.x * IC_BLOCK;
+    const int64_t t0 = (int64_t)blockIdx.x * IC_BLOCK + threadIdx.x;
+    if (t0 == 0) *a.zero_cnt = 0;
+    for (int64_t i = t0; i < ncur; i += stride) a.cur[(int64_t)a.cur_list[i / a.W] * a.W + i % a.W] = 0;
+    for (int64_t i = t0; i < nnew; i += stride) {
+        const int32_t e = a.nxt_list[i / a.W];
+        const int64_t x = (int64_t)e * a.W + i % a.W;
+        a.vis[x] |= a.nxt[x];
+        if (i % a.W == 0 && !a.touched[e]) {
+            a.touched[e] = 1;
+            a.touch_list[atomicAdd(a.touch_cnt, 1)] = e;
+        }
+    }
+}
+
+// Round 0: the seed entries (unique, uploaded to list 0 and to the touched list) get every valid trial.
+__global__ __launch_bounds__(IC_BLOCK) void ic_seed_kernel(const int32_t *__restrict__ seeds, int64_t count, int32_t W, int32_t T,
+                                                          uint64_t *vis, uint64_t *cur, uint8_t *touched) {
+    const int64_t i = (int64_t)blockIdx.x * IC_BLOCK + threadIdx.x;
+    if (i >= count * W) return;
+    const int32_t e = seeds[i / W];
+    const int w = (int)(i % W);
+    const uint64_t m = ic_valid(w, W, T);
+    vis[(int64_t)e * W + w] = m;
+    cur[(int64_t)e * W + w] = m;
+    if (w == 0) touched[e] = 1;
+}
+
+// counts[s][t] = reached vertices of set s in trial t.  A wave takes 64 touched entries and one word; lane t adds bit t of
+// each and flushes its sum with one atomicAdd when the set changes (entries of one set are mostly contiguous).
+__global__ __launch_bounds__(IC_BLOCK) void ic_count_kernel(const int32_t *__restrict__ touch_list, const int32_t *touch_cnt,
+                                                           const uint64_t *__restrict__ vis, int64_t n, int32_t W, int32_t T,
+                                                           int32_t *counts) {
+    const int64_t cnt = *touch_cnt;
+    const int lane = threadIdx.x & 63;
+    const int64_t batches = (cnt + 63) / 64 * W;
+    const int64_t nwaves = (int64_t)gridDim.x * (IC_BLOCK / 64);
+    for (int64_t q = (int64_t)blockIdx.x * (IC_BLOCK / 64) + (threadIdx.x >> 6); q < batches; q += nwaves) {
+        const int64_t b = q / W;
+        const int w = (int)(q % W);
+        const int64_t i = b * 64 + lane;
+        int32_t s = -1;
+        uint64_t x = 0;
+        if (i < cnt) {
+            const int32_t e = touch_list[i];
+            s = (int32_t)(e / n);
+            x = vis[(int64_t)e * W + w];
+        }
+        const int t = 64 * w + lane;
+        int32_t cur_s = -1, acc = 0;
+        for (int j = 0; j < 64; ++j) {
+            const int32_t sj = __shfl(s, j);
+            if (sj < 0) break;
+            if (sj != cur_s) {
+                if (acc && t < T) atomicAdd(&counts[(int64_t)cur_s * T + t], acc);
+                cur_s = sj;
+                acc = 0;
+            }
+            acc += (int32_t)((__shfl(x, j) >> lane) & 1);
+        }
+        if (acc && t < T) atomicAdd(&counts[(int64_t)cur_s * T + t], acc);
+    }
+}
+
+__global__ __launch_bounds__(IC_BLOCK) void ic_reset_kernel(const int32_t *__restrict__ touch_list, const int32_t *touch_cnt,
+                                                           int32_t W, uint64_t *vis, uint64_t *fa, uint64_t *fb, int32_t *mark,
+                                                           uint8_t *touched) {
+    const int64_t items = (int64_t)*touch_cnt * W;
+    for (int64_t i = (int64_t)blockIdx.x * IC_BLOCK + threadIdx.x; i < items; i += (int64_t)gridDim.x * IC_BLOCK) {
+        const int32_t e = touch_list[i / W];
+        const int64_t x = (int64_t)e * W + i % W;
+        vis[x] = 0; fa[x] = 0; fb[x] = 0;
+        if (i % W == 0) { mark[e] = 0; touched[e] = 0; }
+    }
+}
+
+inline int ic_blocks(int64_t threads) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(IC_MAX_BLOCKS, (threads + IC_BLOCK - 1) / IC_BLOCK));
+}
+
+}  // namespace
+
+struct gh_ic {
+    int device = 0;
+    int64_t n = 0, arcs = 0;
+    int directed = 0;
+    hipStream_t stream = nullptr;
+    int64_t *d_out_ptr = nullptr, *d_in_ptr = nullptr;   // d_in_* alias d_out_* for an undirected graph
+    int32_t *d_out_adj = nullptr, *d_in_adj = nullptr;
+    int64_t budget = IC_DEFAULT_BUDGET;
+    // chunk state, grown on demand
+    int64_t cap_words = 0, cap_ents = 0, cap_counts = 0;
+    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
+    int32_t *d_mark = nullptr, *d_list0 = nullptr, *d_list1 = nullptr, *d_touch = nullptr, *d_counts = nullptr, *d_cnt = nullptr;
+    uint8_t *d_touched = nullptr;
+    std::string err;
+};
+
+static thread_local std::string g_ic_error;
+
+namespace {
+
+void ic_free_state(gh_ic *h) {
+    for (void *p : {(void *)h->d_vis, (void *)h->d_fa, (void *)h->d_fb, (void *)h->d_mark, (void *)h->d_list0, (void *)h->d_list1,
+                    (void *)h->d_touch, (void *)h->d_counts, (void *)h->d_cnt, (void *)h->d_touched})
+        if (p) (void)hipFree(p);
+    h->d_vis = h->d_fa = h->d_fb = nullptr;
+    h->d_mark = h->d_list0 = h->d_list1 = h->d_touch = h->d_counts = h->d_cnt = nullptr;
+    h->d_touched = nullptr;
+    h->cap_words = h->cap_ents = h->cap_counts = 0;
+}
+
+// bytes of chunk state per seed set (the budget counts these)
+int64_t ic_bytes_per_set(int64_t n, int W) { return n * (3 * 8 * (int64_t)W + 4 + 1 + 3 * 4); }
+
+gh_status ic_reserve(gh_ic *h, int64_t sets, int32_t W, int32_t T) {
+    // every chunk leaves the state all zero, so any layout that fits reuses it
+    const int64_t words = sets * h->n * W, ents = sets * h->n;
+    if (words <= h->cap_words && ents <= h->cap_ents && sets * T <= h->cap_counts) return GH_OK;
+    ic_free_state(h);
+    auto alloc = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess; };
+    if (!alloc((void **)&h->d_vis, 8 * words) || !alloc((void **)&h->d_fa, 8 * words) || !alloc((void **)&h->d_fb, 8 * words) ||
+        !alloc((void **)&h->d_mark, 4 * ents) || !alloc((void **)&h->d_touched, ents) || !alloc((void **)&h->d_list0, 4 * ents) ||
+        !alloc((void **)&h->d_list1, 4 * ents) || !alloc((void **)&h->d_touch, 4 * ents) ||
+        !alloc((void **)&h->d_counts, 4 * sets * T) || !alloc((void **)&h->d_cnt, 4 * 4)) {
+        ic_free_state(h);
+        h->err = "hipMalloc failed for " + std::to_string(sets) + " seed sets of chunk state";
+        return GH_ERR_NOMEM;
+    }
+    // zero once; afterwards every chunk leaves the state zero behind it (ic_reset_kernel)
+    for (auto [p, bytes] : {std::pair<void *, size_t>{h->d_vis, 8 * words}, {h->d_fa, 8 * words}, {h->d_fb, 8 * words},
+                            {h->d_mark, 4 * ents}, {h->d_touched, (size_t)ents}})
+        if (hipMemsetAsync(p, 0, bytes, h->stream) != hipSuccess) { h->err = "hipMemsetAsync failed"; return GH_ERR_HIP; }
+    h->cap_words = words;
+    h->cap_ents = ents;
+    h->cap_counts = sets * T;
+    return GH_OK;
+}
+
+#define IC_HIP(call)                                                                   \
+    do {                                                                               \
+        const hipError_t e_ = (call);                                                  \
+        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
+    } while (0)
+
+// One chunk: `sets` seed sets given as unique entry ids (s * n + v) in `seeds`; counts -> out (sets, T).
+gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds, int32_t W, int32_t T, uint64_t seed,
+                       uint32_t thr, int32_t max_hops, int32_t *out) {
+    IC_HIP(hipMemsetAsync(h->d_counts, 0, sizeof(int32_t) * sets * T, h->stream));
+    const int32_t c0[4] = {(int32_t)seeds.size(), 0, 0, (int32_t)seeds.size()};   // ring of three + touched count
+    if (!seeds.empty()) {
+        IC_HIP(hipMemcpyAsync(h->d_cnt, c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
+        IC_HIP(hipMemcpyAsync(h->d_list0, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
+        IC_HIP(hipMemcpyAsync(h->d_touch, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
+        const int64_t si = (int64_t)seeds.size() * W;
+        ic_seed_kernel<<<dim3((unsigned)((si + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
+            h->d_list0, (int64_t)seeds.size(), W, T, h->d_vis, h->d_fa, h->d_touched);
+        IC_HIP(hipGetLastError());
+        IcLevel a{};
+        a.out_ptr = h->d_out_ptr; a.out_adj = h->d_out_adj; a.in_ptr = h->d_in_ptr; a.in_adj = h->d_in_adj;
+        a.vis = h->d_vis; a.mark = h->d_mark; a.touched = h->d_touched; a.touch_list = h->d_touch; a.touch_cnt = h->d_cnt + 3;
+        a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = thr; a.directed = h->directed;
+        a.dense = sets * h->n * W;
+        a.pull_min = std::max<int64_t>(1, sets * h->n / IC_PULL_DIV);
+        const int grid = ic_blocks(a.dense);   // a wave per 64 items; no level has more than `dense` items
+        // a level can only find new vertices while fewer than n rounds have passed
+        const int64_t last = max_hops < 0 ? h->n : std::min<int64_t>(max_hops, h->n);
+        for (int64_t r = 1; r <= last; ++r) {
+            a.round = (int32_t)r;
+            a.cur = (r & 1) ? h->d_fa : h->d_fb;
+            a.nxt = (r & 1) ? h->d_fb : h->d_fa;
+            a.cur_list = (r & 1) ? h->d_list0 : h->d_list1;
+            a.nxt_list = (r & 1) ? h->d_list1 : h->d_list0;
+            a.cur_cnt = h->d_cnt + (r - 1) % 3;
+            a.nxt_cnt = h->d_cnt + r % 3;
+            a.zero_cnt = h->d_cnt + (r + 1) % 3;
+            ic_push_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+            ic_pull_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+            ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+            IC_HIP(hipGetLastError());
+            if (r % IC_CHECK_EVERY == 0 && r < last) {
+                int32_t alive = 0;
+                IC_HIP(hipMemcpyAsync(&alive, h->d_cnt + r % 3, sizeof(alive), hipMemcpyDeviceToHost, h->stream));
+                IC_HIP(hipStreamSynchronize(h->stream));
+                if (alive == 0) break;
+            }
+        }
+        const int grid_t = ic_blocks(sets * h->n * W);
+        ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch, h->d_cnt + 3, h->d_vis, h->n, W, T, h->d_counts);
+        ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch, h->d_cnt + 3, W, h->d_vis, h->d_fa, h->d_fb,
+                                                                       h->d_mark, h->d_touched);
+        IC_HIP(hipGetLastError());
+    }
+    IC_HIP(hipMemcpyAsync(out, h->d_counts, sizeof(int32_t) * sets * T, hipMemcpyDeviceToHost, h->stream));
+    IC_HIP(hipStreamSynchronize(h->stream));
+    return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, int64_t n_arcs, const int32_t *arcs, int32_t directed) {
+    auto fail = [&](gh_status st, const std::string &msg) { g_ic_error = msg; return st; };
+    if (!out) return fail(GH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n < 1 || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "n must be in [1, 2^31)");
+    if (n_arcs < 0 || (n_arcs > 0 && !arcs)) return fail(GH_ERR_INVALID, "bad arc list");
+    // canonical arc set: self-loops dropped, duplicates merged; an undirected edge as (min, max)
+    std::vector<uint64_t> key;
+    key.reserve((size_t)n_arcs);
+    for (int64_t i = 0; i < n_arcs; ++i) {
+        const int64_t u = arcs[2 * i], v = arcs[2 * i + 1];
+        if (u < 0 || u >= n || v < 0 || v >= n)
+            return fail(GH_ERR_INVALID, "arc " + std::to_string(i) + " has a vertex id outside [0, n)");
+        if (u == v) continue;
+        const uint64_t a = directed ? u : std::min(u, v), b = directed ? v : std::max(u, v);
+        key.push_back((a << 32) | b);
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    // CSR of arcs by source (push) and by target (pull); undirected: both directions, and the two are the same CSR
+    auto build = [&](bool by_target, std::vector<int64_t> &ptr, std::vector<int32_t> &adj) {
+        ptr.assign((size_t)n + 1, 0);
+        for (uint64_t k : key) {
+            const int32_t a = (int32_t)(k >> 32), b = (int32_t)(k & 0xFFFFFFFFu);
+            if (directed) ++ptr[(by_target ? b : a) + 1];
+            else { ++ptr[a + 1]; ++ptr[b + 1]; }
+        }
+        for (int64_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+        adj.resize((size_t)ptr[n]);
+        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+        for (uint64_t k : key) {
+            const int32_t a = (int32_t)(k >> 32), b = (int32_t)(k & 0xFFFFFFFFu);
+            if (directed) { if (by_target) adj[fill[b]++] = a; else adj[fill[a]++] = b; }
+            else { adj[fill[a]++] = b; adj[fill[b]++] = a; }
+        }
+    };
+    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
+    gh_ic *h = new gh_ic();
+    h->device = device_id;
+    h->n = n;
+    h->arcs = (int64_t)key.size();
+    h->directed = directed ? 1 : 0;
+    auto bail = [&](gh_status st, const std::string &msg) { gh_ic_destroy(h); return fail(st, msg); };
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(GH_ERR_HIP, "hipStreamCreate failed");
+    for (int pass = 0; pass < (directed ? 2 : 1); ++pass) {
+        std::vector<int64_t> ptr;
+        std::vector<int32_t> adj;
+        build(pass == 1, ptr, adj);
+        int64_t *dp = nullptr;
+        int32_t *da = nullptr;
+        if (hipMalloc((void **)&dp, 8 * ptr.size()) != hipSuccess) return bail(GH_ERR_NOMEM, "hipMalloc failed");
+        (pass ? h->d_in_ptr : h->d_out_ptr) = dp;
+        if (hipMalloc((void **)&da, std::max<size_t>(4 * adj.size(), 4)) != hipSuccess) return bail(GH_ERR_NOMEM, "hipMalloc failed");
+        (pass ? h->d_in_adj : h->d_out_adj) = da;
+        if (hipMemcpy(dp, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            (!adj.empty() && hipMemcpy(da, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess))
+            return bail(GH_ERR_HIP, "upload failed");
+    }
+    if (!directed) { h->d_in_ptr = h->d_out_ptr; h->d_in_adj = h->d_out_adj; }
+    *out = h;
+    return GH_OK;
+}
+
+extern "C" void gh_ic_destroy(gh_ic_handle h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    ic_free_state(h);
+    if (h->d_in_ptr && h->d_in_ptr != h->d_out_ptr) (void)hipFree(h->d_in_ptr);
+    if (h->d_in_adj && h->d_in_adj != h->d_out_adj) (void)hipFree(h->d_in_adj);
+    if (h->d_out_ptr) (void)hipFree(h->d_out_ptr);
+    if (h->d_out_adj) (void)hipFree(h->d_out_adj);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+extern "C" const char *gh_ic_last_error(gh_ic_handle h) { return h ? h->err.c_str() : g_ic_error.c_str(); }
+
+extern "C" gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes) {
+    if (!h) return GH_ERR_INVALID;
+    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
+    h->budget = bytes ? bytes : IC_DEFAULT_BUDGET;
+    return GH_OK;
+}
+
+extern "C" int64_t gh_ic_arc_count(gh_ic_handle h) { return h ? h->arcs : -1; }
+
+extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                                  const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                                  int64_t *totals, int32_t *per_trial) {
+    if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (!(p >= 0.0 && p <= 1.0)) return fail(GH_ERR_INVALID, "p must be in [0, 1]");
+    if (n_trials < 1) return fail(GH_ERR_INVALID, "n_trials must be >= 1");
+    if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
+    if (n_sets < 0 || (n_sets > 0 && (!set_offsets || !totals))) return fail(GH_ERR_INVALID, "bad seed-set arguments");
+    if (n_base < 0 || (n_base > 0 && !base)) return fail(GH_ERR_INVALID, "bad base set");
+    if (n_sets > 0 && set_offsets[0] != 0) return fail(GH_ERR_INVALID, "set_offsets[0] must be 0");
+    for (int64_t s = 0; s < n_sets; ++s)
+        if (set_offsets[s + 1] < set_offsets[s]) return fail(GH_ERR_INVALID, "set_offsets must not decrease");
+    const int64_t n_vert = n_sets > 0 ? set_offsets[n_sets] : 0;
+    if (n_vert > 0 && !set_vertices) return fail(GH_ERR_INVALID, "set_vertices is NULL");
+    for (int64_t i = 0; i < n_vert; ++i)
+        if (set_vertices[i] < 0 || set_vertices[i] >= h->n) return fail(GH_ERR_INVALID, "seed vertex id outside [0, n)");
+    for (int64_t i = 0; i < n_base; ++i)
+        if (base[i] < 0 || base[i] >= h->n) return fail(GH_ERR_INVALID, "base vertex id outside [0, n)");
+    if (n_sets == 0) return GH_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    const double tf = std::floor(p * 16777216.0 + 0.5);
+    const uint32_t thr = (uint32_t)std::min(16777216.0, tf);
+    const int32_t T = n_trials, W = (n_trials + 63) / 64;
+    const int64_t per_set = ic_bytes_per_set(h->n, W);
+    int64_t chunk = std::max<int64_t>(1, h->budget / per_set);
+    chunk = std::min<int64_t>({chunk, n_sets, (int64_t)INT32_MAX / h->n});
+    gh_status st = ic_reserve(h, chunk, W, T);
+    if (st != GH_OK) return st;
+    std::vector<int32_t> base_u(base, base + n_base);
+    std::sort(base_u.begin(), base_u.end());
+    base_u.erase(std::unique(base_u.begin(), base_u.end()), base_u.end());
+    std::vector<int32_t> base_counts;
+    if (!base_u.empty()) {   // |R(base)| per trial, with the same coins
+        base_counts.resize(T);
+        st = ic_run_chunk(h, 1, base_u, W, T, seed, thr, max_hops, base_counts.data());
+        if (st != GH_OK) return st;
+    }
+    std::vector<int32_t> counts((size_t)chunk * T), one;
+    std::vector<int32_t> seeds;
+    for (int64_t s0 = 0; s0 < n_sets; s0 += chunk) {
+        const int64_t ns = std::min(chunk, n_sets - s0);
+        seeds.clear();
+        for (int64_t s = 0; s < ns; ++s) {   // unique vertices of base + set s, as entries of the chunk's state
+            one.assign(base_u.begin(), base_u.end());
+            one.insert(one.end(), set_vertices + set_offsets[s0 + s], set_vertices + set_offsets[s0 + s + 1]);
+            std::sort(one.begin(), one.end());
+            one.erase(std::unique(one.begin(), one.end()), one.end());
+            for (int32_t v : one) seeds.push_back((int32_t)(s * h->n + v));
+        }
+        st = ic_run_chunk(h, ns, seeds, W, T, seed, thr, max_hops, counts.data());
+        if (st != GH_OK) return st;
+        for (int64_t s = 0; s < ns; ++s) {
+            int64_t tot = 0;
+            int32_t *row = counts.data() + s * T;
+            for (int32_t t = 0; t < T; ++t) {
+                if (!base_counts.empty()) row[t] -= base_counts[t];
+                tot += row[t];
+            }
+            totals[s0 + s] = tot;
+            if (per_trial) std::copy(row, row + T, per_trial + (s0 + s) * (int64_t)T);
+        }
+    }
+    return GH_OK;
+}

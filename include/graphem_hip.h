@@ -439,6 +439,47 @@ const char *gh_spectral_last_error(void);
  * pseudo-random operand sets over and beyond their fast domain.  Both counts must come back 0.  Blocking. */
 gh_status gh_selftest_arith(int device_id, uint64_t seed, int64_t samples, int64_t *bad_sqrt, int64_t *bad_div);
 
+/* ---- influence: Monte Carlo Independent Cascade (reference influence.py: ndlib_estimated_influence,
+ * greedy_seed_selection; graphem-rapids_amd/influence.py) -------------------------------------------------
+ * A handle over one graph, independent of the layout engine.
+ *
+ * Independent Cascade: round 0 activates the seed set; in round r every vertex activated in round r-1 tries each
+ * inactive neighbour once and succeeds with probability p.  A vertex's hop distance is the round it was activated in.
+ * spread = number of vertices with hop distance <= max_hops (max_hops = -1: no limit).
+ *
+ * Coins are counter-based, so every result can be recomputed bit for bit on the host.  In trial t (0 <= t < n_trials)
+ * the arc pair (a, b) is live iff  coin(seed, t, a, b) < thr,  with uint64 wrapping arithmetic:
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)
+ *     coin   = mix( mix(seed + t * 0x9E3779B97F4A7C15) ^ ((uint64)a << 32 | b) ) >> 40             (24 bits)
+ *     thr    = min(2^24, floor(p * 2^24 + 0.5))                                                      (double, once)
+ * (a, b) = (min(u, v), max(u, v)) for an undirected graph -- both directions share one coin; a cascade tries an
+ * undirected edge at most once, so by deferred decisions the reached set and every hop distance have the distribution
+ * of a separate coin per direction -- and (u, v) per arc u -> v for a directed graph.  The reached set of trial t is
+ * exactly the breadth-first search over the live arcs from the seeds, cut at max_hops.  Results therefore depend only on
+ * (arc set, seed set, p, max_hops, n_trials, seed): not on arc order, duplicate arcs, self-loops, how trials are packed,
+ * how seed sets are batched or chunked. */
+typedef struct gh_ic *gh_ic_handle;
+
+/* arcs: (n_arcs, 2) int32 host array, vertex ids in [0, n).  directed = 0: each row is an undirected edge.  Self-loops
+ * are dropped and duplicates merged; the CSR of arcs by target (and, for a directed graph, by source) is uploaded.
+ * On failure *out = NULL and gh_ic_last_error(NULL) has the message. */
+gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, int64_t n_arcs, const int32_t *arcs, int32_t directed);
+void gh_ic_destroy(gh_ic_handle h);
+const char *gh_ic_last_error(gh_ic_handle h);
+/* Arcs after self-loops and duplicates went (an undirected edge counts once). */
+int64_t gh_ic_arc_count(gh_ic_handle h);
+/* Device bytes of chunk state gh_ic_spread may hold: n * (24 * ceil(n_trials / 64) + 17) bytes per seed set evaluated
+ * at once, at least one set.  0 restores the default, 1 GiB.  Results do not depend on it. */
+gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes);
+/* Evaluates n_sets seed sets with the same coins: set s = set_vertices[set_offsets[s] .. set_offsets[s + 1]) (duplicates
+ * allowed, may be empty).  totals[s] = sum over the n_trials trials of the spread (host int64, n_sets); per_trial (NULL
+ * or host int32 (n_sets, n_trials)) = the spread of every trial.  With n_base > 0 both hold the MARGINAL spread
+ * |R(base + set)| - |R(base)| of each trial instead.  GH_ERR_INVALID for p outside [0, 1], n_trials < 1,
+ * max_hops < -1, a vertex id outside [0, n), decreasing offsets.  Blocking. */
+gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                       const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                       int64_t *totals, int32_t *per_trial);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
