@@ -92,11 +92,9 @@ static void free_all(gh_engine *h) {
     gh_ivf_free(h);
     void *ptrs[] = {h->d_edges, h->d_rowptr, h->d_adj, h->d_pos, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_new_own : (void *)h->d_new, h->d_gbuf, h->d_rows_all, h->d_rows_pk, h->d_stats_all, h->d_tmpF, h->d_tmpF2, h->d_io, h->d_acc,
                     h->d_tflag, h->d_touched, h->d_tcount, h->d_sampled, h->d_q, h->d_qscan, h->d_qA, h->d_qexact, h->d_order, h->d_long_rows, h->d_long_ownptr, h->d_long_ownadj, h->d_long_eptr, h->d_long_erow, h->d_long_terms, h->d_own_long, h->d_cand, h->d_cnt,
-                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_iter, h->d_stats_comb, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
+                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_stats_comb, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
     if (h->h_ring) (void)hipHostFree(h->h_ring);
     for (hipEvent_t e : h->ring_ev)
         if (e) (void)hipEventDestroy(e);
@@ -133,7 +131,6 @@ gh_status gh_check_create_args(int device_id, int64_t n, int32_t D, int64_t E, c
 struct create_switches {
     bool no_presetup = false;   // GRAPHEM_HIP_NO_PRESETUP: keep the next iteration's KNN set-up out of the normalise launch
                                 // (so that per-query flags survive a step for inspection)
-    bool graph = false;         // GRAPHEM_HIP_GRAPH=1: replay iterations from a hipGraph
     const char *reorder = nullptr;   // GRAPHEM_HIP_REORDER=1 | 2 overrides gh_params.reorder (tests / A-B runs: off, breadth-first)
     int tau_separate = -1;      // GRAPHEM_HIP_TAU_SEPARATE=1 | 0: thresholds in a launch of their own | in the fused one; -1: by size
     bool stamps = false;        // GRAPHEM_HIP_STAMPS: wall-clock stamps of the fused launch's workgroups
@@ -141,7 +138,6 @@ struct create_switches {
 static create_switches read_switches() {
     create_switches sw;
     sw.no_presetup = getenv("GRAPHEM_HIP_NO_PRESETUP") != nullptr;
-    if (const char *e = getenv("GRAPHEM_HIP_GRAPH")) sw.graph = atoi(e) != 0;
     sw.reorder = getenv("GRAPHEM_HIP_REORDER");
     if (const char *e = getenv("GRAPHEM_HIP_TAU_SEPARATE")) sw.tau_separate = atoi(e) != 0;
     sw.stamps = getenv("GRAPHEM_HIP_STAMPS") != nullptr;
@@ -209,7 +205,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     h->nblocks_update = (int)((h->rows + 255) / 256);
     GH_A(d_blockstats, (size_t)std::max(std::max(h->nblocks_update, h->n_vblocks), 1) * 2 * h->LD, true);
     GH_A(d_stats, (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD, true);
-    h->d_sampled_cur = h->d_sampled;
+    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled};
     auto up = [&](void *dst, const void *src, size_t bytes) {
         return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
     };
@@ -228,7 +224,6 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_TRY(gh_ivf_alloc(h));
     GH_TRY(gh_cdist_alloc(h));
     GH_A(d_tau_flag, 1, true);
-    GH_A(d_iter, 1, true);
     GH_A(d_wait_failed, 1, true);
     if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
 #undef GH_A
@@ -283,7 +278,6 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     h->pos_rows = n + GH_POS_PAD_ROWS;
     const create_switches sw = read_switches();
     h->opt_no_presetup = sw.no_presetup;
-    h->opt_graph = sw.graph;
 
     gh_graph_plan g;   // vertex order, ownership, pull lists, owned edges, fused blocks (graph_plan.hip)
     gh_plan_graph(h, edges, part != nullptr, sw.reorder ? atoi(sw.reorder) : params->reorder, &g);
@@ -319,7 +313,7 @@ extern "C" gh_status gh_set_positions(gh_handle h, const float *pos) {
     GH_TRY(check_handle(h));
     if (h->f64) return pos ? gh_f64_set_positions_f32(h, pos) : GH_ERR_INVALID;
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
-    h->presetup_valid = false;
+    gh_set_lookahead(h, nullptr);
     GH_HIP(hipMemcpyAsync(h->d_io, pos, sizeof(float) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
     GH_TRY(gh_launch_pad(h, h->d_io, h->d_pos));
     GH_HIP(hipStreamSynchronize(h->stream));  // the host buffer may be released by the caller
@@ -346,8 +340,6 @@ static gh_status check_device_waits(gh_engine *h) {
         GH_HIP(hipMemsetAsync(h->d_wait_failed, 0, sizeof(int32_t), h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
         h->tau_embedded = false;
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }   // captured with the other form
-        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
         h->err = "a workgroup of the fused spring+scan launch timed out waiting for the thresholds of its own launch; "
                  "results since the last successful gh_sync / gh_get_positions are invalid -- set the positions again. "
                  "The engine now computes the thresholds in a launch of their own (as GRAPHEM_HIP_TAU_SEPARATE=1 does); "
@@ -401,29 +393,19 @@ static gh_status check_k(gh_engine *h) {
     return GH_OK;
 }
 
-// Chooses this iteration's sample ids: caller's ids, arange (S >= E, pt.py:412) or the sampler.
-static gh_status set_sample(gh_engine *h, const int32_t *host_ids, const int32_t *dev_ids) {
-    h->sample_pending = false;
-    if (h->S >= h->E) {  // no randomness consumed
-        h->d_sampled_cur = h->d_sampled;
-        h->sample_pending = true;  // produced inside the KNN setup kernel (or by gh_ensure_sample)
-        h->sample_mode = 2;
-        return GH_OK;
-    }
-    if (dev_ids) { h->d_sampled_cur = const_cast<int32_t *>(dev_ids); return GH_OK; }
-    h->d_sampled_cur = h->d_sampled;
-    if (host_ids) {
-        for (int64_t i = 0; i < h->S; ++i)
-            if (host_ids[i] < 0 || host_ids[i] >= h->E) { h->err = "sampled edge id out of range"; return GH_ERR_INVALID; }
-        // a set-up done ahead (inside the last normalise launch) left ITS ids in d_sampled and built the query
-        // records from them: overwriting the ids makes it stale
-        h->presetup_valid = false;
-        GH_HIP(hipMemcpyAsync(h->d_sampled, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
-        GH_HIP(hipStreamSynchronize(h->stream));
-        return GH_OK;
-    }
-    h->sample_pending = true;
-    h->sample_mode = 1;
+// The source of an iteration's ids given the caller's (validated, uploaded to d_sampled), or the engine's own when
+// there are none or S >= E (the reference uses arange, pt.py:412).
+static gh_status caller_ids(gh_engine *h, const int32_t *host_ids, gh_ids *src) {
+    *src = gh_own_ids(h);
+    if (!host_ids || src->mode == GH_IDS_ARANGE) return GH_OK;
+    for (int64_t i = 0; i < h->S; ++i)
+        if (host_ids[i] < 0 || host_ids[i] >= h->E) { h->err = "sampled edge id out of range"; return GH_ERR_INVALID; }
+    // a set-up done ahead (inside the last normalise launch) left ITS ids in d_sampled and built the query
+    // records from them: overwriting the ids makes it stale
+    gh_set_lookahead(h, nullptr);
+    GH_HIP(hipMemcpyAsync(h->d_sampled, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
+    *src = gh_ids{GH_IDS_GIVEN, h->d_sampled};
     return GH_OK;
 }
 
@@ -446,7 +428,7 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
     h->stats_reduced = false;
     h->new0_ready = false;
     if (h->S == 0 || h->k == 0) {  // nothing sampled / no neighbours asked for: spring forces only
-        h->sample_pending = false;
+        h->sample.mode = GH_IDS_GIVEN;
         h->intersect_done = true;
         GH_HIP(hipMemsetAsync(h->d_tcount, 0, sizeof(int32_t), h->stream));
         return gh_launch_spring_mid(h);
@@ -480,117 +462,71 @@ static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world) {
     return GH_OK;
 }
 
-// next_mode < 0: plain finish.  Otherwise the normalise launch of a single-rank step on the fused path
-// also runs the next iteration's KNN set-up, for the sample source expected then (gh_launch_normalise);
-// gh_knn_prepare falls back to its own kernel when the next step turns out different.
-static gh_status step_finish(gh_engine *h, int next_mode = -1, int32_t *next_ids = nullptr) {
-    const bool presetup = next_mode >= 0 && h->rows == h->n && !h->d_gbuf && gh_knn_scan_path(h) &&
+// next: the source of the next iteration's ids, or null.  The normalise launch of a single-rank step on the fused path
+// then also runs that iteration's KNN set-up (gh_launch_normalise); gh_knn_prepare falls back to its own kernel when the
+// next step turns out different.
+static gh_status step_finish(gh_engine *h, const gh_ids *next) {
+    const bool presetup = next && h->rows == h->n && !h->d_gbuf && gh_knn_scan_path(h) &&
                           (h->fused_scan || gh_grid_path(h) || gh_ivf_path(h)) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
-    GH_TRY(gh_launch_normalise(h, true, presetup, next_mode, next_ids));  // also zeroes what the intersection phase touched
+    GH_TRY(gh_launch_normalise(h, true, presetup ? next : nullptr));  // also zeroes what the intersection phase touched
     h->iter += 1;
     return GH_OK;
 }
+
+// The iteration driver of gh_step, gh_run and gh_run_torch_sampled: iteration t takes its ids from src_of_row(t), after
+// before_row(t).  Its normalise launch sets up the next iteration: row t + 1; after the last row, the engine's own draw
+// when the run draws its own ids (a caller that gave ids will give them again), else nothing.
+template <class Src, class Before>
+static gh_status run_iterations(gh_engine *h, int32_t iters, bool draws_own, Src src_of_row, Before before_row) {
+    const gh_ids own = gh_own_ids(h);
+    auto loop = [&]() -> gh_status {
+        for (int32_t t = 0; t < iters; ++t) {
+            GH_TRY(before_row(t));
+            h->sample = src_of_row(t);
+            GH_TRY(step_begin(h, true));
+            GH_TRY(step_merge(h, h->d_partial, 1));
+            const gh_ids next = t + 1 < iters ? src_of_row(t + 1) : own;
+            GH_TRY(step_finish(h, t + 1 < iters || draws_own ? &next : nullptr));
+        }
+        return GH_OK;
+    };
+    const gh_status st = loop();
+    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled};   // (not a row of d_stream_ids, which a later run may replace)
+    return st;
+}
+static gh_status nothing_before(int32_t) { return GH_OK; }
 
 extern "C" gh_status gh_step(gh_handle h, const int32_t *sampled) {
     GH_TRY(check_handle(h));
     if (h->f64) return gh_f64_step(h, sampled);
     GH_TRY(check_whole(h, "gh_step"));
     GH_TRY(check_k(h));
-    GH_TRY(set_sample(h, sampled, nullptr));
-    GH_TRY(step_begin(h, true));
-    GH_TRY(step_merge(h, h->d_partial, 1));
-    // a caller that drew this step's ids itself will do so again; otherwise prepare the next step's own draw
-    return step_finish(h, sampled ? -1 : (h->S >= h->E ? 2 : 1));
+    gh_ids src;
+    GH_TRY(caller_ids(h, sampled, &src));
+    return run_iterations(h, 1, sampled == nullptr, [&](int32_t) { return src; }, nothing_before);
+}
+
+// d_stream_ids with room for `words` ids (a smaller buffer is released once the stream has drained).
+static gh_status ensure_stream_ids(gh_engine *h, size_t words) {
+    if (words <= h->stream_ids_cap) return GH_OK;
+    if (h->d_stream_ids) { GH_HIP(hipStreamSynchronize(h->stream)); GH_HIP(hipFree(h->d_stream_ids)); h->d_stream_ids = nullptr; h->stream_ids_cap = 0; }
+    GH_TRY(dev_alloc(h, &h->d_stream_ids, words, false));
+    h->stream_ids_cap = words;
+    return GH_OK;
 }
 
 // Uploads an (iters, S) host id stream for a run (validated); *d_ids = nullptr when the run draws its own ids
 // (no stream given, or S >= E where the reference uses arange, pt.py:412).
-gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, const int32_t **d_ids) {
+gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, int32_t **d_ids) {
     *d_ids = nullptr;
     if (!sample_stream || h->S >= h->E || iters <= 0) return GH_OK;
     const size_t cnt = (size_t)iters * (size_t)h->S;
     for (size_t i = 0; i < cnt; ++i)
         if (sample_stream[i] < 0 || sample_stream[i] >= h->E) { h->err = "sampled edge id out of range"; return GH_ERR_INVALID; }
-    if (cnt > h->stream_ids_cap) {
-        if (h->d_stream_ids) { GH_HIP(hipStreamSynchronize(h->stream)); GH_HIP(hipFree(h->d_stream_ids)); h->d_stream_ids = nullptr; }
-        GH_TRY(dev_alloc(h, &h->d_stream_ids, cnt, false));
-        h->stream_ids_cap = cnt;
-    }
+    GH_TRY(ensure_stream_ids(h, cnt));
     GH_HIP(hipMemcpyAsync(h->d_stream_ids, sample_stream, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     *d_ids = h->d_stream_ids;
-    return GH_OK;
-}
-
-// One iteration of a device-sampled run as the host enqueues it (set-up of the next iteration inside its normalise launch).
-static gh_status run_one_device_sampled(gh_engine *h) {
-    GH_TRY(set_sample(h, nullptr, nullptr));
-    GH_TRY(step_begin(h, true));
-    GH_TRY(step_merge(h, h->d_partial, 1));
-    return step_finish(h, h->S >= h->E ? 2 : 1);
-}
-
-// Iterations 2.. of a device-sampled run replayed from a hipGraph (OPT-IN: GRAPHEM_HIP_GRAPH=1).  In steady state an
-// iteration is the same four or five launches with the same arguments, except for the iteration number the sampler is
-// keyed with -- that lives in device memory while replaying (d_iter: moved on by stats_fix_kernel, read by the set-up
-// inside the following normalise launch).  Measured (round 3, bench.py, median of 3 passes of 50 iterations, same box):
-// one iteration per graph 172.2 us against 166.3 enqueued at 1 M vertices, 62.3 / 57.3 at 100 K, 121.8 / 117.3 on the
-// 16-component SNAP shape; ten iterations per graph 170.1 / 167.9, 58.6 / 57.6, 117.8 / 117.7 -- a graph launch costs
-// more than it saves on this runtime (the 1.9 - 2.8 us per replayed boundary of tools/micro/grid_barrier.hip did not
-// carry over to kernels with 200-byte argument blocks), so the enqueued loop stays the default.
-static bool graph_replay_applies(gh_engine *h) {
-    // the fused path, or the inverted-file path (its ~18 launches and memsets per iteration: the device counter is moved on
-    // by stats_reduce_kernel there)
-    const bool path = gh_ivf_path(h) || (h->fused_scan && !gh_grid_path(h));
-    return whole_graph(h) && !h->d_gbuf && !h->g_world && !h->cdist && !h->timing && !h->d_stamps && path &&
-           gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && h->K <= 128 && h->LD <= 16 &&
-           h->opt_graph && !h->opt_no_presetup;
-}
-static int graph_iters() { return 10; }   // iterations per captured graph (a graph launch has a cost of its own: one iteration per
-                                          // graph was SLOWER than enqueuing, 172.2 against 166.3 us per iteration at 1 M vertices)
-// Replays as many whole graphs (graph_iters() iterations each) as fit into `count`; *done = iterations replayed.
-static gh_status graph_replay(gh_engine *h, int32_t count, int32_t *done) {
-    *done = 0;
-    const int G = graph_iters();
-    if (count < G) return GH_OK;
-    if (!h->graph_exec) {
-        // captured from the steady state: the previous launch has done this iteration's set-up (presetup_valid)
-        if (!h->presetup_valid || h->presetup_iter != h->iter) { h->err = "graph replay: not in the steady state (enqueuing instead)"; return GH_ERR_RUNTIME; }   // (caller falls back to enqueuing)
-        const bool pv = h->presetup_valid, trp = h->tcount_reset_pending;
-        const int pm = h->presetup_mode;
-        const int32_t *pi = h->presetup_ids;
-        const uint64_t it0 = h->iter, pit = h->presetup_iter;
-        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); h->err = "graph replay: hipStreamBeginCapture failed (enqueuing instead)"; return GH_ERR_RUNTIME; }
-        h->graph_capturing = true;
-        gh_status st = GH_OK;
-        for (int g = 0; g < G && st == GH_OK; ++g) st = run_one_device_sampled(h);   // (iteration numbers: offsets to the device counter)
-        h->graph_capturing = false;
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(h->stream, &g);
-        // nothing ran: the host-side state goes back to where the captured iterations started
-        h->iter = it0; h->presetup_valid = pv; h->presetup_mode = pm; h->presetup_ids = pi; h->presetup_iter = pit;
-        h->tcount_reset_pending = trp;
-        h->new0_ready = false; h->stats_reduced = false; h->intersect_done = false; h->sample_pending = false;
-        if (st != GH_OK || e != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); if (st == GH_OK) h->err = "graph replay: capture failed (enqueuing instead)"; return GH_ERR_RUNTIME; }
-        if (hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGraphDestroy(g); (void)hipGetLastError(); h->graph_exec = nullptr;
-            h->err = "graph replay: hipGraphInstantiate failed (enqueuing instead)";
-            return GH_ERR_RUNTIME;
-        }
-        if (h->graph) (void)hipGraphDestroy(h->graph);   // (a previous capture whose executable was dropped)
-        h->graph = g;
-    }
-    GH_HIP(hipMemcpyAsync(h->d_iter, &h->iter, sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-    GH_HIP(hipStreamSynchronize(h->stream));   // (the source is a member of *h: the copy must not outlive this call's view of it)
-    const int32_t launches = count / G;
-    for (int32_t t = 0; t < launches; ++t) GH_HIP(hipGraphLaunch(h->graph_exec, h->stream));
-    *done = launches * G;
-    h->iter += (uint64_t)*done;
-    h->presetup_valid = true;          // the last replayed normalise launch set the next iteration up
-    h->presetup_iter = h->iter;
-    h->presetup_mode = h->S >= h->E ? 2 : 1;
-    h->presetup_ids = h->d_sampled;
-    h->tcount_reset_pending = false;
     return GH_OK;
 }
 
@@ -601,27 +537,11 @@ extern "C" gh_status gh_run(gh_handle h, int32_t iters, const int32_t *sample_st
     if (iters == 0) return GH_OK;
     GH_TRY(check_whole(h, "gh_run"));
     GH_TRY(check_k(h));
-    const int32_t *d_ids = nullptr;
+    int32_t *d_ids = nullptr;
     GH_TRY(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));
-    const bool use_stream = d_ids != nullptr;
-    int32_t t = 0;
-    if (!use_stream && iters > graph_iters() && graph_replay_applies(h)) {
-        GH_TRY(run_one_device_sampled(h));   // into the steady state (the set-up of iteration 2 rides in this one's normalise launch)
-        t = 1;
-        int32_t done = 0;
-        if (graph_replay(h, iters - 1, &done) == GH_OK) t += done;   // whole graphs; what is left is enqueued below
-    }
-    for (; t < iters; ++t) {
-        GH_TRY(set_sample(h, nullptr, use_stream ? h->d_stream_ids + (size_t)t * h->S : nullptr));
-        GH_TRY(step_begin(h, true));
-        GH_TRY(step_merge(h, h->d_partial, 1));
-        const bool more = t + 1 < iters;
-        if (h->S >= h->E) GH_TRY(step_finish(h, 2));
-        else if (use_stream && more) GH_TRY(step_finish(h, 0, h->d_stream_ids + (size_t)(t + 1) * h->S));
-        else GH_TRY(step_finish(h, use_stream ? -1 : 1));  // after the last id row: nothing to prepare
-    }
-    h->d_sampled_cur = h->d_sampled;
-    return GH_OK;
+    const gh_ids own = gh_own_ids(h);
+    auto src = [&](int32_t t) { return d_ids ? gh_ids{GH_IDS_GIVEN, d_ids + (size_t)t * h->S} : own; };
+    return run_iterations(h, iters, d_ids == nullptr, src, nothing_before);
 }
 
 extern "C" gh_status gh_set_cdist_replay(gh_handle h, int32_t all_ties) {
@@ -681,14 +601,11 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
         if (h->h_ring) { (void)hipHostFree(h->h_ring); h->h_ring = nullptr; h->ring_cap = 0; }
         GH_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->h_ring), ring_words * sizeof(int32_t), hipHostMallocDefault));
         h->ring_cap = ring_words;
+        h->ring_uploads = 0;   // (no copy out of the old slots is pending: the stream has drained)
         for (hipEvent_t &e : h->ring_ev)
             if (!e) GH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    if ((size_t)GH_DEV_RING * S > h->stream_ids_cap) {
-        if (h->d_stream_ids) { GH_HIP(hipStreamSynchronize(h->stream)); GH_HIP(hipFree(h->d_stream_ids)); h->d_stream_ids = nullptr; h->stream_ids_cap = 0; }
-        GH_TRY(dev_alloc(h, &h->d_stream_ids, (size_t)GH_DEV_RING * S, false));
-        h->stream_ids_cap = (size_t)GH_DEV_RING * S;
-    }
+    GH_TRY(ensure_stream_ids(h, (size_t)GH_DEV_RING * S));
 
     std::vector<int32_t> hbuf((size_t)GH_HOST_RING * S);
     std::mutex mu;
@@ -719,7 +636,7 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
             cv.notify_all();
         }
     });
-    int32_t uploaded = 0, uploads = 0;
+    int32_t uploaded = 0;
     // rows [uploaded, uploaded + m) -> device ring; m >= 1 once row `need` is drawn
     auto upload_through = [&](int32_t need) -> gh_status {
         while (uploaded <= need) {
@@ -734,8 +651,9 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
             int32_t m = std::min<int32_t>(have - uploaded, GH_RING_CHUNK);
             m = std::min<int32_t>(m, GH_DEV_RING - uploaded % GH_DEV_RING);     // neither ring wraps inside one copy
             m = std::min<int32_t>(m, GH_HOST_RING - uploaded % GH_HOST_RING);
-            const int slot = uploads % GH_RING_SLOTS;
-            if (uploads >= GH_RING_SLOTS) {
+            // a slot is reused once its last copy has run -- also one enqueued by an earlier call, which returns undrained
+            const int slot = (int)(h->ring_uploads % GH_RING_SLOTS);
+            if (h->ring_uploads >= GH_RING_SLOTS) {
                 const clk::time_point t0 = clk::now();
                 GH_HIP(hipEventSynchronize(h->ring_ev[slot]));
                 slot_wait_ms += ms_since(t0);
@@ -745,7 +663,7 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
             GH_HIP(hipMemcpyAsync(h->d_stream_ids + (size_t)(uploaded % GH_DEV_RING) * S, pin, sizeof(int32_t) * (size_t)m * S, hipMemcpyHostToDevice, h->stream));
             GH_HIP(hipEventRecord(h->ring_ev[slot], h->stream));
             uploaded += m;
-            ++uploads;
+            ++h->ring_uploads;
             {
                 std::lock_guard<std::mutex> lk(mu);
                 taken = uploaded;
@@ -754,26 +672,16 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
         }
         return GH_OK;
     };
-    auto row = [&](int32_t t) { return h->d_stream_ids + (size_t)(t % GH_DEV_RING) * S; };
-    auto loop = [&]() -> gh_status {
-        for (int32_t t = 0; t < iters; ++t) {
-            GH_TRY(upload_through(std::min(t + 1, iters - 1)));   // this iteration's ids, and the next one's for its normalise launch
-            GH_TRY(set_sample(h, nullptr, row(t)));
-            GH_TRY(step_begin(h, true));
-            GH_TRY(step_merge(h, h->d_partial, 1));
-            if (t + 1 < iters) GH_TRY(step_finish(h, 0, row(t + 1)));
-            else GH_TRY(step_finish(h, -1));
-        }
-        return GH_OK;
-    };
-    const gh_status st = loop();
+    auto row = [&](int32_t t) { return gh_ids{GH_IDS_GIVEN, h->d_stream_ids + (size_t)(t % GH_DEV_RING) * S}; };
+    // this iteration's ids, and the next one's for its normalise launch
+    auto upload = [&](int32_t t) { return upload_through(std::min(t + 1, iters - 1)); };
+    const gh_status st = run_iterations(h, iters, false, row, upload);
     {
         std::lock_guard<std::mutex> lk(mu);
         stop = st != GH_OK;
     }
     cv.notify_all();
     producer.join();
-    h->d_sampled_cur = h->d_sampled;
     h->sampler_stats[0] = draw_ms; h->sampler_stats[1] = slot_wait_ms; h->sampler_stats[2] = main_wait_ms; h->sampler_stats[3] = ms_since(t_begin);
     if (st != GH_OK) return st;
     gh_mt_store(&mt, rng_state);
@@ -800,15 +708,15 @@ extern "C" gh_status gh_step_begin(gh_handle h, const int32_t *sampled) {
     GH_TRY(reject_f64(h, "gh_step_begin"));
     GH_TRY(check_k(h));
     h->last_step_own_ids = sampled == nullptr;
-    GH_TRY(set_sample(h, sampled, nullptr));
+    GH_TRY(caller_ids(h, sampled, &h->sample));
     return step_begin(h, false);
 }
 // Part 1 of a split step with the ids already on the device (a row of an uploaded stream), or nullptr: the
 // engine draws them itself, identically on every rank (comm.hip gh_run_partitioned).
-gh_status gh_step_begin_device_ids(gh_engine *h, const int32_t *dev_ids) {
+gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids) {
     GH_TRY(check_k(h));
     h->last_step_own_ids = dev_ids == nullptr;
-    GH_TRY(set_sample(h, nullptr, dev_ids));
+    h->sample = dev_ids ? gh_ids{GH_IDS_GIVEN, dev_ids} : gh_own_ids(h);   // (gh_upload_sample_stream gives none when S >= E)
     return step_begin(h, false);
 }
 extern "C" gh_status gh_set_stream(gh_handle h, void *hip_stream, int32_t use_own) {
@@ -834,7 +742,7 @@ extern "C" int32_t gh_stats_rows(gh_handle h) { return h ? 2 + 2 * gh_fix_blocks
 extern "C" gh_status gh_step_finish(gh_handle h) {
     GH_TRY(check_handle(h));
     GH_TRY(reject_f64(h, "gh_step_finish"));
-    return step_finish(h);
+    return step_finish(h, nullptr);
 }
 
 // Checks of the layout calls (name: the call, what: its layout in the message): world blocks of chunk rows, block `rank`
@@ -913,7 +821,8 @@ extern "C" gh_status gh_step_finish_overlap(gh_handle h) {
     GH_TRY(check_handle(h));
     if (!h->overlap) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
     GH_TRY(gh_launch_patch_rows(h));
-    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? (h->S >= h->E ? 2 : 1) : -1));
+    const gh_ids own = gh_own_ids(h);
+    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? &own : nullptr));
     h->rows_early = false;
     h->iter += 1;
     return GH_OK;
@@ -946,7 +855,8 @@ extern "C" gh_status gh_step_finish_gathered(gh_handle h) {
     GH_TRY(check_handle(h));
     if (!h->d_gbuf) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
     // a rank that drew this step's ids on the device will do so again: prepare them in the same launch
-    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? (h->S >= h->E ? 2 : 1) : -1));
+    const gh_ids own = gh_own_ids(h);
+    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? &own : nullptr));
     h->iter += 1;
     return GH_OK;
 }
@@ -990,7 +900,7 @@ extern "C" gh_status gh_knn_midpoints(gh_handle h, const int32_t *sampled, int32
     GH_TRY(check_whole(h, "gh_knn_midpoints"));
     GH_TRY(check_k(h));
     if (!sampled && h->S < h->E) { h->err = "sampled is NULL"; return GH_ERR_INVALID; }
-    GH_TRY(set_sample(h, sampled, nullptr));
+    GH_TRY(caller_ids(h, sampled, &h->sample));
     GH_TRY(step_begin(h, false));  // the same kernels a step runs (spring forces are a by-product)
     const uint64_t *d_keys = h->d_partial;
     if (h->cd_part) {   // a GH_DIST_CDIST engine created with a (whole-graph) partition: its rows are decided at the merge
@@ -1015,7 +925,7 @@ extern "C" gh_status gh_intersection_forces(gh_handle h, const int32_t *sampled,
     if (!sampled && h->S < h->E) { h->err = "sampled is NULL"; return GH_ERR_INVALID; }
     for (int64_t i = 0; i < h->S * h->k; ++i)
         if (knn[i] < 0 || knn[i] >= h->E) { h->err = "neighbour edge id out of range"; return GH_ERR_INVALID; }
-    GH_TRY(set_sample(h, sampled, nullptr));
+    GH_TRY(caller_ids(h, sampled, &h->sample));
     GH_TRY(gh_ensure_sample(h));
     std::vector<uint64_t> keys((size_t)h->S * h->K, 0);  // the kernel reads ids from key columns 1..k
     for (int64_t s = 0; s < h->S; ++s)

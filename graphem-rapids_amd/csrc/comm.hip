@@ -257,7 +257,7 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
     if (iters < 0) { h->err = "negative iteration count"; return GH_ERR_INVALID; }
     gh_comm *c = h->comm;
     const size_t key_bytes = sizeof(uint64_t) * (size_t)h->S * (h->K + (h->cd_part ? 2 : 0));   // (a GH_DIST_CDIST partition sends K + 1 keys and a flag)
-    const int32_t *d_ids = nullptr;
+    int32_t *d_ids = nullptr;
     GH_TRY_ST(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));   // nullptr: device sampler / arange on every rank
     // a rank that fails leaves the loop: the loopback group must not wait for it (RCCL has its own abort paths)
     auto run = [&]() -> gh_status {

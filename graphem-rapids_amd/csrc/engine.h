@@ -28,6 +28,13 @@ struct gh_timer_slot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// Where the sample ids of an iteration come from.  The values are gh_setup_args::mode on the device (setup_core.h).
+enum { GH_IDS_GIVEN = 0, GH_IDS_SAMPLER = 1, GH_IDS_ARANGE = 2 };
+struct gh_ids {
+    int mode;       // GH_IDS_GIVEN: the ids are at `ids`; GH_IDS_SAMPLER / GH_IDS_ARANGE: produced into `ids` (d_sampled)
+    int32_t *ids;   // (mutable: the set-up writes the ids it draws)
+};
+
 struct gh_comm;   // comm.hip: collective backend of the native partitioned loop
 struct gh_f64;    // f64.hip: state of a float64 engine (gh_create_f64)
 struct gh_ivf;    // ivf.hip: buffers of the inverted-file search (GH_KNN_IVF)
@@ -79,7 +86,7 @@ struct gh_engine {
     int64_t thr_stride = 0, thr_M1 = 0;  // the subset: every thr_stride-th own edge, thr_M1 of them (gh_choose_threshold_subset)
     int32_t *d_vblock = nullptr;  // (n_vblocks + 1) vertex ranges of the fused spring+scan workgroups
     int n_vblocks = 0;
-    bool opt_no_presetup = false, opt_graph = false;   // GRAPHEM_HIP_NO_PRESETUP / GRAPHEM_HIP_GRAPH (read at gh_create)
+    bool opt_no_presetup = false; // GRAPHEM_HIP_NO_PRESETUP (read at gh_create)
     bool fused_scan = false;      // fused spring+scan kernel usable for this graph / partition
 
     // state
@@ -97,7 +104,8 @@ struct gh_engine {
 
     // knn
     int32_t *d_sampled = nullptr; // (S) owned buffer
-    int32_t *d_sampled_cur = nullptr; // ids of the current iteration (d_sampled or a row of d_stream_ids)
+    gh_ids sample{};                  // ids of the current iteration: d_sampled or a row of d_stream_ids, GH_IDS_GIVEN once
+                                      // produced (the sampler / arange run inside knn_setup_kernel or by gh_ensure_sample)
     int32_t *d_stream_ids = nullptr;  // (iters, S) uploaded sample stream of gh_run
     size_t stream_ids_cap = 0;
     // gh_run_torch_sampled (api.hip): pinned upload slots for the rows a host thread draws (torch.randperm's prefixes), one
@@ -106,19 +114,19 @@ struct gh_engine {
 #define GH_RING_CHUNK 32   /* rows per slot = per copy, at most */
     int32_t *h_ring = nullptr;
     size_t ring_cap = 0;              // int32 words allocated in h_ring (GH_RING_SLOTS * GH_RING_CHUNK * S)
+    uint64_t ring_uploads = 0;        // copies out of h_ring so far, over all calls: slot = ring_uploads % GH_RING_SLOTS
     hipEvent_t ring_ev[GH_RING_SLOTS] = {};
     double sampler_stats[4] = {0, 0, 0, 0};   // last gh_run_torch_sampled, host ms: producer drawing, caller waiting for a pinned slot, caller waiting for ids, the call
     bool new0_ready = false;      // the fused kernel of this step wrote d_new = pos + Fs and its block sums
     bool intersect_done = false;  // the KNN kernels of this step already ran the intersection phase
     bool stats_reduced = false;   // ... and reduced the fused kernel's workgroup sums into d_stats (knn_select_kernel)
-    bool presetup_valid = false;  // the last normalise launch also ran the KNN set-up of iteration presetup_iter
-    int presetup_mode = 0;        //   with this sample mode / id pointer (gh_knn_prepare then skips its kernel)
-    const int32_t *presetup_ids = nullptr;
-    uint64_t presetup_iter = 0;
+    struct {
+        bool valid = false;       // the last normalise launch also ran the KNN set-up of iteration `iter` from `src`
+        gh_ids src{};             //   (gh_knn_prepare then skips its kernel); written by gh_set_lookahead only
+        uint64_t iter = 0;
+    } lookahead;
     bool last_step_own_ids = false;     // gh_step_begin was called without ids (device sampler / arange)
     bool tcount_reset_pending = false;  // this step's threshold kernel must reset d_tcount
-    bool sample_pending = false;  // ids of this iteration still to be produced (inside knn_setup_kernel)
-    int sample_mode = 0;          // 1 device sampler, 2 arange
     float *d_iscratch = nullptr;  // (S * k, LD) per-pair scratch of the intersection kernel
     float *d_q = nullptr;         // (S, QS) query records: midpoint coordinates + tau (knn.hip gh_qs)
     float *d_qscan = nullptr;     // (S, QS) pre-filter records (-2q, t) written by the threshold kernel
@@ -188,11 +196,6 @@ struct gh_engine {
     // thresholds inside the fused launch (tau_core.h)
     bool tau_embedded = false;
     unsigned *d_tau_flag = nullptr;      // queries published so far by the current fused launch
-    // iterations replayed from a hipGraph (api.hip gh_run): one captured iteration, the iteration number on the device
-    uint64_t *d_iter = nullptr;
-    bool graph_capturing = false;
-    hipGraphExec_t graph_exec = nullptr;
-    hipGraph_t graph = nullptr;
     int32_t *d_wait_failed = nullptr;    // a consumer gave up waiting: reported by gh_sync / gh_get_positions
 
 #define GH_STAMP_EXTRA 8192
@@ -200,6 +203,15 @@ struct gh_engine {
     bool timing = false;
     std::vector<gh_timer_slot> timers;
 };
+
+// The engine's own ids for an iteration: arange(E) when S >= E (pt.py:412, no randomness consumed: SURVEY Q9), else the
+// device sampler.
+inline gh_ids gh_own_ids(const gh_engine *h) { return gh_ids{h->S >= h->E ? GH_IDS_ARANGE : GH_IDS_SAMPLER, h->d_sampled}; }
+// The normalise launch just enqueued also set up iteration iter + 1 from *next; null: nothing is set up ahead (any more).
+inline void gh_set_lookahead(gh_engine *h, const gh_ids *next) {
+    h->lookahead.valid = next != nullptr;
+    if (next) { h->lookahead.src = *next; h->lookahead.iter = h->iter + 1; }
+}
 
 // RAII-free helper: records start/stop events around a launch when timing is on.
 struct gh_scope {
@@ -233,8 +245,8 @@ extern "C" float *gh_rows_all_device(gh_handle h);
 extern "C" int32_t gh_rows_all_row_floats(gh_handle h);
 extern "C" int32_t gh_step_rows_early(gh_handle h);
 extern "C" gh_status gh_step_finish_overlap(gh_handle h);
-gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, const int32_t **d_ids);
-gh_status gh_step_begin_device_ids(gh_engine *h, const int32_t *dev_ids);
+gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, int32_t **d_ids);
+gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids);
 void gh_comm_free(gh_engine *h);
 // f64.hip
 void gh_set_create_error(const std::string &msg);   // (api.hip) message gh_last_error(NULL) returns
@@ -252,7 +264,7 @@ gh_status gh_knn_local(gh_engine *h, bool fuse_intersect);  // d_sampled, d_mid 
 bool gh_knn_scan_path(const gh_engine *h);
 struct gh_setup_args;
 void gh_choose_threshold_subset(gh_engine *h);   // thr_stride, thr_M1: once knn_method, own_count, fused_scan, Ksel and S are final
-gh_setup_args gh_make_setup_args(const gh_engine *h, int mode, int32_t *sampled, uint64_t iter);  // setup_core.h
+gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter);  // setup_core.h
 unsigned gh_setup_blocks(const gh_setup_args &a);
 int64_t gh_gmin_floats(const gh_engine *h);   // size of d_gmin
 gh_status gh_knn_prepare(gh_engine *h);
@@ -291,9 +303,9 @@ gh_status gh_launch_integrate(gh_engine *h);               // d_Fs, d_acc -> d_n
 gh_status gh_launch_spring_only(gh_engine *h, float *d_F); // F (n, LD), own rows
 gh_status gh_launch_inter_to_dense(gh_engine *h, float *d_F);
 gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float *d_Fi);
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, bool presetup = false, int next_mode = 0,
-                              int32_t *next_ids = nullptr);
-gh_status gh_launch_normalise_gathered(gh_engine *h, int next_mode = -1);
+// next: also the KNN set-up of the next iteration from these ids, in the same launch (null: none)
+gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next = nullptr);
+gh_status gh_launch_normalise_gathered(gh_engine *h, const gh_ids *next);
 gh_status gh_launch_normalise_own(gh_engine *h, const double *stats_all, int world);   // form C: own rows from every rank's statistics
 gh_status gh_launch_unpack_rows(gh_engine *h);   // form C: the gathered packed blocks of the OTHER ranks -> their rows of d_pos
 struct gh_long_args;

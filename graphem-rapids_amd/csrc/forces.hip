@@ -262,9 +262,7 @@ __global__ __launch_bounds__(256) void column_stats_kernel(const float *__restri
 
 // Fixed-order reduction of the per-workgroup partials -> (2, LD) sums.
 __global__ __launch_bounds__(256) void stats_reduce_kernel(const double *__restrict__ blockstats, int nblocks, int LD,
-                                                          double *__restrict__ stats,
-                                                          uint64_t *__restrict__ iter_bump = nullptr /* replayed iterations on the unfused paths: the device's iteration counter (stats_fix_kernel moves it on the fused path) */) {
-    if (iter_bump && blockIdx.x == 0 && threadIdx.x == 0) *iter_bump += 1;
+                                                          double *__restrict__ stats) {
     const int c = blockIdx.x;  // column of the (2*LD) record
     double s = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += blockstats[(int64_t)c * nblocks + b];
@@ -290,13 +288,11 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const double *__restrict
                                                        const int32_t *__restrict__ tcount, int64_t row_lo,
                                                        int64_t rows, float *__restrict__ out_new,
                                                        double *__restrict__ stats, int skip_reduce,
-                                                       uint64_t *__restrict__ iter_bump /* replayed iterations: the device's iteration counter, or null */,
                                                        int32_t *__restrict__ patch_count = nullptr /* form D of a partitioned step
                                                        (gh_overlap_layout): new0 is already travelling to the other ranks; the corrected
                                                        rows go into the rank's patch list instead of out_new */,
                                                        float *__restrict__ patch_rows = nullptr, int patch_cap = 0) {
     __shared__ double red[4][2 * LD];
-    if (iter_bump && blockIdx.x == 0 && threadIdx.x == 0) *iter_bump += 1;   // read by the set-up inside the NEXT launch (normalise)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (!skip_reduce) {  // (the select launch of a single-rank step has done this part already)
         const int c = blockIdx.x;  // gridDim.x == 2 * LD
@@ -919,7 +915,7 @@ gh_status gh_launch_integrate(gh_engine *h) {
 #define GH_FIX_CASE(LL)                                                                                      \
     stats_fix_kernel<LL><<<dim3(gh_fix_blocks(LL)), dim3(256), 0, h->stream>>>(                                  \
         h->d_blockstats, h->n_vblocks, h->d_pos, h->d_Fs, h->d_acc, h->d_touched, h->d_tcount, h->part.row_lo, \
-        h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->graph_capturing ? h->d_iter : nullptr, h->overlap ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
+        h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->overlap ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
         h->overlap ? gh_patch_records(h) : nullptr, (int)h->patch_cap)
         if (h->LD == 4) GH_FIX_CASE(4);
         else if (h->LD == 8) GH_FIX_CASE(8);
@@ -966,7 +962,7 @@ gh_status gh_launch_integrate(gh_engine *h) {
     gh_scope t(h, "stats_reduce");
     if (h->LD <= 16) {
         stats_reduce_kernel<<<dim3(2 * h->LD), dim3(256), 0, h->stream>>>(h->d_blockstats, h->nblocks_update, h->LD,
-                                                                          h->d_stats, h->graph_capturing ? h->d_iter : nullptr);
+                                                                          h->d_stats);
     } else {
         column_stats_kernel<<<dim3(h->D), dim3(256), 0, h->stream>>>(wide_out, h->rows, h->D, h->LD, h->d_stats);
     }
@@ -991,14 +987,14 @@ gh_status gh_launch_intersect(gh_engine *h) {
 #define GH_INTER_ONE(DD, LL)                                                                                       \
     case DD:                                                                                                       \
         intersect_kernel<DD><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(                                   \
-            h->d_pos, h->D, h->LD, h->d_edges, h->d_sampled_cur, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc, \
+            h->d_pos, h->D, h->LD, h->d_edges, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc, \
             h->d_tflag, h->d_touched, h->d_tcount, h->d_iscratch, own_lo, own_hi);                                 \
         break;
     switch (h->D) {
         GH_FOR_EACH_DIM(GH_INTER_ONE)
         default:
             intersect_kernel<0><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(
-                h->d_pos, h->D, h->LD, h->d_edges, h->d_sampled_cur, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc,
+                h->d_pos, h->D, h->LD, h->d_edges, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc,
                 h->d_tflag, h->d_touched, h->d_tcount, h->d_iscratch, own_lo, own_hi);
     }
 #undef GH_INTER_ONE
@@ -1038,10 +1034,10 @@ gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float
     return GH_OK;
 }
 
-// presetup: also run the next iteration's KNN set-up in this launch (single-rank fused steps), for the
-// sample source the caller expects then: mode 0 = the ids at next_ids, 1 = device sampler, 2 = arange.
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, bool presetup, int next_mode, int32_t *next_ids) {
-    h->presetup_valid = false;  // positions change: whatever set-up was done ahead is stale
+// next: also run the next iteration's KNN set-up in this launch (single-rank fused steps), for the sample source the
+// caller expects then.
+gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next) {
+    gh_set_lookahead(h, nullptr);  // positions change: whatever set-up was done ahead is stale
     if (h->rows == 0) return with_cleanup ? gh_launch_inter_cleanup(h) : GH_OK;
     gh_scope t(h, "normalise");
     const int64_t total = h->rows * h->LD / 4;  // float4 elements
@@ -1049,8 +1045,8 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, bool presetup, in
     if (grid > 2048) grid = 2048;
     gh_setup_args sa{};
     unsigned extra = 0;
-    if (presetup) {
-        sa = gh_make_setup_args(h, next_mode, next_mode == 0 ? next_ids : h->d_sampled, h->iter + 1);
+    if (next) {
+        sa = gh_make_setup_args(h, *next, h->iter + 1);
         extra = gh_setup_blocks(sa);
     }
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
@@ -1068,12 +1064,7 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, bool presetup, in
     }
 #undef GH_NORM
     GH_LAUNCH_CHECK();
-    if (presetup) {
-        h->presetup_valid = true;
-        h->presetup_mode = next_mode;
-        h->presetup_ids = next_mode == 0 ? next_ids : h->d_sampled;
-        h->presetup_iter = h->iter + 1;
-    }
+    gh_set_lookahead(h, next);
     return GH_OK;
 }
 
@@ -1081,7 +1072,7 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, bool presetup, in
 // intersection phase touched.  No set-up for the next iteration here: the other ranks' rows arrive with the caller's
 // all-gather of the position blocks.
 gh_status gh_launch_normalise_own(gh_engine *h, const double *stats_all, int world) {
-    h->presetup_valid = false;
+    gh_set_lookahead(h, nullptr);
     const int R = 2 + 2 * gh_fix_blocks(h->LD);
     int nfix = gh_fix_blocks(h->LD), sworld = world;
     size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)world * R * h->LD;
@@ -1129,17 +1120,17 @@ gh_status gh_launch_unpack_rows(gh_engine *h) {
     return GH_OK;
 }
 
-// next_mode >= 0: also the next iteration's KNN set-up (as gh_launch_normalise).
-gh_status gh_launch_normalise_gathered(gh_engine *h, int next_mode) {
-    h->presetup_valid = false;
+// next: also the next iteration's KNN set-up (as gh_launch_normalise).
+gh_status gh_launch_normalise_gathered(gh_engine *h, const gh_ids *next) {
+    gh_set_lookahead(h, nullptr);
     gh_scope t(h, "normalise_gathered");
     unsigned grid = grid_for(h->n * h->LD / 4, 256);
     if (grid > 2048) grid = 2048;
-    const bool presetup = next_mode >= 0 && h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
+    const bool presetup = next && h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
     gh_setup_args sa{};
     unsigned extra = 0;
     if (presetup) {
-        sa = gh_make_setup_args(h, next_mode, h->d_sampled, h->iter + 1);
+        sa = gh_make_setup_args(h, *next, h->iter + 1);
         extra = gh_setup_blocks(sa);
     }
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * 2 * h->LD * (size_t)h->g_world;
@@ -1164,12 +1155,7 @@ gh_status gh_launch_normalise_gathered(gh_engine *h, int next_mode) {
     }
 #undef GH_NORMG
     GH_LAUNCH_CHECK();
-    if (presetup) {
-        h->presetup_valid = true;
-        h->presetup_mode = next_mode;
-        h->presetup_ids = h->d_sampled;
-        h->presetup_iter = h->iter + 1;
-    }
+    gh_set_lookahead(h, presetup ? next : nullptr);
     return GH_OK;
 }
 
@@ -1267,9 +1253,10 @@ gh_status gh_launch_arange(gh_engine *h) {
 }
 
 gh_status gh_ensure_sample(gh_engine *h) {
-    if (!h->sample_pending) return GH_OK;
-    h->sample_pending = false;
-    return h->sample_mode == 2 ? gh_launch_arange(h) : gh_launch_sample(h);
+    const int mode = h->sample.mode;
+    h->sample.mode = GH_IDS_GIVEN;
+    if (mode == GH_IDS_GIVEN) return GH_OK;
+    return mode == GH_IDS_ARANGE ? gh_launch_arange(h) : gh_launch_sample(h);
 }
 
 // include/graphem_hip.h: self-test of the lean IEEE square root / division of the spring phase.

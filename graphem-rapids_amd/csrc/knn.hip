@@ -570,14 +570,11 @@ void gh_choose_threshold_subset(gh_engine *h) {
 
 // Sample ids (if still pending), query records, list reset and -- on the scan path -- the compact
 // threshold subset: one launch.
-gh_setup_args gh_make_setup_args(const gh_engine *h, int mode, int32_t *sampled, uint64_t iter) {
+gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter) {
     const int tiles = (int)((h->thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
-    // replayed iterations: the number of the iteration being set up = device counter + (iter - h->iter - 1): the counter
-    // was moved to "this iteration + 1" by stats_fix_kernel before the normalise launch that carries the set-up
-    const bool dev = h->graph_capturing;
-    return gh_setup_args{h->d_edges, sampled, mode, h->E, h->prm.seed, dev ? iter - h->iter - 1 : iter, h->S, h->D, h->LD, h->d_q, h->d_cnt,
+    return gh_setup_args{h->d_edges, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q, h->d_cnt,
                          h->d_ovf, h->part.edge_lo, h->d_own_eids, reinterpret_cast<const int2 *>(h->d_sub_uv), h->thr_M1, h->thr_stride, h->d_gmin,
-                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag : nullptr, dev ? h->d_iter : nullptr};
+                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag : nullptr};
 }
 
 // Workgroups of 256 threads a set-up takes (knn_setup_kernel, or the head of a normalise launch).
@@ -585,22 +582,22 @@ unsigned gh_setup_blocks(const gh_setup_args &a) {
     return a.tiles > 0 ? (unsigned)a.tiles : (unsigned)((a.S + 255) / 256);
 }
 int64_t gh_gmin_floats(const gh_engine *h) {
-    const gh_setup_args a = gh_make_setup_args(h, 0, nullptr, 0);
+    const gh_setup_args a = gh_make_setup_args(h, gh_ids{GH_IDS_GIVEN, nullptr}, 0);
     if (gh_ivf_path(h)) return h->S * 256 + 4;   // GH_IVF_GROUPS minima per query, written by ivf_probe_kernel
     if (a.tiles == 0) return 4;
     return h->S * a.Gpad + 4;
 }
 
 gh_status gh_knn_prepare(gh_engine *h) {
-    const int mode = h->sample_pending ? h->sample_mode : 0;
-    h->sample_pending = false;
+    const gh_ids src = h->sample;
+    h->sample.mode = GH_IDS_GIVEN;   // produced by the set-up, here or done ahead
     // the previous normalise launch may already have done this iteration's set-up (forces.hip)
-    const bool done = h->presetup_valid && h->presetup_mode == mode && h->presetup_iter == h->iter &&
-                      (mode != 0 || h->presetup_ids == h->d_sampled_cur);
-    h->presetup_valid = false;
+    const bool done = h->lookahead.valid && h->lookahead.iter == h->iter && h->lookahead.src.mode == src.mode &&
+                      h->lookahead.src.ids == src.ids;
+    gh_set_lookahead(h, nullptr);
     h->tcount_reset_pending = done;  // the stand-alone kernel resets d_tcount; else the threshold kernel does
     if (done) return GH_OK;
-    const gh_setup_args a = gh_make_setup_args(h, mode, h->d_sampled_cur, h->iter);
+    const gh_setup_args a = gh_make_setup_args(h, src, h->iter);
     gh_scope t(h, "knn_setup");
     knn_setup_kernel<<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos, a, h->d_tcount, h->d_qexact);
     GH_LAUNCH_CHECK();
@@ -609,7 +606,7 @@ gh_status gh_knn_prepare(gh_engine *h) {
 
 // Arguments of the threshold computation (tau_core.h) for this iteration.
 gh_tau_args gh_make_tau_args(gh_engine *h) {
-    const gh_setup_args a = gh_make_setup_args(h, 0, h->d_sampled_cur, h->iter);
+    const gh_setup_args a = gh_make_setup_args(h, h->sample, h->iter);
     gh_tau_args t{};
     t.gmin = reinterpret_cast<const uint32_t *>(h->d_gmin);
     t.Gpad = a.Gpad;

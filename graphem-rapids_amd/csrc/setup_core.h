@@ -26,7 +26,7 @@
 struct gh_setup_args {
     const int32_t *edges;
     int32_t *sampled;        // ids of the iteration (read for mode 0, written otherwise)
-    int mode;                // 0 ids already in `sampled`, 1 device sampler, 2 arange
+    int mode;                // 0 ids already in `sampled`, 1 device sampler, 2 arange (engine.h GH_IDS_*)
     int64_t E;
     uint64_t seed, iter;
     int64_t S;
@@ -41,10 +41,7 @@ struct gh_setup_args {
     int64_t Gpad;            // row stride of gmin = 16 * tiles
     int tiles;               // ceil(M1 / 256): workgroups of gh_setup_block
     unsigned *tau_flag;      // thresholds inside the fused launch (tau_core.h): the published-queries counter, zeroed here
-    const uint64_t *iter_dev;  // replayed iterations (hipGraph, api.hip): the iteration number lives on the device and
-                               // `iter` above is an offset to it; null: `iter` is the number
 };
-__device__ __forceinline__ uint64_t gh_setup_iter(const gh_setup_args &a) { return a.iter_dev ? *a.iter_dev + a.iter : a.iter; }
 
 #define GH_THR_TILE 128    /* subset edges per set-up workgroup */
 #define GH_THR_GSIZE 64    /* subset edges per group */
@@ -56,7 +53,7 @@ __device__ __forceinline__ void gh_setup_item(const gh_setup_args &a, int64_t t,
     if (t == 0 && a.tau_flag) *a.tau_flag = 0;
     if (t >= a.S) return;
     int32_t e32;
-    if (a.mode == 1) { e32 = gh_sample_id(a.E, a.seed, gh_setup_iter(a), t); a.sampled[t] = e32; }
+    if (a.mode == 1) { e32 = gh_sample_id(a.E, a.seed, a.iter, t); a.sampled[t] = e32; }
     else if (a.mode == 2) { e32 = (int32_t)t; a.sampled[t] = e32; }
     else e32 = a.sampled[t];
     const int QS = gh_qs(a.D, a.LD);
@@ -111,7 +108,7 @@ __device__ __forceinline__ void gh_setup_fetch(const gh_setup_args &a, int blk, 
     // this lane's first query (every workgroup needs all of them; issued before the tile so that both chains of
     // dependent loads -- id -> edge -> rows here, endpoints -> rows below -- are in flight together)
     if (t < a.S) {
-        if (a.mode == 1) st.e32 = gh_sample_id(a.E, a.seed, gh_setup_iter(a), t);
+        if (a.mode == 1) st.e32 = gh_sample_id(a.E, a.seed, a.iter, t);
         else if (a.mode == 2) st.e32 = (int32_t)t;
         else st.e32 = a.sampled[t];
         const int2 uv = reinterpret_cast<const int2 *>(a.edges)[st.e32];
@@ -135,9 +132,8 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
     // so that the distance chain of two references runs on packed fp32 instructions (v_pk_add_f32 / v_pk_fma_f32)
     gh_f2 *rsh = reinterpret_cast<gh_f2 *>(lds);     // [GH_THR_TILE / 2][LD]
     const int t = threadIdx.x;
-    const uint64_t iter = gh_setup_iter(a);
     auto query = [&](int64_t s, int32_t &e32, float (&q)[LD]) {   // (queries past the first 256)
-        if (a.mode == 1) e32 = gh_sample_id(a.E, a.seed, iter, s);
+        if (a.mode == 1) e32 = gh_sample_id(a.E, a.seed, a.iter, s);
         else if (a.mode == 2) e32 = (int32_t)s;
         else e32 = a.sampled[s];
         const int2 uv = reinterpret_cast<const int2 *>(a.edges)[e32];

@@ -365,9 +365,7 @@ gh_status gh_timing_get(gh_handle h, int32_t i, const char **name, double *total
  *   GRAPHEM_HIP_NO_PRESETUP=1     the next iteration's KNN set-up as a launch of its own instead of inside the normalise
  *                                 launch (the per-query flags of gh_knn_last_counts then survive a step);
  *   GRAPHEM_HIP_REORDER=1|2       overrides gh_params.reorder (1 off, 2 breadth-first);
- *   GRAPHEM_HIP_STAMPS=1          allocates the stamp buffer gh_debug_stamps reads;
- *   GRAPHEM_HIP_GRAPH=1           gh_run replays iterations 2.. from a hipGraph of ten iterations (measured slower than
- *                                 enqueuing: 170.1 against 167.9 us per iteration at a million vertices). */
+ *   GRAPHEM_HIP_STAMPS=1          allocates the stamp buffer gh_debug_stamps reads. */
 
 /* Diagnostic runs only (environment GRAPHEM_HIP_STAMPS set at gh_create): 8 wall-clock stamps (100 MHz) per workgroup
  * of the last fused spring+scan launch (tools/stamp_probe.py).  Blocking. */

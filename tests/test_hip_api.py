@@ -323,33 +323,6 @@ def test_integration_md_binding_stub_runs():
     assert not np.array_equal(emb.get_positions(), out)
 
 
-def test_graph_replay_equals_the_enqueued_loop(monkeypatch):
-    """GRAPHEM_HIP_GRAPH=1: iterations 2.. of a device-sampled run replayed from a hipGraph (ten per graph, the iteration
-    number on the device) must give the bits of the enqueued loop, across runs of any length and after set_positions."""
-    import graphem_rapids_amd as gra
-    from graphem_rapids_amd import _native
-    n = 40000
-    edges = gra.random_regular_edges(n, 8, seed=2).astype(np.int32)
-    pos = (np.random.default_rng(1).standard_normal((n, 3)) * 0.1).astype(np.float32)
-
-    def sequence():
-        eng = _native.Engine(n, 3, edges, 1.0, 0.2, 0.5, 10, 256, seed=5)
-        eng.set_positions(pos)
-        eng.run(37)
-        eng.step(None)
-        eng.run(12)
-        a = eng.get_positions()
-        eng.set_positions(pos)
-        eng.run(25)
-        b = eng.get_positions()
-        eng.close()
-        return a, b
-    a0, b0 = sequence()
-    monkeypatch.setenv("GRAPHEM_HIP_GRAPH", "1")
-    a1, b1 = sequence()
-    assert np.array_equal(a0, a1) and np.array_equal(b0, b1)
-
-
 def test_lean_sqrt_and_division_are_ieee():
     """common.h gh_sqrt_ieee / gh_div_by (the spring phase's square root and its D divisions by one distance, with the
     reciprocal shared) must be bit-identical to sqrtf and '/': 2^32 pseudo-random operand sets over and beyond the fast
@@ -389,6 +362,34 @@ def test_run_torch_sampled_equals_run_over_torch_randperm(iters):
     ids2 = np.stack([torch.randperm(E)[:S].numpy() for _ in range(5)]).astype(np.int32)
     a.run(5, ids2)
     b.run_torch_sampled(5, state)
+    assert np.array_equal(state, torch.get_rng_state().numpy())
+    assert np.array_equal(a.get_positions(), b.get_positions())
+    a.close()
+    b.close()
+
+
+def test_run_torch_sampled_back_to_back_calls_equal_one_run():
+    """Two run_torch_sampled calls with nothing between them == one run over the concatenated torch.randperm(E)[:S] ids.
+    The first call returns with its last uploads still queued; the second call's uploads reuse those pinned slots and
+    must wait for them.  A graph large enough that the device, not the host, is the bottleneck."""
+    import torch
+    import graphem_rapids_amd as gra
+    from graphem_rapids_amd import _native
+    n, D, k, S = 1_000_000, 3, 10, 256
+    first, second = 300, 40
+    edges = gra.random_regular_edges(n, 8, seed=2).astype(np.int32)
+    E = len(edges)
+    pos = (np.random.default_rng(1).standard_normal((n, D)) * 0.1).astype(np.float32)
+    a = _native.Engine(n, D, edges, 1.0, 0.2, 0.5, k, S, knn_distance="cdist")
+    b = _native.Engine(n, D, edges, 1.0, 0.2, 0.5, k, S, knn_distance="cdist")
+    a.set_positions(pos)
+    b.set_positions(pos)
+    torch.manual_seed(5)
+    state = torch.get_rng_state().numpy().copy()
+    ids = np.stack([torch.randperm(E)[:S].numpy() for _ in range(first + second)]).astype(np.int32)
+    a.run(first + second, ids)
+    b.run_torch_sampled(first, state)
+    b.run_torch_sampled(second, state)
     assert np.array_equal(state, torch.get_rng_state().numpy())
     assert np.array_equal(a.get_positions(), b.get_positions())
     a.close()
