@@ -28,7 +28,7 @@ SYMBOLS = [
     "gh_knn_cdist_stats", "gh_rank_layout", "gh_step_finish_own", "gh_comm_available", "gh_selftest_arith",
     "gh_create_f64", "gh_set_positions_f64", "gh_get_positions_f64", "gh_positions_device_f64", "gh_spring_forces_f64",
     "gh_intersection_forces_f64", "gh_trlan_sweep", "gh_knn_ivf_config", "gh_knn_ivf_list_sizes",
-    "gh_torch_randperm_prefix", "gh_torch_randperm_isa", "gh_run_torch_sampled", "gh_set_cdist_replay", "gh_sampler_stats",
+    "gh_torch_randperm_prefix", "gh_torch_randperm_isa", "gh_run_torch_sampled", "gh_set_cdist_replay", "gh_set_scan_filter", "gh_get_scan_filter", "gh_qcell_probe", "gh_sampler_stats",
     "gh_overlap_layout", "gh_rows_all_device", "gh_rows_all_row_floats", "gh_stats_all_device", "gh_stats_all_block_doubles", "gh_step_rows_early",
     "gh_step_pack_rows", "gh_step_finish_overlap",
     "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
@@ -54,6 +54,8 @@ class GhPartition(ctypes.Structure):
 
 EDGES_RANGE, EDGES_HASHED = 0, 1  # gh_partition.edge_rule (include/graphem_hip.h)
 
+
+SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphem_hip.h)
 
 _lib = None
 
@@ -194,6 +196,12 @@ def load():
     L.gh_sampler_stats.restype = ctypes.c_int
     L.gh_set_cdist_replay.argtypes = [vp, i32]
     L.gh_set_cdist_replay.restype = ctypes.c_int
+    L.gh_set_scan_filter.argtypes = [vp, i32]
+    L.gh_set_scan_filter.restype = ctypes.c_int
+    L.gh_get_scan_filter.argtypes = [vp, ctypes.POINTER(i32)]
+    L.gh_get_scan_filter.restype = ctypes.c_int
+    L.gh_qcell_probe.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp]
+    L.gh_qcell_probe.restype = ctypes.c_int
     L.gh_knn_ivf_config.argtypes = [vp, vp, vp]
     L.gh_knn_ivf_config.restype = ctypes.c_int
     L.gh_knn_ivf_list_sizes.argtypes = [vp, vp, ctypes.c_int32]
@@ -529,6 +537,16 @@ class Engine:
     def set_cdist_replay(self, all_ties):
         """The loop of a knn_distance='cdist' engine replays every tie (True) or only those that can change a force (False, default)."""
         self._chk(self.lib.gh_set_cdist_replay(self.handle, 1 if all_ties else 0))
+
+    def set_scan_filter(self, mode):
+        """Pre-filter of the fused kernel for n_components <= 3: 'auto', 'mfma' or 'cells' (same results either way)."""
+        self._chk(self.lib.gh_set_scan_filter(self.handle, SCAN_FILTERS[mode]))
+
+    def scan_filter(self):
+        """The pre-filter in use: 'cells', 'mfma', or 'auto' when the engine runs neither."""
+        v = ctypes.c_int32(0)
+        self._chk(self.lib.gh_get_scan_filter(self.handle, ctypes.byref(v)))
+        return {b: a for a, b in SCAN_FILTERS.items()}[v.value]
 
     def knn_ivf_config(self):
         """(lists, probes per query) of a knn_method='ivf' engine; (0, 0) otherwise."""

@@ -2,6 +2,7 @@
 // copies, the iteration driver and the per-phase entry points.
 #include "common.h"
 #include "engine.h"
+#include "qcell_core.h"
 
 #include "torch_randperm.h"
 
@@ -92,7 +93,7 @@ static void free_all(gh_engine *h) {
     gh_ivf_free(h);
     void *ptrs[] = {h->d_edges, h->d_rowptr, h->d_adj, h->d_pos, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_new_own : (void *)h->d_new, h->d_gbuf, h->d_rows_all, h->d_rows_pk, h->d_stats_all, h->d_tmpF, h->d_tmpF2, h->d_io, h->d_acc,
                     h->d_tflag, h->d_touched, h->d_tcount, h->d_sampled, h->d_q, h->d_qscan, h->d_qA, h->d_qexact, h->d_order, h->d_long_rows, h->d_long_ownptr, h->d_long_ownadj, h->d_long_eptr, h->d_long_erow, h->d_long_terms, h->d_own_long, h->d_cand, h->d_cnt,
-                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_stats_comb, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
+                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_qcell, h->d_qc_flag, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_stats_comb, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_ring) (void)hipHostFree(h->h_ring);
@@ -225,6 +226,8 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_TRY(gh_cdist_alloc(h));
     GH_A(d_tau_flag, 1, true);
     GH_A(d_wait_failed, 1, true);
+    GH_A(d_qcell, GH_QC_WORDS, true);
+    GH_A(d_qc_flag, 1, true);
     if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
 #undef GH_A
     if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -288,7 +291,8 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     // workgroups or little more: there the iteration is a chain of launch latencies and this removes one (100 K vertices:
     // 64.9 -> 60.6 us).  A large graph gains nothing (1 M vertices: 175.7 -> 176.7 us, the first round of workgroups waits
     // ~3 us for producers that share their CUs with gathers) and keeps the launch of its own.
-    h->tau_embedded = sw.tau_separate >= 0 ? sw.tau_separate == 0 : h->n_vblocks <= 2048;
+    h->tau_embedded_plan = sw.tau_separate >= 0 ? sw.tau_separate == 0 : h->n_vblocks <= 2048;
+    gh_choose_scan_filter(h);                 // (fused.hip) sets tau_embedded
 
     const gh_status st = allocate_and_upload(h, g, sw);
     if (st != GH_OK) return bail(st);
@@ -330,7 +334,7 @@ static gh_status download_padded(gh_engine *h, const float *d_src, float *host) 
 // A workgroup of a fused launch gave up waiting for that launch's thresholds (tau_core.h): whatever was computed since
 // is not to be trusted.  Cannot happen while workgroups are started in index order; checked where the host synchronises.
 static gh_status check_device_waits(gh_engine *h) {
-    if (!h->tau_embedded || !h->d_wait_failed) return GH_OK;
+    if (!(h->tau_embedded || h->qcells) || !h->d_wait_failed) return GH_OK;
     int32_t failed = 0;
     GH_HIP(hipMemcpyAsync(&failed, h->d_wait_failed, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
@@ -339,7 +343,17 @@ static gh_status check_device_waits(gh_engine *h) {
         // workgroup waits for another any more)
         GH_HIP(hipMemsetAsync(h->d_wait_failed, 0, sizeof(int32_t), h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
-        h->tau_embedded = false;
+        if (h->qcells) {   // the wait was for the query-cell table (fused.hip): back to the split-f16 filter
+            h->scan_filter = GH_FILTER_MFMA;
+            gh_choose_scan_filter(h);
+            h->lookahead.valid = false;
+            h->err = "a workgroup of the fused spring+scan launch timed out waiting for the query-cell table of its own "
+                     "launch; results since the last successful gh_sync / gh_get_positions are invalid -- set the positions "
+                     "again.  The engine now uses the split-f16 pre-filter (GH_FILTER_MFMA); please report this";
+            return GH_ERR_RUNTIME;
+        }
+        h->tau_embedded_plan = false;
+        gh_choose_scan_filter(h);
         h->err = "a workgroup of the fused spring+scan launch timed out waiting for the thresholds of its own launch; "
                  "results since the last successful gh_sync / gh_get_positions are invalid -- set the positions again. "
                  "The engine now computes the thresholds in a launch of their own (as GRAPHEM_HIP_TAU_SEPARATE=1 does); "
@@ -549,6 +563,53 @@ extern "C" gh_status gh_set_cdist_replay(gh_handle h, int32_t all_ties) {
     GH_TRY(reject_f64(h, "gh_set_cdist_replay"));
     if (!h->cdist) { h->err = "gh_set_cdist_replay: not a GH_DIST_CDIST engine"; return GH_ERR_INVALID; }
     h->cd_all_ties = all_ties != 0;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_set_scan_filter(gh_handle h, int32_t mode) {
+    GH_TRY(check_handle(h));
+    GH_TRY(reject_f64(h, "gh_set_scan_filter"));
+    if (mode != GH_FILTER_AUTO && mode != GH_FILTER_MFMA && mode != GH_FILTER_CELLS) {
+        h->err = "gh_set_scan_filter: mode must be GH_FILTER_AUTO, GH_FILTER_MFMA or GH_FILTER_CELLS";
+        return GH_ERR_INVALID;
+    }
+    if (mode == GH_FILTER_CELLS && !gh_fused_cells_ok(h)) {
+        h->err = "gh_set_scan_filter: the query-cell filter needs a fused engine with n_components <= 3 and 1 <= sample_size <= " +
+                 std::to_string(GH_QC_SMAX);
+        return GH_ERR_INVALID;
+    }
+    h->scan_filter = mode;
+    const bool was_embedded = h->tau_embedded;
+    gh_choose_scan_filter(h);
+    // a set-up done ahead for the other threshold placement would not have zeroed the producers' counter: done again
+    if (h->tau_embedded != was_embedded) h->lookahead.valid = false;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_get_scan_filter(gh_handle h, int32_t *mode) {
+    GH_TRY(check_handle(h));
+    if (!mode) { h->err = "mode is NULL"; return GH_ERR_INVALID; }
+    *mode = h->f64 || !gh_fused_uses_mfma(h) || h->D > 3 ? GH_FILTER_AUTO : h->qcells ? GH_FILTER_CELLS : GH_FILTER_MFMA;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_qcell_probe(const float *bounds, int32_t D, const float *q, const float *tau, const float *m, int64_t n,
+                                    float *d2, int32_t *cells) {
+    if (!bounds || !q || !tau || !m || !d2 || !cells || D < 1 || D > 3 || n < 0) return GH_ERR_INVALID;
+    for (int64_t i = 0; i < n; ++i) {
+        float acc = 0.0f;
+        for (int d = 0; d < D; ++d) {
+            const float df = q[i * D + d] - m[i * D + d];   // park's chain (fused.hip)
+            acc = fmaf(df, df, acc);
+            const float *b = bounds + d * (GH_QC_G - 1);
+            int lo, hi;
+            gh_qc_axis_box(b, q[i * D + d], tau[i], lo, hi);
+            cells[(i * D + d) * 3] = gh_qc_axis_cell(b, m[i * D + d]);
+            cells[(i * D + d) * 3 + 1] = lo;
+            cells[(i * D + d) * 3 + 2] = hi;
+        }
+        d2[i] = acc;
+    }
     return GH_OK;
 }
 

@@ -195,7 +195,14 @@ struct gh_engine {
     // timing
     // thresholds inside the fused launch (tau_core.h)
     bool tau_embedded = false;
+    bool tau_embedded_plan = false;      // the creation-time choice; the query-cell filter overrides it (gh_choose_scan_filter)
     unsigned *d_tau_flag = nullptr;      // queries published so far by the current fused launch
+    // pre-filter of the D <= 3 fused kernel's phase B (fused.hip): query-cell table or split-f16 MFMA
+    int scan_filter = 0;                 // GH_FILTER_AUTO | _MFMA | _CELLS, as set by gh_set_scan_filter
+    bool qcells = false;                 // in use: the query-cell table (qcell_core.h)
+    uint32_t *d_qcell = nullptr;         // (GH_QC_WORDS) the table of the current launch, built by its first workgroup
+    unsigned *d_qc_flag = nullptr;       // launch number whose table is complete
+    unsigned qc_epoch = 0;               // number of the last launch on the query-cell path
     int32_t *d_wait_failed = nullptr;    // a consumer gave up waiting: reported by gh_sync / gh_get_positions
 
 #define GH_STAMP_EXTRA 8192
@@ -292,6 +299,8 @@ gh_status gh_radial_topk_device(gh_engine *h, int K, uint64_t *d_part, int npart
 int gh_fused_mfma_kb(const gh_engine *h);          // operand rows the thresholds must write: 0 = split-f16 MFMA form (D <= 3), -1 = none
 bool gh_fused_uses_mfma(const gh_engine *h);       // the fused kernel's pre-filter runs on the matrix pipe
 int gh_fused_tile(const gh_engine *h);              // edges per fused workgroup
+bool gh_fused_cells_ok(const gh_engine *h);         // the query-cell pre-filter can serve this engine (fused.hip)
+void gh_choose_scan_filter(gh_engine *h);           // qcells and tau_embedded from scan_filter and tau_embedded_plan
 gh_status gh_launch_spring_scan(gh_engine *h);             // d_Fs + final-level candidates in one kernel
 gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world);  // -> d_keys_cur
 // forces.hip

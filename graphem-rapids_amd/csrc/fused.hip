@@ -10,11 +10,15 @@
 //            two index_add_ calls) -> Fs; the midpoints (pt.py:785) of the owned edges fall
 //            out of the gathered rows and are kept in LDS, never written to memory;
 //   phase B  those midpoints become the workgroup's reference tile: R per thread in packed
-//            registers, all S queries stream past (scan_core.h).
+//            registers, all S queries stream past (scan_core.h).  For D <= 3 on graphs whose thresholds
+//            have a launch of their own the queries are indexed instead: a cell table of their balls,
+//            built by the launch's first workgroup, sends each midpoint to the few queries that can
+//            reach it (qcell_core.h, spring_scan_cells_kernel).
 // Workgroups in phase A (waiting on gathers) and workgroups in phase B (issuing VALU) share
 // the CUs, so the two bounds overlap instead of adding.
 #include "common.h"
 #include "engine.h"
+#include "qcell_core.h"
 #include "scan_core.h"
 #include "tau_core.h"
 
@@ -46,7 +50,18 @@ static void fused_cfg(int LD, int D, int64_t S, int64_t own_edges, int *nt, int 
     *r = 2;
 }
 bool gh_fused_uses_mfma(const gh_engine *h) { return h->fused_scan && fused_mfma(h->LD, h->D, h->S); }
-int gh_fused_mfma_kb(const gh_engine *h) { return h->fused_scan ? fused_mfma_kb(h->LD, h->D, h->S) : -1; }
+int gh_fused_mfma_kb(const gh_engine *h) { return h->fused_scan && !h->qcells ? fused_mfma_kb(h->LD, h->D, h->S) : -1; }
+// The query-cell pre-filter (spring_scan_cells_kernel) serves D <= 3 with up to GH_QC_SMAX queries: one staged group of
+// query records and one uint8 index per table entry.  AUTO takes it wherever the thresholds have a launch of their own
+// (graphs of more than 2048 fused workgroups); where they are computed inside the fused launch the split-f16 form stays.
+bool gh_fused_cells_ok(const gh_engine *h) {
+    return h->fused_scan && fused_mfma(h->LD, h->D, h->S) && h->D <= 3 && h->S >= 1 && h->S <= GH_QC_SMAX;
+}
+void gh_choose_scan_filter(gh_engine *h) {
+    const bool want = h->scan_filter == GH_FILTER_CELLS || (h->scan_filter == GH_FILTER_AUTO && !h->tau_embedded_plan);
+    h->qcells = want && gh_fused_cells_ok(h);
+    h->tau_embedded = h->tau_embedded_plan && !h->qcells;   // the cell table is built from thresholds already in memory
+}
 int gh_fused_tile(const gh_engine *h) {
     int nt, r;
     fused_cfg(h->LD, h->D, h->S, h->own_count, &nt, &r);
@@ -323,6 +338,165 @@ __global__ __launch_bounds__(256) void spring_scan_mfma_kernel(
 #undef GH_STAMP
 }
 
+// Query-cell form of phase B (D <= 3; qcell_core.h).  Workgroup 0 of the launch builds the cell table of the S query
+// balls from the thresholds a launch of their own has left in memory, while the others run phase A, and publishes it as
+// gh_tau_produce publishes thresholds (write-through stores, the wave waits for them, then the flag -- here the number
+// of this launch, so nothing has to zero it).  The waves without rows in phase A wait for the flag and stage the table
+// (sc1 loads) and the S query records while the others gather; after phase A each thread takes 2 midpoints of the tile:
+// the queries listed in its cell, then the wide ones, each through the exact fp32 test and hit buffer of the MFMA form.
+// Same candidates as that form by construction: both keep exactly the pairs with fp32 d2 <= tau (the MFMA filter and
+// this table only decide which pairs reach the test).
+// rr1m (tools/stamp_probe.py, median workgroup): scan 6.1 -> 3.2 us, operand build / staging 1.2 -> 0.04, lifetime 18.3
+// -> 16.1; the gathers of phase A take 8.1 -> 9.1 us, with more workgroups in phase A at a time.  Kernel 129.5 -> 114.1
+// us.  88 VGPRs (77 for D = 2), 24.2 KB of LDS: five workgroups per CU, as for the MFMA form (91 VGPRs, 30 KB); six
+// would need 80 VGPRs, which the compiler reaches only by spilling (36 bytes per lane; not measured).
+template <int D>
+__global__ __launch_bounds__(256) void spring_scan_cells_kernel(
+    const float *__restrict__ pos, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ adj,
+    const int32_t *__restrict__ first_edge, const int32_t *__restrict__ own_eids,
+    const int32_t *__restrict__ vblock, int64_t row_lo, float L_min, float neg_k, float *__restrict__ Fs,
+    float *__restrict__ out_new, double *__restrict__ blockstats, const float *__restrict__ qt, int S,
+    uint32_t *__restrict__ qcell, unsigned *__restrict__ qc_flag, unsigned epoch, int32_t *__restrict__ wait_failed,
+    uint64_t *__restrict__ cand, int32_t *__restrict__ cnt, gh_long_args la, int cdist, unsigned long long *__restrict__ stamps) {
+    constexpr int LD = 4, NT = 256, R = 2, TILE = NT * R, HITBUF = 512;
+    static_assert(D <= 3, "query records of one 16-byte load");
+    __shared__ float4 tile[TILE];               // fp32 midpoints of the owned edges (x, y, z, 0)
+    __shared__ float4 qrec[GH_QC_SMAX];         // (q_0, q_1, q_2, tau)
+    __shared__ uint32_t tab[GH_QC_WORDS];       // the cell table (qcell_core.h)
+    __shared__ uint64_t hkey[HITBUF];
+    __shared__ int hq[HITBUF];
+    __shared__ uint32_t ids[TILE];
+    __shared__ int hcount;
+    if (blockIdx.x == 0) {   // the table of this launch (scratch counters in the hit buffer)
+        gh_qc_build<D, NT>(reinterpret_cast<const float4 *>(qt), S, tab, qrec, reinterpret_cast<uint32_t *>(hkey));
+        for (int i = threadIdx.x; i < GH_QC_WORDS; i += NT)
+            __hip_atomic_store(qcell + i, tab[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's write-through stores have left ...
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(qc_flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the flag
+        return;
+    }
+    const int nbx = (int)gridDim.x - 1;
+    const int bx = (int)blockIdx.x - 1;
+#define GH_STAMP(k) do { if (stamps && threadIdx.x == 0) stamps[(int64_t)bx * 8 + (k)] = wall_clock64(); } while (0)
+    GH_STAMP(0);
+    if (stamps && threadIdx.x == 0) { stamps[(int64_t)bx * 8 + 6] = vblock[bx + 1] - vblock[bx]; stamps[(int64_t)bx * 8 + 7] = first_edge[vblock[bx + 1]] - first_edge[vblock[bx]]; }
+    float *mids = reinterpret_cast<float *>(tile);
+    const int v0 = vblock[bx], v1 = vblock[bx + 1];
+    const int fe0 = first_edge[v0];
+    const int nedges = first_edge[v1] - fe0;
+    if (threadIdx.x == 0) hcount = 0;
+    for (int j = threadIdx.x; j < nedges; j += NT) ids[j] = own_eids ? (uint32_t)own_eids[fe0 + j] : (uint32_t)(fe0 + j);
+
+    // Staging: the query records (written by the threshold launch before this one: plain loads), then -- once workgroup 0
+    // has published it: a wave-wide poll, one request per wave -- the table (sc1 loads).  A tile of 512 owned edges is ~128
+    // rows for 256 threads, so as a rule waves 2 and 3 have nothing to do in phase A: they stage while the others gather,
+    // and the barrier in gh_block_stats publishes it.  A workgroup whose rows take every wave stages after phase A.
+    const int t_idle = min(NT, (v1 - v0 + 63) / 64 * 64);   // first thread of the first wave without rows
+    auto stage = [&](int t0) {   // by threads t0 .. NT - 1
+        for (int i = (int)threadIdx.x - t0; i < S; i += NT - t0) qrec[i] = reinterpret_cast<const float4 *>(qt)[i];
+        unsigned spins = 0;
+        while ((int)(__hip_atomic_load(qc_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0) {
+            __builtin_amdgcn_s_sleep(32);
+            if (++spins > (1u << 20)) { *wait_failed = 1; break; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // orders the loads below after the poll; no cache invalidate
+        for (int i = (int)threadIdx.x - t0; i < GH_QC_WORDS / 4; i += NT - t0)
+            reinterpret_cast<float4 *>(tab)[i] = gh_ld_f4(reinterpret_cast<const float4 *>(qcell) + i, true);
+    };
+    if (t_idle < NT && (int)threadIdx.x >= t_idle) stage(t_idle);
+
+    __shared__ double red[(NT / 64) * 2 * LD];
+    {
+        double sx[LD], sxx[LD];
+        gh_phase_a<D, LD, NT, true>(pos, rowptr, adj, first_edge, v0, v1, fe0, nedges, row_lo, L_min, neg_k, Fs, out_new, mids, sx, sxx, la);
+        GH_STAMP(1);
+        gh_block_stats<LD, NT>(sx, sxx, red, blockstats, bx, nbx, v1 - v0);  // contains the barrier that ends phase A
+    }
+    GH_STAMP(2);
+    if (t_idle == NT) {
+        stage(0);
+        __syncthreads();
+    }
+    GH_STAMP(3);
+
+    const float *bnd = reinterpret_cast<const float *>(tab + GH_QC_OFF_B);
+    const uint16_t *ptr = reinterpret_cast<const uint16_t *>(tab + GH_QC_OFF_PTR);
+    const uint8_t *ent = reinterpret_cast<const uint8_t *>(tab + GH_QC_OFF_ENT);
+    const uint8_t *wide = reinterpret_cast<const uint8_t *>(tab + GH_QC_OFF_WIDE);
+    const int nwide = (int)tab[GH_QC_OFF_NWIDE];
+    auto park = [&](int s, const float4 qr, int j, const float (&m)[3]) {  // exact decision on pair (query s = qr, reference j)
+        const float q[3] = {qr.x, qr.y, qr.z};
+        float d2 = 0.0f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const float df = q[d] - m[d];
+            d2 = fmaf(df, df, d2);
+        }
+        if (d2 <= qr.w) {
+            if (cdist) d2 = gh_aten_cdist<D>(q, m);   // parity mode: the key carries the value the reference ranks
+            const uint32_t id = ids[j];
+            const int p = atomicAdd(&hcount, 1);
+            if (p < HITBUF) { hkey[p] = gh_key(d2, id); hq[p] = s; }
+            else gh_append_candidate(cand, cnt, s, gh_key(d2, id));
+        }
+    };
+    // A thread's tests: the queries listed in the cells of its two midpoints, then the wide ones against both.  U entries
+    // at a time, their index and record loads issued back to back: the lists are a handful of entries each (rr1m: ~9
+    // tests per midpoint), so the loop is bound by dependent LDS round trips, not by issue -- one entry at a time the
+    // scan took 7.2 us of a workgroup's lifetime against the MFMA form's 6.2.
+    constexpr int U = 4;
+    float m[R][3];
+    int e[R], e1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = (int)threadIdx.x + r * NT;
+        const float4 mv = tile[j < nedges ? j : 0];
+        m[r][0] = mv.x; m[r][1] = mv.y; m[r][2] = mv.z;
+        int c = gh_qc_axis_cell(bnd, m[r][0]) + GH_QC_G * gh_qc_axis_cell(bnd + 8, m[r][1]);
+        if constexpr (D == 3) c += GH_QC_G * GH_QC_G * gh_qc_axis_cell(bnd + 16, m[r][2]);
+        e[r] = j < nedges ? ptr[c] : 0;
+        e1[r] = j < nedges ? ptr[c + 1] : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = (int)threadIdx.x + r * NT;
+        for (int b = e[r]; b < e1[r]; b += U) {
+            int s[U];
+            float4 qr[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] = ent[min(b + u, e1[r] - 1)];
+#pragma unroll
+            for (int u = 0; u < U; ++u) qr[u] = qrec[s[u]];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (b + u < e1[r]) park(s[u], qr[u], j, m[r]);
+        }
+    }
+    for (int b = 0; b < nwide; b += U) {
+        int s[U];
+        float4 qr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) s[u] = wide[min(b + u, nwide - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) qr[u] = qrec[s[u]];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int j = (int)threadIdx.x + r * NT;
+            if (j < nedges) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (b + u < nwide) park(s[u], qr[u], j, m[r]);
+            }
+        }
+    }
+    __syncthreads();
+    GH_STAMP(4);
+    gh_flush_hits<HITBUF, NT>(hkey, hq, &hcount, cand, cnt);
+    GH_STAMP(5);
+#undef GH_STAMP
+}
+
 // Wide rows (5 <= D <= 16) with the pre-filter on the matrix pipe (scan_core.h "Wide rows"): phase A as in
 // spring_scan_kernel, phase B as in spring_scan_mfma_kernel with 16 * KB deep contractions -- each wave owns 4 column
 // blocks of 32 references whose f16 operands stay in registers, the queries stream past as A operands from LDS, a lane
@@ -572,6 +746,14 @@ void launch_mfma_d(gh_engine *h) {
         -h->prm.k_attr, h->d_Fs, h->d_new, h->d_blockstats, h->d_q, reinterpret_cast<const gh_h8 *>(h->d_qA),
         h->d_qexact, (int)h->S, h->d_cand, h->d_cnt, gh_make_long_args(h, true), ta, h->d_stamps);
 }
+template <int D>
+void launch_cells(gh_engine *h) {
+    if (++h->qc_epoch == 0) h->qc_epoch = 1;   // (0 is the flag's value before the first launch)
+    spring_scan_cells_kernel<D><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
+        h->d_pos, h->d_rowptr, h->d_adj, h->d_first_edge, h->d_own_eids, h->d_vblock, h->part.row_lo, h->prm.L_min,
+        -h->prm.k_attr, h->d_Fs, h->d_new, h->d_blockstats, h->d_q, (int)h->S, h->d_qcell, h->d_qc_flag, h->qc_epoch,
+        h->d_wait_failed, h->d_cand, h->d_cnt, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps);
+}
 template <int D, int R>
 void launch_mfma(gh_engine *h) {
     if (R == 2 && h->n_vblocks <= 2048) launch_mfma_d<D, R, (R == 2)>(h);   // one round of workgroups: occupancy does not matter
@@ -629,6 +811,8 @@ gh_status gh_launch_spring_scan(gh_engine *h) {
             case 15: launch_mfmaw<15, 16>(h); break;
             default: launch_mfmaw<16, 16>(h); break;
         }
+    } else if (h->qcells) {
+        if (h->D == 2) launch_cells<2>(h); else launch_cells<3>(h);
     } else if (fused_mfma(h->LD, h->D, h->S)) {
         if (h->D == 2) launch_mfma<2, 2>(h); else launch_mfma<3, 2>(h);
     } else {

@@ -390,6 +390,27 @@ gh_status gh_knn_cdist_stats(gh_handle h, int32_t *full_pass_rows, int32_t *unre
  * replays partial_sort's heap for those two kinds of tie only -- same positions, bit for bit, as with all_ties = 1 (every
  * tie, rows column for column: what gh_knn_midpoints always does, and what row-partitioned engines always do). */
 gh_status gh_set_cdist_replay(gh_handle h, int32_t all_ties);
+/* The pre-filter of the fused spring+scan kernel for n_components <= 3 -- which (query, midpoint) pairs reach the exact
+ * fp32 test d2 <= tau; the candidates, and so the neighbour rows and positions, are the same bit for bit either way.
+ *   GH_FILTER_CELLS  a table of the sampled midpoints' query balls over a quantile grid of 8 cells per axis, built once
+ *                    per iteration on the device; a midpoint tests the queries listed in its cell (and those whose ball
+ *                    spans many cells).  Needs a fused engine with 1 <= sample_size <= 256; the thresholds then have
+ *                    a launch of their own.
+ *   GH_FILTER_MFMA   every pair through the split-f16 matrix-pipe screen.
+ *   GH_FILTER_AUTO   (default) CELLS where the engine would compute the thresholds in a launch of their own anyway
+ *                    (graphs of more than 2048 fused workgroups of 512 owned edges), else MFMA.
+ * Forcing CELLS where it cannot serve is refused.  gh_get_scan_filter reports the filter in use: GH_FILTER_CELLS or
+ * GH_FILTER_MFMA, or GH_FILTER_AUTO when the engine runs neither (another dimension, an unfused or a float64 engine). */
+#define GH_FILTER_AUTO 0
+#define GH_FILTER_MFMA 1
+#define GH_FILTER_CELLS 2
+gh_status gh_set_scan_filter(gh_handle h, int32_t mode);
+gh_status gh_get_scan_filter(gh_handle h, int32_t *mode);
+/* Host copy of the query-cell box (test support): for each of n (q, tau, m) triples of D <= 3 coordinates -- boundaries
+ * (D, 7) per axis -- writes the fp32 chain d2(q, m) of the exact test to d2[i], and per axis the cell of m and q's box
+ * [lo, hi] to cells[(i * D + d) * 3 + {0, 1, 2}]. */
+gh_status gh_qcell_probe(const float *bounds, int32_t D, const float *q, const float *tau, const float *m, int64_t n,
+                         float *d2, int32_t *cells);
 /* GH_KNN_IVF engines: the number of inverted lists and of lists probed per query the engine settled on (0, 0 when the
  * engine searches another way).  Either pointer may be NULL. */
 gh_status gh_knn_ivf_config(gh_handle h, int32_t *lists, int32_t *probes);
