@@ -15,8 +15,9 @@ Order of a run: engine + positions; the device is brought to its steady power st
 for 150 ms, on a second engine over the same graph -- `spinup_steps` in the JSON line); SETTLE_STEPS iterations of the
 measured engine, after which the starting positions are put back (`settle_steps`); W untimed warm-up steps;
 `--repeats` timed passes of EXACTLY K steps each, barrier + synchronize on both sides, the median reported (`value`,
-`ms_per_step`; every pass in `ms_per_step_passes`); then a pass with HIP-event timers for the per-kernel table, the
-parity-mode record and the CPU baseline.
+`ms_per_step`; every pass in `ms_per_step_passes`).  That is all a plain run does.  With --full the line also carries what
+takes runs of its own: a pass with HIP-event timers for the per-kernel table and the kernel rooflines (and, with N > 1,
+`rank0_us_per_step`), the parity-mode record, the public-API record and the CPU baseline.
 
 --dump-outputs DIR writes what the timed passes computed, as a caller of the timed path receives it after their last
 step: DIR/positions.npy (float32, n x D; a fixed seeded sample of rows when that exceeds 64 MB).  The inputs -- graph,
@@ -437,10 +438,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="rr1m", choices=sorted(WORKLOADS))
     ap.add_argument("--sampler", default="device", choices=["device", "host"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event times and the kernel rooflines (a pass "
+                         "of their own; rank0_us_per_step with N > 1), the parity_mode and public_api sub-records, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline record")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # the child process of cpu_baseline_pinned()
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the parity_mode sub-record (the same steps with knn_distance='cdist')")
-    ap.add_argument("--no-public-api", action="store_true", help="skip the public_api sub-record (wall clock around create_graphem(...).run_layout(K))")
+    ap.add_argument("--no-parity-mode", action="store_true", help="--full without the parity_mode sub-record (the same steps with knn_distance='cdist')")
+    ap.add_argument("--no-public-api", action="store_true", help="--full without the public_api sub-record (wall clock around create_graphem(...).run_layout(K))")
     ap.add_argument("--sample-size", type=int, default=None, help="override the workload's number of sampled midpoints")
     ap.add_argument("--knn", default="auto", choices=["auto", "scan", "grid", "ivf"],
                     help="KNN search (gh_params.knn_method); ivf is approximate (recall: tools/ivf_probe.py)")
@@ -582,49 +586,32 @@ def main():
             dt = float(t.item())
         passes.append(dt)
     dt = sorted(passes)[len(passes) // 2]
-    # (the file is written at the end; the download idles the device, so it is brought back to its steady state before
-    # the evented pass -- after a bare download the per-kernel times read ~3 % higher)
     last_pos = (lay if use_dist else eng).get_positions() if args.dump_outputs and rank == 0 else None
-    if args.dump_outputs:
-        spin_up(run, sync, max(1, args.steps), lambda: None, agree)
 
-    # per-kernel durations with HIP events on the launching stream: a second pass of the same K steps
-    eng.timing_enable(True)
-    eng.timing_reset()
-    if use_dist:
-        lay.time_overlap = True
-    run(args.steps)
-    sync()
-    timings = eng.timings()
-    eng.timing_enable(False)
-    exposed_py = None
-    if use_dist:
-        lay.time_overlap = False
-        if lay.exposed_events:   # Python-driven form D: how long the engine's stream still waited for the early all-gather
-            torch.cuda.synchronize()
-            exposed_py = 1e3 * sum(a.elapsed_time(b) for a, b in lay.exposed_events) / len(lay.exposed_events)
-            lay.exposed_events.clear()
+    timings = exposed_py = None
+    if args.full:
+        # (the file is written at the end; the download idles the device, so it is brought back to its steady state before
+        # the evented pass -- after a bare download the per-kernel times read ~3 % higher)
+        if args.dump_outputs:
+            spin_up(run, sync, max(1, args.steps), lambda: None, agree)
+        # per-kernel durations with HIP events on the launching stream: a second pass of the same K steps
+        eng.timing_enable(True)
+        eng.timing_reset()
+        if use_dist:
+            lay.time_overlap = True
+        run(args.steps)
+        sync()
+        timings = eng.timings()
+        eng.timing_enable(False)
+        if use_dist:
+            lay.time_overlap = False
+            if lay.exposed_events:   # Python-driven form D: how long the engine's stream still waited for the early all-gather
+                torch.cuda.synchronize()
+                exposed_py = 1e3 * sum(a.elapsed_time(b) for a, b in lay.exposed_events) / len(lay.exposed_events)
+                lay.exposed_events.clear()
 
     if rank == 0:
         ms = 1e3 * dt / args.steps
-        kern = {name: {"avg_us": 1e3 * tot / cnt, "launches_per_step": cnt / args.steps}
-                for name, (tot, cnt) in sorted(timings.items(), key=lambda kv: -kv[1][0])}
-        E_rank = E // world
-        n_rank = n // world
-        # Dominant kernel: the fused spring+scan kernel (the stand-alone scan when unfused).  It is bound by the
-        # memory system: the spring phase gathers one position row per pull-list entry (2E random 16-byte rows),
-        # and with no locality in the graph most of them miss the L2 (PMC traffic below).
-        roofline, scan_us = fused_roofline(kern, E_rank, n_rank, D, args.workload, world)
-        knn_fp32 = None
-        if scan_us:
-            flops_scan = 3.0 * D * S * E_rank
-            knn_fp32 = {"kernel": roofline["kernel"], "bound": "mfma", "kind": "fp32-equivalent rate, not pipe utilisation",
-                        "what": "the search's algorithmic fp32 flops (3 D S E per launch) over the kernel's duration against the fp32 vector "
-                                "peak; the work itself is done by a split-f16 pre-filter on v_mfma_f32_32x32x16_f16 (D <= 3; packed fp32 VALU "
-                                "otherwise) plus an exact fp32 re-check of the few pairs that pass, in far fewer instructions per pair",
-                        "achieved": flops_scan / (scan_us * 1e-6) / 1e12, "peak": FP32_PEAK / 1e12, "unit": "TFLOP/s (fp32-equivalent)",
-                        "frac": flops_scan / (scan_us * 1e-6) / FP32_PEAK, "algorithmic_flops_per_launch": flops_scan}
-        hbm = iter_roofline(ms, E, n, D)
         out = {
             "metric": "layout iterations/s", "value": args.steps / dt, "unit": "iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_steps": spinup_steps, "settle_steps": settle_steps,
@@ -639,11 +626,32 @@ def main():
                        "parallelism": f"rows/{world}" + (("+gloo-rehearsal-on-one-gpu" if rehearsal else "+rccl") if use_dist else ""),
                        # speed mode (knn_distance='exact', device sampler): exact-difference distances, ties on the smaller id --
                        # 252-256 of 256 neighbour rows equal the reference's at 1 M vertices; the mode whose rows ARE the
-                       # reference's on every vertex is the `parity_mode` record of this line (reference_identical: true)
+                       # reference's on every vertex is the `parity_mode` record of a --full line (reference_identical: true)
                        "reference_identical": args.knn_distance == "cdist" and args.sampler == "host"},
-            "roofline": roofline, "roofline_knn_fp32": knn_fp32, "roofline_iter_hbm": hbm, "kernels": kern,
+            "roofline_iter_hbm": iter_roofline(ms, E, n, D),
         }
-        if use_dist:  # rank 0's split of an iteration (HIP events on the engine's stream, second pass): where a scaling run loses its time
+        if use_dist:
+            out["config"]["finish"] = args.finish
+        if args.full:
+            kern = {name: {"avg_us": 1e3 * tot / cnt, "launches_per_step": cnt / args.steps}
+                    for name, (tot, cnt) in sorted(timings.items(), key=lambda kv: -kv[1][0])}
+            E_rank = E // world
+            n_rank = n // world
+            # Dominant kernel: the fused spring+scan kernel (the stand-alone scan when unfused).  It is bound by the
+            # memory system: the spring phase gathers one position row per pull-list entry (2E random 16-byte rows),
+            # and with no locality in the graph most of them miss the L2 (PMC traffic below).
+            roofline, scan_us = fused_roofline(kern, E_rank, n_rank, D, args.workload, world)
+            knn_fp32 = None
+            if scan_us:
+                flops_scan = 3.0 * D * S * E_rank
+                knn_fp32 = {"kernel": roofline["kernel"], "bound": "mfma", "kind": "fp32-equivalent rate, not pipe utilisation",
+                            "what": "the search's algorithmic fp32 flops (3 D S E per launch) over the kernel's duration against the fp32 vector "
+                                    "peak; the work itself is done by a split-f16 pre-filter on v_mfma_f32_32x32x16_f16 (D <= 3; packed fp32 VALU "
+                                    "otherwise) plus an exact fp32 re-check of the few pairs that pass, in far fewer instructions per pair",
+                            "achieved": flops_scan / (scan_us * 1e-6) / 1e12, "peak": FP32_PEAK / 1e12, "unit": "TFLOP/s (fp32-equivalent)",
+                            "frac": flops_scan / (scan_us * 1e-6) / FP32_PEAK, "algorithmic_flops_per_launch": flops_scan}
+            out.update(roofline=roofline, roofline_knn_fp32=knn_fp32, kernels=kern)
+        if args.full and use_dist:  # rank 0's split of an iteration (HIP events on the engine's stream, second pass): where a scaling run loses its time
             per = lambda name: kern[name]["avg_us"] * kern[name]["launches_per_step"] if name in kern else 0.0
             comp = sum(v["avg_us"] * v["launches_per_step"] for name, v in kern.items() if not name.startswith("allgather"))
             # collectives on the engine's stream are exposed in full; form D's early all-gather of the rows runs on a side
@@ -667,12 +675,11 @@ def main():
                         "existed when it was written (development boxes have one GPU): this record is what a multi-GPU driver run fills in",
                 "loop": "gh_run_partitioned (C library; RCCL all-gathers, form D's rows on a second stream + ncclCommSplit communicator)"
                         if native else "python-driven (torch.distributed; form D's rows on a side stream + a process group of their own)"}
-            out["config"]["finish"] = args.finish
-        if world == 1 and not use_dist and args.knn_distance == "exact" and not args.no_parity_mode:
+        if args.full and world == 1 and not use_dist and args.knn_distance == "exact" and not args.no_parity_mode:
             out["parity_mode"] = parity_mode(args, n, D, k, S, edges, pos, local_rank)
-        if world == 1 and not use_dist and not args.no_public_api:
+        if args.full and world == 1 and not use_dist and not args.no_public_api:
             out["public_api"] = public_api(args, local_rank)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_pinned(args)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         if last_pos is not None:

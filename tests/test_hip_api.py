@@ -464,14 +464,14 @@ def test_public_run_layout_draws_like_the_reference_loop():
 
 
 def test_bench_line_contract_on_a_small_workload():
-    """bench.py end to end (the driver's command on the quick workload): ONE JSON line with the contract's fields, the
-    roofline and cpu_baseline objects, and this round's sub-records (parity_mode with its own roofline, public_api)."""
+    """bench.py --full end to end on the quick workload: ONE JSON line with the contract's fields, the roofline and
+    cpu_baseline objects, and the sub-records (parity_mode with its own roofline, public_api)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                          "--workload", "rr20k"], capture_output=True, text=True, timeout=600)
+                          "--workload", "rr20k", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -488,6 +488,29 @@ def test_bench_line_contract_on_a_small_workload():
     for case in d["public_api"]["cases"].values():
         assert case["torch"]["reference_identical"] is True and case["device"]["reference_identical"] is False
         assert case["torch"]["ms_per_iteration"] > 0 and case["device"]["ms_per_iteration"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """bench.py without --full (the driver's command on the quick workload): ONE JSON line with the headline's fields and
+    none of the records that take runs of their own (per-kernel event pass, parity mode, public API, CPU baseline)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                          "--workload", "rr20k"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_cold", "higher_is_better",
+                "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["metric"] == "layout iterations/s" and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 5 and d["warmup"] == 2 and d["repeats"] == 3
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-6
+    for key in ("roofline", "roofline_knn_fp32", "kernels", "parity_mode", "public_api", "cpu_baseline"):
+        assert key not in d, key
 
 
 def test_bench_dump_outputs_are_the_timed_paths_last_positions(tmp_path):

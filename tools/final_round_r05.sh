@@ -5,17 +5,17 @@
 out=${1:-gpurun_out/final}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT; mkdir -p $out
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_command_rr1m.json 2> $out/bench_driver_command_rr1m.err || exit 1
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_command_rr1m.json 2> $out/bench_driver_command_rr1m.err || exit 1
 echo "driver command done"
 for wl in rr100k er1m rr4m snap16 rr1m_d6 rr1m_d12 pp1m; do
-  python bench.py --workload $wl --steps 50 --warmup 5 --no-cpu-baseline --no-public-api > $out/bench_$wl.json 2>/dev/null || echo "$wl failed"
+  python bench.py --full --workload $wl --steps 50 --warmup 5 --no-cpu-baseline --no-public-api > $out/bench_$wl.json 2>/dev/null || echo "$wl failed"
   echo "$wl done"
 done
-python bench.py --dist --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_python_overlap_rr1m.json 2>/dev/null || echo "dist python failed"
-python bench.py --dist --loop native --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_overlap_rr1m.json 2>/dev/null || echo "dist native failed"
-python bench.py --dist --loop native --finish own --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_own_rr1m.json 2>/dev/null || echo "dist native own failed"
-python bench.py --dist --loop native --workload rr4m --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_overlap_rr4m.json 2>/dev/null || echo "dist native rr4m failed"
-python bench.py --dist --loop native --knn-distance cdist --steps 30 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_cdist_rr1m.json 2>/dev/null || echo "dist native cdist failed"
+python bench.py --full --dist --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_python_overlap_rr1m.json 2>/dev/null || echo "dist python failed"
+python bench.py --full --dist --loop native --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_overlap_rr1m.json 2>/dev/null || echo "dist native failed"
+python bench.py --full --dist --loop native --finish own --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_own_rr1m.json 2>/dev/null || echo "dist native own failed"
+python bench.py --full --dist --loop native --workload rr4m --steps 50 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_overlap_rr4m.json 2>/dev/null || echo "dist native rr4m failed"
+python bench.py --full --dist --loop native --knn-distance cdist --steps 30 --warmup 5 --no-cpu-baseline --no-parity-mode --no-public-api > $out/bench_dist_world1_native_cdist_rr1m.json 2>/dev/null || echo "dist native cdist failed"
 echo "dist done"
 python tools/bench_f64.py rr100k rr1m > $out/bench_f64.log 2>&1
 python tools/cdist_probe.py rr1m 30 > $out/cdist_probe_rr1m.log 2>&1
