@@ -12,6 +12,8 @@ from .generators import (erdos_renyi_graph, generate_random_regular, erdos_renyi
                          edges_to_adjacency, load_snap_edge_list)
 from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influence, greedy_seed_selection,
                         run_influence_benchmark)
+from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
+                         eigenvector_centrality_numpy, run_benchmark, benchmark_correlations)
 
 __version__ = "0.1.0"
 
@@ -55,4 +57,6 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "erdos_renyi_edges", "random_regular_edges", "planted_partition_edges", "edges_to_adjacency", "load_snap_edge_list",
            "graphem_seed_selection", "MemoryManager", "cleanup_gpu_memory", "get_gpu_memory_info",
            "get_optimal_chunk_size", "monitor_memory_usage", "InfluenceGraph", "influence_spread",
-           "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark"]
+           "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark",
+           "CentralityGraph", "betweenness_centrality", "load_centrality", "closeness_centrality", "pagerank",
+           "eigenvector_centrality_numpy", "run_benchmark", "benchmark_correlations"]

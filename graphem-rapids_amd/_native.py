@@ -32,6 +32,8 @@ SYMBOLS = [
     "gh_overlap_layout", "gh_rows_all_device", "gh_rows_all_row_floats", "gh_stats_all_device", "gh_stats_all_block_doubles", "gh_step_rows_early",
     "gh_step_pack_rows", "gh_step_finish_overlap",
     "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
+    "gh_cent_create", "gh_cent_destroy", "gh_cent_last_error", "gh_cent_edge_count", "gh_cent_csr_device",
+    "gh_cent_set_memory_budget", "gh_cent_paths", "gh_cent_pagerank", "gh_spmv_adj_shift",
 ]
 
 
@@ -240,6 +242,24 @@ def load():
     L.gh_ic_set_memory_budget.restype = ctypes.c_int
     L.gh_ic_spread.argtypes = [vp, ctypes.c_double, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, i64, vp, vp]
     L.gh_ic_spread.restype = ctypes.c_int
+    L.gh_cent_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i64, vp]
+    L.gh_cent_create.restype = ctypes.c_int
+    L.gh_cent_destroy.argtypes = [vp]
+    L.gh_cent_destroy.restype = None
+    L.gh_cent_last_error.argtypes = [vp]
+    L.gh_cent_last_error.restype = ctypes.c_char_p
+    L.gh_cent_edge_count.argtypes = [vp]
+    L.gh_cent_edge_count.restype = i64
+    L.gh_cent_csr_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.gh_cent_csr_device.restype = ctypes.c_int
+    L.gh_cent_set_memory_budget.argtypes = [vp, i64]
+    L.gh_cent_set_memory_budget.restype = ctypes.c_int
+    L.gh_cent_paths.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.gh_cent_paths.restype = ctypes.c_int
+    L.gh_cent_pagerank.argtypes = [vp, ctypes.c_double, i32, ctypes.c_double, vp, ctypes.POINTER(i32)]
+    L.gh_cent_pagerank.restype = ctypes.c_int
+    L.gh_spmv_adj_shift.argtypes = [vp, i64, vp, vp, ctypes.c_double, vp, vp]
+    L.gh_spmv_adj_shift.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -627,6 +647,80 @@ class ICGraph:
         self._raise(self.lib.gh_ic_spread(self.handle, float(p), int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                           len(sets), ptr(offsets), ptr(verts), ptr(base), len(base), ptr(totals), ptr(trials)))
         return (totals, trials) if per_trial else totals
+
+
+class CentGraph:
+    """Thin RAII wrapper over a gh_cent_handle: shortest-path centralities, PageRank and the adjacency SpMV of one
+    undirected graph (include/graphem_hip.h)."""
+
+    def __init__(self, n, edges, device_id=0):
+        self.lib = load()
+        self.handle = ctypes.c_void_p()
+        self.n = int(n)
+        edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        st = self.lib.gh_cent_create(ctypes.byref(self.handle), int(device_id), self.n, edges.shape[0], ptr(edges))
+        if st != GH_OK:
+            self.handle = ctypes.c_void_p()
+            self._raise(st)
+        self.edges = int(self.lib.gh_cent_edge_count(self.handle))
+
+    def _raise(self, st):
+        if st == GH_OK:
+            return
+        msg = self.lib.gh_cent_last_error(self.handle if self.handle.value else None)
+        msg = msg.decode() if msg else f"gh_status {st}"
+        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self.lib.gh_cent_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-exception-caught
+            pass
+
+    def set_memory_budget(self, nbytes):
+        """Device bytes of path state a paths call may hold (0: the default, 1 GiB)."""
+        self._raise(self.lib.gh_cent_set_memory_budget(self.handle, int(nbytes)))
+
+    def paths(self, sources, betweenness=True, load=True, distances=True):
+        """One all-sources pass (gh_cent_paths): (betweenness (n,), load (n,), reached (S,), dist_sum (S,)); a part not
+        asked for is None.  Raw sums, unnormalised."""
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64).ravel())
+        if len(src) and (src.min() < 0 or src.max() >= self.n):
+            raise ValueError(f"source ids must lie in [0, {self.n})")
+        src = src.astype(np.int32)
+        bc = np.zeros(self.n) if betweenness else None
+        ld = np.zeros(self.n) if load else None
+        reached = np.zeros(len(src), dtype=np.int64) if distances else None
+        dsum = np.zeros(len(src), dtype=np.int64) if distances else None
+        self._raise(self.lib.gh_cent_paths(self.handle, len(src), ptr(src), ptr(bc), ptr(ld), ptr(reached), ptr(dsum)))
+        return bc, ld, reached, dsum
+
+    def pagerank(self, alpha, max_iter, tol):
+        """(x (n,), iterations): iterations = -1 when max_iter iterations did not converge (gh_cent_pagerank)."""
+        x = np.zeros(self.n)
+        its = ctypes.c_int32(0)
+        self._raise(self.lib.gh_cent_pagerank(self.handle, float(alpha), int(max_iter), float(tol), ptr(x), ctypes.byref(its)))
+        return x, int(its.value)
+
+    def csr_device(self):
+        """(indptr, indices) device pointers of the handle's symmetric CSR."""
+        ip, ix = ctypes.c_void_p(), ctypes.c_void_p()
+        self._raise(self.lib.gh_cent_csr_device(self.handle, ctypes.byref(ip), ctypes.byref(ix)))
+        return ip.value, ix.value
+
+    def spmv_shift(self, stream, x_ptr, y_ptr, c):
+        """y = A x + c x on device pointers, enqueued on `stream` (gh_spmv_adj_shift)."""
+        ip, ix = self.csr_device()
+        st = self.lib.gh_spmv_adj_shift(ctypes.c_void_p(stream), self.n, ctypes.c_void_p(ip), ctypes.c_void_p(ix), float(c),
+                                        ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr))
+        if st != GH_OK:
+            msg = self.lib.gh_cent_last_error(None)
+            raise RuntimeError(msg.decode() if msg else f"gh_status {st}")
 
 
 def knn_points(query, reference, k, device_id=0):

@@ -1,0 +1,618 @@
+// Centrality measures on the GPU (include/graphem_hip.h "centrality"; graphem-rapids_amd/centrality.py): shortest-path
+// betweenness (Brandes), load (Newman) and closeness from one all-sources pass, PageRank, and the adjacency SpMV of the
+// eigenvector solve.  Undirected, unweighted graphs; fp64 throughout, as networkx computes in Python floats.
+//
+// Paths.  A batch of B = 64 G sources; source j of the ordered list is lane j % 64 of group j / 64.  Per (vertex, source)
+// entry the state is source-fastest, [group][vertex][lane], so the wave that owns (v, g) reads a neighbour's row of 64
+// values as one contiguous 256 B (int32) or 512 B (double) load:
+//     dist (int32, -1 = unreached), sigma (double, shortest paths), npred (int32, shortest-path predecessors),
+//     delta (double, Brandes dependency), lam (double, Newman load dependency).
+// Per (v, g) words: vis (uint64, lanes that reached v; invalid lanes of a short last group preset), cur / nxt (uint64, lanes
+// whose BFS reached v at the previous / this level) and range (int2: first and last level any lane reached v at).
+//
+//   cent_init_kernel       dist, vis, cur, range of every (v, g); level-0 entries get sigma = 1.
+//   cent_fwd_kernel (L)    pull: a wave per (v, g) with unreached lanes; lane s sums sigma over the neighbours u whose
+//                          frontier word has bit s, counts them, and the lanes that found one set dist = L.  Writes its
+//                          next frontier word (0 included), so the ping-pong buffers need no clearing; sets flag[L] when
+//                          anything was reached.  A launch after the last level sees flag[L - 1] == 0 and returns.
+//   cent_bwd_kernel (L)    deepest level first, pull: lane s of (x, g) with dist = L sums over neighbours w at L + 1
+//                              delta[x] = sum sigma[x] * ((1 + delta[w]) / sigma[w])         (networkx _accumulate_basic)
+//                              lam[x]   = sum (1 + lam[w]) / npred[w]                         (networkx load._node_betweenness)
+//                          A neighbour's rows are loaded only when L + 1 lies in its level range.
+//   cent_vertex_sum_kernel out[v] += lane-tree sum of the 64 lanes' delta / lam (lanes with dist >= 1: the source itself
+//                          and unreached lanes add nothing), one group after the other in list order.
+//   cent_source_sum_kernel reached / dist_sum per source: integer sums, so the order of the atomics cannot matter.
+// Every (vertex, source) value is written by the one lane that owns it: no float atomics, and the result depends only on
+// the graph and the ordered source list -- not on the batch width (budget), nor on scheduling.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/graphem_hip.h"
+
+#define CENT_BLOCK 256
+#define CENT_MAX_BLOCKS 4096
+#define CENT_CHECK_EVERY 4            // forward levels between two host reads of the level flags
+#define CENT_DEFAULT_BUDGET (1ll << 30)
+#define CENT_SRC_CHUNK 1024           // vertices per workgroup of the per-source sums
+#define PR_BLOCK 256
+#define PR_MAX_BLOCKS 2048
+#define PR_CHECK_EVERY 8              // PageRank iterations between two host reads of the convergence flag
+
+namespace {
+
+struct CentLevel {
+    const int64_t *ptr; const int32_t *adj;
+    int32_t *dist, *npred;
+    double *sigma, *delta, *lam;
+    uint64_t *vis, *cur, *nxt;
+    int2 *range;
+    int32_t *flags;                 // flags[L] = 1: level L reached something
+    int64_t n, G;
+    int32_t level;
+};
+
+__device__ __forceinline__ int cent_lane() { return threadIdx.x & 63; }
+
+// (v, g) items, a wave per item
+#define CENT_WAVE_LOOP(items)                                                                                     \
+    for (int64_t it = (int64_t)blockIdx.x * (CENT_BLOCK / 64) + (threadIdx.x >> 6); it < (items);                \
+         it += (int64_t)gridDim.x * (CENT_BLOCK / 64))
+
+__global__ __launch_bounds__(CENT_BLOCK) void cent_init_kernel(CentLevel a, const int32_t *__restrict__ sources, int64_t n_src) {
+    const int lane = cent_lane();
+    CENT_WAVE_LOOP(a.G * a.n) {
+        const int64_t g = it / a.n, v = it - g * a.n;
+        const int64_t j = g * 64 + lane;
+        const bool valid = j < n_src;
+        const bool src = valid && sources[j] == v;
+        const int64_t e = it * 64 + lane;
+        a.dist[e] = src ? 0 : -1;
+        if (src) { a.sigma[e] = 1.0; a.npred[e] = 0; }
+        const uint64_t s = __ballot(src), inv = __ballot(!valid);
+        if (lane == 0) {
+            a.vis[it] = s | inv;
+            a.cur[it] = s;
+            a.range[it] = s ? make_int2(0, 0) : make_int2(INT32_MAX, -1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(CENT_BLOCK) void cent_fwd_kernel(CentLevel a) {
+    if (__hip_atomic_load(&a.flags[a.level - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+    const int lane = cent_lane();
+    CENT_WAVE_LOOP(a.G * a.n) {
+        const int64_t g = it / a.n, v = it - g * a.n;
+        const uint64_t need = ~a.vis[it];
+        uint64_t found = 0;
+        if (need) {
+            const uint64_t *curg = a.cur + g * a.n;
+            const double *sigg = a.sigma + g * a.n * 64;
+            double sig = 0.0;
+            int32_t np = 0;
+            const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
+            for (int64_t k = beg; k < end; ++k) {
+                const int32_t u = a.adj[k];
+                const uint64_t f = curg[u] & need;
+                if (f == 0) continue;
+                if ((f >> lane) & 1) { sig += sigg[(int64_t)u * 64 + lane]; ++np; }
+            }
+            found = __ballot(np > 0);
+            if (np > 0) {
+                const int64_t e = it * 64 + lane;
+                a.dist[e] = a.level;
+                a.sigma[e] = sig;
+                a.npred[e] = np;
+            }
+        }
+        if (lane == 0) {
+            a.nxt[it] = found;
+            if (found) {
+                a.vis[it] |= found;
+                int2 r = a.range[it];
+                r.x = min(r.x, a.level);
+                r.y = a.level;
+                a.range[it] = r;
+                if (__hip_atomic_load(&a.flags[a.level], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) a.flags[a.level] = 1;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(CENT_BLOCK) void cent_bwd_kernel(CentLevel a, int32_t want_delta, int32_t want_lam) {
+    const int lane = cent_lane();
+    const int32_t L = a.level;
+    CENT_WAVE_LOOP(a.G * a.n) {
+        const int2 r = a.range[it];
+        if (L < r.x || L > r.y) continue;
+        const int64_t g = it / a.n, v = it - g * a.n;
+        const int64_t e = it * 64 + lane;
+        const bool mine = a.dist[e] == L;
+        if (__ballot(mine) == 0) continue;
+        const double sx = mine ? a.sigma[e] : 0.0;
+        double dacc = 0.0, lacc = 0.0;
+        const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
+        for (int64_t k = beg; k < end; ++k) {
+            const int64_t w = g * a.n + a.adj[k];
+            const int2 rw = a.range[w];
+            if (L + 1 < rw.x || L + 1 > rw.y) continue;
+            const int64_t ew = w * 64 + lane;
+            if (mine && a.dist[ew] == L + 1) {
+                if (want_delta) dacc += sx * ((1.0 + a.delta[ew]) / a.sigma[ew]);
+                if (want_lam) lacc += (1.0 + a.lam[ew]) / (double)a.npred[ew];
+            }
+        }
+        if (mine) {
+            if (want_delta) a.delta[e] = dacc;
+            if (want_lam) a.lam[e] = lacc;
+        }
+    }
+}
+
+__device__ __forceinline__ double cent_wave_sum(double x) {   // fixed butterfly; lane 0's value is used
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+__global__ __launch_bounds__(CENT_BLOCK) void cent_vertex_sum_kernel(CentLevel a, double *bc, double *ld) {
+    const int lane = cent_lane();
+    CENT_WAVE_LOOP(a.n) {
+        const int64_t v = it;
+        double sb = bc ? bc[v] : 0.0, sl = ld ? ld[v] : 0.0;
+        for (int64_t g = 0; g < a.G; ++g) {
+            const int64_t e = (g * a.n + v) * 64 + lane;
+            const bool in = a.dist[e] >= 1;
+            if (bc) { const double t = cent_wave_sum(in ? a.delta[e] : 0.0); sb += t; }
+            if (ld) { const double t = cent_wave_sum(in ? a.lam[e] : 0.0); sl += t; }
+        }
+        if (lane == 0) {
+            if (bc) bc[v] = sb;
+            if (ld) ld[v] = sl;
+        }
+    }
+}
+
+// grid (chunks, G): lane s of every wave sums its source's reached count and distances over the chunk's vertices
+__global__ __launch_bounds__(CENT_BLOCK) void cent_source_sum_kernel(CentLevel a, unsigned long long *reached,
+                                                                    unsigned long long *dist_sum) {
+    const int lane = cent_lane();
+    const int64_t g = blockIdx.y;
+    const int64_t v0 = (int64_t)blockIdx.x * CENT_SRC_CHUNK, v1 = min(a.n, v0 + CENT_SRC_CHUNK);
+    unsigned long long cnt = 0, sum = 0;
+    for (int64_t v = v0 + (threadIdx.x >> 6); v < v1; v += CENT_BLOCK / 64) {
+        const int32_t d = a.dist[(g * a.n + v) * 64 + lane];
+        if (d >= 0) { ++cnt; sum += (unsigned long long)d; }
+    }
+    if (cnt) {
+        atomicAdd(&reached[g * 64 + lane], cnt);
+        atomicAdd(&dist_sum[g * 64 + lane], sum);
+    }
+}
+
+// ---- PageRank: networkx _pagerank_scipy on the device ---------------------------------------------------------------
+struct PrState {
+    double dsum;      // sum of x over the dangling vertices, of the current iterate
+    int32_t done;     // 1 once converged or out of iterations
+    int32_t iters;    // iteration that converged; -1: max_iter reached without
+};
+
+__device__ __forceinline__ double pr_block_sum(double v, double *red) {   // fixed order; thread 0 gets the sum
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+    __syncthreads();
+    return s;
+}
+
+// x0 = 1/N; partial sums of its dangling entries
+__global__ __launch_bounds__(PR_BLOCK) void pr_init_kernel(int64_t n, const int64_t *__restrict__ ptr, double *x, double *dpart) {
+    __shared__ double red[PR_BLOCK / 64];
+    double d = 0.0;
+    const double x0 = 1.0 / (double)n;
+    for (int64_t i = (int64_t)blockIdx.x * PR_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * PR_BLOCK) {
+        x[i] = x0;
+        if (ptr[i + 1] == ptr[i]) d += x0;
+    }
+    const double s = pr_block_sum(d, red);
+    if (threadIdx.x == 0) dpart[blockIdx.x] = s;
+}
+
+// y = alpha (x A_rownorm + dsum / N) + (1 - alpha) / N; 8 lanes per row; partial |y - x| and dangling sums per block
+__global__ __launch_bounds__(PR_BLOCK) void pr_step_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ adj,
+                                                          const double *__restrict__ inv_deg, double alpha,
+                                                          const PrState *st, const double *__restrict__ x, double *__restrict__ y,
+                                                          double *epart, double *dpart) {
+    __shared__ double red[PR_BLOCK / 64];
+    if (st->done) return;
+    const double pN = 1.0 / (double)n, dsum = st->dsum;
+    const int sub = threadIdx.x & 7;
+    double err = 0.0, dang = 0.0;
+    const int64_t rows_per = (int64_t)gridDim.x * (PR_BLOCK / 8);
+    const int64_t rounds = (n + rows_per - 1) / rows_per;
+    for (int64_t q = 0; q < rounds; ++q) {   // every thread runs the same rounds (the shuffles need the whole wave)
+        const int64_t row = q * rows_per + (int64_t)blockIdx.x * (PR_BLOCK / 8) + (threadIdx.x >> 3);
+        int64_t beg = 0, end = 0;
+        if (row < n) { beg = ptr[row]; end = ptr[row + 1]; }
+        double acc = 0.0;
+        for (int64_t j = beg + sub; j < end; j += 8) {
+            const int32_t c = adj[j];
+            acc += x[c] * inv_deg[c];
+        }
+        acc += __shfl_xor(acc, 1, 64);
+        acc += __shfl_xor(acc, 2, 64);
+        acc += __shfl_xor(acc, 4, 64);
+        if (row < n && sub == 0) {
+            const double yi = alpha * (acc + dsum * pN) + (1.0 - alpha) * pN;
+            y[row] = yi;
+            err += fabs(yi - x[row]);
+            if (end == beg) dang += yi;
+        }
+    }
+    const double se = pr_block_sum(err, red);
+    const double sd = pr_block_sum(dang, red);
+    if (threadIdx.x == 0) { epart[blockIdx.x] = se; dpart[blockIdx.x] = sd; }
+}
+
+// one workgroup: the L1 change and the next dangling sum; the convergence test of iteration `iter` (0: the start vector)
+__global__ __launch_bounds__(PR_BLOCK) void pr_check_kernel(int32_t nparts, const double *epart, const double *dpart, double ntol,
+                                                           int32_t iter, int32_t max_iter, PrState *st) {
+    __shared__ double red[PR_BLOCK / 64];
+    if (st->done) return;
+    double e = 0.0, d = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += PR_BLOCK) {
+        if (iter > 0) e += epart[i];
+        d += dpart[i];
+    }
+    const double se = pr_block_sum(e, red);
+    const double sd = pr_block_sum(d, red);
+    if (threadIdx.x == 0) {
+        st->dsum = sd;
+        if (iter > 0 && se < ntol) { st->done = 1; st->iters = iter; }
+        else if (iter >= max_iter) { st->done = 1; st->iters = -1; }
+    }
+}
+
+// y = A x + c x, A the 0/1 adjacency; 8 lanes per row
+__global__ __launch_bounds__(256) void spmv_adj_shift_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ adj,
+                                                            double c, const double *__restrict__ x, double *__restrict__ y) {
+    const int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3;
+    const int sub = threadIdx.x & 7;
+    double acc = 0.0;
+    int64_t beg = 0, end = 0;
+    if (row < n) { beg = ptr[row]; end = ptr[row + 1]; }
+    for (int64_t j = beg + sub; j < end; j += 8) acc += x[adj[j]];
+    acc += __shfl_xor(acc, 1, 64);
+    acc += __shfl_xor(acc, 2, 64);
+    acc += __shfl_xor(acc, 4, 64);
+    if (row < n && sub == 0) y[row] = acc + c * x[row];
+}
+
+inline int cent_blocks(int64_t waves) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(CENT_MAX_BLOCKS, (waves + CENT_BLOCK / 64 - 1) / (CENT_BLOCK / 64)));
+}
+
+}  // namespace
+
+struct gh_cent {
+    int device = 0;
+    int64_t n = 0, edges = 0;
+    hipStream_t stream = nullptr;
+    int64_t *d_ptr = nullptr;
+    int32_t *d_adj = nullptr;
+    double *d_inv_deg = nullptr;
+    int64_t budget = CENT_DEFAULT_BUDGET;
+    // path state for G groups, grown on demand
+    int64_t cap_groups = 0;
+    int32_t *d_dist = nullptr, *d_npred = nullptr, *d_flags = nullptr, *d_src = nullptr;
+    double *d_sigma = nullptr, *d_delta = nullptr, *d_lam = nullptr;
+    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
+    int2 *d_range = nullptr;
+    std::string err;
+};
+
+static thread_local std::string g_cent_error;
+
+namespace {
+
+void cent_free_state(gh_cent *h) {
+    for (void *p : {(void *)h->d_dist, (void *)h->d_npred, (void *)h->d_flags, (void *)h->d_src, (void *)h->d_sigma,
+                    (void *)h->d_delta, (void *)h->d_lam, (void *)h->d_vis, (void *)h->d_fa, (void *)h->d_fb, (void *)h->d_range})
+        if (p) (void)hipFree(p);
+    h->d_dist = h->d_npred = h->d_flags = h->d_src = nullptr;
+    h->d_sigma = h->d_delta = h->d_lam = nullptr;
+    h->d_vis = h->d_fa = h->d_fb = nullptr;
+    h->d_range = nullptr;
+    h->cap_groups = 0;
+}
+
+// device bytes of path state per 64-source group (the budget counts these)
+int64_t cent_bytes_per_group(int64_t n) { return n * (64 * (4 + 8 + 4 + 8 + 8) + 3 * 8 + 8); }
+
+gh_status cent_reserve(gh_cent *h, int64_t G) {
+    if (G <= h->cap_groups) return GH_OK;
+    cent_free_state(h);
+    const int64_t ent = G * h->n * 64, words = G * h->n;
+    auto alloc = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess; };
+    if (!alloc((void **)&h->d_dist, 4 * ent) || !alloc((void **)&h->d_npred, 4 * ent) || !alloc((void **)&h->d_sigma, 8 * ent) ||
+        !alloc((void **)&h->d_delta, 8 * ent) || !alloc((void **)&h->d_lam, 8 * ent) || !alloc((void **)&h->d_vis, 8 * words) ||
+        !alloc((void **)&h->d_fa, 8 * words) || !alloc((void **)&h->d_fb, 8 * words) || !alloc((void **)&h->d_range, 8 * words) ||
+        !alloc((void **)&h->d_flags, 4 * (h->n + 2)) || !alloc((void **)&h->d_src, 4 * 64 * G)) {
+        cent_free_state(h);
+        h->err = "hipMalloc failed for " + std::to_string(G) + " source groups of path state";
+        return GH_ERR_NOMEM;
+    }
+    h->cap_groups = G;
+    return GH_OK;
+}
+
+#define CENT_HIP(call)                                                                 \
+    do {                                                                               \
+        const hipError_t e_ = (call);                                                  \
+        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
+    } while (0)
+
+// One batch of ns <= 64 G sources: forward levels, backward levels, sums into the device outputs.
+gh_status cent_run_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, double *d_bc, double *d_ld,
+                         unsigned long long *d_reached, unsigned long long *d_dsum) {
+    const int64_t n = h->n;
+    CentLevel a{};
+    a.ptr = h->d_ptr; a.adj = h->d_adj;
+    a.dist = h->d_dist; a.npred = h->d_npred; a.sigma = h->d_sigma; a.delta = h->d_delta; a.lam = h->d_lam;
+    a.vis = h->d_vis; a.range = h->d_range; a.flags = h->d_flags;
+    a.n = n; a.G = G;
+    CENT_HIP(hipMemcpyAsync(h->d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
+    CENT_HIP(hipMemsetAsync(h->d_flags, 0, 4 * (n + 2), h->stream));
+    const int32_t one = 1;
+    CENT_HIP(hipMemcpyAsync(h->d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
+    const int grid = cent_blocks(G * n);
+    a.cur = h->d_fa;
+    cent_init_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a, h->d_src, ns);
+    CENT_HIP(hipGetLastError());
+    // forward: level L can reach something only while L <= n - 1
+    int32_t maxd = 0;
+    std::vector<int32_t> fl(CENT_CHECK_EVERY);
+    for (int64_t L = 1, checked = 0; L <= n - 1; ++L) {
+        a.level = (int32_t)L;
+        a.cur = (L & 1) ? h->d_fa : h->d_fb;
+        a.nxt = (L & 1) ? h->d_fb : h->d_fa;
+        cent_fwd_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a);
+        CENT_HIP(hipGetLastError());
+        if (L % CENT_CHECK_EVERY == 0 || L == n - 1) {
+            const int64_t cnt = L - checked;
+            CENT_HIP(hipMemcpyAsync(fl.data(), h->d_flags + checked + 1, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
+            CENT_HIP(hipStreamSynchronize(h->stream));
+            bool stop = false;
+            for (int64_t i = 0; i < cnt; ++i) {
+                if (fl[i]) maxd = (int32_t)(checked + 1 + i);
+                else { stop = true; break; }
+            }
+            checked = L;
+            if (stop) break;
+        }
+    }
+    const int want_delta = d_bc != nullptr, want_lam = d_ld != nullptr;
+    if (want_delta || want_lam) {
+        for (int32_t L = maxd; L >= 1; --L) {
+            a.level = L;
+            cent_bwd_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a, want_delta, want_lam);
+        }
+        cent_vertex_sum_kernel<<<dim3(cent_blocks(n)), dim3(CENT_BLOCK), 0, h->stream>>>(a, d_bc, d_ld);
+        CENT_HIP(hipGetLastError());
+    }
+    if (d_reached) {
+        cent_source_sum_kernel<<<dim3((unsigned)((n + CENT_SRC_CHUNK - 1) / CENT_SRC_CHUNK), (unsigned)G), dim3(CENT_BLOCK), 0,
+                                 h->stream>>>(a, d_reached, d_dsum);
+        CENT_HIP(hipGetLastError());
+    }
+    return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t n, int64_t n_edges, const int32_t *edges) {
+    auto fail = [&](gh_status st, const std::string &msg) { g_cent_error = msg; return st; };
+    if (!out) return fail(GH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n < 1 || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "n must be in [1, 2^31)");
+    if (n_edges < 0 || (n_edges > 0 && !edges)) return fail(GH_ERR_INVALID, "bad edge list");
+    // canonical edge set: self-loops dropped, duplicates merged, (min, max)
+    std::vector<uint64_t> key;
+    key.reserve((size_t)n_edges);
+    for (int64_t i = 0; i < n_edges; ++i) {
+        const int64_t u = edges[2 * i], v = edges[2 * i + 1];
+        if (u < 0 || u >= n || v < 0 || v >= n)
+            return fail(GH_ERR_INVALID, "edge " + std::to_string(i) + " has a vertex id outside [0, n)");
+        if (u == v) continue;
+        key.push_back(((uint64_t)std::min(u, v) << 32) | (uint64_t)std::max(u, v));
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    // symmetric CSR, neighbours ascending
+    std::vector<int64_t> ptr((size_t)n + 1, 0);
+    for (uint64_t k : key) { ++ptr[(k >> 32) + 1]; ++ptr[(k & 0xFFFFFFFFu) + 1]; }
+    for (int64_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+    std::vector<int32_t> adj((size_t)ptr[n]);
+    {
+        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+        for (uint64_t k : key) adj[fill[k >> 32]++] = (int32_t)(k & 0xFFFFFFFFu);
+        for (uint64_t k : key) adj[fill[k & 0xFFFFFFFFu]++] = (int32_t)(k >> 32);
+        for (int64_t i = 0; i < n; ++i) std::sort(adj.begin() + ptr[i], adj.begin() + ptr[i + 1]);
+    }
+    std::vector<double> inv_deg((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t d = ptr[i + 1] - ptr[i];
+        inv_deg[i] = d ? 1.0 / (double)d : 0.0;
+    }
+    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
+    gh_cent *h = new gh_cent();
+    h->device = device_id;
+    h->n = n;
+    h->edges = (int64_t)key.size();
+    auto bail = [&](gh_status st, const std::string &msg) { gh_cent_destroy(h); return fail(st, msg); };
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(GH_ERR_HIP, "hipStreamCreate failed");
+    if (hipMalloc((void **)&h->d_ptr, 8 * ptr.size()) != hipSuccess ||
+        hipMalloc((void **)&h->d_adj, std::max<size_t>(4 * adj.size(), 4)) != hipSuccess ||
+        hipMalloc((void **)&h->d_inv_deg, 8 * inv_deg.size()) != hipSuccess)
+        return bail(GH_ERR_NOMEM, "hipMalloc failed");
+    if (hipMemcpy(h->d_ptr, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        (!adj.empty() && hipMemcpy(h->d_adj, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(h->d_inv_deg, inv_deg.data(), 8 * inv_deg.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return bail(GH_ERR_HIP, "upload failed");
+    *out = h;
+    return GH_OK;
+}
+
+extern "C" void gh_cent_destroy(gh_cent_handle h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    cent_free_state(h);
+    if (h->d_ptr) (void)hipFree(h->d_ptr);
+    if (h->d_adj) (void)hipFree(h->d_adj);
+    if (h->d_inv_deg) (void)hipFree(h->d_inv_deg);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+extern "C" const char *gh_cent_last_error(gh_cent_handle h) { return h ? h->err.c_str() : g_cent_error.c_str(); }
+
+extern "C" int64_t gh_cent_edge_count(gh_cent_handle h) { return h ? h->edges : -1; }
+
+extern "C" gh_status gh_cent_csr_device(gh_cent_handle h, const int64_t **indptr, const int32_t **indices) {
+    if (!h || !indptr || !indices) return GH_ERR_INVALID;
+    *indptr = h->d_ptr;
+    *indices = h->d_adj;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_cent_set_memory_budget(gh_cent_handle h, int64_t bytes) {
+    if (!h) return GH_ERR_INVALID;
+    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
+    h->budget = bytes ? bytes : CENT_DEFAULT_BUDGET;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_cent_paths(gh_cent_handle h, int64_t n_sources, const int32_t *sources, double *betweenness,
+                                   double *load, int64_t *reached, int64_t *dist_sum) {
+    if (!h) { g_cent_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (n_sources < 0 || (n_sources > 0 && !sources)) return fail(GH_ERR_INVALID, "bad source list");
+    if ((reached == nullptr) != (dist_sum == nullptr)) return fail(GH_ERR_INVALID, "reached and dist_sum go together");
+    for (int64_t i = 0; i < n_sources; ++i)
+        if (sources[i] < 0 || sources[i] >= h->n) return fail(GH_ERR_INVALID, "source id outside [0, n)");
+    const int64_t n = h->n;
+    if (betweenness) std::fill(betweenness, betweenness + n, 0.0);
+    if (load) std::fill(load, load + n, 0.0);
+    if (reached) { std::fill(reached, reached + n_sources, (int64_t)0); std::fill(dist_sum, dist_sum + n_sources, (int64_t)0); }
+    if (n_sources == 0 || (!betweenness && !load && !reached)) return GH_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    const int64_t groups = (n_sources + 63) / 64;
+    int64_t G = std::max<int64_t>(1, h->budget / cent_bytes_per_group(n));
+    G = std::min<int64_t>({G, groups, (int64_t)65535});   // 65535: grid.y of the per-source sums
+    gh_status st = cent_reserve(h, G);
+    if (st != GH_OK) return st;
+    double *d_bc = nullptr, *d_ld = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    auto cleanup = [&]() {
+        for (void *p : {(void *)d_bc, (void *)d_ld, (void *)d_cnt}) if (p) (void)hipFree(p);
+    };
+    if ((betweenness && hipMalloc((void **)&d_bc, 8 * n) != hipSuccess) || (load && hipMalloc((void **)&d_ld, 8 * n) != hipSuccess) ||
+        (reached && hipMalloc((void **)&d_cnt, 16 * groups * 64) != hipSuccess)) {
+        cleanup();
+        return fail(GH_ERR_NOMEM, "hipMalloc failed for the outputs");
+    }
+    st = GH_OK;
+    do {
+        if (d_bc && hipMemsetAsync(d_bc, 0, 8 * n, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
+        if (d_ld && hipMemsetAsync(d_ld, 0, 8 * n, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
+        if (d_cnt && hipMemsetAsync(d_cnt, 0, 16 * groups * 64, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
+        for (int64_t g0 = 0; g0 < groups && st == GH_OK; g0 += G) {
+            const int64_t gb = std::min(G, groups - g0);
+            const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
+            st = cent_run_batch(h, gb, sources + 64 * g0, ns, d_bc, d_ld, d_cnt ? d_cnt + 64 * g0 : nullptr,
+                                d_cnt ? d_cnt + 64 * groups + 64 * g0 : nullptr);
+        }
+        if (st != GH_OK) break;
+        if (d_bc && hipMemcpyAsync(betweenness, d_bc, 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+        if (d_ld && hipMemcpyAsync(load, d_ld, 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+        if (d_cnt) {
+            if (hipMemcpyAsync(reached, d_cnt, 8 * n_sources, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipMemcpyAsync(dist_sum, d_cnt + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+                st = fail(GH_ERR_HIP, "copy failed");
+                break;
+            }
+        }
+        if (hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipStreamSynchronize failed"); break; }
+    } while (false);
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
+    cleanup();
+    return st;
+}
+
+extern "C" gh_status gh_cent_pagerank(gh_cent_handle h, double alpha, int32_t max_iter, double tol, double *x, int32_t *iterations) {
+    if (!h) { g_cent_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(GH_ERR_INVALID, "alpha must be in [0, 1]");
+    if (max_iter < 1) return fail(GH_ERR_INVALID, "max_iter must be >= 1");
+    if (!(tol >= 0.0)) return fail(GH_ERR_INVALID, "tol must be >= 0");
+    if (!x || !iterations) return fail(GH_ERR_INVALID, "x and iterations must not be NULL");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    const int64_t n = h->n;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(PR_MAX_BLOCKS, (n + PR_BLOCK / 8 - 1) / (PR_BLOCK / 8)));
+    double *d_x = nullptr, *d_part = nullptr;
+    PrState *d_st = nullptr;
+    if (hipMalloc((void **)&d_x, 16 * n) != hipSuccess || hipMalloc((void **)&d_part, 16 * (size_t)nb) != hipSuccess ||
+        hipMalloc((void **)&d_st, sizeof(PrState)) != hipSuccess) {
+        for (void *p : {(void *)d_x, (void *)d_part, (void *)d_st}) if (p) (void)hipFree(p);
+        return fail(GH_ERR_NOMEM, "hipMalloc failed");
+    }
+    double *xb[2] = {d_x, d_x + n};
+    double *epart = d_part, *dpart = d_part + nb;
+    gh_status st = GH_OK;
+    PrState hs{0.0, 0, 0};
+    do {
+        if (hipMemcpyAsync(d_st, &hs, sizeof(hs), hipMemcpyHostToDevice, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+        pr_init_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr, xb[0], dpart);
+        pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, 0, max_iter, d_st);
+        for (int32_t it = 1; it <= max_iter; ++it) {
+            pr_step_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr, h->d_adj, h->d_inv_deg, alpha, d_st,
+                                                                        xb[(it - 1) & 1], xb[it & 1], epart, dpart);
+            pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, it, max_iter, d_st);
+            if (hipGetLastError() != hipSuccess) { st = fail(GH_ERR_HIP, "PageRank launch failed"); break; }
+            if (it % PR_CHECK_EVERY == 0 || it == max_iter) {
+                if (hipMemcpyAsync(&hs, d_st, sizeof(hs), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                    hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+                if (hs.done) break;
+            }
+        }
+        if (st != GH_OK) break;
+        const int32_t last = hs.iters > 0 ? hs.iters : max_iter;
+        if (hipMemcpyAsync(x, xb[last & 1], 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+        *iterations = hs.iters;
+    } while (false);
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
+    for (void *p : {(void *)d_x, (void *)d_part, (void *)d_st}) (void)hipFree(p);
+    return st;
+}
+
+extern "C" gh_status gh_spmv_adj_shift(void *hip_stream, int64_t n, const int64_t *indptr, const int32_t *indices, double c,
+                                       const double *x, double *y) {
+    if (n < 0 || (n > 0 && (!indptr || !indices || !x || !y))) { g_cent_error = "bad SpMV arguments"; return GH_ERR_INVALID; }
+    if (n == 0) return GH_OK;
+    const int64_t threads = 8 * n;
+    spmv_adj_shift_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream>>>(n, indptr, indices, c, x, y);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_cent_error = std::string("spmv_adj_shift_kernel: ") + hipGetErrorString(e); return GH_ERR_HIP; }
+    return GH_OK;
+}

@@ -499,6 +499,55 @@ gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_tri
                        const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                        int64_t *totals, int32_t *per_trial);
 
+/* ---- centrality (reference benchmark.py: run_benchmark, benchmark_correlations; graphem-rapids_amd/centrality.py) ----
+ * A handle over one undirected, unweighted graph, independent of the layout engine.  Self-loops are dropped and
+ * duplicate edges merged.  Everything is fp64.
+ *
+ * Shortest paths from a source s (breadth-first levels): d(s, v) the hop distance, sigma_s(v) the number of shortest
+ * s-v paths (a double, as networkx counts), pred_s(v) the neighbours u of v with d(s, u) = d(s, v) - 1.  Over the
+ * successors w of v (v in pred_s(w)):
+ *     delta_s(v)  = sum_w sigma_s(v) * ((1 + delta_s(w)) / sigma_s(w))     Brandes dependency (betweenness)
+ *     lambda_s(v) = sum_w (1 + lambda_s(w)) / |pred_s(w)|                   Newman load dependency (load centrality)
+ * Sources are taken in list order, 64 to a group (source j: group j / 64).  The per-vertex sums are formed as: for each
+ * group in order, a fixed lane-tree sum over its 64 sources, added to the output with one fp64 add.  Results therefore
+ * depend only on the graph and the ordered source list, bit for bit: not on the memory budget, edge order, duplicate
+ * edges, self-loops, nor run-to-run scheduling. */
+typedef struct gh_cent *gh_cent_handle;
+
+/* edges: (n_edges, 2) int32 host array, vertex ids in [0, n).  On failure *out = NULL and gh_cent_last_error(NULL) has
+ * the message. */
+gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t n, int64_t n_edges, const int32_t *edges);
+void gh_cent_destroy(gh_cent_handle h);
+const char *gh_cent_last_error(gh_cent_handle h);
+/* Edges after self-loops and duplicates went. */
+int64_t gh_cent_edge_count(gh_cent_handle h);
+/* The handle's symmetric CSR on the device (neighbours ascending): indptr (n + 1) int64, indices int32.  Valid until
+ * gh_cent_destroy; for gh_spmv_adj_shift. */
+gh_status gh_cent_csr_device(gh_cent_handle h, const int64_t **indptr, const int32_t **indices);
+/* Device bytes of path state gh_cent_paths may hold: n * (32 * 64 + 32) bytes per 64-source group processed at once, at
+ * least one group.  0 restores the default, 1 GiB.  GH_ERR_INVALID for a negative value.  Results do not depend on it. */
+gh_status gh_cent_set_memory_budget(gh_cent_handle h, int64_t bytes);
+/* One all-sources pass over sources[0 .. n_sources) (ids in [0, n); duplicates allowed).
+ * betweenness (NULL or host double[n]) = sum over the sources s != v of delta_s(v); load (NULL or host double[n]) =
+ * sum over the sources s != v of lambda_s(v): raw sums, unnormalised (networkx _rescale / newman_betweenness_centrality
+ * scale on the host).  reached, dist_sum (both NULL or both host int64[n_sources]): vertices reached from source j (the
+ * source included) and the sum of their distances -- closeness on the host.  GH_ERR_INVALID for an id outside [0, n).
+ * Blocking. */
+gh_status gh_cent_paths(gh_cent_handle h, int64_t n_sources, const int32_t *sources, double *betweenness, double *load,
+                        int64_t *reached, int64_t *dist_sum);
+/* networkx _pagerank_scipy, uniform personalisation: x0 = 1 / N;  x <- alpha (x A_rownorm + (sum of x over the vertices of
+ * degree 0) / N) + (1 - alpha) / N;  stops at the first iteration whose L1 change is < N * tol.  x: host double[n], the
+ * result; *iterations = that iteration, or -1 when max_iter iterations did not converge (x then holds the last
+ * iterate).  The convergence test runs on the device; the host reads its flag every 8 iterations.  GH_ERR_INVALID for
+ * alpha outside [0, 1], max_iter < 1, tol < 0.  Blocking. */
+gh_status gh_cent_pagerank(gh_cent_handle h, double alpha, int32_t max_iter, double tol, double *x, int32_t *iterations);
+/* y = A x + c x for the 0/1 adjacency A in CSR form (e.g. gh_cent_csr_device): the operator of the eigenvector
+ * centrality solve (the shift c > 0 separates the Perron root from -lambda_max on a bipartite graph).  All pointers are
+ * DEVICE pointers; fp64; asynchronous on hip_stream (NULL = default stream).  gh_cent_last_error(NULL) has the message
+ * of a failed call. */
+gh_status gh_spmv_adj_shift(void *hip_stream, int64_t n, const int64_t *indptr, const int32_t *indices, double c,
+                            const double *x, double *y);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
