@@ -91,9 +91,10 @@ static gh_status reject_f64(gh_engine *h, const char *what) {
 static void free_all(gh_engine *h) {
     gh_f64_free(h);
     gh_ivf_free(h);
-    void *ptrs[] = {h->d_edges, h->d_rowptr, h->d_adj, h->d_pos, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_new_own : (void *)h->d_new, h->d_gbuf, h->d_rows_all, h->d_rows_pk, h->d_stats_all, h->d_tmpF, h->d_tmpF2, h->d_io, h->d_acc,
+    const bool repointed = h->layout == GH_LAYOUT_GATHERED || h->layout == GH_LAYOUT_OVERLAP;   // d_new / d_stats: blocks of a layout's buffers
+    void *ptrs[] = {h->d_edges, h->d_rowptr, h->d_adj, h->d_pos, repointed ? (void *)h->d_new_own : (void *)h->d_new, h->d_gbuf, h->d_rows_all, h->d_rows_pk, h->d_stats_all, h->d_tmpF, h->d_tmpF2, h->d_io, h->d_acc,
                     h->d_tflag, h->d_touched, h->d_tcount, h->d_sampled, h->d_q, h->d_qscan, h->d_qA, h->d_qexact, h->d_order, h->d_long_rows, h->d_long_ownptr, h->d_long_ownadj, h->d_long_eptr, h->d_long_erow, h->d_long_terms, h->d_own_long, h->d_cand, h->d_cnt,
-                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_qcell, h->d_qc_flag, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_stats_comb, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, (h->d_gbuf || h->d_rows_all) ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
+                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_qcell, h->d_qc_flag, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, repointed ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_ring) (void)hipHostFree(h->h_ring);
@@ -394,7 +395,7 @@ static bool whole_graph(gh_engine *h) {
 // gh_step / gh_run / the per-phase entry points merge with world = 1 and normalise with the own rows'
 // statistics: on a row partition that would silently corrupt the positions.
 static gh_status check_whole(gh_engine *h, const char *what) {
-    if (whole_graph(h) && !h->d_gbuf && !h->g_world) return GH_OK;
+    if (whole_graph(h) && h->layout == GH_LAYOUT_NONE) return GH_OK;
     h->err = std::string(what) + " needs the whole graph on one rank; a partitioned engine runs gh_step_begin / "
              "gh_step_merge / gh_step_finish_gathered (or gh_run_partitioned)";
     return GH_ERR_INVALID;
@@ -431,7 +432,7 @@ static gh_status step_begin(gh_engine *h, bool fuse_intersect) {
     GH_TRY(step_begin_launches(h, fuse_intersect));
     // form D: new0 = pos + Fs of the own rows is in their block -- written by the fused kernel, or (a rank too small for it;
     // every rank must send at the same point of the iteration) by a launch of its own -- and may travel now
-    if (h->overlap) {
+    if (h->layout == GH_LAYOUT_OVERLAP) {
         if (!h->new0_ready) GH_TRY(gh_launch_new0(h));
         h->rows_early = true;
     }
@@ -480,7 +481,7 @@ static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world) {
 // then also runs that iteration's KNN set-up (gh_launch_normalise); gh_knn_prepare falls back to its own kernel when the
 // next step turns out different.
 static gh_status step_finish(gh_engine *h, const gh_ids *next) {
-    const bool presetup = next && h->rows == h->n && !h->d_gbuf && gh_knn_scan_path(h) &&
+    const bool presetup = next && h->rows == h->n && h->layout != GH_LAYOUT_GATHERED && gh_knn_scan_path(h) &&
                           (h->fused_scan || gh_grid_path(h) || gh_ivf_path(h)) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
     GH_TRY(gh_launch_normalise(h, true, presetup ? next : nullptr));  // also zeroes what the intersection phase touched
     h->iter += 1;
@@ -817,7 +818,7 @@ static gh_status check_layout(gh_engine *h, const char *name, const char *what, 
         h->err = std::string(what) + " does not match the engine's row partition";
         return GH_ERR_INVALID;
     }
-    if (h->d_gbuf || h->g_world) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_NONE) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
     return GH_OK;
 }
 
@@ -832,17 +833,18 @@ extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, 
     h->d_new = reinterpret_cast<float *>(h->d_gbuf + rank * slot);
     h->d_stats = reinterpret_cast<double *>(h->d_gbuf + rank * slot + chunk * h->LD * (int64_t)sizeof(float));
     h->g_slot = slot; h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
+    h->layout = GH_LAYOUT_GATHERED;
     return GH_OK;
 }
 extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
     GH_TRY(check_layout(h, "gh_rank_layout", "rank layout", world, rank, chunk, true));
-    GH_TRY(dev_alloc(h, &h->d_stats_comb, (size_t)2 * h->LD, true));
     // fewer components than the row stride (3 of 4, 5..7 of 8, 9..15 of 16): the finished blocks travel unpadded
     if (h->D < h->LD && world > 1) {
         GH_TRY(dev_alloc(h, &h->d_rows_packed, (size_t)world * chunk * h->D, true));
         h->packed_exchange = h->n >= ((int64_t)1 << 21);
     }
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
+    h->layout = GH_LAYOUT_RANK;
     return GH_OK;
 }
 // Form D: form B's finish (every rank normalises all n rows from the gathered un-normalised rows) with the big collective
@@ -865,25 +867,26 @@ extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank,
     h->d_new = h->d_rows_all + (size_t)rank * chunk * h->LD;
     h->d_stats = h->d_stats_all + (size_t)rank * (size_t)h->stats_block;
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
-    h->overlap = true;
+    h->layout = GH_LAYOUT_OVERLAP;
     return GH_OK;
 }
-extern "C" float *gh_rows_all_device(gh_handle h) { return !h || !h->overlap ? nullptr : h->d_rows_pk ? h->d_rows_pk : h->d_rows_all; }
-extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || !h->overlap ? 0 : h->d_rows_pk ? h->D : h->LD; }
-extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->overlap ? h->d_stats_all : nullptr; }
-extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->overlap ? h->stats_block : 0; }
-extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->overlap && h->rows_early ? 1 : 0; }
+extern "C" float *gh_rows_all_device(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? nullptr : h->d_rows_pk ? h->d_rows_pk : h->d_rows_all; }
+extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? 0 : h->d_rows_pk ? h->D : h->LD; }
+extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->d_stats_all : nullptr; }
+extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->stats_block : 0; }
+extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP && h->rows_early ? 1 : 0; }
 extern "C" gh_status gh_step_pack_rows(gh_handle h, void *hip_stream, int32_t use_engine_stream) {
     GH_TRY(check_handle(h));
-    if (!h->overlap) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
     return gh_launch_pack_rows(h, use_engine_stream ? h->stream : reinterpret_cast<hipStream_t>(hip_stream));
 }
 extern "C" gh_status gh_step_finish_overlap(gh_handle h) {
     GH_TRY(check_handle(h));
-    if (!h->overlap) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
     GH_TRY(gh_launch_patch_rows(h));
     const gh_ids own = gh_own_ids(h);
-    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? &own : nullptr));
+    // (the patch launch has zeroed the accumulators of a step whose rows went early)
+    GH_TRY(gh_launch_normalise(h, !h->rows_early, h->last_step_own_ids ? &own : nullptr, true));
     h->rows_early = false;
     h->iter += 1;
     return GH_OK;
@@ -898,15 +901,15 @@ extern "C" gh_status gh_set_packed_rows(gh_handle h, int32_t on) {
 extern "C" float *gh_rows_packed_device(gh_handle h) { return h && h->packed_exchange ? h->d_rows_packed : nullptr; }
 extern "C" gh_status gh_step_unpack_rows(gh_handle h) {
     GH_TRY(check_handle(h));
-    if (!h->d_stats_comb || h->d_gbuf) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
     if (!h->packed_exchange) { h->err = "the packed block exchange is not in use (gh_set_packed_rows)"; return GH_ERR_INVALID; }
     return gh_launch_unpack_rows(h);
 }
 extern "C" gh_status gh_step_finish_own(gh_handle h, const double *stats_all, int32_t world) {
     GH_TRY(check_handle(h));
-    if (!h->d_stats_comb || h->d_gbuf) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
     if (!stats_all || world != h->g_world) { h->err = "bad statistics buffer / world size"; return GH_ERR_INVALID; }
-    GH_TRY(gh_launch_normalise_own(h, stats_all, world));
+    GH_TRY(gh_launch_normalise(h, true, nullptr, false, stats_all));
     h->iter += 1;
     return GH_OK;
 }
@@ -914,10 +917,10 @@ extern "C" void *gh_gather_buffer_device(gh_handle h) { return h ? h->d_gbuf : n
 extern "C" int64_t gh_gather_slot_bytes(gh_handle h) { return h ? h->g_slot : 0; }
 extern "C" gh_status gh_step_finish_gathered(gh_handle h) {
     GH_TRY(check_handle(h));
-    if (!h->d_gbuf) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
+    if (h->layout != GH_LAYOUT_GATHERED) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
     // a rank that drew this step's ids on the device will do so again: prepare them in the same launch
     const gh_ids own = gh_own_ids(h);
-    GH_TRY(gh_launch_normalise_gathered(h, h->last_step_own_ids ? &own : nullptr));
+    GH_TRY(gh_launch_normalise(h, true, h->last_step_own_ids ? &own : nullptr, true));
     h->iter += 1;
     return GH_OK;
 }

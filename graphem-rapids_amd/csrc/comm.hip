@@ -172,7 +172,7 @@ static gh_status comm_common(gh_engine *h, int world, int rank) {
         h->err = "hipMalloc of the gather buffers failed";
         return GH_ERR_NOMEM;
     }
-    if (h->overlap) {   // form D: a second stream for the early all-gather of the rows, ordered against the engine's by two events
+    if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: a second stream for the early all-gather of the rows, ordered against the engine's by two events
         if (hipStreamCreateWithFlags(&h->comm->stream_b, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_fused, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_rows, hipEventDisableTiming) != hipSuccess) {
@@ -204,7 +204,7 @@ extern "C" gh_status gh_comm_init_rccl(gh_handle h, int32_t world, int32_t rank,
     // form D: the early all-gather needs a communicator of its own to be in flight beside the keys' and the statistics'.
     // Without ncclCommSplit (or if it fails -- on every rank alike: it is a collective call) the rows go out on the engine's
     // stream after the merge, form B's order: correct, nothing hidden.
-    if (h->overlap && api->CommSplit) {   // (also at world 1: the rehearsal of the N > 1 path on a one-GPU box takes the same route)
+    if (h->layout == GH_LAYOUT_OVERLAP && api->CommSplit) {   // (also at world 1: the rehearsal of the N > 1 path on a one-GPU box takes the same route)
         if (api->CommSplit(h->comm->nccl, 0, rank, &h->comm->nccl_b, nullptr) != ncclSuccess) h->comm->nccl_b = nullptr;
     }
     return GH_OK;
@@ -267,7 +267,7 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
             // form D: new0 = pos + Fs of the own rows is complete -- its all-gather starts here, on the side stream when there
             // is a second communicator (RCCL) or on the engine's (loopback: the host rendezvous blocks either way), and runs
             // beside select -> keys -> merge + intersection -> statistics
-            const bool early = h->overlap && gh_step_rows_early(h);
+            const bool early = h->layout == GH_LAYOUT_OVERLAP && gh_step_rows_early(h);
             const bool side = early && c->stream_b && (c->nccl_b || c->loop);
             if (early && (side || c->loop)) {
                 const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
@@ -286,7 +286,7 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
             } else {
                 GH_TRY_ST(gh_step_merge(h, h->d_partial, 1));   // spring forces only: nothing to merge
             }
-            if (h->overlap) {   // form D: (the rows went out above, or go now)
+            if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: (the rows went out above, or go now)
                 const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
                 unsigned char *rows = reinterpret_cast<unsigned char *>(gh_rows_all_device(h));
                 if (!rows_sent) {   // a step without new0 (no fused kernel), or RCCL without a second communicator: form B's order
@@ -299,7 +299,7 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
                     if (hipStreamWaitEvent(h->stream, c->ev_rows, 0) != hipSuccess) { h->err = "hipStreamWaitEvent failed"; return GH_ERR_HIP; }
                 }
                 GH_TRY_ST(gh_step_finish_overlap(h));
-            } else if (h->d_gbuf) {   // form B
+            } else if (h->layout == GH_LAYOUT_GATHERED) {   // form B
                 GH_TRY_ST(comm_all_gather(h, h->d_gbuf + (size_t)c->rank * h->g_slot, h->d_gbuf, (size_t)h->g_slot, "allgather_slots"));
                 GH_TRY_ST(gh_step_finish_gathered(h));
             } else {           // form C

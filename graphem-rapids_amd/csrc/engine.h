@@ -35,6 +35,10 @@ struct gh_ids {
     int32_t *ids;   // (mutable: the set-up writes the ids it draws)
 };
 
+// How a partitioned engine finishes a step (include/graphem_hip.h): set by gh_gather_layout (form B), gh_rank_layout
+// (form C), gh_overlap_layout (form D).
+enum { GH_LAYOUT_NONE = 0, GH_LAYOUT_GATHERED, GH_LAYOUT_RANK, GH_LAYOUT_OVERLAP };
+
 struct gh_comm;   // comm.hip: collective backend of the native partitioned loop
 struct gh_f64;    // f64.hip: state of a float64 engine (gh_create_f64)
 struct gh_ivf;    // ivf.hip: buffers of the inverted-file search (GH_KNN_IVF)
@@ -138,13 +142,12 @@ struct gh_engine {
     double *d_stats_own = nullptr;
     int64_t g_slot = 0, g_chunk = 0;  // slot bytes, rows per rank
     int g_world = 0, g_rank = 0;
-    double *d_stats_comb = nullptr;   // form C (gh_rank_layout): the ranks' statistics added in rank order, (2, LD)
+    int layout = GH_LAYOUT_NONE;
     float *d_rows_packed = nullptr;   // form C, D < LD: (world, chunk, D) the finished blocks WITHOUT the pad columns -- what travels
                                       // (12 instead of 16 bytes per row at 3 components); gh_step_unpack_rows expands it into d_pos
     bool packed_exchange = false;     // ... in use (gh_set_packed_rows; default: from 2 M vertices on, where the saved quarter of
                                       // the all-gather outweighs the expansion kernel -- 30 us at 4 M vertices, 14 at 1 M)
     // form D (gh_overlap_layout): the ranks' un-normalised rows new0 = pos + Fs are all-gathered EARLY, beside the KNN tail
-    bool overlap = false;
     bool rows_early = false;          // this step: new0 of the own rows is in its block (the rows may travel right after step_begin)
     float *d_rows_all = nullptr;      // (world, chunk, LD): d_new is block g_rank of it
     float *d_rows_pk = nullptr;       // (world, chunk, D): the same without pad columns -- what travels when D < LD -- or null
@@ -312,14 +315,15 @@ gh_status gh_launch_integrate(gh_engine *h);               // d_Fs, d_acc -> d_n
 gh_status gh_launch_spring_only(gh_engine *h, float *d_F); // F (n, LD), own rows
 gh_status gh_launch_inter_to_dense(gh_engine *h, float *d_F);
 gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float *d_Fi);
+// d_new -> d_pos (pt.py:802-804).  The own rows from the own statistics; stats_all: form C, the own rows from every rank's
+// statistics; gathered: forms B / D, all n rows from every rank's rows and statistics where the layout holds them.
 // next: also the KNN set-up of the next iteration from these ids, in the same launch (null: none)
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next = nullptr);
-gh_status gh_launch_normalise_gathered(gh_engine *h, const gh_ids *next);
-gh_status gh_launch_normalise_own(gh_engine *h, const double *stats_all, int world);   // form C: own rows from every rank's statistics
+gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next = nullptr, bool gathered = false,
+                              const double *stats_all = nullptr);
 gh_status gh_launch_unpack_rows(gh_engine *h);   // form C: the gathered packed blocks of the OTHER ranks -> their rows of d_pos
 struct gh_long_args;
 gh_long_args gh_make_long_args(const gh_engine *h, bool coop_mid = false);   // common.h; coop_mid: fused kernels
-gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0);  // spring forces of the hub rows  // gathered slots of every rank -> all n rows of d_pos
+gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0);  // spring forces of the hub rows
 inline int32_t *gh_patch_count(gh_engine *h) { return reinterpret_cast<int32_t *>(h->d_stats + (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD); }
 inline float *gh_patch_records(gh_engine *h) { return reinterpret_cast<float *>(gh_patch_count(h) + 4); }
 gh_status gh_launch_new0(gh_engine *h);                            // form D without the fused kernel: d_new = pos + Fs of the own rows

@@ -346,24 +346,55 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const double *__restrict
             ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-// pt.py:802-804: centre by the column mean, divide by (unbiased std + 1e-6).
-// stats = global (sum, sum of squares) over all n rows; every thread derives the same
-// mean / std from them.  Writes rows [row_lo, row_lo+rows) of pos.
-// The workgroups past g_norm (single-rank steps only, rows == n) run the NEXT iteration's KNN set-up
-// (setup_core.h) from the un-normalised rows: one launch and its dependent loads off the iteration.
+// Zero what the intersection phase touched (keeps acc / tflag all-zero between iterations); thread t0 of T.
+__device__ __forceinline__ void gh_clear_touched(double *__restrict__ acc, int32_t *__restrict__ tflag,
+                                                 const int32_t *__restrict__ touched, const int32_t *__restrict__ tcount, int LD,
+                                                 int64_t t0, int64_t T) {
+    const int64_t nt = (int64_t)(*tcount) * LD;
+    for (int64_t t = t0; t < nt; t += T) {
+        const int64_t x = touched[t / LD];
+        const int d = (int)(t % LD);
+        acc[x * LD + d] = 0.0;
+        if (d == 0) tflag[x] = 0;
+    }
+}
+
+// Where a normalise launch reads (gh_launch_normalise builds it from the engine's layout).  Row j of the destination range
+// [out_lo, out_lo + out_rows) of pos is row j % chunk of rank block j / chunk of the un-normalised rows; rank r's statistics
+// rows (sum, sum of squares, then the gh_fix_blocks correction pairs) start at stats + r * stats_block.
+struct gh_norm_src {
+    const float *rows;
+    int64_t chunk;        // rows per rank block
+    int64_t block;        // floats between two blocks
+    int RS;               // floats per row: LD, or D for rows that travelled without their pad columns (form D)
+    int64_t out_lo, out_rows;
+    const double *stats;
+    int world;
+    int64_t stats_block;  // doubles between two ranks' rows
+    __device__ const float *row(int64_t j) const {
+        const float *p = rows;
+        for (; j >= chunk; j -= chunk) p += block;   // (a few blocks; a division here cost the 16-wide set-up 2 VGPRs,
+        return p + j * RS;                           // 130 for the launch, one wave per SIMD less)
+    }
+};
+
+// pt.py:802-804: centre by the column mean, divide by (unbiased std + 1e-6), into rows [out_lo, out_lo + out_rows) of pos:
+// the own rows (single-rank steps, per-phase entry points, form C) or all n rows (forms B and D, include/graphem_hip.h).
+// Mean and std: each rank's statistics rows added in their fixed order, then the rank totals in rank order, so every rank
+// derives the same bits (world = 1: the one rank's total, as 0.0 + x == x).
+// The workgroups before the n_setup-th (all n rows only) run the NEXT iteration's KNN set-up (setup_core.h) from the
+// un-normalised rows: one launch and its dependent loads off the iteration.
 // LDT: the row stride as a compile-time constant for the set-up part (4, 8, 16; 0 = any stride, no tiles): one kernel for
 // all strides carried the 16-wide set-up's 127 VGPRs -- 4 workgroups per CU, so that at 1 M vertices half of the 2048
 // streaming workgroups queued behind the first 1024 (tools/stamp_probe.py: median start 8 us into the launch).
 template <int LDT>
-__global__ __launch_bounds__(256) void normalise_kernel(const float *__restrict__ nw, int64_t rows, int64_t row_lo,
-                                                       int D, int LD, int64_t n, const double *__restrict__ stats,
-                                                       float *__restrict__ pos, double *__restrict__ acc,
+__global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, int LD, int64_t n, float *__restrict__ pos,
+                                                       double *__restrict__ acc /* null: no clean-up */,
                                                        int32_t *__restrict__ tflag,
                                                        const int32_t *__restrict__ touched,
                                                        const int32_t *__restrict__ tcount, int nfix, int g_norm,
                                                        int n_setup, gh_setup_args sa, int32_t *__restrict__ qexact,
                                                        unsigned long long *__restrict__ stamps /* diagnostic, or null */,
-                                                       int stat_world = 1,
                                                        float *__restrict__ packed = nullptr /* form C: the same rows without pad columns, (rows, D) */) {
     if (stamps && (blockIdx.x >= GH_STAMP_EXTRA)) stamps = nullptr;
     if (stamps) stamps += (int64_t)blockIdx.x * 8;
@@ -374,67 +405,73 @@ __global__ __launch_bounds__(256) void normalise_kernel(const float *__restrict_
     __shared__ __align__(16) unsigned char setup_lds[GH_SETUP_LDS_BYTES];
     const bool setup_block = (int)blockIdx.x < n_setup;
     const int nb = (int)blockIdx.x - n_setup;  // index among the normalising workgroups
-    // also zero what the intersection phase touched (acc != nullptr): the integrate kernel that
-    // read those accumulators has finished; tcount itself is reset by the next KNN setup
-    if (acc && !setup_block) {
-        const int64_t nt = (int64_t)(*tcount) * LD;
-        for (int64_t t = nb * (int64_t)blockDim.x + threadIdx.x; t < nt; t += (int64_t)g_norm * blockDim.x) {
-            const int64_t x = touched[t / LD];
-            const int d = (int)(t % LD);
-            acc[x * LD + d] = 0.0;
-            if (d == 0) tflag[x] = 0;
-        }
-    }
+    // also zero what the intersection phase touched: the integrate kernel that read those accumulators has finished;
+    // tcount itself is reset by the next KNN setup
+    if (acc && !setup_block)
+        gh_clear_touched(acc, tflag, touched, tcount, LD, nb * (int64_t)blockDim.x + threadIdx.x, (int64_t)g_norm * blockDim.x);
     // set-up workgroups: the rows they will need are requested before anything else -- two levels of dependent cold loads
     // (edge -> rows), which the statistics' own round trip and arithmetic below then run under instead of in front of
     // (16-wide rows: 64 registers held across the prologue would cost the launch its occupancy; they fetch afterwards)
     constexpr int LDS_ = LDT > 0 ? LDT : 4;
     constexpr bool early_fetch = LDT > 0 && LDT <= 8;
     gh_setup_rows<LDS_> srows;
-    auto raw_row = [=](int64_t v, float (&row)[LDS_]) { gh_load_row<LDS_>(nw, v, row); };
+    auto raw_row = [=](int64_t v, float (&row)[LDS_]) {
+        const float *p = src.row(v);
+        if (src.RS == LD) {
+            gh_load_row<LDS_>(p, 0, row);
+        } else {
+#pragma unroll
+            for (int d = 0; d < LDS_; ++d) row[d] = d < D ? p[d] : 0.0f;
+        }
+    };
     if constexpr (early_fetch)
         if (setup_block && sa.tiles > 0) gh_setup_fetch<LDS_>(sa, (int)blockIdx.x, raw_row, srows);
-    extern __shared__ float ms[];  // mean[LD], std[LD], then the (2 + 2 nfix, LD) statistics rows as doubles
-    // all statistics rows with one load per thread and round, then summed from LDS in the fixed order: a thread adding
+    extern __shared__ float ms[];  // mean[LD], std[LD], then one rank's (2 + 2 nfix, LD) statistics rows as doubles,
+                                   // then (world > 1) the (2, LD) totals of the ranks before it
+    // a rank's statistics rows with one load per thread and round, then summed from LDS in the fixed order: a thread adding
     // its column's 2 nfix corrections straight from memory waited for them one after the other (LD = 16: 64 loads, 7.6 us
     // before any workgroup of this launch knew mean and std -- tools/stamp_probe.py)
-    // (stat_world > 1: form C of a partitioned step -- the statistics rows of every rank, all-gathered in rank order; each
-    // rank's rows in their fixed order, then the next rank's, so every rank derives the same mean / std bits)
     double *srow = reinterpret_cast<double *>(ms + 2 * LD);
     const int R = 2 + 2 * nfix;
-    for (int t = threadIdx.x; t < stat_world * R * LD; t += blockDim.x) srow[t] = stats[t];
-    __syncthreads();
-    for (int d = threadIdx.x; d < LD; d += blockDim.x) {
-        float mean = 0.0f, sd = 1.0f;
-        if (d < D) {
-            double sum = 0.0, sq = 0.0;
-            for (int r = 0; r < stat_world; ++r) {
-                const double *rr = srow + (int64_t)r * R * LD;
-                sum += rr[d];
-                sq += rr[LD + d];
+    double *tot = srow + R * LD;
+    for (int r = 0; r < src.world; ++r) {
+        const double *st = src.stats + (int64_t)r * src.stats_block;
+        for (int t = threadIdx.x; t < R * LD; t += blockDim.x) srow[t] = st[t];
+        __syncthreads();
+        for (int d = threadIdx.x; d < LD; d += blockDim.x) {
+            double sum = srow[d], sq = srow[LD + d];
 #pragma unroll 8
-                for (int b = 0; b < nfix; ++b) {  // corrections of the touched rows (zero when unused)
-                    sum += rr[(2 + 2 * b) * LD + d];
-                    sq += rr[(3 + 2 * b) * LD + d];
-                }
+            for (int b = 0; b < nfix; ++b) {  // corrections of the touched rows (zero when unused)
+                sum += srow[(2 + 2 * b) * LD + d];
+                sq += srow[(3 + 2 * b) * LD + d];
             }
-            const double m = sum / (double)n;
-            double var = (sq - sum * m) / (double)(n - 1);
-            if (var < 0.0) var = 0.0;
-            mean = (float)m;
-            sd = (float)sqrt(var) + 1e-6f;
+            sum = (r > 0 ? tot[d] : 0.0) + sum;
+            sq = (r > 0 ? tot[LD + d] : 0.0) + sq;
+            if (r + 1 < src.world) {
+                tot[d] = sum;
+                tot[LD + d] = sq;
+                continue;
+            }
+            float mean = 0.0f, sd = 1.0f;
+            if (d < D) {
+                const double m = sum / (double)n;
+                double var = (sq - sum * m) / (double)(n - 1);
+                if (var < 0.0) var = 0.0;
+                mean = (float)m;
+                sd = (float)sqrt(var) + 1e-6f;
+            }
+            ms[d] = mean;
+            ms[LD + d] = sd;
         }
-        ms[d] = mean;
-        ms[LD + d] = sd;
+        __syncthreads();
     }
-    __syncthreads();
     GH_STAMP(1);
     if (stamps && threadIdx.x == 0) stamps[6] = setup_block ? 1 : 2;
     if (setup_block) {
         const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         if (t == 0) qexact[0] = 0;
         // position of vertex v, component d < D, exactly as the normalising threads below compute it
-        auto getp = [=](int64_t v, int d) { return (nw[v * LD + d] - ms[d]) / ms[LD + d]; };
+        auto getp = [=](int64_t v, int d) { return (src.row(v)[d] - ms[d]) / ms[LD + d]; };
         if constexpr (LDT > 0) {
             if (sa.tiles > 0) {
                 auto norm = [=](float x, int d) { return (x - ms[d]) / ms[LD + d]; };
@@ -449,159 +486,58 @@ __global__ __launch_bounds__(256) void normalise_kernel(const float *__restrict_
         GH_STAMP(3);
         return;
     }
-    // 16 bytes per thread and step (LD is a multiple of 4, rows are 16-byte aligned)
-    const int64_t total4 = rows * LD / 4;
-    const float4 *src = reinterpret_cast<const float4 *>(nw);
-    float4 *dst = reinterpret_cast<float4 *>(pos + row_lo * LD);
+    // 16 bytes per thread and step (LD is a multiple of 4, rows are 16-byte aligned), one rank block after the other
     // four elements per thread and round, all four loads issued before the first division.  (Measured neutral for the
     // launch as a whole: at 1 M vertices the streaming workgroups are done after 13 us, the set-up workgroups after 17 --
     // 10 us of that are their two levels of cold random loads, edge -> rows, and holding the streaming back by 3.4 us
     // did not shorten them: tools/stamp_probe.py.)
     const int64_t step = (int64_t)g_norm * blockDim.x;
-    auto norm4 = [&](int64_t t, const float4 &v) {
-        const int d0 = (int)((t * 4) % LD);
-        float4 o;
-        o.x = d0 + 0 < D ? (v.x - ms[d0 + 0]) / ms[LD + d0 + 0] : 0.0f;
-        o.y = d0 + 1 < D ? (v.y - ms[d0 + 1]) / ms[LD + d0 + 1] : 0.0f;
-        o.z = d0 + 2 < D ? (v.z - ms[d0 + 2]) / ms[LD + d0 + 2] : 0.0f;
-        o.w = d0 + 3 < D ? (v.w - ms[d0 + 3]) / ms[LD + d0 + 3] : 0.0f;
-        dst[t] = o;
-        if (packed) {   // the copy that travels (gh_step_unpack_rows on the receiving ranks)
-            float *pk = packed + (t * 4 / LD) * D + d0;
-            if (d0 + 0 < D) pk[0] = o.x;
-            if (d0 + 1 < D) pk[1] = o.y;
-            if (d0 + 2 < D) pk[2] = o.z;
-            if (d0 + 3 < D) pk[3] = o.w;
+    const float *in = src.rows;
+    for (int64_t j0 = 0; j0 < src.out_rows; j0 += src.chunk, in += src.block) {
+        const int64_t total4 = min(src.chunk, src.out_rows - j0) * LD / 4;
+        float4 *dst = reinterpret_cast<float4 *>(pos + (src.out_lo + j0) * LD);
+        auto norm4 = [&](int64_t t, const float4 &v) {
+            const int d0 = (int)((t * 4) % LD);
+            float4 o;
+            o.x = d0 + 0 < D ? (v.x - ms[d0 + 0]) / ms[LD + d0 + 0] : 0.0f;
+            o.y = d0 + 1 < D ? (v.y - ms[d0 + 1]) / ms[LD + d0 + 1] : 0.0f;
+            o.z = d0 + 2 < D ? (v.z - ms[d0 + 2]) / ms[LD + d0 + 2] : 0.0f;
+            o.w = d0 + 3 < D ? (v.w - ms[d0 + 3]) / ms[LD + d0 + 3] : 0.0f;
+            dst[t] = o;
+            if (packed) {   // the copy that travels (gh_step_unpack_rows on the receiving ranks; form C has one block)
+                float *pk = packed + (t * 4 / LD) * D + d0;
+                if (d0 + 0 < D) pk[0] = o.x;
+                if (d0 + 1 < D) pk[1] = o.y;
+                if (d0 + 2 < D) pk[2] = o.z;
+                if (d0 + 3 < D) pk[3] = o.w;
+            }
+        };
+        int64_t t = nb * (int64_t)blockDim.x + threadIdx.x;
+        if (src.RS == LD) {
+            const float4 *in4 = reinterpret_cast<const float4 *>(in);
+            for (; t + 3 * step < total4; t += 4 * step) {
+                const float4 v0 = in4[t], v1 = in4[t + step], v2 = in4[t + 2 * step], v3 = in4[t + 3 * step];
+                norm4(t, v0);
+                norm4(t + step, v1);
+                norm4(t + 2 * step, v2);
+                norm4(t + 3 * step, v3);
+            }
+            for (; t < total4; t += step) norm4(t, in4[t]);
+        } else {   // rows without pad columns: what exists of each quarter row
+            for (; t < total4; t += step) {
+                const int d0 = (int)((t * 4) % LD);
+                const float *rp = in + (t * 4 / LD) * src.RS + d0;
+                float4 v;
+                v.x = d0 + 0 < D ? rp[0] : 0.0f;
+                v.y = d0 + 1 < D ? rp[1] : 0.0f;
+                v.z = d0 + 2 < D ? rp[2] : 0.0f;
+                v.w = d0 + 3 < D ? rp[3] : 0.0f;
+                norm4(t, v);
+            }
         }
-    };
-    int64_t t = nb * (int64_t)blockDim.x + threadIdx.x;
-    for (; t + 3 * step < total4; t += 4 * step) {
-        const float4 v0 = src[t], v1 = src[t + step], v2 = src[t + 2 * step], v3 = src[t + 3 * step];
-        norm4(t, v0);
-        norm4(t + step, v1);
-        norm4(t + 2 * step, v2);
-        norm4(t + 3 * step, v3);
     }
-    for (; t < total4; t += step) norm4(t, src[t]);
     GH_STAMP(3);
 #undef GH_STAMP
-}
-
-// The same normalisation for ALL n rows from the gathered slots of every rank (one-collective
-// finish, include/graphem_hip.h): slot r = [chunk rows of new positions | that rank's statistics].
-// The per-rank statistics are added in rank order, so every rank derives the same mean / std.
-// Since round 5 rows and statistics are two strided arrays: form B passes both halves of its slots, form D
-// (gh_overlap_layout) the early all-gathered rows -- RS floats per row: LD, or D when they travelled without pad columns
-// -- and the late all-gathered statistics; skip_cleanup: form D's patch launch has zeroed the accumulators already.
-template <int LDT>
-__global__ __launch_bounds__(256) void normalise_gathered_kernel(const float *__restrict__ rows_base, int64_t rows_block /* floats between two ranks' blocks */,
-                                                                int RS, const double *__restrict__ stats_base, int64_t stats_block /* doubles */,
-                                                                int skip_cleanup,
-                                                                int64_t chunk, int world, int D, int LD, int64_t n,
-                                                                int nfix, float *__restrict__ pos,
-                                                                double *__restrict__ acc, int32_t *__restrict__ tflag,
-                                                                const int32_t *__restrict__ touched,
-                                                                const int32_t *__restrict__ tcount, int g_norm,
-                                                                int n_setup, gh_setup_args sa,
-                                                                int32_t *__restrict__ qexact) {
-    __shared__ __align__(16) unsigned char setup_lds[GH_SETUP_LDS_BYTES];
-    const bool setup_block = (int)blockIdx.x < n_setup;  // the next iteration's KNN set-up, as in normalise_kernel
-    const int nb = (int)blockIdx.x - n_setup;
-    if (!setup_block && !skip_cleanup) {
-        const int64_t nt = (int64_t)(*tcount) * LD;
-        for (int64_t t = nb * (int64_t)blockDim.x + threadIdx.x; t < nt; t += (int64_t)g_norm * blockDim.x) {
-            const int64_t x = touched[t / LD];
-            const int d = (int)(t % LD);
-            acc[x * LD + d] = 0.0;
-            if (d == 0) tflag[x] = 0;
-        }
-    }
-    extern __shared__ float ms[];  // mean[LD], std[LD], then world * 2 * LD doubles of per-rank totals
-    double *part = reinterpret_cast<double *>(ms + 2 * LD);
-    // per-rank totals (sum and sum of squares incl. the correction rows), one thread per (rank, entry) ...
-    for (int t = threadIdx.x; t < world * 2 * LD; t += blockDim.x) {
-        const int r = t / (2 * LD), c = t % (2 * LD), base = c / LD, col = c % LD;
-        const double *st = stats_base + (int64_t)r * stats_block;
-        double v = st[base * LD + col];
-        for (int b = 0; b < nfix; ++b) v += st[(2 + 2 * b + base) * LD + col];
-        part[t] = v;
-    }
-    __syncthreads();
-    // ... added in rank order
-    for (int d = threadIdx.x; d < LD; d += blockDim.x) {
-        float mean = 0.0f, sd = 1.0f;
-        if (d < D) {
-            double sum = 0.0, sq = 0.0;
-            for (int r = 0; r < world; ++r) {
-                sum += part[r * 2 * LD + d];
-                sq += part[r * 2 * LD + LD + d];
-            }
-            const double m = sum / (double)n;
-            double var = (sq - sum * m) / (double)(n - 1);
-            if (var < 0.0) var = 0.0;
-            mean = (float)m;
-            sd = (float)sqrt(var) + 1e-6f;
-        }
-        ms[d] = mean;
-        ms[LD + d] = sd;
-    }
-    __syncthreads();
-    if (setup_block) {
-        const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-        if (t == 0) qexact[0] = 0;
-        auto getp = [=](int64_t v, int d) {
-            const int64_t r = v / chunk;
-            const float *rowsrc = rows_base + r * rows_block;
-            return (rowsrc[(v - r * chunk) * RS + d] - ms[d]) / ms[LD + d];
-        };
-        if constexpr (LDT > 0) {
-            if (sa.tiles > 0) gh_setup_block<LDT>(sa, (int)blockIdx.x, getp, setup_lds);
-            else gh_setup_item(sa, t, getp);
-        } else {
-            gh_setup_item(sa, t, getp);
-        }
-        return;
-    }
-    const int64_t total4 = n * LD / 4;  // 16 bytes per thread and step
-    float4 *dst = reinterpret_cast<float4 *>(pos);
-    for (int64_t t = nb * (int64_t)blockDim.x + threadIdx.x; t < total4; t += (int64_t)g_norm * blockDim.x) {
-        const int64_t i = t * 4 / LD;
-        const int d0 = (int)((t * 4) % LD);
-        const int64_t r = i / chunk;
-        const float *rp = rows_base + r * rows_block + (i - r * chunk) * RS + d0;
-        float4 v;
-        if (RS == LD) v = *reinterpret_cast<const float4 *>(rp);
-        else {   // rows without pad columns: what exists of this quarter row
-            v.x = d0 + 0 < D ? rp[0] : 0.0f;
-            v.y = d0 + 1 < D ? rp[1] : 0.0f;
-            v.z = d0 + 2 < D ? rp[2] : 0.0f;
-            v.w = d0 + 3 < D ? rp[3] : 0.0f;
-        }
-        float4 o;
-        o.x = d0 + 0 < D ? (v.x - ms[d0 + 0]) / ms[LD + d0 + 0] : 0.0f;
-        o.y = d0 + 1 < D ? (v.y - ms[d0 + 1]) / ms[LD + d0 + 1] : 0.0f;
-        o.z = d0 + 2 < D ? (v.z - ms[d0 + 2]) / ms[LD + d0 + 2] : 0.0f;
-        o.w = d0 + 3 < D ? (v.w - ms[d0 + 3]) / ms[LD + d0 + 3] : 0.0f;
-        dst[t] = o;
-    }
-}
-
-// Form C of a partitioned step: every rank's statistics rows (sum, sum of squares, then its correction row pairs),
-// all-gathered in rank order -> one (2, LD) record: per rank its rows in their fixed order, then the ranks in rank order,
-// so every rank derives the same mean / std bits.  One workgroup, thread = (base, column).
-__global__ __launch_bounds__(64) void stats_combine_kernel(const double *__restrict__ all, int world, int R /* rows per rank */,
-                                                          int LD, double *__restrict__ out) {
-    const int t = threadIdx.x;
-    if (t >= 2 * LD) return;
-    const int base = t / LD, col = t % LD;
-    double tot = 0.0;
-    for (int r = 0; r < world; ++r) {
-        const double *st = all + (int64_t)r * R * LD;
-        double v = st[base * LD + col];
-        for (int b = 2 + base; b < R; b += 2) v += st[b * LD + col];
-        tot += v;
-    }
-    out[t] = tot;
 }
 
 // pt.py:796-799 with given force arrays (per-phase entry point gh_integrate_normalise).
@@ -655,15 +591,10 @@ __global__ void inter_to_dense_kernel(const double *__restrict__ acc, const int3
     F[x * LD + d] = (float)acc[x * LD + d];
 }
 
-// Zero what the intersection phase touched (keeps acc / tflag all-zero between iterations).
 __global__ void inter_cleanup_kernel(double *__restrict__ acc, int32_t *__restrict__ tflag,
                                      const int32_t *__restrict__ touched, const int32_t *__restrict__ tcount, int LD) {
-    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (t >= (int64_t)(*tcount) * LD) return;
-    const int64_t x = touched[t / LD];
-    const int d = (int)(t % LD);
-    acc[x * LD + d] = 0.0;
-    if (d == 0) tflag[x] = 0;
+    gh_clear_touched(acc, tflag, touched, tcount, LD, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                     (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void reset_counter_kernel(int32_t *c) { *c = 0; }
@@ -915,8 +846,8 @@ gh_status gh_launch_integrate(gh_engine *h) {
 #define GH_FIX_CASE(LL)                                                                                      \
     stats_fix_kernel<LL><<<dim3(gh_fix_blocks(LL)), dim3(256), 0, h->stream>>>(                                  \
         h->d_blockstats, h->n_vblocks, h->d_pos, h->d_Fs, h->d_acc, h->d_touched, h->d_tcount, h->part.row_lo, \
-        h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->overlap ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
-        h->overlap ? gh_patch_records(h) : nullptr, (int)h->patch_cap)
+        h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
+        h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap)
         if (h->LD == 4) GH_FIX_CASE(4);
         else if (h->LD == 8) GH_FIX_CASE(8);
         else GH_FIX_CASE(16);
@@ -934,8 +865,8 @@ gh_status gh_launch_integrate(gh_engine *h) {
     const unsigned grid = grid_for(h->rows, 256);
     // form D: the own block (d_new) holds new0 and is on its way to the other ranks: statistics as always, the touched rows'
     // values into the patch list (row strides of 4, 8, 16 floats: gh_overlap_layout refuses the others)
-    int32_t *pc = h->overlap ? gh_patch_count(h) + (h->iter & 1) : nullptr;   // (two counters, alternate iterations: patch_rows_kernel)
-    float *pr = h->overlap ? gh_patch_records(h) : nullptr;
+    int32_t *pc = h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr;   // (two counters, alternate iterations: patch_rows_kernel)
+    float *pr = h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr;
     const int pcap = (int)h->patch_cap;
     float *wide_out = h->d_new;
     {
@@ -1034,14 +965,34 @@ gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float
     return GH_OK;
 }
 
-// next: also run the next iteration's KNN set-up in this launch (single-rank fused steps), for the sample source the
-// caller expects then.
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next) {
+// next: also run the next iteration's KNN set-up in this launch (single-rank fused steps, forms B and D), for the sample
+// source the caller expects then.
+gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next, bool gathered, const double *stats_all) {
     gh_set_lookahead(h, nullptr);  // positions change: whatever set-up was done ahead is stale
-    if (h->rows == 0) return with_cleanup ? gh_launch_inter_cleanup(h) : GH_OK;
-    gh_scope t(h, "normalise");
-    const int64_t total = h->rows * h->LD / 4;  // float4 elements
-    unsigned grid = grid_for(total, 1024);  // four elements per thread and round (normalise_kernel)
+    const int R = 2 + 2 * gh_fix_blocks(h->LD);
+    gh_norm_src src{h->d_new, std::max<int64_t>(h->rows, 1), 0, h->LD, h->part.row_lo, h->rows, h->d_stats, 1, 0};
+    if (stats_all) {   // form C: the statistics rows of every rank, all-gathered in rank order
+        src.stats = stats_all;
+        src.world = h->g_world;
+        src.stats_block = (int64_t)R * h->LD;
+    }
+    if (gathered) {   // form B: both halves of the gathered slots; form D: the early-gathered rows (packed or not) and the
+                      // late-gathered statistics
+        const bool overlap = h->layout == GH_LAYOUT_OVERLAP;
+        src.RS = overlap && h->d_rows_pk ? h->D : h->LD;
+        src.rows = overlap ? (h->d_rows_pk ? h->d_rows_pk : h->d_rows_all) : reinterpret_cast<const float *>(h->d_gbuf);
+        src.chunk = std::min(h->g_chunk, h->n);
+        src.block = overlap ? h->g_chunk * src.RS : h->g_slot / (int64_t)sizeof(float);
+        src.out_lo = 0;
+        src.out_rows = h->n;
+        src.stats = overlap ? h->d_stats_all : reinterpret_cast<const double *>(h->d_gbuf + h->g_chunk * h->LD * (int64_t)sizeof(float));
+        src.world = h->g_world;
+        src.stats_block = overlap ? h->stats_block : h->g_slot / (int64_t)sizeof(double);
+        if (!(h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup)) next = nullptr;
+    }
+    if (src.out_rows == 0) return with_cleanup ? gh_launch_inter_cleanup(h) : GH_OK;
+    gh_scope t(h, gathered ? "normalise_gathered" : stats_all ? "normalise_own" : "normalise");
+    unsigned grid = grid_for(src.out_rows * h->LD / 4, 1024);  // four float4 elements per thread and round (normalise_kernel)
     if (grid > 2048) grid = 2048;
     gh_setup_args sa{};
     unsigned extra = 0;
@@ -1049,15 +1000,17 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
         sa = gh_make_setup_args(h, *next, h->iter + 1);
         extra = gh_setup_blocks(sa);
     }
-    const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
-#define GH_NORM(LL)                                                                                         \
-    normalise_kernel<LL><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(                                    \
-        h->d_new, h->rows, h->part.row_lo, h->D, h->LD, h->n, h->d_stats, h->d_pos,                              \
-        with_cleanup ? h->d_acc : nullptr, h->d_tflag, h->d_touched, h->d_tcount, gh_fix_blocks(h->LD), (int)grid, \
-        (int)extra, sa, h->d_qexact, h->d_stamps ? h->d_stamps + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr)
-    if (h->LD == 4) GH_NORM(4);
-    else if (h->LD == 8) GH_NORM(8);
-    else if (h->LD == 16) GH_NORM(16);
+    const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
+    float *packed = stats_all && h->packed_exchange ? h->d_rows_packed + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
+    const int ldt = stats_all ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
+#define GH_NORM(LL)                                                                                                      \
+    normalise_kernel<LL><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(                                                 \
+        src, h->D, h->LD, h->n, h->d_pos, with_cleanup ? h->d_acc : nullptr, h->d_tflag, h->d_touched, h->d_tcount,           \
+        gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact,                                                        \
+        h->d_stamps ? h->d_stamps + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed)
+    if (ldt == 4) GH_NORM(4);
+    else if (ldt == 8) GH_NORM(8);
+    else if (ldt == 16) GH_NORM(16);
     else {
         if (sa.tiles > 0) { h->err = "KNN set-up tiles need a row stride of 4, 8 or 16"; return GH_ERR_RUNTIME; }
         GH_NORM(0);
@@ -1065,38 +1018,6 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
 #undef GH_NORM
     GH_LAUNCH_CHECK();
     gh_set_lookahead(h, next);
-    return GH_OK;
-}
-
-// Form C: normalise the own rows into their block of d_pos from the ranks' gathered statistics; also zeroes what the
-// intersection phase touched.  No set-up for the next iteration here: the other ranks' rows arrive with the caller's
-// all-gather of the position blocks.
-gh_status gh_launch_normalise_own(gh_engine *h, const double *stats_all, int world) {
-    gh_set_lookahead(h, nullptr);
-    const int R = 2 + 2 * gh_fix_blocks(h->LD);
-    int nfix = gh_fix_blocks(h->LD), sworld = world;
-    size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)world * R * h->LD;
-    if (smem > 48 * 1024) {   // wide rows on many ranks: the rows do not fit the workgroup's LDS -- added up by a launch of their own
-        if (2 * h->LD > 64) { h->err = "row stride too large for the partitioned finish"; return GH_ERR_INVALID; }
-        gh_scope t(h, "stats_combine");
-        stats_combine_kernel<<<dim3(1), dim3(64), 0, h->stream>>>(stats_all, world, R, h->LD, h->d_stats_comb);
-        GH_LAUNCH_CHECK();
-        stats_all = h->d_stats_comb;
-        nfix = 0;
-        sworld = 1;
-        smem = sizeof(float) * 2 * h->LD + sizeof(double) * 2 * (size_t)h->LD;
-    }
-    if (h->rows == 0) return gh_launch_inter_cleanup(h);
-    gh_scope t(h, "normalise_own");
-    const int64_t total = h->rows * h->LD / 4;
-    unsigned grid = grid_for(total, 1024);
-    if (grid > 2048) grid = 2048;
-    gh_setup_args sa{};
-    normalise_kernel<0><<<dim3(grid), dim3(256), smem, h->stream>>>(
-        h->d_new, h->rows, h->part.row_lo, h->D, h->LD, h->n, stats_all, h->d_pos, h->d_acc, h->d_tflag, h->d_touched,
-        h->d_tcount, nfix, (int)grid, 0, sa, h->d_qexact, nullptr, sworld,
-        h->packed_exchange ? h->d_rows_packed + (size_t)h->g_rank * h->g_chunk * h->D : nullptr);
-    GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
@@ -1117,45 +1038,6 @@ gh_status gh_launch_unpack_rows(gh_engine *h) {
     unpack_rows_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_rows_packed, h->n, h->D, h->LD, h->part.row_lo,
                                                                                        h->part.row_hi, h->d_pos);
     GH_LAUNCH_CHECK();
-    return GH_OK;
-}
-
-// next: also the next iteration's KNN set-up (as gh_launch_normalise).
-gh_status gh_launch_normalise_gathered(gh_engine *h, const gh_ids *next) {
-    gh_set_lookahead(h, nullptr);
-    gh_scope t(h, "normalise_gathered");
-    unsigned grid = grid_for(h->n * h->LD / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const bool presetup = next && h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
-    gh_setup_args sa{};
-    unsigned extra = 0;
-    if (presetup) {
-        sa = gh_make_setup_args(h, *next, h->iter + 1);
-        extra = gh_setup_blocks(sa);
-    }
-    const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * 2 * h->LD * (size_t)h->g_world;
-    // form B: both halves of the gathered slots; form D: the early-gathered rows (packed or not) and the late-gathered statistics
-    const float *rows_base = h->overlap ? (h->d_rows_pk ? h->d_rows_pk : h->d_rows_all) : reinterpret_cast<const float *>(h->d_gbuf);
-    const int RS = h->overlap && h->d_rows_pk ? h->D : h->LD;
-    const int64_t rows_block = h->overlap ? h->g_chunk * RS : h->g_slot / (int64_t)sizeof(float);
-    const double *stats_base = h->overlap ? h->d_stats_all : reinterpret_cast<const double *>(h->d_gbuf + h->g_chunk * h->LD * (int64_t)sizeof(float));
-    const int64_t stats_block = h->overlap ? h->stats_block : h->g_slot / (int64_t)sizeof(double);
-    const int skip_cleanup = h->overlap && h->rows_early ? 1 : 0;
-#define GH_NORMG(LL)                                                                                              \
-    normalise_gathered_kernel<LL><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(                                   \
-        rows_base, rows_block, RS, stats_base, stats_block, skip_cleanup,                                                  \
-        h->g_chunk, h->g_world, h->D, h->LD, h->n, gh_fix_blocks(h->LD), h->d_pos, h->d_acc,         \
-        h->d_tflag, h->d_touched, h->d_tcount, (int)grid, (int)extra, sa, h->d_qexact)
-    if (h->LD == 4) GH_NORMG(4);
-    else if (h->LD == 8) GH_NORMG(8);
-    else if (h->LD == 16) GH_NORMG(16);
-    else {
-        if (sa.tiles > 0) { h->err = "KNN set-up tiles need a row stride of 4, 8 or 16"; return GH_ERR_RUNTIME; }
-        GH_NORMG(0);
-    }
-#undef GH_NORMG
-    GH_LAUNCH_CHECK();
-    gh_set_lookahead(h, presetup ? next : nullptr);
     return GH_OK;
 }
 
@@ -1206,13 +1088,7 @@ __global__ __launch_bounds__(256) void patch_rows_kernel(float *__restrict__ row
     }
     if (r != rank) return;
     if (t0 == 0) hdr[par ^ 1] = 0;
-    const int64_t nt = (int64_t)(*tcount) * LD;
-    for (int64_t t = t0; t < nt; t += T) {
-        const int64_t x = touched[t / LD];
-        const int d = (int)(t % LD);
-        acc[x * LD + d] = 0.0;
-        if (d == 0) tflag[x] = 0;
-    }
+    gh_clear_touched(acc, tflag, touched, tcount, LD, t0, T);
 }
 gh_status gh_launch_patch_rows(gh_engine *h) {
     gh_scope t(h, "patch_rows");

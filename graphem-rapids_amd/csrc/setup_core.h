@@ -216,7 +216,7 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
     }
 }
 
-// Both halves at once, positions read through getp(vertex, d) (knn_setup_kernel, the gathered normalise).
+// Both halves at once, positions read through getp(vertex, d) (knn_setup_kernel).
 template <int LD, class P>
 __device__ __forceinline__ void gh_setup_block(const gh_setup_args &a, int blk, P getp, unsigned char *lds,
                                                unsigned long long *stamps = nullptr /* diagnostic */) {

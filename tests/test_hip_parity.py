@@ -260,6 +260,7 @@ def test_device_sampler():
                                             (3, "hashed", 2001, 3),     # few edges: per-query search of d_mid
                                             (2, "hashed", 9001, 5),     # D without a templated spring kernel
                                             (3, "hashed", 20001, 16),
+                                            (6, "hashed", 20001, 16),   # more ranks' statistics than fit in LDS at once
                                             (3, "hashed-hubs", 30011, 3)])  # rows with thousands of neighbours
 @pytest.mark.parametrize("finish", ["own", "gathered", "overlap"])
 def test_partitioned_engines_equal_single_engine(world, rule, n, D, finish):
