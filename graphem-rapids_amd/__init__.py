@@ -9,7 +9,12 @@ from .embedder_hip import GraphEmbedderHIP
 from .memory_management import (MemoryManager, cleanup_gpu_memory, get_gpu_memory_info, get_optimal_chunk_size,
                                 monitor_memory_usage)
 from .generators import (erdos_renyi_graph, generate_random_regular, erdos_renyi_edges, random_regular_edges, planted_partition_edges,
-                         edges_to_adjacency, load_snap_edge_list)
+                         edges_to_adjacency, load_snap_edge_list,
+                         generate_sbm, generate_ba, generate_ws, generate_power_cluster, generate_scale_free,
+                         generate_geometric, generate_road_network, generate_bipartite_graph, generate_balanced_tree,
+                         generate_caveman, generate_relaxed_caveman, sbm_edges, bipartite_edges, geometric_edges,
+                         barabasi_albert_edges, caveman_edges, road_network_edges, balanced_tree_edges,
+                         watts_strogatz_edges, powerlaw_cluster_edges, scale_free_edges, relaxed_caveman_edges)
 from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influence, greedy_seed_selection,
                         run_influence_benchmark)
 from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
@@ -59,4 +64,9 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "get_optimal_chunk_size", "monitor_memory_usage", "InfluenceGraph", "influence_spread",
            "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark",
            "CentralityGraph", "betweenness_centrality", "load_centrality", "closeness_centrality", "pagerank",
-           "eigenvector_centrality_numpy", "run_benchmark", "benchmark_correlations"]
+           "eigenvector_centrality_numpy", "run_benchmark", "benchmark_correlations",
+           "generate_sbm", "generate_ba", "generate_ws", "generate_power_cluster", "generate_scale_free",
+           "generate_geometric", "generate_road_network", "generate_bipartite_graph", "generate_balanced_tree",
+           "generate_caveman", "generate_relaxed_caveman", "sbm_edges", "bipartite_edges", "geometric_edges",
+           "barabasi_albert_edges", "caveman_edges", "road_network_edges", "balanced_tree_edges",
+           "watts_strogatz_edges", "powerlaw_cluster_edges", "scale_free_edges", "relaxed_caveman_edges"]

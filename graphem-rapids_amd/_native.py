@@ -34,6 +34,8 @@ SYMBOLS = [
     "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
     "gh_cent_create", "gh_cent_destroy", "gh_cent_last_error", "gh_cent_edge_count", "gh_cent_csr_device",
     "gh_cent_set_memory_budget", "gh_cent_paths", "gh_cent_pagerank", "gh_spmv_adj_shift",
+    "gh_gen_create", "gh_gen_destroy", "gh_gen_last_error", "gh_gen_set_memory_budget", "gh_gen_sbm", "gh_gen_geometric",
+    "gh_gen_ba", "gh_gen_edges", "gh_gen_positions",
 ]
 
 
@@ -260,6 +262,24 @@ def load():
     L.gh_cent_pagerank.restype = ctypes.c_int
     L.gh_spmv_adj_shift.argtypes = [vp, i64, vp, vp, ctypes.c_double, vp, vp]
     L.gh_spmv_adj_shift.restype = ctypes.c_int
+    L.gh_gen_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
+    L.gh_gen_create.restype = ctypes.c_int
+    L.gh_gen_destroy.argtypes = [vp]
+    L.gh_gen_destroy.restype = None
+    L.gh_gen_last_error.argtypes = [vp]
+    L.gh_gen_last_error.restype = ctypes.c_char_p
+    L.gh_gen_set_memory_budget.argtypes = [vp, i64]
+    L.gh_gen_set_memory_budget.restype = ctypes.c_int
+    L.gh_gen_sbm.argtypes = [vp, i32, vp, vp, ctypes.c_uint64, ctypes.POINTER(i64)]
+    L.gh_gen_sbm.restype = ctypes.c_int
+    L.gh_gen_geometric.argtypes = [vp, i64, ctypes.c_double, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
+    L.gh_gen_geometric.restype = ctypes.c_int
+    L.gh_gen_ba.argtypes = [vp, i64, i64, ctypes.c_uint64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    L.gh_gen_ba.restype = ctypes.c_int
+    L.gh_gen_edges.argtypes = [vp, vp]
+    L.gh_gen_edges.restype = ctypes.c_int
+    L.gh_gen_positions.argtypes = [vp, vp]
+    L.gh_gen_positions.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -775,3 +795,73 @@ def selftest_arith(samples, seed=1, device_id=0):
 
 def device_count():
     return int(load().gh_device_count())
+
+
+class Generator:
+    """Thin RAII wrapper over a gh_gen_handle: the counter-based graph generators (include/graphem_hip.h).  device_id < 0
+    is the library's host path, which touches no device and returns the same edges bit for bit."""
+
+    def __init__(self, device_id=0):
+        self.lib = load()
+        self.handle = ctypes.c_void_p()
+        self.device_id = int(device_id)
+        self.rounds = 0
+        st = self.lib.gh_gen_create(ctypes.byref(self.handle), self.device_id)
+        if st != GH_OK:
+            self.handle = ctypes.c_void_p()
+            self._raise(st)
+
+    def _raise(self, st):
+        if st == GH_OK:
+            return
+        msg = self.lib.gh_gen_last_error(self.handle if self.handle.value else None)
+        msg = msg.decode() if msg else f"gh_status {st}"
+        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self.lib.gh_gen_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-exception-caught
+            pass
+
+    def set_memory_budget(self, nbytes):
+        """Bytes a call may allocate for counts and edges (0: the default, 4 GiB); more is a MemoryError, never a cut."""
+        self._raise(self.lib.gh_gen_set_memory_budget(self.handle, int(nbytes)))
+
+    def _edges(self, count):
+        edges = np.zeros((int(count), 2), dtype=np.int32)
+        self._raise(self.lib.gh_gen_edges(self.handle, ptr(edges)))
+        return edges
+
+    def sbm(self, sizes, p_matrix, seed=0):
+        """(E, 2) int32 edges of the block model (gh_gen_sbm)."""
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+        P = np.ascontiguousarray(p_matrix, dtype=np.float64)
+        if P.shape != (len(sizes), len(sizes)) and (len(sizes) or P.size):
+            raise ValueError("p_matrix must be (blocks, blocks)")
+        count = ctypes.c_int64()
+        self._raise(self.lib.gh_gen_sbm(self.handle, len(sizes), ptr(sizes), ptr(P), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        ctypes.byref(count)))
+        return self._edges(count.value)
+
+    def geometric(self, n, radius, dim=2, seed=0):
+        """(edges (E, 2) int32, positions (n, dim) float32) of the random geometric graph (gh_gen_geometric)."""
+        count = ctypes.c_int64()
+        self._raise(self.lib.gh_gen_geometric(self.handle, int(n), float(radius), int(dim), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              ctypes.byref(count)))
+        pos = np.zeros((int(n), int(dim)), dtype=np.float32)
+        self._raise(self.lib.gh_gen_positions(self.handle, ptr(pos)))
+        return self._edges(count.value), pos
+
+    def ba(self, n, m, seed=0):
+        """(E, 2) int32 edges of the preferential-attachment graph (gh_gen_ba); self.rounds = launches it took."""
+        count, rounds = ctypes.c_int64(), ctypes.c_int32()
+        self._raise(self.lib.gh_gen_ba(self.handle, int(n), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(count),
+                                       ctypes.byref(rounds)))
+        self.rounds = int(rounds.value)
+        return self._edges(count.value)

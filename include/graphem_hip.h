@@ -548,6 +548,72 @@ gh_status gh_cent_pagerank(gh_cent_handle h, double alpha, int32_t max_iter, dou
 gh_status gh_spmv_adj_shift(void *hip_stream, int64_t n, const int64_t *indptr, const int32_t *indices, double c,
                             const double *x, double *y);
 
+/* ---- graph generators (reference generators.py: generate_sbm / generate_bipartite_graph, generate_geometric,
+ * generate_ba; graphem-rapids_amd/generators.py) ------------------------------------------------------------------
+ * Three random graph families whose every random decision is a counter-based word, so an edge list is a pure function
+ * of the parameters and the seed -- not of launch geometry, memory budget, scheduling, nor of whether the device or
+ * the host path ran -- and can be recomputed bit for bit in integer arithmetic.  With mix() of the influence section
+ * and G = 0x9E3779B97F4A7C15, uint64 wrapping arithmetic:
+ *     word(seed, i, j) = mix( mix(seed + (i + 1) * G) ^ j )          (i + 1: mix(0) = 0, and seed 0 is the default)
+ * No transcendental function sits between a word and a decision: doubles appear only in tables and thresholds that are
+ * computed once on the host with IEEE +, -, * alone (no fused multiply-add).
+ * Every result is the edge list with u < v, no duplicates, sorted by (u, v).
+ *
+ * Block model.  Blocks a = 0 .. B-1 of sizes[a] vertices, numbered block after block (block a starts at off[a]);
+ * P (B, B) row-major, symmetric, entries in [0, 1].  Block pairs are numbered q = 0, 1, .. in the order (0,0), (0,1), ..,
+ * (0,B-1), (1,1), .. (a <= b).  The pair space of block pair (a, b) has N vertex pairs, index i in [0, N):
+ *     a < b:   N = s_a * s_b;            i -> (off[a] + i / s_b,  off[b] + i % s_b)
+ *     a == b:  N = s (s - 1) / 2, h = (s - 1) / 2 (integer division);
+ *              i <  s * h:  r = i / h, c = i % h  -> { off + r, off + (r + 1 + c) % s }     (circulant layout)
+ *              i >= s * h:  r = i - s * h         -> { off + r, off + r + s / 2 }           (s even: the diameters)
+ * Each pair space is cut into segments of GH_GEN_SBM_SEGMENT indices (the last one shorter); segments are numbered
+ * g = 0, 1, .. through the block pairs in order (a block pair with N = 0 has none).  Gap table of a probability p, with
+ * q = 1 - p and pw[0] = 1, pw[k + 1] = pw[k] * q (doubles, one rounding per operation):
+ *     cdf[k] = (uint64) floor( (1 - pw[k + 1]) * 2^52 ),   k = 0 .. GH_GEN_SBM_TABLE - 1
+ * Segment g covering [lo, hi) of its pair space is walked with pos = lo, j = 0:
+ *     r = word(seed, g, j) >> 12; j += 1;  k = the number of table entries with cdf[k] <= r;
+ *     k == GH_GEN_SBM_TABLE (the tail):  pos += GH_GEN_SBM_TABLE          -- redraw; the geometric gap is memoryless
+ *     else:  pos += k;  if pos < hi: pair(pos) is an edge;  pos += 1
+ * until pos >= hi.  p = 0 gives no edge and p = 1 every pair, exactly.
+ *
+ * Random geometric graph.  Vertex i has the integer coordinates k_d(i) = word(seed, i, d) >> 40 (24 bits), d = 0 ..
+ * dim - 1, 1 <= dim <= 8; its position is k_d * 2^-24 (exact in float32).  (u, v) is an edge iff
+ *     sum over d of (k_d(u) - k_d(v))^2  <=  R2 = (uint64) floor( min(radius * radius, 16.0) * 2^48 ).
+ *
+ * Preferential attachment (networkx barabasi_albert_graph as a process), 1 <= m < n.  The endpoint list: slots
+ * 0 .. 2m-1 hold the star on vertices 0 .. m (slot 2i: vertex 0, slot 2i + 1: vertex i + 1); vertex v > m owns slots
+ * 2m(v - m) + 2t (holding v) and 2m(v - m) + 2t + 1 (holding its t-th accepted target), t = 0 .. m-1.  Vertex v draws
+ *     slot(v, a) = floor( word(seed, v, a) * 2m(v - m) / 2^64 ),   a = 0, 1, 2, ..
+ * and accepts the vertex in that slot as its next target unless it already holds it, until it holds m targets.  Edges:
+ * (0, i) for i = 1 .. m and (target, v); E = m (n - m).  On the device a vertex is finished in the first round in which
+ * every slot it draws belongs to the star, is an even slot, or belongs to a vertex finished in an EARLIER round (one
+ * launch per round; nothing waits on another workgroup); more than GH_GEN_BA_MAX_ROUNDS rounds is an error. */
+#define GH_GEN_SBM_SEGMENT 16384
+#define GH_GEN_SBM_TABLE 1024
+#define GH_GEN_BA_MAX_ROUNDS 4096
+typedef struct gh_gen *gh_gen_handle;
+
+/* device_id >= 0: kernels on that device.  device_id < 0: the host path (no device is touched), same edges bit for
+ * bit.  On failure *out = NULL and gh_gen_last_error(NULL) has the message. */
+gh_status gh_gen_create(gh_gen_handle *out, int device_id);
+void gh_gen_destroy(gh_gen_handle h);
+const char *gh_gen_last_error(gh_gen_handle h);
+/* Bytes a generator call may allocate for segment counts and edges (16 bytes per edge: the 64-bit keys u << 32 | v and
+ * the radix sort's second buffer).  0 restores the default, 4 GiB.  A graph that needs more returns GH_ERR_NOMEM with
+ * the figures in the message, decided from the count pass before any edge is written; nothing is truncated.  Results
+ * do not depend on it. */
+gh_status gh_gen_set_memory_budget(gh_gen_handle h, int64_t bytes);
+/* Each call replaces the handle's result and reports its edge count; vertex ids must fit int32 (n < 2^31).  Blocking.
+ * sizes: host int64[n_blocks], each >= 0; P: host double (n_blocks, n_blocks), symmetric. */
+gh_status gh_gen_sbm(gh_gen_handle h, int32_t n_blocks, const int64_t *sizes, const double *P, uint64_t seed,
+                     int64_t *n_edges);
+gh_status gh_gen_geometric(gh_gen_handle h, int64_t n, double radius, int32_t dim, uint64_t seed, int64_t *n_edges);
+/* rounds (may be NULL): launches the dependency resolution took (0 on the host path, which runs the process in order). */
+gh_status gh_gen_ba(gh_gen_handle h, int64_t n, int64_t m, uint64_t seed, int64_t *n_edges, int32_t *rounds);
+/* The last result: edges host int32 (E, 2); positions host float32 (n, dim) of the last gh_gen_geometric. */
+gh_status gh_gen_edges(gh_gen_handle h, int32_t *edges);
+gh_status gh_gen_positions(gh_gen_handle h, float *positions);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
