@@ -22,6 +22,7 @@
 //   gathers         two to four components: the positions once more with 32-byte rows (f64_pad4_kernel) for the spring
 //                   and midpoint kernels -- a neighbour's row is two 16-byte loads from one sector (321 -> 136 us).
 //   intersection    f64_intersect_kernel: pt.py:638-774 per candidate pair, double atomics into a dense (n, D) array
+//                   (an endpoint's offset from the pair's centre is taken as the mean of its four differences: no cancellation)
 //   update          f64_sum_kernel / f64_centre_kernel / f64_scale_kernel: new = pos + (Fs + Fi); column means, then
 //                   centred sums of squares (two passes, fixed-order reductions), unbiased std + 1e-6, divide.
 // Per-iteration cost at a million vertices (rocprofv3, round 5): spring 136 us, filter 134, midpoints 90, thresholds 61,
@@ -628,13 +629,16 @@ __global__ __launch_bounds__(256) void f64_intersect_kernel(const double *__rest
     const double *p1 = pos + (int64_t)v[0] * D, *p2 = pos + (int64_t)v[1] * D, *q1 = pos + (int64_t)v[2] * D, *q2 = pos + (int64_t)v[3] * D;
     const double o1 = f64_orient(p1, p2, q1), o2 = f64_orient(p1, p2, q2), o3 = f64_orient(q1, q2, p1), o4 = f64_orient(q1, q2, p2);
     if (!(o1 * o2 < 0.0 && o3 * o4 < 0.0)) return;                                      // pt.py:768-772
+    // x - (p1 + p2 + q1 + q2) / 4 (pt.py:722, 730) as the mean of the four differences x - p1 .. x - q2: the same value, but
+    // the sum of four positions is rounded at their magnitude, and on a cloud of 1e-9 around 5.0 that rounding (4e-15) is
+    // 4e-6 of the difference -- one step then ends 1.9e-5 from the exact iteration, as the reference's own float64 run does.
+    // The differences of nearby points are exact, their mean is good to its last bits.
     double diff[F64_MAXD];
     for (int role = 0; role < 4; ++role) {                                              // pt.py:722-734
         const double *x = pos + (int64_t)v[role] * D;
         double s = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double cen = (((p1[d] + p2[d]) + q1[d]) + q2[d]) / 4.0;
-            diff[d] = x[d] - cen;
+            diff[d] = ((((x[d] - p1[d]) + (x[d] - p2[d])) + (x[d] - q1[d])) + (x[d] - q2[d])) / 4.0;
             s = fma(diff[d], diff[d], s);
         }
         const double dist = sqrt(s) + 1e-6;

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import f64_reference as reference
 from conftest import GOLDEN_DIR
 
 pytestmark = pytest.mark.gpu
@@ -117,7 +118,8 @@ def test_float64_search_against_numpy_with_one_stripe_holding_the_best():
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,k,S,kind", [(3, 10, 64, "gauss"), (2, 5, 32, "gauss"), (5, 16, 48, "gauss"), (16, 32, 16, "gauss"),
                                         (7, 10, 16, "gauss"), (3, 10, 32, "collapsed"), (3, 10, 24, "clones"), (4, 10, 32, "gauss"),
-                                        (1, 5, 16, "gauss"), (2, 10, 32, "collapsed"), (3, 10, 16, "far")])
+                                        (1, 5, 16, "gauss"), (2, 10, 32, "collapsed"), (3, 10, 16, "far"), (6, 10, 32, "gauss"),
+                                        (8, 10, 32, "gauss")])
 def test_float64_filtered_search_equals_a_numpy_brute_force(D, k, S, kind):
     """From 131072 edges on the float64 engine searches through a filter (csrc/f64.hip: per query an exclusive bound from
     every stride-th midpoint, one reference-major pass over all midpoints that parks what lies below it, the exact
@@ -125,7 +127,9 @@ def test_float64_filtered_search_equals_a_numpy_brute_force(D, k, S, kind):
     (ties on the smaller id, column 0 dropped, pt.py:421) -- on a Gaussian cloud, on a cloud collapsed to 1e-9 around a
     far point (float keys of many distances coincide), and with every position shared by 64 vertices (ties in every
     row; parked lists overflow and the query falls back to the full passes), and on a cloud outside the f16 range of the
-    matrix-pipe pre-filter (two and three components: such midpoints are scanned in double, such queries take the full passes)."""
+    matrix-pipe pre-filter (two and three components: such midpoints are scanned in double, such queries take the full passes).
+    Every instantiation of the filter runs: matrix pipe (D = 2, 3), F64_FILTER(4, 4), (5, 2), (6, 2), (8, 2), (16, 2) and the
+    run-time one (D = 1, 7).  Then one step on those rows against tests/f64_reference.py."""
     import graphem_rapids_amd as gra
     from graphem_rapids_amd import _native
     rng = np.random.default_rng(D * 100 + k)
@@ -160,8 +164,15 @@ def test_float64_filtered_search_equals_a_numpy_brute_force(D, k, S, kind):
             assert np.allclose(a, b, rtol=1e-15, atol=0), (q, row, order)
             bad += 1
     assert bad <= (S if kind != "gauss" else 1)
-    # ... and the loop runs on it: three iterations equal an engine forced onto the full passes?  (there is no switch: the
-    # small-graph tests above cover the full passes; here the step must reproduce the rows' forces within double rounding)
+    # ... and the step runs on it (there is no switch onto the full passes: the small-graph tests above cover those): with
+    # the rows just checked, one step equals the extended-precision iteration of tests/f64_reference.py on exactly those
+    # rows, within the one-step bar of test_every_phase_and_one_step_in_float64.  (The two collapsed clouds measured 1.9e-5
+    # while f64_intersect_kernel subtracted the rounded centre (p1 + p2 + q1 + q2) / 4 from an endpoint 1e-9 away from it;
+    # 1.9e-14 since it averages the four differences.)
     eng.step(sampled)
-    assert np.isfinite(eng.get_positions()).all()
+    out = eng.get_positions()
     eng.close()
+    assert np.isfinite(out).all()
+    err = float(np.abs(out - reference.step(pos, edges, sampled, knn, 1.0, 0.2, 0.5)).max())
+    print(f"\nfiltered step D={D} k={k} S={S} {kind}: {err:.3e} of bar 1e-10")
+    assert err <= 1e-10
