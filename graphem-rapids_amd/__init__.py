@@ -19,6 +19,8 @@ from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influe
                         run_influence_benchmark)
 from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
                          eigenvector_centrality_numpy, run_benchmark, benchmark_correlations)
+from .visualization import (spearman_matrix, bootstrap_spearman, report_corr, report_full_correlation_matrix,
+                            plot_radial_vs_centrality, display_benchmark_results)
 
 __version__ = "0.1.0"
 
@@ -69,4 +71,6 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "generate_geometric", "generate_road_network", "generate_bipartite_graph", "generate_balanced_tree",
            "generate_caveman", "generate_relaxed_caveman", "sbm_edges", "bipartite_edges", "geometric_edges",
            "barabasi_albert_edges", "caveman_edges", "road_network_edges", "balanced_tree_edges",
-           "watts_strogatz_edges", "powerlaw_cluster_edges", "scale_free_edges", "relaxed_caveman_edges"]
+           "watts_strogatz_edges", "powerlaw_cluster_edges", "scale_free_edges", "relaxed_caveman_edges",
+           "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
+           "plot_radial_vs_centrality", "display_benchmark_results"]

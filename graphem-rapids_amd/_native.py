@@ -36,6 +36,8 @@ SYMBOLS = [
     "gh_cent_set_memory_budget", "gh_cent_paths", "gh_cent_pagerank", "gh_spmv_adj_shift",
     "gh_gen_create", "gh_gen_destroy", "gh_gen_last_error", "gh_gen_set_memory_budget", "gh_gen_sbm", "gh_gen_geometric",
     "gh_gen_ba", "gh_gen_edges", "gh_gen_positions",
+    "gh_corr_create", "gh_corr_destroy", "gh_corr_last_error", "gh_corr_set_memory_budget", "gh_corr_rho", "gh_corr_matrix",
+    "gh_corr_bootstrap",
 ]
 
 
@@ -280,6 +282,20 @@ def load():
     L.gh_gen_edges.restype = ctypes.c_int
     L.gh_gen_positions.argtypes = [vp, vp]
     L.gh_gen_positions.restype = ctypes.c_int
+    L.gh_corr_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i32, vp]
+    L.gh_corr_create.restype = ctypes.c_int
+    L.gh_corr_destroy.argtypes = [vp]
+    L.gh_corr_destroy.restype = None
+    L.gh_corr_last_error.argtypes = [vp]
+    L.gh_corr_last_error.restype = ctypes.c_char_p
+    L.gh_corr_set_memory_budget.argtypes = [vp, i64]
+    L.gh_corr_set_memory_budget.restype = ctypes.c_int
+    L.gh_corr_rho.argtypes = [i64, i64, i64]
+    L.gh_corr_rho.restype = ctypes.c_double
+    L.gh_corr_matrix.argtypes = [vp, vp, vp]
+    L.gh_corr_matrix.restype = ctypes.c_int
+    L.gh_corr_bootstrap.argtypes = [vp, i32, vp, i32, ctypes.c_uint64, vp, vp]
+    L.gh_corr_bootstrap.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -865,3 +881,69 @@ class Generator:
                                        ctypes.byref(rounds)))
         self.rounds = int(rounds.value)
         return self._edges(count.value)
+
+
+class Correlation:
+    """Thin RAII wrapper over a gh_corr_handle: Spearman's rho between the columns of one table, plain and over bootstrap
+    resamples (include/graphem_hip.h "rank correlation").  columns: (m, n) float64, one row per variable.  device_id < 0
+    is the library's host path, which touches no device and returns the same integers bit for bit."""
+
+    def __init__(self, columns, device_id=0):
+        self.lib = load()
+        self.handle = ctypes.c_void_p()
+        self.device_id = int(device_id)
+        cols = np.ascontiguousarray(columns, dtype=np.float64)
+        if cols.ndim != 2:
+            raise ValueError("columns must be (m, n)")
+        self.m, self.n = int(cols.shape[0]), int(cols.shape[1])
+        st = self.lib.gh_corr_create(ctypes.byref(self.handle), self.device_id, self.n, self.m, ptr(cols))
+        if st != GH_OK:
+            self.handle = ctypes.c_void_p()
+            self._raise(st)
+
+    def _raise(self, st):
+        if st == GH_OK:
+            return
+        msg = self.lib.gh_corr_last_error(self.handle if self.handle.value else None)
+        msg = msg.decode() if msg else f"gh_status {st}"
+        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self.lib.gh_corr_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-exception-caught
+            pass
+
+    def set_memory_budget(self, nbytes):
+        """Device bytes of replicate state a bootstrap call may hold (0: the default, 4 GiB); results do not depend on it."""
+        self._raise(self.lib.gh_corr_set_memory_budget(self.handle, int(nbytes)))
+
+    def matrix(self, sums=False):
+        """(m, m) float64 Spearman matrix of the plain statistic (gh_corr_matrix); with sums=True also the int64
+        (m, m, 3) triples (Sxy, Sxx, Syy)."""
+        out = np.zeros((self.m, self.m), dtype=np.float64)
+        trip = np.zeros((self.m, self.m, 3), dtype=np.int64) if sums else None
+        self._raise(self.lib.gh_corr_matrix(self.handle, ptr(out), ptr(trip)))
+        return (out, trip) if sums else out
+
+    def bootstrap(self, pairs, reps, seed=0, sums=False):
+        """(n_pairs, reps) float64 rho of every pair of columns in every resample (gh_corr_bootstrap); with sums=True also
+        the int64 (n_pairs, reps, 3) triples."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        reps = int(reps)
+        shape = (len(pairs), max(reps, 0))
+        out = np.zeros(shape, dtype=np.float64)
+        trip = np.zeros(shape + (3,), dtype=np.int64) if sums else None
+        self._raise(self.lib.gh_corr_bootstrap(self.handle, len(pairs), ptr(pairs), reps, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               ptr(out), ptr(trip)))
+        return (out, trip) if sums else out
+
+
+def corr_rho(sxy, sxx, syy):
+    """The library's conversion of a triple of sums to rho (gh_corr_rho)."""
+    return float(load().gh_corr_rho(int(sxy), int(sxx), int(syy)))

@@ -414,9 +414,13 @@ CORRELATION_KEYS = ("degree", "betweenness", "eigenvector", "pagerank", "closene
 
 
 def benchmark_correlations(graph_generator, graph_params, dim=2, L_min=10.0, k_attr=0.5, k_inter=0.1, n_neighbors=15,
-                           sample_size=512, num_iterations=40, backend="hip", *, betweenness_k=None, **kwargs):
+                           sample_size=512, num_iterations=40, backend="hip", *, betweenness_k=None, bootstrap_reps=None,
+                           bootstrap_seed=0, **kwargs):
     """The reference's benchmark_correlations (benchmark.py:163-243): run_benchmark, then Spearman's rho (and p) between
-    the radii and each centrality under results['correlations'][name] = {'rho', 'p'}."""
+    the radii and each centrality under results['correlations'][name] = {'rho', 'p'}.
+
+    bootstrap_reps: None -- exactly that; an int -- every entry also gets 'ci_low' and 'ci_high', the 2.5 and 97.5
+    percentiles of that many bootstrap replicates (visualization.bootstrap_spearman with seed bootstrap_seed)."""
     from scipy import stats
     results = run_benchmark(graph_generator, graph_params, dim=dim, L_min=L_min, k_attr=k_attr, k_inter=k_inter,
                             n_neighbors=n_neighbors, sample_size=sample_size, num_iterations=num_iterations,
@@ -426,5 +430,12 @@ def benchmark_correlations(graph_generator, graph_params, dim=2, L_min=10.0, k_a
     for name in CORRELATION_KEYS:
         rho, p = stats.spearmanr(radii, results[name])
         correlations[name] = {"rho": rho, "p": p}
+    if bootstrap_reps is not None:
+        from .visualization import bootstrap_spearman
+        _, _, ci_low, ci_high, _ = bootstrap_spearman(radii, [results[name] for name in CORRELATION_KEYS],
+                                                      reps=bootstrap_reps, seed=bootstrap_seed)
+        for j, name in enumerate(CORRELATION_KEYS):
+            correlations[name]["ci_low"] = float(ci_low[j])
+            correlations[name]["ci_high"] = float(ci_high[j])
     results["correlations"] = correlations
     return results

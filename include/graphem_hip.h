@@ -614,6 +614,54 @@ gh_status gh_gen_ba(gh_gen_handle h, int64_t n, int64_t m, uint64_t seed, int64_
 gh_status gh_gen_edges(gh_gen_handle h, int32_t *edges);
 gh_status gh_gen_positions(gh_gen_handle h, float *positions);
 
+/* ---- rank correlation (reference visualization.py: report_corr, report_full_correlation_matrix;
+ * graphem-rapids_amd/visualization.py) ------------------------------------------------------------------------------
+ * Spearman's rho between columns of one table, plain and over bootstrap resamples, in exact integer arithmetic.
+ *
+ * Columns: m >= 1 columns of n doubles, 2 <= n <= GH_CORR_MAX_N (so that n^3 < 2^63), all finite.  Values compare as
+ * IEEE doubles: -0.0 and 0.0 tie.  A tie group of a column is a maximal set of points with equal value.
+ *
+ * Resample b (0 <= b < reps), with word() of the generator section:
+ *     idx(b, j) = floor( word(seed, b, j) * n / 2^64 ),  j = 0 .. n-1          (128-bit product, high word)
+ *     c_i       = the number of j with idx(b, j) = i                            (the sum of c is n)
+ * The plain statistic is the case c_i = 1 for all i.
+ *
+ * For a column and a weight vector c, with the groups in ascending value order, C_g = the sum of c over group g and
+ * B_g = the sum of C over the groups before g:
+ *     u_i = 2 * B_g(i) + C_g(i) - n          (an integer; = 2 * midrank - (n + 1); the weighted mean of u is exactly 0)
+ * For a pair of columns (x, y) with u from x and v from y:
+ *     Sxy = sum c_i u_i v_i,   Sxx = sum c_i u_i^2,   Syy = sum c_i v_i^2                      (exact in int64)
+ *     rho = NaN if Sxx = 0 or Syy = 0, else (double)Sxy / sqrt((double)Sxx * (double)Syy)      (gh_corr_rho)
+ * The device computes the three integers; the conversion to double is gh_corr_rho on the host for both paths, so
+ * device and host agree bit for bit.  Results depend only on (columns, pairs, reps, seed): not on batch size, memory
+ * budget, sort stability, launch geometry, nor on whether the device or the host path ran. */
+#define GH_CORR_MAX_N 2097151
+typedef struct gh_corr *gh_corr_handle;
+
+/* columns: host double (m, n) row-major.  device_id >= 0: kernels on that device; device_id < 0: the host path (no
+ * device is touched).  Each column is prepared once: an order-preserving 64-bit key per value, a sort, and for every
+ * sorted position the start and end of its tie group.  GH_ERR_INVALID for a NaN or an infinity, for n < 2 and for
+ * n > GH_CORR_MAX_N (larger tables need 128-bit sums).  On failure *out = NULL and gh_corr_last_error(NULL) has the
+ * message. */
+gh_status gh_corr_create(gh_corr_handle *out, int device_id, int64_t n, int32_t m, const double *columns);
+void gh_corr_destroy(gh_corr_handle h);
+const char *gh_corr_last_error(gh_corr_handle h);
+/* Device bytes of replicate state gh_corr_bootstrap may hold: about 4 n + 8 n per column in use + 24 per pair, per
+ * replicate processed at once, at least one replicate.  0 restores the default, 4 GiB.  GH_ERR_INVALID for a negative value.
+ * Results do not depend on it; the host path ignores it. */
+gh_status gh_corr_set_memory_budget(gh_corr_handle h, int64_t bytes);
+/* The conversion both paths use. */
+double gh_corr_rho(int64_t sxy, int64_t sxx, int64_t syy);
+/* The m x m matrix of the plain statistic: out host double (m, m), symmetric, diagonal 1 (NaN for a constant column).
+ * sums: NULL or host int64 (m, m, 3), the triple (Sxy, Sxx, Syy) of every entry (row = x, column = y).  Blocking. */
+gh_status gh_corr_matrix(gh_corr_handle h, double *out, int64_t *sums);
+/* pairs: host int32 (n_pairs, 2) of column ids; out: host double (n_pairs, reps), rho of every pair in every resample.
+ * Replicate b uses one c for all pairs.  sums: NULL or host int64 (n_pairs, reps, 3).  Replicates are processed in
+ * batches sized by the memory budget; only columns that occur in `pairs` are ranked.  GH_ERR_INVALID for reps < 1,
+ * n_pairs < 1, a column id outside [0, m).  Blocking. */
+gh_status gh_corr_bootstrap(gh_corr_handle h, int32_t n_pairs, const int32_t *pairs, int32_t reps, uint64_t seed,
+                            double *out, int64_t *sums);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
