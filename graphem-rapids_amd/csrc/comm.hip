@@ -1,10 +1,16 @@
-// The partitioned layout loop without the host language in it:
-// gh_run_partitioned enqueues, per iteration, part 1 (spring pull + KNN scan of the own rows / edges), the
-// all-gather of the ranks' S x (k+1) keys, part 2 (merge, intersection forces, integrate own rows) and then
+// The partitioned layout loop without the host language in it: gh_run_partitioned
+// enqueues all iterations' kernels and collectives, no host synchronisation inside the loop.  It is the one statement in C
+// of the order that exchange_schedule (distributed.py) states for the Python-driven step.  Per iteration: part 1 (spring
+// pull + KNN scan of the own rows / edges), the all-gather of the ranks' S x (k+1) keys, part 2 (merge, intersection forces,
+// integrate own rows) and then
+//   form D (gh_overlap_layout, the default): the all-gather of the new0 = pos + Fs blocks of part 1 went out BEFORE the keys,
+//                              on a side stream and a communicator of its own (or goes now, on the engine's stream: no fused
+//                              kernel in part 1, or no second communicator); all-gather of statistics + patch lists (the
+//                              finished own rows the intersection phase touched); wait for the rows; patch lists over the
+//                              gathered rows, normalise all n rows;
 //   form C (gh_rank_layout):   all-gather of the ranks' column statistics (a few hundred bytes), normalise the OWN rows,
-//                              in-place all-gather of the finished position blocks;
-//   form B (gh_gather_layout): in-place all-gather of the ranks' slots (new rows + statistics), normalise all n rows --
-// kernels and collectives on ONE stream, no host synchronisation inside the loop.
+//                              all-gather of the finished position blocks, in place or without their pad columns + unpack;
+//   form B (gh_gather_layout): in-place all-gather of the ranks' slots (new rows + statistics), normalise all n rows.
 //
 // Collective backends behind one small interface:
 //   RCCL      ncclAllGather on the engine's stream.  librccl.so is opened at gh_comm_init_rccl() (dlopen), so the
@@ -262,6 +268,13 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
     // a rank that fails leaves the loop: the loopback group must not wait for it (RCCL has its own abort paths)
     auto run = [&]() -> gh_status {
         const size_t stats_bytes = sizeof(double) * (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
+        // form D: the own block of new0, packed to its travelling form, to every rank -- on the side stream or the engine's
+        auto send_rows = [&](bool side) -> gh_status {
+            const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
+            unsigned char *rows = reinterpret_cast<unsigned char *>(gh_rows_all_device(h));
+            GH_TRY_ST(gh_launch_pack_rows(h, side ? c->stream_b : h->stream));
+            return comm_all_gather(h, rows + (size_t)c->rank * block, rows, block, "allgather_rows", side);
+        };
         for (int32_t t = 0; t < iters; ++t) {
             GH_TRY_ST(gh_step_begin_device_ids(h, d_ids ? d_ids + (size_t)t * h->S : nullptr));
             // form D: new0 = pos + Fs of the own rows is complete -- its all-gather starts here, on the side stream when there
@@ -269,17 +282,14 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
             // beside select -> keys -> merge + intersection -> statistics
             const bool early = h->layout == GH_LAYOUT_OVERLAP && gh_step_rows_early(h);
             const bool side = early && c->stream_b && (c->nccl_b || c->loop);
-            if (early && (side || c->loop)) {
-                const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
-                unsigned char *rows = reinterpret_cast<unsigned char *>(gh_rows_all_device(h));
+            const bool rows_sent = early && (side || c->loop);
+            if (rows_sent) {
                 if (side) {
                     if (hipEventRecord(c->ev_fused, h->stream) != hipSuccess || hipStreamWaitEvent(c->stream_b, c->ev_fused, 0) != hipSuccess) { h->err = "form D: event hand-off failed"; return GH_ERR_HIP; }
                 }
-                GH_TRY_ST(gh_launch_pack_rows(h, side ? c->stream_b : h->stream));
-                GH_TRY_ST(comm_all_gather(h, rows + (size_t)c->rank * block, rows, block, "allgather_rows", side));
+                GH_TRY_ST(send_rows(side));
                 if (side && hipEventRecord(c->ev_rows, c->stream_b) != hipSuccess) { h->err = "form D: event record failed"; return GH_ERR_HIP; }
             }
-            const bool rows_sent = early && (side || c->loop);
             if (h->S > 0 && h->k > 0) {
                 GH_TRY_ST(comm_all_gather(h, h->d_partial, c->d_gathered, key_bytes, "allgather_keys"));
                 GH_TRY_ST(gh_step_merge(h, c->d_gathered, c->world));
@@ -287,12 +297,8 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
                 GH_TRY_ST(gh_step_merge(h, h->d_partial, 1));   // spring forces only: nothing to merge
             }
             if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: (the rows went out above, or go now)
-                const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
-                unsigned char *rows = reinterpret_cast<unsigned char *>(gh_rows_all_device(h));
-                if (!rows_sent) {   // a step without new0 (no fused kernel), or RCCL without a second communicator: form B's order
-                    GH_TRY_ST(gh_launch_pack_rows(h, h->stream));
-                    GH_TRY_ST(comm_all_gather(h, rows + (size_t)c->rank * block, rows, block, "allgather_rows"));
-                }
+                // a step without new0 (no fused kernel), or RCCL without a second communicator: form B's order
+                if (!rows_sent) GH_TRY_ST(send_rows(false));
                 GH_TRY_ST(comm_all_gather(h, h->d_stats, h->d_stats_all, sizeof(double) * (size_t)h->stats_block, "allgather_stats"));   // statistics + patch list
                 if (early && side) {   // what of the early all-gather is still outstanding is this iteration's EXPOSED collective time
                     gh_scope t(h, "allgather_rows_exposed");

@@ -7,32 +7,13 @@ belongs to one of its two endpoints, picked by a fixed hash of the edge id, and 
 holding that endpoint's row (`edge_ownership="hashed"`: ~E/world edges per rank whatever the
 vertex numbering); with `edge_ownership="range"` a rank owns the edges whose first endpoint it
 holds (a contiguous range of the sorted edge list -- for a u<v edge list rank 0 then holds
-most of the edges).  Every rank holds all n positions and the whole edge list.  Per iteration:
+most of the edges).  Every rank holds all n positions and the whole edge list.
 
-    part 1  (local)   spring pull of own rows + midpoints of own edges; exact KNN of the S
-                      sampled midpoints among the OWN edges -> S x (k+1) keys
-    gather  (RCCL)    all-gather of the keys                       S*(k+1)*8 B per rank
-    part 2  (local)   merge keys -> global KNN; intersection forces (redundant on every rank,
-                      O(S*k)); integrate own rows; own column sums
-  finish="own" (round 3-4; nothing passes over all n rows, three collectives in a row):
-    gather  (RCCL)    all-gather of the ranks' column statistics          18*ld*8 B per rank
-    part 3  (local)   normalise the OWN rows into their block of the position array; the per-rank sums
-                      are added in rank order, so every rank derives the same mean / std
-    gather  (RCCL)    in-place all-gather of the finished position blocks     chunk*D*4 B per rank
-                      (without their pad columns when D < ld -- 12 instead of 16 B per row at D = 3 --, then
-                      expanded into the position array by gh_step_unpack_rows; chunk*ld*4 B when D == ld)
-  finish="overlap" (default; round 5, form D): the LAST collective of finish="gathered" moved to the front
-    part 1  (local)   as above; the fused kernel leaves new0 = pos + Fs of the own rows in this rank's block
-    gather  (RCCL, 2nd stream + 2nd group)   all-gather of the new0 blocks (chunk*D*4 B per rank) -- IN FLIGHT while
-    gather  (RCCL)    all-gather of the keys
-    part 2  (local)   merge; intersection forces; own corrections to the statistics; the finished values of the own touched
-                      rows (pos + (Fs + Fi), <= 4*S*k of them) into the rank's patch list, behind its statistics
-    gather  (RCCL)    all-gather of statistics + patch lists                    ~ (18*ld*8 + min(4*S*k, chunk)*(1+ld)*4) B per rank
-    part 3  (local)   wait for the rows; every rank's patch list over the gathered rows; normalise ALL n rows (next set-up in
-                      the same launch)
-  finish="gathered" (two collectives, every rank normalises all n rows -- 22-51 us per rank at 1 M vertices):
-    gather  (RCCL)    in-place all-gather of slots [un-normalised rows | statistics]
-    part 3  (local)   normalise ALL n rows from the gathered slots
+A step is local compute interleaved with all-gathers, in an order that depends on the finish ("own", form C: every rank
+normalises its own rows; "gathered", form B: one collective of slots, every rank normalises all n rows; "overlap", form
+D, the default: form B's rows travel first, beside the KNN tail).  That order is stated once, by `exchange_schedule`
+below; PartitionedLayout.step performs its exchanges with torch.distributed, step_in_process with device copies between
+several engines of one process (tests, tools).  DESIGN.md section 6 has the byte counts and the reasons.
 
 The loop can also run inside the C library (`native=True`): gh_run_partitioned (csrc/comm.hip) enqueues kernels
 and ncclAllGather calls of all iterations on one stream -- RCCL opened by the library itself, its communicator
@@ -45,6 +26,8 @@ The sample ids are the same on every rank: either passed in, or drawn by the eng
 based sampler from (seed, iteration).  The compute engine is injectable so that the collective
 choreography can be tested with the gloo backend on CPUs (tests/test_distributed_cpu.py).
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -131,6 +114,7 @@ class HipShardEngine:
         from .embedder_hip import device_view
         e = self.eng
         e.gather_layout(world, rank, chunk)
+        self.world, self.rank, self.chunk = world, rank, chunk
         self.gbuf = device_view(e.gather_buffer_device_ptr(), (world, e.gather_slot_bytes()), torch.uint8, self.device, e)
         self.stats = device_view(e.stats_partial_device_ptr(), (e.stats_rows(), e.ld), torch.float64, self.device, e)
 
@@ -213,6 +197,80 @@ class HipShardEngine:
     def run_partitioned(self, iters, sample_stream=None):
         self.eng.run_partitioned(iters, sample_stream)
         self.eng.sync()   # the engine's own stream: torch knows nothing of it, so nothing may be pending when we return
+
+
+# One collective of a step: `send` goes to every rank, `recv` receives the ranks' blocks in rank order (concatenated form:
+# what both the RCCL and the gloo backend accept).  side: the exchange may go on a side stream and a process group of its
+# own; its driver then makes the `pack` call on the stream it chose, in front of the collective.
+Exchange = namedtuple("Exchange", "name send recv side pack", defaults=(False, None))
+JOIN = Exchange("join", None, None)   # the side stream's exchange must have arrived before the schedule goes on
+
+
+def exchange_schedule(e, finish, gathered, sampled=None):
+    """One step of one rank's engine `e` (after its gather_layout / rank_layout / overlap_layout call; `gathered`: this
+    engine's (world, S, key columns) receive buffer for the ranks' keys): runs the local
+    phases and yields an Exchange wherever a collective must happen -- THE statement of a partitioned step's order
+    (csrc/comm.hip, gh_run_partitioned, is its one counterpart in C).
+
+      gathered (B):  keys -> merge -> slots [un-normalised rows | statistics] -> normalise all n rows
+      own (C):       keys -> merge -> statistics -> normalise the own rows -> finished blocks, padded in place in the position
+                     array or without their pad columns and then expanded
+      overlap (D):   rows new0 = pos + Fs (on the side, in flight beside:) -> keys -> merge -> statistics + patch lists -> JOIN
+                     -> patch lists over the gathered rows, normalise all n rows.  A step without the fused kernel has no
+                     new0: its rows go after the merge, their intersection forces in them, and nothing is joined."""
+    def in_place(name, blocks, **kw):   # the rank's own block is where it will be received
+        return Exchange(name, blocks[e.rank], blocks.view(-1), **kw)
+
+    e.step_begin(sampled)
+    early = finish == "overlap" and e.step_rows_early()
+    if early:
+        yield in_place("rows", e.rows_all, side=True, pack=e.step_pack_rows)
+    yield Exchange("keys", e.partial, gathered.flatten(0, 1))
+    e.step_merge(gathered, e.world)
+    if finish == "overlap":
+        if not early:
+            e.step_pack_rows()
+            yield in_place("rows", e.rows_all)
+        yield Exchange("stats", e.stats.view(-1), e.stats_all.view(-1))   # (block `rank` of stats_all)
+        if early:
+            yield JOIN
+        e.step_finish_overlap()
+    elif finish == "own":
+        yield Exchange("stats", e.stats.view(-1), e.stats_all.view(-1))
+        e.step_finish_own(e.stats_all)
+        packed = getattr(e, "packed_blocks", None)
+        if packed is not None:
+            yield in_place("blocks", packed)
+            e.step_unpack_rows()
+        else:
+            yield in_place("blocks", e.pos_blocks)
+    else:
+        yield in_place("slots", e.gbuf)
+        e.step_finish_gathered()
+
+
+def step_in_process(shards, finish, sampled=None, after=None):
+    """One step of the engines of ALL ranks in this process, in lock step on the current stream, every all-gather a device
+    copy (tests and tools on one GPU).  after: {exchange name: callable}, called when that exchange has been made."""
+    def keys(sh):   # a receive buffer per rank, as in a real run
+        return torch.empty((len(shards), *sh.partial.shape), dtype=sh.partial.dtype, device=sh.partial.device)
+    schedules = [exchange_schedule(sh, finish, keys(sh), sampled) for sh in shards]
+    while True:
+        xs = [next(s, None) for s in schedules]
+        names = {x.name if x else None for x in xs}
+        assert len(names) == 1, f"the ranks' schedules disagree: {names}"
+        if xs[0] is None:
+            return
+        if xs[0] is JOIN:   # (nothing went on a side stream)
+            continue
+        for x in xs:
+            if x.pack:
+                x.pack()
+        sent = torch.stack([x.send.reshape(-1) for x in xs])   # a copy: the in-place gathers send from their receive views
+        for x in xs:
+            x.recv.view(len(xs), -1).copy_(sent)
+        if after and xs[0].name in after:
+            after[xs[0].name]()
 
 
 class PartitionedLayout:
@@ -324,62 +382,32 @@ class PartitionedLayout:
         if self.native:
             self.engine.run_partitioned(1, None if sampled is None else np.asarray(sampled, dtype=np.int32)[None, :])
             return
-        e = self.engine
-        e.step_begin(sampled)
-        if self.finish == "overlap":
-            self._step_overlap(e)
-            return
-        # output in concatenated form (world*S, K): accepted by both the RCCL and the gloo backend
-        dist.all_gather_into_tensor(self.gathered.view(self.world * self.S, self.key_cols), e.partial, group=self.group)
-        e.step_merge(self.gathered, self.world)
-        if self.finish == "own":
-            dist.all_gather_into_tensor(e.stats_all.view(-1), e.stats.view(-1), group=self.group)   # concatenated form: RCCL and gloo
-            e.step_finish_own(e.stats_all)
-            packed = getattr(e, "packed_blocks", None)
-            if packed is not None:   # the blocks without their pad columns, then expanded into the position array
-                dist.all_gather_into_tensor(packed.view(-1), packed[self.rank], group=self.group)
-                e.step_unpack_rows()
-                return
-            # in-place all-gather of the finished blocks: rank r's rows are block r of the position array
-            dist.all_gather_into_tensor(e.pos_blocks.view(-1), e.pos_blocks[self.rank], group=self.group)
-            return
-        # in-place all-gather of the slots: rank r's new rows + statistics sit in row r of gbuf
-        dist.all_gather_into_tensor(e.gbuf.view(-1), e.gbuf[self.rank], group=self.group)
-        e.step_finish_gathered()
-
-    def _step_overlap(self, e):
-        """Form D: the all-gather of the new0 blocks goes out first -- on the engine's side stream and the rows' own process
-        group when there is a GPU, so that it is in flight beside everything up to the statistics."""
-        early = e.step_rows_early()
-        side = getattr(e, "side", None) if early else None
-        rows_group = self.rows_group if self.rows_group is not None else self.group
-
-        def send_rows(stream):
-            e.step_pack_rows(stream)
-            dist.all_gather_into_tensor(e.rows_all.view(-1), e.rows_all[self.rank], group=rows_group if stream is not None else self.group)
-
-        if early and side is not None:
-            side.wait_stream(torch.cuda.current_stream(side.device))   # the fused kernel's new0
-            with torch.cuda.stream(side):
-                send_rows(side)
-        elif early:
-            send_rows(None)
-        dist.all_gather_into_tensor(self.gathered.view(self.world * self.S, self.key_cols), e.partial, group=self.group)
-        e.step_merge(self.gathered, self.world)
-        if not early:   # no fused kernel in part 1: the rows travel with their intersection forces in them
-            send_rows(None)
-        dist.all_gather_into_tensor(e.stats_all.view(-1), e.stats.view(-1), group=self.group)
-        if early and side is not None:
-            cur = torch.cuda.current_stream(side.device)
-            if self.time_overlap:
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(cur)
-                cur.wait_stream(side)
-                b.record(cur)
-                self.exposed_events.append((a, b))
+        # (only a GPU engine after overlap_layout has a side stream; only form D's early rows and their JOIN ask for it)
+        side = getattr(self.engine, "side", None)
+        for x in exchange_schedule(self.engine, self.finish, self.gathered, sampled):
+            if x is JOIN:
+                if side is not None:
+                    self._join(side)
+            elif x.side and side is not None:   # in flight beside everything up to the join: a process group of its own
+                side.wait_stream(torch.cuda.current_stream(side.device))   # the fused kernel's new0
+                with torch.cuda.stream(side):
+                    x.pack(side)
+                    dist.all_gather_into_tensor(x.recv, x.send, group=self.rows_group if self.rows_group is not None else self.group)
             else:
-                cur.wait_stream(side)
-        e.step_finish_overlap()
+                if x.pack:
+                    x.pack()
+                dist.all_gather_into_tensor(x.recv, x.send, group=self.group)
+
+    def _join(self, side):
+        cur = torch.cuda.current_stream(side.device)
+        if self.time_overlap:   # what is left of the rows' all-gather here is the step's exposed collective time
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(cur)
+            cur.wait_stream(side)
+            b.record(cur)
+            self.exposed_events.append((a, b))
+        else:
+            cur.wait_stream(side)
 
     def run(self, iters, sample_stream=None):
         if self.native:

@@ -178,7 +178,7 @@ def test_cdist_on_row_partitions_gives_the_references_rows(world, n, D, k, S, ki
     ATen-mode step."""
     import torch
     import graphem_rapids_amd as gra
-    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
     from graphem_rapids_amd import _native
     rng = np.random.default_rng(n + 17 * world + k)
     edges = np.ascontiguousarray(gra.random_regular_edges(n, 8, seed=D + k), dtype=np.int32)
@@ -194,28 +194,21 @@ def test_cdist_on_row_partitions_gives_the_references_rows(world, n, D, k, S, ki
         sh.rank_layout(world, r, chunk)
         sh.set_positions(pos)
         shards.append(sh)
-    for sh in shards:
-        sh.step_begin(sampled)
-    gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-    for sh in shards:
-        sh.step_merge(gathered, world)
     listed = []
-    for r, sh in enumerate(shards):
-        knn = sh.merged_knn()
-        bad = np.nonzero(~(knn == want).all(axis=1))[0]
-        assert len(bad) == 0, f"rank {r}: {len(bad)} rows differ; first: row {bad[0]}\n  hip  {knn[bad[0]]}\n  aten {want[bad[0]]}"
-        full, unresolved = sh.eng.knn_cdist_stats()
-        assert unresolved == 0
-        listed.append(full)
-    assert len(set(listed)) == 1          # every rank lists the same rows
+
+    def merged_rows():   # between the merge of the keys and the finish
+        for r, sh in enumerate(shards):
+            knn = sh.merged_knn()
+            bad = np.nonzero(~(knn == want).all(axis=1))[0]
+            assert len(bad) == 0, f"rank {r}: {len(bad)} rows differ; first: row {bad[0]}\n  hip  {knn[bad[0]]}\n  aten {want[bad[0]]}"
+            full, unresolved = sh.eng.knn_cdist_stats()
+            assert unresolved == 0
+            listed.append(full)
+
+    step_in_process(shards, "own", sampled, after={"stats": merged_rows})
+    assert len(listed) == world and len(set(listed)) == 1   # every rank lists the same rows
     if kind.startswith("lattice"):
         assert listed[0] > 0              # the tie path was really taken
-    stats_all = torch.stack([sh.stats.clone() for sh in shards]).contiguous()
-    for sh in shards:
-        sh.step_finish_own(stats_all)
-    blocks = torch.stack([sh.pos_blocks[r].clone() for r, sh in enumerate(shards)])
-    for sh in shards:
-        sh.pos_blocks.copy_(blocks)
     torch.cuda.synchronize()
     ref = oracle.step_aten(pos, edges, sampled, k)
     outs = [sh.get_positions() for sh in shards]

@@ -220,7 +220,7 @@ def _partitioned_steps(finish, world, n, D, edges, pos, k, S, samples, packed=No
     collectives emulated with device copies.  Yields every rank's positions after each step."""
     import torch
     from graphem_rapids_amd import _native
-    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
     shards = []
     for r in range(world):
         chunk, lo, hi = partition_rows(n, world, r)
@@ -235,41 +235,11 @@ def _partitioned_steps(finish, world, n, D, edges, pos, k, S, samples, packed=No
         shards.append(sh)
     try:
         for sampled in samples:
-            for sh in shards:
-                sh.step_begin(sampled)
-            if finish == "overlap":
-                assert all(sh.step_rows_early() for sh in shards)
-                for sh in shards:
-                    sh.step_pack_rows()
-                rows = torch.stack([sh.rows_all[r].clone() for r, sh in enumerate(shards)])
-                for sh in shards:
-                    sh.rows_all.copy_(rows)
-            gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-            for sh in shards:
-                sh.step_merge(gathered, world)
-            if finish == "overlap":
-                stats = torch.stack([sh.stats_all[r].clone() for r, sh in enumerate(shards)])
-                for sh in shards:
-                    sh.stats_all.copy_(stats)
-                    sh.step_finish_overlap()
-            elif finish == "own":
-                stats_all = torch.stack([sh.stats.clone() for sh in shards]).contiguous()
-                for sh in shards:
-                    sh.step_finish_own(stats_all)
-                if shards[0].packed_blocks is not None and packed:
-                    blocks = torch.stack([sh.packed_blocks[r].clone() for r, sh in enumerate(shards)])
-                    for sh in shards:
-                        sh.packed_blocks.copy_(blocks)
-                        sh.step_unpack_rows()
-                else:
-                    blocks = torch.stack([sh.pos_blocks[r].clone() for r, sh in enumerate(shards)])
-                    for sh in shards:
-                        sh.pos_blocks.copy_(blocks)
-            else:
-                slots = torch.stack([sh.gbuf[r].clone() for r, sh in enumerate(shards)])
-                for sh in shards:
-                    sh.gbuf.copy_(slots)
-                    sh.step_finish_gathered()
+            order = []
+            step_in_process(shards, finish, sampled, after={x: (lambda x=x: order.append(x)) for x in ("rows", "keys")})
+            assert order == (["rows", "keys"] if finish == "overlap" else ["keys"])   # form D: every rank's rows went early
+            if finish == "own":
+                assert (shards[0].packed_blocks is not None) == bool(packed and D < shards[0].ld)
             torch.cuda.synchronize()
             yield [sh.get_positions() for sh in shards]
     finally:

@@ -270,7 +270,7 @@ def test_partitioned_engines_equal_single_engine(world, rule, n, D, finish):
     ownership rules of gh_partition."""
     import torch
     from graphem_rapids_amd import _native
-    from graphem_rapids_amd.distributed import HipShardEngine, owned_edge_ids, partition_edges, partition_rows
+    from graphem_rapids_amd.distributed import HipShardEngine, owned_edge_ids, partition_edges, partition_rows, step_in_process
     k, S = 10, 256
     edges, pos, _ = _random_case(n - 1, D, 8, k, S, seed=21)  # last vertex isolated
     if rule == "hashed-hubs":   # two hubs (in different row blocks) on top, and an edge between them
@@ -313,55 +313,15 @@ def test_partitioned_engines_equal_single_engine(world, rule, n, D, finish):
         shards[-1].set_positions(pos)
     assert owned == len(edges)  # every edge searched by exactly one rank
     for t in range(3):
-        for sh in shards:
-            sh.step_begin(stream[t])
+        order = []   # (every rank's schedule names the same exchange at every point: step_in_process checks it)
+        step_in_process(shards, finish, stream[t], after={x: (lambda x=x: order.append(x)) for x in ("rows", "keys")})
         if finish == "overlap":
             # form D: the new0 blocks travel FIRST, then keys, merge, statistics + patch lists (the owners' finished touched
             # rows); every rank writes the patch lists over the gathered rows and normalises all n rows
-            def exchange_rows():
-                for sh in shards:
-                    sh.step_pack_rows()
-                rows = torch.stack([sh.rows_all[r].clone() for r, sh in enumerate(shards)])
-                for sh in shards:
-                    sh.rows_all.copy_(rows)
-            early = shards[0].step_rows_early()
-            assert all(sh.step_rows_early() == early for sh in shards)
-            assert early      # (a rank without the fused kernel -- the 2001-vertex graph -- makes new0 with a launch of its own)
-            if early:
-                exchange_rows()
-            gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-            for sh in shards:
-                sh.step_merge(gathered, world)
-            if not early:
-                exchange_rows()
-            stats = torch.stack([sh.stats_all[r].clone() for r, sh in enumerate(shards)])
-            for sh in shards:
-                sh.stats_all.copy_(stats)
-                sh.step_finish_overlap()
-            continue
-        gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-        for sh in shards:
-            sh.step_merge(gathered, world)
-        if finish == "own":   # all-gather of the statistics, own rows normalised, in-place all-gather of the blocks
-            stats_all = torch.stack([sh.stats.clone() for sh in shards]).contiguous()
-            for sh in shards:
-                sh.step_finish_own(stats_all)
-            if shards[0].packed_blocks is not None:   # D < ld: the blocks travel without their pad columns, then are expanded
-                assert D < shards[0].ld
-                packed = torch.stack([sh.packed_blocks[r].clone() for r, sh in enumerate(shards)])
-                for sh in shards:
-                    sh.packed_blocks.copy_(packed)
-                    sh.step_unpack_rows()
-                continue
-            assert D == shards[0].ld
-            blocks = torch.stack([sh.pos_blocks[r].clone() for r, sh in enumerate(shards)])
-            for sh in shards:
-                sh.pos_blocks.copy_(blocks)
-            continue
-        slots = torch.stack([sh.gbuf[r].clone() for r, sh in enumerate(shards)])   # the all-gather of the slots
-        for sh in shards:
-            sh.gbuf.copy_(slots)
-            sh.step_finish_gathered()
+            # (a rank without the fused kernel -- the 2001-vertex graph -- makes new0 with a launch of its own)
+            assert order == ["rows", "keys"]
+        if finish == "own":   # D < ld: the blocks travel without their pad columns, then are expanded
+            assert (shards[0].packed_blocks is not None) == (D < shards[0].ld)
     torch.cuda.synchronize()
     tol = 2e-6
     for sh in shards:
@@ -786,7 +746,7 @@ def test_random_partitioned_configurations(seed, finish):
     (one collective of slots) and form D (rows early, statistics + patch lists late)."""
     import torch
     from graphem_rapids_amd import _native
-    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
     rng = np.random.default_rng(3000 + seed)
     world = int(rng.choice([2, 3, 5]))
     n = int(rng.integers(6000, 25000))
@@ -815,27 +775,7 @@ def test_random_partitioned_configurations(seed, finish):
         sh.set_positions(pos)
         shards.append(sh)
     for t in range(3):
-        for sh in shards:
-            sh.step_begin(first if t == 0 else None)
-        if finish == "overlap":
-            for sh in shards:
-                sh.step_pack_rows()
-            rows = torch.stack([sh.rows_all[r].clone() for r, sh in enumerate(shards)])
-            for sh in shards:
-                sh.rows_all.copy_(rows)
-        gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-        for sh in shards:
-            sh.step_merge(gathered, world)
-        if finish == "overlap":
-            stats = torch.stack([sh.stats_all[r].clone() for r, sh in enumerate(shards)])
-            for sh in shards:
-                sh.stats_all.copy_(stats)
-                sh.step_finish_overlap()
-            continue
-        slots = torch.stack([sh.gbuf[r].clone() for r, sh in enumerate(shards)])
-        for sh in shards:
-            sh.gbuf.copy_(slots)
-            sh.step_finish_gathered()
+        step_in_process(shards, finish, first if t == 0 else None)
     torch.cuda.synchronize()
     outs = [sh.get_positions() for sh in shards]
     for sh in shards:

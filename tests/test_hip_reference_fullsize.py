@@ -162,13 +162,13 @@ def test_partitioned_engine_refuses_whole_graph_calls():
 
 def test_c4_rr4m_eight_row_partitions_equal_one_engine():
     """BASELINE configs[3]: random-regular n = 4 M, d = 8 (E = 16 M), D = 3, row-partitioned over 8 ranks.
-    Eight partitioned engines on ONE GPU with the two collectives of a step emulated by device copies must
+    Eight partitioned engines on ONE GPU with the three collectives of a step emulated by device copies must
     reproduce the single engine (the oracle of the multi-GPU mode), and the single engine's spring
     forces and KNN ids must equal the CPU oracle's exactly at this size."""
     import torch
     import graphem_rapids_amd as gra
     from graphem_rapids_amd import _native
-    from graphem_rapids_amd.distributed import HipShardEngine, owned_edge_ids, partition_rows
+    from graphem_rapids_amd.distributed import HipShardEngine, owned_edge_ids, partition_rows, step_in_process
     n, D, k, S, world = 4_000_000, 3, 10, 256, 8
     edges = np.ascontiguousarray(gra.random_regular_edges(n, 8, seed=0), dtype=np.int32)
     assert len(edges) == 16_000_000
@@ -197,17 +197,8 @@ def test_c4_rr4m_eight_row_partitions_equal_one_engine():
         shards[-1].rank_layout(world, r, chunk)
         shards[-1].set_positions(pos)
     for t in range(2):
-        for sh in shards:
-            sh.step_begin(stream[t])
-        gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()   # all-gather of the keys
-        for sh in shards:
-            sh.step_merge(gathered, world)
-        stats_all = torch.stack([sh.stats.clone() for sh in shards]).contiguous()    # all-gather of the statistics
-        for sh in shards:
-            sh.step_finish_own(stats_all)
-        blocks = torch.stack([sh.pos_blocks[r].clone() for r, sh in enumerate(shards)])   # in-place all-gather of the blocks
-        for sh in shards:
-            sh.pos_blocks.copy_(blocks)
+        step_in_process(shards, "own", stream[t])   # all-gathers of the keys, the statistics and the finished blocks
+    assert shards[0].packed_blocks is not None   # (the blocks travelled without pad columns: the library's default from 2 M vertices)
     torch.cuda.synchronize()
     first = shards[0].get_positions()
     assert np.abs(first - ref).max() <= 2e-6

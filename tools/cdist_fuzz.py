@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np, torch
 import graphem_rapids_amd as gra
 from graphem_rapids_amd import _native
-from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
 import oracle
 from test_hip_cdist import _positions
 
@@ -47,13 +47,13 @@ for c in range(N):
             sh.rank_layout(world, r, chunk)
             sh.set_positions(pos)
             shards.append(sh)
-        for sh in shards:
-            sh.step_begin(sampled)
-        gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-        for sh in shards:
-            sh.step_merge(gathered, world)
-        got = [sh.merged_knn() for sh in shards]
-        full, unresolved = shards[0].eng.knn_cdist_stats()
+        got, counts = [], []
+
+        def merged_rows():   # between the merge of the keys and the finish
+            got.extend(sh.merged_knn() for sh in shards)
+            counts.append(shards[0].eng.knn_cdist_stats())
+        step_in_process(shards, "own", sampled, after={"stats": merged_rows})
+        full, unresolved = counts[0]
         for sh in shards:
             sh.eng.close()
     nbad = max(int((~(g == want).all(axis=1)).sum()) for g in got)

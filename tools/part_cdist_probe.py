@@ -1,10 +1,10 @@
 """Parity mode on row partitions, what rank 0 computes after the all-gather of the keys: `world` engines on ONE GPU (the
-all-gather emulated by stacking the ranks' records), a few iterations from the reference's start, then the engine's
+all-gathers emulated by device copies), a few iterations from the reference's start, then the engine's
 HIP-event timers of rank 0's merge + prefix + replay.  Usage: python tools/part_cdist_probe.py [workload] [world ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
-from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
 from graphem_rapids_amd import _native
 
 wl = sys.argv[1] if len(sys.argv) > 1 else "rr1m"
@@ -26,18 +26,7 @@ for world in worlds:
         sampled = rng.permutation(E)[:S].astype(np.int32)
         if t == 2:
             shards[0].eng.timing_reset()
-        for sh in shards:
-            sh.step_begin(sampled)
-        gathered = torch.stack([sh.partial.clone() for sh in shards]).contiguous()
-        for sh in shards:
-            sh.step_merge(gathered, world)
-        listed.append(shards[0].eng.knn_cdist_stats()[0])
-        stats_all = torch.stack([sh.stats.clone() for sh in shards]).contiguous()
-        for sh in shards:
-            sh.step_finish_own(stats_all)
-        blocks = torch.stack([sh.pos_blocks[r].clone() for r, sh in enumerate(shards)])
-        for sh in shards:
-            sh.pos_blocks.copy_(blocks)
+        step_in_process(shards, "own", sampled, after={"stats": lambda: listed.append(shards[0].eng.knn_cdist_stats()[0])})
     torch.cuda.synchronize()
     tm = {kk: round(1e3 * tot / cnt, 1) for kk, (tot, cnt) in shards[0].eng.timings().items()}
     print(wl, "world", world, "listed rows per iteration", listed, "rank 0 kernels (us):", tm)

@@ -12,7 +12,7 @@ all-gather on the side stream."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
-from graphem_rapids_amd.distributed import HipShardEngine, partition_rows
+from graphem_rapids_amd.distributed import JOIN, HipShardEngine, exchange_schedule, partition_rows
 
 wl = sys.argv[1] if len(sys.argv) > 1 else "rr1m"
 finish = sys.argv[2] if len(sys.argv) > 2 else "own"
@@ -26,43 +26,23 @@ for world in (1, 2, 4, 8):
         sh.set_positions(pos)
         gathered = torch.empty((world, S, k + 1), dtype=torch.int64, device="cuda")
 
-        def it_overlap():
-            sh.step_begin(None)
-            sh.step_pack_rows()
-            # stand-in for the early all-gather: every rank's block like this one's (as the form-B stand-in below: the statistics
-            # are world x this rank's sums, so the layout stays a layout; torch copies, not on the timers)
-            sh.rows_all.copy_(sh.rows_all[rank].expand_as(sh.rows_all).clone())
-            for w in range(world):
-                gathered[w].copy_(sh.partial)
-            sh.step_merge(gathered, world)
-            st = sh.stats_all[rank].clone()
-            for w in range(world):
-                sh.stats_all[w].copy_(st)                  # every rank's sums like this one's: the totals stay those of a layout
-            sh.step_finish_overlap()
-
         def it():
-            if finish == "overlap":
-                return it_overlap()
-            sh.step_begin(None)
-            for w in range(world):
-                gathered[w].copy_(sh.partial)              # stand-in for the all-gather of the keys
-            sh.step_merge(gathered, world)
-            if finish == "own":
-                for w in range(world):
-                    sh.stats_all[w].copy_(sh.stats)        # stand-in for the all-gather of the statistics
-                sh.stats_all[1:].zero_()                   # (one rank's sums count once: rows of the others are absent anyway)
-                sh.step_finish_own(sh.stats_all)
-                if sh.packed_blocks is not None:           # the receiving side of the unpadded block exchange
-                    # (stand-in for the all-gather: the other ranks' blocks = their current rows, so that the layout this
-                    # rank keeps computing on stays a layout; torch copies, not on the engine's timers)
-                    pk = sh.packed_blocks.view(world, chunk, D)
-                    own = pk[rank].clone()
+            # the schedule of a step with a one-rank stand-in for every all-gather (torch copies, not on the engine's timers):
+            # the other ranks' blocks like this one's, so that the layout this rank keeps computing on stays a layout
+            for x in exchange_schedule(sh, finish, gathered):
+                if x is JOIN:
+                    continue
+                if x.pack:
+                    x.pack()
+                recv = x.recv.view(world, -1)
+                if x.name != "blocks":
+                    recv.copy_(x.send.reshape(1, -1).expand_as(recv).clone())
+                    if x.name == "stats" and finish == "own":   # one rank's sums count once (rows of the others are absent anyway)
+                        recv[1:].zero_()
+                elif sh.packed_blocks is not None:   # the receiving side of the unpadded block exchange: the other ranks'
+                    pk, own = recv.view(world, chunk, D), x.send.view(chunk, D).clone()   # blocks = their current rows
                     pk.copy_(sh.pos[: world * chunk].view(world, chunk, sh.ld)[:, :, :D])
                     pk[rank].copy_(own)
-                    sh.step_unpack_rows()
-            else:
-                sh.gbuf.copy_(sh.gbuf[rank].expand_as(sh.gbuf).clone())
-                sh.step_finish_gathered()
         for _ in range(5):
             it()
         torch.cuda.synchronize()
