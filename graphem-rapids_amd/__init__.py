@@ -19,6 +19,10 @@ from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influe
                         run_influence_benchmark)
 from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
                          eigenvector_centrality_numpy, run_benchmark, benchmark_correlations)
+from . import graphstats
+from .graphstats import (connected_components, number_connected_components, is_connected, largest_connected_component,
+                         eccentricity, diameter, radius, average_shortest_path_length, triangles, clustering,
+                         average_clustering, transitivity, graph_summary, print_graph_summary)
 from .visualization import (spearman_matrix, bootstrap_spearman, report_corr, report_full_correlation_matrix,
                             plot_radial_vs_centrality, display_benchmark_results)
 
@@ -72,5 +76,8 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "generate_caveman", "generate_relaxed_caveman", "sbm_edges", "bipartite_edges", "geometric_edges",
            "barabasi_albert_edges", "caveman_edges", "road_network_edges", "balanced_tree_edges",
            "watts_strogatz_edges", "powerlaw_cluster_edges", "scale_free_edges", "relaxed_caveman_edges",
+           "graphstats", "connected_components", "number_connected_components", "is_connected",
+           "largest_connected_component", "eccentricity", "diameter", "radius", "average_shortest_path_length",
+           "triangles", "clustering", "average_clustering", "transitivity", "graph_summary", "print_graph_summary",
            "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
            "plot_radial_vs_centrality", "display_benchmark_results"]

@@ -34,6 +34,7 @@ SYMBOLS = [
     "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
     "gh_cent_create", "gh_cent_destroy", "gh_cent_last_error", "gh_cent_edge_count", "gh_cent_csr_device",
     "gh_cent_set_memory_budget", "gh_cent_paths", "gh_cent_pagerank", "gh_spmv_adj_shift",
+    "gh_cent_components", "gh_cent_distances", "gh_cent_triangles",
     "gh_gen_create", "gh_gen_destroy", "gh_gen_last_error", "gh_gen_set_memory_budget", "gh_gen_sbm", "gh_gen_geometric",
     "gh_gen_ba", "gh_gen_edges", "gh_gen_positions",
     "gh_corr_create", "gh_corr_destroy", "gh_corr_last_error", "gh_corr_set_memory_budget", "gh_corr_rho", "gh_corr_matrix",
@@ -262,6 +263,12 @@ def load():
     L.gh_cent_paths.restype = ctypes.c_int
     L.gh_cent_pagerank.argtypes = [vp, ctypes.c_double, i32, ctypes.c_double, vp, ctypes.POINTER(i32)]
     L.gh_cent_pagerank.restype = ctypes.c_int
+    L.gh_cent_components.argtypes = [vp, vp, ctypes.POINTER(i64)]
+    L.gh_cent_components.restype = ctypes.c_int
+    L.gh_cent_distances.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.gh_cent_distances.restype = ctypes.c_int
+    L.gh_cent_triangles.argtypes = [vp, vp]
+    L.gh_cent_triangles.restype = ctypes.c_int
     L.gh_spmv_adj_shift.argtypes = [vp, i64, vp, vp, ctypes.c_double, vp, vp]
     L.gh_spmv_adj_shift.restype = ctypes.c_int
     L.gh_gen_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
@@ -742,6 +749,32 @@ class CentGraph:
         its = ctypes.c_int32(0)
         self._raise(self.lib.gh_cent_pagerank(self.handle, float(alpha), int(max_iter), float(tol), ptr(x), ctypes.byref(its)))
         return x, int(its.value)
+
+    def components(self):
+        """(labels (n,) int32, n_components): labels[v] = the smallest vertex id in v's component (gh_cent_components)."""
+        labels = np.zeros(self.n, dtype=np.int32)
+        count = ctypes.c_int64(0)
+        self._raise(self.lib.gh_cent_components(self.handle, ptr(labels), ctypes.byref(count)))
+        return labels, int(count.value)
+
+    def distances(self, sources, reached=True, dist_sum=True, eccentricity=True):
+        """Breadth-first levels from `sources` (gh_cent_distances): (reached (S,) int64, dist_sum (S,) int64, eccentricity
+        (S,) int32); a part not asked for is None."""
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64).ravel())
+        if len(src) and (src.min() < 0 or src.max() >= self.n):
+            raise ValueError(f"source ids must lie in [0, {self.n})")
+        src = src.astype(np.int32)
+        cnt = np.zeros(len(src), dtype=np.int64) if reached else None
+        dsum = np.zeros(len(src), dtype=np.int64) if dist_sum else None
+        ecc = np.zeros(len(src), dtype=np.int32) if eccentricity else None
+        self._raise(self.lib.gh_cent_distances(self.handle, len(src), ptr(src), ptr(cnt), ptr(dsum), ptr(ecc)))
+        return cnt, dsum, ecc
+
+    def triangles(self):
+        """(n,) int64 triangles through every vertex (gh_cent_triangles)."""
+        tri = np.zeros(self.n, dtype=np.int64)
+        self._raise(self.lib.gh_cent_triangles(self.handle, ptr(tri)))
+        return tri
 
     def csr_device(self):
         """(indptr, indices) device pointers of the handle's symmetric CSR."""

@@ -186,6 +186,29 @@ class CentralityGraph:
             ld = ld * (self.n / k)
         return {"betweenness": bc, "load": ld, "closeness": closeness_from(reached, dsum, self.n, wf_improved)}
 
+    def component_labels(self):
+        """(n,) int32: the smallest vertex id in every vertex's connected component (gh_cent_components)."""
+        if self._g is None:
+            return np.zeros(0, dtype=np.int32)
+        return self._g.components()[0]
+
+    def distances(self, sources=None):
+        """Breadth-first levels from vertex ids `sources` (None: every vertex; gh_cent_distances): (reached (S,) int64,
+        dist_sum (S,) int64, eccentricity (S,) int32).  reached counts the source itself; for a source that does not
+        reach every vertex, eccentricity is its greatest finite distance."""
+        src = np.arange(self.n, dtype=np.int64) if sources is None else np.asarray(sources, dtype=np.int64).ravel()
+        if len(src) and (src.min() < 0 or src.max() >= self.n):
+            raise ValueError(f"source ids must lie in [0, {self.n})")
+        if self._g is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32)
+        return self._g.distances(src)
+
+    def triangle_counts(self):
+        """(n,) int64: the number of triangles through every vertex (gh_cent_triangles)."""
+        if self._g is None:
+            return np.zeros(0, dtype=np.int64)
+        return self._g.triangles()
+
     def pagerank(self, alpha=0.85, max_iter=100, tol=1e-6, return_iterations=False):
         """networkx pagerank(G, alpha, max_iter=max_iter, tol=tol) (_pagerank_scipy): raises
         PowerIterationFailedConvergence when max_iter iterations do not converge."""

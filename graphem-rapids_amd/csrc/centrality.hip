@@ -33,11 +33,11 @@
 #include <vector>
 
 #include "../../include/graphem_hip.h"
+#include "cent_handle.h"
 
 #define CENT_BLOCK 256
 #define CENT_MAX_BLOCKS 4096
 #define CENT_CHECK_EVERY 4            // forward levels between two host reads of the level flags
-#define CENT_DEFAULT_BUDGET (1ll << 30)
 #define CENT_SRC_CHUNK 1024           // vertices per workgroup of the per-source sums
 #define PR_BLOCK 256
 #define PR_MAX_BLOCKS 2048
@@ -302,23 +302,6 @@ inline int cent_blocks(int64_t waves) {
 }
 
 }  // namespace
-
-struct gh_cent {
-    int device = 0;
-    int64_t n = 0, edges = 0;
-    hipStream_t stream = nullptr;
-    int64_t *d_ptr = nullptr;
-    int32_t *d_adj = nullptr;
-    double *d_inv_deg = nullptr;
-    int64_t budget = CENT_DEFAULT_BUDGET;
-    // path state for G groups, grown on demand
-    int64_t cap_groups = 0;
-    int32_t *d_dist = nullptr, *d_npred = nullptr, *d_flags = nullptr, *d_src = nullptr;
-    double *d_sigma = nullptr, *d_delta = nullptr, *d_lam = nullptr;
-    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
-    int2 *d_range = nullptr;
-    std::string err;
-};
 
 static thread_local std::string g_cent_error;
 

@@ -1,0 +1,372 @@
+// Graph statistics on the GPU (include/graphem_hip.h "graph statistics"; graphem-rapids_amd/graphstats.py): connected
+// components, hop distances from many sources, and triangles per vertex, over the centrality handle's deduplicated
+// symmetric CSR (neighbours ascending).  Everything is an integer: no result depends on the order of an atomic.
+//
+// Components.  label[v] starts as v and only ever drops, to the id of a vertex of v's component.
+//   gs_hook_kernel   m = the smallest label among v and its neighbours; when m < label[v], atomicMin m onto
+//                    label[label[v]] (the tree's root, once the trees are stars) and onto label[v].
+//   gs_jump_kernel   pointer jumping: label[v] = the root of v's tree (follow label[] until it points at itself).  Roots
+//                    are not written here, so every tree is a star afterwards.
+//   A round that hooks nothing saw label[u] == label[v] on every arc of a forest of stars: one root per component, and
+//   since label[x] <= x stays inside the component, that root is the component's smallest id.  Round r runs only when
+//   round r - 1 set its flag; the host reads the flags every GS_CHECK_EVERY rounds.
+//
+// Distances.  64 sources to a group; bit b of a word belongs to source 64 g + b.  Per (group, vertex) three words,
+// [group][vertex]: vis (sources that reached v; the unused bits of a short last group preset), cur and nxt (sources
+// whose frontier holds v at the previous / this level).  Lane = vertex, so the 64 words a wave holds are one group's.
+//   gs_level_kernel (L)   nxt[v] = (OR of cur over the neighbours) & ~vis[v], always stored, so the ping-pong buffers need
+//                         no clearing.  The wave transposes its 64 new words with 64 ballots: lane b adds the population
+//                         count of bit b to a register, over a grid-stride loop; then, per source, integer atomics:
+//                         reached += count, dist_sum += L count, eccentricity = max(., L).  Sets flags[L] when anything
+//                         was reached; a launch after the last level sees flags[L - 1] == 0 and returns.
+//
+// Triangles.  One thread per arc (u, v) with u < v: the shorter of the two rows, from its first entry above v, is searched
+// in the longer one by bisection (the window shrinks as both ascend), so an arc costs min(deg) log(max deg).  Every
+// triangle u < v < w is found once, at its arc (u, v), and credited to its three vertices with 64-bit integer atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/graphem_hip.h"
+#include "cent_handle.h"
+
+#define GS_BLOCK 256
+#define GS_MAX_BLOCKS 4096
+#define GS_CHECK_EVERY 4   // component rounds / distance levels between two host reads of the flags
+
+namespace {
+
+typedef unsigned long long gs_u64;
+
+__device__ __forceinline__ int32_t gs_flag(const int32_t *f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+#define GS_GRID_LOOP(i, items) \
+    for (int64_t i = (int64_t)blockIdx.x * GS_BLOCK + threadIdx.x; i < (items); i += (int64_t)gridDim.x * GS_BLOCK)
+
+// ---- components -----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GS_BLOCK) void gs_label_init_kernel(int64_t n, int32_t *label) {
+    GS_GRID_LOOP(v, n) label[v] = (int32_t)v;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void gs_hook_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ adj,
+                                                           int32_t *label, int32_t *flags, int32_t r) {
+    if (gs_flag(&flags[r - 1]) == 0) return;
+    GS_GRID_LOOP(v, n) {
+        const int32_t lv = label[v];
+        int32_t m = lv;
+        const int64_t beg = ptr[v], end = ptr[v + 1];
+        for (int64_t k = beg; k < end; ++k) m = min(m, label[adj[k]]);
+        if (m < lv) {
+            atomicMin(&label[lv], m);
+            atomicMin(&label[v], m);
+            if (gs_flag(&flags[r]) == 0) flags[r] = 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void gs_jump_kernel(int64_t n, int32_t *label, const int32_t *flags, int32_t r) {
+    if (gs_flag(&flags[r]) == 0) return;
+    GS_GRID_LOOP(v, n) {
+        int32_t l = label[v];
+        for (;;) {
+            const int32_t p = label[l];
+            if (p == l) break;
+            l = p;
+        }
+        label[v] = l;
+    }
+}
+
+// ---- distances ------------------------------------------------------------------------------------------------------
+struct GsLevel {
+    const int64_t *ptr; const int32_t *adj;
+    uint64_t *vis; const uint64_t *cur; uint64_t *nxt;
+    int32_t *flags;              // flags[L] = 1: level L reached something
+    gs_u64 *reached, *dist_sum;  // per source of the batch
+    int32_t *ecc;
+    int64_t n;
+    int32_t level;
+};
+
+// vis = the unused bits of the batch's last group, 0 elsewhere; cur = 0
+__global__ __launch_bounds__(GS_BLOCK) void gs_dist_fill_kernel(int64_t n, int64_t G, uint64_t unused_last, uint64_t *vis, uint64_t *cur) {
+    GS_GRID_LOOP(i, G * n) {
+        vis[i] = i >= (G - 1) * n ? unused_last : 0;
+        cur[i] = 0;
+    }
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void gs_dist_seed_kernel(int64_t n, int64_t n_src, const int32_t *__restrict__ sources, gs_u64 *vis,
+                                                                gs_u64 *cur, gs_u64 *reached, gs_u64 *dist_sum, int32_t *ecc) {
+    GS_GRID_LOOP(j, n_src) {
+        const int64_t w = (j >> 6) * n + sources[j];
+        const gs_u64 bit = 1ull << (j & 63);
+        atomicOr(&vis[w], bit);
+        atomicOr(&cur[w], bit);
+        reached[j] = 1;
+        dist_sum[j] = 0;
+        ecc[j] = 0;
+    }
+}
+
+// grid (x, G): the waves of row g stride over the vertices, 64 at a time
+__global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(GsLevel a) {
+    if (gs_flag(&a.flags[a.level - 1]) == 0) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = blockIdx.y, off = g * a.n;
+    uint64_t *vis = a.vis + off, *nxt = a.nxt + off;
+    const uint64_t *cur = a.cur + off;
+    const int64_t stride = (int64_t)gridDim.x * GS_BLOCK;
+    uint32_t cnt = 0;   // lane b: vertices that source 64 g + b reached at this level (< 2^31)
+    for (int64_t base = (int64_t)blockIdx.x * GS_BLOCK + (threadIdx.x & ~63); base < a.n; base += stride) {
+        const int64_t v = base + lane;
+        uint64_t w = 0;
+        if (v < a.n) {
+            const uint64_t need = ~vis[v];
+            if (need) {
+                uint64_t acc = 0;
+                const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
+                for (int64_t k = beg; k < end; ++k) acc |= cur[a.adj[k]];
+                w = acc & need;
+                if (w) vis[v] = ~need | w;
+            }
+            nxt[v] = w;
+        }
+        if (__ballot(w != 0) == 0) continue;
+#pragma unroll 8
+        for (int b = 0; b < 64; ++b) {
+            const uint64_t col = __ballot((w >> b) & 1);
+            if (lane == b) cnt += (uint32_t)__popcll(col);
+        }
+    }
+    if (cnt) {
+        const int64_t j = g * 64 + lane;
+        atomicAdd(&a.reached[j], (gs_u64)cnt);
+        atomicAdd(&a.dist_sum[j], (gs_u64)cnt * (gs_u64)a.level);
+        atomicMax(&a.ecc[j], a.level);
+        if (gs_flag(&a.flags[a.level]) == 0) a.flags[a.level] = 1;
+    }
+}
+
+// ---- triangles ------------------------------------------------------------------------------------------------------
+// first position in [lo, hi) whose entry is >= x
+__device__ __forceinline__ int64_t gs_lower_bound(const int32_t *__restrict__ a, int64_t lo, int64_t hi, int32_t x) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void gs_triangle_kernel(int64_t n, int64_t arcs, const int64_t *__restrict__ ptr,
+                                                               const int32_t *__restrict__ adj, gs_u64 *tri) {
+    GS_GRID_LOOP(e, arcs) {
+        const int32_t v = adj[e];
+        int64_t lo = 0, hi = n;   // the row of arc e: the last u with ptr[u] <= e
+        while (hi - lo > 1) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (ptr[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        const int32_t u = (int32_t)lo;
+        if (v <= u) continue;
+        const int64_t ub = ptr[u], ue = ptr[u + 1], vb = ptr[v], ve = ptr[v + 1];
+        const bool u_short = ue - ub <= ve - vb;
+        int64_t sb = u_short ? ub : vb, lb = u_short ? vb : ub;
+        const int64_t se = u_short ? ue : ve, le = u_short ? ve : ue;
+        sb = gs_lower_bound(adj, sb, se, v + 1);
+        lb = gs_lower_bound(adj, lb, le, v + 1);
+        gs_u64 c = 0;
+        for (int64_t k = sb; k < se && lb < le; ++k) {
+            const int32_t w = adj[k];
+            lb = gs_lower_bound(adj, lb, le, w);
+            if (lb < le && adj[lb] == w) {
+                ++c;
+                atomicAdd(&tri[w], 1ull);
+            }
+        }
+        if (c) {
+            atomicAdd(&tri[u], c);
+            atomicAdd(&tri[v], c);
+        }
+    }
+}
+
+inline int gs_blocks(int64_t items) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(GS_MAX_BLOCKS, (items + GS_BLOCK - 1) / GS_BLOCK));
+}
+
+#define GS_HIP(call)                                                                   \
+    do {                                                                               \
+        const hipError_t e_ = (call);                                                  \
+        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
+    } while (0)
+
+// frees its device buffers when a call returns, on every path
+struct GsBuffers {
+    std::vector<void *> p;
+    ~GsBuffers() { for (void *q : p) (void)hipFree(q); }
+    template <typename T> bool alloc(T **out, size_t bytes) {
+        void *q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return false;
+        p.push_back(q);
+        *out = (T *)q;
+        return true;
+    }
+};
+
+gh_status gs_components(gh_cent *h, int32_t *labels) {
+    const int64_t n = h->n;
+    GsBuffers buf;
+    int32_t *d_label = nullptr, *d_flags = nullptr;
+    if (!buf.alloc(&d_label, 4 * n) || !buf.alloc(&d_flags, 4 * (GS_CHECK_EVERY + 1))) {
+        h->err = "hipMalloc failed for the component labels";
+        return GH_ERR_NOMEM;
+    }
+    const int grid = gs_blocks(n);
+    const int32_t one = 1;
+    GS_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
+    gs_label_init_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label);
+    GS_HIP(hipGetLastError());
+    // a round that hooks lowers a label, so n rounds bound the loop from far above
+    for (int64_t done = 0;; done += GS_CHECK_EVERY) {
+        if (done > n + GS_CHECK_EVERY) { h->err = "component labels did not settle"; return GH_ERR_RUNTIME; }
+        GS_HIP(hipMemsetAsync(d_flags + 1, 0, 4 * GS_CHECK_EVERY, h->stream));
+        for (int32_t r = 1; r <= GS_CHECK_EVERY; ++r) {
+            gs_hook_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, h->d_ptr, h->d_adj, d_label, d_flags, r);
+            gs_jump_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label, d_flags, r);
+        }
+        GS_HIP(hipGetLastError());
+        int32_t last = 0;
+        GS_HIP(hipMemcpyAsync(&last, d_flags + GS_CHECK_EVERY, 4, hipMemcpyDeviceToHost, h->stream));
+        GS_HIP(hipStreamSynchronize(h->stream));
+        if (!last) break;
+    }
+    GS_HIP(hipMemcpyAsync(labels, d_label, 4 * n, hipMemcpyDeviceToHost, h->stream));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    return GH_OK;
+}
+
+// One batch of G groups holding ns <= 64 G sources; d_out: reached, dist_sum, eccentricity of the batch's sources.
+gh_status gs_distance_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, uint64_t *d_vis, uint64_t *d_fa, uint64_t *d_fb,
+                            int32_t *d_flags, int32_t *d_src, gs_u64 *d_reached, gs_u64 *d_dsum, int32_t *d_ecc) {
+    const int64_t n = h->n;
+    GS_HIP(hipMemcpyAsync(d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
+    GS_HIP(hipMemsetAsync(d_flags, 0, 4 * (n + 2), h->stream));
+    const int32_t one = 1;
+    GS_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
+    const int64_t in_last = ns - 64 * (G - 1);
+    const uint64_t unused_last = in_last < 64 ? ~0ull << in_last : 0;
+    gs_dist_fill_kernel<<<dim3(gs_blocks(G * n)), dim3(GS_BLOCK), 0, h->stream>>>(n, G, unused_last, d_vis, d_fa);
+    gs_dist_seed_kernel<<<dim3(gs_blocks(ns)), dim3(GS_BLOCK), 0, h->stream>>>(n, ns, d_src, (gs_u64 *)d_vis, (gs_u64 *)d_fa, d_reached,
+                                                                              d_dsum, d_ecc);
+    GS_HIP(hipGetLastError());
+    GsLevel a{};
+    a.ptr = h->d_ptr; a.adj = h->d_adj;
+    a.vis = d_vis; a.flags = d_flags;
+    a.reached = d_reached; a.dist_sum = d_dsum; a.ecc = d_ecc;
+    a.n = n;
+    const int64_t per_row = std::max<int64_t>(1, GS_MAX_BLOCKS / G);
+    const dim3 grid((unsigned)std::min<int64_t>(per_row, (n + GS_BLOCK - 1) / GS_BLOCK), (unsigned)G);
+    // level L can reach something only while L <= n - 1
+    std::vector<int32_t> fl(GS_CHECK_EVERY);
+    for (int64_t L = 1, checked = 0; L <= n - 1; ++L) {
+        a.level = (int32_t)L;
+        a.cur = (L & 1) ? d_fa : d_fb;
+        a.nxt = (L & 1) ? d_fb : d_fa;
+        gs_level_kernel<<<grid, dim3(GS_BLOCK), 0, h->stream>>>(a);
+        GS_HIP(hipGetLastError());
+        if (L % GS_CHECK_EVERY == 0 || L == n - 1) {
+            const int64_t cnt = L - checked;
+            GS_HIP(hipMemcpyAsync(fl.data(), d_flags + checked + 1, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
+            GS_HIP(hipStreamSynchronize(h->stream));
+            if (std::find(fl.begin(), fl.begin() + cnt, 0) != fl.begin() + cnt) break;
+            checked = L;
+        }
+    }
+    return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_cent_components(gh_cent_handle h, int32_t *labels, int64_t *n_components) {
+    if (!h) return GH_ERR_INVALID;
+    if (!labels && h->n > 0) { h->err = "labels must not be NULL"; return GH_ERR_INVALID; }
+    if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GH_ERR_RUNTIME; }
+    if (h->n > 0) {
+        const gh_status st = gs_components(h, labels);
+        if (st != GH_OK) { (void)hipStreamSynchronize(h->stream); return st; }
+    }
+    if (n_components) {
+        int64_t c = 0;
+        for (int64_t v = 0; v < h->n; ++v) c += labels[v] == v;
+        *n_components = c;
+    }
+    return GH_OK;
+}
+
+extern "C" gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, const int32_t *sources, int64_t *reached,
+                                       int64_t *dist_sum, int32_t *eccentricity) {
+    if (!h) return GH_ERR_INVALID;
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (n_sources < 0 || (n_sources > 0 && !sources)) return fail(GH_ERR_INVALID, "bad source list");
+    for (int64_t i = 0; i < n_sources; ++i)
+        if (sources[i] < 0 || sources[i] >= h->n) return fail(GH_ERR_INVALID, "source id outside [0, n)");
+    if (n_sources == 0 || (!reached && !dist_sum && !eccentricity)) return GH_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    const int64_t n = h->n, groups = (n_sources + 63) / 64;
+    int64_t G = std::max<int64_t>(1, h->budget / (24 * n));   // 3 words per (group, vertex)
+    G = std::min<int64_t>({G, groups, (int64_t)65535});       // 65535: grid.y
+    GsBuffers buf;
+    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
+    int32_t *d_flags = nullptr, *d_src = nullptr, *d_ecc = nullptr;
+    gs_u64 *d_cnt = nullptr;
+    if (!buf.alloc(&d_vis, 8 * G * n) || !buf.alloc(&d_fa, 8 * G * n) || !buf.alloc(&d_fb, 8 * G * n) || !buf.alloc(&d_flags, 4 * (n + 2)) ||
+        !buf.alloc(&d_src, 4 * 64 * G) || !buf.alloc(&d_cnt, 16 * 64 * groups) || !buf.alloc(&d_ecc, 4 * 64 * groups))
+        return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(G) + " source groups of distance state");
+    gh_status st = GH_OK;
+    for (int64_t g0 = 0; g0 < groups && st == GH_OK; g0 += G) {
+        const int64_t gb = std::min(G, groups - g0);
+        const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
+        st = gs_distance_batch(h, gb, sources + 64 * g0, ns, d_vis, d_fa, d_fb, d_flags, d_src, d_cnt + 64 * g0,
+                               d_cnt + 64 * groups + 64 * g0, d_ecc + 64 * g0);
+    }
+    auto copy_back = [&]() -> gh_status {
+        if (reached) GS_HIP(hipMemcpyAsync(reached, d_cnt, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        if (dist_sum) GS_HIP(hipMemcpyAsync(dist_sum, d_cnt + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        if (eccentricity) GS_HIP(hipMemcpyAsync(eccentricity, d_ecc, 4 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        GS_HIP(hipStreamSynchronize(h->stream));
+        return GH_OK;
+    };
+    if (st == GH_OK) st = copy_back();
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
+    return st;
+}
+
+extern "C" gh_status gh_cent_triangles(gh_cent_handle h, int64_t *triangles) {
+    if (!h) return GH_ERR_INVALID;
+    if (!triangles && h->n > 0) { h->err = "triangles must not be NULL"; return GH_ERR_INVALID; }
+    if (h->n == 0) return GH_OK;
+    if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GH_ERR_RUNTIME; }
+    const int64_t n = h->n, arcs = 2 * h->edges;
+    GsBuffers buf;
+    gs_u64 *d_tri = nullptr;
+    if (!buf.alloc(&d_tri, 8 * n)) { h->err = "hipMalloc failed for the triangle counts"; return GH_ERR_NOMEM; }
+    auto run = [&]() -> gh_status {
+        GS_HIP(hipMemsetAsync(d_tri, 0, 8 * n, h->stream));
+        if (arcs > 0) {
+            gs_triangle_kernel<<<dim3(gs_blocks(arcs)), dim3(GS_BLOCK), 0, h->stream>>>(n, arcs, h->d_ptr, h->d_adj, d_tri);
+            GS_HIP(hipGetLastError());
+        }
+        GS_HIP(hipMemcpyAsync(triangles, d_tri, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        GS_HIP(hipStreamSynchronize(h->stream));
+        return GH_OK;
+    };
+    const gh_status st = run();
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
+    return st;
+}

@@ -548,6 +548,31 @@ gh_status gh_cent_pagerank(gh_cent_handle h, double alpha, int32_t max_iter, dou
 gh_status gh_spmv_adj_shift(void *hip_stream, int64_t n, const int64_t *indptr, const int32_t *indices, double c,
                             const double *x, double *y);
 
+/* ---- graph statistics (reference examples: real_world_datasets_example.py:111-175; graphem-rapids_amd/graphstats.py) --
+ * Connected components, hop distances and triangles over a gh_cent handle's graph: undirected, unweighted, self-loops
+ * dropped and duplicate edges merged.  Every output is an integer and every device sum is an integer atomic, so each
+ * result is a pure function of the graph (and, for distances, of the source list), bit for bit: not of the memory
+ * budget, edge order, duplicate edges, self-loops, nor run-to-run scheduling.  The calls are blocking and report through
+ * gh_cent_last_error(h); a NULL handle gives GH_ERR_INVALID. */
+
+/* labels (host int32[n]): labels[v] = the smallest vertex id in v's component; an isolated vertex is its own component.
+ * *n_components (may be NULL) = the number of distinct labels.  Hook and shortcut: every vertex takes the smallest label
+ * among its neighbours and hooks its tree's root under it, then pointer jumping flattens every tree, until a round
+ * changes nothing; the host reads the device's change flags every 4 rounds. */
+gh_status gh_cent_components(gh_cent_handle h, int32_t *labels, int64_t *n_components);
+/* Breadth-first levels from sources[0 .. n_sources) (ids in [0, n); duplicates allowed; n_sources = 0 is a no-op), 64
+ * sources to a machine word.  Each of reached, dist_sum (host int64[n_sources]) and eccentricity (host
+ * int32[n_sources]) may be NULL: reached[j] = vertices source j reaches, itself included; dist_sum[j] = the sum of
+ * their hop distances; eccentricity[j] = the greatest of them -- the greatest FINITE distance when source j does not
+ * reach every vertex (reached[j] < n says so).  Device state: 24 n bytes per 64-source group (three 64-bit words per
+ * vertex: visited, frontier, next frontier), as many groups at once as gh_cent_set_memory_budget allows, at least one;
+ * results do not depend on it.  GH_ERR_INVALID for an id outside [0, n). */
+gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, const int32_t *sources, int64_t *reached,
+                            int64_t *dist_sum, int32_t *eccentricity);
+/* triangles (host int64[n]): triangles[v] = the number of triangles through v.  Per edge the shorter neighbour row is
+ * searched in the longer one, so an edge costs min(deg) log(max deg); counts are 64-bit throughout. */
+gh_status gh_cent_triangles(gh_cent_handle h, int64_t *triangles);
+
 /* ---- graph generators (reference generators.py: generate_sbm / generate_bipartite_graph, generate_geometric,
  * generate_ba; graphem-rapids_amd/generators.py) ------------------------------------------------------------------
  * Three random graph families whose every random decision is a counter-based word, so an edge list is a pure function
