@@ -13,34 +13,6 @@ LIB_PATH = os.path.join(_HERE, "libgraphem_hip.so")
 
 GH_OK, GH_ERR_INVALID, GH_ERR_RUNTIME, GH_ERR_K_TOO_LARGE, GH_ERR_HIP, GH_ERR_NOMEM = range(6)
 
-# Every symbol include/graphem_hip.h declares.
-SYMBOLS = [
-    "gh_create", "gh_destroy", "gh_last_error", "gh_set_positions", "gh_get_positions", "gh_positions_device",
-    "gh_row_stride", "gh_step", "gh_run", "gh_sync", "gh_spring_forces", "gh_knn_midpoints",
-    "gh_intersection_forces", "gh_integrate_normalise", "gh_step_begin", "gh_knn_partial_device", "gh_knn_partial_cols", "gh_knn_merged_device", "gh_rows_packed_device", "gh_step_unpack_rows", "gh_set_packed_rows", "gh_step_merge",
-    "gh_stats_partial_device", "gh_step_finish", "gh_timing_enable", "gh_timing_reset", "gh_timing_count",
-    "gh_timing_get", "gh_device_count", "gh_version", "gh_knn_last_counts", "gh_set_stream",
-    "gh_positions_rows_allocated", "gh_knn_points", "gh_stats_rows", "gh_spmv_symnorm",
-    "gh_spectral_last_error", "gh_gather_layout", "gh_gather_buffer_device", "gh_gather_slot_bytes",
-    "gh_step_finish_gathered", "gh_vertex_order", "gh_positions_unpadded_device", "gh_radial_topk",
-    "gh_comm_unique_id", "gh_comm_init_rccl", "gh_loopback_group_create", "gh_loopback_group_destroy",
-    "gh_comm_init_loopback", "gh_comm_destroy", "gh_run_partitioned", "gh_comm_last_error", "gh_debug_stamps",
-    "gh_knn_cdist_stats", "gh_rank_layout", "gh_step_finish_own", "gh_comm_available", "gh_selftest_arith",
-    "gh_create_f64", "gh_set_positions_f64", "gh_get_positions_f64", "gh_positions_device_f64", "gh_spring_forces_f64",
-    "gh_intersection_forces_f64", "gh_trlan_sweep", "gh_knn_ivf_config", "gh_knn_ivf_list_sizes",
-    "gh_torch_randperm_prefix", "gh_torch_randperm_isa", "gh_run_torch_sampled", "gh_set_cdist_replay", "gh_set_scan_filter", "gh_get_scan_filter", "gh_qcell_probe", "gh_sampler_stats",
-    "gh_overlap_layout", "gh_rows_all_device", "gh_rows_all_row_floats", "gh_stats_all_device", "gh_stats_all_block_doubles", "gh_step_rows_early",
-    "gh_step_pack_rows", "gh_step_finish_overlap",
-    "gh_ic_create", "gh_ic_destroy", "gh_ic_last_error", "gh_ic_arc_count", "gh_ic_set_memory_budget", "gh_ic_spread",
-    "gh_cent_create", "gh_cent_destroy", "gh_cent_last_error", "gh_cent_edge_count", "gh_cent_csr_device",
-    "gh_cent_set_memory_budget", "gh_cent_paths", "gh_cent_pagerank", "gh_spmv_adj_shift",
-    "gh_cent_components", "gh_cent_distances", "gh_cent_triangles",
-    "gh_gen_create", "gh_gen_destroy", "gh_gen_last_error", "gh_gen_set_memory_budget", "gh_gen_sbm", "gh_gen_geometric",
-    "gh_gen_ba", "gh_gen_edges", "gh_gen_positions",
-    "gh_corr_create", "gh_corr_destroy", "gh_corr_last_error", "gh_corr_set_memory_budget", "gh_corr_rho", "gh_corr_matrix",
-    "gh_corr_bootstrap",
-]
-
 
 class GhParams(ctypes.Structure):
     _fields_ = [("L_min", ctypes.c_float), ("k_attr", ctypes.c_float), ("k_inter", ctypes.c_float),
@@ -64,6 +36,132 @@ EDGES_RANGE, EDGES_HASHED = 0, 1  # gh_partition.edge_rule (include/graphem_hip.
 
 SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphem_hip.h)
 
+
+# Every symbol include/graphem_hip.h declares: name -> (restype, argtypes).  load() applies the table, so a symbol cannot be
+# bound without a signature (ctypes would pass its 64-bit pointers as int).
+vp, i32, i64, u64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+_int, _str, _P = ctypes.c_int, ctypes.c_char_p, ctypes.POINTER
+SIGNATURES = {
+    "gh_create": (_int, [_P(vp), _int, i64, i32, i64, vp, _P(GhParams), _P(GhPartition)]),
+    "gh_destroy": (None, [vp]),
+    "gh_last_error": (_str, [vp]),
+    "gh_set_positions": (_int, [vp, vp]),
+    "gh_get_positions": (_int, [vp, vp]),
+    "gh_positions_device": (vp, [vp]),
+    "gh_row_stride": (i32, [vp]),
+    "gh_step": (_int, [vp, vp]),
+    "gh_run": (_int, [vp, i32, vp]),
+    "gh_sync": (_int, [vp]),
+    "gh_spring_forces": (_int, [vp, vp]),
+    "gh_knn_midpoints": (_int, [vp, vp, vp]),
+    "gh_intersection_forces": (_int, [vp, vp, vp, vp]),
+    "gh_integrate_normalise": (_int, [vp, vp, vp, vp]),
+    "gh_step_begin": (_int, [vp, vp]),
+    "gh_knn_partial_device": (vp, [vp]),
+    "gh_knn_partial_cols": (i32, [vp]),
+    "gh_knn_merged_device": (vp, [vp]),
+    "gh_rows_packed_device": (vp, [vp]),
+    "gh_step_unpack_rows": (_int, [vp]),
+    "gh_set_packed_rows": (_int, [vp, i32]),
+    "gh_step_merge": (_int, [vp, vp, i32]),
+    "gh_stats_partial_device": (vp, [vp]),
+    "gh_step_finish": (_int, [vp]),
+    "gh_timing_enable": (_int, [vp, i32]),
+    "gh_timing_reset": (_int, [vp]),
+    "gh_timing_count": (i32, [vp]),
+    "gh_timing_get": (_int, [vp, i32, _P(_str), _P(f64), _P(i64)]),
+    "gh_device_count": (i32, []),
+    "gh_version": (_str, []),
+    "gh_knn_last_counts": (_int, [vp, vp, vp, vp]),
+    "gh_set_stream": (_int, [vp, vp, i32]),
+    "gh_positions_rows_allocated": (i64, [vp]),
+    "gh_knn_points": (_int, [_int, vp, i64, vp, i64, i32, i32, vp]),
+    "gh_stats_rows": (i32, [vp]),
+    "gh_spmv_symnorm": (_int, [vp, i64, vp, vp, vp, vp, vp]),
+    "gh_spectral_last_error": (_str, []),
+    "gh_gather_layout": (_int, [vp, i32, i32, i64]),
+    "gh_gather_buffer_device": (vp, [vp]),
+    "gh_gather_slot_bytes": (i64, [vp]),
+    "gh_step_finish_gathered": (_int, [vp]),
+    "gh_vertex_order": (_int, [vp, vp]),
+    "gh_positions_unpadded_device": (vp, [vp]),
+    "gh_radial_topk": (_int, [vp, i32, vp]),
+    "gh_comm_unique_id": (_int, [vp]),
+    "gh_comm_init_rccl": (_int, [vp, i32, i32, vp]),
+    "gh_loopback_group_create": (vp, [i32]),
+    "gh_loopback_group_destroy": (None, [vp]),
+    "gh_comm_init_loopback": (_int, [vp, vp, i32]),
+    "gh_comm_destroy": (_int, [vp]),
+    "gh_run_partitioned": (_int, [vp, i32, vp]),
+    "gh_comm_last_error": (_str, []),
+    "gh_debug_stamps": (_int, [vp, vp, i64]),
+    "gh_knn_cdist_stats": (_int, [vp, vp, vp]),
+    "gh_rank_layout": (_int, [vp, i32, i32, i64]),
+    "gh_step_finish_own": (_int, [vp, vp, i32]),
+    "gh_comm_available": (i32, []),
+    "gh_selftest_arith": (_int, [_int, u64, i64, _P(i64), _P(i64)]),
+    "gh_create_f64": (_int, [_P(vp), _int, i64, i32, i64, vp, _P(GhParams), f64, f64, f64]),
+    "gh_set_positions_f64": (_int, [vp, vp]),
+    "gh_get_positions_f64": (_int, [vp, vp]),
+    "gh_positions_device_f64": (vp, [vp]),
+    "gh_spring_forces_f64": (_int, [vp, vp]),
+    "gh_intersection_forces_f64": (_int, [vp, vp, vp, vp]),
+    "gh_trlan_sweep": (_int, [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "gh_knn_ivf_config": (_int, [vp, vp, vp]),
+    "gh_knn_ivf_list_sizes": (_int, [vp, vp, i32]),
+    "gh_torch_randperm_prefix": (_int, [vp, i64, i64, i64, i32, vp]),
+    "gh_torch_randperm_isa": (_str, []),
+    "gh_run_torch_sampled": (_int, [vp, i32, vp, i64]),
+    "gh_set_cdist_replay": (_int, [vp, i32]),
+    "gh_set_scan_filter": (_int, [vp, i32]),
+    "gh_get_scan_filter": (_int, [vp, _P(i32)]),
+    "gh_qcell_probe": (_int, [vp, i32, vp, vp, vp, i64, vp, vp]),
+    "gh_sampler_stats": (_int, [vp, vp]),
+    "gh_overlap_layout": (_int, [vp, i32, i32, i64]),
+    "gh_rows_all_device": (vp, [vp]),
+    "gh_rows_all_row_floats": (i32, [vp]),
+    "gh_stats_all_device": (vp, [vp]),
+    "gh_stats_all_block_doubles": (i64, [vp]),
+    "gh_step_rows_early": (i32, [vp]),
+    "gh_step_pack_rows": (_int, [vp, vp, i32]),
+    "gh_step_finish_overlap": (_int, [vp]),
+    "gh_ic_create": (_int, [_P(vp), _int, i64, i64, vp, i32]),
+    "gh_ic_destroy": (None, [vp]),
+    "gh_ic_last_error": (_str, [vp]),
+    "gh_ic_arc_count": (i64, [vp]),
+    "gh_ic_set_memory_budget": (_int, [vp, i64]),
+    "gh_ic_spread": (_int, [vp, f64, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
+    "gh_cent_create": (_int, [_P(vp), _int, i64, i64, vp]),
+    "gh_cent_destroy": (None, [vp]),
+    "gh_cent_last_error": (_str, [vp]),
+    "gh_cent_edge_count": (i64, [vp]),
+    "gh_cent_csr_device": (_int, [vp, _P(vp), _P(vp)]),
+    "gh_cent_set_memory_budget": (_int, [vp, i64]),
+    "gh_cent_paths": (_int, [vp, i64, vp, vp, vp, vp, vp]),
+    "gh_cent_pagerank": (_int, [vp, f64, i32, f64, vp, _P(i32)]),
+    "gh_spmv_adj_shift": (_int, [vp, i64, vp, vp, f64, vp, vp]),
+    "gh_cent_components": (_int, [vp, vp, _P(i64)]),
+    "gh_cent_distances": (_int, [vp, i64, vp, vp, vp, vp]),
+    "gh_cent_triangles": (_int, [vp, vp]),
+    "gh_gen_create": (_int, [_P(vp), _int]),
+    "gh_gen_destroy": (None, [vp]),
+    "gh_gen_last_error": (_str, [vp]),
+    "gh_gen_set_memory_budget": (_int, [vp, i64]),
+    "gh_gen_sbm": (_int, [vp, i32, vp, vp, u64, _P(i64)]),
+    "gh_gen_geometric": (_int, [vp, i64, f64, i32, u64, _P(i64)]),
+    "gh_gen_ba": (_int, [vp, i64, i64, u64, _P(i64), _P(i32)]),
+    "gh_gen_edges": (_int, [vp, vp]),
+    "gh_gen_positions": (_int, [vp, vp]),
+    "gh_corr_create": (_int, [_P(vp), _int, i64, i32, vp]),
+    "gh_corr_destroy": (None, [vp]),
+    "gh_corr_last_error": (_str, [vp]),
+    "gh_corr_set_memory_budget": (_int, [vp, i64]),
+    "gh_corr_rho": (f64, [i64, i64, i64]),
+    "gh_corr_matrix": (_int, [vp, vp, vp]),
+    "gh_corr_bootstrap": (_int, [vp, i32, vp, i32, u64, vp, vp]),
+}
+SYMBOLS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -80,260 +178,76 @@ def load():
             f"{LIB_PATH} is missing: build it with `python graphem-rapids_amd/build.py` "
             "(hipcc --offload-arch=gfx950). The HIP backend has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    L.gh_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i32, i64, vp, ctypes.POINTER(GhParams),
-                            ctypes.POINTER(GhPartition)]
-    L.gh_create.restype = ctypes.c_int
-    L.gh_destroy.argtypes = [vp]
-    L.gh_destroy.restype = None
-    L.gh_last_error.argtypes = [vp]
-    L.gh_last_error.restype = ctypes.c_char_p
-    for name in ("gh_set_positions", "gh_get_positions", "gh_spring_forces", "gh_step", "gh_step_begin"):
-        getattr(L, name).argtypes = [vp, vp]
-        getattr(L, name).restype = ctypes.c_int
-    L.gh_positions_device.argtypes = [vp]
-    L.gh_positions_device.restype = vp
-    L.gh_row_stride.argtypes = [vp]
-    L.gh_row_stride.restype = i32
-    L.gh_run.argtypes = [vp, i32, vp]
-    L.gh_run.restype = ctypes.c_int
-    L.gh_torch_randperm_prefix.argtypes = [vp, i64, i64, i64, i32, vp]
-    L.gh_torch_randperm_prefix.restype = ctypes.c_int
-    L.gh_torch_randperm_isa.argtypes = []
-    L.gh_torch_randperm_isa.restype = ctypes.c_char_p
-    L.gh_run_torch_sampled.argtypes = [vp, i32, vp, i64]
-    L.gh_run_torch_sampled.restype = ctypes.c_int
-    L.gh_radial_topk.argtypes = [vp, i32, vp]
-    L.gh_radial_topk.restype = ctypes.c_int
-    L.gh_vertex_order.argtypes = [vp, vp]
-    L.gh_vertex_order.restype = ctypes.c_int
-    L.gh_positions_unpadded_device.argtypes = [vp]
-    L.gh_positions_unpadded_device.restype = vp
-    L.gh_gather_layout.argtypes = [vp, i32, i32, i64]
-    L.gh_gather_layout.restype = ctypes.c_int
-    L.gh_rank_layout.argtypes = [vp, i32, i32, i64]
-    L.gh_rank_layout.restype = ctypes.c_int
-    L.gh_overlap_layout.argtypes = [vp, i32, i32, i64]
-    L.gh_overlap_layout.restype = ctypes.c_int
-    L.gh_rows_all_device.argtypes = [vp]
-    L.gh_rows_all_device.restype = vp
-    L.gh_rows_all_row_floats.argtypes = [vp]
-    L.gh_rows_all_row_floats.restype = i32
-    L.gh_stats_all_device.argtypes = [vp]
-    L.gh_stats_all_device.restype = vp
-    L.gh_stats_all_block_doubles.argtypes = [vp]
-    L.gh_stats_all_block_doubles.restype = i64
-    L.gh_step_rows_early.argtypes = [vp]
-    L.gh_step_rows_early.restype = i32
-    L.gh_step_pack_rows.argtypes = [vp, vp, i32]
-    L.gh_step_pack_rows.restype = ctypes.c_int
-    L.gh_step_finish_overlap.argtypes = [vp]
-    L.gh_step_finish_overlap.restype = ctypes.c_int
-    L.gh_step_finish_own.argtypes = [vp, vp, i32]
-    L.gh_step_finish_own.restype = ctypes.c_int
-    L.gh_create_f64.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i32, i64, vp, ctypes.POINTER(GhParams),
-                                ctypes.c_double, ctypes.c_double, ctypes.c_double]
-    L.gh_create_f64.restype = ctypes.c_int
-    for name in ("gh_set_positions_f64", "gh_get_positions_f64", "gh_spring_forces_f64"):
-        getattr(L, name).argtypes = [vp, vp]
-        getattr(L, name).restype = ctypes.c_int
-    L.gh_positions_device_f64.argtypes = [vp]
-    L.gh_positions_device_f64.restype = vp
-    L.gh_intersection_forces_f64.argtypes = [vp, vp, vp, vp]
-    L.gh_intersection_forces_f64.restype = ctypes.c_int
-    L.gh_selftest_arith.argtypes = [ctypes.c_int, ctypes.c_uint64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-    L.gh_selftest_arith.restype = ctypes.c_int
-    L.gh_comm_available.argtypes = []
-    L.gh_comm_available.restype = i32
-    L.gh_gather_buffer_device.argtypes = [vp]
-    L.gh_gather_buffer_device.restype = vp
-    L.gh_gather_slot_bytes.argtypes = [vp]
-    L.gh_gather_slot_bytes.restype = i64
-    for name in ("gh_sync", "gh_step_finish", "gh_step_finish_gathered", "gh_timing_reset"):
-        getattr(L, name).argtypes = [vp]
-        getattr(L, name).restype = ctypes.c_int
-    L.gh_knn_midpoints.argtypes = [vp, vp, vp]
-    L.gh_knn_midpoints.restype = ctypes.c_int
-    L.gh_intersection_forces.argtypes = [vp, vp, vp, vp]
-    L.gh_intersection_forces.restype = ctypes.c_int
-    L.gh_integrate_normalise.argtypes = [vp, vp, vp, vp]
-    L.gh_integrate_normalise.restype = ctypes.c_int
-    L.gh_knn_partial_device.argtypes = [vp]
-    L.gh_knn_partial_device.restype = vp
-    L.gh_knn_partial_cols.argtypes = [vp]
-    L.gh_knn_partial_cols.restype = i32
-    L.gh_knn_merged_device.argtypes = [vp]
-    L.gh_knn_merged_device.restype = vp
-    L.gh_rows_packed_device.argtypes = [vp]
-    L.gh_rows_packed_device.restype = vp
-    L.gh_step_unpack_rows.argtypes = [vp]
-    L.gh_step_unpack_rows.restype = ctypes.c_int
-    L.gh_set_packed_rows.argtypes = [vp, i32]
-    L.gh_set_packed_rows.restype = ctypes.c_int
-    L.gh_step_merge.argtypes = [vp, vp, i32]
-    L.gh_step_merge.restype = ctypes.c_int
-    L.gh_stats_partial_device.argtypes = [vp]
-    L.gh_stats_partial_device.restype = vp
-    L.gh_timing_enable.argtypes = [vp, i32]
-    L.gh_timing_enable.restype = ctypes.c_int
-    L.gh_timing_count.argtypes = [vp]
-    L.gh_timing_count.restype = i32
-    L.gh_timing_get.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
-                                ctypes.POINTER(i64)]
-    L.gh_timing_get.restype = ctypes.c_int
-    L.gh_set_stream.argtypes = [vp, vp, i32]
-    L.gh_set_stream.restype = ctypes.c_int
-    L.gh_positions_rows_allocated.argtypes = [vp]
-    L.gh_positions_rows_allocated.restype = i64
-    L.gh_spmv_symnorm.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.gh_spmv_symnorm.restype = ctypes.c_int
-    L.gh_trlan_sweep.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    L.gh_trlan_sweep.restype = ctypes.c_int
-    L.gh_spectral_last_error.argtypes = []
-    L.gh_spectral_last_error.restype = ctypes.c_char_p
-    L.gh_stats_rows.argtypes = [vp]
-    L.gh_stats_rows.restype = i32
-    L.gh_knn_points.argtypes = [ctypes.c_int, vp, i64, vp, i64, i32, i32, vp]
-    L.gh_knn_points.restype = ctypes.c_int
-    L.gh_knn_last_counts.argtypes = [vp, vp, vp, vp]
-    L.gh_knn_last_counts.restype = ctypes.c_int
-    L.gh_knn_cdist_stats.argtypes = [vp, vp, vp]
-    L.gh_knn_cdist_stats.restype = ctypes.c_int
-    L.gh_sampler_stats.argtypes = [vp, vp]
-    L.gh_sampler_stats.restype = ctypes.c_int
-    L.gh_set_cdist_replay.argtypes = [vp, i32]
-    L.gh_set_cdist_replay.restype = ctypes.c_int
-    L.gh_set_scan_filter.argtypes = [vp, i32]
-    L.gh_set_scan_filter.restype = ctypes.c_int
-    L.gh_get_scan_filter.argtypes = [vp, ctypes.POINTER(i32)]
-    L.gh_get_scan_filter.restype = ctypes.c_int
-    L.gh_qcell_probe.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp]
-    L.gh_qcell_probe.restype = ctypes.c_int
-    L.gh_knn_ivf_config.argtypes = [vp, vp, vp]
-    L.gh_knn_ivf_config.restype = ctypes.c_int
-    L.gh_knn_ivf_list_sizes.argtypes = [vp, vp, ctypes.c_int32]
-    L.gh_knn_ivf_list_sizes.restype = ctypes.c_int
-    L.gh_comm_unique_id.argtypes = [vp]
-    L.gh_comm_unique_id.restype = ctypes.c_int
-    L.gh_comm_init_rccl.argtypes = [vp, i32, i32, vp]
-    L.gh_comm_init_rccl.restype = ctypes.c_int
-    L.gh_loopback_group_create.argtypes = [i32]
-    L.gh_loopback_group_create.restype = vp
-    L.gh_loopback_group_destroy.argtypes = [vp]
-    L.gh_loopback_group_destroy.restype = None
-    L.gh_comm_init_loopback.argtypes = [vp, vp, i32]
-    L.gh_comm_init_loopback.restype = ctypes.c_int
-    L.gh_comm_destroy.argtypes = [vp]
-    L.gh_comm_destroy.restype = ctypes.c_int
-    L.gh_run_partitioned.argtypes = [vp, i32, vp]
-    L.gh_run_partitioned.restype = ctypes.c_int
-    L.gh_comm_last_error.argtypes = []
-    L.gh_comm_last_error.restype = ctypes.c_char_p
-    L.gh_debug_stamps.argtypes = [vp, vp, i64]
-    L.gh_debug_stamps.restype = ctypes.c_int
-    L.gh_device_count.argtypes = []
-    L.gh_device_count.restype = i32
-    L.gh_version.argtypes = []
-    L.gh_version.restype = ctypes.c_char_p
-    L.gh_ic_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i64, vp, i32]
-    L.gh_ic_create.restype = ctypes.c_int
-    L.gh_ic_destroy.argtypes = [vp]
-    L.gh_ic_destroy.restype = None
-    L.gh_ic_last_error.argtypes = [vp]
-    L.gh_ic_last_error.restype = ctypes.c_char_p
-    L.gh_ic_arc_count.argtypes = [vp]
-    L.gh_ic_arc_count.restype = i64
-    L.gh_ic_set_memory_budget.argtypes = [vp, i64]
-    L.gh_ic_set_memory_budget.restype = ctypes.c_int
-    L.gh_ic_spread.argtypes = [vp, ctypes.c_double, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, i64, vp, vp]
-    L.gh_ic_spread.restype = ctypes.c_int
-    L.gh_cent_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i64, vp]
-    L.gh_cent_create.restype = ctypes.c_int
-    L.gh_cent_destroy.argtypes = [vp]
-    L.gh_cent_destroy.restype = None
-    L.gh_cent_last_error.argtypes = [vp]
-    L.gh_cent_last_error.restype = ctypes.c_char_p
-    L.gh_cent_edge_count.argtypes = [vp]
-    L.gh_cent_edge_count.restype = i64
-    L.gh_cent_csr_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
-    L.gh_cent_csr_device.restype = ctypes.c_int
-    L.gh_cent_set_memory_budget.argtypes = [vp, i64]
-    L.gh_cent_set_memory_budget.restype = ctypes.c_int
-    L.gh_cent_paths.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.gh_cent_paths.restype = ctypes.c_int
-    L.gh_cent_pagerank.argtypes = [vp, ctypes.c_double, i32, ctypes.c_double, vp, ctypes.POINTER(i32)]
-    L.gh_cent_pagerank.restype = ctypes.c_int
-    L.gh_cent_components.argtypes = [vp, vp, ctypes.POINTER(i64)]
-    L.gh_cent_components.restype = ctypes.c_int
-    L.gh_cent_distances.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.gh_cent_distances.restype = ctypes.c_int
-    L.gh_cent_triangles.argtypes = [vp, vp]
-    L.gh_cent_triangles.restype = ctypes.c_int
-    L.gh_spmv_adj_shift.argtypes = [vp, i64, vp, vp, ctypes.c_double, vp, vp]
-    L.gh_spmv_adj_shift.restype = ctypes.c_int
-    L.gh_gen_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-    L.gh_gen_create.restype = ctypes.c_int
-    L.gh_gen_destroy.argtypes = [vp]
-    L.gh_gen_destroy.restype = None
-    L.gh_gen_last_error.argtypes = [vp]
-    L.gh_gen_last_error.restype = ctypes.c_char_p
-    L.gh_gen_set_memory_budget.argtypes = [vp, i64]
-    L.gh_gen_set_memory_budget.restype = ctypes.c_int
-    L.gh_gen_sbm.argtypes = [vp, i32, vp, vp, ctypes.c_uint64, ctypes.POINTER(i64)]
-    L.gh_gen_sbm.restype = ctypes.c_int
-    L.gh_gen_geometric.argtypes = [vp, i64, ctypes.c_double, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
-    L.gh_gen_geometric.restype = ctypes.c_int
-    L.gh_gen_ba.argtypes = [vp, i64, i64, ctypes.c_uint64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
-    L.gh_gen_ba.restype = ctypes.c_int
-    L.gh_gen_edges.argtypes = [vp, vp]
-    L.gh_gen_edges.restype = ctypes.c_int
-    L.gh_gen_positions.argtypes = [vp, vp]
-    L.gh_gen_positions.restype = ctypes.c_int
-    L.gh_corr_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, i64, i32, vp]
-    L.gh_corr_create.restype = ctypes.c_int
-    L.gh_corr_destroy.argtypes = [vp]
-    L.gh_corr_destroy.restype = None
-    L.gh_corr_last_error.argtypes = [vp]
-    L.gh_corr_last_error.restype = ctypes.c_char_p
-    L.gh_corr_set_memory_budget.argtypes = [vp, i64]
-    L.gh_corr_set_memory_budget.restype = ctypes.c_int
-    L.gh_corr_rho.argtypes = [i64, i64, i64]
-    L.gh_corr_rho.restype = ctypes.c_double
-    L.gh_corr_matrix.argtypes = [vp, vp, vp]
-    L.gh_corr_matrix.restype = ctypes.c_int
-    L.gh_corr_bootstrap.argtypes = [vp, i32, vp, i32, ctypes.c_uint64, vp, vp]
-    L.gh_corr_bootstrap.restype = ctypes.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
 
-def raise_for(status, handle):
-    """Map a gh_status to the exception type the reference raises for the same condition."""
+def raise_for(status, handle, last_error="gh_last_error"):
+    """Map a gh_status to the exception type the reference raises for the same condition; the message is the handle's, or
+    with no handle the create-time message of the module whose `last_error` symbol is named."""
     if status == GH_OK:
         return
-    msg = load().gh_last_error(handle)
+    msg = getattr(load(), last_error)(handle)
     msg = msg.decode() if msg else f"gh_status {status}"
-    if status == GH_ERR_INVALID:
-        raise ValueError(msg)
-    if status == GH_ERR_NOMEM:
-        raise MemoryError(msg)
-    raise RuntimeError(msg)
+    raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(status, RuntimeError)(msg)
 
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-class Engine:
+class Handle:
+    """Owner of one native handle.  A subclass names its module's symbols and opens the handle with _create."""
+    _destroy = _last_error = None
+
+    def _create(self, symbol, *args):
+        """handle = symbol(&handle, *args); a failed create raises the module's create-time message and owns nothing."""
+        self.lib = load()
+        self.handle = ctypes.c_void_p()
+        st = getattr(self.lib, symbol)(ctypes.byref(self.handle), *args)
+        if st != GH_OK:
+            self.handle = ctypes.c_void_p()
+            self._raise(st)
+
+    def _raise(self, st):
+        if st != GH_OK:
+            raise_for(st, self.handle if self.handle.value else None, self._last_error)
+
+    _chk = _raise
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-exception-caught
+            pass
+
+
+class BudgetHandle(Handle):
+    """A handle whose calls size their working state by a memory budget (the default is in each class's docstring)."""
+    _set_budget = None
+
+    def set_memory_budget(self, nbytes):
+        """Bytes of working state a call on this handle may hold (0: the module's default); results do not depend on it."""
+        self._raise(getattr(self.lib, self._set_budget)(self.handle, int(nbytes)))
+
+
+class Engine(Handle):
     """Thin RAII wrapper over a gh_handle."""
+    _destroy, _last_error = "gh_destroy", "gh_last_error"
 
     def __init__(self, n, D, edges, L_min, k_attr, k_inter, n_neighbors, sample_size, seed=0, device_id=0,
                  partition=None, reorder="auto", knn_method="auto", knn_distance="exact", dtype="float32", ivf_lists=0,
                  ivf_probes=0):
         """dtype='float64': the engine of csrc/f64.hip -- every phase in double; positions, spring and intersection forces
         cross the boundary as float64 arrays (whole graph only; reorder / knn_method / knn_distance do not apply)."""
-        self.lib = load()
-        self.handle = ctypes.c_void_p()
         self.n, self.D = int(n), int(D)
         if dtype not in ("float32", "float64"):
             raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
@@ -351,31 +265,13 @@ class Engine:
             vals = [int(x) for x in partition]  # (row_lo, row_hi, edge_lo, edge_hi[, edge_rule])
             part = ctypes.pointer(GhPartition(*(vals + [EDGES_RANGE] * (5 - len(vals)))))
         if self.f64:
-            st = self.lib.gh_create_f64(ctypes.byref(self.handle), int(device_id), self.n, self.D, self.E, ptr(edges),
-                                        ctypes.byref(prm), float(L_min), float(k_attr), float(k_inter))
+            self._create("gh_create_f64", int(device_id), self.n, self.D, self.E, ptr(edges), ctypes.byref(prm), float(L_min),
+                         float(k_attr), float(k_inter))
         else:
-            st = self.lib.gh_create(ctypes.byref(self.handle), int(device_id), self.n, self.D, self.E, ptr(edges),
-                                    ctypes.byref(prm), part)
-        if st != GH_OK:
-            self.handle = ctypes.c_void_p()
-            raise_for(st, None)
+            self._create("gh_create", int(device_id), self.n, self.D, self.E, ptr(edges), ctypes.byref(prm), part)
         self.k = int(n_neighbors)
         self.S = min(int(sample_size), self.E)
         self.ld = self.lib.gh_row_stride(self.handle)
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.gh_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pylint: disable=broad-exception-caught
-            pass
-
-    def _chk(self, st):
-        raise_for(st, self.handle)
 
     def set_positions(self, pos):
         pos = np.ascontiguousarray(pos, dtype=self.np_dtype)
@@ -640,42 +536,16 @@ class Engine:
         return out
 
 
-class ICGraph:
-    """Thin RAII wrapper over a gh_ic_handle: Monte Carlo Independent Cascade on one graph (include/graphem_hip.h)."""
+class ICGraph(BudgetHandle):
+    """Thin RAII wrapper over a gh_ic_handle: Monte Carlo Independent Cascade on one graph (include/graphem_hip.h).
+    Memory budget: device bytes of chunk state a spread call may hold, 1 GiB by default."""
+    _destroy, _last_error, _set_budget = "gh_ic_destroy", "gh_ic_last_error", "gh_ic_set_memory_budget"
 
     def __init__(self, n, arcs, directed=False, device_id=0):
-        self.lib = load()
-        self.handle = ctypes.c_void_p()
         self.n, self.directed = int(n), bool(directed)
         arcs = np.ascontiguousarray(arcs, dtype=np.int32).reshape(-1, 2)
-        st = self.lib.gh_ic_create(ctypes.byref(self.handle), int(device_id), self.n, arcs.shape[0], ptr(arcs),
-                                   1 if self.directed else 0)
-        if st != GH_OK:
-            self.handle = ctypes.c_void_p()
-            self._raise(st)
+        self._create("gh_ic_create", int(device_id), self.n, arcs.shape[0], ptr(arcs), 1 if self.directed else 0)
         self.arcs = int(self.lib.gh_ic_arc_count(self.handle))
-
-    def _raise(self, st):
-        if st == GH_OK:
-            return
-        msg = self.lib.gh_ic_last_error(self.handle if self.handle.value else None)
-        msg = msg.decode() if msg else f"gh_status {st}"
-        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.gh_ic_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pylint: disable=broad-exception-caught
-            pass
-
-    def set_memory_budget(self, nbytes):
-        """Device bytes of chunk state a spread call may hold (0: the default, 1 GiB)."""
-        self._raise(self.lib.gh_ic_set_memory_budget(self.handle, int(nbytes)))
 
     def spread(self, sets, p, n_trials, seed=0, max_hops=-1, base=None, per_trial=False):
         """sets: a list of vertex-id sequences.  Returns totals (n_sets,) int64 and, with per_trial, the (n_sets, n_trials)
@@ -692,42 +562,16 @@ class ICGraph:
         return (totals, trials) if per_trial else totals
 
 
-class CentGraph:
+class CentGraph(BudgetHandle):
     """Thin RAII wrapper over a gh_cent_handle: shortest-path centralities, PageRank and the adjacency SpMV of one
-    undirected graph (include/graphem_hip.h)."""
+    undirected graph (include/graphem_hip.h).  Memory budget: device bytes of path state a paths call may hold, 1 GiB by default."""
+    _destroy, _last_error, _set_budget = "gh_cent_destroy", "gh_cent_last_error", "gh_cent_set_memory_budget"
 
     def __init__(self, n, edges, device_id=0):
-        self.lib = load()
-        self.handle = ctypes.c_void_p()
         self.n = int(n)
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
-        st = self.lib.gh_cent_create(ctypes.byref(self.handle), int(device_id), self.n, edges.shape[0], ptr(edges))
-        if st != GH_OK:
-            self.handle = ctypes.c_void_p()
-            self._raise(st)
+        self._create("gh_cent_create", int(device_id), self.n, edges.shape[0], ptr(edges))
         self.edges = int(self.lib.gh_cent_edge_count(self.handle))
-
-    def _raise(self, st):
-        if st == GH_OK:
-            return
-        msg = self.lib.gh_cent_last_error(self.handle if self.handle.value else None)
-        msg = msg.decode() if msg else f"gh_status {st}"
-        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.gh_cent_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pylint: disable=broad-exception-caught
-            pass
-
-    def set_memory_budget(self, nbytes):
-        """Device bytes of path state a paths call may hold (0: the default, 1 GiB)."""
-        self._raise(self.lib.gh_cent_set_memory_budget(self.handle, int(nbytes)))
 
     def paths(self, sources, betweenness=True, load=True, distances=True):
         """One all-sources pass (gh_cent_paths): (betweenness (n,), load (n,), reached (S,), dist_sum (S,)); a part not
@@ -846,41 +690,16 @@ def device_count():
     return int(load().gh_device_count())
 
 
-class Generator:
+class Generator(BudgetHandle):
     """Thin RAII wrapper over a gh_gen_handle: the counter-based graph generators (include/graphem_hip.h).  device_id < 0
-    is the library's host path, which touches no device and returns the same edges bit for bit."""
+    is the library's host path, which touches no device and returns the same edges bit for bit.  Memory budget: bytes a call may allocate
+    for counts and edges, 4 GiB by default; more is a MemoryError, never a cut."""
+    _destroy, _last_error, _set_budget = "gh_gen_destroy", "gh_gen_last_error", "gh_gen_set_memory_budget"
 
     def __init__(self, device_id=0):
-        self.lib = load()
-        self.handle = ctypes.c_void_p()
         self.device_id = int(device_id)
         self.rounds = 0
-        st = self.lib.gh_gen_create(ctypes.byref(self.handle), self.device_id)
-        if st != GH_OK:
-            self.handle = ctypes.c_void_p()
-            self._raise(st)
-
-    def _raise(self, st):
-        if st == GH_OK:
-            return
-        msg = self.lib.gh_gen_last_error(self.handle if self.handle.value else None)
-        msg = msg.decode() if msg else f"gh_status {st}"
-        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.gh_gen_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pylint: disable=broad-exception-caught
-            pass
-
-    def set_memory_budget(self, nbytes):
-        """Bytes a call may allocate for counts and edges (0: the default, 4 GiB); more is a MemoryError, never a cut."""
-        self._raise(self.lib.gh_gen_set_memory_budget(self.handle, int(nbytes)))
+        self._create("gh_gen_create", self.device_id)
 
     def _edges(self, count):
         edges = np.zeros((int(count), 2), dtype=np.int32)
@@ -916,45 +735,20 @@ class Generator:
         return self._edges(count.value)
 
 
-class Correlation:
+class Correlation(BudgetHandle):
     """Thin RAII wrapper over a gh_corr_handle: Spearman's rho between the columns of one table, plain and over bootstrap
     resamples (include/graphem_hip.h "rank correlation").  columns: (m, n) float64, one row per variable.  device_id < 0
-    is the library's host path, which touches no device and returns the same integers bit for bit."""
+    is the library's host path, which touches no device and returns the same integers bit for bit.  Memory budget: device bytes of
+    replicate state a bootstrap call may hold, 4 GiB by default."""
+    _destroy, _last_error, _set_budget = "gh_corr_destroy", "gh_corr_last_error", "gh_corr_set_memory_budget"
 
     def __init__(self, columns, device_id=0):
-        self.lib = load()
-        self.handle = ctypes.c_void_p()
         self.device_id = int(device_id)
         cols = np.ascontiguousarray(columns, dtype=np.float64)
         if cols.ndim != 2:
             raise ValueError("columns must be (m, n)")
         self.m, self.n = int(cols.shape[0]), int(cols.shape[1])
-        st = self.lib.gh_corr_create(ctypes.byref(self.handle), self.device_id, self.n, self.m, ptr(cols))
-        if st != GH_OK:
-            self.handle = ctypes.c_void_p()
-            self._raise(st)
-
-    def _raise(self, st):
-        if st == GH_OK:
-            return
-        msg = self.lib.gh_corr_last_error(self.handle if self.handle.value else None)
-        msg = msg.decode() if msg else f"gh_status {st}"
-        raise {GH_ERR_INVALID: ValueError, GH_ERR_NOMEM: MemoryError}.get(st, RuntimeError)(msg)
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.gh_corr_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pylint: disable=broad-exception-caught
-            pass
-
-    def set_memory_budget(self, nbytes):
-        """Device bytes of replicate state a bootstrap call may hold (0: the default, 4 GiB); results do not depend on it."""
-        self._raise(self.lib.gh_corr_set_memory_budget(self.handle, int(nbytes)))
+        self._create("gh_corr_create", self.device_id, self.n, self.m, ptr(cols))
 
     def matrix(self, sums=False):
         """(m, m) float64 Spearman matrix of the plain statistic (gh_corr_matrix); with sums=True also the int64

@@ -304,17 +304,14 @@ inline int cent_blocks(int64_t waves) {
 }  // namespace
 
 static thread_local std::string g_cent_error;
+void cent_set_create_error(const std::string &msg) { g_cent_error = msg; }
 
 namespace {
 
 void cent_free_state(gh_cent *h) {
-    for (void *p : {(void *)h->d_dist, (void *)h->d_npred, (void *)h->d_flags, (void *)h->d_src, (void *)h->d_sigma,
-                    (void *)h->d_delta, (void *)h->d_lam, (void *)h->d_vis, (void *)h->d_fa, (void *)h->d_fb, (void *)h->d_range})
-        if (p) (void)hipFree(p);
-    h->d_dist = h->d_npred = h->d_flags = h->d_src = nullptr;
-    h->d_sigma = h->d_delta = h->d_lam = nullptr;
-    h->d_vis = h->d_fa = h->d_fb = nullptr;
-    h->d_range = nullptr;
+    h->d_dist.reset(); h->d_npred.reset(); h->d_flags.reset(); h->d_src.reset();
+    h->d_sigma.reset(); h->d_delta.reset(); h->d_lam.reset();
+    h->d_vis.reset(); h->d_fa.reset(); h->d_fb.reset(); h->d_range.reset();
     h->cap_groups = 0;
 }
 
@@ -325,11 +322,9 @@ gh_status cent_reserve(gh_cent *h, int64_t G) {
     if (G <= h->cap_groups) return GH_OK;
     cent_free_state(h);
     const int64_t ent = G * h->n * 64, words = G * h->n;
-    auto alloc = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess; };
-    if (!alloc((void **)&h->d_dist, 4 * ent) || !alloc((void **)&h->d_npred, 4 * ent) || !alloc((void **)&h->d_sigma, 8 * ent) ||
-        !alloc((void **)&h->d_delta, 8 * ent) || !alloc((void **)&h->d_lam, 8 * ent) || !alloc((void **)&h->d_vis, 8 * words) ||
-        !alloc((void **)&h->d_fa, 8 * words) || !alloc((void **)&h->d_fb, 8 * words) || !alloc((void **)&h->d_range, 8 * words) ||
-        !alloc((void **)&h->d_flags, 4 * (h->n + 2)) || !alloc((void **)&h->d_src, 4 * 64 * G)) {
+    if (!h->d_dist.alloc(4 * ent) || !h->d_npred.alloc(4 * ent) || !h->d_sigma.alloc(8 * ent) || !h->d_delta.alloc(8 * ent) ||
+        !h->d_lam.alloc(8 * ent) || !h->d_vis.alloc(8 * words) || !h->d_fa.alloc(8 * words) || !h->d_fb.alloc(8 * words) ||
+        !h->d_range.alloc(8 * words) || !h->d_flags.alloc(4 * (h->n + 2)) || !h->d_src.alloc(4 * 64 * G)) {
         cent_free_state(h);
         h->err = "hipMalloc failed for " + std::to_string(G) + " source groups of path state";
         return GH_ERR_NOMEM;
@@ -338,51 +333,32 @@ gh_status cent_reserve(gh_cent *h, int64_t G) {
     return GH_OK;
 }
 
-#define CENT_HIP(call)                                                                 \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
-    } while (0)
-
 // One batch of ns <= 64 G sources: forward levels, backward levels, sums into the device outputs.
 gh_status cent_run_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, double *d_bc, double *d_ld,
                          unsigned long long *d_reached, unsigned long long *d_dsum) {
     const int64_t n = h->n;
     CentLevel a{};
-    a.ptr = h->d_ptr; a.adj = h->d_adj;
-    a.dist = h->d_dist; a.npred = h->d_npred; a.sigma = h->d_sigma; a.delta = h->d_delta; a.lam = h->d_lam;
-    a.vis = h->d_vis; a.range = h->d_range; a.flags = h->d_flags;
+    a.ptr = h->d_ptr.p; a.adj = h->d_adj.p;
+    a.dist = h->d_dist.p; a.npred = h->d_npred.p; a.sigma = h->d_sigma.p; a.delta = h->d_delta.p; a.lam = h->d_lam.p;
+    a.vis = h->d_vis.p; a.range = h->d_range.p; a.flags = h->d_flags.p;
     a.n = n; a.G = G;
-    CENT_HIP(hipMemcpyAsync(h->d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
-    CENT_HIP(hipMemsetAsync(h->d_flags, 0, 4 * (n + 2), h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_src.p, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_flags.p, 0, 4 * (n + 2), h->stream));
     const int32_t one = 1;
-    CENT_HIP(hipMemcpyAsync(h->d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_flags.p, &one, 4, hipMemcpyHostToDevice, h->stream));
     const int grid = cent_blocks(G * n);
-    a.cur = h->d_fa;
-    cent_init_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a, h->d_src, ns);
-    CENT_HIP(hipGetLastError());
-    // forward: level L can reach something only while L <= n - 1
+    a.cur = h->d_fa.p;
+    cent_init_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a, h->d_src.p, ns);
+    GH_HIP(hipGetLastError());
     int32_t maxd = 0;
-    std::vector<int32_t> fl(CENT_CHECK_EVERY);
-    for (int64_t L = 1, checked = 0; L <= n - 1; ++L) {
-        a.level = (int32_t)L;
-        a.cur = (L & 1) ? h->d_fa : h->d_fb;
-        a.nxt = (L & 1) ? h->d_fb : h->d_fa;
+    GH_TRY_ST(gh_level_loop(h, n, h->d_flags.p, CENT_CHECK_EVERY, &maxd, [&](int32_t L) -> gh_status {
+        a.level = L;
+        a.cur = (L & 1) ? h->d_fa.p : h->d_fb.p;
+        a.nxt = (L & 1) ? h->d_fb.p : h->d_fa.p;
         cent_fwd_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a);
-        CENT_HIP(hipGetLastError());
-        if (L % CENT_CHECK_EVERY == 0 || L == n - 1) {
-            const int64_t cnt = L - checked;
-            CENT_HIP(hipMemcpyAsync(fl.data(), h->d_flags + checked + 1, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
-            CENT_HIP(hipStreamSynchronize(h->stream));
-            bool stop = false;
-            for (int64_t i = 0; i < cnt; ++i) {
-                if (fl[i]) maxd = (int32_t)(checked + 1 + i);
-                else { stop = true; break; }
-            }
-            checked = L;
-            if (stop) break;
-        }
-    }
+        GH_HIP(hipGetLastError());
+        return GH_OK;
+    }));
     const int want_delta = d_bc != nullptr, want_lam = d_ld != nullptr;
     if (want_delta || want_lam) {
         for (int32_t L = maxd; L >= 1; --L) {
@@ -390,12 +366,12 @@ gh_status cent_run_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, 
             cent_bwd_kernel<<<dim3(grid), dim3(CENT_BLOCK), 0, h->stream>>>(a, want_delta, want_lam);
         }
         cent_vertex_sum_kernel<<<dim3(cent_blocks(n)), dim3(CENT_BLOCK), 0, h->stream>>>(a, d_bc, d_ld);
-        CENT_HIP(hipGetLastError());
+        GH_HIP(hipGetLastError());
     }
     if (d_reached) {
         cent_source_sum_kernel<<<dim3((unsigned)((n + CENT_SRC_CHUNK - 1) / CENT_SRC_CHUNK), (unsigned)G), dim3(CENT_BLOCK), 0,
                                  h->stream>>>(a, d_reached, d_dsum);
-        CENT_HIP(hipGetLastError());
+        GH_HIP(hipGetLastError());
     }
     return GH_OK;
 }
@@ -408,18 +384,8 @@ extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t 
     *out = nullptr;
     if (n < 1 || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "n must be in [1, 2^31)");
     if (n_edges < 0 || (n_edges > 0 && !edges)) return fail(GH_ERR_INVALID, "bad edge list");
-    // canonical edge set: self-loops dropped, duplicates merged, (min, max)
     std::vector<uint64_t> key;
-    key.reserve((size_t)n_edges);
-    for (int64_t i = 0; i < n_edges; ++i) {
-        const int64_t u = edges[2 * i], v = edges[2 * i + 1];
-        if (u < 0 || u >= n || v < 0 || v >= n)
-            return fail(GH_ERR_INVALID, "edge " + std::to_string(i) + " has a vertex id outside [0, n)");
-        if (u == v) continue;
-        key.push_back(((uint64_t)std::min(u, v) << 32) | (uint64_t)std::max(u, v));
-    }
-    std::sort(key.begin(), key.end());
-    key.erase(std::unique(key.begin(), key.end()), key.end());
+    GH_TRY_ST(gh_canonical_edge_keys(n, n_edges, edges, false, "edge", &key, &g_cent_error));
     // symmetric CSR, neighbours ascending
     std::vector<int64_t> ptr((size_t)n + 1, 0);
     for (uint64_t k : key) { ++ptr[(k >> 32) + 1]; ++ptr[(k & 0xFFFFFFFFu) + 1]; }
@@ -436,20 +402,18 @@ extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t 
         const int64_t d = ptr[i + 1] - ptr[i];
         inv_deg[i] = d ? 1.0 / (double)d : 0.0;
     }
-    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
     gh_cent *h = new gh_cent();
-    h->device = device_id;
+    h->budget = CENT_DEFAULT_BUDGET;
     h->n = n;
     h->edges = (int64_t)key.size();
     auto bail = [&](gh_status st, const std::string &msg) { gh_cent_destroy(h); return fail(st, msg); };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(GH_ERR_HIP, "hipStreamCreate failed");
-    if (hipMalloc((void **)&h->d_ptr, 8 * ptr.size()) != hipSuccess ||
-        hipMalloc((void **)&h->d_adj, std::max<size_t>(4 * adj.size(), 4)) != hipSuccess ||
-        hipMalloc((void **)&h->d_inv_deg, 8 * inv_deg.size()) != hipSuccess)
+    const gh_status st = gh_host_open(h, device_id, &g_cent_error);
+    if (st != GH_OK) { gh_cent_destroy(h); return st; }
+    if (!h->d_ptr.alloc(8 * ptr.size()) || !h->d_adj.alloc(4 * adj.size()) || !h->d_inv_deg.alloc(8 * inv_deg.size()))
         return bail(GH_ERR_NOMEM, "hipMalloc failed");
-    if (hipMemcpy(h->d_ptr, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        (!adj.empty() && hipMemcpy(h->d_adj, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(h->d_inv_deg, inv_deg.data(), 8 * inv_deg.size(), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(h->d_ptr.p, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        (!adj.empty() && hipMemcpy(h->d_adj.p, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(h->d_inv_deg.p, inv_deg.data(), 8 * inv_deg.size(), hipMemcpyHostToDevice) != hipSuccess)
         return bail(GH_ERR_HIP, "upload failed");
     *out = h;
     return GH_OK;
@@ -457,13 +421,7 @@ extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t 
 
 extern "C" void gh_cent_destroy(gh_cent_handle h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    cent_free_state(h);
-    if (h->d_ptr) (void)hipFree(h->d_ptr);
-    if (h->d_adj) (void)hipFree(h->d_adj);
-    if (h->d_inv_deg) (void)hipFree(h->d_inv_deg);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    gh_host_close(h);
     delete h;
 }
 
@@ -472,17 +430,15 @@ extern "C" const char *gh_cent_last_error(gh_cent_handle h) { return h ? h->err.
 extern "C" int64_t gh_cent_edge_count(gh_cent_handle h) { return h ? h->edges : -1; }
 
 extern "C" gh_status gh_cent_csr_device(gh_cent_handle h, const int64_t **indptr, const int32_t **indices) {
+    if (!h) g_cent_error = "handle is NULL";
     if (!h || !indptr || !indices) return GH_ERR_INVALID;
-    *indptr = h->d_ptr;
-    *indices = h->d_adj;
+    *indptr = h->d_ptr.p;
+    *indices = h->d_adj.p;
     return GH_OK;
 }
 
 extern "C" gh_status gh_cent_set_memory_budget(gh_cent_handle h, int64_t bytes) {
-    if (!h) return GH_ERR_INVALID;
-    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
-    h->budget = bytes ? bytes : CENT_DEFAULT_BUDGET;
-    return GH_OK;
+    return gh_host_set_budget(h, bytes, CENT_DEFAULT_BUDGET, &g_cent_error);
 }
 
 extern "C" gh_status gh_cent_paths(gh_cent_handle h, int64_t n_sources, const int32_t *sources, double *betweenness,
@@ -502,43 +458,32 @@ extern "C" gh_status gh_cent_paths(gh_cent_handle h, int64_t n_sources, const in
     const int64_t groups = (n_sources + 63) / 64;
     int64_t G = std::max<int64_t>(1, h->budget / cent_bytes_per_group(n));
     G = std::min<int64_t>({G, groups, (int64_t)65535});   // 65535: grid.y of the per-source sums
-    gh_status st = cent_reserve(h, G);
-    if (st != GH_OK) return st;
-    double *d_bc = nullptr, *d_ld = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : {(void *)d_bc, (void *)d_ld, (void *)d_cnt}) if (p) (void)hipFree(p);
-    };
-    if ((betweenness && hipMalloc((void **)&d_bc, 8 * n) != hipSuccess) || (load && hipMalloc((void **)&d_ld, 8 * n) != hipSuccess) ||
-        (reached && hipMalloc((void **)&d_cnt, 16 * groups * 64) != hipSuccess)) {
-        cleanup();
+    GH_TRY_ST(cent_reserve(h, G));
+    gh_dev<double> d_bc, d_ld;               // allocated only for the outputs asked for
+    gh_dev<unsigned long long> d_cnt;        // reached, then dist_sum, 64 per group
+    if ((betweenness && !d_bc.alloc(8 * n)) || (load && !d_ld.alloc(8 * n)) || (reached && !d_cnt.alloc(16 * groups * 64)))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for the outputs");
-    }
-    st = GH_OK;
-    do {
-        if (d_bc && hipMemsetAsync(d_bc, 0, 8 * n, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
-        if (d_ld && hipMemsetAsync(d_ld, 0, 8 * n, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
-        if (d_cnt && hipMemsetAsync(d_cnt, 0, 16 * groups * 64, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipMemsetAsync failed"); break; }
-        for (int64_t g0 = 0; g0 < groups && st == GH_OK; g0 += G) {
+    auto run = [&]() -> gh_status {
+        if (d_bc.p) GH_HIP(hipMemsetAsync(d_bc.p, 0, 8 * n, h->stream));
+        if (d_ld.p) GH_HIP(hipMemsetAsync(d_ld.p, 0, 8 * n, h->stream));
+        if (d_cnt.p) GH_HIP(hipMemsetAsync(d_cnt.p, 0, 16 * groups * 64, h->stream));
+        for (int64_t g0 = 0; g0 < groups; g0 += G) {
             const int64_t gb = std::min(G, groups - g0);
             const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
-            st = cent_run_batch(h, gb, sources + 64 * g0, ns, d_bc, d_ld, d_cnt ? d_cnt + 64 * g0 : nullptr,
-                                d_cnt ? d_cnt + 64 * groups + 64 * g0 : nullptr);
+            GH_TRY_ST(cent_run_batch(h, gb, sources + 64 * g0, ns, d_bc.p, d_ld.p, d_cnt.p ? d_cnt.p + 64 * g0 : nullptr,
+                                     d_cnt.p ? d_cnt.p + 64 * groups + 64 * g0 : nullptr));
         }
-        if (st != GH_OK) break;
-        if (d_bc && hipMemcpyAsync(betweenness, d_bc, 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
-        if (d_ld && hipMemcpyAsync(load, d_ld, 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
-        if (d_cnt) {
-            if (hipMemcpyAsync(reached, d_cnt, 8 * n_sources, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipMemcpyAsync(dist_sum, d_cnt + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-                st = fail(GH_ERR_HIP, "copy failed");
-                break;
-            }
+        if (d_bc.p) GH_HIP(hipMemcpyAsync(betweenness, d_bc.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (d_ld.p) GH_HIP(hipMemcpyAsync(load, d_ld.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (d_cnt.p) {
+            GH_HIP(hipMemcpyAsync(reached, d_cnt.p, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
+            GH_HIP(hipMemcpyAsync(dist_sum, d_cnt.p + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
         }
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "hipStreamSynchronize failed"); break; }
-    } while (false);
-    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
-    cleanup();
+        GH_HIP(hipStreamSynchronize(h->stream));
+        return GH_OK;
+    };
+    const gh_status st = run();
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);   // nothing is in flight when the outputs are freed
     return st;
 }
 
@@ -552,40 +497,34 @@ extern "C" gh_status gh_cent_pagerank(gh_cent_handle h, double alpha, int32_t ma
     if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
     const int64_t n = h->n;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(PR_MAX_BLOCKS, (n + PR_BLOCK / 8 - 1) / (PR_BLOCK / 8)));
-    double *d_x = nullptr, *d_part = nullptr;
-    PrState *d_st = nullptr;
-    if (hipMalloc((void **)&d_x, 16 * n) != hipSuccess || hipMalloc((void **)&d_part, 16 * (size_t)nb) != hipSuccess ||
-        hipMalloc((void **)&d_st, sizeof(PrState)) != hipSuccess) {
-        for (void *p : {(void *)d_x, (void *)d_part, (void *)d_st}) if (p) (void)hipFree(p);
-        return fail(GH_ERR_NOMEM, "hipMalloc failed");
-    }
-    double *xb[2] = {d_x, d_x + n};
-    double *epart = d_part, *dpart = d_part + nb;
-    gh_status st = GH_OK;
-    PrState hs{0.0, 0, 0};
-    do {
-        if (hipMemcpyAsync(d_st, &hs, sizeof(hs), hipMemcpyHostToDevice, h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
-        pr_init_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr, xb[0], dpart);
-        pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, 0, max_iter, d_st);
-        for (int32_t it = 1; it <= max_iter; ++it) {
-            pr_step_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr, h->d_adj, h->d_inv_deg, alpha, d_st,
+    gh_dev<double> d_x, d_part;
+    gh_dev<PrState> d_st;
+    if (!d_x.alloc(16 * n) || !d_part.alloc(16 * (size_t)nb) || !d_st.alloc(sizeof(PrState))) return fail(GH_ERR_NOMEM, "hipMalloc failed");
+    double *xb[2] = {d_x.p, d_x.p + n};
+    double *epart = d_part.p, *dpart = d_part.p + nb;
+    auto run = [&]() -> gh_status {
+        PrState hs{0.0, 0, 0};
+        GH_HIP(hipMemcpyAsync(d_st.p, &hs, sizeof(hs), hipMemcpyHostToDevice, h->stream));
+        pr_init_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr.p, xb[0], dpart);
+        pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, 0, max_iter, d_st.p);
+        for (int32_t it = 1; it <= max_iter && !hs.done; ++it) {
+            pr_step_kernel<<<dim3(nb), dim3(PR_BLOCK), 0, h->stream>>>(n, h->d_ptr.p, h->d_adj.p, h->d_inv_deg.p, alpha, d_st.p,
                                                                         xb[(it - 1) & 1], xb[it & 1], epart, dpart);
-            pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, it, max_iter, d_st);
-            if (hipGetLastError() != hipSuccess) { st = fail(GH_ERR_HIP, "PageRank launch failed"); break; }
+            pr_check_kernel<<<dim3(1), dim3(PR_BLOCK), 0, h->stream>>>(nb, epart, dpart, (double)n * tol, it, max_iter, d_st.p);
+            GH_HIP(hipGetLastError());
             if (it % PR_CHECK_EVERY == 0 || it == max_iter) {
-                if (hipMemcpyAsync(&hs, d_st, sizeof(hs), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                    hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
-                if (hs.done) break;
+                GH_HIP(hipMemcpyAsync(&hs, d_st.p, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+                GH_HIP(hipStreamSynchronize(h->stream));
             }
         }
-        if (st != GH_OK) break;
         const int32_t last = hs.iters > 0 ? hs.iters : max_iter;
-        if (hipMemcpyAsync(x, xb[last & 1], 8 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) { st = fail(GH_ERR_HIP, "copy failed"); break; }
+        GH_HIP(hipMemcpyAsync(x, xb[last & 1], 8 * n, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
         *iterations = hs.iters;
-    } while (false);
-    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)d_x, (void *)d_part, (void *)d_st}) (void)hipFree(p);
+        return GH_OK;
+    };
+    const gh_status st = run();
+    if (st != GH_OK) (void)hipStreamSynchronize(h->stream);   // nothing is in flight when the buffers are freed
     return st;
 }
 

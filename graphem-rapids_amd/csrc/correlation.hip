@@ -28,7 +28,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/graphem_hip.h"
+#include "host_util.h"
 
 #define CORR_GOLDEN 0x9E3779B97F4A7C15ull
 #define CORR_BLOCK 256
@@ -219,77 +219,55 @@ __global__ __launch_bounds__(CORR_BLOCK) void corr_moments_kernel(int64_t n, int
     }
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)) == hipSuccess; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 inline unsigned corr_grid(int64_t items) {
     return (unsigned)std::min<int64_t>(CORR_MAX_X_BLOCKS, std::max<int64_t>(1, (items + CORR_BLOCK - 1) / CORR_BLOCK));
 }
 
 }  // namespace
 
-struct gh_corr {
-    int device = -1;                 // < 0: host path
-    hipStream_t stream = nullptr;
-    int64_t budget = CORR_DEFAULT_BUDGET;
+struct gh_corr : gh_host {          // device < 0: host path
     int64_t n = 0, ns = 0, es = 0;   // points; row strides of order / gs / ge / c / u and of E (multiples of 4)
     int32_t m = 0;
     // per column and sorted position: the point, its tie group's first position and the position after its last
-    int32_t *d_order = nullptr, *d_gs = nullptr, *d_ge = nullptr;
+    gh_dev<int32_t> d_order, d_gs, d_ge;
     std::vector<int32_t> h_order, h_gs, h_ge;
-    std::string err;
 };
 
 static thread_local std::string g_corr_error;
 
 namespace {
 
-#define CORR_HIP(call)                                                                 \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
-    } while (0)
-
-void corr_free(gh_corr *h) {
-    if (h->d_order) (void)hipFree(h->d_order);
-    if (h->d_gs) (void)hipFree(h->d_gs);
-    if (h->d_ge) (void)hipFree(h->d_ge);
-    h->d_order = h->d_gs = h->d_ge = nullptr;
-}
-
 gh_status corr_prepare_device(gh_corr *h, const double *columns) {
     const int64_t n = h->n, ns = h->ns;
     const size_t table = 4 * (size_t)ns * h->m;
-    if (hipMalloc((void **)&h->d_order, table) != hipSuccess || hipMalloc((void **)&h->d_gs, table) != hipSuccess ||
-        hipMalloc((void **)&h->d_ge, table) != hipSuccess) {
+    if (!h->d_order.alloc(table) || !h->d_gs.alloc(table) || !h->d_ge.alloc(table)) {
         h->err = "hipMalloc failed for " + std::to_string(3 * table) + " bytes of column order";
         return GH_ERR_NOMEM;
     }
-    CORR_HIP(hipMemsetAsync(h->d_order, 0, table, h->stream));   // the padding of every row is a valid point
-    DevBuf d_col, d_keys, d_skeys, d_ids, d_tmp;
+    GH_HIP(hipMemsetAsync(h->d_order.p, 0, table, h->stream));   // the padding of every row is a valid point
+    gh_dev<double> d_col;
+    gh_dev<uint64_t> d_keys, d_skeys;
+    gh_dev<uint32_t> d_ids;
+    gh_dev<void> d_tmp;
     if (!d_col.alloc(8 * n) || !d_keys.alloc(8 * n) || !d_skeys.alloc(8 * n) || !d_ids.alloc(4 * n)) {
         h->err = "hipMalloc failed for the sort buffers";
         return GH_ERR_NOMEM;
     }
     size_t temp = 0;
-    CORR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, d_keys.as<uint64_t>(), d_skeys.as<uint64_t>(), d_ids.as<uint32_t>(),
-                                                (uint32_t *)h->d_order, (int)n, 0, 64, h->stream));
+    GH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, d_keys.p, d_skeys.p, d_ids.p,
+                                                (uint32_t *)h->d_order.p, (int)n, 0, 64, h->stream));
     if (!d_tmp.alloc(temp)) { h->err = "hipMalloc failed for the sort's work space"; return GH_ERR_NOMEM; }
     const dim3 blk(CORR_BLOCK), grd((unsigned)((n + CORR_BLOCK - 1) / CORR_BLOCK));
     for (int32_t col = 0; col < h->m; ++col) {
-        CORR_HIP(hipMemcpyAsync(d_col.p, columns + (int64_t)col * n, 8 * n, hipMemcpyHostToDevice, h->stream));
-        corr_key_kernel<<<grd, blk, 0, h->stream>>>(n, d_col.as<double>(), d_keys.as<uint64_t>(), d_ids.as<uint32_t>());
-        CORR_HIP(hipGetLastError());
-        CORR_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, temp, d_keys.as<uint64_t>(), d_skeys.as<uint64_t>(), d_ids.as<uint32_t>(),
-                                                    (uint32_t *)(h->d_order + (int64_t)col * ns), (int)n, 0, 64, h->stream));
-        corr_groups_kernel<<<grd, blk, 0, h->stream>>>(n, d_skeys.as<uint64_t>(), h->d_gs + (int64_t)col * ns, h->d_ge + (int64_t)col * ns);
-        CORR_HIP(hipGetLastError());
+        GH_HIP(hipMemcpyAsync(d_col.p, columns + (int64_t)col * n, 8 * n, hipMemcpyHostToDevice, h->stream));
+        corr_key_kernel<<<grd, blk, 0, h->stream>>>(n, d_col.p, d_keys.p, d_ids.p);
+        GH_HIP(hipGetLastError());
+        GH_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, temp, d_keys.p, d_skeys.p, d_ids.p,
+                                                    (uint32_t *)(h->d_order.p + (int64_t)col * ns), (int)n, 0, 64, h->stream));
+        corr_groups_kernel<<<grd, blk, 0, h->stream>>>(n, d_skeys.p, h->d_gs.p + (int64_t)col * ns, h->d_ge.p + (int64_t)col * ns);
+        GH_HIP(hipGetLastError());
     }
-    CORR_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
@@ -379,36 +357,38 @@ gh_status corr_device(gh_corr *h, bool plain, int32_t reps, uint64_t seed, const
     const int32_t ncu = (int32_t)ucols.size(), n_pairs = (int32_t)(pair_slots.size() / 2);
     const int64_t per_rep = 4 * ns + (int64_t)ncu * 4 * (ns + es) + 24 * (int64_t)n_pairs;
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>({(int64_t)reps, (int64_t)CORR_MAX_BATCH, h->budget / per_rep}));
-    DevBuf d_c, d_E, d_u, d_ucols, d_slots, d_sums;
+    gh_dev<uint32_t> d_c, d_E;
+    gh_dev<int32_t> d_u, d_ucols, d_slots;
+    gh_dev<unsigned long long> d_sums;
     if (!d_c.alloc(4 * (size_t)(batch * ns)) || !d_E.alloc(4 * (size_t)(batch * ncu * es)) || !d_u.alloc(4 * (size_t)(batch * ncu * ns)) ||
         !d_ucols.alloc(4 * (size_t)ncu) || !d_slots.alloc(8 * (size_t)n_pairs) || !d_sums.alloc(24 * (size_t)(batch * n_pairs))) {
         h->err = "hipMalloc failed for " + std::to_string(batch) + " replicates of " + std::to_string(per_rep) + " bytes";
         return GH_ERR_NOMEM;
     }
-    CORR_HIP(hipMemcpyAsync(d_ucols.p, ucols.data(), 4 * (size_t)ncu, hipMemcpyHostToDevice, h->stream));
-    CORR_HIP(hipMemcpyAsync(d_slots.p, pair_slots.data(), 8 * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(d_ucols.p, ucols.data(), 4 * (size_t)ncu, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(d_slots.p, pair_slots.data(), 8 * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
     const unsigned gx = corr_grid(n);
     const unsigned mx = (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, (n + 16 * CORR_BLOCK - 1) / (16 * CORR_BLOCK)));
     for (int64_t b0 = 0; b0 < reps; b0 += batch) {
         const int64_t nb = std::min<int64_t>(batch, reps - b0);
-        if (plain) CORR_HIP(hipMemsetD32Async((hipDeviceptr_t)d_c.p, 1, (size_t)(nb * ns), h->stream));
+        if (plain) GH_HIP(hipMemsetD32Async((hipDeviceptr_t)d_c.p, 1, (size_t)(nb * ns), h->stream));
         else {
-            CORR_HIP(hipMemsetAsync(d_c.p, 0, 4 * (size_t)(nb * ns), h->stream));
-            corr_counts_kernel<<<dim3(gx, (unsigned)nb), dim3(CORR_BLOCK), 0, h->stream>>>(n, ns, seed, b0, d_c.as<uint32_t>());
-            CORR_HIP(hipGetLastError());
+            GH_HIP(hipMemsetAsync(d_c.p, 0, 4 * (size_t)(nb * ns), h->stream));
+            corr_counts_kernel<<<dim3(gx, (unsigned)nb), dim3(CORR_BLOCK), 0, h->stream>>>(n, ns, seed, b0, d_c.p);
+            GH_HIP(hipGetLastError());
         }
         corr_scan_kernel<<<dim3((unsigned)ncu, (unsigned)nb), dim3(CORR_SCAN_BLOCK), 0, h->stream>>>(
-            n, ns, es, d_c.as<uint32_t>(), h->d_order, d_ucols.as<int32_t>(), ncu, d_E.as<uint32_t>());
-        CORR_HIP(hipGetLastError());
+            n, ns, es, d_c.p, h->d_order.p, d_ucols.p, ncu, d_E.p);
+        GH_HIP(hipGetLastError());
         corr_rank_kernel<<<dim3(gx, (unsigned)ncu, (unsigned)nb), dim3(CORR_BLOCK), 0, h->stream>>>(
-            n, ns, es, h->d_order, h->d_gs, h->d_ge, d_ucols.as<int32_t>(), ncu, d_E.as<uint32_t>(), d_u.as<int32_t>());
-        CORR_HIP(hipGetLastError());
-        CORR_HIP(hipMemsetAsync(d_sums.p, 0, 24 * (size_t)(nb * n_pairs), h->stream));
+            n, ns, es, h->d_order.p, h->d_gs.p, h->d_ge.p, d_ucols.p, ncu, d_E.p, d_u.p);
+        GH_HIP(hipGetLastError());
+        GH_HIP(hipMemsetAsync(d_sums.p, 0, 24 * (size_t)(nb * n_pairs), h->stream));
         corr_moments_kernel<<<dim3(mx, (unsigned)n_pairs, (unsigned)nb), dim3(CORR_BLOCK), 0, h->stream>>>(
-            n, ns, d_c.as<uint32_t>(), d_u.as<int32_t>(), d_slots.as<int32_t>(), ncu, n_pairs, d_sums.as<unsigned long long>());
-        CORR_HIP(hipGetLastError());
-        CORR_HIP(hipMemcpyAsync(sums + b0 * n_pairs * 3, d_sums.p, 24 * (size_t)(nb * n_pairs), hipMemcpyDeviceToHost, h->stream));
-        CORR_HIP(hipStreamSynchronize(h->stream));
+            n, ns, d_c.p, d_u.p, d_slots.p, ncu, n_pairs, d_sums.p);
+        GH_HIP(hipGetLastError());
+        GH_HIP(hipMemcpyAsync(sums + b0 * n_pairs * 3, d_sums.p, 24 * (size_t)(nb * n_pairs), hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
     }
     return GH_OK;
 }
@@ -444,56 +424,32 @@ extern "C" gh_status gh_corr_create(gh_corr_handle *out, int device_id, int64_t 
             return GH_ERR_INVALID;
         }
     gh_corr *h = new gh_corr();
-    h->device = device_id < 0 ? -1 : device_id;
+    h->budget = CORR_DEFAULT_BUDGET;
     h->n = n;
     h->m = m;
     h->ns = corr_pad4(n);
     h->es = corr_pad4(n + 1);
-    if (h->device < 0) {
-        corr_prepare_host(h, columns);
-        *out = h;
-        return GH_OK;
+    gh_status st = GH_OK;
+    if (device_id < 0) corr_prepare_host(h, columns);
+    else {
+        st = gh_host_open(h, device_id, &g_corr_error);
+        if (st == GH_OK && (st = corr_prepare_device(h, columns)) != GH_OK) g_corr_error = h->err;
     }
-    if (hipSetDevice(device_id) != hipSuccess) {
-        delete h;
-        g_corr_error = "invalid device ordinal " + std::to_string(device_id);
-        return GH_ERR_RUNTIME;
-    }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        g_corr_error = "hipStreamCreate failed";
-        return GH_ERR_HIP;
-    }
-    const gh_status st = corr_prepare_device(h, columns);
-    if (st != GH_OK) {
-        g_corr_error = h->err;
-        corr_free(h);
-        (void)hipStreamDestroy(h->stream);
-        delete h;
-        return st;
-    }
+    if (st != GH_OK) { gh_corr_destroy(h); return st; }
     *out = h;
     return GH_OK;
 }
 
 extern "C" void gh_corr_destroy(gh_corr_handle h) {
     if (!h) return;
-    if (h->device >= 0) {
-        (void)hipSetDevice(h->device);
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        corr_free(h);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
+    gh_host_close(h);
     delete h;
 }
 
 extern "C" const char *gh_corr_last_error(gh_corr_handle h) { return h ? h->err.c_str() : g_corr_error.c_str(); }
 
 extern "C" gh_status gh_corr_set_memory_budget(gh_corr_handle h, int64_t bytes) {
-    if (!h) return GH_ERR_INVALID;
-    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
-    h->budget = bytes ? bytes : CORR_DEFAULT_BUDGET;
-    return GH_OK;
+    return gh_host_set_budget(h, bytes, CORR_DEFAULT_BUDGET, &g_corr_error);
 }
 
 extern "C" gh_status gh_corr_matrix(gh_corr_handle h, double *out, int64_t *sums) {

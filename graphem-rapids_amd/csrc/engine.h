@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/graphem_hip.h"
+#include "host_util.h"   // GH_HIP, GH_TRY_ST, GH_LAUNCH_CHECK
 
 // Candidate-list capacity per query in the filtered KNN scan, and the LDS sort size.
 #define GH_CAND_CAP 16384   /* (8192 until round 3: one query of a 16 M-vertex run reached 8777 candidates and its exhaustive fallback cost 0.5 s) */
@@ -334,27 +335,3 @@ gh_status gh_launch_unpad(gh_engine *h, const float *d_src_nLD, float *d_dst_nD)
 gh_status gh_launch_sample(gh_engine *h);                  // device sampler -> d_sampled
 gh_status gh_launch_arange(gh_engine *h);
 gh_status gh_ensure_sample(gh_engine *h);                  // run a pending stand-alone sampler launch
-
-#define GH_HIP(call)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            h->err = std::string(#call) + ": " + hipGetErrorString(e_);                     \
-            return GH_ERR_HIP;                                                              \
-        }                                                                                   \
-    } while (0)
-
-#define GH_TRY_ST(x)                                                                        \
-    do {                                                                                    \
-        gh_status st_ = (x);                                                                \
-        if (st_ != GH_OK) return st_;                                                       \
-    } while (0)
-
-#define GH_LAUNCH_CHECK()                                                                   \
-    do {                                                                                    \
-        hipError_t e_ = hipGetLastError();                                                  \
-        if (e_ != hipSuccess) {                                                             \
-            h->err = std::string("kernel launch: ") + hipGetErrorString(e_);                \
-            return GH_ERR_HIP;                                                              \
-        }                                                                                   \
-    } while (0)

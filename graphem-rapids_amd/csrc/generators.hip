@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/graphem_hip.h"
+#include "host_util.h"
 
 #define GEN_GOLDEN 0x9E3779B97F4A7C15ull
 #define GEN_BLOCK 256
@@ -301,42 +301,24 @@ __global__ __launch_bounds__(GEN_BLOCK) void gen_unpack_kernel(int64_t n_edges, 
 inline unsigned gen_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + GEN_BLOCK - 1) / GEN_BLOCK); }
 inline int gen_bits(int64_t n) { int b = 1; while (b < 32 && ((int64_t)1 << b) < n) ++b; return b; }
 
-// a device allocation that frees itself
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)) == hipSuccess; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 }  // namespace
 
-struct gh_gen {
-    int device = -1;                 // < 0: host path
-    hipStream_t stream = nullptr;
-    int64_t budget = GEN_DEFAULT_BUDGET;
+struct gh_gen : gh_host {           // device < 0: host path
     int64_t n_edges = 0;
-    int32_t *d_edges = nullptr;      // device result (E, 2)
+    gh_dev<int32_t> d_edges;         // device result (E, 2)
     std::vector<int32_t> h_edges;    // host-path result
     int64_t pos_count = 0;           // n * dim of the last geometric call
-    float *d_pos = nullptr;
+    gh_dev<float> d_pos;
     std::vector<float> h_pos;
-    std::string err;
 };
 
 static thread_local std::string g_gen_error;
 
 namespace {
 
-#define GEN_HIP(call)                                                                  \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
-    } while (0)
-
 void gen_drop_result(gh_gen *h) {
-    if (h->d_edges) { (void)hipFree(h->d_edges); h->d_edges = nullptr; }
-    if (h->d_pos) { (void)hipFree(h->d_pos); h->d_pos = nullptr; }
+    h->d_edges.reset();
+    h->d_pos.reset();
     h->h_edges.clear();
     h->h_pos.clear();
     h->n_edges = 0;
@@ -350,23 +332,22 @@ gh_status gen_over_budget(gh_gen *h, const char *what, int64_t edges, int64_t by
 }
 
 // Sorts `keys` (n_edges of them, device) with `alt` as the second buffer and leaves the int32 pairs in h->d_edges.
-gh_status gen_finish_device(gh_gen *h, DevBuf &keys, DevBuf &alt, int64_t n_edges, int64_t n_vertices) {
+gh_status gen_finish_device(gh_gen *h, gh_dev<uint64_t> &keys, gh_dev<uint64_t> &alt, int64_t n_edges, int64_t n_vertices) {
     if (n_edges >= ((int64_t)1 << 31)) { h->err = "more than 2^31 - 1 edges"; return GH_ERR_INVALID; }
     if (n_edges > 0) {
-        hipcub::DoubleBuffer<uint64_t> db(keys.as<uint64_t>(), alt.as<uint64_t>());
+        hipcub::DoubleBuffer<uint64_t> db(keys.p, alt.p);
         size_t temp = 0;
         const int end_bit = 32 + gen_bits(n_vertices);
-        GEN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, temp, db, (int)n_edges, 0, end_bit, h->stream));
-        DevBuf tmp;
+        GH_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, temp, db, (int)n_edges, 0, end_bit, h->stream));
+        gh_dev<void> tmp;
         if (!tmp.alloc(temp)) { h->err = "hipMalloc failed for the sort's work space"; return GH_ERR_NOMEM; }
-        GEN_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, temp, db, (int)n_edges, 0, end_bit, h->stream));
+        GH_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, temp, db, (int)n_edges, 0, end_bit, h->stream));
         // the pairs go into whichever buffer the sorted keys are not in: 8 bytes per edge either way
-        DevBuf &out = db.Current() == keys.as<uint64_t>() ? alt : keys;
+        gh_dev<uint64_t> &out = db.Current() == keys.p ? alt : keys;
         gen_unpack_kernel<<<dim3(gen_grid(n_edges)), dim3(GEN_BLOCK), 0, h->stream>>>(n_edges, db.Current(), out.as<int32_t>());
-        GEN_HIP(hipGetLastError());
-        GEN_HIP(hipStreamSynchronize(h->stream));
-        h->d_edges = out.as<int32_t>();
-        out.p = nullptr;
+        GH_HIP(hipGetLastError());
+        GH_HIP(hipStreamSynchronize(h->stream));
+        h->d_edges = std::move(out);
     }
     h->n_edges = n_edges;
     return GH_OK;
@@ -388,14 +369,14 @@ gh_status gen_scan(gh_gen *h, const int64_t *counts, int64_t *offsets, int64_t i
     if (items == 0) return GH_OK;
     if (items >= ((int64_t)1 << 31)) { h->err = "more than 2^31 - 1 work items"; return GH_ERR_INVALID; }
     size_t temp = 0;
-    GEN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, counts, offsets, (int)items, h->stream));
-    DevBuf tmp;
+    GH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, counts, offsets, (int)items, h->stream));
+    gh_dev<void> tmp;
     if (!tmp.alloc(temp)) { h->err = "hipMalloc failed for the scan's work space"; return GH_ERR_NOMEM; }
-    GEN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, temp, counts, offsets, (int)items, h->stream));
+    GH_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, temp, counts, offsets, (int)items, h->stream));
     int64_t last_off = 0, last_cnt = 0;
-    GEN_HIP(hipMemcpyAsync(&last_off, offsets + items - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    GEN_HIP(hipMemcpyAsync(&last_cnt, counts + items - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    GEN_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipMemcpyAsync(&last_off, offsets + items - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(&last_cnt, counts + items - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     *total = last_off + last_cnt;
     return GH_OK;
 }
@@ -406,18 +387,10 @@ extern "C" gh_status gh_gen_create(gh_gen_handle *out, int device_id) {
     if (!out) { g_gen_error = "out is NULL"; return GH_ERR_INVALID; }
     *out = nullptr;
     gh_gen *h = new gh_gen();
-    h->device = device_id < 0 ? -1 : device_id;
-    if (h->device >= 0) {
-        if (hipSetDevice(device_id) != hipSuccess) {
-            delete h;
-            g_gen_error = "invalid device ordinal " + std::to_string(device_id);
-            return GH_ERR_RUNTIME;
-        }
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete h;
-            g_gen_error = "hipStreamCreate failed";
-            return GH_ERR_HIP;
-        }
+    h->budget = GEN_DEFAULT_BUDGET;
+    if (device_id >= 0) {
+        const gh_status st = gh_host_open(h, device_id, &g_gen_error);
+        if (st != GH_OK) { gh_gen_destroy(h); return st; }
     }
     *out = h;
     return GH_OK;
@@ -425,22 +398,14 @@ extern "C" gh_status gh_gen_create(gh_gen_handle *out, int device_id) {
 
 extern "C" void gh_gen_destroy(gh_gen_handle h) {
     if (!h) return;
-    if (h->device >= 0) {
-        (void)hipSetDevice(h->device);
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        gen_drop_result(h);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
+    gh_host_close(h);
     delete h;
 }
 
 extern "C" const char *gh_gen_last_error(gh_gen_handle h) { return h ? h->err.c_str() : g_gen_error.c_str(); }
 
 extern "C" gh_status gh_gen_set_memory_budget(gh_gen_handle h, int64_t bytes) {
-    if (!h) return GH_ERR_INVALID;
-    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
-    h->budget = bytes ? bytes : GEN_DEFAULT_BUDGET;
-    return GH_OK;
+    return gh_host_set_budget(h, bytes, GEN_DEFAULT_BUDGET, &g_gen_error);
 }
 
 extern "C" gh_status gh_gen_sbm(gh_gen_handle h, int32_t n_blocks, const int64_t *sizes, const double *P, uint64_t seed,
@@ -507,24 +472,26 @@ extern "C" gh_status gh_gen_sbm(gh_gen_handle h, int32_t n_blocks, const int64_t
         return GH_OK;
     }
     if (16 * n_seg > h->budget) return gen_over_budget(h, "block model segment counts", -1, 16 * n_seg);
-    DevBuf d_pairs, d_tables, d_counts, d_offsets, d_keys, d_alt;
+    gh_dev<SbmPair> d_pairs;
+    gh_dev<uint64_t> d_tables, d_keys, d_alt;
+    gh_dev<int64_t> d_counts, d_offsets;
     if (!d_pairs.alloc(sizeof(SbmPair) * pairs.size()) || !d_tables.alloc(8 * tables.size()) || !d_counts.alloc(8 * n_seg) ||
         !d_offsets.alloc(8 * n_seg))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for the block model's segment state");
-    GEN_HIP(hipMemcpyAsync(d_pairs.p, pairs.data(), sizeof(SbmPair) * pairs.size(), hipMemcpyHostToDevice, h->stream));
-    if (!tables.empty()) GEN_HIP(hipMemcpyAsync(d_tables.p, tables.data(), 8 * tables.size(), hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(d_pairs.p, pairs.data(), sizeof(SbmPair) * pairs.size(), hipMemcpyHostToDevice, h->stream));
+    if (!tables.empty()) GH_HIP(hipMemcpyAsync(d_tables.p, tables.data(), 8 * tables.size(), hipMemcpyHostToDevice, h->stream));
     const unsigned grid = std::min<unsigned>(gen_grid(n_seg), GEN_MAX_BLOCKS);
-    gen_sbm_kernel<false><<<dim3(grid), dim3(GEN_BLOCK), 0, h->stream>>>(n_seg, seed, d_pairs.as<SbmPair>(), n_pairs, d_tables.as<uint64_t>(),
-                                                                       d_counts.as<int64_t>(), nullptr, nullptr);
-    GEN_HIP(hipGetLastError());
+    gen_sbm_kernel<false><<<dim3(grid), dim3(GEN_BLOCK), 0, h->stream>>>(n_seg, seed, d_pairs.p, n_pairs, d_tables.p,
+                                                                       d_counts.p, nullptr, nullptr);
+    GH_HIP(hipGetLastError());
     int64_t total = 0;
-    gh_status st = gen_scan(h, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_seg, &total);
+    gh_status st = gen_scan(h, d_counts.p, d_offsets.p, n_seg, &total);
     if (st != GH_OK) return st;
     if (16 * n_seg + 16 * total > h->budget) return gen_over_budget(h, "block model", total, 16 * n_seg + 16 * total);
     if (!d_keys.alloc(8 * total) || !d_alt.alloc(8 * total)) return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(total) + " edges");
-    gen_sbm_kernel<true><<<dim3(grid), dim3(GEN_BLOCK), 0, h->stream>>>(n_seg, seed, d_pairs.as<SbmPair>(), n_pairs, d_tables.as<uint64_t>(),
-                                                                      nullptr, d_offsets.as<int64_t>(), d_keys.as<uint64_t>());
-    GEN_HIP(hipGetLastError());
+    gen_sbm_kernel<true><<<dim3(grid), dim3(GEN_BLOCK), 0, h->stream>>>(n_seg, seed, d_pairs.p, n_pairs, d_tables.p,
+                                                                      nullptr, d_offsets.p, d_keys.p);
+    GH_HIP(hipGetLastError());
     st = gen_finish_device(h, d_keys, d_alt, total, off[B]);
     if (st != GH_OK) return st;
     *n_edges = total;
@@ -588,34 +555,36 @@ extern "C" gh_status gh_gen_geometric(gh_gen_handle h, int64_t n, double radius,
         *n_edges = h->n_edges;
         return GH_OK;
     }
-    DevBuf d_coords, d_scoords, d_cell, d_scell, d_ids, d_sid, d_start, d_counts, d_offsets, d_keys, d_alt, d_tmp;
-    if (hipMalloc((void **)&h->d_pos, std::max<size_t>(4 * (size_t)n * dim, 8)) != hipSuccess) { h->d_pos = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc failed for the positions"); }
+    gh_dev<uint32_t> d_coords, d_scoords, d_cell, d_scell, d_ids, d_sid;
+    gh_dev<int32_t> d_start;
+    gh_dev<int64_t> d_counts, d_offsets;
+    gh_dev<uint64_t> d_keys, d_alt;
+    gh_dev<void> d_tmp;
+    if (!h->d_pos.alloc(4 * (size_t)n * dim)) return fail(GH_ERR_NOMEM, "hipMalloc failed for the positions");
     if (!d_coords.alloc(4 * (size_t)n * dim) || !d_scoords.alloc(4 * (size_t)n * dim) || !d_cell.alloc(4 * n) || !d_scell.alloc(4 * n) ||
         !d_ids.alloc(4 * n) || !d_sid.alloc(4 * n) || !d_start.alloc(4 * (n_cells + 1)) || !d_counts.alloc(8 * n) || !d_offsets.alloc(8 * n))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for the geometric graph's point state");
     const dim3 blk(GEN_BLOCK), grd(gen_grid(n));
-    gen_geo_points_kernel<<<grd, blk, 0, h->stream>>>(n, seed, g, d_coords.as<uint32_t>(), h->d_pos, d_cell.as<uint32_t>(), d_ids.as<uint32_t>());
-    GEN_HIP(hipGetLastError());
+    gen_geo_points_kernel<<<grd, blk, 0, h->stream>>>(n, seed, g, d_coords.p, h->d_pos.p, d_cell.p, d_ids.p);
+    GH_HIP(hipGetLastError());
     size_t temp = 0;
     const int cell_bits = gen_bits(n_cells);
-    GEN_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, d_cell.as<uint32_t>(), d_scell.as<uint32_t>(), d_ids.as<uint32_t>(),
-                                               d_sid.as<uint32_t>(), (int)n, 0, cell_bits, h->stream));
+    GH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, d_cell.p, d_scell.p, d_ids.p,
+                                               d_sid.p, (int)n, 0, cell_bits, h->stream));
     if (!d_tmp.alloc(temp)) return fail(GH_ERR_NOMEM, "hipMalloc failed for the sort's work space");
-    GEN_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, temp, d_cell.as<uint32_t>(), d_scell.as<uint32_t>(), d_ids.as<uint32_t>(),
-                                               d_sid.as<uint32_t>(), (int)n, 0, cell_bits, h->stream));
-    gen_geo_gather_kernel<<<grd, blk, 0, h->stream>>>(n, dim, d_coords.as<uint32_t>(), d_sid.as<uint32_t>(), d_scoords.as<uint32_t>());
-    gen_geo_cells_kernel<<<dim3(gen_grid(n_cells + 1)), blk, 0, h->stream>>>(n, n_cells, d_scell.as<uint32_t>(), d_start.as<int32_t>());
-    gen_geo_pairs_kernel<false><<<grd, blk, 0, h->stream>>>(n, g, d_scoords.as<uint32_t>(), d_sid.as<uint32_t>(), d_start.as<int32_t>(),
-                                                          d_counts.as<int64_t>(), nullptr, nullptr);
-    GEN_HIP(hipGetLastError());
+    GH_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, temp, d_cell.p, d_scell.p, d_ids.p,
+                                               d_sid.p, (int)n, 0, cell_bits, h->stream));
+    gen_geo_gather_kernel<<<grd, blk, 0, h->stream>>>(n, dim, d_coords.p, d_sid.p, d_scoords.p);
+    gen_geo_cells_kernel<<<dim3(gen_grid(n_cells + 1)), blk, 0, h->stream>>>(n, n_cells, d_scell.p, d_start.p);
+    gen_geo_pairs_kernel<false><<<grd, blk, 0, h->stream>>>(n, g, d_scoords.p, d_sid.p, d_start.p, d_counts.p, nullptr, nullptr);
+    GH_HIP(hipGetLastError());
     int64_t total = 0;
-    gh_status st = gen_scan(h, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n, &total);
+    gh_status st = gen_scan(h, d_counts.p, d_offsets.p, n, &total);
     if (st != GH_OK) return st;
     if (16 * total > h->budget) return gen_over_budget(h, "geometric graph", total, 16 * total);
     if (!d_keys.alloc(8 * total) || !d_alt.alloc(8 * total)) return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(total) + " edges");
-    gen_geo_pairs_kernel<true><<<grd, blk, 0, h->stream>>>(n, g, d_scoords.as<uint32_t>(), d_sid.as<uint32_t>(), d_start.as<int32_t>(),
-                                                         nullptr, d_offsets.as<int64_t>(), d_keys.as<uint64_t>());
-    GEN_HIP(hipGetLastError());
+    gen_geo_pairs_kernel<true><<<grd, blk, 0, h->stream>>>(n, g, d_scoords.p, d_sid.p, d_start.p, nullptr, d_offsets.p, d_keys.p);
+    GH_HIP(hipGetLastError());
     st = gen_finish_device(h, d_keys, d_alt, total, n);
     if (st != GH_OK) return st;
     *n_edges = total;
@@ -652,14 +621,15 @@ extern "C" gh_status gh_gen_ba(gh_gen_handle h, int64_t n, int64_t m, uint64_t s
     }
     const int64_t state = n * m * 4 + n * (4 + 8 + 4 + 8);
     if (16 * E + state > h->budget) return gen_over_budget(h, "preferential attachment", E, 16 * E + state);
-    DevBuf d_tgt, d_acc, d_att, d_done, d_list0, d_list1, d_cnt, d_keys, d_alt;
+    gh_dev<int32_t> d_tgt, d_acc, d_done, d_list0, d_list1, d_cnt;
+    gh_dev<int64_t> d_att;
+    gh_dev<uint64_t> d_keys, d_alt;
     if (!d_tgt.alloc(4 * n * m) || !d_acc.alloc(4 * n) || !d_att.alloc(8 * n) || !d_done.alloc(4 * n) || !d_list0.alloc(4 * n) ||
         !d_list1.alloc(4 * n) || !d_cnt.alloc(4) || !d_keys.alloc(8 * E) || !d_alt.alloc(8 * E))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(E) + " edges of attachment state");
     const dim3 blk(GEN_BLOCK);
-    gen_ba_init_kernel<<<dim3(gen_grid(n)), blk, 0, h->stream>>>(n, m, d_acc.as<int32_t>(), d_att.as<int64_t>(), d_done.as<int32_t>(),
-                                                                d_list0.as<int32_t>());
-    GEN_HIP(hipGetLastError());
+    gen_ba_init_kernel<<<dim3(gen_grid(n)), blk, 0, h->stream>>>(n, m, d_acc.p, d_att.p, d_done.p, d_list0.p);
+    GH_HIP(hipGetLastError());
     int64_t active = n - m - 1;
     int32_t round = 0;
     while (active > 0) {
@@ -667,23 +637,22 @@ extern "C" gh_status gh_gen_ba(gh_gen_handle h, int64_t n, int64_t m, uint64_t s
             return fail(GH_ERR_RUNTIME, "preferential attachment: " + std::to_string(active) + " vertices unresolved after " +
                                             std::to_string(round) + " rounds");
         ++round;
-        int32_t *cur = (round & 1) ? d_list0.as<int32_t>() : d_list1.as<int32_t>();
-        int32_t *nxt = (round & 1) ? d_list1.as<int32_t>() : d_list0.as<int32_t>();
-        GEN_HIP(hipMemsetAsync(d_cnt.p, 0, 4, h->stream));
-        gen_ba_round_kernel<<<dim3(gen_grid(active)), blk, 0, h->stream>>>(active, cur, nxt, d_cnt.as<int32_t>(), m, seed, round,
-                                                                          d_tgt.as<int32_t>(), d_acc.as<int32_t>(), d_att.as<int64_t>(),
-                                                                          d_done.as<int32_t>());
-        GEN_HIP(hipGetLastError());
+        int32_t *cur = (round & 1) ? d_list0.p : d_list1.p;
+        int32_t *nxt = (round & 1) ? d_list1.p : d_list0.p;
+        GH_HIP(hipMemsetAsync(d_cnt.p, 0, 4, h->stream));
+        gen_ba_round_kernel<<<dim3(gen_grid(active)), blk, 0, h->stream>>>(active, cur, nxt, d_cnt.p, m, seed, round,
+                                                                          d_tgt.p, d_acc.p, d_att.p, d_done.p);
+        GH_HIP(hipGetLastError());
         int32_t left = 0;
-        GEN_HIP(hipMemcpyAsync(&left, d_cnt.p, 4, hipMemcpyDeviceToHost, h->stream));
-        GEN_HIP(hipStreamSynchronize(h->stream));
+        GH_HIP(hipMemcpyAsync(&left, d_cnt.p, 4, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
         if (left >= active)
             return fail(GH_ERR_RUNTIME, "preferential attachment: round " + std::to_string(round) + " finished no vertex");
         active = left;
     }
     if (rounds) *rounds = round;
-    gen_ba_keys_kernel<<<dim3(gen_grid(E)), blk, 0, h->stream>>>(n, m, d_tgt.as<int32_t>(), d_keys.as<uint64_t>());
-    GEN_HIP(hipGetLastError());
+    gen_ba_keys_kernel<<<dim3(gen_grid(E)), blk, 0, h->stream>>>(n, m, d_tgt.p, d_keys.p);
+    GH_HIP(hipGetLastError());
     const gh_status st = gen_finish_device(h, d_keys, d_alt, E, n);
     if (st != GH_OK) return st;
     *n_edges = E;
@@ -696,8 +665,8 @@ extern "C" gh_status gh_gen_edges(gh_gen_handle h, int32_t *edges) {
     if (!edges) { h->err = "edges is NULL"; return GH_ERR_INVALID; }
     if (h->device < 0) { std::copy(h->h_edges.begin(), h->h_edges.end(), edges); return GH_OK; }
     (void)hipSetDevice(h->device);
-    GEN_HIP(hipMemcpyAsync(edges, h->d_edges, 8 * (size_t)h->n_edges, hipMemcpyDeviceToHost, h->stream));
-    GEN_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipMemcpyAsync(edges, h->d_edges.p, 8 * (size_t)h->n_edges, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
@@ -707,7 +676,7 @@ extern "C" gh_status gh_gen_positions(gh_gen_handle h, float *positions) {
     if (!positions) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
     if (h->device < 0) { std::copy(h->h_pos.begin(), h->h_pos.end(), positions); return GH_OK; }
     (void)hipSetDevice(h->device);
-    GEN_HIP(hipMemcpyAsync(positions, h->d_pos, 4 * (size_t)h->pos_count, hipMemcpyDeviceToHost, h->stream));
-    GEN_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipMemcpyAsync(positions, h->d_pos.p, 4 * (size_t)h->pos_count, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }

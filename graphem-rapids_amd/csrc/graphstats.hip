@@ -200,54 +200,34 @@ inline int gs_blocks(int64_t items) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(GS_MAX_BLOCKS, (items + GS_BLOCK - 1) / GS_BLOCK));
 }
 
-#define GS_HIP(call)                                                                   \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
-    } while (0)
-
-// frees its device buffers when a call returns, on every path
-struct GsBuffers {
-    std::vector<void *> p;
-    ~GsBuffers() { for (void *q : p) (void)hipFree(q); }
-    template <typename T> bool alloc(T **out, size_t bytes) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return false;
-        p.push_back(q);
-        *out = (T *)q;
-        return true;
-    }
-};
-
 gh_status gs_components(gh_cent *h, int32_t *labels) {
     const int64_t n = h->n;
-    GsBuffers buf;
-    int32_t *d_label = nullptr, *d_flags = nullptr;
-    if (!buf.alloc(&d_label, 4 * n) || !buf.alloc(&d_flags, 4 * (GS_CHECK_EVERY + 1))) {
+    gh_dev<int32_t> d_label, d_flags;
+    if (!d_label.alloc(4 * n) || !d_flags.alloc(4 * (GS_CHECK_EVERY + 1))) {
         h->err = "hipMalloc failed for the component labels";
         return GH_ERR_NOMEM;
     }
     const int grid = gs_blocks(n);
     const int32_t one = 1;
-    GS_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
-    gs_label_init_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label);
-    GS_HIP(hipGetLastError());
+    GH_HIP(hipMemcpyAsync(d_flags.p, &one, 4, hipMemcpyHostToDevice, h->stream));
+    gs_label_init_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label.p);
+    GH_HIP(hipGetLastError());
     // a round that hooks lowers a label, so n rounds bound the loop from far above
     for (int64_t done = 0;; done += GS_CHECK_EVERY) {
         if (done > n + GS_CHECK_EVERY) { h->err = "component labels did not settle"; return GH_ERR_RUNTIME; }
-        GS_HIP(hipMemsetAsync(d_flags + 1, 0, 4 * GS_CHECK_EVERY, h->stream));
+        GH_HIP(hipMemsetAsync(d_flags.p + 1, 0, 4 * GS_CHECK_EVERY, h->stream));
         for (int32_t r = 1; r <= GS_CHECK_EVERY; ++r) {
-            gs_hook_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, h->d_ptr, h->d_adj, d_label, d_flags, r);
-            gs_jump_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label, d_flags, r);
+            gs_hook_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, h->d_ptr.p, h->d_adj.p, d_label.p, d_flags.p, r);
+            gs_jump_kernel<<<dim3(grid), dim3(GS_BLOCK), 0, h->stream>>>(n, d_label.p, d_flags.p, r);
         }
-        GS_HIP(hipGetLastError());
+        GH_HIP(hipGetLastError());
         int32_t last = 0;
-        GS_HIP(hipMemcpyAsync(&last, d_flags + GS_CHECK_EVERY, 4, hipMemcpyDeviceToHost, h->stream));
-        GS_HIP(hipStreamSynchronize(h->stream));
+        GH_HIP(hipMemcpyAsync(&last, d_flags.p + GS_CHECK_EVERY, 4, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
         if (!last) break;
     }
-    GS_HIP(hipMemcpyAsync(labels, d_label, 4 * n, hipMemcpyDeviceToHost, h->stream));
-    GS_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipMemcpyAsync(labels, d_label.p, 4 * n, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
@@ -255,46 +235,38 @@ gh_status gs_components(gh_cent *h, int32_t *labels) {
 gh_status gs_distance_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, uint64_t *d_vis, uint64_t *d_fa, uint64_t *d_fb,
                             int32_t *d_flags, int32_t *d_src, gs_u64 *d_reached, gs_u64 *d_dsum, int32_t *d_ecc) {
     const int64_t n = h->n;
-    GS_HIP(hipMemcpyAsync(d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
-    GS_HIP(hipMemsetAsync(d_flags, 0, 4 * (n + 2), h->stream));
+    GH_HIP(hipMemcpyAsync(d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemsetAsync(d_flags, 0, 4 * (n + 2), h->stream));
     const int32_t one = 1;
-    GS_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
     const int64_t in_last = ns - 64 * (G - 1);
     const uint64_t unused_last = in_last < 64 ? ~0ull << in_last : 0;
     gs_dist_fill_kernel<<<dim3(gs_blocks(G * n)), dim3(GS_BLOCK), 0, h->stream>>>(n, G, unused_last, d_vis, d_fa);
     gs_dist_seed_kernel<<<dim3(gs_blocks(ns)), dim3(GS_BLOCK), 0, h->stream>>>(n, ns, d_src, (gs_u64 *)d_vis, (gs_u64 *)d_fa, d_reached,
                                                                               d_dsum, d_ecc);
-    GS_HIP(hipGetLastError());
+    GH_HIP(hipGetLastError());
     GsLevel a{};
-    a.ptr = h->d_ptr; a.adj = h->d_adj;
+    a.ptr = h->d_ptr.p; a.adj = h->d_adj.p;
     a.vis = d_vis; a.flags = d_flags;
     a.reached = d_reached; a.dist_sum = d_dsum; a.ecc = d_ecc;
     a.n = n;
     const int64_t per_row = std::max<int64_t>(1, GS_MAX_BLOCKS / G);
     const dim3 grid((unsigned)std::min<int64_t>(per_row, (n + GS_BLOCK - 1) / GS_BLOCK), (unsigned)G);
-    // level L can reach something only while L <= n - 1
-    std::vector<int32_t> fl(GS_CHECK_EVERY);
-    for (int64_t L = 1, checked = 0; L <= n - 1; ++L) {
-        a.level = (int32_t)L;
+    int32_t last_level = 0;   // the kernel keeps the eccentricities itself
+    return gh_level_loop(h, n, d_flags, GS_CHECK_EVERY, &last_level, [&](int32_t L) -> gh_status {
+        a.level = L;
         a.cur = (L & 1) ? d_fa : d_fb;
         a.nxt = (L & 1) ? d_fb : d_fa;
         gs_level_kernel<<<grid, dim3(GS_BLOCK), 0, h->stream>>>(a);
-        GS_HIP(hipGetLastError());
-        if (L % GS_CHECK_EVERY == 0 || L == n - 1) {
-            const int64_t cnt = L - checked;
-            GS_HIP(hipMemcpyAsync(fl.data(), d_flags + checked + 1, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
-            GS_HIP(hipStreamSynchronize(h->stream));
-            if (std::find(fl.begin(), fl.begin() + cnt, 0) != fl.begin() + cnt) break;
-            checked = L;
-        }
-    }
-    return GH_OK;
+        GH_HIP(hipGetLastError());
+        return GH_OK;
+    });
 }
 
 }  // namespace
 
 extern "C" gh_status gh_cent_components(gh_cent_handle h, int32_t *labels, int64_t *n_components) {
-    if (!h) return GH_ERR_INVALID;
+    if (!h) { cent_set_create_error("handle is NULL"); return GH_ERR_INVALID; }
     if (!labels && h->n > 0) { h->err = "labels must not be NULL"; return GH_ERR_INVALID; }
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GH_ERR_RUNTIME; }
     if (h->n > 0) {
@@ -311,7 +283,7 @@ extern "C" gh_status gh_cent_components(gh_cent_handle h, int32_t *labels, int64
 
 extern "C" gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, const int32_t *sources, int64_t *reached,
                                        int64_t *dist_sum, int32_t *eccentricity) {
-    if (!h) return GH_ERR_INVALID;
+    if (!h) { cent_set_create_error("handle is NULL"); return GH_ERR_INVALID; }
     auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
     if (n_sources < 0 || (n_sources > 0 && !sources)) return fail(GH_ERR_INVALID, "bad source list");
     for (int64_t i = 0; i < n_sources; ++i)
@@ -321,49 +293,46 @@ extern "C" gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, cons
     const int64_t n = h->n, groups = (n_sources + 63) / 64;
     int64_t G = std::max<int64_t>(1, h->budget / (24 * n));   // 3 words per (group, vertex)
     G = std::min<int64_t>({G, groups, (int64_t)65535});       // 65535: grid.y
-    GsBuffers buf;
-    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
-    int32_t *d_flags = nullptr, *d_src = nullptr, *d_ecc = nullptr;
-    gs_u64 *d_cnt = nullptr;
-    if (!buf.alloc(&d_vis, 8 * G * n) || !buf.alloc(&d_fa, 8 * G * n) || !buf.alloc(&d_fb, 8 * G * n) || !buf.alloc(&d_flags, 4 * (n + 2)) ||
-        !buf.alloc(&d_src, 4 * 64 * G) || !buf.alloc(&d_cnt, 16 * 64 * groups) || !buf.alloc(&d_ecc, 4 * 64 * groups))
+    gh_dev<uint64_t> d_vis, d_fa, d_fb;
+    gh_dev<int32_t> d_flags, d_src, d_ecc;
+    gh_dev<gs_u64> d_cnt;
+    if (!d_vis.alloc(8 * G * n) || !d_fa.alloc(8 * G * n) || !d_fb.alloc(8 * G * n) || !d_flags.alloc(4 * (n + 2)) ||
+        !d_src.alloc(4 * 64 * G) || !d_cnt.alloc(16 * 64 * groups) || !d_ecc.alloc(4 * 64 * groups))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(G) + " source groups of distance state");
-    gh_status st = GH_OK;
-    for (int64_t g0 = 0; g0 < groups && st == GH_OK; g0 += G) {
-        const int64_t gb = std::min(G, groups - g0);
-        const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
-        st = gs_distance_batch(h, gb, sources + 64 * g0, ns, d_vis, d_fa, d_fb, d_flags, d_src, d_cnt + 64 * g0,
-                               d_cnt + 64 * groups + 64 * g0, d_ecc + 64 * g0);
-    }
-    auto copy_back = [&]() -> gh_status {
-        if (reached) GS_HIP(hipMemcpyAsync(reached, d_cnt, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
-        if (dist_sum) GS_HIP(hipMemcpyAsync(dist_sum, d_cnt + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
-        if (eccentricity) GS_HIP(hipMemcpyAsync(eccentricity, d_ecc, 4 * n_sources, hipMemcpyDeviceToHost, h->stream));
-        GS_HIP(hipStreamSynchronize(h->stream));
+    auto run = [&]() -> gh_status {
+        for (int64_t g0 = 0; g0 < groups; g0 += G) {
+            const int64_t gb = std::min(G, groups - g0);
+            const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
+            GH_TRY_ST(gs_distance_batch(h, gb, sources + 64 * g0, ns, d_vis.p, d_fa.p, d_fb.p, d_flags.p, d_src.p, d_cnt.p + 64 * g0,
+                                        d_cnt.p + 64 * groups + 64 * g0, d_ecc.p + 64 * g0));
+        }
+        if (reached) GH_HIP(hipMemcpyAsync(reached, d_cnt.p, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        if (dist_sum) GH_HIP(hipMemcpyAsync(dist_sum, d_cnt.p + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        if (eccentricity) GH_HIP(hipMemcpyAsync(eccentricity, d_ecc.p, 4 * n_sources, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
         return GH_OK;
     };
-    if (st == GH_OK) st = copy_back();
+    const gh_status st = run();
     if (st != GH_OK) (void)hipStreamSynchronize(h->stream);
     return st;
 }
 
 extern "C" gh_status gh_cent_triangles(gh_cent_handle h, int64_t *triangles) {
-    if (!h) return GH_ERR_INVALID;
+    if (!h) { cent_set_create_error("handle is NULL"); return GH_ERR_INVALID; }
     if (!triangles && h->n > 0) { h->err = "triangles must not be NULL"; return GH_ERR_INVALID; }
     if (h->n == 0) return GH_OK;
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GH_ERR_RUNTIME; }
     const int64_t n = h->n, arcs = 2 * h->edges;
-    GsBuffers buf;
-    gs_u64 *d_tri = nullptr;
-    if (!buf.alloc(&d_tri, 8 * n)) { h->err = "hipMalloc failed for the triangle counts"; return GH_ERR_NOMEM; }
+    gh_dev<gs_u64> d_tri;
+    if (!d_tri.alloc(8 * n)) { h->err = "hipMalloc failed for the triangle counts"; return GH_ERR_NOMEM; }
     auto run = [&]() -> gh_status {
-        GS_HIP(hipMemsetAsync(d_tri, 0, 8 * n, h->stream));
+        GH_HIP(hipMemsetAsync(d_tri.p, 0, 8 * n, h->stream));
         if (arcs > 0) {
-            gs_triangle_kernel<<<dim3(gs_blocks(arcs)), dim3(GS_BLOCK), 0, h->stream>>>(n, arcs, h->d_ptr, h->d_adj, d_tri);
-            GS_HIP(hipGetLastError());
+            gs_triangle_kernel<<<dim3(gs_blocks(arcs)), dim3(GS_BLOCK), 0, h->stream>>>(n, arcs, h->d_ptr.p, h->d_adj.p, d_tri.p);
+            GH_HIP(hipGetLastError());
         }
-        GS_HIP(hipMemcpyAsync(triangles, d_tri, 8 * n, hipMemcpyDeviceToHost, h->stream));
-        GS_HIP(hipStreamSynchronize(h->stream));
+        GH_HIP(hipMemcpyAsync(triangles, d_tri.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
         return GH_OK;
     };
     const gh_status st = run();

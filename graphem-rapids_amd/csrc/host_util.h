@@ -1,0 +1,128 @@
+// Host plumbing shared by every handle behind the C ABI: the HIP-call checks, a device allocation that frees itself, the
+// life cycle of an analysis handle (device, stream, budget, message), the canonical edge set, and the level loop of a
+// breadth-first pass.  No kernel and no policy lives here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/graphem_hip.h"
+
+// The checks need a handle `h` in scope whose `err` takes the message "<call>: <hip error string>".
+#define GH_HIP(call)                                                                        \
+    do {                                                                                    \
+        hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            h->err = std::string(#call) + ": " + hipGetErrorString(e_);                     \
+            return GH_ERR_HIP;                                                              \
+        }                                                                                   \
+    } while (0)
+
+#define GH_TRY_ST(x)                                                                        \
+    do {                                                                                    \
+        gh_status st_ = (x);                                                                \
+        if (st_ != GH_OK) return st_;                                                       \
+    } while (0)
+
+#define GH_LAUNCH_CHECK()                                                                   \
+    do {                                                                                    \
+        hipError_t e_ = hipGetLastError();                                                  \
+        if (e_ != hipSuccess) {                                                             \
+            h->err = std::string("kernel launch: ") + hipGetErrorString(e_);                \
+            return GH_ERR_HIP;                                                              \
+        }                                                                                   \
+    } while (0)
+
+// A device allocation that frees itself.  Never smaller than 16 bytes, so an empty array still has an address to hand
+// to a kernel.  Moving it, also to a buffer of another element type, hands the allocation over.
+template <class T> struct gh_dev {
+    T *p = nullptr;
+    gh_dev() = default;
+    gh_dev(const gh_dev &) = delete;
+    gh_dev &operator=(const gh_dev &) = delete;
+    template <class U> gh_dev(gh_dev<U> &&o) noexcept : p((T *)o.release()) {}
+    template <class U> gh_dev &operator=(gh_dev<U> &&o) noexcept { reset((T *)o.release()); return *this; }
+    ~gh_dev() { reset(); }
+    T *release() { T *q = p; p = nullptr; return q; }
+    void reset(T *q = nullptr) { if (p) (void)hipFree(p); p = q; }
+    bool alloc(size_t bytes) { reset(); return hipMalloc((void **)&p, std::max<size_t>(bytes, 16)) == hipSuccess; }
+    template <class U> U *as() const { return (U *)p; }
+};
+
+// What every analysis handle (gh_ic, gh_cent, gh_gen, gh_corr) starts with.  device < 0: a host-path handle without a stream.
+struct gh_host {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    int64_t budget = 0;
+    std::string err;
+};
+
+// Selects the device and creates the handle's stream; a failure leaves its message in *msg (the module's create-time text).
+inline gh_status gh_host_open(gh_host *h, int device_id, std::string *msg) {
+    if (hipSetDevice(device_id) != hipSuccess) { *msg = "invalid device ordinal " + std::to_string(device_id); return GH_ERR_RUNTIME; }
+    h->device = device_id;
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { *msg = "hipStreamCreate failed"; return GH_ERR_HIP; }
+    return GH_OK;
+}
+
+// Waits for the handle's work and destroys its stream; the handle's gh_dev members free themselves when it is deleted.
+inline void gh_host_close(gh_host *h) {
+    if (h->device < 0) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+    h->stream = nullptr;
+}
+
+// gh_*_set_memory_budget: 0 means `dflt`; *null_msg is the module's create-time text.
+inline gh_status gh_host_set_budget(gh_host *h, int64_t bytes, int64_t dflt, std::string *null_msg) {
+    if (!h) { *null_msg = "handle is NULL"; return GH_ERR_INVALID; }
+    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
+    h->budget = bytes ? bytes : dflt;
+    return GH_OK;
+}
+
+// The canonical edge set of `count` vertex pairs on n vertices: ids validated, self-loops dropped, duplicates merged, as
+// ascending keys (a << 32) | b -- (u, v) as given when directed, else (min, max).  `noun` names a pair in the message.
+inline gh_status gh_canonical_edge_keys(int64_t n, int64_t count, const int32_t *pairs, bool directed, const char *noun,
+                                        std::vector<uint64_t> *keys, std::string *err) {
+    keys->clear();
+    keys->reserve((size_t)count);
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t u = pairs[2 * i], v = pairs[2 * i + 1];
+        if (u < 0 || u >= n || v < 0 || v >= n) {
+            *err = std::string(noun) + " " + std::to_string(i) + " has a vertex id outside [0, n)";
+            return GH_ERR_INVALID;
+        }
+        if (u == v) continue;
+        const uint64_t a = directed ? u : std::min(u, v), b = directed ? v : std::max(u, v);
+        keys->push_back((a << 32) | b);
+    }
+    std::sort(keys->begin(), keys->end());
+    keys->erase(std::unique(keys->begin(), keys->end()), keys->end());
+    return GH_OK;
+}
+
+// The host loop of a breadth-first pass whose level kernel sets d_flags[L] when level L reached something (d_flags[0] is
+// preset).  launch(L) enqueues level L = 1, 2, ..; a level can reach something only while L <= n - 1.  Every `every` levels
+// the new flags are read back, and the loop ends at the first empty one.  *last = the last level that reached something.
+template <class Launch>
+gh_status gh_level_loop(gh_host *h, int64_t n, const int32_t *d_flags, int every, int32_t *last, Launch launch) {
+    *last = 0;
+    std::vector<int32_t> fl((size_t)every);
+    for (int64_t L = 1, checked = 0; L <= n - 1; ++L) {
+        GH_TRY_ST(launch((int32_t)L));
+        if (L % every != 0 && L != n - 1) continue;
+        const int64_t cnt = L - checked;
+        GH_HIP(hipMemcpyAsync(fl.data(), d_flags + checked + 1, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < cnt; ++i) {
+            if (!fl[i]) return GH_OK;
+            *last = (int32_t)(checked + 1 + i);
+        }
+        checked = L;
+    }
+    return GH_OK;
+}

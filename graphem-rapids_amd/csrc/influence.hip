@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/graphem_hip.h"
+#include "host_util.h"
 
 #define IC_GOLDEN 0x9E3779B97F4A7C15ull
 #define IC_BLOCK 256
@@ -260,20 +260,18 @@ inline int ic_blocks(int64_t threads) {
 
 }  // namespace
 
-struct gh_ic {
-    int device = 0;
+struct gh_ic : gh_host {
     int64_t n = 0, arcs = 0;
     int directed = 0;
-    hipStream_t stream = nullptr;
-    int64_t *d_out_ptr = nullptr, *d_in_ptr = nullptr;   // d_in_* alias d_out_* for an undirected graph
-    int32_t *d_out_adj = nullptr, *d_in_adj = nullptr;
-    int64_t budget = IC_DEFAULT_BUDGET;
+    gh_dev<int64_t> d_out_ptr, d_in_own_ptr;   // d_in_own_*: the by-target CSR of a directed graph
+    gh_dev<int32_t> d_out_adj, d_in_own_adj;
+    const int64_t *d_in_ptr = nullptr;          // not owned: d_in_own_*, or d_out_* for an undirected graph
+    const int32_t *d_in_adj = nullptr;
     // chunk state, grown on demand
     int64_t cap_words = 0, cap_ents = 0, cap_counts = 0;
-    uint64_t *d_vis = nullptr, *d_fa = nullptr, *d_fb = nullptr;
-    int32_t *d_mark = nullptr, *d_list0 = nullptr, *d_list1 = nullptr, *d_touch = nullptr, *d_counts = nullptr, *d_cnt = nullptr;
-    uint8_t *d_touched = nullptr;
-    std::string err;
+    gh_dev<uint64_t> d_vis, d_fa, d_fb;
+    gh_dev<int32_t> d_mark, d_list0, d_list1, d_touch, d_counts, d_cnt;
+    gh_dev<uint8_t> d_touched;
 };
 
 static thread_local std::string g_ic_error;
@@ -281,12 +279,8 @@ static thread_local std::string g_ic_error;
 namespace {
 
 void ic_free_state(gh_ic *h) {
-    for (void *p : {(void *)h->d_vis, (void *)h->d_fa, (void *)h->d_fb, (void *)h->d_mark, (void *)h->d_list0, (void *)h->d_list1,
-                    (void *)h->d_touch, (void *)h->d_counts, (void *)h->d_cnt, (void *)h->d_touched})
-        if (p) (void)hipFree(p);
-    h->d_vis = h->d_fa = h->d_fb = nullptr;
-    h->d_mark = h->d_list0 = h->d_list1 = h->d_touch = h->d_counts = h->d_cnt = nullptr;
-    h->d_touched = nullptr;
+    h->d_vis.reset(); h->d_fa.reset(); h->d_fb.reset(); h->d_mark.reset(); h->d_list0.reset(); h->d_list1.reset();
+    h->d_touch.reset(); h->d_counts.reset(); h->d_cnt.reset(); h->d_touched.reset();
     h->cap_words = h->cap_ents = h->cap_counts = 0;
 }
 
@@ -298,18 +292,16 @@ gh_status ic_reserve(gh_ic *h, int64_t sets, int32_t W, int32_t T) {
     const int64_t words = sets * h->n * W, ents = sets * h->n;
     if (words <= h->cap_words && ents <= h->cap_ents && sets * T <= h->cap_counts) return GH_OK;
     ic_free_state(h);
-    auto alloc = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess; };
-    if (!alloc((void **)&h->d_vis, 8 * words) || !alloc((void **)&h->d_fa, 8 * words) || !alloc((void **)&h->d_fb, 8 * words) ||
-        !alloc((void **)&h->d_mark, 4 * ents) || !alloc((void **)&h->d_touched, ents) || !alloc((void **)&h->d_list0, 4 * ents) ||
-        !alloc((void **)&h->d_list1, 4 * ents) || !alloc((void **)&h->d_touch, 4 * ents) ||
-        !alloc((void **)&h->d_counts, 4 * sets * T) || !alloc((void **)&h->d_cnt, 4 * 4)) {
+    if (!h->d_vis.alloc(8 * words) || !h->d_fa.alloc(8 * words) || !h->d_fb.alloc(8 * words) || !h->d_mark.alloc(4 * ents) ||
+        !h->d_touched.alloc(ents) || !h->d_list0.alloc(4 * ents) || !h->d_list1.alloc(4 * ents) || !h->d_touch.alloc(4 * ents) ||
+        !h->d_counts.alloc(4 * sets * T) || !h->d_cnt.alloc(4 * 4)) {
         ic_free_state(h);
         h->err = "hipMalloc failed for " + std::to_string(sets) + " seed sets of chunk state";
         return GH_ERR_NOMEM;
     }
     // zero once; afterwards every chunk leaves the state zero behind it (ic_reset_kernel)
-    for (auto [p, bytes] : {std::pair<void *, size_t>{h->d_vis, 8 * words}, {h->d_fa, 8 * words}, {h->d_fb, 8 * words},
-                            {h->d_mark, 4 * ents}, {h->d_touched, (size_t)ents}})
+    for (auto [p, bytes] : {std::pair<void *, size_t>{h->d_vis.p, 8 * words}, {h->d_fa.p, 8 * words}, {h->d_fb.p, 8 * words},
+                            {h->d_mark.p, 4 * ents}, {h->d_touched.p, (size_t)ents}})
         if (hipMemsetAsync(p, 0, bytes, h->stream) != hipSuccess) { h->err = "hipMemsetAsync failed"; return GH_ERR_HIP; }
     h->cap_words = words;
     h->cap_ents = ents;
@@ -317,28 +309,22 @@ gh_status ic_reserve(gh_ic *h, int64_t sets, int32_t W, int32_t T) {
     return GH_OK;
 }
 
-#define IC_HIP(call)                                                                   \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) { h->err = std::string(#call ": ") + hipGetErrorString(e_); return GH_ERR_HIP; } \
-    } while (0)
-
 // One chunk: `sets` seed sets given as unique entry ids (s * n + v) in `seeds`; counts -> out (sets, T).
 gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds, int32_t W, int32_t T, uint64_t seed,
                        uint32_t thr, int32_t max_hops, int32_t *out) {
-    IC_HIP(hipMemsetAsync(h->d_counts, 0, sizeof(int32_t) * sets * T, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_counts.p, 0, sizeof(int32_t) * sets * T, h->stream));
     const int32_t c0[4] = {(int32_t)seeds.size(), 0, 0, (int32_t)seeds.size()};   // ring of three + touched count
     if (!seeds.empty()) {
-        IC_HIP(hipMemcpyAsync(h->d_cnt, c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
-        IC_HIP(hipMemcpyAsync(h->d_list0, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
-        IC_HIP(hipMemcpyAsync(h->d_touch, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
+        GH_HIP(hipMemcpyAsync(h->d_cnt.p, c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
+        GH_HIP(hipMemcpyAsync(h->d_list0.p, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
+        GH_HIP(hipMemcpyAsync(h->d_touch.p, seeds.data(), 4 * seeds.size(), hipMemcpyHostToDevice, h->stream));
         const int64_t si = (int64_t)seeds.size() * W;
         ic_seed_kernel<<<dim3((unsigned)((si + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
-            h->d_list0, (int64_t)seeds.size(), W, T, h->d_vis, h->d_fa, h->d_touched);
-        IC_HIP(hipGetLastError());
+            h->d_list0.p, (int64_t)seeds.size(), W, T, h->d_vis.p, h->d_fa.p, h->d_touched.p);
+        GH_HIP(hipGetLastError());
         IcLevel a{};
-        a.out_ptr = h->d_out_ptr; a.out_adj = h->d_out_adj; a.in_ptr = h->d_in_ptr; a.in_adj = h->d_in_adj;
-        a.vis = h->d_vis; a.mark = h->d_mark; a.touched = h->d_touched; a.touch_list = h->d_touch; a.touch_cnt = h->d_cnt + 3;
+        a.out_ptr = h->d_out_ptr.p; a.out_adj = h->d_out_adj.p; a.in_ptr = h->d_in_ptr; a.in_adj = h->d_in_adj;
+        a.vis = h->d_vis.p; a.mark = h->d_mark.p; a.touched = h->d_touched.p; a.touch_list = h->d_touch.p; a.touch_cnt = h->d_cnt.p + 3;
         a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = thr; a.directed = h->directed;
         a.dense = sets * h->n * W;
         a.pull_min = std::max<int64_t>(1, sets * h->n / IC_PULL_DIV);
@@ -347,32 +333,32 @@ gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds
         const int64_t last = max_hops < 0 ? h->n : std::min<int64_t>(max_hops, h->n);
         for (int64_t r = 1; r <= last; ++r) {
             a.round = (int32_t)r;
-            a.cur = (r & 1) ? h->d_fa : h->d_fb;
-            a.nxt = (r & 1) ? h->d_fb : h->d_fa;
-            a.cur_list = (r & 1) ? h->d_list0 : h->d_list1;
-            a.nxt_list = (r & 1) ? h->d_list1 : h->d_list0;
-            a.cur_cnt = h->d_cnt + (r - 1) % 3;
-            a.nxt_cnt = h->d_cnt + r % 3;
-            a.zero_cnt = h->d_cnt + (r + 1) % 3;
+            a.cur = (r & 1) ? h->d_fa.p : h->d_fb.p;
+            a.nxt = (r & 1) ? h->d_fb.p : h->d_fa.p;
+            a.cur_list = (r & 1) ? h->d_list0.p : h->d_list1.p;
+            a.nxt_list = (r & 1) ? h->d_list1.p : h->d_list0.p;
+            a.cur_cnt = h->d_cnt.p + (r - 1) % 3;
+            a.nxt_cnt = h->d_cnt.p + r % 3;
+            a.zero_cnt = h->d_cnt.p + (r + 1) % 3;
             ic_push_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
             ic_pull_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
             ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-            IC_HIP(hipGetLastError());
+            GH_HIP(hipGetLastError());
             if (r % IC_CHECK_EVERY == 0 && r < last) {
                 int32_t alive = 0;
-                IC_HIP(hipMemcpyAsync(&alive, h->d_cnt + r % 3, sizeof(alive), hipMemcpyDeviceToHost, h->stream));
-                IC_HIP(hipStreamSynchronize(h->stream));
+                GH_HIP(hipMemcpyAsync(&alive, h->d_cnt.p + r % 3, sizeof(alive), hipMemcpyDeviceToHost, h->stream));
+                GH_HIP(hipStreamSynchronize(h->stream));
                 if (alive == 0) break;
             }
         }
         const int grid_t = ic_blocks(sets * h->n * W);
-        ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch, h->d_cnt + 3, h->d_vis, h->n, W, T, h->d_counts);
-        ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch, h->d_cnt + 3, W, h->d_vis, h->d_fa, h->d_fb,
-                                                                       h->d_mark, h->d_touched);
-        IC_HIP(hipGetLastError());
+        ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, h->n, W, T, h->d_counts.p);
+        ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, W, h->d_vis.p, h->d_fa.p, h->d_fb.p,
+                                                                       h->d_mark.p, h->d_touched.p);
+        GH_HIP(hipGetLastError());
     }
-    IC_HIP(hipMemcpyAsync(out, h->d_counts, sizeof(int32_t) * sets * T, hipMemcpyDeviceToHost, h->stream));
-    IC_HIP(hipStreamSynchronize(h->stream));
+    GH_HIP(hipMemcpyAsync(out, h->d_counts.p, sizeof(int32_t) * sets * T, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
@@ -384,19 +370,8 @@ extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, i
     *out = nullptr;
     if (n < 1 || n >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "n must be in [1, 2^31)");
     if (n_arcs < 0 || (n_arcs > 0 && !arcs)) return fail(GH_ERR_INVALID, "bad arc list");
-    // canonical arc set: self-loops dropped, duplicates merged; an undirected edge as (min, max)
     std::vector<uint64_t> key;
-    key.reserve((size_t)n_arcs);
-    for (int64_t i = 0; i < n_arcs; ++i) {
-        const int64_t u = arcs[2 * i], v = arcs[2 * i + 1];
-        if (u < 0 || u >= n || v < 0 || v >= n)
-            return fail(GH_ERR_INVALID, "arc " + std::to_string(i) + " has a vertex id outside [0, n)");
-        if (u == v) continue;
-        const uint64_t a = directed ? u : std::min(u, v), b = directed ? v : std::max(u, v);
-        key.push_back((a << 32) | b);
-    }
-    std::sort(key.begin(), key.end());
-    key.erase(std::unique(key.begin(), key.end()), key.end());
+    GH_TRY_ST(gh_canonical_edge_keys(n, n_arcs, arcs, directed != 0, "arc", &key, &g_ic_error));
     // CSR of arcs by source (push) and by target (pull); undirected: both directions, and the two are the same CSR
     auto build = [&](bool by_target, std::vector<int64_t> &ptr, std::vector<int32_t> &adj) {
         ptr.assign((size_t)n + 1, 0);
@@ -414,53 +389,41 @@ extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, i
             else { adj[fill[a]++] = b; adj[fill[b]++] = a; }
         }
     };
-    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
     gh_ic *h = new gh_ic();
-    h->device = device_id;
+    h->budget = IC_DEFAULT_BUDGET;
     h->n = n;
     h->arcs = (int64_t)key.size();
     h->directed = directed ? 1 : 0;
     auto bail = [&](gh_status st, const std::string &msg) { gh_ic_destroy(h); return fail(st, msg); };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(GH_ERR_HIP, "hipStreamCreate failed");
+    const gh_status st = gh_host_open(h, device_id, &g_ic_error);
+    if (st != GH_OK) { gh_ic_destroy(h); return st; }
     for (int pass = 0; pass < (directed ? 2 : 1); ++pass) {
         std::vector<int64_t> ptr;
         std::vector<int32_t> adj;
         build(pass == 1, ptr, adj);
-        int64_t *dp = nullptr;
-        int32_t *da = nullptr;
-        if (hipMalloc((void **)&dp, 8 * ptr.size()) != hipSuccess) return bail(GH_ERR_NOMEM, "hipMalloc failed");
-        (pass ? h->d_in_ptr : h->d_out_ptr) = dp;
-        if (hipMalloc((void **)&da, std::max<size_t>(4 * adj.size(), 4)) != hipSuccess) return bail(GH_ERR_NOMEM, "hipMalloc failed");
-        (pass ? h->d_in_adj : h->d_out_adj) = da;
-        if (hipMemcpy(dp, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            (!adj.empty() && hipMemcpy(da, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess))
+        gh_dev<int64_t> &dp = pass ? h->d_in_own_ptr : h->d_out_ptr;
+        gh_dev<int32_t> &da = pass ? h->d_in_own_adj : h->d_out_adj;
+        if (!dp.alloc(8 * ptr.size()) || !da.alloc(4 * adj.size())) return bail(GH_ERR_NOMEM, "hipMalloc failed");
+        if (hipMemcpy(dp.p, ptr.data(), 8 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            (!adj.empty() && hipMemcpy(da.p, adj.data(), 4 * adj.size(), hipMemcpyHostToDevice) != hipSuccess))
             return bail(GH_ERR_HIP, "upload failed");
     }
-    if (!directed) { h->d_in_ptr = h->d_out_ptr; h->d_in_adj = h->d_out_adj; }
+    h->d_in_ptr = directed ? h->d_in_own_ptr.p : h->d_out_ptr.p;
+    h->d_in_adj = directed ? h->d_in_own_adj.p : h->d_out_adj.p;
     *out = h;
     return GH_OK;
 }
 
 extern "C" void gh_ic_destroy(gh_ic_handle h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    ic_free_state(h);
-    if (h->d_in_ptr && h->d_in_ptr != h->d_out_ptr) (void)hipFree(h->d_in_ptr);
-    if (h->d_in_adj && h->d_in_adj != h->d_out_adj) (void)hipFree(h->d_in_adj);
-    if (h->d_out_ptr) (void)hipFree(h->d_out_ptr);
-    if (h->d_out_adj) (void)hipFree(h->d_out_adj);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    gh_host_close(h);
     delete h;
 }
 
 extern "C" const char *gh_ic_last_error(gh_ic_handle h) { return h ? h->err.c_str() : g_ic_error.c_str(); }
 
 extern "C" gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes) {
-    if (!h) return GH_ERR_INVALID;
-    if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
-    h->budget = bytes ? bytes : IC_DEFAULT_BUDGET;
-    return GH_OK;
+    return gh_host_set_budget(h, bytes, IC_DEFAULT_BUDGET, &g_ic_error);
 }
 
 extern "C" int64_t gh_ic_arc_count(gh_ic_handle h) { return h ? h->arcs : -1; }

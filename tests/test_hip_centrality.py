@@ -144,6 +144,27 @@ def test_bitwise_across_budgets_edge_order_and_runs():
     h.close()
 
 
+def test_path_state_regrown_kept_and_reused_across_budgets():
+    """One handle, three calls: the path state is allocated for one group, re-grown for all five, then reused as it is."""
+    from graphem_rapids_amd import _native
+    n = 300
+    g = _native.CentGraph(n, gr.erdos_renyi_edges(n, 0.03, seed=1))
+    src = np.arange(n)   # 5 groups of 64 sources, the last one short
+    # path state per 64-source group: n * (64 * (4 + 8 + 4 + 8 + 8) + 3 * 8 + 8) bytes (dist, sigma, npred, delta, lam per
+    # entry; vis, cur, nxt and the level range per word); groups per batch = max(1, budget // that), at most the 5 there are
+    per_group = n * (64 * 32 + 32)
+    assert (1 << 30) // per_group >= 5
+    runs = []
+    for budget in (per_group, 0, per_group):   # 1 group, all 5 (0: the default, 1 GiB), 1 group in the larger state
+        g.set_memory_budget(budget)
+        runs.append(g.paths(src))
+    g.close()
+    assert runs[0][2].min() >= 1   # every source reached itself: the call did run
+    for other in runs[1:]:
+        for a, b in zip(runs[0], other):
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
 def test_exact_paths_20000_against_restatement():
     n = 20000
     edges = gr.random_regular_edges(n, 3, seed=7)

@@ -92,6 +92,26 @@ def test_invariance_edge_order_batching_chunking():
     b.close()
 
 
+def test_chunk_state_regrown_kept_and_reused_across_budgets():
+    """One handle, three calls: the chunk state is allocated for one seed set, re-grown for all 40, then reused as it is."""
+    n, T = 200, 70   # 70 trials: two 64-bit words per entry
+    rng = np.random.default_rng(5)
+    arcs = np.concatenate([_path(n), rng.integers(0, n, (20, 2))])
+    sets = [[5 * i] for i in range(40)]
+    g = _native.ICGraph(n, arcs)
+    # chunk state per seed set: n * (3 * 8 * W + 4 + 1 + 3 * 4) bytes with W = ceil(T / 64) words (vis, cur, nxt; the round
+    # stamp, the touched byte and three lists per entry); sets per chunk = max(1, budget // that), at most the 40 there are
+    per_set = n * (3 * 8 * 2 + 17)
+    assert (1 << 30) // per_set >= 40
+    runs = []
+    for budget in (per_set, 0, per_set):   # 1 set per chunk, all 40 (0: the default, 1 GiB), 1 set in the larger state
+        g.set_memory_budget(budget)
+        runs.append(g.spread(sets, 0.3, T, 11, -1, per_trial=True)[1])
+    g.close()
+    assert runs[0].shape == (40, T) and runs[0].min() >= 1   # every seed counts itself
+    assert np.array_equal(runs[0], runs[1]) and np.array_equal(runs[0], runs[2])
+
+
 @pytest.mark.parametrize("hops", [None, 2])
 def test_marginal_mode(hops):
     n, arcs, _ = GRAPHS["planted"]
