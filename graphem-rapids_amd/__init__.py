@@ -23,6 +23,8 @@ from . import graphstats
 from .graphstats import (connected_components, number_connected_components, is_connected, largest_connected_component,
                          eccentricity, diameter, radius, average_shortest_path_length, triangles, clustering,
                          average_clustering, transitivity, graph_summary, print_graph_summary)
+from . import quality
+from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality)
 from .visualization import (spearman_matrix, bootstrap_spearman, report_corr, report_full_correlation_matrix,
                             plot_radial_vs_centrality, display_benchmark_results)
 
@@ -80,4 +82,6 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "largest_connected_component", "eccentricity", "diameter", "radius", "average_shortest_path_length",
            "triangles", "clustering", "average_clustering", "transitivity", "graph_summary", "print_graph_summary",
            "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
-           "plot_radial_vs_centrality", "display_benchmark_results"]
+           "plot_radial_vs_centrality", "display_benchmark_results",
+           "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
+           "layout_quality"]

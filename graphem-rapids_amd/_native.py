@@ -159,6 +159,13 @@ SIGNATURES = {
     "gh_corr_rho": (f64, [i64, i64, i64]),
     "gh_corr_matrix": (_int, [vp, vp, vp]),
     "gh_corr_bootstrap": (_int, [vp, i32, vp, i32, u64, vp, vp]),
+    "gh_qual_create": (_int, [_P(vp), _int, i64, i64, vp]),
+    "gh_qual_destroy": (None, [vp]),
+    "gh_qual_last_error": (_str, [vp]),
+    "gh_qual_set_positions": (_int, [vp, vp, i32, i64, i32]),
+    "gh_qual_crossings": (_int, [vp, i64, vp, vp, _P(i64)]),
+    "gh_qual_pairs": (_int, [vp, i64, vp, vp]),
+    "gh_qual_edge_lengths": (_int, [vp, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -774,3 +781,57 @@ class Correlation(BudgetHandle):
 def corr_rho(sxy, sxx, syy):
     """The library's conversion of a triple of sums to rho (gh_corr_rho)."""
     return float(load().gh_corr_rho(int(sxy), int(sxx), int(syy)))
+
+
+class LayoutQuality(Handle):
+    """Thin RAII wrapper over a gh_qual_handle: exact edge-crossing counts under the engine's float32 test and edge-length
+    statistics of one layout (include/graphem_hip.h "layout quality").  edges: (E, 2) int32, ids kept as given.
+    device_id < 0 is the library's host path, which touches no device and returns the same integers."""
+    _destroy, _last_error = "gh_qual_destroy", "gh_qual_last_error"
+
+    def __init__(self, edges, n, device_id=0):
+        self.device_id = int(device_id)
+        edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        self.n, self.E = int(n), int(edges.shape[0])
+        self._create("gh_qual_create", self.device_id, self.n, self.E, ptr(edges))
+
+    def set_positions(self, pos, D=None, ld=None):
+        """Snapshot of host float32 positions (gh_qual_set_positions): an (n, D) array, or with D and ld given the first D
+        columns of a buffer of n rows of ld floats."""
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        if D is None:
+            if pos.ndim != 2 or pos.shape[0] != self.n:
+                raise ValueError(f"positions must be ({self.n}, D), got {pos.shape}")
+            D = ld = pos.shape[1]
+        elif pos.size < self.n * int(ld):
+            raise ValueError(f"a buffer of {pos.size} floats is smaller than n * ld = {self.n * int(ld)}")
+        self._raise(self.lib.gh_qual_set_positions(self.handle, ptr(pos), int(D), int(ld), 0))
+
+    def set_positions_device(self, dev_ptr, D, ld=None):
+        """Snapshot of (n, D) float32 rows at a device pointer on the handle's device, row stride ld floats (default D)."""
+        self._raise(self.lib.gh_qual_set_positions(self.handle, ctypes.c_void_p(int(dev_ptr)), int(D),
+                                                   int(D if ld is None else ld), 1))
+
+    def crossings(self, rows=None):
+        """(counts int32, their int sum) for the edge ids `rows`, any order, repeats allowed; None = all edges in order."""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            if len(rows) == 0:
+                rows = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean all edges)
+        counts = np.zeros(self.E if rows is None else len(rows), dtype=np.int32)
+        total = ctypes.c_int64()
+        self._raise(self.lib.gh_qual_crossings(self.handle, len(counts), ptr(rows), ptr(counts), ctypes.byref(total)))
+        return counts, int(total.value)
+
+    def pairs(self, pairs):
+        """bool per pair of edge ids: do the two edges cross (gh_qual_pairs)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        cross = np.zeros(len(pairs), dtype=np.uint8)
+        self._raise(self.lib.gh_qual_pairs(self.handle, len(pairs), ptr(pairs), ptr(cross)))
+        return cross.astype(bool)
+
+    def edge_lengths(self):
+        """float64 (min, max, sum, sum of squares) of the edge lengths (gh_qual_edge_lengths)."""
+        out = np.zeros(4, dtype=np.float64)
+        self._raise(self.lib.gh_qual_edge_lengths(self.handle, ptr(out)))
+        return out

@@ -4,7 +4,7 @@
 // the same launch (knn.hip).
 #include "common.h"
 
-__device__ __forceinline__ float gh_orient2d(const float *a, const float *b, const float *c) {
+__host__ __device__ __forceinline__ float gh_orient2d(const float *a, const float *b, const float *c) {
     return (b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0]);
 }
 

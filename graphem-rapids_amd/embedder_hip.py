@@ -371,6 +371,21 @@ class GraphEmbedderHIP:
     def kernel_timings(self):
         return self._engine.timings()
 
+    # ---- layout quality (quality.py) ------------------------------------------------------
+    def edge_crossings(self, sample_size=None, seed=0):
+        """The exact number of crossing pairs of edges of the current layout under the engine's own float32 test on
+        coordinates 0 and 1 (an int); with `sample_size` the pair (estimate, standard_error) from that many sampled edges.
+        The positions are read on the device."""
+        from . import quality
+        if sample_size is None:
+            return quality.edge_crossings(self)
+        return quality.estimate_edge_crossings(self, sample_size=sample_size, seed=seed)
+
+    def layout_quality(self, **kw):
+        """quality.layout_quality of the current layout: crossings, edge-length statistics, L_min."""
+        from . import quality
+        return quality.layout_quality(self, **kw)
+
     def display_layout(self, edge_width=1, node_size=3, node_colors=None):
         """Plotly rendering is outside the accelerated path."""
         if self.n_components not in (2, 3):

@@ -687,6 +687,54 @@ gh_status gh_corr_matrix(gh_corr_handle h, double *out, int64_t *sums);
 gh_status gh_corr_bootstrap(gh_corr_handle h, int32_t n_pairs, const int32_t *pairs, int32_t reps, uint64_t seed,
                             double *out, int64_t *sums);
 
+/* ---- layout quality: edge crossings and edge lengths (graphem-rapids_amd/quality.py) -------------------------------
+ * The one measure of the loop's own product: how many pairs of edges of a layout cross, under the test the engine
+ * itself uses, as an exact integer.
+ *
+ * pos: (n, D) float32.  edges: (E, 2) int32, taken as given: ids are kept, nothing is merged or dropped, and an edge's
+ * index is its id.  Edges i != j CROSS iff D >= 2, they share no vertex (the four-way id comparison of gh_intersect_pair),
+ * and with a = pos[u_i], b = pos[v_i], c = pos[u_j], d = pos[v_j] on coordinates 0 and 1 only and
+ *     orient(p, q, r) = (q0 - p0) * (r1 - p1) - (q1 - p1) * (r0 - p0)
+ * (every operation a separate IEEE float32 operation, no contraction, gradual underflow)
+ *     orient(a, b, c) * orient(a, b, d) < 0   and   orient(c, d, a) * orient(c, d, b) < 0,     both products in float32.
+ * That is gh_orient2d and the test of csrc/intersect_core.h (reference pt.py:760-772) without its i < j filter.  The
+ * relation is symmetric in (i, j): the two products are exchanged.  Self-loops and duplicate edges never cross anything.
+ * Swapping an edge's endpoints changes the point the differences are taken from, so orient(b, a, c) is -orient(a, b, c)
+ * only up to rounding: counts of nearly collinear quadruples can depend on the direction an edge is stored in, exactly as
+ * the engine's own forces do.
+ *     counts[r] = the number of edges j in [0, E) that cross edge rows[r]
+ * and with all edges as rows the layout's crossing number is sum(counts) / 2.
+ * It is a float32 rule: the same formula in double gives other counts wherever the four points are nearly collinear,
+ * and two segments with disjoint bounding boxes can cross under it (csrc/quality.hip has a case), so every pair is tested.
+ *
+ * Edge lengths use all D coordinates: L_e = sqrt(sum_d ((double)x_u,d - (double)x_v,d)^2), the sum in order
+ * d = 0 .. D-1, in double, no contraction.
+ *
+ * Results depend only on (edges, positions, rows / pairs): not on launch geometry, nor on whether the device or the
+ * host path ran -- except the two length sums, whose order of summation is the path's own. */
+typedef struct gh_qual *gh_qual_handle;
+
+/* edges: host int32 (n_edges, 2).  device_id >= 0: kernels on that device; device_id < 0: the host path (no device is
+ * touched).  GH_ERR_INVALID for a vertex id outside [0, n) ("edge <i> has a vertex id outside [0, n)").  On failure
+ * *out = NULL and gh_qual_last_error(NULL) has the message. */
+gh_status gh_qual_create(gh_qual_handle *out, int device_id, int64_t n, int64_t n_edges, const int32_t *edges);
+void gh_qual_destroy(gh_qual_handle h);
+const char *gh_qual_last_error(gh_qual_handle h);
+/* Takes a snapshot of (n, D) float32 rows; ld >= D is the row stride in floats.  on_device = 0: pos is a host pointer.
+ * on_device = 1: pos is a device pointer on the handle's device (gh_positions_unpadded_device(engine) with ld = D, for
+ * one); it is copied on the handle's stream before the call returns, and the engine may go on afterwards.  Later
+ * queries see the snapshot until positions are set again.  GH_ERR_INVALID for D < 1, ld < D, on_device on a host-path
+ * handle.  D = 1 is valid: every count is 0. */
+gh_status gh_qual_set_positions(gh_qual_handle h, const float *pos, int32_t D, int64_t ld, int32_t on_device);
+/* rows: host int32, n_rows edge ids in any order and with repeats; NULL = all E edges in order (n_rows is ignored).
+ * counts: host int32, one per row.  sum (may be NULL): the sum of counts.  GH_ERR_INVALID for an id outside [0, E)
+ * and for a query before any positions were set.  Blocking. */
+gh_status gh_qual_crossings(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int32_t *counts, int64_t *sum);
+/* The test for explicit pairs: pairs host int32 (n_pairs, 2) of edge ids; cross[p] = 0 or 1.  Blocking. */
+gh_status gh_qual_pairs(gh_qual_handle h, int64_t n_pairs, const int32_t *pairs, uint8_t *cross);
+/* out = {min L, max L, sum L, sum L^2} over all edges; {+inf, -inf, 0, 0} for an empty edge list.  Blocking. */
+gh_status gh_qual_edge_lengths(gh_qual_handle h, double out[4]);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
