@@ -166,6 +166,16 @@ SIGNATURES = {
     "gh_qual_crossings": (_int, [vp, i64, vp, vp, _P(i64)]),
     "gh_qual_pairs": (_int, [vp, i64, vp, vp]),
     "gh_qual_edge_lengths": (_int, [vp, vp]),
+    "gh_ingest_create": (_int, [_P(vp), _int]),
+    "gh_ingest_destroy": (None, [vp]),
+    "gh_ingest_last_error": (_str, [vp]),
+    "gh_ingest_set_memory_budget": (_int, [vp, i64]),
+    "gh_ingest_parse": (_int, [vp, vp, i64, i32, i32, i32]),
+    "gh_ingest_parse_uploaded": (_int, [vp, vp, vp, i64, i32, i32, i32]),
+    "gh_ingest_counts": (_int, [vp, _P(i64), _P(i64), _P(i64)]),
+    "gh_ingest_chunking": (_int, [vp, _P(i64), _P(i64)]),
+    "gh_ingest_copy_vertices": (_int, [vp, vp]),
+    "gh_ingest_copy_edges": (_int, [vp, i32, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -834,4 +844,65 @@ class LayoutQuality(Handle):
         """float64 (min, max, sum, sum of squares) of the edge lengths (gh_qual_edge_lengths)."""
         out = np.zeros(4, dtype=np.float64)
         self._raise(self.lib.gh_qual_edge_lengths(self.handle, ptr(out)))
+        return out
+
+
+class EdgeListParser(BudgetHandle):
+    """Thin RAII wrapper over a gh_ingest_handle: the text of an edge list to (vertices, edges) under the rule of
+    include/graphem_hip.h "edge-list ingestion".  device_id < 0 is the library's host path, which touches no device and
+    returns the same arrays bit for bit.  Memory budget: device bytes of working state per chunk of text, 4 GiB by default,
+    at least MIN_BUDGET.  A handle can parse again; each parse replaces its result."""
+    _destroy, _last_error, _set_budget = "gh_ingest_destroy", "gh_ingest_last_error", "gh_ingest_set_memory_budget"
+    FORMATS = {"snap": 0, "edges": 1, "mtx": 2}
+    VERTICES_FROM = {"edges": 0, "rows": 1}
+    MIN_BUDGET = 4096
+
+    def __init__(self, device_id=0):
+        self.device_id = int(device_id)
+        self.rows = self.n_edges = self.n_vertices = 0
+        self._create("gh_ingest_create", self.device_id)
+
+    def _codes(self, fmt, vertices_from):
+        if fmt not in self.FORMATS:
+            raise ValueError(f"format must be one of {sorted(self.FORMATS)}, got {fmt!r}")
+        if vertices_from not in self.VERTICES_FROM:
+            raise ValueError(f"vertices_from must be 'edges' or 'rows', got {vertices_from!r}")
+        return self.FORMATS[fmt], self.VERTICES_FROM[vertices_from]
+
+    def _counts(self):
+        r, e, v = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self._raise(self.lib.gh_ingest_counts(self.handle, ctypes.byref(r), ctypes.byref(e), ctypes.byref(v)))
+        self.rows, self.n_edges, self.n_vertices = int(r.value), int(e.value), int(v.value)
+
+    def parse(self, data, fmt="snap", directed=False, vertices_from="edges"):
+        """Parses the bytes of a file (bytes, bytearray or a uint8 array); a malformed line is a ValueError naming it."""
+        f, vf = self._codes(fmt, vertices_from)
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._raise(self.lib.gh_ingest_parse(self.handle, ptr(buf) if buf.size else None, int(buf.size), f, int(bool(directed)), vf))
+        self._counts()
+
+    def parse_uploaded(self, data, dev_ptr, fmt="snap", directed=False, vertices_from="edges"):
+        """parse() for a text whose bytes are also on the handle's device already, 16-byte aligned at dev_ptr."""
+        f, vf = self._codes(fmt, vertices_from)
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._raise(self.lib.gh_ingest_parse_uploaded(self.handle, ptr(buf) if buf.size else None, ctypes.c_void_p(int(dev_ptr)),
+                                                      int(buf.size), f, int(bool(directed)), vf))
+        self._counts()
+
+    def chunking(self):
+        """(bytes of text per chunk under the current budget, chunks the last parse took -- 0 on the host path)."""
+        cb, ch = ctypes.c_int64(), ctypes.c_int64()
+        self._raise(self.lib.gh_ingest_chunking(self.handle, ctypes.byref(cb), ctypes.byref(ch)))
+        return int(cb.value), int(ch.value)
+
+    def vertices(self):
+        """int64 (n_vertices,): the sorted distinct labels."""
+        out = np.zeros(self.n_vertices, dtype=np.int64)
+        self._raise(self.lib.gh_ingest_copy_vertices(self.handle, ptr(out)))
+        return out
+
+    def edges(self, relabel=False):
+        """int64 (n_edges, 2): labels, or with relabel their ranks in vertices()."""
+        out = np.zeros((self.n_edges, 2), dtype=np.int64)
+        self._raise(self.lib.gh_ingest_copy_edges(self.handle, int(bool(relabel)), ptr(out)))
         return out
