@@ -72,6 +72,7 @@ SIGNATURES = {
     "gh_timing_get": (_int, [vp, i32, _P(_str), _P(f64), _P(i64)]),
     "gh_device_count": (i32, []),
     "gh_version": (_str, []),
+    "gh_debug_live_allocations": (None, [_P(i64), _P(i64)]),
     "gh_knn_last_counts": (_int, [vp, vp, vp, vp]),
     "gh_set_stream": (_int, [vp, vp, i32]),
     "gh_positions_rows_allocated": (i64, [vp]),
@@ -705,6 +706,13 @@ def selftest_arith(samples, seed=1, device_id=0):
 
 def device_count():
     return int(load().gh_device_count())
+
+
+def live_allocations():
+    """(count, bytes) of the device allocations the library's handles hold in this process (gh_debug_live_allocations)."""
+    count, nbytes = ctypes.c_int64(), ctypes.c_int64()
+    load().gh_debug_live_allocations(ctypes.byref(count), ctypes.byref(nbytes))
+    return count.value, nbytes.value
 
 
 class Generator(BudgetHandle):

@@ -52,25 +52,6 @@ static void resolve_timers(gh_engine *h) {
 }
 
 // ---- helpers -----------------------------------------------------------------------
-template <typename T>
-static gh_status dev_alloc(gh_engine *h, T **p, size_t count, bool zero) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-    if (e != hipSuccess) {
-        h->err = std::string("hipMalloc failed: ") + hipGetErrorString(e);
-        return GH_ERR_NOMEM;
-    }
-    if (zero) GH_HIP(hipMemsetAsync(*p, 0, count * sizeof(T), h->stream));
-    return GH_OK;
-}
-
-#define GH_TRY(x)                        \
-    do {                                 \
-        gh_status st_ = (x);             \
-        if (st_ != GH_OK) return st_;    \
-    } while (0)
-
 static gh_status check_handle(gh_engine *h) {
     if (!h) return GH_ERR_INVALID;
     hipError_t e = hipSetDevice(h->device);
@@ -86,21 +67,6 @@ static gh_status reject_f64(gh_engine *h, const char *what) {
     if (!h->f64) return GH_OK;
     h->err = std::string(what) + " is not available on a float64 engine";
     return GH_ERR_INVALID;
-}
-
-static void free_all(gh_engine *h) {
-    gh_f64_free(h);
-    gh_ivf_free(h);
-    const bool repointed = h->layout == GH_LAYOUT_GATHERED || h->layout == GH_LAYOUT_OVERLAP;   // d_new / d_stats: blocks of a layout's buffers
-    void *ptrs[] = {h->d_edges, h->d_rowptr, h->d_adj, h->d_pos, repointed ? (void *)h->d_new_own : (void *)h->d_new, h->d_gbuf, h->d_rows_all, h->d_rows_pk, h->d_stats_all, h->d_tmpF, h->d_tmpF2, h->d_io, h->d_acc,
-                    h->d_tflag, h->d_touched, h->d_tcount, h->d_sampled, h->d_q, h->d_qscan, h->d_qA, h->d_qexact, h->d_order, h->d_long_rows, h->d_long_ownptr, h->d_long_ownadj, h->d_long_eptr, h->d_long_erow, h->d_long_terms, h->d_own_long, h->d_cand, h->d_cnt,
-                    h->d_ovf, h->d_sel_redo, h->d_tq_count, h->d_tq_base, h->d_tq_touched, h->d_dbg_cnt, h->d_partial, h->d_merged, h->d_first_edge, h->d_own_eids, h->d_mid, h->d_Fs, h->d_gmin, h->d_sub_uv, h->d_stamps, h->d_tau_flag, h->d_wait_failed, h->d_qcell, h->d_qc_flag, h->d_grid_u32, h->d_grid_smid, h->d_grid_temp, h->d_rows_packed, h->d_rare, h->d_cd_rows, h->d_cd_vbuf, h->d_cd_cmin, h->d_cd_stat, h->d_vblock, h->d_blockstats, repointed ? (void *)h->d_stats_own : (void *)h->d_stats, h->d_iscratch, h->d_stream_ids};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->h_ring) (void)hipHostFree(h->h_ring);
-    for (hipEvent_t e : h->ring_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
 }
 
 // ---- lifetime ----------------------------------------------------------------------
@@ -153,7 +119,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     const bool hashed = h->part.edge_rule == GH_EDGES_HASHED;
     const size_t nLD = (size_t)n * h->LD, S = (size_t)h->S;
     gh_status st;
-#define GH_A(p, count, zero) GH_TRY(dev_alloc(h, &h->p, (count), (zero)))
+#define GH_A(p, count, zero) GH_TRY_ST(gh_alloc(h, h->p, (count), (zero)))
     GH_A(d_edges, (size_t)E * 2, false);
     GH_A(d_rowptr, (size_t)h->rows + 1, false);
     GH_A(d_adj, (size_t)h->adj_len, false);
@@ -176,7 +142,8 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     }
     GH_A(d_vblock, g.vblock.size(), false);
     GH_A(d_pos, (size_t)h->pos_rows * h->LD, true);
-    GH_A(d_new, (size_t)h->rows * h->LD, true);
+    GH_A(d_new_buf, (size_t)h->rows * h->LD, true);
+    h->d_new = h->d_new_buf.p;
     GH_A(d_tmpF, nLD, true);
     GH_A(d_tmpF2, nLD, true);
     GH_A(d_io, (size_t)n * D, false);
@@ -189,7 +156,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_qscan, S * (size_t)(h->LD + 4), true);
     GH_A(d_qA, S * 16, true);
     GH_A(d_qexact, S + 1, true);
-    if ((st = dev_alloc(h, &h->d_cand, scan_path ? S * GH_CAND_CAP : 1, false)) != GH_OK) {
+    if ((st = gh_alloc(h, h->d_cand, scan_path ? S * GH_CAND_CAP : 1, false)) != GH_OK) {
         h->err = "hipMalloc of the KNN candidate lists failed: sample_size = " + std::to_string(h->S) + " needs " +
                  std::to_string((S * GH_CAND_CAP * sizeof(uint64_t)) >> 20) + " MiB (128 KiB per sampled midpoint)";
         return st;
@@ -206,38 +173,39 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_iscratch, S * (size_t)h->k * h->LD, false);
     h->nblocks_update = (int)((h->rows + 255) / 256);
     GH_A(d_blockstats, (size_t)std::max(std::max(h->nblocks_update, h->n_vblocks), 1) * 2 * h->LD, true);
-    GH_A(d_stats, (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD, true);
-    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled};
+    GH_A(d_stats_buf, (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD, true);
+    h->d_stats = h->d_stats_buf.p;
+    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled.p};
     auto up = [&](void *dst, const void *src, size_t bytes) {
         return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
     };
     auto up32 = [&](void *dst, const std::vector<int32_t> &v) { return up(dst, v.data(), sizeof(int32_t) * v.size()); };
-    if (!up(h->d_edges, g.edges, sizeof(int32_t) * 2 * (size_t)E) || !up32(h->d_rowptr, g.rowptr) ||
-        !up(h->d_adj, g.adj.data(), sizeof(int32_t) * (size_t)h->adj_len) || !up32(h->d_first_edge, g.first_edge) ||
-        !up32(h->d_vblock, g.vblock) || (hashed && !up32(h->d_own_eids, g.own_eids)) ||
-        (h->nlong && (!up32(h->d_long_rows, g.long_rows) || !up32(h->d_long_ownptr, g.long_ownptr) ||
-                      !up32(h->d_long_eptr, g.long_eptr) || !up32(h->d_long_erow, g.long_erow) ||
-                      !up32(h->d_long_ownadj, g.long_ownadj) || !up(h->d_own_long, g.own_long.data(), g.own_long.size()))) ||
+    if (!up(h->d_edges.p, g.edges, sizeof(int32_t) * 2 * (size_t)E) || !up32(h->d_rowptr.p, g.rowptr) ||
+        !up(h->d_adj.p, g.adj.data(), sizeof(int32_t) * (size_t)h->adj_len) || !up32(h->d_first_edge.p, g.first_edge) ||
+        !up32(h->d_vblock.p, g.vblock) || (hashed && !up32(h->d_own_eids.p, g.own_eids)) ||
+        (h->nlong && (!up32(h->d_long_rows.p, g.long_rows) || !up32(h->d_long_ownptr.p, g.long_ownptr) ||
+                      !up32(h->d_long_eptr.p, g.long_eptr) || !up32(h->d_long_erow.p, g.long_erow) ||
+                      !up32(h->d_long_ownadj.p, g.long_ownadj) || !up(h->d_own_long.p, g.own_long.data(), g.own_long.size()))) ||
         hipStreamSynchronize(h->stream) != hipSuccess) {
         h->err = "upload of the graph failed";
         return GH_ERR_HIP;
     }
-    GH_TRY(gh_grid_alloc(h));
-    GH_TRY(gh_ivf_alloc(h));
-    GH_TRY(gh_cdist_alloc(h));
+    GH_TRY_ST(gh_grid_alloc(h));
+    GH_TRY_ST(gh_ivf_alloc(h));
+    GH_TRY_ST(gh_cdist_alloc(h));
     GH_A(d_tau_flag, 1, true);
     GH_A(d_wait_failed, 1, true);
     GH_A(d_qcell, GH_QC_WORDS, true);
     GH_A(d_qc_flag, 1, true);
     if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
 #undef GH_A
-    if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv.p, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
         h->err = "upload of the threshold subset failed";
         return GH_ERR_HIP;
     }
     if (!h->order_host.empty()) {
-        GH_TRY(dev_alloc(h, &h->d_order, (size_t)n, false));
-        if (hipMemcpy(h->d_order, h->order_host.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+        GH_TRY_ST(gh_alloc(h, h->d_order, (size_t)n, false));
+        if (hipMemcpy(h->d_order.p, h->order_host.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
             h->err = "upload of the vertex order failed";
             return GH_ERR_HIP;
         }
@@ -249,11 +217,12 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
                                const gh_params *params, const gh_partition *part) {
     if (!out) return GH_ERR_INVALID;
     *out = nullptr;
-    GH_TRY(gh_check_create_args(device_id, n, D, E, edges, params));
+    GH_TRY_ST(gh_check_create_args(device_id, n, D, E, edges, params));
     auto fail = [&](gh_status st, const std::string &msg) { g_create_error = msg; return st; };
-    gh_engine *h = new (std::nothrow) gh_engine();
+    std::unique_ptr<gh_engine> owner(new (std::nothrow) gh_engine());
+    gh_engine *h = owner.get();
     if (!h) return fail(GH_ERR_NOMEM, "out of host memory");
-    auto refuse = [&](const char *msg) { delete h; return fail(GH_ERR_INVALID, msg); };
+    auto refuse = [&](const char *msg) { return fail(GH_ERR_INVALID, msg); };
     h->device = device_id;
     h->n = n; h->E = E; h->D = D; h->LD = gh_ld(D);
     h->prm = *params;
@@ -275,9 +244,8 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
         return refuse("partition out of range");
     h->rows = h->part.row_hi - h->part.row_lo;
 
-    auto bail = [&](gh_status st) { g_create_error = h->err; free_all(h); delete h; return st; };
-    if (hipSetDevice(device_id) != hipSuccess) return bail(GH_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(GH_ERR_HIP); }
+    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_HIP, "");
+    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(GH_ERR_HIP, "hipStreamCreate failed");
     h->stream = h->own_stream;
     h->pos_rows = n + GH_POS_PAD_ROWS;
     const create_switches sw = read_switches();
@@ -296,9 +264,13 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     gh_choose_scan_filter(h);                 // (fused.hip) sets tau_embedded
 
     const gh_status st = allocate_and_upload(h, g, sw);
-    if (st != GH_OK) return bail(st);
-    *out = h;
+    if (st != GH_OK) return fail(st, h->err);
+    *out = owner.release();
     return GH_OK;
+}
+
+gh_engine::~gh_engine() {
+    if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 extern "C" void gh_destroy(gh_handle h) {
@@ -306,8 +278,6 @@ extern "C" void gh_destroy(gh_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     resolve_timers(h);
-    gh_comm_free(h);
-    free_all(h);
     delete h;
 }
 
@@ -315,19 +285,19 @@ extern "C" const char *gh_last_error(gh_handle h) { return h ? h->err.c_str() : 
 
 // ---- positions ---------------------------------------------------------------------
 extern "C" gh_status gh_set_positions(gh_handle h, const float *pos) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->f64) return pos ? gh_f64_set_positions_f32(h, pos) : GH_ERR_INVALID;
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
     gh_set_lookahead(h, nullptr);
-    GH_HIP(hipMemcpyAsync(h->d_io, pos, sizeof(float) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
-    GH_TRY(gh_launch_pad(h, h->d_io, h->d_pos));
+    GH_HIP(hipMemcpyAsync(h->d_io.p, pos, sizeof(float) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
+    GH_TRY_ST(gh_launch_pad(h, h->d_io.p, h->d_pos.p));
     GH_HIP(hipStreamSynchronize(h->stream));  // the host buffer may be released by the caller
     return GH_OK;
 }
 
 static gh_status download_padded(gh_engine *h, const float *d_src, float *host) {
-    GH_TRY(gh_launch_unpad(h, d_src, h->d_io));
-    GH_HIP(hipMemcpyAsync(host, h->d_io, sizeof(float) * (size_t)h->n * h->D, hipMemcpyDeviceToHost, h->stream));
+    GH_TRY_ST(gh_launch_unpad(h, d_src, h->d_io.p));
+    GH_HIP(hipMemcpyAsync(host, h->d_io.p, sizeof(float) * (size_t)h->n * h->D, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
@@ -335,14 +305,14 @@ static gh_status download_padded(gh_engine *h, const float *d_src, float *host) 
 // A workgroup of a fused launch gave up waiting for that launch's thresholds (tau_core.h): whatever was computed since
 // is not to be trusted.  Cannot happen while workgroups are started in index order; checked where the host synchronises.
 static gh_status check_device_waits(gh_engine *h) {
-    if (!(h->tau_embedded || h->qcells) || !h->d_wait_failed) return GH_OK;
+    if (!(h->tau_embedded || h->qcells) || !h->d_wait_failed.p) return GH_OK;
     int32_t failed = 0;
-    GH_HIP(hipMemcpyAsync(&failed, h->d_wait_failed, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(&failed, h->d_wait_failed.p, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     if (failed) {
         // reported once: the flag is cleared and the engine goes on with the thresholds as a launch of their own (no
         // workgroup waits for another any more)
-        GH_HIP(hipMemsetAsync(h->d_wait_failed, 0, sizeof(int32_t), h->stream));
+        GH_HIP(hipMemsetAsync(h->d_wait_failed.p, 0, sizeof(int32_t), h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
         if (h->qcells) {   // the wait was for the query-cell table (fused.hip): back to the split-f16 filter
             h->scan_filter = GH_FILTER_MFMA;
@@ -365,25 +335,25 @@ static gh_status check_device_waits(gh_engine *h) {
 }
 
 extern "C" gh_status gh_get_positions(gh_handle h, float *pos) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->f64) return pos ? gh_f64_get_positions_f32(h, pos) : GH_ERR_INVALID;
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
-    GH_TRY(check_device_waits(h));
-    return download_padded(h, h->d_pos, pos);
+    GH_TRY_ST(check_device_waits(h));
+    return download_padded(h, h->d_pos.p, pos);
 }
 
-extern "C" float *gh_positions_device(gh_handle h) { return h && !h->f64 ? h->d_pos : nullptr; }
+extern "C" float *gh_positions_device(gh_handle h) { return h && !h->f64 ? h->d_pos.p : nullptr; }
 extern "C" gh_status gh_vertex_order(gh_handle h, int32_t *order) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (!order) { h->err = "order is NULL"; return GH_ERR_INVALID; }
     for (int64_t i = 0; i < h->n; ++i) order[i] = h->order_host.empty() ? (int32_t)i : h->order_host[(size_t)i];
     return GH_OK;
 }
 extern "C" const float *gh_positions_unpadded_device(gh_handle h) {
     if (!h || h->f64 || hipSetDevice(h->device) != hipSuccess) return nullptr;
-    if (gh_launch_unpad(h, h->d_pos, h->d_io) != GH_OK) return nullptr;
+    if (gh_launch_unpad(h, h->d_pos.p, h->d_io.p) != GH_OK) return nullptr;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return nullptr;
-    return h->d_io;
+    return h->d_io.p;
 }
 extern "C" int32_t gh_row_stride(gh_handle h) { return h ? h->LD : 0; }
 
@@ -418,9 +388,9 @@ static gh_status caller_ids(gh_engine *h, const int32_t *host_ids, gh_ids *src) 
     // a set-up done ahead (inside the last normalise launch) left ITS ids in d_sampled and built the query
     // records from them: overwriting the ids makes it stale
     gh_set_lookahead(h, nullptr);
-    GH_HIP(hipMemcpyAsync(h->d_sampled, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_sampled.p, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
-    *src = gh_ids{GH_IDS_GIVEN, h->d_sampled};
+    *src = gh_ids{GH_IDS_GIVEN, h->d_sampled.p};
     return GH_OK;
 }
 
@@ -429,11 +399,11 @@ static gh_status caller_ids(gh_engine *h, const int32_t *host_ids, gh_ids *src) 
 static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect);
 static gh_status step_begin(gh_engine *h, bool fuse_intersect) {
     h->rows_early = false;
-    GH_TRY(step_begin_launches(h, fuse_intersect));
+    GH_TRY_ST(step_begin_launches(h, fuse_intersect));
     // form D: new0 = pos + Fs of the own rows is in their block -- written by the fused kernel, or (a rank too small for it;
     // every rank must send at the same point of the iteration) by a launch of its own -- and may travel now
     if (h->layout == GH_LAYOUT_OVERLAP) {
-        if (!h->new0_ready) GH_TRY(gh_launch_new0(h));
+        if (!h->new0_ready) GH_TRY_ST(gh_launch_new0(h));
         h->rows_early = true;
     }
     return GH_OK;
@@ -445,35 +415,35 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
     if (h->S == 0 || h->k == 0) {  // nothing sampled / no neighbours asked for: spring forces only
         h->sample.mode = GH_IDS_GIVEN;
         h->intersect_done = true;
-        GH_HIP(hipMemsetAsync(h->d_tcount, 0, sizeof(int32_t), h->stream));
+        GH_HIP(hipMemsetAsync(h->d_tcount.p, 0, sizeof(int32_t), h->stream));
         return gh_launch_spring_mid(h);
     }
     if (gh_grid_path(h)) {  // sub-quadratic search: thresholds, own midpoints to memory, grid build + cell search
-        GH_TRY(gh_knn_prepare(h));          // query records only: the thresholds come from the grid itself
-        GH_TRY(gh_launch_spring_mid(h));
-        GH_TRY(gh_grid_search(h));
+        GH_TRY_ST(gh_knn_prepare(h));          // query records only: the thresholds come from the grid itself
+        GH_TRY_ST(gh_launch_spring_mid(h));
+        GH_TRY_ST(gh_grid_search(h));
         return gh_knn_finish(h, true, fuse_intersect);
     }
     if (gh_ivf_path(h)) {   // inverted-file search (approximate: probed lists only; ivf.hip)
-        GH_TRY(gh_knn_prepare(h));          // query records only
-        GH_TRY(gh_launch_spring_mid(h));
-        GH_TRY(gh_ivf_search(h));
+        GH_TRY_ST(gh_knn_prepare(h));          // query records only
+        GH_TRY_ST(gh_launch_spring_mid(h));
+        GH_TRY_ST(gh_ivf_search(h));
         return gh_knn_finish(h, true, fuse_intersect);
     }
     if (h->fused_scan && gh_knn_scan_path(h)) {
-        GH_TRY(gh_knn_prepare(h));
-        if (!h->tau_embedded) GH_TRY(gh_knn_thresholds(h));   // else: the first workgroups of the fused launch (tau_core.h)
-        GH_TRY(gh_launch_spring_scan(h));
+        GH_TRY_ST(gh_knn_prepare(h));
+        if (!h->tau_embedded) GH_TRY_ST(gh_knn_thresholds(h));   // else: the first workgroups of the fused launch (tau_core.h)
+        GH_TRY_ST(gh_launch_spring_scan(h));
         return gh_knn_finish(h, false, fuse_intersect);
     }
-    GH_TRY(gh_launch_spring_mid(h));
+    GH_TRY_ST(gh_launch_spring_mid(h));
     return gh_knn_local(h, fuse_intersect);
 }
 
 static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world) {
-    GH_TRY(gh_knn_merge(h, gathered, world));
-    if (!h->intersect_done) GH_TRY(gh_launch_intersect(h));
-    GH_TRY(gh_launch_integrate(h));
+    GH_TRY_ST(gh_knn_merge(h, gathered, world));
+    if (!h->intersect_done) GH_TRY_ST(gh_launch_intersect(h));
+    GH_TRY_ST(gh_launch_integrate(h));
     return GH_OK;
 }
 
@@ -483,7 +453,7 @@ static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world) {
 static gh_status step_finish(gh_engine *h, const gh_ids *next) {
     const bool presetup = next && h->rows == h->n && h->layout != GH_LAYOUT_GATHERED && gh_knn_scan_path(h) &&
                           (h->fused_scan || gh_grid_path(h) || gh_ivf_path(h)) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
-    GH_TRY(gh_launch_normalise(h, true, presetup ? next : nullptr));  // also zeroes what the intersection phase touched
+    GH_TRY_ST(gh_launch_normalise(h, true, presetup ? next : nullptr));  // also zeroes what the intersection phase touched
     h->iter += 1;
     return GH_OK;
 }
@@ -496,36 +466,36 @@ static gh_status run_iterations(gh_engine *h, int32_t iters, bool draws_own, Src
     const gh_ids own = gh_own_ids(h);
     auto loop = [&]() -> gh_status {
         for (int32_t t = 0; t < iters; ++t) {
-            GH_TRY(before_row(t));
+            GH_TRY_ST(before_row(t));
             h->sample = src_of_row(t);
-            GH_TRY(step_begin(h, true));
-            GH_TRY(step_merge(h, h->d_partial, 1));
+            GH_TRY_ST(step_begin(h, true));
+            GH_TRY_ST(step_merge(h, h->d_partial.p, 1));
             const gh_ids next = t + 1 < iters ? src_of_row(t + 1) : own;
-            GH_TRY(step_finish(h, t + 1 < iters || draws_own ? &next : nullptr));
+            GH_TRY_ST(step_finish(h, t + 1 < iters || draws_own ? &next : nullptr));
         }
         return GH_OK;
     };
     const gh_status st = loop();
-    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled};   // (not a row of d_stream_ids, which a later run may replace)
+    h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled.p};  // (not a row of d_stream_ids, which a later run may replace)
     return st;
 }
 static gh_status nothing_before(int32_t) { return GH_OK; }
 
 extern "C" gh_status gh_step(gh_handle h, const int32_t *sampled) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->f64) return gh_f64_step(h, sampled);
-    GH_TRY(check_whole(h, "gh_step"));
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_whole(h, "gh_step"));
+    GH_TRY_ST(check_k(h));
     gh_ids src;
-    GH_TRY(caller_ids(h, sampled, &src));
+    GH_TRY_ST(caller_ids(h, sampled, &src));
     return run_iterations(h, 1, sampled == nullptr, [&](int32_t) { return src; }, nothing_before);
 }
 
 // d_stream_ids with room for `words` ids (a smaller buffer is released once the stream has drained).
 static gh_status ensure_stream_ids(gh_engine *h, size_t words) {
     if (words <= h->stream_ids_cap) return GH_OK;
-    if (h->d_stream_ids) { GH_HIP(hipStreamSynchronize(h->stream)); GH_HIP(hipFree(h->d_stream_ids)); h->d_stream_ids = nullptr; h->stream_ids_cap = 0; }
-    GH_TRY(dev_alloc(h, &h->d_stream_ids, words, false));
+    if (h->d_stream_ids.p) { GH_HIP(hipStreamSynchronize(h->stream)); h->d_stream_ids.reset(); h->stream_ids_cap = 0; }
+    GH_TRY_ST(gh_alloc(h, h->d_stream_ids, words, false));
     h->stream_ids_cap = words;
     return GH_OK;
 }
@@ -538,38 +508,38 @@ gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sa
     const size_t cnt = (size_t)iters * (size_t)h->S;
     for (size_t i = 0; i < cnt; ++i)
         if (sample_stream[i] < 0 || sample_stream[i] >= h->E) { h->err = "sampled edge id out of range"; return GH_ERR_INVALID; }
-    GH_TRY(ensure_stream_ids(h, cnt));
-    GH_HIP(hipMemcpyAsync(h->d_stream_ids, sample_stream, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, h->stream));
+    GH_TRY_ST(ensure_stream_ids(h, cnt));
+    GH_HIP(hipMemcpyAsync(h->d_stream_ids.p, sample_stream, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
-    *d_ids = h->d_stream_ids;
+    *d_ids = h->d_stream_ids.p;
     return GH_OK;
 }
 
 extern "C" gh_status gh_run(gh_handle h, int32_t iters, const int32_t *sample_stream) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->f64) return iters < 0 ? GH_ERR_INVALID : gh_f64_run(h, iters, sample_stream);
     if (iters < 0) { h->err = "negative iteration count"; return GH_ERR_INVALID; }
     if (iters == 0) return GH_OK;
-    GH_TRY(check_whole(h, "gh_run"));
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_whole(h, "gh_run"));
+    GH_TRY_ST(check_k(h));
     int32_t *d_ids = nullptr;
-    GH_TRY(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));
+    GH_TRY_ST(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));
     const gh_ids own = gh_own_ids(h);
     auto src = [&](int32_t t) { return d_ids ? gh_ids{GH_IDS_GIVEN, d_ids + (size_t)t * h->S} : own; };
     return run_iterations(h, iters, d_ids == nullptr, src, nothing_before);
 }
 
 extern "C" gh_status gh_set_cdist_replay(gh_handle h, int32_t all_ties) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_set_cdist_replay"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_set_cdist_replay"));
     if (!h->cdist) { h->err = "gh_set_cdist_replay: not a GH_DIST_CDIST engine"; return GH_ERR_INVALID; }
     h->cd_all_ties = all_ties != 0;
     return GH_OK;
 }
 
 extern "C" gh_status gh_set_scan_filter(gh_handle h, int32_t mode) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_set_scan_filter"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_set_scan_filter"));
     if (mode != GH_FILTER_AUTO && mode != GH_FILTER_MFMA && mode != GH_FILTER_CELLS) {
         h->err = "gh_set_scan_filter: mode must be GH_FILTER_AUTO, GH_FILTER_MFMA or GH_FILTER_CELLS";
         return GH_ERR_INVALID;
@@ -588,7 +558,7 @@ extern "C" gh_status gh_set_scan_filter(gh_handle h, int32_t mode) {
 }
 
 extern "C" gh_status gh_get_scan_filter(gh_handle h, int32_t *mode) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (!mode) { h->err = "mode is NULL"; return GH_ERR_INVALID; }
     *mode = h->f64 || !gh_fused_uses_mfma(h) || h->D > 3 ? GH_FILTER_AUTO : h->qcells ? GH_FILTER_CELLS : GH_FILTER_MFMA;
     return GH_OK;
@@ -639,7 +609,7 @@ extern "C" const char *gh_torch_randperm_isa(void) { return gh_mt_isa(); }
 #define GH_DEV_RING 128    /* rows of the device ring: a row is overwritten GH_DEV_RING - GH_RING_CHUNK - 1 iterations after its own at the earliest */
 #define GH_HOST_RING 256   /* rows the producer may be ahead of the uploads */
 extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *rng_state, int64_t state_bytes) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (iters < 0) { h->err = "negative iteration count"; return GH_ERR_INVALID; }
     if (!rng_state || state_bytes != GH_TORCH_RNG_STATE_BYTES) { h->err = "rng_state must be the 5056 bytes of torch.get_rng_state()"; return GH_ERR_INVALID; }
     if (iters == 0) return GH_OK;
@@ -651,23 +621,23 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
         std::vector<int32_t> ids((size_t)iters * S);
         std::vector<int64_t> scratch((size_t)gh_rp_scratch_words(h->S));
         for (int32_t t = 0; t < iters; ++t) gh_torch_randperm_prefix_one(&mt, h->E, h->S, ids.data() + (size_t)t * S, scratch.data());
-        GH_TRY(gh_f64_run(h, iters, ids.data()));
+        GH_TRY_ST(gh_f64_run(h, iters, ids.data()));
         gh_mt_store(&mt, rng_state);
         return GH_OK;
     }
-    GH_TRY(check_whole(h, "gh_run_torch_sampled"));
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_whole(h, "gh_run_torch_sampled"));
+    GH_TRY_ST(check_k(h));
     const size_t ring_words = (size_t)GH_RING_SLOTS * GH_RING_CHUNK * S;
-    if (h->ring_cap < ring_words) {
+    if (h->ring.cap < ring_words) {
         GH_HIP(hipStreamSynchronize(h->stream));
-        if (h->h_ring) { (void)hipHostFree(h->h_ring); h->h_ring = nullptr; h->ring_cap = 0; }
-        GH_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->h_ring), ring_words * sizeof(int32_t), hipHostMallocDefault));
-        h->ring_cap = ring_words;
-        h->ring_uploads = 0;   // (no copy out of the old slots is pending: the stream has drained)
-        for (hipEvent_t &e : h->ring_ev)
+        if (h->ring.host) { (void)hipHostFree(h->ring.host); h->ring.host = nullptr; h->ring.cap = 0; }
+        GH_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->ring.host), ring_words * sizeof(int32_t), hipHostMallocDefault));
+        h->ring.cap = ring_words;
+        h->ring.uploads = 0;   // (no copy out of the old slots is pending: the stream has drained)
+        for (hipEvent_t &e : h->ring.ev)
             if (!e) GH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    GH_TRY(ensure_stream_ids(h, (size_t)GH_DEV_RING * S));
+    GH_TRY_ST(ensure_stream_ids(h, (size_t)GH_DEV_RING * S));
 
     std::vector<int32_t> hbuf((size_t)GH_HOST_RING * S);
     std::mutex mu;
@@ -714,18 +684,18 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
             m = std::min<int32_t>(m, GH_DEV_RING - uploaded % GH_DEV_RING);     // neither ring wraps inside one copy
             m = std::min<int32_t>(m, GH_HOST_RING - uploaded % GH_HOST_RING);
             // a slot is reused once its last copy has run -- also one enqueued by an earlier call, which returns undrained
-            const int slot = (int)(h->ring_uploads % GH_RING_SLOTS);
-            if (h->ring_uploads >= GH_RING_SLOTS) {
+            const int slot = (int)(h->ring.uploads % GH_RING_SLOTS);
+            if (h->ring.uploads >= GH_RING_SLOTS) {
                 const clk::time_point t0 = clk::now();
-                GH_HIP(hipEventSynchronize(h->ring_ev[slot]));
+                GH_HIP(hipEventSynchronize(h->ring.ev[slot]));
                 slot_wait_ms += ms_since(t0);
             }
-            int32_t *pin = h->h_ring + (size_t)slot * GH_RING_CHUNK * S;
+            int32_t *pin = h->ring.host + (size_t)slot * GH_RING_CHUNK * S;
             memcpy(pin, hbuf.data() + (size_t)(uploaded % GH_HOST_RING) * S, sizeof(int32_t) * (size_t)m * S);
-            GH_HIP(hipMemcpyAsync(h->d_stream_ids + (size_t)(uploaded % GH_DEV_RING) * S, pin, sizeof(int32_t) * (size_t)m * S, hipMemcpyHostToDevice, h->stream));
-            GH_HIP(hipEventRecord(h->ring_ev[slot], h->stream));
+            GH_HIP(hipMemcpyAsync(h->d_stream_ids.p + (size_t)(uploaded % GH_DEV_RING) * S, pin, sizeof(int32_t) * (size_t)m * S, hipMemcpyHostToDevice, h->stream));
+            GH_HIP(hipEventRecord(h->ring.ev[slot], h->stream));
             uploaded += m;
-            ++h->ring_uploads;
+            ++h->ring.uploads;
             {
                 std::lock_guard<std::mutex> lk(mu);
                 taken = uploaded;
@@ -734,7 +704,7 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
         }
         return GH_OK;
     };
-    auto row = [&](int32_t t) { return gh_ids{GH_IDS_GIVEN, h->d_stream_ids + (size_t)(t % GH_DEV_RING) * S}; };
+    auto row = [&](int32_t t) { return gh_ids{GH_IDS_GIVEN, h->d_stream_ids.p + (size_t)(t % GH_DEV_RING) * S}; };
     // this iteration's ids, and the next one's for its normalise launch
     auto upload = [&](int32_t t) { return upload_through(std::min(t + 1, iters - 1)); };
     const gh_status st = run_iterations(h, iters, false, row, upload);
@@ -751,14 +721,14 @@ extern "C" gh_status gh_run_torch_sampled(gh_handle h, int32_t iters, uint8_t *r
 }
 
 extern "C" gh_status gh_sampler_stats(gh_handle h, double *out4) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (!out4) { h->err = "out4 is NULL"; return GH_ERR_INVALID; }
     for (int i = 0; i < 4; ++i) out4[i] = h->sampler_stats[i];
     return GH_OK;
 }
 
 extern "C" gh_status gh_sync(gh_handle h) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     GH_HIP(hipStreamSynchronize(h->stream));
     resolve_timers(h);
     return check_device_waits(h);
@@ -766,44 +736,44 @@ extern "C" gh_status gh_sync(gh_handle h) {
 
 // ---- multi-GPU split step ----------------------------------------------------------
 extern "C" gh_status gh_step_begin(gh_handle h, const int32_t *sampled) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_step_begin"));
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_step_begin"));
+    GH_TRY_ST(check_k(h));
     h->last_step_own_ids = sampled == nullptr;
-    GH_TRY(caller_ids(h, sampled, &h->sample));
+    GH_TRY_ST(caller_ids(h, sampled, &h->sample));
     return step_begin(h, false);
 }
 // Part 1 of a split step with the ids already on the device (a row of an uploaded stream), or nullptr: the
 // engine draws them itself, identically on every rank (comm.hip gh_run_partitioned).
 gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids) {
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_k(h));
     h->last_step_own_ids = dev_ids == nullptr;
     h->sample = dev_ids ? gh_ids{GH_IDS_GIVEN, dev_ids} : gh_own_ids(h);   // (gh_upload_sample_stream gives none when S >= E)
     return step_begin(h, false);
 }
 extern "C" gh_status gh_set_stream(gh_handle h, void *hip_stream, int32_t use_own) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_set_stream"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_set_stream"));
     GH_HIP(hipStreamSynchronize(h->stream));
     resolve_timers(h);
     h->stream = use_own ? h->own_stream : reinterpret_cast<hipStream_t>(hip_stream);
     return GH_OK;
 }
 extern "C" int64_t gh_positions_rows_allocated(gh_handle h) { return h ? h->pos_rows : 0; }
-extern "C" uint64_t *gh_knn_partial_device(gh_handle h) { return h ? h->d_partial : nullptr; }
+extern "C" uint64_t *gh_knn_partial_device(gh_handle h) { return h ? h->d_partial.p : nullptr; }
 extern "C" const uint64_t *gh_knn_merged_device(gh_handle h) { return h ? h->d_keys_cur : nullptr; }
 extern "C" int32_t gh_knn_partial_cols(gh_handle h) { return h ? h->K + (h->cd_part ? 2 : 0) : 0; }
 extern "C" gh_status gh_step_merge(gh_handle h, const uint64_t *gathered, int32_t world) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_step_merge"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_step_merge"));
     if (!gathered || world < 1) { h->err = "bad gathered buffer / world size"; return GH_ERR_INVALID; }
     return step_merge(h, gathered, world);
 }
 extern "C" double *gh_stats_partial_device(gh_handle h) { return h ? h->d_stats : nullptr; }
 extern "C" int32_t gh_stats_rows(gh_handle h) { return h ? 2 + 2 * gh_fix_blocks(h->LD) : 0; }
 extern "C" gh_status gh_step_finish(gh_handle h) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_step_finish"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_step_finish"));
     return step_finish(h, nullptr);
 }
 
@@ -811,8 +781,8 @@ extern "C" gh_status gh_step_finish(gh_handle h) {
 // the engine's row partition, the blocks within d_pos if within_pos; no layout set yet.
 static gh_status check_layout(gh_engine *h, const char *name, const char *what, int32_t world, int32_t rank, int64_t chunk,
                               bool within_pos = false) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, name));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, name));
     if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n || (within_pos && chunk * world > h->pos_rows) ||
         h->part.row_lo != std::min<int64_t>(h->n, rank * chunk) || h->part.row_hi != std::min<int64_t>(h->n, (rank + 1) * chunk)) {
         h->err = std::string(what) + " does not match the engine's row partition";
@@ -823,24 +793,22 @@ static gh_status check_layout(gh_engine *h, const char *name, const char *what, 
 }
 
 extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY(check_layout(h, "gh_gather_layout", "gather layout", world, rank, chunk));
+    GH_TRY_ST(check_layout(h, "gh_gather_layout", "gather layout", world, rank, chunk));
     const int64_t stats_bytes = (int64_t)sizeof(double) * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
     const int64_t slot = (chunk * h->LD * (int64_t)sizeof(float) + stats_bytes + 15) / 16 * 16;
     GH_HIP(hipStreamSynchronize(h->stream));
-    GH_TRY(dev_alloc(h, &h->d_gbuf, (size_t)(slot * world), true));
-    h->d_new_own = h->d_new;
-    h->d_stats_own = h->d_stats;
-    h->d_new = reinterpret_cast<float *>(h->d_gbuf + rank * slot);
-    h->d_stats = reinterpret_cast<double *>(h->d_gbuf + rank * slot + chunk * h->LD * (int64_t)sizeof(float));
+    GH_TRY_ST(gh_alloc(h, h->d_gbuf, (size_t)(slot * world), true));
+    h->d_new = reinterpret_cast<float *>(h->d_gbuf.p + rank * slot);
+    h->d_stats = reinterpret_cast<double *>(h->d_gbuf.p + rank * slot + chunk * h->LD * (int64_t)sizeof(float));
     h->g_slot = slot; h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
     h->layout = GH_LAYOUT_GATHERED;
     return GH_OK;
 }
 extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY(check_layout(h, "gh_rank_layout", "rank layout", world, rank, chunk, true));
+    GH_TRY_ST(check_layout(h, "gh_rank_layout", "rank layout", world, rank, chunk, true));
     // fewer components than the row stride (3 of 4, 5..7 of 8, 9..15 of 16): the finished blocks travel unpadded
     if (h->D < h->LD && world > 1) {
-        GH_TRY(dev_alloc(h, &h->d_rows_packed, (size_t)world * chunk * h->D, true));
+        GH_TRY_ST(gh_alloc(h, h->d_rows_packed, (size_t)world * chunk * h->D, true));
         h->packed_exchange = h->n >= ((int64_t)1 << 21);
     }
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
@@ -850,7 +818,7 @@ extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, in
 // Form D: form B's finish (every rank normalises all n rows from the gathered un-normalised rows) with the big collective
 // moved to the front of the KNN tail -- see include/graphem_hip.h.
 extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY(check_layout(h, "gh_overlap_layout", "overlap layout", world, rank, chunk));
+    GH_TRY_ST(check_layout(h, "gh_overlap_layout", "overlap layout", world, rank, chunk));
     if (h->LD > 16) { h->err = "gh_overlap_layout: up to 16 components (use gh_rank_layout / gh_gather_layout beyond)"; return GH_ERR_INVALID; }
     const size_t R = (size_t)(2 + 2 * gh_fix_blocks(h->LD));
     // a rank's block of the late all-gather: statistics rows, 16 bytes for the patch count, the patch records
@@ -858,120 +826,116 @@ extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank,
     h->stats_block = (int64_t)(R * h->LD) + 2 + ((int64_t)h->patch_cap * (1 + h->LD) * 4 + 7) / 8;
     h->stats_block = (h->stats_block + 1) / 2 * 2;   // 16-byte multiples
     GH_HIP(hipStreamSynchronize(h->stream));
-    GH_TRY(dev_alloc(h, &h->d_rows_all, (size_t)world * chunk * h->LD, true));
-    GH_TRY(dev_alloc(h, &h->d_stats_all, (size_t)world * (size_t)h->stats_block, true));
-    if (h->D < h->LD && world > 1) GH_TRY(dev_alloc(h, &h->d_rows_pk, (size_t)world * chunk * h->D, true));
+    GH_TRY_ST(gh_alloc(h, h->d_rows_all, (size_t)world * chunk * h->LD, true));
+    GH_TRY_ST(gh_alloc(h, h->d_stats_all, (size_t)world * (size_t)h->stats_block, true));
+    if (h->D < h->LD && world > 1) GH_TRY_ST(gh_alloc(h, h->d_rows_pk, (size_t)world * chunk * h->D, true));
     GH_HIP(hipStreamSynchronize(h->stream));
-    h->d_new_own = h->d_new;
-    h->d_stats_own = h->d_stats;
-    h->d_new = h->d_rows_all + (size_t)rank * chunk * h->LD;
-    h->d_stats = h->d_stats_all + (size_t)rank * (size_t)h->stats_block;
+    h->d_new = h->d_rows_all.p + (size_t)rank * chunk * h->LD;
+    h->d_stats = h->d_stats_all.p + (size_t)rank * (size_t)h->stats_block;
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
     h->layout = GH_LAYOUT_OVERLAP;
     return GH_OK;
 }
-extern "C" float *gh_rows_all_device(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? nullptr : h->d_rows_pk ? h->d_rows_pk : h->d_rows_all; }
-extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? 0 : h->d_rows_pk ? h->D : h->LD; }
-extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->d_stats_all : nullptr; }
+extern "C" float *gh_rows_all_device(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? nullptr : h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p; }
+extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? 0 : h->d_rows_pk.p ? h->D : h->LD; }
+extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->d_stats_all.p : nullptr; }
 extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->stats_block : 0; }
 extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP && h->rows_early ? 1 : 0; }
 extern "C" gh_status gh_step_pack_rows(gh_handle h, void *hip_stream, int32_t use_engine_stream) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
     return gh_launch_pack_rows(h, use_engine_stream ? h->stream : reinterpret_cast<hipStream_t>(hip_stream));
 }
 extern "C" gh_status gh_step_finish_overlap(gh_handle h) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
-    GH_TRY(gh_launch_patch_rows(h));
+    GH_TRY_ST(gh_launch_patch_rows(h));
     const gh_ids own = gh_own_ids(h);
     // (the patch launch has zeroed the accumulators of a step whose rows went early)
-    GH_TRY(gh_launch_normalise(h, !h->rows_early, h->last_step_own_ids ? &own : nullptr, true));
+    GH_TRY_ST(gh_launch_normalise(h, !h->rows_early, h->last_step_own_ids ? &own : nullptr, true));
     h->rows_early = false;
     h->iter += 1;
     return GH_OK;
 }
 
 extern "C" gh_status gh_set_packed_rows(gh_handle h, int32_t on) {
-    GH_TRY(check_handle(h));
-    if (on && !h->d_rows_packed) { h->err = "no packed block exchange for this engine (needs gh_rank_layout with world > 1 and fewer components than the row stride)"; return GH_ERR_INVALID; }
+    GH_TRY_ST(check_handle(h));
+    if (on && !h->d_rows_packed.p) { h->err = "no packed block exchange for this engine (needs gh_rank_layout with world > 1 and fewer components than the row stride)"; return GH_ERR_INVALID; }
     h->packed_exchange = on != 0;
     return GH_OK;
 }
-extern "C" float *gh_rows_packed_device(gh_handle h) { return h && h->packed_exchange ? h->d_rows_packed : nullptr; }
+extern "C" float *gh_rows_packed_device(gh_handle h) { return h && h->packed_exchange ? h->d_rows_packed.p : nullptr; }
 extern "C" gh_status gh_step_unpack_rows(gh_handle h) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
     if (!h->packed_exchange) { h->err = "the packed block exchange is not in use (gh_set_packed_rows)"; return GH_ERR_INVALID; }
     return gh_launch_unpack_rows(h);
 }
 extern "C" gh_status gh_step_finish_own(gh_handle h, const double *stats_all, int32_t world) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
     if (!stats_all || world != h->g_world) { h->err = "bad statistics buffer / world size"; return GH_ERR_INVALID; }
-    GH_TRY(gh_launch_normalise(h, true, nullptr, false, stats_all));
+    GH_TRY_ST(gh_launch_normalise(h, true, nullptr, false, stats_all));
     h->iter += 1;
     return GH_OK;
 }
-extern "C" void *gh_gather_buffer_device(gh_handle h) { return h ? h->d_gbuf : nullptr; }
+extern "C" void *gh_gather_buffer_device(gh_handle h) { return h ? h->d_gbuf.p : nullptr; }
 extern "C" int64_t gh_gather_slot_bytes(gh_handle h) { return h ? h->g_slot : 0; }
 extern "C" gh_status gh_step_finish_gathered(gh_handle h) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_GATHERED) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
     // a rank that drew this step's ids on the device will do so again: prepare them in the same launch
     const gh_ids own = gh_own_ids(h);
-    GH_TRY(gh_launch_normalise(h, true, h->last_step_own_ids ? &own : nullptr, true));
+    GH_TRY_ST(gh_launch_normalise(h, true, h->last_step_own_ids ? &own : nullptr, true));
     h->iter += 1;
     return GH_OK;
 }
 
 extern "C" gh_status gh_radial_topk(gh_handle h, int32_t k, int32_t *ids) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_radial_topk"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_radial_topk"));
     if (!ids) { h->err = "ids is NULL"; return GH_ERR_INVALID; }
     if (k < 1 || k > 64 || k > h->n) { h->err = "gh_radial_topk: k must be in [1, min(n, 64)]"; return GH_ERR_INVALID; }
     int nparts = (int)((h->n + 2047) / 2048);
     if (nparts > 256) nparts = 256;
-    uint64_t *d_part = nullptr;
-    int32_t *d_ids = nullptr;
-    GH_TRY(dev_alloc(h, &d_part, (size_t)nparts * k, false));
-    gh_status st = dev_alloc(h, &d_ids, (size_t)k, false);
-    if (st == GH_OK) st = gh_radial_topk_device(h, k, d_part, nparts, d_ids);
-    if (st == GH_OK && hipMemcpyAsync(ids, d_ids, sizeof(int32_t) * k, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+    gh_dev<uint64_t> d_part;
+    gh_dev<int32_t> d_ids;
+    GH_TRY_ST(gh_alloc(h, d_part, (size_t)nparts * k, false));
+    gh_status st = gh_alloc(h, d_ids, (size_t)k, false);
+    if (st == GH_OK) st = gh_radial_topk_device(h, k, d_part.p, nparts, d_ids.p);
+    if (st == GH_OK && hipMemcpyAsync(ids, d_ids.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
         h->err = "gh_radial_topk: copy failed";
         st = GH_ERR_HIP;
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess && st == GH_OK) { h->err = "gh_radial_topk: sync failed"; st = GH_ERR_HIP; }
-    (void)hipFree(d_part);
-    (void)hipFree(d_ids);
-    return st;
+    return st;   // (the stream has drained: the temporaries may go)
 }
 
 // ---- per-phase entry points --------------------------------------------------------
 
 extern "C" gh_status gh_spring_forces(gh_handle h, float *F) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_spring_forces (use gh_spring_forces_f64)"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_spring_forces (use gh_spring_forces_f64)"));
     if (!F) { h->err = "F is NULL"; return GH_ERR_INVALID; }
-    GH_TRY(gh_launch_spring_only(h, h->d_tmpF));
-    return download_padded(h, h->d_tmpF, F);
+    GH_TRY_ST(gh_launch_spring_only(h, h->d_tmpF.p));
+    return download_padded(h, h->d_tmpF.p, F);
 }
 
 extern "C" gh_status gh_knn_midpoints(gh_handle h, const int32_t *sampled, int32_t *knn) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     if (h->f64) return knn ? gh_f64_knn_midpoints(h, sampled, knn) : GH_ERR_INVALID;
     if (!knn) { h->err = "knn is NULL"; return GH_ERR_INVALID; }
-    GH_TRY(check_whole(h, "gh_knn_midpoints"));
-    GH_TRY(check_k(h));
+    GH_TRY_ST(check_whole(h, "gh_knn_midpoints"));
+    GH_TRY_ST(check_k(h));
     if (!sampled && h->S < h->E) { h->err = "sampled is NULL"; return GH_ERR_INVALID; }
-    GH_TRY(caller_ids(h, sampled, &h->sample));
-    GH_TRY(step_begin(h, false));  // the same kernels a step runs (spring forces are a by-product)
-    const uint64_t *d_keys = h->d_partial;
+    GH_TRY_ST(caller_ids(h, sampled, &h->sample));
+    GH_TRY_ST(step_begin(h, false));  // the same kernels a step runs (spring forces are a by-product)
+    const uint64_t *d_keys = h->d_partial.p;
     if (h->cd_part) {   // a GH_DIST_CDIST engine created with a (whole-graph) partition: its rows are decided at the merge
         h->intersect_done = true;   // (no intersection phase here)
-        GH_TRY(gh_knn_merge(h, h->d_partial, 1));
+        GH_TRY_ST(gh_knn_merge(h, h->d_partial.p, 1));
         h->intersect_done = false;
-        d_keys = h->d_merged;
+        d_keys = h->d_merged.p;
     }
     std::vector<uint64_t> keys((size_t)h->S * h->K);
     GH_HIP(hipMemcpyAsync(keys.data(), d_keys, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost, h->stream));
@@ -982,58 +946,58 @@ extern "C" gh_status gh_knn_midpoints(gh_handle h, const int32_t *sampled, int32
 }
 
 extern "C" gh_status gh_intersection_forces(gh_handle h, const int32_t *sampled, const int32_t *knn, float *F) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_intersection_forces (use gh_intersection_forces_f64)"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_intersection_forces (use gh_intersection_forces_f64)"));
     if (!knn || !F) { h->err = "NULL argument"; return GH_ERR_INVALID; }
-    GH_TRY(check_whole(h, "gh_intersection_forces"));
+    GH_TRY_ST(check_whole(h, "gh_intersection_forces"));
     if (!sampled && h->S < h->E) { h->err = "sampled is NULL"; return GH_ERR_INVALID; }
     for (int64_t i = 0; i < h->S * h->k; ++i)
         if (knn[i] < 0 || knn[i] >= h->E) { h->err = "neighbour edge id out of range"; return GH_ERR_INVALID; }
-    GH_TRY(caller_ids(h, sampled, &h->sample));
-    GH_TRY(gh_ensure_sample(h));
+    GH_TRY_ST(caller_ids(h, sampled, &h->sample));
+    GH_TRY_ST(gh_ensure_sample(h));
     std::vector<uint64_t> keys((size_t)h->S * h->K, 0);  // the kernel reads ids from key columns 1..k
     for (int64_t s = 0; s < h->S; ++s)
         for (int c = 1; c < h->K; ++c) keys[(size_t)s * h->K + c] = (uint32_t)knn[s * h->k + (c - 1)];
-    GH_HIP(hipMemcpyAsync(h->d_merged, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_merged.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
-    h->d_keys_cur = h->d_merged;
-    GH_TRY(gh_launch_intersect(h));
-    GH_TRY(gh_launch_inter_to_dense(h, h->d_tmpF));
-    GH_TRY(gh_launch_inter_cleanup(h));
-    return download_padded(h, h->d_tmpF, F);
+    h->d_keys_cur = h->d_merged.p;
+    GH_TRY_ST(gh_launch_intersect(h));
+    GH_TRY_ST(gh_launch_inter_to_dense(h, h->d_tmpF.p));
+    GH_TRY_ST(gh_launch_inter_cleanup(h));
+    return download_padded(h, h->d_tmpF.p, F);
 }
 
 extern "C" gh_status gh_integrate_normalise(gh_handle h, const float *Fs, const float *Fi, float *out) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_integrate_normalise"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_integrate_normalise"));
     if (!Fs || !Fi || !out) { h->err = "NULL argument"; return GH_ERR_INVALID; }
-    GH_TRY(check_whole(h, "gh_integrate_normalise"));
+    GH_TRY_ST(check_whole(h, "gh_integrate_normalise"));
     const size_t bytes = sizeof(float) * (size_t)h->n * h->D;
-    GH_HIP(hipMemcpyAsync(h->d_io, Fs, bytes, hipMemcpyHostToDevice, h->stream));
-    GH_TRY(gh_launch_pad(h, h->d_io, h->d_tmpF));
+    GH_HIP(hipMemcpyAsync(h->d_io.p, Fs, bytes, hipMemcpyHostToDevice, h->stream));
+    GH_TRY_ST(gh_launch_pad(h, h->d_io.p, h->d_tmpF.p));
     GH_HIP(hipStreamSynchronize(h->stream));
-    GH_HIP(hipMemcpyAsync(h->d_io, Fi, bytes, hipMemcpyHostToDevice, h->stream));
-    GH_TRY(gh_launch_pad(h, h->d_io, h->d_tmpF2));
+    GH_HIP(hipMemcpyAsync(h->d_io.p, Fi, bytes, hipMemcpyHostToDevice, h->stream));
+    GH_TRY_ST(gh_launch_pad(h, h->d_io.p, h->d_tmpF2.p));
     GH_HIP(hipStreamSynchronize(h->stream));
-    GH_TRY(gh_launch_integrate_given(h, h->d_tmpF, h->d_tmpF2));
+    GH_TRY_ST(gh_launch_integrate_given(h, h->d_tmpF.p, h->d_tmpF2.p));
     // normalise into scratch so the current positions stay unchanged
-    GH_HIP(hipMemcpyAsync(h->d_tmpF, h->d_pos, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
-    GH_TRY(gh_launch_normalise(h, false));
-    GH_TRY(gh_launch_unpad(h, h->d_pos, h->d_io));
-    GH_HIP(hipMemcpyAsync(out, h->d_io, bytes, hipMemcpyDeviceToHost, h->stream));
-    GH_HIP(hipMemcpyAsync(h->d_pos, h->d_tmpF, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_tmpF.p, h->d_pos.p, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
+    GH_TRY_ST(gh_launch_normalise(h, false));
+    GH_TRY_ST(gh_launch_unpad(h, h->d_pos.p, h->d_io.p));
+    GH_HIP(hipMemcpyAsync(out, h->d_io.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_pos.p, h->d_tmpF.p, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
 // ---- instrumentation ---------------------------------------------------------------
 extern "C" gh_status gh_timing_enable(gh_handle h, int32_t on) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     h->timing = on != 0;
     return GH_OK;
 }
 extern "C" gh_status gh_timing_reset(gh_handle h) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     GH_HIP(hipStreamSynchronize(h->stream));
     resolve_timers(h);
     h->timers.clear();
@@ -1060,30 +1024,30 @@ extern "C" gh_status gh_timing_get(gh_handle h, int32_t i, const char **name, do
 // after those n_vblocks records, GH_STAMP_EXTRA records of the last normalise launch's first workgroups (set-up
 // workgroups first): start, mean / std known, [tile staged], end, -, -, 1 = set-up / 2 = normalising.
 extern "C" gh_status gh_debug_stamps(gh_handle h, unsigned long long *out, int64_t count) {
-    GH_TRY(check_handle(h));
-    if (!h->d_stamps) { h->err = "GRAPHEM_HIP_STAMPS was not set when the engine was created"; return GH_ERR_INVALID; }
+    GH_TRY_ST(check_handle(h));
+    if (!h->d_stamps.p) { h->err = "GRAPHEM_HIP_STAMPS was not set when the engine was created"; return GH_ERR_INVALID; }
     const int64_t have = ((int64_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8;
     GH_HIP(hipStreamSynchronize(h->stream));
-    GH_HIP(hipMemcpy(out, h->d_stamps, sizeof(unsigned long long) * (size_t)std::min(count, have), hipMemcpyDeviceToHost));
+    GH_HIP(hipMemcpy(out, h->d_stamps.p, sizeof(unsigned long long) * (size_t)std::min(count, have), hipMemcpyDeviceToHost));
     return GH_OK;
 }
 
 extern "C" gh_status gh_knn_last_counts(gh_handle h, int32_t *subset_counts, int32_t *final_counts, int32_t *overflow) {
-    GH_TRY(check_handle(h));
-    GH_TRY(reject_f64(h, "gh_knn_last_counts"));
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_knn_last_counts"));
     const size_t bytes = sizeof(int32_t) * (size_t)h->S;
-    if (subset_counts) GH_HIP(hipMemcpyAsync(subset_counts, h->d_dbg_cnt, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (final_counts) GH_HIP(hipMemcpyAsync(final_counts, h->d_dbg_cnt + h->S, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (overflow) GH_HIP(hipMemcpyAsync(overflow, h->d_ovf, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (subset_counts) GH_HIP(hipMemcpyAsync(subset_counts, h->d_dbg_cnt.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (final_counts) GH_HIP(hipMemcpyAsync(final_counts, h->d_dbg_cnt.p + h->S, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (overflow) GH_HIP(hipMemcpyAsync(overflow, h->d_ovf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 
 extern "C" gh_status gh_knn_cdist_stats(gh_handle h, int32_t *full_pass_rows, int32_t *unresolved_tie_rows) {
-    GH_TRY(check_handle(h));
+    GH_TRY_ST(check_handle(h));
     int32_t rare = 0, stat = 0;
-    if (h->cdist && h->d_rare) {
-        const int32_t *hdr = h->d_cd_stat + 4 * (h->cd_set ^ 1);   // the counters of the last search
+    if (h->cdist && h->d_rare.p) {
+        const int32_t *hdr = h->d_cd_stat.p + 4 * (h->cd_set ^ 1);  // the counters of the last search
         GH_HIP(hipMemcpyAsync(&rare, hdr, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         GH_HIP(hipMemcpyAsync(&stat, hdr + 1, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
@@ -1102,29 +1066,22 @@ extern "C" gh_status gh_knn_points(int device_id, const float *q, int64_t nq, co
     if (k > GH_SEL_BUF - GH_SEL_CHUNK) return fail(GH_ERR_INVALID, "k too large for the HIP backend (max 2048)");
     if (nref >= ((int64_t)1 << 31)) return fail(GH_ERR_INVALID, "too many reference points");
     if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_RUNTIME, "invalid device ordinal " + std::to_string(device_id));
-    float *d_q = nullptr, *d_ref = nullptr;
-    uint64_t *d_keys = nullptr;
+    gh_dev<float> d_q, d_ref;
+    gh_dev<uint64_t> d_keys;
     std::vector<uint64_t> keys((size_t)nq * k);
     gh_status st = GH_OK;
     std::string err;
-    auto cleanup = [&]() { if (d_q) (void)hipFree(d_q); if (d_ref) (void)hipFree(d_ref); if (d_keys) (void)hipFree(d_keys); };
-    if (hipMalloc((void **)&d_q, sizeof(float) * (size_t)std::max<int64_t>(nq * D, 1)) != hipSuccess ||
-        hipMalloc((void **)&d_ref, sizeof(float) * (size_t)std::max<int64_t>(nref * D, 1)) != hipSuccess ||
-        hipMalloc((void **)&d_keys, sizeof(uint64_t) * std::max<size_t>(keys.size(), 1)) != hipSuccess) {
-        cleanup();
+    if (!d_q.alloc(sizeof(float) * (size_t)nq * D) || !d_ref.alloc(sizeof(float) * (size_t)nref * D) ||
+        !d_keys.alloc(sizeof(uint64_t) * keys.size()))
         return fail(GH_ERR_NOMEM, "hipMalloc failed");
-    }
-    if (hipMemcpy(d_q, q, sizeof(float) * (size_t)nq * D, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ref, ref, sizeof(float) * (size_t)nref * D, hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
+    if (hipMemcpy(d_q.p, q, sizeof(float) * (size_t)nq * D, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_ref.p, ref, sizeof(float) * (size_t)nref * D, hipMemcpyHostToDevice) != hipSuccess)
         return fail(GH_ERR_HIP, "upload failed");
-    }
-    st = gh_knn_points_device(nullptr, d_q, nq, d_ref, nref, D, k, d_keys, &err);
-    if (st == GH_OK && hipMemcpy(keys.data(), d_keys, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost) != hipSuccess) {
+    st = gh_knn_points_device(nullptr, d_q.p, nq, d_ref.p, nref, D, k, d_keys.p, &err);
+    if (st == GH_OK && hipMemcpy(keys.data(), d_keys.p, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost) != hipSuccess) {
         st = GH_ERR_HIP;
         err = "download failed";
     }
-    cleanup();
     if (st != GH_OK) return fail(st, err);
     for (size_t i = 0; i < keys.size(); ++i) out[i] = (int64_t)(keys[i] & 0xFFFFFFFFu);
     return GH_OK;
@@ -1136,3 +1093,8 @@ extern "C" int32_t gh_device_count(void) {
     return n;
 }
 extern "C" const char *gh_version(void) { return "graphem_hip 0.1 (gfx950)"; }
+
+extern "C" void gh_debug_live_allocations(int64_t *count, int64_t *bytes) {
+    if (count) *count = gh_live_count.load();
+    if (bytes) *bytes = gh_live_bytes.load();
+}

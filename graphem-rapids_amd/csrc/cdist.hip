@@ -1082,19 +1082,8 @@ __global__ __launch_bounds__(64) void cdist_nth_kernel(int S, int r0, int R, int
 }
 
 cdist_args make_cdist_args(gh_engine *h) {
-    return cdist_args{h->d_pos, h->d_edges, h->D, h->LD, h->E, h->d_q, gh_qs(h->D, h->LD), gh_qtau(h->D, h->LD),
+    return cdist_args{h->d_pos.p, h->d_edges.p, h->D, h->LD, h->E, h->d_q.p, gh_qs(h->D, h->LD), gh_qtau(h->D, h->LD),
                       (h->S > 25 || h->E > 25) ? 1 : 0};
-}
-
-template <typename T>
-gh_status cdist_dev_alloc(gh_engine *h, T **p, size_t count) {
-    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        h->err = "hipMalloc failed (GH_DIST_CDIST buffers: up to min(sample_size, 2^30 / E) rows of E floats; sample_size = " +
-                 std::to_string(h->S) + ", E = " + std::to_string(h->E) + ")";
-        return GH_ERR_NOMEM;
-    }
-    return GH_OK;
 }
 
 int64_t cdist_vstride(const gh_engine *h) { return (h->E + 1023) / 1024 * 1024; }   // whole workgroups of cdist_prefix_kernel
@@ -1112,14 +1101,16 @@ gh_status gh_cdist_alloc(gh_engine *h) {
     if (R < 16) R = 16;
     if (R > h->S) R = h->S;
     h->cd_R = (int)R;
-    GH_TRY_ST(cdist_dev_alloc(h, &h->d_rare, (size_t)h->S + 1));
-    GH_TRY_ST(cdist_dev_alloc(h, &h->d_cd_rows, 2 * (size_t)h->S));
-    GH_TRY_ST(cdist_dev_alloc(h, &h->d_cd_vbuf, (size_t)(R * vstride)));
-    GH_TRY_ST(cdist_dev_alloc(h, &h->d_cd_cmin, (size_t)(R * h->cd_nchunks)));
-    GH_TRY_ST(cdist_dev_alloc(h, &h->d_cd_stat, 8));
-    GH_HIP(hipMemsetAsync(h->d_rare, 0, sizeof(int32_t) * ((size_t)h->S + 1), h->stream));
-    GH_HIP(hipMemsetAsync(h->d_cd_rows, 0, sizeof(int32_t) * 2 * (size_t)h->S, h->stream));
-    GH_HIP(hipMemsetAsync(h->d_cd_stat, 0, sizeof(int32_t) * 8, h->stream));
+    if (gh_alloc(h, h->d_rare, (size_t)h->S + 1, false) != GH_OK || gh_alloc(h, h->d_cd_rows, 2 * (size_t)h->S, false) != GH_OK ||
+        gh_alloc(h, h->d_cd_vbuf, (size_t)(R * vstride), false) != GH_OK || gh_alloc(h, h->d_cd_cmin, (size_t)(R * h->cd_nchunks), false) != GH_OK ||
+        gh_alloc(h, h->d_cd_stat, 8, false) != GH_OK) {
+        h->err = "hipMalloc failed (GH_DIST_CDIST buffers: up to min(sample_size, 2^30 / E) rows of E floats; sample_size = " +
+                 std::to_string(h->S) + ", E = " + std::to_string(h->E) + ")";
+        return GH_ERR_NOMEM;
+    }
+    GH_HIP(hipMemsetAsync(h->d_rare.p, 0, sizeof(int32_t) * ((size_t)h->S + 1), h->stream));
+    GH_HIP(hipMemsetAsync(h->d_cd_rows.p, 0, sizeof(int32_t) * 2 * (size_t)h->S, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_cd_stat.p, 0, sizeof(int32_t) * 8, h->stream));
     return GH_OK;
 }
 
@@ -1141,8 +1132,8 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
         {
             gh_scope t(h, "cdist_prefix");
             const dim3 grid(gx, ys);
-#define GH_CPRE(LL, NP) cdist_prefix_kernel<LL, NP><<<grid, dim3(256), 0, h->stream>>>(a, rr, all, r0, h->cd_R, h->d_cd_vbuf, vstride, \
-                                                                                       h->d_cd_cmin, h->cd_nchunks)
+#define GH_CPRE(LL, NP) cdist_prefix_kernel<LL, NP><<<grid, dim3(256), 0, h->stream>>>(a, rr, all, r0, h->cd_R, h->d_cd_vbuf.p, vstride, \
+                                                                                       h->d_cd_cmin.p, h->cd_nchunks)
             if (npt == 4) {
                 if (h->LD == 4) GH_CPRE(4, 4); else if (h->LD == 8) GH_CPRE(8, 4); else if (h->LD == 16) GH_CPRE(16, 4); else GH_CPRE(0, 4);
             } else {
@@ -1154,7 +1145,7 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
         if (nth_form && all_rows && h->E <= GH_CD_NTH_MAX) {   // tiny graphs: ATen's nth_element + sort, replayed
             gh_scope t(h, "cdist_nth");
             cdist_nth_kernel<<<dim3((unsigned)h->cd_R), dim3(64), sizeof(uint64_t) * (size_t)h->E, h->stream>>>(
-                (int)h->S, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf, vstride, out_keys, rr.hdr);
+                (int)h->S, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf.p, vstride, out_keys, rr.hdr);
             GH_LAUNCH_CHECK();
             continue;
         }
@@ -1163,7 +1154,7 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
         const inter_args ia = make_inter_args(h, fuse);
         const bool scalar_heap = h->K <= GH_CD_KS && !nth_form;
 #define GH_CREP(DD, HEAPv, INTv) cdist_replay_kernel<DD, HEAPv, INTv><<<dim3((unsigned)h->cd_R), dim3(256), smem, h->stream>>>( \
-        rr, all, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf, vstride, h->d_cd_cmin, h->cd_nchunks, h->d_cand, out_keys, nth_form, ia, h->d_stamps, \
+        rr, all, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf.p, vstride, h->d_cd_cmin.p, h->cd_nchunks, h->d_cand.p, out_keys, nth_form, ia, h->d_stamps.p, \
         (int)h->S, (int)(((int64_t)h->n_vblocks + GH_STAMP_EXTRA) * 8 / 32))
 #define GH_CREP_D(DD) case DD: if (scalar_heap) GH_CREP(DD, 0, true); else GH_CREP(DD, 1, true); break;
         if (fuse) {
@@ -1195,14 +1186,14 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
 gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) {
     const cdist_args a = make_cdist_args(h);
     if (h->cd_part && all_rows) {   // too few own edges for the scan: nothing proven, every row is replayed after the merge
-        GH_HIP(hipMemsetAsync(h->d_partial, 0xFF, sizeof(uint64_t) * (size_t)h->S * (h->K + 2), h->stream));
+        GH_HIP(hipMemsetAsync(h->d_partial.p, 0xFF, sizeof(uint64_t) * (size_t)h->S * (h->K + 2), h->stream));
         h->intersect_done = false;
         h->stats_reduced = false;
         return GH_OK;
     }
     const int set = h->cd_part ? h->cd_set ^ 1 : h->cd_set;   // (a partitioned engine's search takes its counter set at the merge)
     if (!h->cd_part) h->cd_set ^= 1;
-    const cdist_rows rr{h->d_rare, h->d_cd_rows, h->d_cd_rows + h->S, h->d_cd_stat + 4 * set, h->d_cd_stat + 4 * (set ^ 1)};
+    const cdist_rows rr{h->d_rare.p, h->d_cd_rows.p, h->d_cd_rows.p + h->S, h->d_cd_stat.p + 4 * set, h->d_cd_stat.p + 4 * (set ^ 1)};
     const bool fuse = !all_rows && !h->cd_part && fuse_intersect && h->K <= 64 && h->D >= 2 && h->D <= 16;
     bool reduce = false;
     if (!all_rows) {
@@ -1214,7 +1205,7 @@ gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) 
         const int part_mode = h->cd_part ? 1 : 0;
 #define GH_CSEL(DD)                                                                                                                \
     knn_select_cdist_kernel<DD><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), 0, h->stream>>>(          \
-        h->d_cand, h->d_cnt, h->K, a, h->d_partial, h->d_ovf, h->d_dbg_cnt + h->S, rr, ia, (int)h->S, h->d_blockstats, h->n_vblocks, \
+        h->d_cand.p, h->d_cnt.p, h->K, a, h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + h->S, rr, ia, (int)h->S, h->d_blockstats.p, h->n_vblocks, \
         h->d_stats, part_mode, (fuse && !h->cd_all_ties) ? 1 : 0)
         switch (h->D) {
             case 2: GH_CSEL(2); break;   case 3: GH_CSEL(3); break;   case 4: GH_CSEL(4); break;   case 5: GH_CSEL(5); break;
@@ -1225,7 +1216,7 @@ gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) 
 #undef GH_CSEL
         GH_LAUNCH_CHECK();
     }
-    if (!h->cd_part) GH_TRY_ST(cdist_replay_rounds(h, a, rr, all_rows, fuse, h->d_partial));
+    if (!h->cd_part) GH_TRY_ST(cdist_replay_rounds(h, a, rr, all_rows, fuse, h->d_partial.p));
     h->intersect_done = fuse;
     h->stats_reduced = reduce;
     return GH_OK;
@@ -1238,7 +1229,7 @@ gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) 
     const cdist_args a = make_cdist_args(h);
     const int set = h->cd_set;
     h->cd_set ^= 1;
-    const cdist_rows rr{h->d_rare, h->d_cd_rows, h->d_cd_rows + h->S, h->d_cd_stat + 4 * set, h->d_cd_stat + 4 * (set ^ 1)};
+    const cdist_rows rr{h->d_rare.p, h->d_cd_rows.p, h->d_cd_rows.p + h->S, h->d_cd_stat.p + 4 * set, h->d_cd_stat.p + 4 * (set ^ 1)};
     const bool fuse = !h->intersect_done && h->K <= 64 && h->D >= 2 && h->D <= 16;
     const int total = world * (h->K + 1);
     int n2 = 2;
@@ -1253,13 +1244,13 @@ gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) 
         gh_scope t(h, fuse ? "knn_merge_cdist_intersect" : "knn_merge_cdist");
         const inter_args ia = make_inter_args(h, fuse);
 #define GH_CMRG(DD) knn_merge_cdist_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2 * (bound ? 2 : 1), h->stream>>>( \
-        gathered, world, h->S, h->K, h->E, h->d_merged, rr, ia, h->d_cand, bound)
+        gathered, world, h->S, h->K, h->E, h->d_merged.p, rr, ia, h->d_cand.p, bound)
         if (fuse) { GH_DISPATCH_DIM(h->D, GH_CMRG) } else { GH_CMRG(0); }
 #undef GH_CMRG
         GH_LAUNCH_CHECK();
     }
-    GH_TRY_ST(cdist_replay_rounds(h, a, rr, false, fuse, h->d_merged));
-    h->d_keys_cur = h->d_merged;
+    GH_TRY_ST(cdist_replay_rounds(h, a, rr, false, fuse, h->d_merged.p));
+    h->d_keys_cur = h->d_merged.p;
     if (fuse) h->intersect_done = true;
     return GH_OK;
 }

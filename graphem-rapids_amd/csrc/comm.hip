@@ -107,17 +107,28 @@ struct gh_comm {
     int world = 1, rank = 0;
     ncclComm_t nccl = nullptr;          // RCCL backend
     gh_loop_group *loop = nullptr;      // loopback backend
-    uint64_t *d_gathered = nullptr;     // (world, S, K) keys of all ranks
-    double *d_stats_all = nullptr;      // (world, stats rows, LD) statistics of all ranks (form C)
+    gh_dev<uint64_t> d_gathered;        // (world, S, K) keys of all ranks
+    gh_dev<double> d_stats_all;         // (world, stats rows, LD) statistics of all ranks (form C)
     // form D: the all-gather of the new0 blocks runs beside the KNN tail, on a stream and a communicator of its own
     ncclComm_t nccl_b = nullptr;        // ncclCommSplit of `nccl` (same ranks); null: the loopback backend, or no overlap
     hipStream_t stream_b = nullptr;
     hipEvent_t ev_fused = nullptr, ev_rows = nullptr;
+    gh_comm() = default;
+    gh_comm(const gh_comm &) = delete;
+    gh_comm &operator=(const gh_comm &) = delete;
+    ~gh_comm() {
+        if (nccl_b) (void)rccl()->CommDestroy(nccl_b);
+        if (nccl) (void)rccl()->CommDestroy(nccl);
+        if (stream_b) (void)hipStreamDestroy(stream_b);
+        if (ev_fused) (void)hipEventDestroy(ev_fused);
+        if (ev_rows) (void)hipEventDestroy(ev_rows);
+    }
 };
+void gh_delete(gh_comm *c) { delete c; }
 
 // side: the collective goes on the second stream / communicator (form D's early all-gather of the rows)
 static gh_status comm_all_gather(gh_engine *h, const void *send, void *recv, size_t bytes, const char *what, bool side = false) {
-    gh_comm *c = h->comm;
+    gh_comm *c = h->comm.get();
     const hipStream_t stream = side ? c->stream_b : h->stream;
     gh_scope t(h, what, stream);
     if (c->nccl) {
@@ -166,23 +177,20 @@ static gh_status comm_common(gh_engine *h, int world, int rank) {
         h->err = "call gh_rank_layout (or gh_gather_layout) with the same world and rank first";
         return GH_ERR_INVALID;
     }
-    h->comm = new (std::nothrow) gh_comm();
+    h->comm.reset(new (std::nothrow) gh_comm());
     if (!h->comm) { h->err = "out of host memory"; return GH_ERR_NOMEM; }
     h->comm->world = world;
     h->comm->rank = rank;
     const size_t stats_doubles = (size_t)world * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
-    if (hipMalloc(reinterpret_cast<void **>(&h->comm->d_gathered), sizeof(uint64_t) * (size_t)world * h->S * (h->K + (h->cd_part ? 2 : 0)) + 16) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&h->comm->d_stats_all), sizeof(double) * stats_doubles + 16) != hipSuccess) {
-        if (h->comm->d_gathered) (void)hipFree(h->comm->d_gathered);
-        delete h->comm; h->comm = nullptr;
-        h->err = "hipMalloc of the gather buffers failed";
-        return GH_ERR_NOMEM;
-    }
+    // (16 spare bytes behind each)
+    gh_status st = gh_alloc(h, h->comm->d_gathered, (size_t)world * h->S * (h->K + (h->cd_part ? 2 : 0)) + 2, false);
+    if (st == GH_OK) st = gh_alloc(h, h->comm->d_stats_all, stats_doubles + 2, false);
+    if (st != GH_OK) { h->comm.reset(); return st; }
     if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: a second stream for the early all-gather of the rows, ordered against the engine's by two events
         if (hipStreamCreateWithFlags(&h->comm->stream_b, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_fused, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_rows, hipEventDisableTiming) != hipSuccess) {
-            gh_comm_free(h);
+            h->comm.reset();
             h->err = "form D: creating the side stream failed";
             return GH_ERR_HIP;
         }
@@ -202,9 +210,7 @@ extern "C" gh_status gh_comm_init_rccl(gh_handle h, int32_t world, int32_t rank,
     const ncclResult_t r = api->CommInitRank(&h->comm->nccl, world, id, rank);
     if (r != ncclSuccess) {
         h->err = std::string("ncclCommInitRank: ") + api->GetErrorString(r);
-        (void)hipFree(h->comm->d_gathered);
-        (void)hipFree(h->comm->d_stats_all);
-        delete h->comm; h->comm = nullptr;
+        h->comm.reset();
         return GH_ERR_RUNTIME;
     }
     // form D: the early all-gather needs a communicator of its own to be in flight beside the keys' and the statistics'.
@@ -235,24 +241,11 @@ extern "C" gh_status gh_comm_init_loopback(gh_handle h, gh_loop_group *group, in
     return GH_OK;
 }
 
-void gh_comm_free(gh_engine *h) {
-    if (!h->comm) return;
-    if (h->comm->nccl_b) (void)rccl()->CommDestroy(h->comm->nccl_b);
-    if (h->comm->nccl) (void)rccl()->CommDestroy(h->comm->nccl);
-    if (h->comm->stream_b) (void)hipStreamDestroy(h->comm->stream_b);
-    if (h->comm->ev_fused) (void)hipEventDestroy(h->comm->ev_fused);
-    if (h->comm->ev_rows) (void)hipEventDestroy(h->comm->ev_rows);
-    if (h->comm->d_gathered) (void)hipFree(h->comm->d_gathered);
-    if (h->comm->d_stats_all) (void)hipFree(h->comm->d_stats_all);
-    delete h->comm;
-    h->comm = nullptr;
-}
-
 extern "C" gh_status gh_comm_destroy(gh_handle h) {
     if (!h) return GH_ERR_INVALID;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    gh_comm_free(h);
+    h->comm.reset();
     return GH_OK;
 }
 
@@ -261,7 +254,7 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GH_ERR_HIP; }
     if (!h->comm) { h->err = "no communicator: call gh_comm_init_rccl / gh_comm_init_loopback first"; return GH_ERR_INVALID; }
     if (iters < 0) { h->err = "negative iteration count"; return GH_ERR_INVALID; }
-    gh_comm *c = h->comm;
+    gh_comm *c = h->comm.get();
     const size_t key_bytes = sizeof(uint64_t) * (size_t)h->S * (h->K + (h->cd_part ? 2 : 0));   // (a GH_DIST_CDIST partition sends K + 1 keys and a flag)
     int32_t *d_ids = nullptr;
     GH_TRY_ST(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));   // nullptr: device sampler / arange on every rank
@@ -291,33 +284,33 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
                 if (side && hipEventRecord(c->ev_rows, c->stream_b) != hipSuccess) { h->err = "form D: event record failed"; return GH_ERR_HIP; }
             }
             if (h->S > 0 && h->k > 0) {
-                GH_TRY_ST(comm_all_gather(h, h->d_partial, c->d_gathered, key_bytes, "allgather_keys"));
-                GH_TRY_ST(gh_step_merge(h, c->d_gathered, c->world));
+                GH_TRY_ST(comm_all_gather(h, h->d_partial.p, c->d_gathered.p, key_bytes, "allgather_keys"));
+                GH_TRY_ST(gh_step_merge(h, c->d_gathered.p, c->world));
             } else {
-                GH_TRY_ST(gh_step_merge(h, h->d_partial, 1));   // spring forces only: nothing to merge
+                GH_TRY_ST(gh_step_merge(h, h->d_partial.p, 1));  // spring forces only: nothing to merge
             }
             if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: (the rows went out above, or go now)
                 // a step without new0 (no fused kernel), or RCCL without a second communicator: form B's order
                 if (!rows_sent) GH_TRY_ST(send_rows(false));
-                GH_TRY_ST(comm_all_gather(h, h->d_stats, h->d_stats_all, sizeof(double) * (size_t)h->stats_block, "allgather_stats"));   // statistics + patch list
+                GH_TRY_ST(comm_all_gather(h, h->d_stats, h->d_stats_all.p, sizeof(double) * (size_t)h->stats_block, "allgather_stats"));  // statistics + patch list
                 if (early && side) {   // what of the early all-gather is still outstanding is this iteration's EXPOSED collective time
                     gh_scope t(h, "allgather_rows_exposed");
                     if (hipStreamWaitEvent(h->stream, c->ev_rows, 0) != hipSuccess) { h->err = "hipStreamWaitEvent failed"; return GH_ERR_HIP; }
                 }
                 GH_TRY_ST(gh_step_finish_overlap(h));
             } else if (h->layout == GH_LAYOUT_GATHERED) {   // form B
-                GH_TRY_ST(comm_all_gather(h, h->d_gbuf + (size_t)c->rank * h->g_slot, h->d_gbuf, (size_t)h->g_slot, "allgather_slots"));
+                GH_TRY_ST(comm_all_gather(h, h->d_gbuf.p + (size_t)c->rank * h->g_slot, h->d_gbuf.p, (size_t)h->g_slot, "allgather_slots"));
                 GH_TRY_ST(gh_step_finish_gathered(h));
             } else {           // form C
-                GH_TRY_ST(comm_all_gather(h, h->d_stats, c->d_stats_all, stats_bytes, "allgather_stats"));
-                GH_TRY_ST(gh_step_finish_own(h, c->d_stats_all, c->world));
+                GH_TRY_ST(comm_all_gather(h, h->d_stats, c->d_stats_all.p, stats_bytes, "allgather_stats"));
+                GH_TRY_ST(gh_step_finish_own(h, c->d_stats_all.p, c->world));
                 if (h->packed_exchange) {   // the blocks travel without their pad columns (12 instead of 16 bytes per row at D = 3)
                     const size_t block = sizeof(float) * (size_t)h->g_chunk * h->D;
-                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_rows_packed) + (size_t)c->rank * block, h->d_rows_packed, block, "allgather_rows"));
+                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_rows_packed.p) + (size_t)c->rank * block, h->d_rows_packed.p, block, "allgather_rows"));
                     GH_TRY_ST(gh_launch_unpack_rows(h));
                 } else {
                     const size_t block = sizeof(float) * (size_t)h->g_chunk * h->LD;
-                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_pos) + (size_t)c->rank * block, h->d_pos, block, "allgather_rows"));
+                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_pos.p) + (size_t)c->rank * block, h->d_pos.p, block, "allgather_rows"));
                 }
             }
         }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -33,21 +34,48 @@ struct gh_timer_slot {
 enum { GH_IDS_GIVEN = 0, GH_IDS_SAMPLER = 1, GH_IDS_ARANGE = 2 };
 struct gh_ids {
     int mode;       // GH_IDS_GIVEN: the ids are at `ids`; GH_IDS_SAMPLER / GH_IDS_ARANGE: produced into `ids` (d_sampled)
-    int32_t *ids;   // (mutable: the set-up writes the ids it draws)
+    int32_t *ids;   // a view (mutable: the set-up writes the ids it draws)
 };
 
 // How a partitioned engine finishes a step (include/graphem_hip.h): set by gh_gather_layout (form B), gh_rank_layout
 // (form C), gh_overlap_layout (form D).
 enum { GH_LAYOUT_NONE = 0, GH_LAYOUT_GATHERED, GH_LAYOUT_RANK, GH_LAYOUT_OVERLAP };
 
+// Parts of the engine whose types are complete only in their own translation units: each defines its gh_delete there.
 struct gh_comm;   // comm.hip: collective backend of the native partitioned loop
 struct gh_f64;    // f64.hip: state of a float64 engine (gh_create_f64)
 struct gh_ivf;    // ivf.hip: buffers of the inverted-file search (GH_KNN_IVF)
+void gh_delete(gh_comm *);
+void gh_delete(gh_f64 *);
+void gh_delete(gh_ivf *);
+struct gh_part_delete {
+    template <class T> void operator()(T *p) const { gh_delete(p); }
+};
 
+// gh_run_torch_sampled (api.hip): pinned upload slots for the rows a host thread draws (torch.randperm's prefixes), one
+// event per slot (recorded behind the slot's copy: the slot is reused once it has fired)
+#define GH_RING_SLOTS 8
+#define GH_RING_CHUNK 32   /* rows per slot = per copy, at most */
+struct gh_ring {
+    int32_t *host = nullptr;
+    size_t cap = 0;              // int32 words allocated in host (GH_RING_SLOTS * GH_RING_CHUNK * S)
+    uint64_t uploads = 0;        // copies out of host so far, over all calls: slot = uploads % GH_RING_SLOTS
+    hipEvent_t ev[GH_RING_SLOTS] = {};
+    gh_ring() = default;
+    gh_ring(const gh_ring &) = delete;
+    gh_ring &operator=(const gh_ring &) = delete;
+    ~gh_ring() {
+        if (host) (void)hipHostFree(host);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// Ownership is stated by type: a gh_dev member owns its device memory, a raw pointer is a view into memory owned
+// elsewhere, and deleting the engine releases everything it holds.
 struct gh_engine {
+    ~gh_engine();   // (api.hip) destroys own_stream; the members release themselves
     int device = 0;
-    gh_comm *comm = nullptr;
-    gh_f64 *f64 = nullptr;    // non-null: a float64 engine -- only this, the sizes, the parameters and the stream are in use
     int64_t n = 0, E = 0;
     int D = 0, LD = 0, k = 0, K = 0;
     int64_t S = 0;
@@ -58,69 +86,63 @@ struct gh_engine {
     std::string err;
 
     hipStream_t stream = nullptr;       // stream all work is enqueued on
-    hipStream_t own_stream = nullptr;   // created by gh_create
+    hipStream_t own_stream = nullptr;   // created by gh_create, destroyed by ~gh_engine
     int64_t pos_rows = 0;               // rows allocated in d_pos (n + GH_POS_PAD_ROWS)
 
     // graph
-    int32_t *d_edges = nullptr;   // (E, 2)
-    int32_t *d_rowptr = nullptr;  // (rows + 1) pull lists of own rows, reference summation order
-    int32_t *d_adj = nullptr;     // neighbours
+    gh_dev<int32_t> d_edges;      // (E, 2)
+    gh_dev<int32_t> d_rowptr;     // (rows + 1) pull lists of own rows, reference summation order
+    gh_dev<int32_t> d_adj;        // neighbours
     int64_t adj_len = 0;
-    int32_t *d_first_edge = nullptr; // (rows + 1) offset of each own row's owned edges: the first owned edge id
+    gh_dev<int32_t> d_first_edge;    // (rows + 1) offset of each own row's owned edges: the first owned edge id
                                      // (rule A: smaller endpoint owns) or a prefix count into d_own_eids (rule B)
-    int32_t *d_own_eids = nullptr;   // rule B (balanced ownership of partitioned engines): ids of the owned edges
+    gh_dev<int32_t> d_own_eids;      // rule B (balanced ownership of partitioned engines): ids of the owned edges
                                      // in (row, list) order; null under rule A
     int64_t own_count = 0;           // edges this rank owns (midpoints in d_mid, searched by its KNN kernels)
     int64_t mid_base = 0;            // d_mid row of an owned edge = d_first_edge offset - mid_base
     bool fused_mid = false;       // own edge range == edges owned by own rows: spring kernel writes midpoints
-    int32_t *d_long_rows = nullptr;   // local ids of the own rows with more than GH_LONG_DEG neighbours (common.h)
-    int32_t *d_long_ownptr = nullptr; // their owned (hub-hub) edges: offsets ...
-    int32_t *d_long_ownadj = nullptr; // ... and neighbours
-    int32_t *d_long_eptr = nullptr;   // (nlong + 1) prefix of their degrees
-    int32_t *d_long_erow = nullptr;   // (long_entries) index of the long row a list entry belongs to
-    uint8_t *d_own_long = nullptr;    // (own_count) owned-edge slots whose owner row is long (common.h gh_long_midpoints)
-    float *d_long_terms = nullptr;    // (long_entries * D) force terms of their neighbours, component-major per row
+    gh_dev<int32_t> d_long_rows;      // local ids of the own rows with more than GH_LONG_DEG neighbours (common.h)
+    gh_dev<int32_t> d_long_ownptr;    // their owned (hub-hub) edges: offsets ...
+    gh_dev<int32_t> d_long_ownadj;    // ... and neighbours
+    gh_dev<int32_t> d_long_eptr;      // (nlong + 1) prefix of their degrees
+    gh_dev<int32_t> d_long_erow;      // (long_entries) index of the long row a list entry belongs to
+    gh_dev<uint8_t> d_own_long;       // (own_count) owned-edge slots whose owner row is long (common.h gh_long_midpoints)
+    gh_dev<float> d_long_terms;       // (long_entries * D) force terms of their neighbours, component-major per row
     int nlong = 0;
     int long_deg = 128;               // rows with more neighbours than this are long (common.h gh_long_degree)
     int64_t long_entries = 0;
     int long_max_deg = 0;             // longest long row (forces.hip: one launch for the long rows when moderate)
-    float *d_mid = nullptr;       // (own_count, LD) midpoints of the own edges, current iteration
-    float *d_Fs = nullptr;        // (rows, LD) spring forces of the own rows
-    float *d_gmin = nullptr;      // (S, Gpad) group minima of the threshold subset (setup_core.h), float bits
-    int32_t *d_sub_uv = nullptr;  // (thr_M1, 2) endpoints of the subset edges
+    gh_dev<float> d_mid;          // (own_count, LD) midpoints of the own edges, current iteration
+    gh_dev<float> d_Fs;           // (rows, LD) spring forces of the own rows
+    gh_dev<float> d_gmin;         // (S, Gpad) group minima of the threshold subset (setup_core.h), float bits
+    gh_dev<int32_t> d_sub_uv;     // (thr_M1, 2) endpoints of the subset edges
     int64_t thr_stride = 0, thr_M1 = 0;  // the subset: every thr_stride-th own edge, thr_M1 of them (gh_choose_threshold_subset)
-    int32_t *d_vblock = nullptr;  // (n_vblocks + 1) vertex ranges of the fused spring+scan workgroups
+    gh_dev<int32_t> d_vblock;     // (n_vblocks + 1) vertex ranges of the fused spring+scan workgroups
     int n_vblocks = 0;
     bool opt_no_presetup = false; // GRAPHEM_HIP_NO_PRESETUP (read at gh_create)
     bool fused_scan = false;      // fused spring+scan kernel usable for this graph / partition
 
     // state
-    float *d_pos = nullptr;       // (n, LD)
-    float *d_new = nullptr;       // (rows, LD) un-normalised update of own rows
-    float *d_tmpF = nullptr;      // (n, LD) scratch for the per-phase entry points
-    float *d_tmpF2 = nullptr;
-    float *d_io = nullptr;        // (n, D) staging for unpadded host copies
+    gh_dev<float> d_pos;          // (n, LD)
+    gh_dev<float> d_new_buf;      // (rows, LD) the engine's own storage for ...
+    float *d_new = nullptr;       // ... the un-normalised update of own rows.  A view: d_new_buf, or block g_rank of d_gbuf (form B) / d_rows_all (form D)
+    gh_dev<float> d_tmpF;         // (n, LD) scratch for the per-phase entry points
+    gh_dev<float> d_tmpF2;
+    gh_dev<float> d_io;           // (n, D) staging for unpadded host copies
 
     // intersection accumulators
-    double *d_acc = nullptr;      // (n, LD) zero between iterations
-    int32_t *d_tflag = nullptr;   // (n) zero between iterations
-    int32_t *d_touched = nullptr; // (4 * S * k)
-    int32_t *d_tcount = nullptr;  // (1)
+    gh_dev<double> d_acc;         // (n, LD) zero between iterations
+    gh_dev<int32_t> d_tflag;      // (n) zero between iterations
+    gh_dev<int32_t> d_touched;    // (4 * S * k)
+    gh_dev<int32_t> d_tcount;     // (1)
 
     // knn
-    int32_t *d_sampled = nullptr; // (S) owned buffer
+    gh_dev<int32_t> d_sampled;    // (S) owned buffer
     gh_ids sample{};                  // ids of the current iteration: d_sampled or a row of d_stream_ids, GH_IDS_GIVEN once
                                       // produced (the sampler / arange run inside knn_setup_kernel or by gh_ensure_sample)
-    int32_t *d_stream_ids = nullptr;  // (iters, S) uploaded sample stream of gh_run
+    gh_dev<int32_t> d_stream_ids;     // (iters, S) uploaded sample stream of gh_run
     size_t stream_ids_cap = 0;
-    // gh_run_torch_sampled (api.hip): pinned upload slots for the rows a host thread draws (torch.randperm's prefixes), one
-    // event per slot (recorded behind the slot's copy: the slot is reused once it has fired)
-#define GH_RING_SLOTS 8
-#define GH_RING_CHUNK 32   /* rows per slot = per copy, at most */
-    int32_t *h_ring = nullptr;
-    size_t ring_cap = 0;              // int32 words allocated in h_ring (GH_RING_SLOTS * GH_RING_CHUNK * S)
-    uint64_t ring_uploads = 0;        // copies out of h_ring so far, over all calls: slot = ring_uploads % GH_RING_SLOTS
-    hipEvent_t ring_ev[GH_RING_SLOTS] = {};
+    gh_ring ring;                     // gh_run_torch_sampled
     double sampler_stats[4] = {0, 0, 0, 0};   // last gh_run_torch_sampled, host ms: producer drawing, caller waiting for a pinned slot, caller waiting for ids, the call
     bool new0_ready = false;      // the fused kernel of this step wrote d_new = pos + Fs and its block sums
     bool intersect_done = false;  // the KNN kernels of this step already ran the intersection phase
@@ -132,92 +154,107 @@ struct gh_engine {
     } lookahead;
     bool last_step_own_ids = false;     // gh_step_begin was called without ids (device sampler / arange)
     bool tcount_reset_pending = false;  // this step's threshold kernel must reset d_tcount
-    float *d_iscratch = nullptr;  // (S * k, LD) per-pair scratch of the intersection kernel
-    float *d_q = nullptr;         // (S, QS) query records: midpoint coordinates + tau (knn.hip gh_qs)
-    float *d_qscan = nullptr;     // (S, QS) pre-filter records (-2q, t) written by the threshold kernel
-    uint16_t *d_qA = nullptr;     // (S, 16) f16 A-operand rows of the split-f16 MFMA pre-filter (D <= 3), same kernel
-    int32_t *d_order = nullptr;       // internal row of every vertex (BFS reordering), or null: identity
+    gh_dev<float> d_iscratch;     // (S * k, LD) per-pair scratch of the intersection kernel
+    gh_dev<float> d_q;            // (S, QS) query records: midpoint coordinates + tau (knn.hip gh_qs)
+    gh_dev<float> d_qscan;        // (S, QS) pre-filter records (-2q, t) written by the threshold kernel
+    gh_dev<uint16_t> d_qA;        // (S, 16) f16 A-operand rows of the split-f16 MFMA pre-filter (D <= 3), same kernel
+    gh_dev<int32_t> d_order;          // internal row of every vertex (BFS reordering), or null: identity
     std::vector<int32_t> order_host;  // the same on the host (empty: identity)
-    unsigned char *d_gbuf = nullptr;  // gather buffer of the one-collective finish (gh_gather_layout), or null
-    float *d_new_own = nullptr;       // allocations behind d_new / d_stats while they point into d_gbuf
-    double *d_stats_own = nullptr;
+    gh_dev<unsigned char> d_gbuf;     // gather buffer of the one-collective finish (gh_gather_layout), or null
     int64_t g_slot = 0, g_chunk = 0;  // slot bytes, rows per rank
     int g_world = 0, g_rank = 0;
     int layout = GH_LAYOUT_NONE;
-    float *d_rows_packed = nullptr;   // form C, D < LD: (world, chunk, D) the finished blocks WITHOUT the pad columns -- what travels
+    gh_dev<float> d_rows_packed;      // form C, D < LD: (world, chunk, D) the finished blocks WITHOUT the pad columns -- what travels
                                       // (12 instead of 16 bytes per row at 3 components); gh_step_unpack_rows expands it into d_pos
     bool packed_exchange = false;     // ... in use (gh_set_packed_rows; default: from 2 M vertices on, where the saved quarter of
                                       // the all-gather outweighs the expansion kernel -- 30 us at 4 M vertices, 14 at 1 M)
     // form D (gh_overlap_layout): the ranks' un-normalised rows new0 = pos + Fs are all-gathered EARLY, beside the KNN tail
     bool rows_early = false;          // this step: new0 of the own rows is in its block (the rows may travel right after step_begin)
-    float *d_rows_all = nullptr;      // (world, chunk, LD): d_new is block g_rank of it
-    float *d_rows_pk = nullptr;       // (world, chunk, D): the same without pad columns -- what travels when D < LD -- or null
-    double *d_stats_all = nullptr;    // (world, stats_block) doubles: per rank its statistics rows, then its PATCH LIST -- two int32 counters used by alternate iterations (16 bytes
+    gh_dev<float> d_rows_all;         // (world, chunk, LD): d_new is block g_rank of it
+    gh_dev<float> d_rows_pk;          // (world, chunk, D): the same without pad columns -- what travels when D < LD -- or null
+    gh_dev<double> d_stats_all;       // (world, stats_block) doubles: per rank its statistics rows, then its PATCH LIST -- two int32 counters used by alternate iterations (16 bytes
                                       // reserved) and patch_cap records (row as int32 bits, LD floats): the own rows the intersection phase touched, as
                                       // finished by their owner, pos + (Fs + Fi); d_stats is block g_rank of it
     int64_t stats_block = 0;          // doubles per rank in d_stats_all
     int64_t patch_cap = 0;            // records per rank: min(4 S k, chunk)
-    int32_t *d_qexact = nullptr;  // [0] = count, [1..] = queries outside the f16 range (scanned exactly)
-    uint64_t *d_cand = nullptr;   // (S, GH_CAND_CAP)
-    int32_t *d_cnt = nullptr;     // (S * GH_CNT_STRIDE) one counter per 128-byte line
-    int32_t *d_ovf = nullptr;     // (S)
-    int32_t *d_sel_redo = nullptr;// (S) queries knn_select_wave_kernel left to the workgroup form (zero between launches)
-    int32_t *d_tq_count = nullptr, *d_tq_base = nullptr, *d_tq_touched = nullptr;   // (S), (S), (S, 4 k): per-query runs of the touched list (S >= 2048)
-    int32_t *d_dbg_cnt = nullptr; // (2, S) candidate-list lengths seen by the last subset / final select
-    uint64_t *d_partial = nullptr;// (S, K) this rank's best keys, ascending
-    uint64_t *d_merged = nullptr; // (S, K) keys merged over the ranks (world > 1)
-    const uint64_t *d_keys_cur = nullptr;  // keys the intersection phase reads: d_partial or d_merged
+    gh_dev<int32_t> d_qexact;     // [0] = count, [1..] = queries outside the f16 range (scanned exactly)
+    gh_dev<uint64_t> d_cand;      // (S, GH_CAND_CAP)
+    gh_dev<int32_t> d_cnt;        // (S * GH_CNT_STRIDE) one counter per 128-byte line
+    gh_dev<int32_t> d_ovf;        // (S)
+    gh_dev<int32_t> d_sel_redo;   // (S) queries knn_select_wave_kernel left to the workgroup form (zero between launches)
+    gh_dev<int32_t> d_tq_count, d_tq_base, d_tq_touched;                            // (S), (S), (S, 4 k): per-query runs of the touched list (S >= 2048)
+    gh_dev<int32_t> d_dbg_cnt;    // (2, S) candidate-list lengths seen by the last subset / final select
+    gh_dev<uint64_t> d_partial;   // (S, K) this rank's best keys, ascending
+    gh_dev<uint64_t> d_merged;    // (S, K) keys merged over the ranks (world > 1)
+    const uint64_t *d_keys_cur = nullptr;  // view: the keys the intersection phase reads, d_partial or d_merged
 
     // GH_DIST_CDIST (cdist.hip): the reference's cdist + topk values and tie order
     bool cdist = false;
     bool cd_part = false;             // ... on a row partition: d_partial holds (S, K + 2) per-rank records, the rows are decided at the merge (cdist.hip)
     bool cd_all_ties = false;         // gh_set_cdist_replay: the loop lists every tie too (rows column for column), not only those that can change a force
     int Ksel = 0;                     // keys the candidate selection extracts: K, or K + 1 with cdist (boundary ties)
-    int32_t *d_rare = nullptr;        // [1..S] = the listed queries: partial_sort's heap is replayed for them
-    int32_t *d_cd_rows = nullptr;     // (2, S) per listed slot: prefix length P (ids below it are valued), tail length
-    float *d_cd_vbuf = nullptr;       // (cd_R, cd_nchunks * 64) cdist values of those queries against the edges below P
-    float *d_cd_cmin = nullptr;       // (cd_R, cd_nchunks) minimum of each chunk of 64 edge ids
-    int32_t *d_cd_stat = nullptr;     // two sets (used alternately) of [0] listed rows, [1] rows whose tie order ATen leaves to std::nth_element (not reproduced), [2] the longest prefix
+    gh_dev<int32_t> d_rare;           // [1..S] = the listed queries: partial_sort's heap is replayed for them
+    gh_dev<int32_t> d_cd_rows;        // (2, S) per listed slot: prefix length P (ids below it are valued), tail length
+    gh_dev<float> d_cd_vbuf;          // (cd_R, cd_nchunks * 64) cdist values of those queries against the edges below P
+    gh_dev<float> d_cd_cmin;          // (cd_R, cd_nchunks) minimum of each chunk of 64 edge ids
+    gh_dev<int32_t> d_cd_stat;        // two sets (used alternately) of [0] listed rows, [1] rows whose tie order ATen leaves to std::nth_element (not reproduced), [2] the longest prefix
     int cd_R = 0, cd_nchunks = 0, cd_set = 0;   // cd_set: the counter set the NEXT search uses
 
     // grid KNN (grid.hip; GH_KNN_GRID)
     int grid_G = 0, grid_bits = 0;
     int64_t grid_cells = 0;
     size_t grid_temp_bytes = 0;
-    uint32_t *d_grid_u32 = nullptr;   // keys, rows, sorted keys, sorted rows, cell starts, sorted edge ids
-    void *d_grid_smid = nullptr;      // (own_count) float4 midpoints in cell order
-    void *d_grid_temp = nullptr;      // radix sort scratch
-
-    gh_ivf *ivf = nullptr;            // GH_KNN_IVF (ivf.hip)
+    gh_dev<uint32_t> d_grid_u32;      // keys, rows, sorted keys, sorted rows, cell starts, sorted edge ids
+    gh_dev<float> d_grid_smid;        // (own_count) float4 midpoints in cell order
+    gh_dev<unsigned char> d_grid_temp; // radix sort scratch
 
     // normalisation
-    double *d_blockstats = nullptr; // (nblocks, 2, LD)
+    gh_dev<double> d_blockstats;    // (nblocks, 2, LD)
     int nblocks_update = 0;
-    double *d_stats = nullptr;      // (2 + 2*gh_fix_blocks(LD), LD): sum, sum of squares, then correction row pairs;
-                                    // summed elementwise over the ranks by the caller when partitioned
+    gh_dev<double> d_stats_buf;     // the engine's own storage for ...
+    double *d_stats = nullptr;      // ... (2 + 2*gh_fix_blocks(LD), LD): sum, sum of squares, then correction row pairs;
+                                    // summed elementwise over the ranks by the caller when partitioned.  A view: d_stats_buf,
+                                    // or the own block of d_gbuf (form B) / d_stats_all (form D)
 
     // timing
     // thresholds inside the fused launch (tau_core.h)
     bool tau_embedded = false;
     bool tau_embedded_plan = false;      // the creation-time choice; the query-cell filter overrides it (gh_choose_scan_filter)
-    unsigned *d_tau_flag = nullptr;      // queries published so far by the current fused launch
+    gh_dev<unsigned> d_tau_flag;         // queries published so far by the current fused launch
     // pre-filter of the D <= 3 fused kernel's phase B (fused.hip): query-cell table or split-f16 MFMA
     int scan_filter = 0;                 // GH_FILTER_AUTO | _MFMA | _CELLS, as set by gh_set_scan_filter
     bool qcells = false;                 // in use: the query-cell table (qcell_core.h)
-    uint32_t *d_qcell = nullptr;         // (GH_QC_WORDS) the table of the current launch, built by its first workgroup
-    unsigned *d_qc_flag = nullptr;       // launch number whose table is complete
+    gh_dev<uint32_t> d_qcell;            // (GH_QC_WORDS) the table of the current launch, built by its first workgroup
+    gh_dev<unsigned> d_qc_flag;          // launch number whose table is complete
     unsigned qc_epoch = 0;               // number of the last launch on the query-cell path
-    int32_t *d_wait_failed = nullptr;    // a consumer gave up waiting: reported by gh_sync / gh_get_positions
+    gh_dev<int32_t> d_wait_failed;       // a consumer gave up waiting: reported by gh_sync / gh_get_positions
 
 #define GH_STAMP_EXTRA 8192
-    unsigned long long *d_stamps = nullptr;   // GRAPHEM_HIP_STAMPS: (n_vblocks, 8) wall-clock stamps of the last fused launch
+    gh_dev<unsigned long long> d_stamps;      // GRAPHEM_HIP_STAMPS: (n_vblocks, 8) wall-clock stamps of the last fused launch
     bool timing = false;
     std::vector<gh_timer_slot> timers;
+
+    // (last, so that they go first, in this order: comm, f64, ivf)
+    std::unique_ptr<gh_ivf, gh_part_delete> ivf;     // GH_KNN_IVF (ivf.hip)
+    std::unique_ptr<gh_f64, gh_part_delete> f64;     // non-null: a float64 engine -- only this, the sizes, the parameters and the stream are in use
+    std::unique_ptr<gh_comm, gh_part_delete> comm;
 };
+
+// The allocator of the engine's translation units: `count` elements (at least one) into `buf`, whose earlier allocation, if
+// any, is released first; zero: filled with zeros on the engine's stream.
+template <class T> gh_status gh_alloc(gh_engine *h, gh_dev<T> &buf, size_t count, bool zero) {
+    if (count == 0) count = 1;
+    if (!buf.alloc(count * sizeof(T))) {
+        h->err = std::string("hipMalloc failed: ") + hipGetErrorString(hipGetLastError());
+        return GH_ERR_NOMEM;
+    }
+    if (zero) GH_HIP(hipMemsetAsync(buf.p, 0, count * sizeof(T), h->stream));
+    return GH_OK;
+}
 
 // The engine's own ids for an iteration: arange(E) when S >= E (pt.py:412, no randomness consumed: SURVEY Q9), else the
 // device sampler.
-inline gh_ids gh_own_ids(const gh_engine *h) { return gh_ids{h->S >= h->E ? GH_IDS_ARANGE : GH_IDS_SAMPLER, h->d_sampled}; }
+inline gh_ids gh_own_ids(const gh_engine *h) { return gh_ids{h->S >= h->E ? GH_IDS_ARANGE : GH_IDS_SAMPLER, h->d_sampled.p}; }
 // The normalise launch just enqueued also set up iteration iter + 1 from *next; null: nothing is set up ahead (any more).
 inline void gh_set_lookahead(gh_engine *h, const gh_ids *next) {
     h->lookahead.valid = next != nullptr;
@@ -258,13 +295,11 @@ extern "C" int32_t gh_step_rows_early(gh_handle h);
 extern "C" gh_status gh_step_finish_overlap(gh_handle h);
 gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, int32_t **d_ids);
 gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids);
-void gh_comm_free(gh_engine *h);
 // f64.hip
 void gh_set_create_error(const std::string &msg);   // (api.hip) message gh_last_error(NULL) returns
 // (api.hip) argument and device checks of gh_create / gh_create_f64; f64_max_D > 0: the float64 engine's, with its k_attr
 gh_status gh_check_create_args(int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges, const gh_params *params,
                                int f64_max_D = 0, double f64_k_attr = 0.0);
-void gh_f64_free(gh_engine *h);
 gh_status gh_f64_set_positions_f32(gh_engine *h, const float *pos);
 gh_status gh_f64_get_positions_f32(gh_engine *h, float *pos);
 gh_status gh_f64_step(gh_engine *h, const int32_t *sampled);
@@ -296,7 +331,6 @@ gh_status gh_grid_search(gh_engine *h);            // d_mid + tau -> candidate l
 // ivf.hip
 bool gh_ivf_path(const gh_engine *h);
 gh_status gh_ivf_alloc(gh_engine *h);
-void gh_ivf_free(gh_engine *h);
 gh_status gh_ivf_search(gh_engine *h);             // d_mid + query records -> tau and candidate lists (probed lists only)
 // fused.hip
 gh_status gh_radial_topk_device(gh_engine *h, int K, uint64_t *d_part, int nparts, int32_t *d_ids);

@@ -36,26 +36,27 @@
 #include <vector>
 
 struct gh_f64 {
-    double *pos = nullptr, *nw = nullptr, *Fs = nullptr, *Fi = nullptr, *mid = nullptr, *io = nullptr;
-    double2 *pos4 = nullptr;      // (n, 2) double2 = (n, 4) doubles: the positions with 32-byte rows (2..4 components; rebuilt every step)
-    double *part = nullptr;       // (blocks, D) partial sums of the reductions
-    double *colstat = nullptr;    // (2, D): mean, std + 1e-6
-    int32_t *rowptr = nullptr, *adj = nullptr, *edges = nullptr, *sampled = nullptr, *knn = nullptr;
-    int32_t *fail = nullptr;      // a query whose boundary ties exceeded the pass-2 buffer (never seen; reported)
+    gh_dev<double> pos, nw, Fs, Fi, mid, io;
+    gh_dev<double2> pos4;         // (n, 2) double2 = (n, 4) doubles: the positions with 32-byte rows (2..4 components; rebuilt every step)
+    gh_dev<double> part;          // (blocks, D) partial sums of the reductions
+    gh_dev<double> colstat;       // (2, D): mean, std + 1e-6
+    gh_dev<int32_t> rowptr, adj, edges, sampled, knn;
+    gh_dev<int32_t> fail;         // a query whose boundary ties exceeded the pass-2 buffer (never seen; reported)
     // filtered search (graphs from F64_FILTER_MIN_EDGES edges on): per query a bound from every `stride`-th midpoint, one
     // reference-major pass over all midpoints that parks what passes it, the exact ranking over the parked ones
     int64_t stride = 0;           // 0: the two full passes per query (small graphs)
-    double *sub = nullptr;        // (ceil(E / stride), D) every stride-th midpoint, contiguous (written beside mid)
-    gh_h8 *qA = nullptr;          // (S, 2) the queries' A-operand rows of the matrix-pipe pre-filter (2 or 3 components)
-    double *pmax = nullptr;       // (ceil(n / 256)) per-block maxima of |coordinate| over the positions (f64_pad4_kernel)
-    double *qaux = nullptr;       // (S, 2) sqrt of that bound (-1: the query takes the full passes), |q|: for the filter's fp32 pre-check
-    double *tq = nullptr;         // (S) exclusive bound on the double distance: the float above the K-th smallest rounded-down subset distance
-    int32_t *cnt = nullptr;       // (S * F64_CNT_STRIDE) parked midpoints per query, one counter per 128-byte line (may exceed F64_CAND_CAP: then that query takes the full passes)
-    double *cand_d = nullptr;     // (S, F64_CAND_CAP) their squared distances ...
-    int32_t *cand_i = nullptr;    // ... and edge ids
+    gh_dev<double> sub;           // (ceil(E / stride), D) every stride-th midpoint, contiguous (written beside mid)
+    gh_dev<gh_h8> qA;             // (S, 2) the queries' A-operand rows of the matrix-pipe pre-filter (2 or 3 components)
+    gh_dev<double> pmax;          // (ceil(n / 256)) per-block maxima of |coordinate| over the positions (f64_pad4_kernel)
+    gh_dev<double> qaux;          // (S, 2) sqrt of that bound (-1: the query takes the full passes), |q|: for the filter's fp32 pre-check
+    gh_dev<double> tq;            // (S) exclusive bound on the double distance: the float above the K-th smallest rounded-down subset distance
+    gh_dev<int32_t> cnt;          // (S * F64_CNT_STRIDE) parked midpoints per query, one counter per 128-byte line (may exceed F64_CAND_CAP: then that query takes the full passes)
+    gh_dev<double> cand_d;        // (S, F64_CAND_CAP) their squared distances ...
+    gh_dev<int32_t> cand_i;       // ... and edge ids
     int nblocks = 0;
     double L_min = 1.0, k_attr = 0.2, k_inter = 0.5;   // the constructor's constants as doubles (gh_params holds floats)
 };
+void gh_delete(gh_f64 *f) { delete f; }
 
 namespace {
 
@@ -742,62 +743,42 @@ __global__ void f64_to_f32_kernel(const double *__restrict__ src, int64_t count,
 
 inline unsigned f64_grid(int64_t total) { return (unsigned)((total + 255) / 256); }
 
-template <typename T>
-gh_status f64_alloc(gh_engine *h, T **p, size_t count) {
-    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        h->err = "hipMalloc failed (float64 engine)";
-        return GH_ERR_NOMEM;
-    }
-    return GH_OK;
-}
-
-void f64_free(gh_engine *h) {
-    gh_f64 *f = h->f64;
-    if (!f) return;
-    void *ptrs[] = {f->pos, f->nw, f->Fs, f->Fi, f->mid, f->io, f->part, f->colstat, f->rowptr, f->adj, f->edges, f->sampled, f->knn, f->fail,
-                    f->tq, f->cnt, f->cand_d, f->cand_i, f->sub, f->qaux, f->qA, f->pmax, f->pos4};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete f;
-    h->f64 = nullptr;
-}
-
 // (n, 4) copy of the positions for the gathering kernels (2..4 components)
 void f64_refresh_pos4(gh_engine *h) {
-    gh_f64 *f = h->f64;
-    if (f->pos4) f64_pad4_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos, h->n, h->D, f->pos4, f->pmax);
+    gh_f64 *f = h->f64.get();
+    if (f->pos4.p) f64_pad4_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos.p, h->n, h->D, f->pos4.p, f->pmax.p);
 }
 template <typename K2, typename K3, typename K4>
 void f64_by_dim(int D, K2 k2, K3 k3, K4 k4) { if (D == 2) k2(); else if (D == 3) k3(); else k4(); }
 
 gh_status f64_knn(gh_engine *h, const int32_t *host_ids, bool pos4_fresh = false) {
-    gh_f64 *f = h->f64;
+    gh_f64 *f = h->f64.get();
     if ((int64_t)h->K > h->E) { h->err = "selected index k out of range"; return GH_ERR_K_TOO_LARGE; }
     if (h->S >= h->E) {
-        f64_sample_kernel<<<dim3(f64_grid(h->S)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, 2, f->sampled);
+        f64_sample_kernel<<<dim3(f64_grid(h->S)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, 2, f->sampled.p);
     } else if (host_ids) {
         for (int64_t i = 0; i < h->S; ++i)
             if (host_ids[i] < 0 || host_ids[i] >= h->E) { h->err = "sampled edge id out of range"; return GH_ERR_INVALID; }
-        GH_HIP(hipMemcpyAsync(f->sampled, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
+        GH_HIP(hipMemcpyAsync(f->sampled.p, host_ids, sizeof(int32_t) * (size_t)h->S, hipMemcpyHostToDevice, h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
     } else {
-        f64_sample_kernel<<<dim3(f64_grid(h->S)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, 1, f->sampled);
+        f64_sample_kernel<<<dim3(f64_grid(h->S)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, 1, f->sampled.p);
     }
-    if (f->pos4) {
+    if (f->pos4.p) {
         if (!pos4_fresh) f64_refresh_pos4(h);
-#define F64_MID4(DD) f64_mid4_kernel<DD><<<dim3(f64_grid(h->E)), dim3(256), 0, h->stream>>>(f->pos4, f->edges, h->E, f->mid, std::max<int64_t>(f->stride, 1), f->stride > 0 ? f->sub : nullptr)
+#define F64_MID4(DD) f64_mid4_kernel<DD><<<dim3(f64_grid(h->E)), dim3(256), 0, h->stream>>>(f->pos4.p, f->edges.p, h->E, f->mid.p, std::max<int64_t>(f->stride, 1), f->stride > 0 ? f->sub.p : nullptr)
         f64_by_dim(h->D, [&] { F64_MID4(2); }, [&] { F64_MID4(3); }, [&] { F64_MID4(4); });
 #undef F64_MID4
     } else {
-        f64_mid_kernel<<<dim3(f64_grid(h->E * h->D)), dim3(256), 0, h->stream>>>(f->pos, f->edges, h->E, h->D, f->mid, f->stride, f->sub);
+        f64_mid_kernel<<<dim3(f64_grid(h->E * h->D)), dim3(256), 0, h->stream>>>(f->pos.p, f->edges.p, h->E, h->D, f->mid.p, f->stride, f->sub.p);
     }
     if (f->stride > 0) {
-        f64_knn_kernel<1><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid, h->E, h->D, f->sampled, h->K, f->knn, f->fail, f->stride, f->tq, f->cnt,
-                                                                             f->cand_d, f->cand_i, f->sub, f->qaux, (h->D == 2 || h->D == 3) ? f->qA : nullptr, f->pmax, (int)f64_grid(h->n));
+        f64_knn_kernel<1><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid.p, h->E, h->D, f->sampled.p, h->K, f->knn.p, f->fail.p, f->stride, f->tq.p, f->cnt.p,
+                                                                             f->cand_d.p, f->cand_i.p, f->sub.p, f->qaux.p, (h->D == 2 || h->D == 3) ? f->qA.p : nullptr, f->pmax.p, (int)f64_grid(h->n));
 #define F64_FILTER(DD, UU) f64_filter_kernel<DD, UU, (DD > 0 && UU % 2 == 0)><<<dim3((unsigned)((h->E + 256 * UU - 1) / (256 * UU))), dim3(256), 0, h->stream>>>( \
-        f->mid, h->E, h->D, f->sampled, h->S, f->tq, f->cnt, f->cand_d, f->cand_i)
+        f->mid.p, h->E, h->D, f->sampled.p, h->S, f->tq.p, f->cnt.p, f->cand_d.p, f->cand_i.p)
 #define F64_FILTER3(DD) f64_filter_mf_kernel<DD><<<dim3((unsigned)((h->E + 511) / 512)), dim3(256), 0, h->stream>>>( \
-        f->mid, h->E, f->sampled, (int)h->S, f->tq, f->qaux, f->qA, f->cnt, f->cand_d, f->cand_i)
+        f->mid.p, h->E, f->sampled.p, (int)h->S, f->tq.p, f->qaux.p, f->qA.p, f->cnt.p, f->cand_d.p, f->cand_i.p)
         switch (h->D) {
             case 2: F64_FILTER3(2); break;
             case 3: F64_FILTER3(3); break;
@@ -810,43 +791,43 @@ gh_status f64_knn(gh_engine *h, const int32_t *host_ids, bool pos4_fresh = false
         }
 #undef F64_FILTER
 #undef F64_FILTER3
-        f64_knn_kernel<2><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid, h->E, h->D, f->sampled, h->K, f->knn, f->fail, f->stride, f->tq, f->cnt,
-                                                                             f->cand_d, f->cand_i, nullptr);
+        f64_knn_kernel<2><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid.p, h->E, h->D, f->sampled.p, h->K, f->knn.p, f->fail.p, f->stride, f->tq.p, f->cnt.p,
+                                                                             f->cand_d.p, f->cand_i.p, nullptr);
     } else {
-        f64_knn_kernel<0><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid, h->E, h->D, f->sampled, h->K, f->knn, f->fail, 1, nullptr, nullptr,
+        f64_knn_kernel<0><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid.p, h->E, h->D, f->sampled.p, h->K, f->knn.p, f->fail.p, 1, nullptr, nullptr,
                                                                              nullptr, nullptr, nullptr);
     }
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
-// spring forces of the current positions -> f->Fs (refreshes the padded copy of the positions)
+// spring forces of the current positions -> f->Fs.p (refreshes the padded copy of the positions)
 void f64_launch_spring(gh_engine *h) {
-    gh_f64 *f = h->f64;
-    if (f->pos4) {
+    gh_f64 *f = h->f64.get();
+    if (f->pos4.p) {
         f64_refresh_pos4(h);
-#define F64_SPR4(DD) f64_spring4_kernel<DD><<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos4, f->rowptr, f->adj, h->n, f->L_min, -f->k_attr, f->Fs)
+#define F64_SPR4(DD) f64_spring4_kernel<DD><<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos4.p, f->rowptr.p, f->adj.p, h->n, f->L_min, -f->k_attr, f->Fs.p)
         f64_by_dim(h->D, [&] { F64_SPR4(2); }, [&] { F64_SPR4(3); }, [&] { F64_SPR4(4); });
 #undef F64_SPR4
     } else {
-        f64_spring_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos, h->D, f->rowptr, f->adj, h->n, f->L_min, -f->k_attr, f->Fs);
+        f64_spring_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos.p, h->D, f->rowptr.p, f->adj.p, h->n, f->L_min, -f->k_attr, f->Fs.p);
     }
 }
 
 gh_status f64_step(gh_engine *h, const int32_t *host_ids) {
-    gh_f64 *f = h->f64;
+    gh_f64 *f = h->f64.get();
     const size_t bytes = sizeof(double) * (size_t)h->n * h->D;
     f64_launch_spring(h);
-    GH_HIP(hipMemsetAsync(f->Fi, 0, bytes, h->stream));
+    GH_HIP(hipMemsetAsync(f->Fi.p, 0, bytes, h->stream));
     if (h->S > 0 && h->k > 0) {
         GH_TRY_ST(f64_knn(h, host_ids, true));
-        f64_intersect_kernel<<<dim3(f64_grid(h->S * h->k)), dim3(256), 0, h->stream>>>(f->pos, h->D, f->edges, f->sampled, f->knn, h->S, h->k,
-                                                                                      f->k_inter, f->Fi);
+        f64_intersect_kernel<<<dim3(f64_grid(h->S * h->k)), dim3(256), 0, h->stream>>>(f->pos.p, h->D, f->edges.p, f->sampled.p, f->knn.p, h->S, h->k,
+                                                                                      f->k_inter, f->Fi.p);
     }
     const int nb = f->nblocks;
-    f64_sum_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->pos, f->Fs, f->Fi, h->n, h->D, f->nw, f->part);
-    f64_centre_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->nw, h->n, h->D, f->part, nb, f->colstat, f->part + (size_t)nb * h->D);
-    f64_scale_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->nw, h->n, h->D, f->part + (size_t)nb * h->D, nb, f->colstat, f->pos);
+    f64_sum_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->pos.p, f->Fs.p, f->Fi.p, h->n, h->D, f->nw.p, f->part.p);
+    f64_centre_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->nw.p, h->n, h->D, f->part.p, nb, f->colstat.p, f->part.p + (size_t)nb * h->D);
+    f64_scale_kernel<<<dim3(nb), dim3(256), 0, h->stream>>>(f->nw.p, h->n, h->D, f->part.p + (size_t)nb * h->D, nb, f->colstat.p, f->pos.p);
     GH_LAUNCH_CHECK();
     h->iter += 1;
     return GH_OK;
@@ -861,15 +842,14 @@ gh_status f64_check(gh_engine *h) {
 
 }  // namespace
 
-void gh_f64_free(gh_engine *h) { f64_free(h); }
-
 extern "C" gh_status gh_create_f64(gh_handle *out, int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges, const gh_params *params,
                                    double L_min, double k_attr, double k_inter) {
     if (!out) return GH_ERR_INVALID;
     *out = nullptr;
     GH_TRY_ST(gh_check_create_args(device_id, n, D, E, edges, params, F64_MAXD, k_attr));
     auto fail = [&](gh_status st, const std::string &msg) { gh_set_create_error(msg); return st; };
-    gh_engine *h = new (std::nothrow) gh_engine();
+    std::unique_ptr<gh_engine> owner(new (std::nothrow) gh_engine());
+    gh_engine *h = owner.get();
     if (!h) return fail(GH_ERR_NOMEM, "out of host memory");
     h->device = device_id;
     h->n = n; h->E = E; h->D = D; h->LD = D;
@@ -878,13 +858,12 @@ extern "C" gh_status gh_create_f64(gh_handle *out, int device_id, int64_t n, int
     h->S = std::min<int64_t>(params->sample_size, E);
     h->part = gh_partition{0, n, 0, E, GH_EDGES_RANGE};
     h->rows = n;
-    auto bail = [&](gh_status st) { gh_set_create_error(h->err); f64_free(h); if (h->own_stream) (void)hipStreamDestroy(h->own_stream); delete h; return st; };
-    if (hipSetDevice(device_id) != hipSuccess) { h->err = "hipSetDevice failed"; return bail(GH_ERR_HIP); }
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(GH_ERR_HIP); }
+    if (hipSetDevice(device_id) != hipSuccess) return fail(GH_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(GH_ERR_HIP, "hipStreamCreate failed");
     h->stream = h->own_stream;
-    h->f64 = new (std::nothrow) gh_f64();
-    if (!h->f64) { h->err = "out of host memory"; return bail(GH_ERR_NOMEM); }
-    gh_f64 *f = h->f64;
+    h->f64.reset(new (std::nothrow) gh_f64());
+    if (!h->f64) return fail(GH_ERR_NOMEM, "out of host memory");
+    gh_f64 *f = h->f64.get();
     f->L_min = L_min; f->k_attr = k_attr; f->k_inter = k_inter;
     std::vector<int32_t> rowptr, adj;
     gh_pull_lists(n, E, edges, rowptr, adj);   // the reference's summation order (graph_plan.hip)
@@ -898,37 +877,36 @@ extern "C" gh_status gh_create_f64(gh_handle *out, int device_id, int64_t n, int
         f->nblocks = (int)nb;
     }
     gh_status st;
-    if ((st = f64_alloc(h, &f->pos, nD)) || (st = f64_alloc(h, &f->nw, nD)) || (st = f64_alloc(h, &f->Fs, nD)) || (st = f64_alloc(h, &f->Fi, nD)) ||
-        (st = f64_alloc(h, &f->io, nD)) || (st = f64_alloc(h, &f->mid, (size_t)E * D)) || (st = f64_alloc(h, &f->part, (size_t)2 * f->nblocks * D)) ||
-        (st = f64_alloc(h, &f->colstat, (size_t)2 * D)) || (st = f64_alloc(h, &f->rowptr, (size_t)n + 1)) || (st = f64_alloc(h, &f->adj, adj.size())) ||
-        (st = f64_alloc(h, &f->edges, (size_t)std::max<int64_t>(2 * E, 1))) || (st = f64_alloc(h, &f->sampled, (size_t)std::max<int64_t>(h->S, 1))) ||
-        (st = f64_alloc(h, &f->knn, (size_t)std::max<int64_t>(h->S * h->k, 1))) || (st = f64_alloc(h, &f->fail, 1)))
-        return bail(st);
+    if ((st = gh_alloc(h, f->pos, nD, false)) || (st = gh_alloc(h, f->nw, nD, false)) || (st = gh_alloc(h, f->Fs, nD, false)) || (st = gh_alloc(h, f->Fi, nD, false)) ||
+        (st = gh_alloc(h, f->io, nD, false)) || (st = gh_alloc(h, f->mid, (size_t)E * D, false)) || (st = gh_alloc(h, f->part, (size_t)2 * f->nblocks * D, false)) ||
+        (st = gh_alloc(h, f->colstat, (size_t)2 * D, false)) || (st = gh_alloc(h, f->rowptr, (size_t)n + 1, false)) || (st = gh_alloc(h, f->adj, adj.size(), false)) ||
+        (st = gh_alloc(h, f->edges, (size_t)std::max<int64_t>(2 * E, 1), false)) || (st = gh_alloc(h, f->sampled, (size_t)std::max<int64_t>(h->S, 1), false)) ||
+        (st = gh_alloc(h, f->knn, (size_t)std::max<int64_t>(h->S * h->k, 1), false)) || (st = gh_alloc(h, f->fail, 1, false)))
+        return fail(st, h->err);
     // the filtered search: from F64_FILTER_MIN_EDGES edges on, while the parked lists stay below 1 GiB.  stride: about 1024
     // parked midpoints per query (the subset's K-th smallest sits near rank K * stride of all; every parked midpoint is a
     // returning atomic on its query's counter)
     if (E >= F64_FILTER_MIN_EDGES && h->S > 0 && h->k > 0 && (size_t)h->S * F64_CAND_CAP * 12 <= ((size_t)1 << 30)) {
         f->stride = std::min<int64_t>(1024, std::max<int64_t>(16, 1024 / h->K));
-        if ((st = f64_alloc(h, &f->sub, (size_t)((E + f->stride - 1) / f->stride) * D)) || (st = f64_alloc(h, &f->tq, (size_t)h->S)) || (st = f64_alloc(h, &f->qaux, (size_t)2 * h->S)) || (st = f64_alloc(h, &f->qA, (size_t)2 * h->S)) ||  (st = f64_alloc(h, &f->cnt, (size_t)h->S * F64_CNT_STRIDE)) ||
-            (st = f64_alloc(h, &f->cand_d, (size_t)h->S * F64_CAND_CAP)) || (st = f64_alloc(h, &f->cand_i, (size_t)h->S * F64_CAND_CAP)))
-            return bail(st);
+        if ((st = gh_alloc(h, f->sub, (size_t)((E + f->stride - 1) / f->stride) * D, false)) || (st = gh_alloc(h, f->tq, (size_t)h->S, false)) || (st = gh_alloc(h, f->qaux, (size_t)2 * h->S, false)) || (st = gh_alloc(h, f->qA, (size_t)2 * h->S, false)) ||  (st = gh_alloc(h, f->cnt, (size_t)h->S * F64_CNT_STRIDE, false)) ||
+            (st = gh_alloc(h, f->cand_d, (size_t)h->S * F64_CAND_CAP, false)) || (st = gh_alloc(h, f->cand_i, (size_t)h->S * F64_CAND_CAP, false)))
+            return fail(st, h->err);
     }
-    if (D >= 2 && D <= 4 && ((st = f64_alloc(h, &f->pos4, (size_t)2 * n)) || (st = f64_alloc(h, &f->pmax, (size_t)f64_grid(n))))) return bail(st);
-    if (hipMemset(f->pos, 0, sizeof(double) * nD) != hipSuccess || hipMemset(f->fail, 0, sizeof(int32_t)) != hipSuccess ||
-        hipMemcpy(f->rowptr, rowptr.data(), sizeof(int32_t) * rowptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->adj, adj.data(), sizeof(int32_t) * (size_t)(2 * E), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->edges, edges, sizeof(int32_t) * (size_t)(2 * E), hipMemcpyHostToDevice) != hipSuccess) {
-        h->err = "upload of the graph failed";
-        return bail(GH_ERR_HIP);
+    if (D >= 2 && D <= 4 && ((st = gh_alloc(h, f->pos4, (size_t)2 * n, false)) || (st = gh_alloc(h, f->pmax, (size_t)f64_grid(n), false)))) return fail(st, h->err);
+    if (hipMemset(f->pos.p, 0, sizeof(double) * nD) != hipSuccess || hipMemset(f->fail.p, 0, sizeof(int32_t)) != hipSuccess ||
+        hipMemcpy(f->rowptr.p, rowptr.data(), sizeof(int32_t) * rowptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->adj.p, adj.data(), sizeof(int32_t) * (size_t)(2 * E), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->edges.p, edges, sizeof(int32_t) * (size_t)(2 * E), hipMemcpyHostToDevice) != hipSuccess) {
+        return fail(GH_ERR_HIP, "upload of the graph failed");
     }
-    *out = h;
+    *out = owner.release();
     return GH_OK;
 }
 
 extern "C" gh_status gh_set_positions_f64(gh_handle h, const double *pos) {
     GH_TRY_ST(f64_check(h));
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
-    GH_HIP(hipMemcpyAsync(h->f64->pos, pos, sizeof(double) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(h->f64->pos.p, pos, sizeof(double) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
@@ -936,10 +914,10 @@ static gh_status f64_download(gh_engine *h, const double *d_src, double *host) {
     GH_HIP(hipMemcpyAsync(host, d_src, sizeof(double) * (size_t)h->n * h->D, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     int32_t failed = 0;
-    GH_HIP(hipMemcpyAsync(&failed, h->f64->fail, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(&failed, h->f64->fail.p, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     if (failed) {   // reported once: the flag is cleared
-        GH_HIP(hipMemsetAsync(h->f64->fail, 0, sizeof(int32_t), h->stream));
+        GH_HIP(hipMemsetAsync(h->f64->fail.p, 0, sizeof(int32_t), h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
         h->err = "float64 KNN: more than 1024 midpoints share the float value of the K-th distance";
         return GH_ERR_RUNTIME;
@@ -949,23 +927,23 @@ static gh_status f64_download(gh_engine *h, const double *d_src, double *host) {
 extern "C" gh_status gh_get_positions_f64(gh_handle h, double *pos) {
     GH_TRY_ST(f64_check(h));
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
-    return f64_download(h, h->f64->pos, pos);
+    return f64_download(h, h->f64->pos.p, pos);
 }
-extern "C" double *gh_positions_device_f64(gh_handle h) { return h && h->f64 ? h->f64->pos : nullptr; }
+extern "C" double *gh_positions_device_f64(gh_handle h) { return h && h->f64 ? h->f64->pos.p : nullptr; }
 
 // float32 accessors of the common ABI on a float64 engine: converted on the way.
 gh_status gh_f64_set_positions_f32(gh_engine *h, const float *pos) {
     GH_TRY_ST(f64_check(h));
-    float *tmp = reinterpret_cast<float *>(h->f64->io);
+    float *tmp = reinterpret_cast<float *>(h->f64->io.p);
     GH_HIP(hipMemcpyAsync(tmp, pos, sizeof(float) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
-    f64_from_f32_kernel<<<dim3(f64_grid(h->n * h->D)), dim3(256), 0, h->stream>>>(tmp, h->n * h->D, h->f64->pos);
+    f64_from_f32_kernel<<<dim3(f64_grid(h->n * h->D)), dim3(256), 0, h->stream>>>(tmp, h->n * h->D, h->f64->pos.p);
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 gh_status gh_f64_get_positions_f32(gh_engine *h, float *pos) {
     GH_TRY_ST(f64_check(h));
-    float *tmp = reinterpret_cast<float *>(h->f64->io);
-    f64_to_f32_kernel<<<dim3(f64_grid(h->n * h->D)), dim3(256), 0, h->stream>>>(h->f64->pos, h->n * h->D, tmp);
+    float *tmp = reinterpret_cast<float *>(h->f64->io.p);
+    f64_to_f32_kernel<<<dim3(f64_grid(h->n * h->D)), dim3(256), 0, h->stream>>>(h->f64->pos.p, h->n * h->D, tmp);
     GH_HIP(hipMemcpyAsync(pos, tmp, sizeof(float) * (size_t)h->n * h->D, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
@@ -984,34 +962,34 @@ gh_status gh_f64_run(gh_engine *h, int32_t iters, const int32_t *sample_stream) 
 extern "C" gh_status gh_spring_forces_f64(gh_handle h, double *F) {
     GH_TRY_ST(f64_check(h));
     if (!F) { h->err = "F is NULL"; return GH_ERR_INVALID; }
-    gh_f64 *f = h->f64;
+    gh_f64 *f = h->f64.get();
     f64_launch_spring(h);
     GH_LAUNCH_CHECK();
-    return f64_download(h, f->Fs, F);
+    return f64_download(h, f->Fs.p, F);
 }
 gh_status gh_f64_knn_midpoints(gh_engine *h, const int32_t *sampled, int32_t *knn) {
     GH_TRY_ST(f64_check(h));
     if (!sampled && h->S < h->E) { h->err = "sampled is NULL"; return GH_ERR_INVALID; }
     GH_TRY_ST(f64_knn(h, sampled));
-    GH_HIP(hipMemcpyAsync(knn, h->f64->knn, sizeof(int32_t) * (size_t)h->S * h->k, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(knn, h->f64->knn.p, sizeof(int32_t) * (size_t)h->S * h->k, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 extern "C" gh_status gh_intersection_forces_f64(gh_handle h, const int32_t *sampled, const int32_t *knn, double *F) {
     GH_TRY_ST(f64_check(h));
     if (!knn || !F || (!sampled && h->S < h->E)) { h->err = "NULL argument"; return GH_ERR_INVALID; }
-    gh_f64 *f = h->f64;
+    gh_f64 *f = h->f64.get();
     for (int64_t i = 0; i < h->S * h->k; ++i)
         if (knn[i] < 0 || knn[i] >= h->E) { h->err = "neighbour edge id out of range"; return GH_ERR_INVALID; }
     std::vector<int32_t> ids((size_t)h->S);
     for (int64_t i = 0; i < h->S; ++i) ids[(size_t)i] = h->S >= h->E ? (int32_t)i : sampled[i];
     // the engine's stream is non-blocking and a run may still be in flight on it, reading and writing these buffers:
     // everything goes through that stream (the host arrays are done with at the synchronisation of f64_download)
-    GH_HIP(hipMemcpyAsync(f->sampled, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, h->stream));
-    GH_HIP(hipMemcpyAsync(f->knn, knn, sizeof(int32_t) * (size_t)h->S * h->k, hipMemcpyHostToDevice, h->stream));
-    GH_HIP(hipMemsetAsync(f->Fi, 0, sizeof(double) * (size_t)h->n * h->D, h->stream));
-    f64_intersect_kernel<<<dim3(f64_grid(h->S * h->k)), dim3(256), 0, h->stream>>>(f->pos, h->D, f->edges, f->sampled, f->knn, h->S, h->k,
-                                                                                  f->k_inter, f->Fi);
+    GH_HIP(hipMemcpyAsync(f->sampled.p, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(f->knn.p, knn, sizeof(int32_t) * (size_t)h->S * h->k, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemsetAsync(f->Fi.p, 0, sizeof(double) * (size_t)h->n * h->D, h->stream));
+    f64_intersect_kernel<<<dim3(f64_grid(h->S * h->k)), dim3(256), 0, h->stream>>>(f->pos.p, h->D, f->edges.p, f->sampled.p, f->knn.p, h->S, h->k,
+                                                                                  f->k_inter, f->Fi.p);
     GH_LAUNCH_CHECK();
-    return f64_download(h, f->Fi, F);
+    return f64_download(h, f->Fi.p, F);
 }

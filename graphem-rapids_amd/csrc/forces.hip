@@ -679,8 +679,8 @@ gh_status launch_spring(gh_engine *h, float *outF, int64_t f_row0) {
     const unsigned grid = grid_for(h->rows, 256);
     const float neg_k = -h->prm.k_attr;
     const gh_long_args la = gh_make_long_args(h);
-#define GH_SPRING_ARGS h->d_pos, h->d_rowptr, h->d_adj, h->d_first_edge, h->mid_base, h->part.row_lo, h->rows, \
-                       h->prm.L_min, neg_k, outF, f_row0, h->d_mid, la
+#define GH_SPRING_ARGS h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->mid_base, h->part.row_lo, h->rows, \
+                       h->prm.L_min, neg_k, outF, f_row0, h->d_mid.p, la
 #define GH_SPRING_CASE(DD, LL)                                                                              \
     if (la.n > 0) spring_kernel<DD, LL, WRITE_MID, true><<<dim3(grid), dim3(256), 0, h->stream>>>(GH_SPRING_ARGS); \
     else spring_kernel<DD, LL, WRITE_MID, false><<<dim3(grid), dim3(256), 0, h->stream>>>(GH_SPRING_ARGS)
@@ -690,8 +690,8 @@ gh_status launch_spring(gh_engine *h, float *outF, int64_t f_row0) {
         GH_FOR_EACH_DIM(GH_SPRING_ONE)
         default:
             spring_generic_kernel<<<dim3(grid), dim3(256), 0, h->stream>>>(
-                h->d_pos, h->D, h->LD, h->d_rowptr, h->d_adj, h->part.row_lo, h->rows, h->prm.L_min, neg_k, outF,
-                f_row0, h->d_tmpF2);
+                h->d_pos.p, h->D, h->LD, h->d_rowptr.p, h->d_adj.p, h->part.row_lo, h->rows, h->prm.L_min, neg_k, outF,
+                f_row0, h->d_tmpF2.p);
     }
 #undef GH_SPRING_ONE
 #undef GH_SPRING_CASE
@@ -706,9 +706,9 @@ static bool spring_is_templated_d(int D) { return gh_dim_templated(D); }
 
 gh_long_args gh_make_long_args(const gh_engine *h, bool coop_mid) {
     if (h->nlong == 0 || !spring_is_templated_d(h->D)) return gh_long_args{nullptr, nullptr, nullptr, 0, h->long_deg, nullptr, nullptr, nullptr};
-    const bool coop = coop_mid && h->d_own_long && h->d_own_eids;
-    return gh_long_args{h->d_long_rows, h->d_long_ownptr, h->d_long_ownadj, h->nlong, h->long_deg,
-                        coop ? h->d_own_long : nullptr, h->d_own_eids, h->d_edges};
+    const bool coop = coop_mid && h->d_own_long.p && h->d_own_eids.p;
+    return gh_long_args{h->d_long_rows.p, h->d_long_ownptr.p, h->d_long_ownadj.p, h->nlong, h->long_deg,
+                        coop ? h->d_own_long.p : nullptr, h->d_own_eids.p, h->d_edges.p};
 }
 
 // Spring forces of the long own rows -> outF rows (i + f_row0); no-op for graphs without hubs.
@@ -781,7 +781,7 @@ gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0) {
 #define GH_LONG_FUSED(DD, LL)                                                                                                 \
     case DD:                                                                                                                  \
         long_rows_kernel<DD, LL><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(                                \
-            h->d_pos, h->d_rowptr, h->d_adj, la.rows, h->d_long_eptr, la.n, h->part.row_lo, h->prm.L_min, neg_k, outF, f_row0); \
+            h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, la.n, h->part.row_lo, h->prm.L_min, neg_k, outF, f_row0); \
         break;
         switch (h->D) {
             GH_FOR_EACH_DIM(GH_LONG_FUSED)
@@ -793,10 +793,10 @@ gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0) {
     }
 #define GH_LONG_CASE(DD, LL)                                                                                          \
     long_terms_kernel<DD, LL><<<dim3(grid_for(h->long_entries, 256)), dim3(256), 0, h->stream>>>(                       \
-        h->d_pos, h->d_rowptr, h->d_adj, la.rows, h->d_long_eptr, h->d_long_erow, (int)h->long_entries, h->part.row_lo,     \
-        h->prm.L_min, neg_k, h->d_long_terms);                                                                          \
-    long_sum_kernel<DD, LL><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(h->d_long_terms, la.rows,   \
-                                                                                          h->d_long_eptr, la.n, outF, f_row0)
+        h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, h->d_long_erow.p, (int)h->long_entries, h->part.row_lo, \
+        h->prm.L_min, neg_k, h->d_long_terms.p);                                                                        \
+    long_sum_kernel<DD, LL><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(h->d_long_terms.p, la.rows, \
+                                                                                          h->d_long_eptr.p, la.n, outF, f_row0)
 #define GH_LONG_ONE(DD, LL) case DD: GH_LONG_CASE(DD, LL); break;
     switch (h->D) {
         GH_FOR_EACH_DIM(GH_LONG_ONE)
@@ -815,7 +815,7 @@ gh_status launch_mid_gather(gh_engine *h) {
     if (M == 0) return GH_OK;
     gh_scope t(h, "mid_gather");
     mid_gather_kernel<<<dim3(grid_for(M * h->LD, 256)), dim3(256), 0, h->stream>>>(
-        h->d_pos, h->d_edges, h->part.edge_lo, h->d_own_eids, M, h->D, h->LD, h->d_mid);
+        h->d_pos.p, h->d_edges.p, h->part.edge_lo, h->d_own_eids.p, M, h->D, h->LD, h->d_mid.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -827,7 +827,7 @@ gh_status gh_launch_spring_mid(gh_engine *h) {
     const bool fused = h->fused_mid && spring_is_templated(h->D);
     if (h->rows > 0) {
         gh_scope t(h, fused ? "spring_mid" : "spring");
-        gh_status st = fused ? launch_spring<true>(h, h->d_Fs, 0) : launch_spring<false>(h, h->d_Fs, 0);
+        gh_status st = fused ? launch_spring<true>(h, h->d_Fs.p, 0) : launch_spring<false>(h, h->d_Fs.p, 0);
         if (st) return st;
     }
     if (!fused) return launch_mid_gather(h);
@@ -845,7 +845,7 @@ gh_status gh_launch_integrate(gh_engine *h) {
         const struct reset_flag { gh_engine *e; ~reset_flag() { e->stats_reduced = false; } } reset{h};
 #define GH_FIX_CASE(LL)                                                                                      \
     stats_fix_kernel<LL><<<dim3(gh_fix_blocks(LL)), dim3(256), 0, h->stream>>>(                                  \
-        h->d_blockstats, h->n_vblocks, h->d_pos, h->d_Fs, h->d_acc, h->d_touched, h->d_tcount, h->part.row_lo, \
+        h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo, \
         h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
         h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap)
         if (h->LD == 4) GH_FIX_CASE(4);
@@ -873,26 +873,26 @@ gh_status gh_launch_integrate(gh_engine *h) {
         gh_scope t(h, "integrate");
         switch (h->LD) {
             case 4:
-                integrate_kernel<4><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos, h->d_Fs, h->part.row_lo, h->rows,
-                                                                            h->d_acc, h->d_tflag, h->d_new, h->d_blockstats, pc, pr, pcap);
+                integrate_kernel<4><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
+                                                                            h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
                 break;
             case 8:
-                integrate_kernel<8><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos, h->d_Fs, h->part.row_lo, h->rows,
-                                                                            h->d_acc, h->d_tflag, h->d_new, h->d_blockstats, pc, pr, pcap);
+                integrate_kernel<8><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
+                                                                            h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
                 break;
             case 16:
-                integrate_kernel<16><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos, h->d_Fs, h->part.row_lo, h->rows,
-                                                                             h->d_acc, h->d_tflag, h->d_new, h->d_blockstats, pc, pr, pcap);
+                integrate_kernel<16><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
+                                                                             h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
                 break;
             default:
                 integrate_generic_kernel<<<dim3(grid_for(h->rows * h->LD, 256)), dim3(256), 0, h->stream>>>(
-                    h->d_pos, h->d_Fs, h->LD, h->part.row_lo, h->rows, h->d_acc, h->d_tflag, wide_out);
+                    h->d_pos.p, h->d_Fs.p, h->LD, h->part.row_lo, h->rows, h->d_acc.p, h->d_tflag.p, wide_out);
         }
         GH_LAUNCH_CHECK();
     }
     gh_scope t(h, "stats_reduce");
     if (h->LD <= 16) {
-        stats_reduce_kernel<<<dim3(2 * h->LD), dim3(256), 0, h->stream>>>(h->d_blockstats, h->nblocks_update, h->LD,
+        stats_reduce_kernel<<<dim3(2 * h->LD), dim3(256), 0, h->stream>>>(h->d_blockstats.p, h->nblocks_update, h->LD,
                                                                           h->d_stats);
     } else {
         column_stats_kernel<<<dim3(h->D), dim3(256), 0, h->stream>>>(wide_out, h->rows, h->D, h->LD, h->d_stats);
@@ -918,15 +918,15 @@ gh_status gh_launch_intersect(gh_engine *h) {
 #define GH_INTER_ONE(DD, LL)                                                                                       \
     case DD:                                                                                                       \
         intersect_kernel<DD><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(                                   \
-            h->d_pos, h->D, h->LD, h->d_edges, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc, \
-            h->d_tflag, h->d_touched, h->d_tcount, h->d_iscratch, own_lo, own_hi);                                 \
+            h->d_pos.p, h->D, h->LD, h->d_edges.p, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc.p, \
+            h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p, own_lo, own_hi);                         \
         break;
     switch (h->D) {
         GH_FOR_EACH_DIM(GH_INTER_ONE)
         default:
             intersect_kernel<0><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(
-                h->d_pos, h->D, h->LD, h->d_edges, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc,
-                h->d_tflag, h->d_touched, h->d_tcount, h->d_iscratch, own_lo, own_hi);
+                h->d_pos.p, h->D, h->LD, h->d_edges.p, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc.p,
+                h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p, own_lo, own_hi);
     }
 #undef GH_INTER_ONE
     GH_LAUNCH_CHECK();
@@ -937,7 +937,7 @@ gh_status gh_launch_inter_to_dense(gh_engine *h, float *d_F) {
     GH_HIP(hipMemsetAsync(d_F, 0, sizeof(float) * h->n * h->LD, h->stream));
     const int64_t maxT = 4 * h->S * h->k * h->LD;
     if (maxT == 0) return GH_OK;
-    inter_to_dense_kernel<<<dim3(grid_for(maxT, 256)), dim3(256), 0, h->stream>>>(h->d_acc, h->d_touched, h->d_tcount,
+    inter_to_dense_kernel<<<dim3(grid_for(maxT, 256)), dim3(256), 0, h->stream>>>(h->d_acc.p, h->d_touched.p, h->d_tcount.p,
                                                                                   h->LD, d_F);
     GH_LAUNCH_CHECK();
     return GH_OK;
@@ -947,9 +947,9 @@ gh_status gh_launch_inter_cleanup(gh_engine *h) {
     const int64_t maxT = 4 * h->S * h->k * h->LD;
     if (maxT == 0) return GH_OK;
     gh_scope t(h, "inter_cleanup");
-    inter_cleanup_kernel<<<dim3(grid_for(maxT, 256)), dim3(256), 0, h->stream>>>(h->d_acc, h->d_tflag, h->d_touched,
-                                                                                 h->d_tcount, h->LD);
-    reset_counter_kernel<<<dim3(1), dim3(1), 0, h->stream>>>(h->d_tcount);
+    inter_cleanup_kernel<<<dim3(grid_for(maxT, 256)), dim3(256), 0, h->stream>>>(h->d_acc.p, h->d_tflag.p, h->d_touched.p,
+                                                                                 h->d_tcount.p, h->LD);
+    reset_counter_kernel<<<dim3(1), dim3(1), 0, h->stream>>>(h->d_tcount.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -958,7 +958,7 @@ gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float
     GH_HIP(hipMemsetAsync(h->d_stats, 0, sizeof(double) * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD, h->stream));
     // whole graph on one rank only (per-phase entry point)
     const int64_t total = h->n * h->LD;
-    integrate_given_kernel<<<dim3(grid_for(total, 256)), dim3(256), 0, h->stream>>>(h->d_pos, d_Fs, d_Fi, total,
+    integrate_given_kernel<<<dim3(grid_for(total, 256)), dim3(256), 0, h->stream>>>(h->d_pos.p, d_Fs, d_Fi, total,
                                                                                     h->d_new);
     column_stats_kernel<<<dim3(h->D), dim3(256), 0, h->stream>>>(h->d_new, h->n, h->D, h->LD, h->d_stats);
     GH_LAUNCH_CHECK();
@@ -979,13 +979,13 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
     if (gathered) {   // form B: both halves of the gathered slots; form D: the early-gathered rows (packed or not) and the
                       // late-gathered statistics
         const bool overlap = h->layout == GH_LAYOUT_OVERLAP;
-        src.RS = overlap && h->d_rows_pk ? h->D : h->LD;
-        src.rows = overlap ? (h->d_rows_pk ? h->d_rows_pk : h->d_rows_all) : reinterpret_cast<const float *>(h->d_gbuf);
+        src.RS = overlap && h->d_rows_pk.p ? h->D : h->LD;
+        src.rows = overlap ? (h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p) : reinterpret_cast<const float *>(h->d_gbuf.p);
         src.chunk = std::min(h->g_chunk, h->n);
         src.block = overlap ? h->g_chunk * src.RS : h->g_slot / (int64_t)sizeof(float);
         src.out_lo = 0;
         src.out_rows = h->n;
-        src.stats = overlap ? h->d_stats_all : reinterpret_cast<const double *>(h->d_gbuf + h->g_chunk * h->LD * (int64_t)sizeof(float));
+        src.stats = overlap ? h->d_stats_all.p : reinterpret_cast<const double *>(h->d_gbuf.p + h->g_chunk * h->LD * (int64_t)sizeof(float));
         src.world = h->g_world;
         src.stats_block = overlap ? h->stats_block : h->g_slot / (int64_t)sizeof(double);
         if (!(h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup)) next = nullptr;
@@ -1001,13 +1001,13 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
         extra = gh_setup_blocks(sa);
     }
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
-    float *packed = stats_all && h->packed_exchange ? h->d_rows_packed + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
+    float *packed = stats_all && h->packed_exchange ? h->d_rows_packed.p + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
     const int ldt = stats_all ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
 #define GH_NORM(LL)                                                                                                      \
     normalise_kernel<LL><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(                                                 \
-        src, h->D, h->LD, h->n, h->d_pos, with_cleanup ? h->d_acc : nullptr, h->d_tflag, h->d_touched, h->d_tcount,           \
-        gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact,                                                        \
-        h->d_stamps ? h->d_stamps + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed)
+        src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p, \
+        gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,                                                      \
+        h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed)
     if (ldt == 4) GH_NORM(4);
     else if (ldt == 8) GH_NORM(8);
     else if (ldt == 16) GH_NORM(16);
@@ -1035,8 +1035,8 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const float *__restric
 gh_status gh_launch_unpack_rows(gh_engine *h) {
     if (!h->packed_exchange) return GH_OK;
     gh_scope t(h, "unpack_rows");
-    unpack_rows_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_rows_packed, h->n, h->D, h->LD, h->part.row_lo,
-                                                                                       h->part.row_hi, h->d_pos);
+    unpack_rows_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_rows_packed.p, h->n, h->D, h->LD, h->part.row_lo,
+                                                                                       h->part.row_hi, h->d_pos.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -1052,16 +1052,16 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict_
 gh_status gh_launch_new0(gh_engine *h) {
     if (h->rows == 0) return GH_OK;
     gh_scope t(h, "new0");
-    new0_kernel<<<dim3(grid_for(h->rows * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_pos, h->d_Fs, h->part.row_lo, h->rows * h->LD, h->LD, h->d_new);
+    new0_kernel<<<dim3(grid_for(h->rows * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows * h->LD, h->LD, h->d_new);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 gh_status gh_launch_pack_rows(gh_engine *h, hipStream_t stream) {
-    if (!h->d_rows_pk || h->rows == 0) return GH_OK;
+    if (!h->d_rows_pk.p || h->rows == 0) return GH_OK;
     gh_scope t(h, "pack_rows", stream);
     // (chunk rows, not only the real ones: the block of a rank with fewer rows must not travel with stale bytes)
     pack_rows_kernel<<<dim3(grid_for(h->g_chunk * h->D, 256)), dim3(256), 0, stream>>>(h->d_new, h->g_chunk, h->D, h->LD,
-                                                                                        h->d_rows_pk + (size_t)h->g_rank * h->g_chunk * h->D);
+                                                                                        h->d_rows_pk.p + (size_t)h->g_rank * h->g_chunk * h->D);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -1097,33 +1097,33 @@ gh_status gh_launch_patch_rows(gh_engine *h) {
     if (grid > 64) grid = 64;
     const int stat_doubles = (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
     patch_rows_kernel<<<dim3(grid, (unsigned)h->g_world), dim3(256), 0, h->stream>>>(
-        h->d_rows_pk ? h->d_rows_pk : h->d_rows_all, h->d_rows_pk ? h->D : h->LD, h->D, h->LD, h->d_stats_all, h->stats_block, stat_doubles,
-        h->g_rank, (int)h->patch_cap, (int)(h->iter & 1), h->d_acc, h->d_tflag, h->d_touched, h->d_tcount);
+        h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p, h->d_rows_pk.p ? h->D : h->LD, h->D, h->LD, h->d_stats_all.p, h->stats_block, stat_doubles,
+        h->g_rank, (int)h->patch_cap, (int)(h->iter & 1), h->d_acc.p, h->d_tflag.p, h->d_touched.p, h->d_tcount.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
 gh_status gh_launch_pad(gh_engine *h, const float *d_src_nD, float *d_dst_nLD) {
-    pad_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(d_src_nD, h->n, h->D, h->LD, h->d_order, d_dst_nLD);
+    pad_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(d_src_nD, h->n, h->D, h->LD, h->d_order.p, d_dst_nLD);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
 gh_status gh_launch_unpad(gh_engine *h, const float *d_src_nLD, float *d_dst_nD) {
-    unpad_kernel<<<dim3(grid_for(h->n * h->D, 256)), dim3(256), 0, h->stream>>>(d_src_nLD, h->n, h->D, h->LD, h->d_order, d_dst_nD);
+    unpad_kernel<<<dim3(grid_for(h->n * h->D, 256)), dim3(256), 0, h->stream>>>(d_src_nLD, h->n, h->D, h->LD, h->d_order.p, d_dst_nD);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
 gh_status gh_launch_sample(gh_engine *h) {
     gh_scope t(h, "sample");
-    sample_kernel<<<dim3(grid_for(h->S, 256)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, h->d_sampled);
+    sample_kernel<<<dim3(grid_for(h->S, 256)), dim3(256), 0, h->stream>>>(h->E, h->S, h->prm.seed, h->iter, h->d_sampled.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
 gh_status gh_launch_arange(gh_engine *h) {
-    arange_kernel<<<dim3(grid_for(h->S, 256)), dim3(256), 0, h->stream>>>(h->S, h->d_sampled);
+    arange_kernel<<<dim3(grid_for(h->S, 256)), dim3(256), 0, h->stream>>>(h->S, h->d_sampled.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -1139,18 +1139,18 @@ gh_status gh_ensure_sample(gh_engine *h) {
 extern "C" gh_status gh_selftest_arith(int device_id, uint64_t seed, int64_t samples, int64_t *bad_sqrt, int64_t *bad_div) {
     if (!bad_sqrt || !bad_div || samples < 0) return GH_ERR_INVALID;
     if (hipSetDevice(device_id) != hipSuccess) return GH_ERR_HIP;
-    unsigned long long *d_bad = nullptr, host[2] = {0, 0};
-    if (hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(host)) != hipSuccess) return GH_ERR_NOMEM;
+    unsigned long long host[2] = {0, 0};
+    gh_dev<unsigned long long> d_bad;
+    if (!d_bad.alloc(sizeof(host))) return GH_ERR_NOMEM;
     gh_status st = GH_OK;
     const unsigned blocks = 4096;
     const int64_t per_thread = (samples + (int64_t)blocks * 256 - 1) / ((int64_t)blocks * 256);
-    if (hipMemset(d_bad, 0, sizeof(host)) != hipSuccess) st = GH_ERR_HIP;
+    if (hipMemset(d_bad.p, 0, sizeof(host)) != hipSuccess) st = GH_ERR_HIP;
     if (st == GH_OK) {
-        arith_selftest_kernel<<<dim3(blocks), dim3(256)>>>(seed, per_thread, d_bad);
+        arith_selftest_kernel<<<dim3(blocks), dim3(256)>>>(seed, per_thread, d_bad.p);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(host, d_bad, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) st = GH_ERR_HIP;
+            hipMemcpy(host, d_bad.p, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) st = GH_ERR_HIP;
     }
-    (void)hipFree(d_bad);
     *bad_sqrt = (int64_t)host[0];
     *bad_div = (int64_t)host[1];
     return st;

@@ -731,10 +731,10 @@ gh_tau_args fused_tau_args(gh_engine *h, int nt) {
     if (!h->tau_embedded) return ta;
     ta = gh_make_tau_args(h);
     ta.cdist = h->cdist ? 1 : 0;
-    ta.flag = h->d_tau_flag;          // zeroed by this iteration's set-up (setup_core.h), S once the producers are through
+    ta.flag = h->d_tau_flag.p;        // zeroed by this iteration's set-up (setup_core.h), S once the producers are through
     ta.target = (unsigned)h->S;
     ta.nblocks = gh_tau_blocks((int)h->S, nt);
-    ta.wait_failed = h->d_wait_failed;
+    ta.wait_failed = h->d_wait_failed.p;
     return ta;
 }
 
@@ -742,17 +742,17 @@ template <int D, int R, bool DEFER>
 void launch_mfma_d(gh_engine *h) {
     const gh_tau_args ta = fused_tau_args(h, 256);
     spring_scan_mfma_kernel<D, R, DEFER><<<dim3(fused_grid(h, ta)), dim3(256), 0, h->stream>>>(
-        h->d_pos, h->d_rowptr, h->d_adj, h->d_first_edge, h->d_own_eids, h->d_vblock, h->part.row_lo, h->prm.L_min,
-        -h->prm.k_attr, h->d_Fs, h->d_new, h->d_blockstats, h->d_q, reinterpret_cast<const gh_h8 *>(h->d_qA),
-        h->d_qexact, (int)h->S, h->d_cand, h->d_cnt, gh_make_long_args(h, true), ta, h->d_stamps);
+        h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min,
+        -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, reinterpret_cast<const gh_h8 *>(h->d_qA.p),
+        h->d_qexact.p, (int)h->S, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), ta, h->d_stamps.p);
 }
 template <int D>
 void launch_cells(gh_engine *h) {
     if (++h->qc_epoch == 0) h->qc_epoch = 1;   // (0 is the flag's value before the first launch)
     spring_scan_cells_kernel<D><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
-        h->d_pos, h->d_rowptr, h->d_adj, h->d_first_edge, h->d_own_eids, h->d_vblock, h->part.row_lo, h->prm.L_min,
-        -h->prm.k_attr, h->d_Fs, h->d_new, h->d_blockstats, h->d_q, (int)h->S, h->d_qcell, h->d_qc_flag, h->qc_epoch,
-        h->d_wait_failed, h->d_cand, h->d_cnt, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps);
+        h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min,
+        -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, (int)h->S, h->d_qcell.p, h->d_qc_flag.p, h->qc_epoch,
+        h->d_wait_failed.p, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps.p);
 }
 template <int D, int R>
 void launch_mfma(gh_engine *h) {
@@ -779,9 +779,9 @@ void launch_mfmaw_l(gh_engine *h) {
     }
     const gh_tau_args ta = fused_tau_args(h, 256);
     spring_scan_mfmaw_kernel<D, LD, LONG><<<dim3(fused_grid(h, ta), ny), dim3(256), 0, h->stream>>>(
-        h->d_pos, h->d_rowptr, h->d_adj, h->d_first_edge, h->d_own_eids, h->d_vblock, h->part.row_lo, h->prm.L_min, -h->prm.k_attr,
-        h->d_Fs, h->d_new, h->d_blockstats, h->d_q, h->d_qscan, (int)h->S,
-        h->d_cand, h->d_cnt, gh_make_long_args(h, true), ta, h->d_stamps);
+        h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min, -h->prm.k_attr,
+        h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, h->d_qscan.p, (int)h->S,
+        h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), ta, h->d_stamps.p);
 }
 template <int D, int LD>
 void launch_mfmaw(gh_engine *h) {
@@ -793,7 +793,7 @@ void launch_mfmaw(gh_engine *h) {
 
 gh_status gh_launch_spring_scan(gh_engine *h) {
     if (h->n_vblocks == 0) return GH_OK;
-    GH_TRY_ST(gh_launch_spring_long(h, h->d_Fs, 0));  // hubs first: their rows' forces are read back in phase A
+    GH_TRY_ST(gh_launch_spring_long(h, h->d_Fs.p, 0));  // hubs first: their rows' forces are read back in phase A
     gh_scope t(h, "spring_scan");
     if (fused_mfma(h->LD, h->D, h->S) && h->D > 3) {
         switch (h->D) {

@@ -347,34 +347,30 @@ gh_status gh_grid_alloc(gh_engine *h) {
     }
     h->grid_temp_bytes = temp;
     const size_t words = 4 * M + M + 16;   // keys, rows (in + out), edge ids, frame
-    if (hipMalloc(reinterpret_cast<void **>(&h->d_grid_u32), sizeof(uint32_t) * words) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&h->d_grid_smid), sizeof(float) * ((size_t)h->LD * M + 4)) != hipSuccess ||
-        hipMalloc(&h->d_grid_temp, temp + 16) != hipSuccess) {
-        h->err = "hipMalloc of the grid buffers failed";
-        return GH_ERR_NOMEM;
-    }
-    return GH_OK;
+    GH_TRY_ST(gh_alloc(h, h->d_grid_u32, words, false));
+    GH_TRY_ST(gh_alloc(h, h->d_grid_smid, (size_t)h->LD * M + 4, false));
+    return gh_alloc(h, h->d_grid_temp, temp + 16, false);
 }
 
 // d_mid (this iteration's own midpoints) + the query records -> tau of every query and its candidate list.
 gh_status gh_grid_search(gh_engine *h) {
     const int64_t M = h->own_count;
-    uint32_t *keys = h->d_grid_u32, *rows = keys + M, *skeys = rows + M, *srows = skeys + M;
+    uint32_t *keys = h->d_grid_u32.p, *rows = keys + M, *skeys = rows + M, *srows = skeys + M;
     uint32_t *sid = srows + M;
     grid_frame *frame = reinterpret_cast<grid_frame *>(sid + M);
-    float4 *smid = reinterpret_cast<float4 *>(h->d_grid_smid);
+    float4 *smid = reinterpret_cast<float4 *>(h->d_grid_smid.p);
     const unsigned gridM = (unsigned)((M + 255) / 256);
     const int QS = gh_qs(h->D, h->LD), LD4 = h->LD / 4;
     {
         gh_scope t(h, "grid_build");
-        grid_frame_kernel<<<dim3(1), dim3(256), 0, h->stream>>>(h->d_q, QS, h->S, std::min(h->D, 3), h->grid_G / 2, h->D >= 3 ? 23 - 4 : 23 - 7, frame,
-                                                                  h->tcount_reset_pending ? h->d_tcount : nullptr);
-        if (h->D == 2) grid_cell_kernel<2><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid, h->LD, M, frame, keys, rows);
-        else grid_cell_kernel<3><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid, h->LD, M, frame, keys, rows);
+        grid_frame_kernel<<<dim3(1), dim3(256), 0, h->stream>>>(h->d_q.p, QS, h->S, std::min(h->D, 3), h->grid_G / 2, h->D >= 3 ? 23 - 4 : 23 - 7, frame,
+                                                                  h->tcount_reset_pending ? h->d_tcount.p : nullptr);
+        if (h->D == 2) grid_cell_kernel<2><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
+        else grid_cell_kernel<3><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
         size_t temp = h->grid_temp_bytes;
-        GH_HIP(hipcub::DeviceRadixSort::SortPairs(h->d_grid_temp, temp, keys, skeys, rows, srows, (int)M, 0, h->grid_bits, h->stream));
-        grid_gather_kernel<<<dim3((unsigned)((M * LD4 + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid, LD4, srows, M, h->part.edge_lo,
-                                                                                               h->d_own_eids, smid, sid);
+        GH_HIP(hipcub::DeviceRadixSort::SortPairs(h->d_grid_temp.p, temp, keys, skeys, rows, srows, (int)M, 0, h->grid_bits, h->stream));
+        grid_gather_kernel<<<dim3((unsigned)((M * LD4 + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, LD4, srows, M, h->part.edge_lo,
+                                                                                               h->d_own_eids.p, smid, sid);
         GH_LAUNCH_CHECK();
     }
     gh_scope t(h, "grid_tau_scan");
@@ -382,9 +378,9 @@ gh_status gh_grid_search(gh_engine *h) {
     const dim3 sgrid((unsigned)h->S, h->S <= 2048 ? 32 : h->S <= 16384 ? 16 : 4);   // an outlier's box can hold the whole bulk: its runs over several workgroups
 #define GH_GRID_ONE(DD, LL)                                                                                                              \
     case DD:                                                                                                                              \
-        grid_tau_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(smid, skeys, (int)M, frame, h->d_q, h->K);                 \
-        grid_tau_fallback_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(1024), 0, h->stream>>>(smid, M, fb_stride, h->d_q, h->K);               \
-        grid_scan_kernel<DD, LL><<<sgrid, dim3(256), 0, h->stream>>>(smid, sid, skeys, (int)M, frame, h->d_q, h->d_cand, h->d_cnt);          \
+        grid_tau_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(smid, skeys, (int)M, frame, h->d_q.p, h->K);               \
+        grid_tau_fallback_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(1024), 0, h->stream>>>(smid, M, fb_stride, h->d_q.p, h->K);             \
+        grid_scan_kernel<DD, LL><<<sgrid, dim3(256), 0, h->stream>>>(smid, sid, skeys, (int)M, frame, h->d_q.p, h->d_cand.p, h->d_cnt.p);    \
         break;
     switch (h->D) {
         GH_FOR_EACH_DIM(GH_GRID_ONE)

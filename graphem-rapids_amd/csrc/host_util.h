@@ -1,4 +1,5 @@
-// Host plumbing shared by every handle behind the C ABI: the HIP-call checks, a device allocation that frees itself, the
+// Host plumbing shared by every handle behind the C ABI, the layout engine included: the HIP-call checks, gh_dev -- a device
+// allocation that frees itself, the type of every buffer a handle owns -- with the process-wide count of the live ones, the
 // life cycle of an analysis handle (device, stream, budget, message), the canonical edge set, and the level loop of a
 // breadth-first pass.  No kernel and no policy lives here.
 #pragma once
@@ -6,6 +7,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -36,20 +38,48 @@
         }                                                                                   \
     } while (0)
 
+// Live gh_dev allocations of the process and their bytes (gh_debug_live_allocations): what a test of the handles' life
+// cycles reads, since the card's free memory also moves with other processes.
+inline std::atomic<int64_t> gh_live_count{0}, gh_live_bytes{0};
+
 // A device allocation that frees itself.  Never smaller than 16 bytes, so an empty array still has an address to hand
-// to a kernel.  Moving it, also to a buffer of another element type, hands the allocation over.
+// to a kernel.  Moving it, also to a buffer of another element type, hands the allocation over (and counts it once).
+// No conversion to T *: a member of this type owns its memory, a raw pointer is a view of somebody else's.
 template <class T> struct gh_dev {
     T *p = nullptr;
+    size_t bytes = 0;   // as allocated
     gh_dev() = default;
     gh_dev(const gh_dev &) = delete;
     gh_dev &operator=(const gh_dev &) = delete;
-    template <class U> gh_dev(gh_dev<U> &&o) noexcept : p((T *)o.release()) {}
-    template <class U> gh_dev &operator=(gh_dev<U> &&o) noexcept { reset((T *)o.release()); return *this; }
+    template <class U> gh_dev(gh_dev<U> &&o) noexcept { take(o); }
+    template <class U> gh_dev &operator=(gh_dev<U> &&o) noexcept { take(o); return *this; }
     ~gh_dev() { reset(); }
-    T *release() { T *q = p; p = nullptr; return q; }
-    void reset(T *q = nullptr) { if (p) (void)hipFree(p); p = q; }
-    bool alloc(size_t bytes) { reset(); return hipMalloc((void **)&p, std::max<size_t>(bytes, 16)) == hipSuccess; }
+    void reset() {
+        if (p) { (void)hipFree(p); gh_live_count -= 1; gh_live_bytes -= (int64_t)bytes; }
+        p = nullptr;
+        bytes = 0;
+    }
+    bool alloc(size_t want) {
+        reset();
+        want = std::max<size_t>(want, 16);
+        if (hipMalloc((void **)&p, want) != hipSuccess) { p = nullptr; return false; }
+        bytes = want;
+        gh_live_count += 1;
+        gh_live_bytes += (int64_t)bytes;
+        return true;
+    }
     template <class U> U *as() const { return (U *)p; }
+
+private:
+    template <class U> void take(gh_dev<U> &o) {
+        T *q = (T *)o.p;
+        const size_t b = o.bytes;
+        o.p = nullptr;
+        o.bytes = 0;
+        reset();
+        p = q;
+        bytes = b;
+    }
 };
 
 // What every analysis handle (gh_ic, gh_cent, gh_gen, gh_corr) starts with.  device < 0: a host-path handle without a stream.

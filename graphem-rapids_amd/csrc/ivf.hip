@@ -51,7 +51,7 @@ struct gh_ivf {
     int64_t M = 0;                // own midpoints
     int64_t cap_rows = 0;         // rows of the list-ordered copy: M + C * GH_IVF_TILE (every list padded to whole tiles)
     int64_t max_tiles = 0;
-    unsigned char *blob = nullptr;
+    gh_dev<unsigned char> blob;   // the one allocation; what follows are views into it
     float *cent = nullptr;        // (C, LD) centroids, fp32
     uint4 *A = nullptr;           // (C, 2) f16 operand rows: -2 c, 8 halfs per lane half
     float *cnorm = nullptr;       // (C) |c|^2
@@ -804,17 +804,12 @@ bool gh_ivf_path(const gh_engine *h) {
            h->own_count >= 64 * 64 && h->own_count < ((int64_t)1 << 31) - (int64_t)GH_IVF_MAX_LISTS * GH_IVF_TILE;
 }
 
-void gh_ivf_free(gh_engine *h) {
-    if (!h->ivf) return;
-    if (h->ivf->blob) (void)hipFree(h->ivf->blob);
-    delete h->ivf;
-    h->ivf = nullptr;
-}
+void gh_delete(gh_ivf *v) { delete v; }
 
 gh_status gh_ivf_alloc(gh_engine *h) {
     if (!gh_ivf_path(h)) return GH_OK;
     gh_ivf *v = new gh_ivf();
-    h->ivf = v;
+    h->ivf.reset(v);
     const int64_t M = h->own_count;
     v->M = M;
     // lists: about sqrt(M) / 2, a multiple of 64, at least 64 members on average (the assignment costs M * C score
@@ -847,12 +842,9 @@ gh_status gh_ivf_alloc(gh_engine *h) {
                  o_sc = take(4 * C * GH_IVF_CSTRIDE), o_r2 = take(v->exact ? 4 * C * GH_IVF_CSTRIDE : 16), o_ss = take(4 * (size_t)v->awgs * C), o_lc = take(4 * C), o_ls = take(4 * (C + 1)), o_tl = take(4 * v->max_tiles), o_me = take(16),
                  o_lm = take(4 * v->cap_rows * LD), o_li = take(4 * v->cap_rows), o_lq = take(4 * C * GH_IVF_CSTRIDE), o_qs = take(4 * (C + 1)),
                  o_pl = take(4 * S * P), o_ps = take(4 * S * P), o_pq = take(4 * S * P);
-    if (hipMalloc(reinterpret_cast<void **>(&v->blob), off) != hipSuccess) {
-        h->err = "hipMalloc of the IVF buffers failed";
-        return GH_ERR_NOMEM;
-    }
-    if (hipMemset(v->blob, 0, off) != hipSuccess) { h->err = "hipMemset of the IVF buffers failed"; return GH_ERR_HIP; }
-    unsigned char *b = v->blob;
+    GH_TRY_ST(gh_alloc(h, v->blob, off, false));
+    if (hipMemset(v->blob.p, 0, off) != hipSuccess) { h->err = "hipMemset of the IVF buffers failed"; return GH_ERR_HIP; }
+    unsigned char *b = v->blob.p;
     v->cent = reinterpret_cast<float *>(b + o_cent);
     v->A = reinterpret_cast<uint4 *>(b + o_A);
     v->cnorm = reinterpret_cast<float *>(b + o_cn);
@@ -892,7 +884,7 @@ extern "C" gh_status gh_knn_ivf_config(gh_handle h, int32_t *lists, int32_t *pro
 
 // d_mid (this iteration's own midpoints) + the query records -> tau of every query and its candidate list.
 gh_status gh_ivf_search(gh_engine *h) {
-    gh_ivf *v = h->ivf;
+    gh_ivf *v = h->ivf.get();
     const int64_t M = v->M;
     const int C = v->C, P = v->P, QS = gh_qs(h->D, h->LD), S = (int)h->S;
     // members the threshold is taken from: the K-th smallest of an m-sample of the N probed members sits near rank K * N / m
@@ -911,7 +903,7 @@ gh_status gh_ivf_search(gh_engine *h) {
     {
         gh_scope t(h, "ivf_build");
         GH_HIP(hipMemsetAsync(v->lids, 0xFF, sizeof(uint32_t) * (size_t)v->cap_rows, h->stream));
-#define GH_X(L) ivf_centroid_kernel<L><<<dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid, M, C, v->cent, v->A, v->cnorm, v->count, v->lqcount, v->r2);
+#define GH_X(L) ivf_centroid_kernel<L><<<dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, C, v->cent, v->A, v->cnorm, v->count, v->lqcount, v->r2);
         GH_IVF_LD(GH_X)
 #undef GH_X
         GH_LAUNCH_CHECK();
@@ -921,7 +913,7 @@ gh_status gh_ivf_search(gh_engine *h) {
         const size_t lds = (size_t)C * 44;
 #define GH_X(L)                                                                                                                                  \
     if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_assign_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    ivf_assign_kernel<L><<<dim3((unsigned)v->awgs), dim3(256), lds, h->stream>>>(h->d_mid, M, v->share, C, v->A, v->cnorm, v->assign, v->rank, v->count, v->wgbase, v->r2);
+    ivf_assign_kernel<L><<<dim3((unsigned)v->awgs), dim3(256), lds, h->stream>>>(h->d_mid.p, M, v->share, C, v->A, v->cnorm, v->assign, v->rank, v->count, v->wgbase, v->r2);
         GH_IVF_LD(GH_X)
 #undef GH_X
         GH_LAUNCH_CHECK();
@@ -930,7 +922,7 @@ gh_status gh_ivf_search(gh_engine *h) {
         gh_scope t(h, "ivf_layout");
         ivf_list_layout_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(v->count, C, v->lcount, v->lstart, v->tile_list, v->meta);
         const int Q = h->LD / 4;
-#define GH_X(L) ivf_scatter_kernel<L><<<dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid, M, v->assign, v->rank, v->lstart, v->wgbase, v->share, C, h->part.edge_lo, h->d_own_eids, v->lmid, v->lids);
+#define GH_X(L) ivf_scatter_kernel<L><<<dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, v->assign, v->rank, v->lstart, v->wgbase, v->share, C, h->part.edge_lo, h->d_own_eids.p, v->lmid, v->lids);
         GH_IVF_LD(GH_X)
 #undef GH_X
         GH_LAUNCH_CHECK();
@@ -943,9 +935,9 @@ gh_status gh_ivf_search(gh_engine *h) {
 #define GH_PROBE2(L, NVv, EX)                                                                                                                         \
     {                                                                                                                                                 \
         if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_probe_kernel<L, NVv, EX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        ivf_probe_kernel<L, NVv, EX><<<dim3(pb), dim3(1024), lds, h->stream>>>(h->d_q, QS, S, h->D, v->A, v->cnorm, C, P, h->Ksel, v->lstart, v->lcount, v->lmid, \
+        ivf_probe_kernel<L, NVv, EX><<<dim3(pb), dim3(1024), lds, h->stream>>>(h->d_q.p, QS, S, h->D, v->A, v->cnorm, C, P, h->Ksel, v->lstart, v->lcount, v->lmid, \
                                                                               tau_members, v->r2, v->pair_l, v->pair_slot, v->lqcount,                \
-                                                                              reinterpret_cast<uint32_t *>(h->d_gmin), h->d_cnt);                    \
+                                                                              reinterpret_cast<uint32_t *>(h->d_gmin.p), h->d_cnt.p);                \
     }
 #define GH_PROBE(L, NVv)                      \
     if (v->exact) GH_PROBE2(L, NVv, true)     \
@@ -967,8 +959,8 @@ gh_status gh_ivf_search(gh_engine *h) {
     {
         gh_scope t(h, "ivf_scan");
         const dim3 grid((unsigned)v->max_tiles);
-#define GH_X(DD) ivf_scan_kernel<DD><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q, h->d_qscan, h->d_cand, h->d_cnt)
-#define GH_XM(DD, LL) ivf_scan_mfma_kernel<DD, LL><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q, h->d_qscan, h->d_cand, h->d_cnt)
+#define GH_X(DD) ivf_scan_kernel<DD><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p)
+#define GH_XM(DD, LL) ivf_scan_mfma_kernel<DD, LL><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p)
         if (h->D >= 4) {
             switch (h->D) {
                 case 4: GH_XM(4, 4); break;

@@ -443,7 +443,7 @@ void launch_scan(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, 
     if (qgroup > GH_SCAN_QGROUP) qgroup = GH_SCAN_QGROUP;
     groups = (int)((h->S + qgroup - 1) / qgroup);
     knn_scan_kernel<D, R><<<dim3((unsigned)tiles, (unsigned)groups), dim3(256), 0, h->stream>>>(
-        mid, h->part.edge_lo, h->d_own_eids, M, mem_stride, id_stride, h->d_q, h->d_qscan, (int)h->S, qgroup, h->d_cand, h->d_cnt,
+        mid, h->part.edge_lo, h->d_own_eids.p, M, mem_stride, id_stride, h->d_q.p, h->d_qscan.p, (int)h->S, qgroup, h->d_cand.p, h->d_cnt.p,
         h->cdist ? 1 : 0);
 }
 
@@ -461,15 +461,15 @@ void launch_scan_d(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride
 
 // mid == nullptr: gather the endpoints from positions instead (slow; the exact fallback only).
 search_args make_search_args(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, int64_t id_stride) {
-    return search_args{mid, h->d_pos, h->d_edges, h->d_own_eids, h->LD, h->D, h->part.edge_lo, M, mem_stride, id_stride,
-                       h->d_q, gh_qs(h->D, h->LD)};
+    return search_args{mid, h->d_pos.p, h->d_edges.p, h->d_own_eids.p, h->LD, h->D, h->part.edge_lo, M, mem_stride, id_stride,
+                       h->d_q.p, gh_qs(h->D, h->LD)};
 }
 
 // with_intersect only takes effect in the extraction kernel (K <= GH_EXTRACT_MAX_K).
 void launch_block_select(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, int64_t id_stride,
                          const int32_t *only_flagged, uint64_t *out_keys, bool write_tau, bool with_intersect) {
     const int QS = gh_qs(h->D, h->LD);
-    float *tau_out = write_tau ? h->d_q + gh_qtau(h->D, h->LD) : nullptr;
+    float *tau_out = write_tau ? h->d_q.p + gh_qtau(h->D, h->LD) : nullptr;
     if (h->K <= GH_EXTRACT_MAX_K) {
 #define GH_BSEL(DD)                                                                                             \
     knn_block_select_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>(       \
@@ -480,8 +480,8 @@ void launch_block_select(gh_engine *h, const float *mid, int64_t M, int64_t mem_
     } else {
         const size_t smem = sizeof(uint64_t) * GH_SEL_BUF + sizeof(float) * (size_t)h->LD;
         knn_block_select_sort_kernel<<<dim3((unsigned)h->S), dim3(256), smem, h->stream>>>(
-            mid, h->d_pos, h->d_edges, h->d_own_eids, h->LD, h->D, h->part.edge_lo, M,
-            mem_stride, id_stride, h->d_q, QS, h->K, only_flagged, out_keys, tau_out);
+            mid, h->d_pos.p, h->d_edges.p, h->d_own_eids.p, h->LD, h->D, h->part.edge_lo, M,
+            mem_stride, id_stride, h->d_q.p, QS, h->K, only_flagged, out_keys, tau_out);
     }
 }
 
@@ -521,29 +521,29 @@ gh_status launch_select(gh_engine *h, bool final_level, bool with_intersect, con
     bool wave_tq = false;
     if (wave) {
 #define GH_SELW(DD)                                                                                                      \
-    knn_select_wave_kernel<DD><<<dim3((unsigned)h->S), dim3(64), 0, h->stream>>>(h->d_cand, h->d_cnt, h->K, h->d_partial,   \
-                                                                                 h->d_dbg_cnt + (size_t)h->S, h->d_sel_redo, \
+    knn_select_wave_kernel<DD><<<dim3((unsigned)h->S), dim3(64), 0, h->stream>>>(h->d_cand.p, h->d_cnt.p, h->K, h->d_partial.p, \
+                                                                                 h->d_dbg_cnt.p + (size_t)h->S, h->d_sel_redo.p, \
                                                                                  iaw, (int)h->S)
         inter_args iaw = make_inter_args(h, with_intersect);
         wave_tq = with_intersect && h->k <= 127 && h->D >= 2 && h->LD <= 16;   // the lanes-per-coordinate form of the phase (intersect_query)
-        if (wave_tq) { iaw.tq_count = h->d_tq_count; iaw.tq_touched = h->d_tq_touched; }
+        if (wave_tq) { iaw.tq_count = h->d_tq_count.p; iaw.tq_touched = h->d_tq_touched.p; }
         if (with_intersect) { GH_DISPATCH_DIM(h->D, GH_SELW) } else { GH_SELW(0); }
 #undef GH_SELW
     }
 #define GH_SEL(DD)                                                                                                                          \
     knn_select_kernel<DD><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>( \
-        h->d_cand, h->d_cnt, h->K, final_level ? 1 : 0, h->d_q + gh_qtau(h->D, h->LD), gh_qs(h->D, h->LD),                                     \
-        h->d_partial, h->d_ovf, h->d_dbg_cnt + (size_t)(final_level ? 1 : 0) * h->S,                                                           \
+        h->d_cand.p, h->d_cnt.p, h->K, final_level ? 1 : 0, h->d_q.p + gh_qtau(h->D, h->LD), gh_qs(h->D, h->LD),                               \
+        h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + (size_t)(final_level ? 1 : 0) * h->S,                                                     \
         make_search_args(h, fb_mid, h->own_count, 1, 1), make_inter_args(h, with_intersect), (int)h->S,                                        \
-        h->d_blockstats, h->n_vblocks, h->d_stats, wave ? h->d_sel_redo : nullptr)
+        h->d_blockstats.p, h->n_vblocks, h->d_stats, wave ? h->d_sel_redo.p : nullptr)
     if (with_intersect) { GH_DISPATCH_DIM(h->D, GH_SEL) } else { GH_SEL(0); }
 #undef GH_SEL
     if (wave_tq) {
         const int k4 = 4 * h->k;
-        knn_touched_prefix_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(h->d_tq_count, (int)h->S, h->d_tq_base, h->d_tcount);
+        knn_touched_prefix_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(h->d_tq_count.p, (int)h->S, h->d_tq_base.p, h->d_tcount.p);
         knn_touched_copy_kernel<<<dim3((unsigned)(((int64_t)h->S * k4 + 255) / 256)), dim3(256), 0, h->stream>>>(
-            h->d_tq_count, h->d_tq_base, h->d_tq_touched, (int)h->S, k4, h->d_touched);
-        GH_HIP(hipMemsetAsync(h->d_tq_count, 0, sizeof(int32_t) * (size_t)h->S, h->stream));
+            h->d_tq_count.p, h->d_tq_base.p, h->d_tq_touched.p, (int)h->S, k4, h->d_touched.p);
+        GH_HIP(hipMemsetAsync(h->d_tq_count.p, 0, sizeof(int32_t) * (size_t)h->S, h->stream));
     }
     GH_LAUNCH_CHECK();
     h->stats_reduced = reduce;
@@ -572,9 +572,9 @@ void gh_choose_threshold_subset(gh_engine *h) {
 // threshold subset: one launch.
 gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter) {
     const int tiles = (int)((h->thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
-    return gh_setup_args{h->d_edges, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q, h->d_cnt,
-                         h->d_ovf, h->part.edge_lo, h->d_own_eids, reinterpret_cast<const int2 *>(h->d_sub_uv), h->thr_M1, h->thr_stride, h->d_gmin,
-                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag : nullptr};
+    return gh_setup_args{h->d_edges.p, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q.p, h->d_cnt.p,
+                         h->d_ovf.p, h->part.edge_lo, h->d_own_eids.p, reinterpret_cast<const int2 *>(h->d_sub_uv.p), h->thr_M1, h->thr_stride, h->d_gmin.p,
+                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag.p : nullptr};
 }
 
 // Workgroups of 256 threads a set-up takes (knn_setup_kernel, or the head of a normalise launch).
@@ -599,7 +599,7 @@ gh_status gh_knn_prepare(gh_engine *h) {
     if (done) return GH_OK;
     const gh_setup_args a = gh_make_setup_args(h, src, h->iter);
     gh_scope t(h, "knn_setup");
-    knn_setup_kernel<<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos, a, h->d_tcount, h->d_qexact);
+    knn_setup_kernel<<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos.p, a, h->d_tcount.p, h->d_qexact.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -608,19 +608,19 @@ gh_status gh_knn_prepare(gh_engine *h) {
 gh_tau_args gh_make_tau_args(gh_engine *h) {
     const gh_setup_args a = gh_make_setup_args(h, h->sample, h->iter);
     gh_tau_args t{};
-    t.gmin = reinterpret_cast<const uint32_t *>(h->d_gmin);
+    t.gmin = reinterpret_cast<const uint32_t *>(h->d_gmin.p);
     t.Gpad = a.Gpad;
     t.D = h->D;
     t.QS = gh_qs(h->D, h->LD);
     t.QT = gh_qtau(h->D, h->LD);
     t.K = h->Ksel;   // GH_DIST_CDIST: a bound for K + 1 neighbours (cdist.hip)
     t.S = (int)h->S;
-    t.qt = h->d_q;
-    t.qscan = h->d_qscan;
-    t.qA = reinterpret_cast<_Float16 *>(h->d_qA);
+    t.qt = h->d_q.p;
+    t.qscan = h->d_qscan.p;
+    t.qA = reinterpret_cast<_Float16 *>(h->d_qA.p);
     t.qA_kb = gh_fused_mfma_kb(h);   // -1: no MFMA form in use
-    t.qexact = h->d_qexact;
-    t.tcount_reset = h->tcount_reset_pending ? h->d_tcount : nullptr;
+    t.qexact = h->d_qexact.p;
+    t.tcount_reset = h->tcount_reset_pending ? h->d_tcount.p : nullptr;
     return t;
 }
 
@@ -647,7 +647,7 @@ gh_status gh_knn_thresholds(gh_engine *h, int64_t groups) {
 gh_status gh_knn_finish(gh_engine *h, bool have_mid, bool fuse_intersect) {
     if (h->cdist) return gh_knn_finish_cdist(h, false, fuse_intersect);   // the reference's cdist + topk rows (cdist.hip)
     const bool fuse = fuse_intersect && h->K <= GH_EXTRACT_MAX_K;
-    GH_TRY_ST(launch_select(h, true, fuse, have_mid ? h->d_mid : nullptr));
+    GH_TRY_ST(launch_select(h, true, fuse, have_mid ? h->d_mid.p : nullptr));
     h->intersect_done = fuse;
     return GH_OK;
 }
@@ -660,7 +660,7 @@ gh_status gh_knn_local(gh_engine *h, bool fuse_intersect) {
         if (h->cdist) return gh_knn_finish_cdist(h, true, false);   // every query against all edges (cdist.hip)
         const bool fuse = fuse_intersect && h->K <= GH_EXTRACT_MAX_K;
         gh_scope t(h, "knn_block_select");
-        launch_block_select(h, h->d_mid, Mtot, 1, 1, nullptr, h->d_partial, false, fuse);
+        launch_block_select(h, h->d_mid.p, Mtot, 1, 1, nullptr, h->d_partial.p, false, fuse);
         GH_LAUNCH_CHECK();
         h->intersect_done = fuse;
         return GH_OK;
@@ -668,7 +668,7 @@ gh_status gh_knn_local(gh_engine *h, bool fuse_intersect) {
     GH_TRY_ST(gh_knn_thresholds(h));
     {
         gh_scope t(h, "knn_scan");
-        launch_scan_d<8>(h, h->d_mid, Mtot, 1, 1);
+        launch_scan_d<8>(h, h->d_mid.p, Mtot, 1, 1);
         GH_LAUNCH_CHECK();
     }
     return gh_knn_finish(h, true, fuse_intersect);
@@ -690,11 +690,11 @@ gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world) {
     gh_scope t(h, "knn_merge_intersect");
 #define GH_MERGE(DD)                                                                                      \
     knn_merge_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2, h->stream>>>(      \
-        gathered, world, h->S, h->K, h->d_merged, make_inter_args(h, !h->intersect_done))
+        gathered, world, h->S, h->K, h->d_merged.p, make_inter_args(h, !h->intersect_done))
     if (!h->intersect_done) { GH_DISPATCH_DIM(h->D, GH_MERGE) } else { GH_MERGE(0); }
 #undef GH_MERGE
     GH_LAUNCH_CHECK();
-    h->d_keys_cur = h->d_merged;
+    h->d_keys_cur = h->d_merged.p;
     h->intersect_done = true;
     return GH_OK;
 }
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(256) void radial_topk_merge_kernel(const uint64_t *
 }
 
 gh_status gh_radial_topk_device(gh_engine *h, int K, uint64_t *d_part, int nparts, int32_t *d_ids) {
-    radial_topk_kernel<<<dim3((unsigned)nparts), dim3(256), 0, h->stream>>>(h->d_pos, h->d_order, h->n, h->D, h->LD, K, d_part);
+    radial_topk_kernel<<<dim3((unsigned)nparts), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_order.p, h->n, h->D, h->LD, K, d_part);
     radial_topk_merge_kernel<<<dim3(1), dim3(256), 0, h->stream>>>(d_part, nparts, K, d_ids);
     GH_LAUNCH_CHECK();
     return GH_OK;

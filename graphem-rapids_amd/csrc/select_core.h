@@ -253,8 +253,8 @@ __device__ __forceinline__ void gh_reduce_stats_column(const double *__restrict_
 inline inter_args make_inter_args(gh_engine *h, bool on) {
     inter_args ia{};
     if (on) {
-        ia = inter_args{h->d_pos, h->d_edges, h->sample.ids, h->D, h->LD, h->k, h->prm.k_inter,
-                        h->d_acc, h->d_tflag, h->d_touched, h->d_tcount, h->d_iscratch};
+        ia = inter_args{h->d_pos.p, h->d_edges.p, h->sample.ids, h->D, h->LD, h->k, h->prm.k_inter,
+                        h->d_acc.p, h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p};
         if (h->rows != h->n) { ia.own_lo = (int32_t)h->part.row_lo; ia.own_hi = (int32_t)h->part.row_hi; }
     }
     return ia;

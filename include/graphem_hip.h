@@ -803,6 +803,10 @@ gh_status gh_ingest_copy_edges(gh_ingest_handle h, int32_t relabel, int64_t *edg
 int32_t gh_device_count(void);
 const char *gh_version(void);
 
+/* Debugging aid for tests of the handles' life cycles: the device allocations that handles and calls of this library hold
+ * in this process right now, and their bytes (either pointer may be NULL).  Closing a handle gives back all of its own. */
+void gh_debug_live_allocations(int64_t *count, int64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  The product package never imports this module.
 """
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -19,8 +20,12 @@ _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 
 def build(force=False):
     srcs = [os.path.join(_HERE, f) for f in ("graphem_oracle.c", "aten_cdist_topk.cpp", "Makefile")]
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.run(["make", "-C", _HERE, "-B" if force else "-s"], check=True, stdout=subprocess.DEVNULL)
+    # One process at a time: the ranks of a multi-process test all come here, and a second make would rewrite the library
+    # under the first one's dlopen (the lock is on the Makefile, so no file is added).
+    with open(srcs[-1], "rb") as guard:
+        fcntl.flock(guard, fcntl.LOCK_EX)
+        if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
+            subprocess.run(["make", "-C", _HERE, "-B" if force else "-s"], check=True, stdout=subprocess.DEVNULL)
     return _LIB_PATH
 
 

@@ -549,3 +549,139 @@ def test_bench_dump_outputs_are_the_timed_paths_last_positions(tmp_path):
     want = eng.get_positions()
     eng.close()
     assert np.abs(got - want).max() <= 1e-5   # (other sample draws move the layout by orders of magnitude more)
+
+
+def _leak_cases():
+    """(name, body) pairs of test_closing_a_handle_returns_every_device_allocation: a body builds its handles, does its work
+    and returns them open."""
+    import torch
+    import graphem_rapids_amd as gra
+    from graphem_rapids_amd import _native
+    from graphem_rapids_amd.distributed import HipShardEngine, partition_rows, step_in_process
+    n, S, k = 6000, 64, 5
+    edges = gra.random_regular_edges(n, 6, seed=1).astype(np.int32)
+    rng = np.random.default_rng(3)
+
+    def engine(D=3, graph=edges, nv=n, **kw):
+        eng = _native.Engine(nv, D, graph, 1.0, 0.2, 0.5, k, S, **kw)
+        eng.set_positions(rng.standard_normal((nv, D)).astype(eng.np_dtype))
+        return eng
+
+    def stepped(**kw):
+        eng = engine(**kw)
+        eng.step()
+        eng.sync()
+        return [eng]
+
+    def default():
+        eng = engine()
+        eng.step()
+        eng.step()
+        for iters in (2, 5):   # the second stream is longer than the buffer of the first
+            eng.run(iters, np.stack([rng.permutation(len(edges))[:S] for _ in range(iters)]).astype(np.int32))
+        assert len(eng.radial_topk(4)) == 4
+        torch.manual_seed(1)
+        state = torch.get_rng_state().numpy().copy()
+        eng.run_torch_sampled(3, state)   # (returns with uploads still queued: the next call reuses their pinned slots)
+        eng.run_torch_sampled(3, state)
+        eng.sync()
+        return [eng]
+
+    def partitioned(finish):
+        shards = []
+        pos = rng.standard_normal((n, 3)).astype(np.float32)
+        for r in range(2):
+            chunk, lo, hi = partition_rows(n, 2, r)
+            sh = HipShardEngine(n, 3, edges, 1.0, 0.2, 0.5, k, S, 7, (lo, hi, 0, 0, _native.EDGES_HASHED), 0)
+            if finish == "own":
+                sh.rank_layout(2, r, chunk, packed=True)
+            elif finish == "overlap":
+                sh.overlap_layout(2, r, chunk)
+            else:
+                sh.gather_layout(2, r, chunk)
+            sh.set_positions(pos)
+            shards.append(sh)
+        step_in_process(shards, finish, rng.permutation(len(edges))[:S].astype(np.int32))
+        torch.cuda.synchronize()
+        return [sh.eng for sh in shards]
+
+    def loopback():
+        lib = _native.load()
+        eng = engine(partition=(0, n, 0, 0, _native.EDGES_HASHED))
+        eng.overlap_layout(1, 0, n)
+        group = lib.gh_loopback_group_create(1)
+        before = _native.live_allocations()
+        eng.comm_init_loopback(group, 0)
+        assert _native.live_allocations()[0] > before[0]
+        eng.comm_destroy()
+        assert _native.live_allocations() == before
+        lib.gh_loopback_group_destroy(group)
+        return [eng]
+
+    def knn_points():
+        ids = _native.knn_points(rng.standard_normal((100, 3)), rng.standard_normal((50, 3)), 4)
+        assert ids.shape == (100, 4)
+        return []
+
+    small = gra.random_regular_edges(500, 4, seed=2).astype(np.int32)
+
+    def ic():
+        g = _native.ICGraph(500, small)
+        g.spread([[0, 1], [2]], 0.1, 8, seed=1)
+        return [g]
+
+    def cent():
+        g = _native.CentGraph(500, small)
+        g.paths(np.arange(8))
+        g.distances(np.arange(8))
+        return [g]
+
+    def gen():
+        g = _native.Generator(0)
+        g.ba(500, 3, seed=1)
+        return [g]
+
+    def corr():
+        c = _native.Correlation([rng.standard_normal(500), rng.standard_normal(500)], 0)
+        c.matrix()
+        return [c]
+
+    def qual():
+        q = _native.LayoutQuality(small, 500, 0)
+        q.set_positions(rng.standard_normal((500, 2)).astype(np.float32))
+        q.crossings()
+        return [q]
+
+    def ingest():
+        p = _native.EdgeListParser(0)
+        p.parse("".join(f"{i} {i + 1}\n" for i in range(10)).encode())
+        return [p]
+
+    return [("default", default), ("bfs", lambda: stepped(reorder="bfs")), ("grid", lambda: stepped(knn_method="grid")),
+            ("ivf", lambda: stepped(knn_method="ivf")), ("cdist", lambda: stepped(knn_distance="cdist")),
+            ("float64", lambda: stepped(D=2, graph=gra.random_regular_edges(300, 4, seed=2).astype(np.int32), nv=300, dtype="float64")),
+            ("hubs", lambda: stepped(graph=gra.random_regular_edges(200, 30, seed=4).astype(np.int32), nv=200)),
+            ("gathered", lambda: partitioned("gathered")), ("own", lambda: partitioned("own")),
+            ("overlap", lambda: partitioned("overlap")), ("loopback", loopback), ("knn_points", knn_points), ("ic", ic),
+            ("cent", cent), ("gen", gen), ("corr", corr), ("qual", qual), ("ingest", ingest)]
+
+
+def test_closing_a_handle_returns_every_device_allocation():
+    """gh_debug_live_allocations, the count and bytes of the device allocations the library's handles hold: above the
+    baseline while a handle lives, back at it after close() -- for every kind of engine (each KNN method and distance,
+    reordering, float64, hub rows, the three partitioned finishes, a communicator), for a call without a handle and for the
+    analysis handles.  (The card's free memory is no signal: other processes share it.)"""
+    import gc
+    from graphem_rapids_amd import _native
+    cases = _leak_cases()
+    gc.collect()
+    baseline = _native.live_allocations()
+    for name, body in cases:
+        handles = body()
+        if handles:
+            assert _native.live_allocations()[0] > baseline[0], name
+        for h in handles:
+            h.close()
+        del handles
+        gc.collect()
+        assert _native.live_allocations() == baseline, name

@@ -1,6 +1,7 @@
 """The handle wrappers of graphem-rapids_amd/_native.py and the life cycle behind them (csrc/host_util.h), without a GPU: a
 create that fails owns nothing, a refused budget changes nothing, close is idempotent and a closed handle refuses every call,
-every exported symbol carries a ctypes signature, and the create-time messages of two modules stay apart."""
+every exported symbol carries a ctypes signature, the create-time messages of two modules stay apart, and host-path handles
+and a refused engine leave the count of live device allocations where it was."""
 import numpy as np
 import pytest
 
@@ -75,3 +76,26 @@ def test_create_messages_of_two_modules_stay_apart():
         _native.CentGraph(5, [[0, 1], [2, 7]])
     assert lib.gh_ic_last_error(None).decode().startswith("arc 0 ")
     assert lib.gh_cent_last_error(None).decode().startswith("edge 1 ")
+
+
+def test_host_path_handles_and_a_refused_engine_hold_no_device_allocation():
+    """gh_debug_live_allocations counts what the library's handles hold on devices: a host-path handle (device_id = -1) of
+    each kind, used and closed, and a gh_create that is refused (for its partition where there is a device, for the lack of
+    one elsewhere) leave the count and the bytes unchanged."""
+    start = _native.live_allocations()
+    g = _native.Generator(-1)
+    edges = g.ba(50, 3, seed=1)
+    g.close()
+    c = _native.Correlation(COLS, -1)
+    c.matrix()
+    c.close()
+    q = _native.LayoutQuality(edges, 50, -1)
+    q.set_positions(np.random.default_rng(0).standard_normal((50, 2)).astype(np.float32))
+    q.crossings()
+    q.close()
+    p = _native.EdgeListParser(-1)
+    p.parse(b"0 1\n1 2\n")
+    p.close()
+    with pytest.raises((ValueError, RuntimeError), match="partition out of range|no HIP device available"):
+        _native.Engine(50, 2, edges, 1.0, 0.2, 0.5, 3, 8, partition=(10, 5, 0, 0))   # row_lo > row_hi
+    assert _native.live_allocations() == start
