@@ -24,7 +24,8 @@ from .graphstats import (connected_components, number_connected_components, is_c
                          eccentricity, diameter, radius, average_shortest_path_length, triangles, clustering,
                          average_clustering, transitivity, graph_summary, print_graph_summary)
 from . import quality
-from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality)
+from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
+                      neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality)
 from . import datasets
 from .datasets import (read_edge_list, parse_edge_list, load_dataset, load_dataset_as_networkx, load_dataset_adjacency,
                        list_available_datasets, get_data_directory, SNAPDataset, NetworkRepositoryDataset,
@@ -88,7 +89,7 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
            "plot_radial_vs_centrality", "display_benchmark_results",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
-           "layout_quality",
+           "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",
            "load_dataset_adjacency", "list_available_datasets", "get_data_directory", "SNAPDataset",
            "NetworkRepositoryDataset", "SemanticScholarDataset"]

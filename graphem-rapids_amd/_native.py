@@ -167,6 +167,8 @@ SIGNATURES = {
     "gh_qual_crossings": (_int, [vp, i64, vp, vp, _P(i64)]),
     "gh_qual_pairs": (_int, [vp, i64, vp, vp]),
     "gh_qual_edge_lengths": (_int, [vp, vp]),
+    "gh_qual_neighbor_sizes": (_int, [vp, i64, vp, vp]),
+    "gh_qual_neighbor_ranks": (_int, [vp, i64, vp, vp, vp, vp, vp]),
     "gh_ingest_create": (_int, [_P(vp), _int]),
     "gh_ingest_destroy": (None, [vp]),
     "gh_ingest_last_error": (_str, [vp]),
@@ -803,7 +805,8 @@ def corr_rho(sxy, sxx, syy):
 
 class LayoutQuality(Handle):
     """Thin RAII wrapper over a gh_qual_handle: exact edge-crossing counts under the engine's float32 test and edge-length
-    statistics of one layout (include/graphem_hip.h "layout quality").  edges: (E, 2) int32, ids kept as given.
+    statistics of one layout (include/graphem_hip.h "layout quality"), and the exact neighbour ranks on the simple graph of
+    the same edge list ("embedding quality").  edges: (E, 2) int32, ids kept as given.
     device_id < 0 is the library's host path, which touches no device and returns the same integers."""
     _destroy, _last_error = "gh_qual_destroy", "gh_qual_last_error"
 
@@ -853,6 +856,22 @@ class LayoutQuality(Handle):
         out = np.zeros(4, dtype=np.float64)
         self._raise(self.lib.gh_qual_edge_lengths(self.handle, ptr(out)))
         return out
+
+    def neighbor_ranks(self, rows=None):
+        """(indptr int64, neighbors int32, dist2 float32, below int32, equal int32) in CSR form over the source vertex ids
+        `rows`, any order, repeats allowed; None = all vertices in order (gh_qual_neighbor_sizes, gh_qual_neighbor_ranks)."""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            if len(rows) == 0:
+                rows = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean all vertices)
+        n_rows = self.n if rows is None else len(rows)
+        indptr = np.zeros(n_rows + 1, dtype=np.int64)
+        self._raise(self.lib.gh_qual_neighbor_sizes(self.handle, n_rows, ptr(rows), ptr(indptr)))
+        slots = int(indptr[-1])
+        neighbors, dist2 = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.float32)
+        below, equal = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.int32)
+        self._raise(self.lib.gh_qual_neighbor_ranks(self.handle, n_rows, ptr(rows), ptr(neighbors), ptr(dist2), ptr(below), ptr(equal)))
+        return indptr, neighbors, dist2, below, equal
 
 
 class EdgeListParser(BudgetHandle):

@@ -14,7 +14,12 @@
 //   qual_length_kernel     per-edge length in double; min / max / sum / sum of squares by wave shuffles and one LDS step,
 //                          one partial per workgroup, combined on the host in workgroup order (deterministic, no atomics)
 //
-// The kernel runs the full square: row i meets every column j, and nothing is credited to a column.  There is no pruning
+//   qual_rank_kernel       neighbour ranks ("embedding quality" in the header): a wave owns up to 64 (source, neighbour) slots
+//                          of one source, lane i keeps threshold i and its two counts in registers, the workgroup walks the
+//                          position tiles through LDS, and per 64 columns each threshold costs two compares, two ballots and
+//                          two popcounts; no atomics.  qual_rank_sum_kernel adds the partial counts of split columns.
+//
+// The crossing kernel runs the full square: row i meets every column j, and nothing is credited to a column.  There is no pruning
 // by bounding boxes: it would not be exact.  Two segments whose closed bounding boxes are disjoint CAN cross under the
 // float32 test, because for four nearly collinear points all four orientation values are rounding noise of either sign:
 //     a = (0.06998461484909058, 0.06998474150896072)   b = (2.662574529647827, 2.662574291229248)
@@ -41,6 +46,12 @@
 #define QUAL_MIN_BLOCKS 2048                // fewer row blocks than this: the column tiles are split over gridDim.y
 #define QUAL_LEN_BLOCKS 1024
 #define QUAL_HOST_THREADS 16
+#define QUAL_RANK_PIECE 64                  // slots of one source that one wave owns: lane i keeps threshold i (at most 64)
+#define QUAL_RANK_WAVES (QUAL_BLOCK / 64)   // pieces per workgroup: they share the staged position tile
+#define QUAL_RANK_LDS 8192                  // floats of the position tile, D rows of tile_cols columns: 32 KiB
+#define QUAL_RANK_TILE 1024                 // columns of a tile at most; fewer when D * 1024 floats do not fit
+#define QUAL_RANK_LAUNCH_PAIRS (1ll << 40)  // (piece, column) pairs per launch: pieces are taken in batches of about a second
+#define QUAL_RANK_LAUNCH_ITEMS (1ll << 22)
 
 namespace {
 
@@ -161,6 +172,112 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_length_kernel(int64_t E, cons
     }
 }
 
+// ---- neighbour ranks -------------------------------------------------------------------------------------------------
+// The exact-difference chain of the header: (((0 + t_0 t_0) + t_1 t_1) + ...), t_d = a[d] - b[d * sb], every operation a
+// separate float32 operation (the Makefile's -ffp-contract=off keeps the product and the sum apart).  a is a packed row; b
+// has stride sb, which is 1 for a packed row and the tile's column count for a column of the staged tile.
+__host__ __device__ __forceinline__ float qual_d2(const float *a, const float *b, int64_t sb, int D) {
+    float s = 0.0f;
+    for (int d = 0; d < D; ++d) {
+        const float t = a[d] - b[d * sb];
+        s = s + t * t;
+    }
+    return s;
+}
+
+// What one column at distance d adds to the two counts of a threshold t: IEEE comparisons, so a NaN on either side adds
+// nothing and +inf equals +inf.
+__host__ __device__ __forceinline__ int qual_is_below(float d, float t) { return (int)(d < t); }
+__host__ __device__ __forceinline__ int qual_is_equal(float d, float t) { return (int)(d == t); }
+// Column v itself is at distance t exactly -- d2(u, v) is the very chain the threshold came from -- so the walk over all
+// columns counts it in `equal` once unless t is NaN.  This is the w != v exclusion, made once per slot, not once per column.
+__host__ __device__ __forceinline__ int qual_own_column(float t) { return (int)(t == t); }
+
+// lane i's x, for an i that is the same in every lane
+__device__ __forceinline__ float qual_lane_value(float x, int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i)); }
+
+// The threshold as it is returned: the sign and payload of a NaN are whatever the hardware and the compiler's choice of
+// instructions made of them (a negated operand flips the sign), so a NaN is returned as the one quiet NaN 0x7FC00000.
+__host__ __device__ __forceinline__ float qual_returned_d2(float t) {
+    union { uint32_t u; float f; } nan = {0x7FC00000u};
+    return t == t ? t : nan.f;
+}
+
+// A piece: up to QUAL_RANK_PIECE consecutive output slots [slot0, slot0 + len) of source u.  A row longer than a piece is
+// cut into several; the counts of a slot do not depend on the cut.
+struct qual_item {
+    int64_t slot0;
+    int32_t u, len;
+};
+
+// Wave w of workgroup blockIdx.x owns piece item0 + 4 * blockIdx.x + w and meets the columns of the tiles
+// [blockIdx.y * tiles_per_chunk, ...).  out[blockIdx.y * batch_slots + (slot - slot_base)] = (below, equal) among them;
+// d2out[slot] = the threshold (written by chunk 0).  STAGED: the tile goes through LDS as D rows of tile_cols columns, so
+// consecutive lanes read consecutive words; otherwise (D too large for one 64-column tile) columns are read from memory.
+template <bool STAGED>
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_rank_kernel(int64_t n, int D, const float *__restrict__ pos, int tile_cols,
+                                                               const qual_item *__restrict__ items, int64_t item0, int64_t n_items,
+                                                               const int32_t *__restrict__ nbr, int64_t tiles_per_chunk, int64_t slot_base,
+                                                               int64_t batch_slots, float *__restrict__ d2out, int2 *__restrict__ out) {
+    __shared__ float s_tile[STAGED ? QUAL_RANK_LDS : 1];
+    const int lane = threadIdx.x & 63;
+    const int64_t it = (int64_t)blockIdx.x * QUAL_RANK_WAVES + (threadIdx.x >> 6);
+    const bool live = it < n_items;   // the same in every lane; an idle wave stages its share of the tile and counts nothing
+    const int64_t slot0 = live ? items[item0 + it].slot0 : 0;
+    // one value per wave, said so to the compiler: the loops over a piece's thresholds are scalar loops
+    const int u = __builtin_amdgcn_readfirstlane(live ? items[item0 + it].u : 0);
+    const int len = __builtin_amdgcn_readfirstlane(live ? items[item0 + it].len : 0);
+    const float *xu = pos + (int64_t)u * D;
+    const bool mine = lane < len;
+    const int v = mine ? nbr[slot0 + lane] : 0;
+    const float tv = mine ? qual_d2(xu, pos + (int64_t)v * D, 1, D) : NAN;
+    float tmax = -INFINITY;   // the largest threshold that is no NaN: a column beyond it adds nothing to any count of the piece
+    for (int i = 0; i < len; ++i) tmax = fmaxf(tmax, qual_lane_value(tv, i));
+    const int64_t n_tiles = (n + tile_cols - 1) / tile_cols;
+    const int64_t t0 = (int64_t)blockIdx.y * tiles_per_chunk, t1 = min(n_tiles, t0 + tiles_per_chunk);
+    int32_t below = 0, equal = 0;
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t base = t * tile_cols;
+        const int m = (int)min((int64_t)tile_cols, n - base);   // the last tile is partial
+        if (STAGED) {
+            __syncthreads();
+            for (int d = 0; d < D; ++d)
+                for (int c = threadIdx.x; c < m; c += QUAL_BLOCK) s_tile[d * tile_cols + c] = pos[(base + c) * D + d];
+            __syncthreads();
+        }
+        if (!live) continue;
+        for (int c0 = 0; c0 < m; c0 += 64) {
+            const int c = c0 + lane;
+            const int64_t w = base + c;
+            float d = NAN;   // a lane past the tile's end and the column w == u add nothing
+            if (c < m && w != u) d = STAGED ? qual_d2(xu, s_tile + c, tile_cols, D) : qual_d2(xu, pos + w * D, 1, D);
+            if (__ballot(d <= tmax) == 0) continue;
+            for (int i = 0; i < len; ++i) {
+                const float ti = qual_lane_value(tv, i);
+                const int nb = __popcll(__ballot(qual_is_below(d, ti))), ne = __popcll(__ballot(qual_is_equal(d, ti)));
+                if (lane == i) { below += nb; equal += ne; }
+            }
+        }
+    }
+    if (mine) {
+        if (v >= t0 * tile_cols && v < t1 * tile_cols) equal -= qual_own_column(tv);   // v < n: t1 * tile_cols may pass n, v cannot
+        out[(int64_t)blockIdx.y * batch_slots + (slot0 - slot_base) + lane] = make_int2(below, equal);
+        if (blockIdx.y == 0) d2out[slot0 + lane] = qual_returned_d2(tv);
+    }
+}
+
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_rank_sum_kernel(int64_t slots, int chunks, const int2 *__restrict__ part, int2 *__restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x;
+    if (s >= slots) return;
+    int2 a = make_int2(0, 0);
+    for (int c = 0; c < chunks; ++c) {
+        const int2 p = part[(int64_t)c * slots + s];
+        a.x += p.x;
+        a.y += p.y;
+    }
+    out[s] = a;
+}
+
 unsigned qual_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + QUAL_BLOCK - 1) / QUAL_BLOCK); }
 
 }  // namespace
@@ -175,6 +292,11 @@ struct gh_qual : gh_host {          // device < 0: host path
     std::vector<int2> h_edges;
     std::vector<float> h_pos;
     std::vector<float4> h_seg;
+    // the simple graph of the edge list (self-loops dropped, repeats and both directions merged), built by the first
+    // neighbour query: neighbours of u = g_idx[g_ptr[u] .. g_ptr[u + 1]), ids ascending
+    bool g_built = false;
+    std::vector<int64_t> g_ptr;
+    std::vector<int32_t> g_idx;
 };
 
 static thread_local std::string g_qual_error;
@@ -246,6 +368,134 @@ void qual_crossings_host(const gh_qual *h, int64_t n_rows, const int32_t *rows, 
             counts[r] = cnt;
         }
     });
+}
+
+// The simple graph, once per handle.  A device handle keeps its edge list on the device only, so it is read back here.
+gh_status qual_build_graph(gh_qual *h) {
+    if (h->g_built) return GH_OK;
+    std::vector<int2> fetched;
+    const int2 *edges = h->h_edges.data();
+    if (h->device >= 0 && h->E > 0) {
+        GH_HIP(hipSetDevice(h->device));
+        fetched.resize((size_t)h->E);
+        GH_HIP(hipMemcpyAsync(fetched.data(), h->d_edges.p, 8 * (size_t)h->E, hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
+        edges = fetched.data();
+    }
+    std::vector<uint64_t> keys;
+    GH_TRY_ST(gh_canonical_edge_keys(h->n, h->E, (const int32_t *)edges, false, "edge", &keys, &h->err));
+    h->g_ptr.assign((size_t)h->n + 1, 0);
+    for (uint64_t k : keys) {
+        h->g_ptr[(size_t)(k >> 32) + 1] += 1;
+        h->g_ptr[(size_t)(k & 0xFFFFFFFFu) + 1] += 1;
+    }
+    for (int64_t u = 0; u < h->n; ++u) h->g_ptr[u + 1] += h->g_ptr[u];
+    h->g_idx.resize(2 * keys.size());
+    std::vector<int64_t> fill(h->g_ptr.begin(), h->g_ptr.end() - 1);
+    // keys ascend by (a, b) with a < b: row b takes its smaller neighbours a in ascending order first, then row a its
+    // larger neighbours b in ascending order, so every row ends up ascending
+    for (uint64_t k : keys) h->g_idx[(size_t)fill[k & 0xFFFFFFFFu]++] = (int32_t)(k >> 32);
+    for (uint64_t k : keys) h->g_idx[(size_t)fill[k >> 32]++] = (int32_t)(k & 0xFFFFFFFFu);
+    h->g_built = true;
+    return GH_OK;
+}
+
+// The checks both neighbour calls share; afterwards *n_rows is the row count (n for rows == NULL) and the graph is built.
+gh_status qual_rank_rows(gh_qual *h, int64_t *n_rows, const int32_t *rows) {
+    if (!rows) *n_rows = h->n;
+    if (*n_rows < 0) return qual_invalid(h, "n_rows must be >= 0, got " + std::to_string(*n_rows));
+    for (int64_t r = 0; rows && r < *n_rows; ++r)
+        if (rows[r] < 0 || rows[r] >= h->n) return qual_invalid(h, "row " + std::to_string(r) + " has a vertex id outside [0, n)");
+    return qual_build_graph(h);
+}
+
+void qual_ranks_host(const gh_qual *h, int64_t n_rows, const int32_t *rows, const int64_t *indptr, const int32_t *nbr, float *d2,
+                     int32_t *below, int32_t *equal) {
+    const int64_t n = h->n;
+    const int D = h->D;
+    const float *pos = h->h_pos.data();
+    qual_host_parallel(n_rows, 1, [=](int64_t first, int64_t last) {
+        for (int64_t r = first; r < last; ++r) {
+            const int64_t u = rows ? rows[r] : r, s0 = indptr[r], k = indptr[r + 1] - s0;
+            const float *xu = pos + u * D;
+            float tmax = -INFINITY;
+            for (int64_t i = 0; i < k; ++i) {
+                d2[s0 + i] = qual_returned_d2(qual_d2(xu, pos + (int64_t)nbr[s0 + i] * D, 1, D));
+                tmax = fmaxf(tmax, d2[s0 + i]);
+                below[s0 + i] = 0;
+                equal[s0 + i] = -qual_own_column(d2[s0 + i]);
+            }
+            for (int64_t w = 0; k > 0 && w < n; ++w) {
+                if (w == u) continue;
+                const float d = qual_d2(xu, pos + w * D, 1, D);
+                if (!(d <= tmax)) continue;
+                for (int64_t i = 0; i < k; ++i) {
+                    below[s0 + i] += qual_is_below(d, d2[s0 + i]);
+                    equal[s0 + i] += qual_is_equal(d, d2[s0 + i]);
+                }
+            }
+        }
+    });
+}
+
+gh_status qual_ranks_device(gh_qual *h, int64_t n_rows, const int32_t *rows, const int64_t *indptr, const int32_t *nbr, float *d2,
+                            int32_t *below, int32_t *equal) {
+    const int64_t slots = indptr[n_rows], n = h->n;
+    // rows are cut into pieces of at most QUAL_RANK_PIECE slots, one wave each
+    std::vector<qual_item> items;
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int64_t s = indptr[r]; s < indptr[r + 1]; s += QUAL_RANK_PIECE)
+            items.push_back({s, rows ? rows[r] : (int32_t)r, (int32_t)std::min<int64_t>(QUAL_RANK_PIECE, indptr[r + 1] - s)});
+    const int64_t n_items = (int64_t)items.size();
+    GH_HIP(hipSetDevice(h->device));
+    gh_dev<qual_item> d_items;
+    gh_dev<int32_t> d_nbr;
+    gh_dev<float> d_d2;
+    gh_dev<int2> d_cnt, d_part;
+    if (!d_items.alloc(sizeof(qual_item) * (size_t)n_items) || !d_nbr.alloc(4 * (size_t)slots) || !d_d2.alloc(4 * (size_t)slots) ||
+        !d_cnt.alloc(8 * (size_t)slots)) {
+        h->err = "hipMalloc failed for " + std::to_string(16 * (n_items + slots)) + " bytes of neighbour slots";
+        return GH_ERR_NOMEM;
+    }
+    GH_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(qual_item) * (size_t)n_items, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(d_nbr.p, nbr, 4 * (size_t)slots, hipMemcpyHostToDevice, h->stream));
+    // the tile: D rows of tile_cols columns in QUAL_RANK_LDS floats, tile_cols a multiple of 64; none fits: no staging
+    const int fit = (int)std::min<int64_t>(QUAL_RANK_TILE, QUAL_RANK_LDS / h->D / 64 * 64);
+    const bool staged = fit >= 64;
+    const int tile_cols = staged ? fit : QUAL_RANK_TILE;
+    const int64_t n_tiles = (n + tile_cols - 1) / tile_cols;
+    const int64_t batch = std::max<int64_t>(QUAL_RANK_WAVES, std::min<int64_t>(QUAL_RANK_LAUNCH_ITEMS, QUAL_RANK_LAUNCH_PAIRS / n / QUAL_RANK_WAVES * QUAL_RANK_WAVES));
+    for (int64_t item0 = 0; item0 < n_items; item0 += batch) {
+        const int64_t ni = std::min(batch, n_items - item0);
+        const int64_t slot_base = items[item0].slot0, batch_slots = items[item0 + ni - 1].slot0 + items[item0 + ni - 1].len - slot_base;
+        const int64_t blocks = (ni + QUAL_RANK_WAVES - 1) / QUAL_RANK_WAVES;
+        // a few pieces only (a sample, a small graph): their columns are split so that every compute unit has work
+        const int64_t chunks = std::max<int64_t>(1, std::min(n_tiles, QUAL_MIN_BLOCKS / blocks));
+        const int64_t tiles_per_chunk = (n_tiles + chunks - 1) / chunks;
+        const int64_t used = (n_tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+        if (used > 1 && d_part.bytes < 8 * (size_t)(used * batch_slots) && !d_part.alloc(8 * (size_t)(used * batch_slots))) {
+            h->err = "hipMalloc failed for the partial counts";
+            return GH_ERR_NOMEM;
+        }
+        int2 *out = used > 1 ? d_part.p : d_cnt.p + slot_base;
+        auto kernel = staged ? qual_rank_kernel<true> : qual_rank_kernel<false>;
+        kernel<<<dim3((unsigned)blocks, (unsigned)used), dim3(QUAL_BLOCK), 0, h->stream>>>(
+            n, h->D, h->d_pos.p, tile_cols, d_items.p, item0, ni, d_nbr.p, tiles_per_chunk, slot_base, batch_slots, d_d2.p, out);
+        GH_LAUNCH_CHECK();
+        if (used > 1) {
+            qual_rank_sum_kernel<<<dim3(qual_grid(batch_slots)), dim3(QUAL_BLOCK), 0, h->stream>>>(batch_slots, (int)used, d_part.p, d_cnt.p + slot_base);
+            GH_LAUNCH_CHECK();
+        }
+    }
+    std::vector<int2> cnt((size_t)slots);
+    GH_HIP(hipMemcpyAsync(d2, d_d2.p, 4 * (size_t)slots, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, 8 * (size_t)slots, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
+    for (int64_t s = 0; s < slots; ++s) {
+        below[s] = cnt[s].x;
+        equal[s] = cnt[s].y;
+    }
+    return GH_OK;
 }
 
 }  // namespace
@@ -425,5 +675,39 @@ extern "C" gh_status gh_qual_edge_lengths(gh_qual_handle h, double out[4]) {
         }
     }
     out[0] = all.mn; out[1] = all.mx; out[2] = all.s; out[3] = all.ss;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_qual_neighbor_sizes(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int64_t *indptr) {
+    if (!h) { g_qual_error = "handle is NULL"; return GH_ERR_INVALID; }
+    if (!indptr) return qual_invalid(h, "indptr is NULL");
+    GH_TRY_ST(qual_rank_rows(h, &n_rows, rows));
+    indptr[0] = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t u = rows ? rows[r] : r;
+        indptr[r + 1] = indptr[r] + (h->g_ptr[u + 1] - h->g_ptr[u]);
+    }
+    return GH_OK;
+}
+
+extern "C" gh_status gh_qual_neighbor_ranks(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int32_t *neighbors, float *d2,
+                                            int32_t *below, int32_t *equal) {
+    if (!h) { g_qual_error = "handle is NULL"; return GH_ERR_INVALID; }
+    if (h->D < 1) return qual_invalid(h, "no positions were set");
+    GH_TRY_ST(qual_rank_rows(h, &n_rows, rows));
+    std::vector<int64_t> indptr((size_t)n_rows + 1, 0);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t u = rows ? rows[r] : r;
+        indptr[r + 1] = indptr[r] + (h->g_ptr[u + 1] - h->g_ptr[u]);
+    }
+    const int64_t slots = indptr[n_rows];
+    if (slots == 0) return GH_OK;
+    if (!neighbors || !d2 || !below || !equal) return qual_invalid(h, "neighbors, d2, below or equal is NULL");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t u = rows ? rows[r] : r;
+        std::copy(h->g_idx.begin() + h->g_ptr[u], h->g_idx.begin() + h->g_ptr[u + 1], neighbors + indptr[r]);
+    }
+    if (h->device < 0) qual_ranks_host(h, n_rows, rows, indptr.data(), neighbors, d2, below, equal);
+    else GH_TRY_ST(qual_ranks_device(h, n_rows, rows, indptr.data(), neighbors, d2, below, equal));
     return GH_OK;
 }

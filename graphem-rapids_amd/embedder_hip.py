@@ -386,6 +386,12 @@ class GraphEmbedderHIP:
         from . import quality
         return quality.layout_quality(self, **kw)
 
+    def embedding_quality(self, **kw):
+        """quality.embedding_quality of the current layout: link AUC, neighbourhood preservation, mean rank.  The positions
+        are read on the device."""
+        from . import quality
+        return quality.embedding_quality(self, **kw)
+
     def display_layout(self, edge_width=1, node_size=3, node_colors=None):
         """Plotly rendering is outside the accelerated path."""
         if self.n_components not in (2, 3):

@@ -10,6 +10,12 @@ Every function takes either a GraphEmbedderHIP, whose edges and device positions
 (positions, edges): positions (n, D) array-like, edges an (E, 2) array or a scipy sparse adjacency.  An adjacency goes
 through the embedder's own rule (upper triangle of the nonzero pattern in CSR row order), so edge ids equal the
 embedder's.  Edge ids are kept as given: nothing is merged or dropped.
+
+Embedding quality asks the other question: are a vertex's neighbours nearer to it than the vertices it is not joined to?
+neighbor_ranks returns, for every (source, neighbour), how many other vertices lie strictly nearer and how many exactly
+as near -- exact integers under the float32 distance of include/graphem_hip.h "embedding quality", over ALL D coordinates
+and on the SIMPLE graph of the edge list (self-loops dropped, repeats and both directions merged) -- and link_auc,
+neighborhood_preservation and embedding_quality are a few divisions of sums of those integers.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -24,6 +30,18 @@ EXACT_MAX_EDGES = 1_000_000
 # The same for the library's host path (no device): 8.5 s at 400 000 edges on 16 threads of the same machine's host,
 # 1.9e10 pair tests per second, a second at 137 000 edges.
 HOST_EXACT_MAX_EDGES = 100_000
+# embedding_quality(exact=None) takes every vertex as a source up to this many vertices and samples sources above it.
+# Measured on one MI355X (2026-10-19, tools/embedding_quality.py --n 100000 --iters 20 --time --host and --n 1000000
+# --iters 20 --time --host --repeats 2; random-regular d = 8, D = 3, the layout after 20 iterations):
+# neighbor_ranks over all sources takes 0.0345 s at 100 K vertices and 3.19 s at a million, 2.9e11 and 3.1e11 (source,
+# column) pairs per second, and the time grows with the square of n; the whole embedding_quality(exact=True) call takes
+# 0.086 s and 3.61 s, so about 0.42 us per vertex on top of the kernel (graph, slots, numpy).  3.19e-12 n^2 + 0.42e-6 n is
+# a second at 500 000 vertices.  4096 sampled sources take 1.6 ms at 100 K and 14.7 ms at a million.
+EXACT_MAX_VERTICES = 500_000
+# The same for the library's host path (no device): 4096 sources take 0.097 s at 100 K and 0.884 s at a million on 16
+# threads of the same machine's host, 4.2e9 and 4.6e9 pairs per second; all sources were not run there, and at that rate
+# they take a second at 66 000 vertices.
+HOST_EXACT_MAX_VERTICES = 60_000
 
 
 def _edges_from_adjacency(adjacency):
@@ -96,6 +114,23 @@ class _Snapshot:
         stderr = E / 2 * np.std(counts.astype(np.float64), ddof=1) / np.sqrt(S) * np.sqrt(1 - S / E) if S >= 2 else 0.0
         return float(estimate), float(stderr)
 
+    def ranks(self, rows=None):
+        """neighbor_ranks' dict for the source ids `rows` (None: all vertices)."""
+        indptr, neighbors, dist2, below, equal = self.q.neighbor_ranks(rows)
+        sources = np.arange(self.q.n, dtype=np.int64) if rows is None else np.array(rows, dtype=np.int64).ravel()
+        return {"sources": sources, "indptr": indptr, "neighbors": neighbors, "dist2": dist2,
+                "below": below.astype(np.int64), "equal": equal.astype(np.int64)}
+
+    def sample(self, exact, sample_size, seed):
+        """The source ids embedding_quality uses: None (all vertices) or the sorted sample."""
+        n = self.q.n
+        if exact is None:
+            exact = n <= (EXACT_MAX_VERTICES if self.q.device_id >= 0 else HOST_EXACT_MAX_VERTICES)
+        S = min(int(sample_size), n)
+        if exact or S >= n:
+            return None
+        return np.sort(np.random.default_rng(seed).choice(n, S, replace=False))
+
     def length_stats(self):
         E = self.q.E
         mn, mx, s, ss = (float(v) for v in self.q.edge_lengths())
@@ -156,3 +191,100 @@ def layout_quality(x, edges=None, exact=None, sample_size=4096, seed=0, device_i
         if s.L_min is not None:
             out["L_min"] = s.L_min
         return out
+
+
+# ---- embedding quality: neighbour ranks and what is computed from them ----------------------------------------------------
+def neighbor_ranks(x, edges=None, rows=None, device_id=None):
+    """For the source vertex ids `rows` (any order, repeats allowed; None = all vertices in order), in CSR form: dict of
+    sources (int64), indptr (int64, len(sources) + 1), and per slot neighbors (int32, the distinct neighbours of the source
+    in the simple graph, ids ascending), dist2 (float32, d2(source, neighbour) under the header's float32 chain), below and
+    equal (int64): how many vertices other than the source and that neighbour lie strictly nearer to the source than the
+    neighbour, and how many exactly as near.  Neighbours and non-neighbours are counted alike."""
+    with _Snapshot(x, edges, device_id) as s:
+        return s.ranks(rows)
+
+
+def _non_neighbor_counts(r):
+    """(k per slot, b_bar, q_bar): the counts of a slot among the NON-neighbours only.  The counts among the source's other
+    neighbours come from dist2 within the row -- b_N = #{v' in N(u), v' != v: d2(u, v') < d2(u, v)}, q_N likewise for
+    equality -- and b_bar = below - b_N, q_bar = equal - q_N."""
+    indptr, d2 = r["indptr"], r["dist2"]
+    k = np.diff(indptr)
+    row = np.repeat(np.arange(len(k), dtype=np.uint64), k)
+    if len(d2) == 0:
+        return k[:0], r["below"], r["equal"]
+    # one sort by (row, distance): a distance is >= +0, +inf or the one NaN 0x7FC00000, and on those the float32 bits order
+    # as the values do, NaN last
+    order = np.argsort((row << np.uint64(32)) | d2.view(np.uint32), kind="stable")
+    sd, srow = d2[order], row[order]
+    idx = np.arange(len(sd))
+    new_row = np.r_[True, srow[1:] != srow[:-1]]
+    new_val = new_row | np.r_[True, sd[1:] != sd[:-1]]   # NaN != NaN: every NaN is a group of its own
+    row_start = np.maximum.accumulate(np.where(new_row, idx, 0))
+    val_start = np.maximum.accumulate(np.where(new_val, idx, 0))
+    group = np.cumsum(new_val) - 1
+    b_n, q_n = np.zeros(len(sd), dtype=np.int64), np.zeros(len(sd), dtype=np.int64)
+    b_n[order] = np.where(np.isnan(sd), 0, val_start - row_start)   # nothing is below a NaN
+    q_n[order] = np.bincount(group)[group] - 1
+    return np.repeat(k, k), r["below"] - b_n, r["equal"] - q_n
+
+
+def _link_auc(counts, n):
+    k, b_bar, q_bar = counts
+    m = n - 1 - k
+    use = m >= 1
+    den = 2 * int(np.sum(m[use]))                    # sum over slots of 2 m_u = sum over sources of 2 k_u m_u
+    if den == 0:
+        return float("nan")
+    num = den - 2 * int(np.sum(b_bar[use])) - int(np.sum(q_bar[use]))   # sum of 2 (m - b_bar - q_bar) + q_bar, in Python integers
+    return num / den
+
+
+def _preservation(r):
+    k = np.diff(r["indptr"])
+    row = np.repeat(np.arange(len(k)), k)
+    h = np.bincount(row[r["below"] < k[row]], minlength=len(k)).astype(np.int64)
+    has = k >= 1
+    if not has.any():
+        return {"precision": float("nan"), "jaccard": float("nan")}
+    return {"precision": int(h.sum()) / int(k.sum()), "jaccard": float(np.mean(h[has] / (2 * k[has] - h[has])))}
+
+
+def link_auc(x, edges=None, rows=None, device_id=None):
+    """Link-reconstruction AUC: the probability that a neighbour of a source lies nearer to it than a non-neighbour, a tie
+    counted one half, pooled over the sources in `rows` (None: all) that have a neighbour and a non-neighbour (k_u >= 1,
+    m_u = n - 1 - k_u >= 1): sum over slots of 2 (m_u - b_bar - q_bar) + q_bar, divided by sum over sources of 2 k_u m_u --
+    exact integers and one float64 division.  A non-neighbour at a NaN distance counts as farther.  nan when no source
+    qualifies."""
+    with _Snapshot(x, edges, device_id) as s:
+        return _link_auc(_non_neighbor_counts(s.ranks(rows)), s.q.n)
+
+
+def neighborhood_preservation(x, edges=None, rows=None, device_id=None):
+    """dict(precision, jaccard): how much of N(u) is among the k_u vertices nearest to u.  h_u = #{v in N(u): below(u -> v) <
+    k_u}: a neighbour is kept when fewer than k_u other vertices are STRICTLY nearer, so ties count in the neighbour's
+    favour.  precision = sum h_u / sum k_u (one division of integers); jaccard = the mean over the sources with k_u >= 1 of
+    h_u / (2 k_u - h_u).  nan for both when no source has a neighbour."""
+    with _Snapshot(x, edges, device_id) as s:
+        return _preservation(s.ranks(rows))
+
+
+def embedding_quality(x, edges=None, exact=None, sample_size=4096, seed=0, device_id=None):
+    """dict: n_vertices, sources (how many source vertices were used), sources_exact (every vertex was one), link_auc,
+    neighborhood_precision, neighborhood_jaccard (link_auc and neighborhood_preservation over those sources) and mean_rank
+    (the mean over slots of b_bar, the number of non-neighbours strictly nearer than the neighbour; nan without slots).
+
+    exact=True takes every vertex as a source; exact=False takes S = min(sample_size, n) of them, rows =
+    sort(default_rng(seed).choice(n, S, replace=False)); exact=None takes all up to EXACT_MAX_VERTICES vertices
+    (HOST_EXACT_MAX_VERTICES on the host path) and samples above."""
+    with _Snapshot(x, edges, device_id) as s:
+        n = s.q.n
+        rows = s.sample(exact, sample_size, seed)
+        r = s.ranks(rows)
+        counts = _non_neighbor_counts(r)
+        b_bar = counts[1]
+        pres = _preservation(r)
+        return {"n_vertices": n, "sources": len(r["sources"]), "sources_exact": rows is None,
+                "link_auc": _link_auc(counts, n), "neighborhood_precision": pres["precision"],
+                "neighborhood_jaccard": pres["jaccard"],
+                "mean_rank": int(b_bar.sum()) / len(b_bar) if len(b_bar) else float("nan")}

@@ -735,6 +735,38 @@ gh_status gh_qual_pairs(gh_qual_handle h, int64_t n_pairs, const int32_t *pairs,
 /* out = {min L, max L, sum L, sum L^2} over all edges; {+inf, -inf, 0, 0} for an empty edge list.  Blocking. */
 gh_status gh_qual_edge_lengths(gh_qual_handle h, double out[4]);
 
+/* ---- embedding quality: exact neighbour ranks (graphem-rapids_amd/quality.py: neighbor_ranks, link_auc,
+ * neighborhood_preservation, embedding_quality) -- the same gh_qual handle ------------------------------------------------
+ * Are a vertex's neighbours nearer to it than the vertices it is not joined to?  Under every such measure lies one exact
+ * pair of integers per (vertex, neighbour): how many other vertices lie strictly nearer, and how many exactly as near.
+ *
+ * Graph.  The simple undirected graph of the handle's edge list: self-loops dropped, repeats and both directions merged
+ * (graphstats.py's convention).  N(u) = u's distinct neighbours, ids ascending; k_u = |N(u)|; m_u = n - 1 - k_u.  The
+ * crossing functions above keep taking the edge list as given.  The graph is built on the host by the first query.
+ * Distance.  For float32 rows x,
+ *     d2(u, w) = (((0 + t_0 * t_0) + t_1 * t_1) + ... + t_{D-1} * t_{D-1}),   t_d = x[u][d] - x[w][d],
+ * every subtraction, product and sum a separate IEEE float32 operation in the order d = 0 .. D-1, nothing contracted, all
+ * D coordinates used.  (a - b)^2 and (b - a)^2 are the same float, so d2 is symmetric in (u, w) bit for bit.  It is a
+ * float32 rule: a float64 embedder's positions are rounded to float32 first.  Comparisons are IEEE: a NaN distance is
+ * neither below nor equal to anything, +inf equals +inf.  A NaN threshold is returned as the quiet NaN 0x7FC00000: the
+ * sign and payload an operation gives a NaN are the hardware's, not IEEE's.
+ * Counts.  For a source u and each v in N(u), with t = d2(u, v):
+ *     below(u -> v) = #{ w in [0, n), w != u, w != v : d2(u, w) <  t }
+ *     equal(u -> v) = #{ w in [0, n), w != u, w != v : d2(u, w) == t }
+ * over neighbours and non-neighbours alike.  Results depend only on (edges, positions, rows): not on launch geometry, on
+ * how a long row is cut into pieces, or on whether the device or the host path ran.  No float is ever summed.
+ *
+ * rows: host int32, n_rows source vertex ids in any order, repeats allowed; NULL = all n vertices in order (n_rows is
+ * ignored).  The result is in CSR form over rows: row r owns the slots [indptr[r], indptr[r + 1]), one per neighbour of
+ * rows[r], ids ascending.  GH_ERR_INVALID for a row id outside [0, n) ("row <r> has a vertex id outside [0, n)"). */
+/* indptr: host int64, n_rows + 1 (n + 1 for rows == NULL).  Needs no positions. */
+gh_status gh_qual_neighbor_sizes(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int64_t *indptr);
+/* The fill: host arrays of indptr[n_rows] slots each (they may be NULL when that is 0): the neighbour's id, the
+ * threshold d2(u, v) (its bits), below and equal.  GH_ERR_INVALID for a query before any positions were set.  D = 1 is
+ * valid.  Blocking. */
+gh_status gh_qual_neighbor_ranks(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int32_t *neighbors, float *d2,
+                                 int32_t *below, int32_t *equal);
+
 /* ---- edge-list ingestion: text -> (vertices, edges) (reference datasets.py: SNAPDataset.load, _load_mtx_file,
  * _load_edges_file; graphem-rapids_amd/datasets.py) ------------------------------------------------------------------
  * The reference reads a file in text mode line by line, tests line.startswith(c), takes line.strip().split() and calls
