@@ -174,7 +174,6 @@ __global__ __launch_bounds__(256) void knn_select_cdist_kernel(uint64_t *__restr
                                                                and listing are decided after the ranks' keys are merged */,
                                                                int force_ties /* the loop: list a row only for a tie that can change what
                                                                the intersection phase reads (below) */) {
-    constexpr int LDT = DT <= 4 ? 4 : DT <= 8 ? 8 : 16;
     __shared__ uint64_t best[GH_EXTRACT_MAX_K];
     __shared__ uint64_t best2[GH_EXTRACT_MAX_K];
     __shared__ uint64_t red[4 * GH_EXTRACT_MAX_K];
@@ -1132,14 +1131,14 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
         {
             gh_scope t(h, "cdist_prefix");
             const dim3 grid(gx, ys);
-#define GH_CPRE(LL, NP) cdist_prefix_kernel<LL, NP><<<grid, dim3(256), 0, h->stream>>>(a, rr, all, r0, h->cd_R, h->d_cd_vbuf.p, vstride, \
-                                                                                       h->d_cd_cmin.p, h->cd_nchunks)
-            if (npt == 4) {
-                if (h->LD == 4) GH_CPRE(4, 4); else if (h->LD == 8) GH_CPRE(8, 4); else if (h->LD == 16) GH_CPRE(16, 4); else GH_CPRE(0, 4);
-            } else {
-                if (h->LD == 4) GH_CPRE(4, 1); else if (h->LD == 8) GH_CPRE(8, 1); else if (h->LD == 16) GH_CPRE(16, 1); else GH_CPRE(0, 1);
-            }
-#undef GH_CPRE
+            const auto prefix = [&](auto np) {
+                const auto launch = [&](auto ld) {   // 0: any row stride
+                    cdist_prefix_kernel<ld(), np()><<<grid, dim3(256), 0, h->stream>>>(a, rr, all, r0, h->cd_R, h->d_cd_vbuf.p, vstride,
+                                                                                      h->d_cd_cmin.p, h->cd_nchunks);
+                };
+                if (!gh_dispatch_stride(h->LD, launch)) launch(gh_int<0>{});
+            };
+            if (npt == 4) prefix(gh_int<4>{}); else prefix(gh_int<1>{});
             GH_LAUNCH_CHECK();
         }
         if (nth_form && all_rows && h->E <= GH_CD_NTH_MAX) {   // tiny graphs: ATen's nth_element + sort, replayed
@@ -1153,25 +1152,25 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
         const size_t smem = h->K <= 64 ? 0 : sizeof(uint64_t) * (size_t)h->K;
         const inter_args ia = make_inter_args(h, fuse);
         const bool scalar_heap = h->K <= GH_CD_KS && !nth_form;
-#define GH_CREP(DD, HEAPv, INTv) cdist_replay_kernel<DD, HEAPv, INTv><<<dim3((unsigned)h->cd_R), dim3(256), smem, h->stream>>>( \
-        rr, all, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf.p, vstride, h->d_cd_cmin.p, h->cd_nchunks, h->d_cand.p, out_keys, nth_form, ia, h->d_stamps.p, \
-        (int)h->S, (int)(((int64_t)h->n_vblocks + GH_STAMP_EXTRA) * 8 / 32))
-#define GH_CREP_D(DD) case DD: if (scalar_heap) GH_CREP(DD, 0, true); else GH_CREP(DD, 1, true); break;
-        if (fuse) {
-            switch (h->D) {
-                GH_CREP_D(2) GH_CREP_D(3) GH_CREP_D(4) GH_CREP_D(5) GH_CREP_D(6) GH_CREP_D(7) GH_CREP_D(8) GH_CREP_D(9)
-                GH_CREP_D(10) GH_CREP_D(11) GH_CREP_D(12) GH_CREP_D(13) GH_CREP_D(14) GH_CREP_D(15)
-                default: if (scalar_heap) GH_CREP(16, 0, true); else GH_CREP(16, 1, true); break;
+        const auto replay = [&](auto d, auto heap, auto inter) {
+            cdist_replay_kernel<d(), heap(), inter()><<<dim3((unsigned)h->cd_R), dim3(256), smem, h->stream>>>(
+                rr, all, r0, h->cd_R, h->E, h->K, h->d_cd_vbuf.p, vstride, h->d_cd_cmin.p, h->cd_nchunks, h->d_cand.p, out_keys, nth_form, ia,
+                h->d_stamps.p, (int)h->S, (int)(((int64_t)h->n_vblocks + GH_STAMP_EXTRA) * 8 / 32));
+        };
+        if (fuse) {   // (both callers fuse for 2..16 components only)
+            if (!gh_dispatch_dim(h->D, [&](auto d, auto) {
+                    if (scalar_heap) replay(d, gh_int<0>{}, std::true_type{}); else replay(d, gh_int<1>{}, std::true_type{});
+                })) {
+                h->err = "cdist_replay: the fused intersection phase needs 2..16 components";
+                return GH_ERR_RUNTIME;
             }
         } else if (scalar_heap) {
-            GH_CREP(0, 0, false);
+            replay(gh_int<0>{}, gh_int<0>{}, std::false_type{});
         } else if (h->K <= 64) {
-            GH_CREP(0, 1, false);
+            replay(gh_int<0>{}, gh_int<1>{}, std::false_type{});
         } else {
-            GH_CREP(0, 2, false);
+            replay(gh_int<0>{}, gh_int<2>{}, std::false_type{});
         }
-#undef GH_CREP_D
-#undef GH_CREP
         GH_LAUNCH_CHECK();
     }
     return GH_OK;
@@ -1194,26 +1193,22 @@ gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) 
     const int set = h->cd_part ? h->cd_set ^ 1 : h->cd_set;   // (a partitioned engine's search takes its counter set at the merge)
     if (!h->cd_part) h->cd_set ^= 1;
     const cdist_rows rr{h->d_rare.p, h->d_cd_rows.p, h->d_cd_rows.p + h->S, h->d_cd_stat.p + 4 * set, h->d_cd_stat.p + 4 * (set ^ 1)};
-    const bool fuse = !all_rows && !h->cd_part && fuse_intersect && h->K <= 64 && h->D >= 2 && h->D <= 16;
+    const bool fuse = !all_rows && !h->cd_part && fuse_intersect && h->K <= 64 && gh_dim_templated(h->D);
     bool reduce = false;
     if (!all_rows) {
-        if (h->D < 2 || h->D > 16) { h->err = "GH_DIST_CDIST: the candidate selection needs 2..16 components"; return GH_ERR_RUNTIME; }
         // the column sums of the fused kernel's workgroup partials ride along (stats_fix_kernel then skips them)
         reduce = h->new0_ready && h->rows > 0 && h->LD <= 16 && h->S < 2048;
         gh_scope t(h, fuse ? "knn_select_cdist_intersect" : "knn_select_cdist");
         const inter_args ia = make_inter_args(h, fuse);
         const int part_mode = h->cd_part ? 1 : 0;
-#define GH_CSEL(DD)                                                                                                                \
-    knn_select_cdist_kernel<DD><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), 0, h->stream>>>(          \
-        h->d_cand.p, h->d_cnt.p, h->K, a, h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + h->S, rr, ia, (int)h->S, h->d_blockstats.p, h->n_vblocks, \
-        h->d_stats, part_mode, (fuse && !h->cd_all_ties) ? 1 : 0)
-        switch (h->D) {
-            case 2: GH_CSEL(2); break;   case 3: GH_CSEL(3); break;   case 4: GH_CSEL(4); break;   case 5: GH_CSEL(5); break;
-            case 6: GH_CSEL(6); break;   case 7: GH_CSEL(7); break;   case 8: GH_CSEL(8); break;   case 9: GH_CSEL(9); break;
-            case 10: GH_CSEL(10); break; case 11: GH_CSEL(11); break; case 12: GH_CSEL(12); break; case 13: GH_CSEL(13); break;
-            case 14: GH_CSEL(14); break; case 15: GH_CSEL(15); break; default: GH_CSEL(16); break;
+        if (!gh_dispatch_dim(h->D, [&](auto d, auto) {
+                knn_select_cdist_kernel<d()><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), 0, h->stream>>>(
+                    h->d_cand.p, h->d_cnt.p, h->K, a, h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + h->S, rr, ia, (int)h->S, h->d_blockstats.p,
+                    h->n_vblocks, h->d_stats, part_mode, (fuse && !h->cd_all_ties) ? 1 : 0);
+            })) {   // (the candidate lists come from the scan path, which gh_knn_scan_path opens for these dimensions only)
+            h->err = "GH_DIST_CDIST: the candidate selection needs 2..16 components";
+            return GH_ERR_RUNTIME;
         }
-#undef GH_CSEL
         GH_LAUNCH_CHECK();
     }
     if (!h->cd_part) GH_TRY_ST(cdist_replay_rounds(h, a, rr, all_rows, fuse, h->d_partial.p));
@@ -1230,7 +1225,7 @@ gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) 
     const int set = h->cd_set;
     h->cd_set ^= 1;
     const cdist_rows rr{h->d_rare.p, h->d_cd_rows.p, h->d_cd_rows.p + h->S, h->d_cd_stat.p + 4 * set, h->d_cd_stat.p + 4 * (set ^ 1)};
-    const bool fuse = !h->intersect_done && h->K <= 64 && h->D >= 2 && h->D <= 16;
+    const bool fuse = !h->intersect_done && h->K <= 64 && gh_dim_templated(h->D);
     const int total = world * (h->K + 1);
     int n2 = 2;
     while (n2 < total) n2 <<= 1;
@@ -1243,10 +1238,11 @@ gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) 
     {
         gh_scope t(h, fuse ? "knn_merge_cdist_intersect" : "knn_merge_cdist");
         const inter_args ia = make_inter_args(h, fuse);
-#define GH_CMRG(DD) knn_merge_cdist_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2 * (bound ? 2 : 1), h->stream>>>( \
-        gathered, world, h->S, h->K, h->E, h->d_merged.p, rr, ia, h->d_cand.p, bound)
-        if (fuse) { GH_DISPATCH_DIM(h->D, GH_CMRG) } else { GH_CMRG(0); }
-#undef GH_CMRG
+        const auto merge = [&](auto d) {
+            knn_merge_cdist_kernel<d()><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2 * (bound ? 2 : 1), h->stream>>>(
+                gathered, world, h->S, h->K, h->E, h->d_merged.p, rr, ia, h->d_cand.p, bound);
+        };
+        if (!(fuse && gh_dispatch_dim(h->D, [&](auto d, auto) { merge(d); }))) merge(gh_int<0>{});
         GH_LAUNCH_CHECK();
     }
     GH_TRY_ST(cdist_replay_rounds(h, a, rr, false, fuse, h->d_merged.p));

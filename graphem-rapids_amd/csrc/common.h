@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dispatch.h"
+
 #define GH_WAVE 64
 // Neighbour rows a thread of the spring pull has in flight (tuning: -DGH_DEPTH8=.. -DGH_DEPTH16=..)
 #ifndef GH_DEPTH8
@@ -14,12 +16,6 @@
 #define GH_DEPTH16 2
 #endif
 #define GH_GATHER_DEPTH(LD) ((LD) <= 4 ? 8 : (LD) <= 8 ? GH_DEPTH8 : GH_DEPTH16)
-
-// Row stride (floats) of the padded position array for an embedding dimension D:
-// rows are 16-byte aligned so a vertex is fetched with dwordx4 loads.
-__host__ __device__ inline int gh_ld(int D) {
-    return D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : ((D + 3) & ~3);
-}
 
 // torch.norm(x, dim=1) reduction order of the reference's CPU backend (pt.py:623,
 // pt.py:731), squared: full groups of 8 -> eight fma lane accumulators summed left
@@ -203,18 +199,6 @@ __device__ __forceinline__ void spring_pull(const float *__restrict__ pos, const
     }
 }
 
-
-// Embedding dimensions with compile-time kernels (spring pull, fused spring+scan, hub sums, intersection
-// pairs): every D from 2 to 16, so that e.g. n_components = 6 does not fall onto the generic
-// one-thread-per-vertex kernels (2.4-2.8x slower at 1M vertices); larger D use those.  The norm order (gh_sumsq<D>) is the reference's for every D, so each D is its own
-// instantiation rather than a padded neighbour.
-__host__ __device__ inline bool gh_dim_templated(int D) {
-    return D >= 2 && D <= 16;
-}
-// X(D, LD) for every templated dimension
-#define GH_FOR_EACH_DIM(X)                                                                                    \
-    X(2, 4) X(3, 4) X(4, 4) X(5, 8) X(6, 8) X(7, 8) X(8, 8) X(9, 16) X(10, 16) X(11, 16) X(12, 16) X(13, 16) X(14, 16) \
-        X(15, 16) X(16, 16)
 
 // ---------------------------------------------------------------------------------
 // Long rows (hubs).  A thread walking a pull list of thousands of entries eight gathers at a time

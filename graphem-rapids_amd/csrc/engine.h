@@ -200,7 +200,7 @@ struct gh_engine {
     gh_dev<int32_t> d_cd_stat;        // two sets (used alternately) of [0] listed rows, [1] rows whose tie order ATen leaves to std::nth_element (not reproduced), [2] the longest prefix
     int cd_R = 0, cd_nchunks = 0, cd_set = 0;   // cd_set: the counter set the NEXT search uses
 
-    // grid KNN (grid.hip; GH_KNN_GRID)
+    // grid KNN (grid_core.h; GH_KNN_GRID)
     int grid_G = 0, grid_bits = 0;
     int64_t grid_cells = 0;
     size_t grid_temp_bytes = 0;
@@ -324,7 +324,7 @@ gh_status gh_knn_points_device(hipStream_t stream, const float *d_q, int64_t nq,
 gh_status gh_cdist_alloc(gh_engine *h);
 gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world);   // row partitions: the ranks' (S, K + 2) records -> d_merged, the reference's rows
 gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect);   // candidate lists (or nothing) -> d_partial, the reference's rows
-// grid.hip
+// grid_core.h
 bool gh_grid_path(const gh_engine *h);
 gh_status gh_grid_alloc(gh_engine *h);
 gh_status gh_grid_search(gh_engine *h);            // d_mid + tau -> candidate lists

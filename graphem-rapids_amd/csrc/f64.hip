@@ -748,8 +748,6 @@ void f64_refresh_pos4(gh_engine *h) {
     gh_f64 *f = h->f64.get();
     if (f->pos4.p) f64_pad4_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos.p, h->n, h->D, f->pos4.p, f->pmax.p);
 }
-template <typename K2, typename K3, typename K4>
-void f64_by_dim(int D, K2 k2, K3 k3, K4 k4) { if (D == 2) k2(); else if (D == 3) k3(); else k4(); }
 
 gh_status f64_knn(gh_engine *h, const int32_t *host_ids, bool pos4_fresh = false) {
     gh_f64 *f = h->f64.get();
@@ -766,31 +764,27 @@ gh_status f64_knn(gh_engine *h, const int32_t *host_ids, bool pos4_fresh = false
     }
     if (f->pos4.p) {
         if (!pos4_fresh) f64_refresh_pos4(h);
-#define F64_MID4(DD) f64_mid4_kernel<DD><<<dim3(f64_grid(h->E)), dim3(256), 0, h->stream>>>(f->pos4.p, f->edges.p, h->E, f->mid.p, std::max<int64_t>(f->stride, 1), f->stride > 0 ? f->sub.p : nullptr)
-        f64_by_dim(h->D, [&] { F64_MID4(2); }, [&] { F64_MID4(3); }, [&] { F64_MID4(4); });
-#undef F64_MID4
+        gh_dispatch_value<2, 3, 4>(h->D, [&](auto d) {   // (pos4 exists for these dimensions only)
+            f64_mid4_kernel<d()><<<dim3(f64_grid(h->E)), dim3(256), 0, h->stream>>>(f->pos4.p, f->edges.p, h->E, f->mid.p, std::max<int64_t>(f->stride, 1), f->stride > 0 ? f->sub.p : nullptr);
+        });
     } else {
         f64_mid_kernel<<<dim3(f64_grid(h->E * h->D)), dim3(256), 0, h->stream>>>(f->pos.p, f->edges.p, h->E, h->D, f->mid.p, f->stride, f->sub.p);
     }
     if (f->stride > 0) {
         f64_knn_kernel<1><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid.p, h->E, h->D, f->sampled.p, h->K, f->knn.p, f->fail.p, f->stride, f->tq.p, f->cnt.p,
                                                                              f->cand_d.p, f->cand_i.p, f->sub.p, f->qaux.p, (h->D == 2 || h->D == 3) ? f->qA.p : nullptr, f->pmax.p, (int)f64_grid(h->n));
-#define F64_FILTER(DD, UU) f64_filter_kernel<DD, UU, (DD > 0 && UU % 2 == 0)><<<dim3((unsigned)((h->E + 256 * UU - 1) / (256 * UU))), dim3(256), 0, h->stream>>>( \
-        f->mid.p, h->E, h->D, f->sampled.p, h->S, f->tq.p, f->cnt.p, f->cand_d.p, f->cand_i.p)
-#define F64_FILTER3(DD) f64_filter_mf_kernel<DD><<<dim3((unsigned)((h->E + 511) / 512)), dim3(256), 0, h->stream>>>( \
-        f->mid.p, h->E, f->sampled.p, (int)h->S, f->tq.p, f->qaux.p, f->qA.p, f->cnt.p, f->cand_d.p, f->cand_i.p)
-        switch (h->D) {
-            case 2: F64_FILTER3(2); break;
-            case 3: F64_FILTER3(3); break;
-            case 4: F64_FILTER(4, 4); break;
-            case 5: F64_FILTER(5, 2); break;
-            case 6: F64_FILTER(6, 2); break;
-            case 8: F64_FILTER(8, 2); break;
-            case 16: F64_FILTER(16, 2); break;
-            default: F64_FILTER(0, 1); break;
-        }
-#undef F64_FILTER
-#undef F64_FILTER3
+        // 2, 3: the matrix-pipe filter; 4, 5, 6, 8, 16: the dimension's own kernel, U references per thread; 0: any dimension
+        const auto filter = [&](auto d, auto u) {
+            f64_filter_kernel<d(), u(), (d() > 0 && u() % 2 == 0)><<<dim3((unsigned)((h->E + 256 * u() - 1) / (256 * u()))), dim3(256), 0, h->stream>>>(
+                f->mid.p, h->E, h->D, f->sampled.p, h->S, f->tq.p, f->cnt.p, f->cand_d.p, f->cand_i.p);
+        };
+        if (!gh_dispatch_value<2, 3>(h->D, [&](auto d) {
+                f64_filter_mf_kernel<d()><<<dim3((unsigned)((h->E + 511) / 512)), dim3(256), 0, h->stream>>>(
+                    f->mid.p, h->E, f->sampled.p, (int)h->S, f->tq.p, f->qaux.p, f->qA.p, f->cnt.p, f->cand_d.p, f->cand_i.p);
+            }) &&
+            !gh_dispatch_value<4>(h->D, [&](auto d) { filter(d, gh_int<4>{}); }) &&
+            !gh_dispatch_value<5, 6, 8, 16>(h->D, [&](auto d) { filter(d, gh_int<2>{}); }))
+            filter(gh_int<0>{}, gh_int<1>{});
         f64_knn_kernel<2><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(f->mid.p, h->E, h->D, f->sampled.p, h->K, f->knn.p, f->fail.p, f->stride, f->tq.p, f->cnt.p,
                                                                              f->cand_d.p, f->cand_i.p, nullptr);
     } else {
@@ -806,9 +800,9 @@ void f64_launch_spring(gh_engine *h) {
     gh_f64 *f = h->f64.get();
     if (f->pos4.p) {
         f64_refresh_pos4(h);
-#define F64_SPR4(DD) f64_spring4_kernel<DD><<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos4.p, f->rowptr.p, f->adj.p, h->n, f->L_min, -f->k_attr, f->Fs.p)
-        f64_by_dim(h->D, [&] { F64_SPR4(2); }, [&] { F64_SPR4(3); }, [&] { F64_SPR4(4); });
-#undef F64_SPR4
+        gh_dispatch_value<2, 3, 4>(h->D, [&](auto d) {   // (pos4 exists for these dimensions only)
+            f64_spring4_kernel<d()><<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos4.p, f->rowptr.p, f->adj.p, h->n, f->L_min, -f->k_attr, f->Fs.p);
+        });
     } else {
         f64_spring_kernel<<<dim3(f64_grid(h->n)), dim3(256), 0, h->stream>>>(f->pos.p, h->D, f->rowptr.p, f->adj.p, h->n, f->L_min, -f->k_attr, f->Fs.p);
     }

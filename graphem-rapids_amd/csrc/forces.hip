@@ -576,7 +576,7 @@ __global__ __launch_bounds__(256) void intersect_kernel(const float *__restrict_
     // neighbour c of query r is key column c+1: column 0 is dropped blindly (pt.py:421)
     const int32_t i = sampled[r], j = (int32_t)gh_key_id(keys[r * (k + 1) + (t - r * k) + 1]);
     if constexpr (DT >= 2)
-        gh_intersect_pair_t<DT, (DT <= 4 ? 4 : DT <= 8 ? 8 : 16)>(pos, edges, i, j, k_inter, acc, tflag, touched, tcount, own_lo, own_hi);
+        gh_intersect_pair_t<DT, gh_ld(DT)>(pos, edges, i, j, k_inter, acc, tflag, touched, tcount, own_lo, own_hi);
     else
         gh_intersect_pair(pos, D, LD, edges, i, j, k_inter, acc, tflag, touched, tcount, scratch + t * LD, own_lo, own_hi);
 }
@@ -671,41 +671,32 @@ __global__ __launch_bounds__(256) void arith_selftest_kernel(uint64_t seed, int6
 
 inline unsigned grid_for(int64_t total, int bs) { return (unsigned)((total + bs - 1) / bs); }
 
-bool spring_is_templated(int D) { return gh_dim_templated(D); }
-
 // WRITE_MID only when the engine's edge range follows row ownership (h->fused_mid).
 template <bool WRITE_MID>
 gh_status launch_spring(gh_engine *h, float *outF, int64_t f_row0) {
     const unsigned grid = grid_for(h->rows, 256);
     const float neg_k = -h->prm.k_attr;
     const gh_long_args la = gh_make_long_args(h);
-#define GH_SPRING_ARGS h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->mid_base, h->part.row_lo, h->rows, \
-                       h->prm.L_min, neg_k, outF, f_row0, h->d_mid.p, la
-#define GH_SPRING_CASE(DD, LL)                                                                              \
-    if (la.n > 0) spring_kernel<DD, LL, WRITE_MID, true><<<dim3(grid), dim3(256), 0, h->stream>>>(GH_SPRING_ARGS); \
-    else spring_kernel<DD, LL, WRITE_MID, false><<<dim3(grid), dim3(256), 0, h->stream>>>(GH_SPRING_ARGS)
     GH_TRY_ST(gh_launch_spring_long(h, outF, f_row0));  // hubs first: spring_row reads their forces back
-#define GH_SPRING_ONE(DD, LL) case DD: GH_SPRING_CASE(DD, LL); break;
-    switch (h->D) {
-        GH_FOR_EACH_DIM(GH_SPRING_ONE)
-        default:
-            spring_generic_kernel<<<dim3(grid), dim3(256), 0, h->stream>>>(
-                h->d_pos.p, h->D, h->LD, h->d_rowptr.p, h->d_adj.p, h->part.row_lo, h->rows, h->prm.L_min, neg_k, outF,
-                f_row0, h->d_tmpF2.p);
-    }
-#undef GH_SPRING_ONE
-#undef GH_SPRING_CASE
-#undef GH_SPRING_ARGS
+    const auto spring = [&](auto d, auto ld, auto has_long) {
+        spring_kernel<d(), ld(), WRITE_MID, has_long()><<<dim3(grid), dim3(256), 0, h->stream>>>(
+            h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->mid_base, h->part.row_lo, h->rows, h->prm.L_min, neg_k,
+            outF, f_row0, h->d_mid.p, la);
+    };
+    if (!gh_dispatch_dim(h->D, [&](auto d, auto ld) {
+            if (la.n > 0) spring(d, ld, std::true_type{}); else spring(d, ld, std::false_type{});
+        }))
+        spring_generic_kernel<<<dim3(grid), dim3(256), 0, h->stream>>>(
+            h->d_pos.p, h->D, h->LD, h->d_rowptr.p, h->d_adj.p, h->part.row_lo, h->rows, h->prm.L_min, neg_k, outF,
+            f_row0, h->d_tmpF2.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
 
 }  // namespace
 
-static bool spring_is_templated_d(int D) { return gh_dim_templated(D); }
-
 gh_long_args gh_make_long_args(const gh_engine *h, bool coop_mid) {
-    if (h->nlong == 0 || !spring_is_templated_d(h->D)) return gh_long_args{nullptr, nullptr, nullptr, 0, h->long_deg, nullptr, nullptr, nullptr};
+    if (h->nlong == 0 || !gh_dim_templated(h->D)) return gh_long_args{nullptr, nullptr, nullptr, 0, h->long_deg, nullptr, nullptr, nullptr};
     const bool coop = coop_mid && h->d_own_long.p && h->d_own_eids.p;
     return gh_long_args{h->d_long_rows.p, h->d_long_ownptr.p, h->d_long_ownadj.p, h->nlong, h->long_deg,
                         coop ? h->d_own_long.p : nullptr, h->d_own_eids.p, h->d_edges.p};
@@ -777,33 +768,19 @@ gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0) {
     if (la.n == 0) return GH_OK;
     gh_scope t(h, "spring_long");
     const float neg_k = -h->prm.k_attr;
-    if (h->long_max_deg <= GH_LONG_ONE_LAUNCH_MAX_DEG) {
-#define GH_LONG_FUSED(DD, LL)                                                                                                 \
-    case DD:                                                                                                                  \
-        long_rows_kernel<DD, LL><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(                                \
-            h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, la.n, h->part.row_lo, h->prm.L_min, neg_k, outF, f_row0); \
-        break;
-        switch (h->D) {
-            GH_FOR_EACH_DIM(GH_LONG_FUSED)
-            default: break;
+    // (gh_make_long_args returns no long rows for a dimension outside the dispatcher's domain)
+    gh_dispatch_dim(h->D, [&](auto d, auto ld) {
+        if (h->long_max_deg <= GH_LONG_ONE_LAUNCH_MAX_DEG) {
+            long_rows_kernel<d(), ld()><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(
+                h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, la.n, h->part.row_lo, h->prm.L_min, neg_k, outF, f_row0);
+            return;
         }
-#undef GH_LONG_FUSED
-        GH_LAUNCH_CHECK();
-        return GH_OK;
-    }
-#define GH_LONG_CASE(DD, LL)                                                                                          \
-    long_terms_kernel<DD, LL><<<dim3(grid_for(h->long_entries, 256)), dim3(256), 0, h->stream>>>(                       \
-        h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, h->d_long_erow.p, (int)h->long_entries, h->part.row_lo, \
-        h->prm.L_min, neg_k, h->d_long_terms.p);                                                                        \
-    long_sum_kernel<DD, LL><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(h->d_long_terms.p, la.rows, \
-                                                                                          h->d_long_eptr.p, la.n, outF, f_row0)
-#define GH_LONG_ONE(DD, LL) case DD: GH_LONG_CASE(DD, LL); break;
-    switch (h->D) {
-        GH_FOR_EACH_DIM(GH_LONG_ONE)
-        default: break;  // gh_make_long_args returns none for other dimensions
-    }
-#undef GH_LONG_ONE
-#undef GH_LONG_CASE
+        long_terms_kernel<d(), ld()><<<dim3(grid_for(h->long_entries, 256)), dim3(256), 0, h->stream>>>(
+            h->d_pos.p, h->d_rowptr.p, h->d_adj.p, la.rows, h->d_long_eptr.p, h->d_long_erow.p, (int)h->long_entries, h->part.row_lo,
+            h->prm.L_min, neg_k, h->d_long_terms.p);
+        long_sum_kernel<d(), ld()><<<dim3((unsigned)((la.n + 3) / 4)), dim3(256), 0, h->stream>>>(h->d_long_terms.p, la.rows,
+                                                                                                  h->d_long_eptr.p, la.n, outF, f_row0);
+    });
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -824,7 +801,7 @@ gh_status launch_mid_gather(gh_engine *h) {
 
 // Spring forces of the own rows -> d_Fs, and the midpoints of the own edges -> d_mid.
 gh_status gh_launch_spring_mid(gh_engine *h) {
-    const bool fused = h->fused_mid && spring_is_templated(h->D);
+    const bool fused = h->fused_mid && gh_dim_templated(h->D);
     if (h->rows > 0) {
         gh_scope t(h, fused ? "spring_mid" : "spring");
         gh_status st = fused ? launch_spring<true>(h, h->d_Fs.p, 0) : launch_spring<false>(h, h->d_Fs.p, 0);
@@ -843,15 +820,16 @@ gh_status gh_launch_integrate(gh_engine *h) {
         h->new0_ready = false;
         gh_scope t(h, "stats_fix");
         const struct reset_flag { gh_engine *e; ~reset_flag() { e->stats_reduced = false; } } reset{h};
-#define GH_FIX_CASE(LL)                                                                                      \
-    stats_fix_kernel<LL><<<dim3(gh_fix_blocks(LL)), dim3(256), 0, h->stream>>>(                                  \
-        h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo, \
-        h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0, h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr, \
-        h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap)
-        if (h->LD == 4) GH_FIX_CASE(4);
-        else if (h->LD == 8) GH_FIX_CASE(8);
-        else GH_FIX_CASE(16);
-#undef GH_FIX_CASE
+        if (!gh_dispatch_stride(h->LD, [&](auto ld) {
+                stats_fix_kernel<ld()><<<dim3(gh_fix_blocks(ld())), dim3(256), 0, h->stream>>>(
+                    h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo,
+                    h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0,
+                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr,
+                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap);
+            })) {   // unreachable: only gh_launch_spring_scan sets new0_ready, and it needs one of these strides
+            h->err = "stats_fix: the fused step left its sums for a row stride other than 4, 8 or 16";
+            return GH_ERR_RUNTIME;
+        }
         GH_LAUNCH_CHECK();
         return GH_OK;
     }
@@ -871,23 +849,12 @@ gh_status gh_launch_integrate(gh_engine *h) {
     float *wide_out = h->d_new;
     {
         gh_scope t(h, "integrate");
-        switch (h->LD) {
-            case 4:
-                integrate_kernel<4><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
-                                                                            h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
-                break;
-            case 8:
-                integrate_kernel<8><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
-                                                                            h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
-                break;
-            case 16:
-                integrate_kernel<16><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows,
-                                                                             h->d_acc.p, h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
-                break;
-            default:
-                integrate_generic_kernel<<<dim3(grid_for(h->rows * h->LD, 256)), dim3(256), 0, h->stream>>>(
-                    h->d_pos.p, h->d_Fs.p, h->LD, h->part.row_lo, h->rows, h->d_acc.p, h->d_tflag.p, wide_out);
-        }
+        if (!gh_dispatch_stride(h->LD, [&](auto ld) {
+                integrate_kernel<ld()><<<dim3(grid), dim3(256), 0, h->stream>>>(h->d_pos.p, h->d_Fs.p, h->part.row_lo, h->rows, h->d_acc.p,
+                                                                               h->d_tflag.p, h->d_new, h->d_blockstats.p, pc, pr, pcap);
+            }))
+            integrate_generic_kernel<<<dim3(grid_for(h->rows * h->LD, 256)), dim3(256), 0, h->stream>>>(
+                h->d_pos.p, h->d_Fs.p, h->LD, h->part.row_lo, h->rows, h->d_acc.p, h->d_tflag.p, wide_out);
         GH_LAUNCH_CHECK();
     }
     gh_scope t(h, "stats_reduce");
@@ -915,20 +882,12 @@ gh_status gh_launch_intersect(gh_engine *h) {
     const bool own_only = h->rows != h->n;
     const int32_t own_lo = own_only ? (int32_t)h->part.row_lo : 0, own_hi = own_only ? (int32_t)h->part.row_hi : 0x7FFFFFFF;
     gh_scope t(h, "intersect");
-#define GH_INTER_ONE(DD, LL)                                                                                       \
-    case DD:                                                                                                       \
-        intersect_kernel<DD><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(                                   \
-            h->d_pos.p, h->D, h->LD, h->d_edges.p, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc.p, \
-            h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p, own_lo, own_hi);                         \
-        break;
-    switch (h->D) {
-        GH_FOR_EACH_DIM(GH_INTER_ONE)
-        default:
-            intersect_kernel<0><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(
-                h->d_pos.p, h->D, h->LD, h->d_edges.p, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc.p,
-                h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p, own_lo, own_hi);
-    }
-#undef GH_INTER_ONE
+    const auto intersect = [&](auto d) {   // 0: any dimension (the scratch form)
+        intersect_kernel<d()><<<dim3(grid_for(P, 256)), dim3(256), 0, h->stream>>>(
+            h->d_pos.p, h->D, h->LD, h->d_edges.p, h->sample.ids, h->d_keys_cur, h->S, h->k, h->prm.k_inter, h->d_acc.p,
+            h->d_tflag.p, h->d_touched.p, h->d_tcount.p, h->d_iscratch.p, own_lo, own_hi);
+    };
+    if (!gh_dispatch_dim(h->D, [&](auto d, auto) { intersect(d); })) intersect(gh_int<0>{});
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -1003,19 +962,16 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
     float *packed = stats_all && h->packed_exchange ? h->d_rows_packed.p + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
     const int ldt = stats_all ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
-#define GH_NORM(LL)                                                                                                      \
-    normalise_kernel<LL><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(                                                 \
-        src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p, \
-        gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,                                                      \
-        h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed)
-    if (ldt == 4) GH_NORM(4);
-    else if (ldt == 8) GH_NORM(8);
-    else if (ldt == 16) GH_NORM(16);
-    else {
+    const auto normalise = [&](auto ld) {   // 0: any row stride, no set-up tiles
+        normalise_kernel<ld()><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(
+            src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p,
+            gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,
+            h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed);
+    };
+    if (!gh_dispatch_stride(ldt, normalise)) {
         if (sa.tiles > 0) { h->err = "KNN set-up tiles need a row stride of 4, 8 or 16"; return GH_ERR_RUNTIME; }
-        GH_NORM(0);
+        normalise(gh_int<0>{});
     }
-#undef GH_NORM
     GH_LAUNCH_CHECK();
     gh_set_lookahead(h, next);
     return GH_OK;

@@ -795,27 +795,17 @@ gh_status gh_launch_spring_scan(gh_engine *h) {
     if (h->n_vblocks == 0) return GH_OK;
     GH_TRY_ST(gh_launch_spring_long(h, h->d_Fs.p, 0));  // hubs first: their rows' forces are read back in phase A
     gh_scope t(h, "spring_scan");
-    if (fused_mfma(h->LD, h->D, h->S) && h->D > 3) {
-        switch (h->D) {
-            case 4: launch_mfmaw<4, 4>(h); break;
-            case 5: launch_mfmaw<5, 8>(h); break;
-            case 6: launch_mfmaw<6, 8>(h); break;
-            case 7: launch_mfmaw<7, 8>(h); break;
-            case 8: launch_mfmaw<8, 8>(h); break;
-            case 9: launch_mfmaw<9, 16>(h); break;
-            case 10: launch_mfmaw<10, 16>(h); break;
-            case 11: launch_mfmaw<11, 16>(h); break;
-            case 12: launch_mfmaw<12, 16>(h); break;
-            case 13: launch_mfmaw<13, 16>(h); break;
-            case 14: launch_mfmaw<14, 16>(h); break;
-            case 15: launch_mfmaw<15, 16>(h); break;
-            default: launch_mfmaw<16, 16>(h); break;
-        }
+    bool launched = false;
+    if (fused_mfma(h->LD, h->D, h->S) && h->D > 3) {   // the wide form: 4..16
+        launched = gh_dispatch_dim(h->D, [&](auto d, auto ld) {
+            if constexpr (d() > 3) launch_mfmaw<d(), ld()>(h);
+        });
     } else if (h->qcells) {
-        if (h->D == 2) launch_cells<2>(h); else launch_cells<3>(h);
+        launched = gh_dispatch_value<2, 3>(h->D, [&](auto d) { launch_cells<d()>(h); });
     } else if (fused_mfma(h->LD, h->D, h->S)) {
-        if (h->D == 2) launch_mfma<2, 2>(h); else launch_mfma<3, 2>(h);
-    } else {
+        launched = gh_dispatch_value<2, 3>(h->D, [&](auto d) { launch_mfma<d(), 2>(h); });
+    }
+    if (!launched) {   // unreachable: fused_scan needs gh_dim_templated(D) (graph_plan.hip), fused_mfma() a row stride of 4, 8 or 16
         h->err = "fused spring+scan launched for an unsupported dimension";
         return GH_ERR_RUNTIME;
     }

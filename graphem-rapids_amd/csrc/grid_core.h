@@ -365,8 +365,9 @@ gh_status gh_grid_search(gh_engine *h) {
         gh_scope t(h, "grid_build");
         grid_frame_kernel<<<dim3(1), dim3(256), 0, h->stream>>>(h->d_q.p, QS, h->S, std::min(h->D, 3), h->grid_G / 2, h->D >= 3 ? 23 - 4 : 23 - 7, frame,
                                                                   h->tcount_reset_pending ? h->d_tcount.p : nullptr);
-        if (h->D == 2) grid_cell_kernel<2><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
-        else grid_cell_kernel<3><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
+        gh_dispatch_value<2, 3>(h->D, [&](auto d) {   // (any other dimension: the error below)
+            grid_cell_kernel<d()><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
+        });
         size_t temp = h->grid_temp_bytes;
         GH_HIP(hipcub::DeviceRadixSort::SortPairs(h->d_grid_temp.p, temp, keys, skeys, rows, srows, (int)M, 0, h->grid_bits, h->stream));
         grid_gather_kernel<<<dim3((unsigned)((M * LD4 + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, LD4, srows, M, h->part.edge_lo,
@@ -376,17 +377,16 @@ gh_status gh_grid_search(gh_engine *h) {
     gh_scope t(h, "grid_tau_scan");
     const int64_t fb_stride = M >= 8 * 64 * (int64_t)h->K ? 8 : 1;   // sparse queries only: a tight bound keeps their boxes small
     const dim3 sgrid((unsigned)h->S, h->S <= 2048 ? 32 : h->S <= 16384 ? 16 : 4);   // an outlier's box can hold the whole bulk: its runs over several workgroups
-#define GH_GRID_ONE(DD, LL)                                                                                                              \
-    case DD:                                                                                                                              \
-        grid_tau_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(smid, skeys, (int)M, frame, h->d_q.p, h->K);               \
-        grid_tau_fallback_kernel<DD, LL><<<dim3((unsigned)h->S), dim3(1024), 0, h->stream>>>(smid, M, fb_stride, h->d_q.p, h->K);             \
-        grid_scan_kernel<DD, LL><<<sgrid, dim3(256), 0, h->stream>>>(smid, sid, skeys, (int)M, frame, h->d_q.p, h->d_cand.p, h->d_cnt.p);    \
-        break;
-    switch (h->D) {
-        GH_FOR_EACH_DIM(GH_GRID_ONE)
-        default: h->err = "grid KNN: unsupported dimension"; return GH_ERR_RUNTIME;
+    // 2 or 3 components only (gh_grid_path)
+    if (!gh_dispatch_value<2, 3>(h->D, [&](auto d) {
+            constexpr int LD = gh_ld(d());
+            grid_tau_kernel<d(), LD><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(smid, skeys, (int)M, frame, h->d_q.p, h->K);
+            grid_tau_fallback_kernel<d(), LD><<<dim3((unsigned)h->S), dim3(1024), 0, h->stream>>>(smid, M, fb_stride, h->d_q.p, h->K);
+            grid_scan_kernel<d(), LD><<<sgrid, dim3(256), 0, h->stream>>>(smid, sid, skeys, (int)M, frame, h->d_q.p, h->d_cand.p, h->d_cnt.p);
+        })) {
+        h->err = "grid KNN: unsupported dimension";
+        return GH_ERR_RUNTIME;
     }
-#undef GH_GRID_ONE
     GH_LAUNCH_CHECK();
     return GH_OK;
 }

@@ -167,10 +167,12 @@ __device__ __forceinline__ void gh_intersect_pair_any(const float *__restrict__ 
                                                       float k_inter, double *__restrict__ acc,
                                                       int32_t *__restrict__ tflag, int32_t *__restrict__ touched,
                                                       int32_t *__restrict__ tcount, float *__restrict__ diff) {
-#define GH_INTERSECT_ONE(DD, LL) \
-    case DD: gh_intersect_pair_t<DD, LL>(pos, edges, i, j, k_inter, acc, tflag, touched, tcount); break;
+#define GH_INTERSECT_ONE(DD) \
+    case DD: gh_intersect_pair_t<DD, gh_ld(DD)>(pos, edges, i, j, k_inter, acc, tflag, touched, tcount); break;
     switch (D) {
-        GH_FOR_EACH_DIM(GH_INTERSECT_ONE)
+        GH_INTERSECT_ONE(2) GH_INTERSECT_ONE(3) GH_INTERSECT_ONE(4) GH_INTERSECT_ONE(5) GH_INTERSECT_ONE(6)
+        GH_INTERSECT_ONE(7) GH_INTERSECT_ONE(8) GH_INTERSECT_ONE(9) GH_INTERSECT_ONE(10) GH_INTERSECT_ONE(11)
+        GH_INTERSECT_ONE(12) GH_INTERSECT_ONE(13) GH_INTERSECT_ONE(14) GH_INTERSECT_ONE(15) GH_INTERSECT_ONE(16)
         default: gh_intersect_pair(pos, D, LD, edges, i, j, k_inter, acc, tflag, touched, tcount, diff);
     }
 #undef GH_INTERSECT_ONE

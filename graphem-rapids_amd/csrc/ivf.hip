@@ -564,7 +564,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float *__restrict__
                                                        const float *__restrict__ qt, const float *__restrict__ qscan,
                                                        uint64_t *__restrict__ cand, int32_t *__restrict__ cnt) {
     constexpr int R = GH_IVF_TILE / 256;
-    constexpr int LD = D <= 4 ? 4 : D <= 8 ? 8 : 16;
+    constexpr int LD = gh_ld(D);
     constexpr int QS = D <= 3 ? 4 : LD + 4;
     constexpr int QT = D <= 3 ? 3 : LD;
     __shared__ float4 qsh[(GH_SCAN_QGROUP + 1) * (QS / 4)];
@@ -882,8 +882,10 @@ extern "C" gh_status gh_knn_ivf_config(gh_handle h, int32_t *lists, int32_t *pro
     return GH_OK;
 }
 
-// d_mid (this iteration's own midpoints) + the query records -> tau of every query and its candidate list.
-gh_status gh_ivf_search(gh_engine *h) {
+// The lists of this iteration and what each query probes of them, for the row stride LD: centroids, assignment, list
+// layout, probe -> group minima for the thresholds and the (list, query) pairs of the scan.
+template <int LD>
+static gh_status ivf_build_and_probe(gh_engine *h) {
     gh_ivf *v = h->ivf.get();
     const int64_t M = v->M;
     const int C = v->C, P = v->P, QS = gh_qs(h->D, h->LD), S = (int)h->S;
@@ -894,37 +896,24 @@ gh_status gh_ivf_search(gh_engine *h) {
     // 1024 ... 8192
     const int64_t probed = (int64_t)P * (M / C);
     const int tau_members = v->exact ? std::max(4096, 16 * h->Ksel) /* a tight threshold keeps the ball small */ : (int)std::min<int64_t>(8192, std::max<int64_t>(std::max(1024, 16 * h->Ksel), probed / (h->D > 8 ? 16 : 64)));
-#define GH_IVF_LD(X)                          \
-    switch (h->LD) {                          \
-        case 4: { X(4) } break;               \
-        case 8: { X(8) } break;               \
-        default: { X(16) } break;             \
-    }
     {
         gh_scope t(h, "ivf_build");
         GH_HIP(hipMemsetAsync(v->lids, 0xFF, sizeof(uint32_t) * (size_t)v->cap_rows, h->stream));
-#define GH_X(L) ivf_centroid_kernel<L><<<dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, C, v->cent, v->A, v->cnorm, v->count, v->lqcount, v->r2);
-        GH_IVF_LD(GH_X)
-#undef GH_X
+        ivf_centroid_kernel<LD><<<dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, C, v->cent, v->A, v->cnorm, v->count, v->lqcount, v->r2);
         GH_LAUNCH_CHECK();
     }
     {
         gh_scope t(h, "ivf_assign");
         const size_t lds = (size_t)C * 44;
-#define GH_X(L)                                                                                                                                  \
-    if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_assign_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    ivf_assign_kernel<L><<<dim3((unsigned)v->awgs), dim3(256), lds, h->stream>>>(h->d_mid.p, M, v->share, C, v->A, v->cnorm, v->assign, v->rank, v->count, v->wgbase, v->r2);
-        GH_IVF_LD(GH_X)
-#undef GH_X
+        if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_assign_kernel<LD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ivf_assign_kernel<LD><<<dim3((unsigned)v->awgs), dim3(256), lds, h->stream>>>(h->d_mid.p, M, v->share, C, v->A, v->cnorm, v->assign, v->rank, v->count, v->wgbase, v->r2);
         GH_LAUNCH_CHECK();
     }
     {
         gh_scope t(h, "ivf_layout");
         ivf_list_layout_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(v->count, C, v->lcount, v->lstart, v->tile_list, v->meta);
         const int Q = h->LD / 4;
-#define GH_X(L) ivf_scatter_kernel<L><<<dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, v->assign, v->rank, v->lstart, v->wgbase, v->share, C, h->part.edge_lo, h->d_own_eids.p, v->lmid, v->lids);
-        GH_IVF_LD(GH_X)
-#undef GH_X
+        ivf_scatter_kernel<LD><<<dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, h->stream>>>(h->d_mid.p, M, v->assign, v->rank, v->lstart, v->wgbase, v->share, C, h->part.edge_lo, h->d_own_eids.p, v->lmid, v->lids);
         GH_LAUNCH_CHECK();
     }
     {
@@ -932,65 +921,44 @@ gh_status gh_ivf_search(gh_engine *h) {
         const unsigned pb = (unsigned)((S + 15) / 16);
         const int nv = (C + 63) / 64;
         const size_t lds = (size_t)C * 40;
-#define GH_PROBE2(L, NVv, EX)                                                                                                                         \
-    {                                                                                                                                                 \
-        if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_probe_kernel<L, NVv, EX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        ivf_probe_kernel<L, NVv, EX><<<dim3(pb), dim3(1024), lds, h->stream>>>(h->d_q.p, QS, S, h->D, v->A, v->cnorm, C, P, h->Ksel, v->lstart, v->lcount, v->lmid, \
-                                                                              tau_members, v->r2, v->pair_l, v->pair_slot, v->lqcount,                \
-                                                                              reinterpret_cast<uint32_t *>(h->d_gmin.p), h->d_cnt.p);                \
-    }
-#define GH_PROBE(L, NVv)                      \
-    if (v->exact) GH_PROBE2(L, NVv, true)     \
-    else GH_PROBE2(L, NVv, false)
-#define GH_X(L)                               \
-    if (nv <= 8) { GH_PROBE(L, 8) }           \
-    else if (nv <= 16) { GH_PROBE(L, 16) }    \
-    else { GH_PROBE(L, 32) }
-        GH_IVF_LD(GH_X)
-#undef GH_X
-#undef GH_PROBE2
-#undef GH_PROBE
+        const auto probe = [&](auto nvc, auto exact) -> gh_status {
+            if (lds > 48 * 1024) GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_probe_kernel<LD, nvc(), exact()>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ivf_probe_kernel<LD, nvc(), exact()><<<dim3(pb), dim3(1024), lds, h->stream>>>(h->d_q.p, QS, S, h->D, v->A, v->cnorm, C, P, h->Ksel, v->lstart, v->lcount, v->lmid,
+                                                                                        tau_members, v->r2, v->pair_l, v->pair_slot, v->lqcount,
+                                                                                        reinterpret_cast<uint32_t *>(h->d_gmin.p), h->d_cnt.p);
+            return GH_OK;
+        };
+        const auto probe_nv = [&](auto nvc) { return v->exact ? probe(nvc, std::true_type{}) : probe(nvc, std::false_type{}); };
+        GH_TRY_ST(nv <= 8 ? probe_nv(gh_int<8>{}) : nv <= 16 ? probe_nv(gh_int<16>{}) : probe_nv(gh_int<32>{}));
         ivf_query_layout_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(v->lqcount, C, v->qstart);
         const int64_t npairs = (int64_t)S * P;
         ivf_pair_scatter_kernel<<<dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, h->stream>>>(v->pair_l, v->pair_slot, npairs, P, v->qstart, v->pair_q);
         GH_LAUNCH_CHECK();
     }
+    return GH_OK;
+}
+
+// d_mid (this iteration's own midpoints) + the query records -> tau of every query and its candidate list.
+gh_status gh_ivf_search(gh_engine *h) {
+    gh_ivf *v = h->ivf.get();
+    // gh_ivf_path: 2 <= D and a row stride of at most 16, so both dispatchers below find their kernels
+    gh_status st = GH_ERR_RUNTIME;
+    if (!gh_dispatch_stride(h->LD, [&](auto ld) { st = ivf_build_and_probe<ld()>(h); })) h->err = "ivf_search: row stride other than 4, 8 or 16";
+    GH_TRY_ST(st);
     GH_TRY_ST(gh_knn_thresholds(h, GH_IVF_GROUPS));
     {
         gh_scope t(h, "ivf_scan");
         const dim3 grid((unsigned)v->max_tiles);
-#define GH_X(DD) ivf_scan_kernel<DD><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p)
-#define GH_XM(DD, LL) ivf_scan_mfma_kernel<DD, LL><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p)
-        if (h->D >= 4) {
-            switch (h->D) {
-                case 4: GH_XM(4, 4); break;
-                case 5: GH_XM(5, 8); break;
-                case 6: GH_XM(6, 8); break;
-                case 7: GH_XM(7, 8); break;
-                case 8: GH_XM(8, 8); break;
-                case 9: GH_XM(9, 16); break;
-                case 10: GH_XM(10, 16); break;
-                case 11: GH_XM(11, 16); break;
-                case 12: GH_XM(12, 16); break;
-                case 13: GH_XM(13, 16); break;
-                case 14: GH_XM(14, 16); break;
-                case 15: GH_XM(15, 16); break;
-                default: GH_XM(16, 16); break;
-            }
-        } else {
-            switch (h->D) {
-                case 2: GH_X(2); break;
-                case 3: GH_X(3); break;
-                case 4: GH_X(4); break;
-                default:
-                    if (h->LD == 8) GH_X(8);
-                    else GH_X(16);
-            }
+        if (!gh_dispatch_dim(h->D, [&](auto d, auto ld) {   // below 4 components the VALU form
+                if constexpr (d() >= 4)
+                    ivf_scan_mfma_kernel<d(), ld()><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p);
+                else
+                    ivf_scan_kernel<d()><<<grid, dim3(256), 0, h->stream>>>(v->lmid, v->lids, v->tile_list, v->meta, v->qstart, v->pair_q, h->d_q.p, h->d_qscan.p, h->d_cand.p, h->d_cnt.p);
+            })) {
+            h->err = "ivf_scan: no kernel for this dimension";
+            return GH_ERR_RUNTIME;
         }
-#undef GH_XM
-#undef GH_X
         GH_LAUNCH_CHECK();
     }
-#undef GH_IVF_LD
     return GH_OK;
 }

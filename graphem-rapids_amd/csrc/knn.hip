@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(
     const float *__restrict__ qt, const float *__restrict__ qscan, int S, int qgroup,
     uint64_t *__restrict__ cand, int32_t *__restrict__ cnt, int cdist /* GH_DIST_CDIST: keys carry ATen's cdist value */) {
     static_assert(R % 2 == 0, "references are processed in packed pairs");
-    constexpr int LD = D <= 4 ? 4 : D <= 8 ? 8 : 16;
+    constexpr int LD = gh_ld(D);
     constexpr int QS = D <= 3 ? 4 : LD + 4;
     __shared__ float4 qsh[(GH_SCAN_QGROUP + 1) * (QS / 4)];
     __shared__ float taush[GH_SCAN_QGROUP];
@@ -447,16 +447,15 @@ void launch_scan(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, 
         h->cdist ? 1 : 0);
 }
 
+// D <= 4: the dimension's own kernel; above, one kernel per row stride (the whole padded row is compared), with fewer
+// references per thread.  false: neither (gh_knn_scan_path admits no such engine).
 template <int R>
-void launch_scan_d(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, int64_t id_stride) {
-    switch (h->D) {
-        case 2: launch_scan<2, R>(h, mid, M, mem_stride, id_stride); break;
-        case 3: launch_scan<3, R>(h, mid, M, mem_stride, id_stride); break;
-        case 4: launch_scan<4, R>(h, mid, M, mem_stride, id_stride); break;
-        default:
-            if (h->LD == 8) launch_scan<8, (R > 4 ? 4 : R)>(h, mid, M, mem_stride, id_stride);
-            else launch_scan<16, (R > 2 ? 2 : R)>(h, mid, M, mem_stride, id_stride);
-    }
+bool launch_scan_d(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, int64_t id_stride) {
+    if (h->D <= 4) return gh_dispatch_value<2, 3, 4>(h->D, [&](auto d) { launch_scan<d(), R>(h, mid, M, mem_stride, id_stride); });
+    return gh_dispatch_value<8, 16>(h->LD, [&](auto ld) {
+        constexpr int RL = ld() == 8 ? 4 : 2;
+        launch_scan<ld(), (R > RL ? RL : R)>(h, mid, M, mem_stride, id_stride);
+    });
 }
 
 // mid == nullptr: gather the endpoints from positions instead (slow; the exact fallback only).
@@ -471,12 +470,13 @@ void launch_block_select(gh_engine *h, const float *mid, int64_t M, int64_t mem_
     const int QS = gh_qs(h->D, h->LD);
     float *tau_out = write_tau ? h->d_q.p + gh_qtau(h->D, h->LD) : nullptr;
     if (h->K <= GH_EXTRACT_MAX_K) {
-#define GH_BSEL(DD)                                                                                             \
-    knn_block_select_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>(       \
-        make_search_args(h, mid, M, mem_stride, id_stride), h->K, only_flagged, out_keys, tau_out,                     \
-        make_inter_args(h, with_intersect))
-        if (with_intersect) { GH_DISPATCH_DIM(h->D, GH_BSEL) } else { GH_BSEL(0); }   // (no intersection phase: nothing depends on the dimension at compile time)
-#undef GH_BSEL
+        const auto select = [&](auto d) {
+            knn_block_select_kernel<d()><<<dim3((unsigned)h->S), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>(
+                make_search_args(h, mid, M, mem_stride, id_stride), h->K, only_flagged, out_keys, tau_out,
+                make_inter_args(h, with_intersect));
+        };
+        // (no intersection phase: nothing depends on the dimension at compile time)
+        if (!(with_intersect && gh_dispatch_dim(h->D, [&](auto d, auto) { select(d); }))) select(gh_int<0>{});
     } else {
         const size_t smem = sizeof(uint64_t) * GH_SEL_BUF + sizeof(float) * (size_t)h->LD;
         knn_block_select_sort_kernel<<<dim3((unsigned)h->S), dim3(256), smem, h->stream>>>(
@@ -520,24 +520,23 @@ gh_status launch_select(gh_engine *h, bool final_level, bool with_intersect, con
     const bool wave = final_level && !reduce && h->S >= 2048;
     bool wave_tq = false;
     if (wave) {
-#define GH_SELW(DD)                                                                                                      \
-    knn_select_wave_kernel<DD><<<dim3((unsigned)h->S), dim3(64), 0, h->stream>>>(h->d_cand.p, h->d_cnt.p, h->K, h->d_partial.p, \
-                                                                                 h->d_dbg_cnt.p + (size_t)h->S, h->d_sel_redo.p, \
-                                                                                 iaw, (int)h->S)
         inter_args iaw = make_inter_args(h, with_intersect);
         wave_tq = with_intersect && h->k <= 127 && h->D >= 2 && h->LD <= 16;   // the lanes-per-coordinate form of the phase (intersect_query)
         if (wave_tq) { iaw.tq_count = h->d_tq_count.p; iaw.tq_touched = h->d_tq_touched.p; }
-        if (with_intersect) { GH_DISPATCH_DIM(h->D, GH_SELW) } else { GH_SELW(0); }
-#undef GH_SELW
+        const auto select_wave = [&](auto d) {
+            knn_select_wave_kernel<d()><<<dim3((unsigned)h->S), dim3(64), 0, h->stream>>>(
+                h->d_cand.p, h->d_cnt.p, h->K, h->d_partial.p, h->d_dbg_cnt.p + (size_t)h->S, h->d_sel_redo.p, iaw, (int)h->S);
+        };
+        if (!(with_intersect && gh_dispatch_dim(h->D, [&](auto d, auto) { select_wave(d); }))) select_wave(gh_int<0>{});
     }
-#define GH_SEL(DD)                                                                                                                          \
-    knn_select_kernel<DD><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>( \
-        h->d_cand.p, h->d_cnt.p, h->K, final_level ? 1 : 0, h->d_q.p + gh_qtau(h->D, h->LD), gh_qs(h->D, h->LD),                               \
-        h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + (size_t)(final_level ? 1 : 0) * h->S,                                                     \
-        make_search_args(h, fb_mid, h->own_count, 1, 1), make_inter_args(h, with_intersect), (int)h->S,                                        \
-        h->d_blockstats.p, h->n_vblocks, h->d_stats, wave ? h->d_sel_redo.p : nullptr)
-    if (with_intersect) { GH_DISPATCH_DIM(h->D, GH_SEL) } else { GH_SEL(0); }
-#undef GH_SEL
+    const auto select = [&](auto d) {
+        knn_select_kernel<d()><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), sizeof(float) * (size_t)h->LD, h->stream>>>(
+            h->d_cand.p, h->d_cnt.p, h->K, final_level ? 1 : 0, h->d_q.p + gh_qtau(h->D, h->LD), gh_qs(h->D, h->LD),
+            h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + (size_t)(final_level ? 1 : 0) * h->S,
+            make_search_args(h, fb_mid, h->own_count, 1, 1), make_inter_args(h, with_intersect), (int)h->S,
+            h->d_blockstats.p, h->n_vblocks, h->d_stats, wave ? h->d_sel_redo.p : nullptr);
+    };
+    if (!(with_intersect && gh_dispatch_dim(h->D, [&](auto d, auto) { select(d); }))) select(gh_int<0>{});
     if (wave_tq) {
         const int k4 = 4 * h->k;
         knn_touched_prefix_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(h->d_tq_count.p, (int)h->S, h->d_tq_base.p, h->d_tcount.p);
@@ -668,7 +667,10 @@ gh_status gh_knn_local(gh_engine *h, bool fuse_intersect) {
     GH_TRY_ST(gh_knn_thresholds(h));
     {
         gh_scope t(h, "knn_scan");
-        launch_scan_d<8>(h, h->d_mid.p, Mtot, 1, 1);
+        if (!launch_scan_d<8>(h, h->d_mid.p, Mtot, 1, 1)) {
+            h->err = "knn_scan: no scan kernel for this dimension and row stride";
+            return GH_ERR_RUNTIME;
+        }
         GH_LAUNCH_CHECK();
     }
     return gh_knn_finish(h, true, fuse_intersect);
@@ -688,11 +690,11 @@ gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world) {
         return GH_ERR_INVALID;
     }
     gh_scope t(h, "knn_merge_intersect");
-#define GH_MERGE(DD)                                                                                      \
-    knn_merge_kernel<DD><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2, h->stream>>>(      \
-        gathered, world, h->S, h->K, h->d_merged.p, make_inter_args(h, !h->intersect_done))
-    if (!h->intersect_done) { GH_DISPATCH_DIM(h->D, GH_MERGE) } else { GH_MERGE(0); }
-#undef GH_MERGE
+    const auto merge = [&](auto d) {
+        knn_merge_kernel<d()><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2, h->stream>>>(
+            gathered, world, h->S, h->K, h->d_merged.p, make_inter_args(h, !h->intersect_done));
+    };
+    if (!(!h->intersect_done && gh_dispatch_dim(h->D, [&](auto d, auto) { merge(d); }))) merge(gh_int<0>{});
     GH_LAUNCH_CHECK();
     h->d_keys_cur = h->d_merged.p;
     h->intersect_done = true;

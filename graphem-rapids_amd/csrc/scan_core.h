@@ -115,7 +115,7 @@ __device__ __forceinline__ void gh_scan_queries(const gh_f2 (&m)[R / 2][D], cons
                                                 int *hcount, uint64_t *__restrict__ cand,
                                                 int32_t *__restrict__ cnt, const int *qmap = nullptr /* LDS: query of slot s (ivf.hip) */,
                                                 int cdist = 0 /* GH_DIST_CDIST: keys carry ATen's cdist value */) {
-    constexpr int LD = D <= 4 ? 4 : D <= 8 ? 8 : 16;
+    constexpr int LD = gh_ld(D);
     constexpr int QS = D <= 3 ? 4 : LD + 4;
     constexpr int QT = D <= 3 ? 3 : LD;
     float4 rec[QS / 4], nxt[QS / 4];

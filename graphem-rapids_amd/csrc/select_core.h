@@ -32,7 +32,7 @@ struct inter_args {
 template <int DT>
 __device__ __forceinline__ void intersect_query(const inter_args &ia, int64_t qi, const uint64_t *best, gh_pair_list *pl) {
     if constexpr (DT >= 2) {
-        constexpr int LL = DT <= 4 ? 4 : DT <= 8 ? 8 : 16;
+        constexpr int LL = gh_ld(DT);
         if (ia.k <= 127 && blockDim.x % (4 * LL) == 0) {   // lanes = (role, coordinate)
             if (ia.tq_count)
                 gh_intersect_query_wide<DT, LL>(ia.pos, ia.edges, ia.sampled[qi], best, ia.k, ia.k_inter, ia.acc, ia.tflag,
@@ -47,22 +47,13 @@ __device__ __forceinline__ void intersect_query(const inter_args &ia, int64_t qi
     for (int c = threadIdx.x; c < ia.k; c += blockDim.x) {
         const int32_t j = (int32_t)gh_key_id(best[c + 1]);
         if constexpr (DT >= 2)
-            gh_intersect_pair_t<DT, (DT <= 4 ? 4 : DT <= 8 ? 8 : 16)>(ia.pos, ia.edges, ia.sampled[qi], j, ia.k_inter, ia.acc, ia.tflag,
-                                                                     ia.touched, ia.tcount, ia.own_lo, ia.own_hi);
+            gh_intersect_pair_t<DT, gh_ld(DT)>(ia.pos, ia.edges, ia.sampled[qi], j, ia.k_inter, ia.acc, ia.tflag,
+                                               ia.touched, ia.tcount, ia.own_lo, ia.own_hi);
         else
             gh_intersect_pair(ia.pos, ia.D, ia.LD, ia.edges, ia.sampled[qi], j, ia.k_inter, ia.acc, ia.tflag, ia.touched, ia.tcount,
                               ia.scratch + (qi * ia.k + c) * ia.LD, ia.own_lo, ia.own_hi);
     }
 }
-// host side: run X<DT> for the engine's dimension (0 past 16)
-#define GH_DISPATCH_DIM(Dval, X)                                                      \
-    switch (Dval) {                                                                   \
-        case 2: X(2); break;  case 3: X(3); break;  case 4: X(4); break;  case 5: X(5); break;    \
-        case 6: X(6); break;  case 7: X(7); break;  case 8: X(8); break;  case 9: X(9); break;    \
-        case 10: X(10); break; case 11: X(11); break; case 12: X(12); break; case 13: X(13); break; \
-        case 14: X(14); break; case 15: X(15); break; case 16: X(16); break;                        \
-        default: X(0); break;                                                         \
-    }
 
 // Bitonic sort of n2 (power of two) keys in LDS by one 256-thread workgroup, ascending.
 // Only used when K > GH_EXTRACT_MAX_K (latency-bound: ~20 us per 1024 keys).
