@@ -23,6 +23,8 @@ from . import graphstats
 from .graphstats import (connected_components, number_connected_components, is_connected, largest_connected_component,
                          eccentricity, diameter, radius, average_shortest_path_length, triangles, clustering,
                          average_clustering, transitivity, graph_summary, print_graph_summary)
+from . import communities
+from .communities import (modularity, louvain_communities, louvain_partitions, community_labels, adjusted_rand_index)
 from . import quality
 from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
                       neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality)
@@ -88,6 +90,8 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "triangles", "clustering", "average_clustering", "transitivity", "graph_summary", "print_graph_summary",
            "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
            "plot_radial_vs_centrality", "display_benchmark_results",
+           "communities", "modularity", "louvain_communities", "louvain_partitions", "community_labels",
+           "adjusted_rand_index",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
            "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",

@@ -144,6 +144,8 @@ SIGNATURES = {
     "gh_cent_components": (_int, [vp, vp, _P(i64)]),
     "gh_cent_distances": (_int, [vp, i64, vp, vp, vp, vp]),
     "gh_cent_triangles": (_int, [vp, vp]),
+    "gh_cent_modularity": (_int, [vp, vp, vp]),
+    "gh_cent_louvain": (_int, [vp, u64, i32, i32, vp, _P(i32), vp, vp, vp]),
     "gh_gen_create": (_int, [_P(vp), _int]),
     "gh_gen_destroy": (None, [vp]),
     "gh_gen_last_error": (_str, [vp]),
@@ -583,8 +585,9 @@ class ICGraph(BudgetHandle):
 
 
 class CentGraph(BudgetHandle):
-    """Thin RAII wrapper over a gh_cent_handle: shortest-path centralities, PageRank and the adjacency SpMV of one
-    undirected graph (include/graphem_hip.h).  Memory budget: device bytes of path state a paths call may hold, 1 GiB by default."""
+    """Thin RAII wrapper over a gh_cent_handle: shortest-path centralities, PageRank, the adjacency SpMV, graph statistics
+    and communities of one undirected graph (include/graphem_hip.h).  Memory budget: device bytes of path state a paths
+    call (or of spill tables a louvain call) may hold, 1 GiB by default."""
     _destroy, _last_error, _set_budget = "gh_cent_destroy", "gh_cent_last_error", "gh_cent_set_memory_budget"
 
     def __init__(self, n, edges, device_id=0):
@@ -639,6 +642,31 @@ class CentGraph(BudgetHandle):
         tri = np.zeros(self.n, dtype=np.int64)
         self._raise(self.lib.gh_cent_triangles(self.handle, ptr(tri)))
         return tri
+
+    def modularity(self, labels):
+        """(sum I, sum T^2, M) of a labelling with values in [0, n), as Python ints (gh_cent_modularity)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if len(labels) != self.n:
+            raise ValueError(f"labels must have {self.n} entries")
+        out = np.zeros(3, dtype=np.int64)
+        self._raise(self.lib.gh_cent_modularity(self.handle, ptr(labels), ptr(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def louvain(self, seed=0, max_levels=32, max_rounds=1000):
+        """The Louvain levels (gh_cent_louvain): (labels (L, n) int32, numerators [L] of Python ints, n_communities (L,)
+        int64, rounds (L,) int32, M)."""
+        max_levels = int(max_levels)
+        if max_levels < 1 or int(max_rounds) < 1:
+            raise ValueError("max_levels and max_rounds must be >= 1")
+        labels = np.zeros((max_levels, self.n), dtype=np.int32)
+        numerators = np.zeros(max_levels, dtype=np.int64)
+        counts = np.zeros(max_levels, dtype=np.int64)
+        rounds = np.zeros(max_levels, dtype=np.int32)
+        levels = ctypes.c_int32(0)
+        self._raise(self.lib.gh_cent_louvain(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, max_levels, int(max_rounds), ptr(labels),
+                                             ctypes.byref(levels), ptr(numerators), ptr(counts), ptr(rounds)))
+        L = int(levels.value)
+        return labels[:L].copy(), [int(x) for x in numerators[:L]], counts[:L].copy(), rounds[:L].copy(), 2 * self.edges
 
     def csr_device(self):
         """(indptr, indices) device pointers of the handle's symmetric CSR."""

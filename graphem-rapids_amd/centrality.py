@@ -209,6 +209,29 @@ class CentralityGraph:
             return np.zeros(0, dtype=np.int64)
         return self._g.triangles()
 
+    def louvain_levels(self, seed=0, max_levels=32, max_rounds=1000):
+        """The Louvain levels of include/graphem_hip.h "communities" (gh_cent_louvain): (labels (L, n) int32, numerators
+        [L] of Python ints, n_communities (L,) int64, rounds (L,) int32, M).  labels[l][v] = the smallest vertex id in v's
+        community after level l; L >= 1 for a graph with vertices (the singletons when nothing merges).  Modularity of
+        level l is numerators[l] / M**2."""
+        if int(max_levels) < 1 or int(max_rounds) < 1:
+            raise ValueError("max_levels and max_rounds must be >= 1")
+        if self._g is None:
+            return np.zeros((0, 0), np.int32), [], np.zeros(0, np.int64), np.zeros(0, np.int32), 0
+        return self._g.louvain(seed, max_levels, max_rounds)
+
+    def modularity_terms(self, labels):
+        """(sum I, sum T^2, M) of the labelling `labels` ((n,) ints in [0, n)), three exact Python ints
+        (gh_cent_modularity): modularity = (M sum I - sum T^2) / M**2."""
+        labels = np.asarray(labels).ravel()
+        if len(labels) != self.n:
+            raise ValueError(f"labels must have {self.n} entries")
+        if self.n and (labels.min() < 0 or labels.max() >= self.n):
+            raise ValueError(f"labels must lie in [0, {self.n})")
+        if self._g is None:
+            return 0, 0, 0
+        return self._g.modularity(labels)
+
     def pagerank(self, alpha=0.85, max_iter=100, tol=1e-6, return_iterations=False):
         """networkx pagerank(G, alpha, max_iter=max_iter, tol=tol) (_pagerank_scipy): raises
         PowerIterationFailedConvergence when max_iter iterations do not converge."""

@@ -1,9 +1,17 @@
 // The centrality handle (include/graphem_hip.h "centrality"), shared by centrality.hip, which owns its life cycle, and
-// graphstats.hip, which reads the CSR, the stream and the budget and reports through err.
+// graphstats.hip and communities.hip, which read the CSR, the stream and the budget and report through err.
 #pragma once
 #include "host_util.h"
 
 #define CENT_DEFAULT_BUDGET (1ll << 30)
+
+// One level graph of communities.hip: CSR with weights, self weights and weighted degrees (level 0 reads the handle's CSR).
+struct cent_level_graph {
+    gh_dev<int64_t> ptr, self, k;
+    gh_dev<int32_t> adj;
+    gh_dev<uint32_t> wgt;
+    void reset() { ptr.reset(); self.reset(); k.reset(); adj.reset(); wgt.reset(); }
+};
 
 struct gh_cent : gh_host {
     int64_t n = 0, edges = 0;
@@ -16,6 +24,8 @@ struct gh_cent : gh_host {
     gh_dev<double> d_sigma, d_delta, d_lam;
     gh_dev<uint64_t> d_vis, d_fa, d_fb;
     gh_dev<int2> d_range;
+    // the current and the next level graph of a gh_cent_louvain call; released when the call returns
+    cent_level_graph lv[2];
 };
 
 // (centrality.hip) the message gh_cent_last_error(NULL) returns on this thread

@@ -92,7 +92,11 @@ struct gh_host {
 
 // Selects the device and creates the handle's stream; a failure leaves its message in *msg (the module's create-time text).
 inline gh_status gh_host_open(gh_host *h, int device_id, std::string *msg) {
-    if (hipSetDevice(device_id) != hipSuccess) { *msg = "invalid device ordinal " + std::to_string(device_id); return GH_ERR_RUNTIME; }
+    if (hipSetDevice(device_id) != hipSuccess) {
+        (void)hipGetLastError();   // reported here; left in the thread it would fail the next HIP user's check (torch's)
+        *msg = "invalid device ordinal " + std::to_string(device_id);
+        return GH_ERR_RUNTIME;
+    }
     h->device = device_id;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { *msg = "hipStreamCreate failed"; return GH_ERR_HIP; }
     return GH_OK;

@@ -573,6 +573,56 @@ gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, const int32_t *
  * searched in the longer one, so an edge costs min(deg) log(max deg); counts are 64-bit throughout. */
 gh_status gh_cent_triangles(gh_cent_handle h, int64_t *triangles);
 
+/* ---- communities: Louvain levels and exact modularity (graphem-rapids_amd/communities.py) -------------------------------
+ * Over a gh_cent handle's graph: undirected, unweighted, self-loops dropped and duplicate edges merged.  Every quantity
+ * is an exact integer and no floating-point number is ever compared, so the result is a pure function of (edge set, n,
+ * seed, max_levels, max_rounds), id for id: not of edge order, duplicate edges, self-loops, the memory budget, nor
+ * run-to-run scheduling.  M = the sum of the degrees = 2 * edges.  Both calls give GH_ERR_INVALID for a handle of more
+ * than 2^30 edges; up to there every product below fits int64 (M W <= M^2, k T <= M^2, sum T^2 <= M^2 <= 2^62).  A
+ * handle of exactly 2^30 edges is refused as well: its 2^31 arcs are one more than the aggregation sort can count.
+ *
+ * Level graph: vertices 0 .. n_l - 1, symmetric integer weights w(u, v) >= 1 for u != v, a self weight s(u) >= 0, and
+ * k(u) = s(u) + sum over v != u of w(u, v).  Level 0 has s = 0 and w = 1; sum k = M on every level.
+ *
+ * Numerator of a labelling c:  I(c) = sum over u in c of s(u) + sum over the ORDERED pairs u != v in c of w(u, v);
+ * T(c) = sum over u in c of k(u);  N = M * sum_c I(c) - sum_c T(c)^2.  Modularity is N / M^2: one division of two exact
+ * integers, left to the caller.
+ *
+ * One level starts from singletons, c(u) = u.  Round r = 0, 1, ... computes everything from the labels at its start:
+ *   1. For every u and every community d != c(u) that holds a neighbour of u:
+ *          W(u, d) = sum over v in d, v != u, of w(u, v);      val(d) = M W(u, d) - k(u) T(d);
+ *          stay(u) = M W(u, c(u)) - k(u) (T(c(u)) - k(u)).
+ *      target(u) = the d of largest val, the smallest d among equals, if val(d) > stay(u) strictly; else target(u) = c(u).
+ *   2. If no vertex has target != c, the level ends.
+ *   3. prio(u) = mix( mix(seed + level * 0x9E3779B97F4A7C15) ^ ((uint64)r << 32 | u) ), mix() as in the influence section,
+ *      wrapping uint64 arithmetic.  u moves iff target(u) != c(u) and (prio(u), u) > (prio(v), v) for every neighbour
+ *      v != u with target(v) != c(v): the movers of a round are pairwise non-adjacent.
+ *   4. The moves are applied and N' computed.  N' > N keeps them and resets the failure count; otherwise the round is
+ *      discarded and counts as one failure.  The level ends at two failures in a row, or after max_rounds rounds; the
+ *      labels are then the last accepted ones.
+ * rounds[level] = the rounds whose step 1 ran, the one that found no target included.
+ *
+ * Aggregation: a community's id is the level vertex it started from; coarse vertex ids are the ranks of the ids in use,
+ * ascending; coarse w(a, b) = sum of w(u, v) over u in a, v in b; coarse s(a) = I(a).  The run ends when a level merges
+ * nothing, or after max_levels levels.
+ *
+ * Device work per round: the best-move pass (rows up to 32 entries by groups of 8 lanes that combine the row's
+ * (community, weight) pairs from a staged copy in LDS; longer rows by a workgroup with an LDS hash table keyed by
+ * community; a row whose communities do not fit it goes on to a third pass over hash tables in global memory, as many at
+ * once as gh_cent_set_memory_budget allows, at least one), the mover test, and the integer sums of N'.  The host reads
+ * {any target, sum I', sum T'^2} once per round.  Aggregation sorts the arcs by their 64-bit (c(u), c(v)) keys and
+ * reduces equal keys into the next level's CSR; that storage is proportional to the arcs and not divided by the budget. */
+
+/* labels: host int32[n], any values in [0, n) (GH_ERR_INVALID otherwise).  out = {sum_c I(c), sum_c T(c)^2, M}. */
+gh_status gh_cent_modularity(gh_cent_handle h, const int32_t *labels, int64_t out[3]);
+/* labels: host int32 (max_levels, n); row l, for l < *n_levels, is the labelling after level l: labels[l][v] = the
+ * smallest ORIGINAL vertex id in v's community (the convention of gh_cent_components).  One row per level that merged
+ * something; when level 0 merges nothing, *n_levels = 1 and row 0 holds the singletons.  numerators (host
+ * int64[max_levels]), n_communities (host int64[max_levels]) and rounds (host int32[max_levels]) give N, the community
+ * count and the rounds run per row.  GH_ERR_INVALID for max_levels < 1 or max_rounds < 1.  Blocking. */
+gh_status gh_cent_louvain(gh_cent_handle h, uint64_t seed, int32_t max_levels, int32_t max_rounds, int32_t *labels,
+                          int32_t *n_levels, int64_t *numerators, int64_t *n_communities, int32_t *rounds);
+
 /* ---- graph generators (reference generators.py: generate_sbm / generate_bipartite_graph, generate_geometric,
  * generate_ba; graphem-rapids_amd/generators.py) ------------------------------------------------------------------
  * Three random graph families whose every random decision is a counter-based word, so an edge list is a pure function
