@@ -132,6 +132,16 @@ SIGNATURES = {
     "gh_ic_arc_count": (i64, [vp]),
     "gh_ic_set_memory_budget": (_int, [vp, i64]),
     "gh_ic_spread": (_int, [vp, f64, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
+    "gh_ic_rr_sample": (_int, [vp, vp, f64, i32, u64, i64, vp, vp]),
+    "gh_rr_create": (_int, [_P(vp), _int, i64]),
+    "gh_rr_destroy": (None, [vp]),
+    "gh_rr_last_error": (_str, [vp]),
+    "gh_rr_set_memory_budget": (_int, [vp, i64]),
+    "gh_rr_counts": (_int, [vp, _P(i64), _P(i64)]),
+    "gh_rr_download": (_int, [vp, vp, vp, vp]),
+    "gh_rr_upload": (_int, [vp, i64, vp, vp, vp]),
+    "gh_rr_cover": (_int, [vp, i64, vp, vp]),
+    "gh_rr_count_hit": (_int, [vp, vp, i64, _P(i64)]),
     "gh_cent_create": (_int, [_P(vp), _int, i64, i64, vp]),
     "gh_cent_destroy": (None, [vp]),
     "gh_cent_last_error": (_str, [vp]),
@@ -582,6 +592,68 @@ class ICGraph(BudgetHandle):
         self._raise(self.lib.gh_ic_spread(self.handle, float(p), int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                           len(sets), ptr(offsets), ptr(verts), ptr(base), len(base), ptr(totals), ptr(trials)))
         return (totals, trials) if per_trial else totals
+
+
+    def rr_sample(self, rr, n_samples, p, seed=0, max_hops=-1, trials=None, roots=None):
+        """Appends n_samples reverse-reachable sets to the RRSets `rr` (gh_ic_rr_sample); trials uint64 / roots int32 of
+        n_samples, or None for the header's defaults."""
+        n_samples = int(n_samples)
+        if trials is not None:
+            trials = np.ascontiguousarray(np.asarray(trials).ravel(), dtype=np.uint64)
+        if roots is not None:
+            roots = np.ascontiguousarray(np.asarray(roots).ravel(), dtype=np.int32)
+        for a in (trials, roots):
+            if a is not None and len(a) != n_samples:
+                raise ValueError(f"trials and roots must have n_samples = {n_samples} entries")
+        self._raise(self.lib.gh_ic_rr_sample(self.handle, rr.handle, float(p), int(max_hops), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                             n_samples, ptr(trials), ptr(roots)))
+
+
+class RRSets(BudgetHandle):
+    """Thin RAII wrapper over a gh_rr_handle: a collection of reverse-reachable sets (or any set system over 0 .. n-1) on
+    the device (include/graphem_hip.h).  Memory budget: device bytes the collection may hold, 4 GiB by default."""
+    _destroy, _last_error, _set_budget = "gh_rr_destroy", "gh_rr_last_error", "gh_rr_set_memory_budget"
+
+    def __init__(self, n, device_id=0):
+        self.n = int(n)
+        self._create("gh_rr_create", int(device_id), self.n)
+
+    def counts(self):
+        """(sets, members in all)."""
+        sets, members = ctypes.c_int64(), ctypes.c_int64()
+        self._raise(self.lib.gh_rr_counts(self.handle, ctypes.byref(sets), ctypes.byref(members)))
+        return sets.value, members.value
+
+    def download(self):
+        """(indptr int64 (sets + 1), members int32, roots int32 (sets))."""
+        sets, total = self.counts()
+        indptr, members, roots = np.zeros(sets + 1, dtype=np.int64), np.zeros(total, dtype=np.int32), np.zeros(sets, dtype=np.int32)
+        self._raise(self.lib.gh_rr_download(self.handle, ptr(indptr), ptr(members), ptr(roots)))
+        return indptr, members, roots
+
+    def upload(self, indptr, members, roots=None):
+        indptr = np.ascontiguousarray(np.asarray(indptr).ravel(), dtype=np.int64)
+        members = np.ascontiguousarray(np.asarray(members).ravel(), dtype=np.int32)
+        if len(indptr) < 1 or (len(indptr) > 0 and indptr[-1] != len(members)):
+            raise ValueError("indptr must have sets + 1 entries and end at len(members)")
+        if roots is not None:
+            roots = np.ascontiguousarray(np.asarray(roots).ravel(), dtype=np.int32)
+            if len(roots) != len(indptr) - 1:
+                raise ValueError("roots must have one entry per set")
+        self._raise(self.lib.gh_rr_upload(self.handle, len(indptr) - 1, ptr(indptr), ptr(members), ptr(roots)))
+
+    def cover(self, k):
+        """Greedy maximum coverage: (seeds int32, gains int64) of min(k, n) rounds (gh_rr_cover)."""
+        rounds = max(0, min(int(k), self.n))
+        seeds, gains = np.zeros(rounds, dtype=np.int32), np.zeros(rounds, dtype=np.int64)
+        self._raise(self.lib.gh_rr_cover(self.handle, int(k), ptr(seeds), ptr(gains)))
+        return seeds, gains
+
+    def count_hit(self, vertices):
+        verts = np.ascontiguousarray(np.asarray(vertices).ravel(), dtype=np.int32)
+        count = ctypes.c_int64()
+        self._raise(self.lib.gh_rr_count_hit(self.handle, ptr(verts), len(verts), ctypes.byref(count)))
+        return count.value
 
 
 class CentGraph(BudgetHandle):

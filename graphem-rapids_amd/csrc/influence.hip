@@ -25,7 +25,10 @@
 #include <string>
 #include <vector>
 
+#include <hipcub/hipcub.hpp>
+
 #include "host_util.h"
+#include "rr_handle.h"
 
 #define IC_GOLDEN 0x9E3779B97F4A7C15ull
 #define IC_BLOCK 256
@@ -69,16 +72,28 @@ struct IcLevel {
     const int32_t *cur_cnt; int32_t *nxt_cnt; int32_t *zero_cnt; int32_t *touch_cnt;
     int64_t n, pull_min, dense;                       // dense = sets * n * W
     uint64_t seed;
+    const uint64_t *trial_tab;                        // REV: the trial of bit b of word w at [64 * w + b]
     uint32_t thr;
     int32_t W, T, directed, round;
 };
+
+// REV (reverse-reachable sets, gh_ic_rr_sample): the host swaps the two CSRs, so a level walks every arc backwards; the
+// coin stays that of the original arc (the pair the other way round), and a lane's trial comes from the per-bit table.
+template <bool REV> __device__ __forceinline__ uint64_t ic_lane_word(const IcLevel &a, int32_t w, int lane) {
+    if constexpr (REV) return ic_mix(a.seed + a.trial_tab[64 * w + lane] * IC_GOLDEN);
+    else return ic_mix(a.seed + (uint64_t)(64 * w + lane) * IC_GOLDEN);
+}
+template <bool REV> __device__ __forceinline__ uint64_t ic_arc_key(int32_t from, int32_t to, int directed) {
+    if constexpr (REV) return ic_key(to, from, directed);
+    else return ic_key(from, to, directed);
+}
 
 __device__ __forceinline__ void ic_append(const IcLevel &a, int32_t e) {   // one lane
     if (__hip_atomic_load(&a.mark[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.round) return;
     if (atomicExch(&a.mark[e], a.round) != a.round) a.nxt_list[atomicAdd(a.nxt_cnt, 1)] = e;
 }
 
-__global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
+template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
     const int64_t cnt = *a.cur_cnt;
     if (cnt == 0 || cnt >= a.pull_min) return;
     const int lane = threadIdx.x & 63;
@@ -101,7 +116,7 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
             const uint64_t fj = uni64(__shfl(f, j));
             const int64_t s = ej / a.n;
             const int32_t u = (int32_t)(ej - s * a.n);
-            const uint64_t h = ic_mix(a.seed + (uint64_t)(64 * wj + lane) * IC_GOLDEN);
+            const uint64_t h = ic_lane_word<REV>(a, wj, lane);
             const int64_t beg = a.out_ptr[u], end = a.out_ptr[u + 1];
             // 64 arcs at a time: the coins of arc q go to lane q as one live mask, then every lane does its arc's
             // memory work (visited load, atomicOr, append) in parallel instead of one lane arc after arc
@@ -111,7 +126,7 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
                 uint64_t mine = 0;
                 for (int q = 0; q < m; ++q) {
                     const int32_t v = __builtin_amdgcn_readlane(vk, q);
-                    const uint64_t live = __ballot((uint32_t)(ic_mix(h ^ ic_key(u, v, a.directed)) >> 40) < a.thr) & fj;
+                    const uint64_t live = __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < a.thr) & fj;
                     if (lane == q) mine = live;
                 }
                 if (mine) {
@@ -127,7 +142,7 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
     }
 }
 
-__global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
+template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
     const int64_t cnt = *a.cur_cnt;
     if (cnt == 0 || cnt < a.pull_min) return;
     const int lane = threadIdx.x & 63;
@@ -164,8 +179,8 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
                     const int32_t u = __builtin_amdgcn_readlane(uk, q);
                     const uint64_t f = uni64(__shfl(fk, q)) & ~acc;
                     if (f == 0) continue;
-                    if (!have_h) { h = ic_mix(a.seed + (uint64_t)(64 * wj + lane) * IC_GOLDEN); have_h = true; }
-                    acc |= __ballot((uint32_t)(ic_mix(h ^ ic_key(u, v, a.directed)) >> 40) < a.thr) & f;
+                    if (!have_h) { h = ic_lane_word<REV>(a, wj, lane); have_h = true; }
+                    acc |= __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < a.thr) & f;
                 }
             }
             if (acc && lane == 0) {
@@ -272,6 +287,12 @@ struct gh_ic : gh_host {
     gh_dev<uint64_t> d_vis, d_fa, d_fb;
     gh_dev<int32_t> d_mark, d_list0, d_list1, d_touch, d_counts, d_cnt;
     gh_dev<uint8_t> d_touched;
+    // gh_ic_rr_sample: per-bit trials, counts, offsets and cursors of a chunk, the unsorted members, the scan / sort temp
+    int64_t cap_rr_bits = 0, cap_rr_scatter = 0;
+    gh_dev<uint64_t> d_rr_trials;
+    gh_dev<int32_t> d_rr_count, d_rr_cursor, d_rr_scatter;
+    gh_dev<int64_t> d_rr_off;
+    gh_dev<char> d_rr_tmp;
 };
 
 static thread_local std::string g_ic_error;
@@ -309,6 +330,44 @@ gh_status ic_reserve(gh_ic *h, int64_t sets, int32_t W, int32_t T) {
     return GH_OK;
 }
 
+// The levels of one chunk whose round 0 is in place (list 0, the touched list, their counts): push / pull / advance until
+// the frontier is empty or max_hops levels have run.  REV: the CSRs swapped and the per-bit trial table (gh_ic_rr_sample).
+template <bool REV>
+gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t seed, uint32_t thr, int32_t max_hops,
+                        const uint64_t *trial_tab) {
+    IcLevel a{};
+    a.out_ptr = REV ? h->d_in_ptr : h->d_out_ptr.p; a.out_adj = REV ? h->d_in_adj : h->d_out_adj.p;
+    a.in_ptr = REV ? h->d_out_ptr.p : h->d_in_ptr; a.in_adj = REV ? h->d_out_adj.p : h->d_in_adj;
+    a.vis = h->d_vis.p; a.mark = h->d_mark.p; a.touched = h->d_touched.p; a.touch_list = h->d_touch.p; a.touch_cnt = h->d_cnt.p + 3;
+    a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = thr; a.directed = h->directed; a.trial_tab = trial_tab;
+    a.dense = sets * h->n * W;
+    a.pull_min = std::max<int64_t>(1, sets * h->n / IC_PULL_DIV);
+    const int grid = ic_blocks(a.dense);   // a wave per 64 items; no level has more than `dense` items
+    // a level can only find new vertices while fewer than n rounds have passed
+    const int64_t last = max_hops < 0 ? h->n : std::min<int64_t>(max_hops, h->n);
+    for (int64_t r = 1; r <= last; ++r) {
+        a.round = (int32_t)r;
+        a.cur = (r & 1) ? h->d_fa.p : h->d_fb.p;
+        a.nxt = (r & 1) ? h->d_fb.p : h->d_fa.p;
+        a.cur_list = (r & 1) ? h->d_list0.p : h->d_list1.p;
+        a.nxt_list = (r & 1) ? h->d_list1.p : h->d_list0.p;
+        a.cur_cnt = h->d_cnt.p + (r - 1) % 3;
+        a.nxt_cnt = h->d_cnt.p + r % 3;
+        a.zero_cnt = h->d_cnt.p + (r + 1) % 3;
+        ic_push_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+        ic_pull_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+        ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+        GH_HIP(hipGetLastError());
+        if (r % IC_CHECK_EVERY == 0 && r < last) {
+            int32_t alive = 0;
+            GH_HIP(hipMemcpyAsync(&alive, h->d_cnt.p + r % 3, sizeof(alive), hipMemcpyDeviceToHost, h->stream));
+            GH_HIP(hipStreamSynchronize(h->stream));
+            if (alive == 0) break;
+        }
+    }
+    return GH_OK;
+}
+
 // One chunk: `sets` seed sets given as unique entry ids (s * n + v) in `seeds`; counts -> out (sets, T).
 gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds, int32_t W, int32_t T, uint64_t seed,
                        uint32_t thr, int32_t max_hops, int32_t *out) {
@@ -322,35 +381,7 @@ gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds
         ic_seed_kernel<<<dim3((unsigned)((si + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
             h->d_list0.p, (int64_t)seeds.size(), W, T, h->d_vis.p, h->d_fa.p, h->d_touched.p);
         GH_HIP(hipGetLastError());
-        IcLevel a{};
-        a.out_ptr = h->d_out_ptr.p; a.out_adj = h->d_out_adj.p; a.in_ptr = h->d_in_ptr; a.in_adj = h->d_in_adj;
-        a.vis = h->d_vis.p; a.mark = h->d_mark.p; a.touched = h->d_touched.p; a.touch_list = h->d_touch.p; a.touch_cnt = h->d_cnt.p + 3;
-        a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = thr; a.directed = h->directed;
-        a.dense = sets * h->n * W;
-        a.pull_min = std::max<int64_t>(1, sets * h->n / IC_PULL_DIV);
-        const int grid = ic_blocks(a.dense);   // a wave per 64 items; no level has more than `dense` items
-        // a level can only find new vertices while fewer than n rounds have passed
-        const int64_t last = max_hops < 0 ? h->n : std::min<int64_t>(max_hops, h->n);
-        for (int64_t r = 1; r <= last; ++r) {
-            a.round = (int32_t)r;
-            a.cur = (r & 1) ? h->d_fa.p : h->d_fb.p;
-            a.nxt = (r & 1) ? h->d_fb.p : h->d_fa.p;
-            a.cur_list = (r & 1) ? h->d_list0.p : h->d_list1.p;
-            a.nxt_list = (r & 1) ? h->d_list1.p : h->d_list0.p;
-            a.cur_cnt = h->d_cnt.p + (r - 1) % 3;
-            a.nxt_cnt = h->d_cnt.p + r % 3;
-            a.zero_cnt = h->d_cnt.p + (r + 1) % 3;
-            ic_push_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-            ic_pull_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-            ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-            GH_HIP(hipGetLastError());
-            if (r % IC_CHECK_EVERY == 0 && r < last) {
-                int32_t alive = 0;
-                GH_HIP(hipMemcpyAsync(&alive, h->d_cnt.p + r % 3, sizeof(alive), hipMemcpyDeviceToHost, h->stream));
-                GH_HIP(hipStreamSynchronize(h->stream));
-                if (alive == 0) break;
-            }
-        }
+        GH_TRY_ST(ic_run_levels<false>(h, sets, W, T, seed, thr, max_hops, nullptr));
         const int grid_t = ic_blocks(sets * h->n * W);
         ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, h->n, W, T, h->d_counts.p);
         ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, W, h->d_vis.p, h->d_fa.p, h->d_fb.p,
@@ -489,6 +520,209 @@ extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, in
             }
             totals[s0 + s] = tot;
             if (per_trial) std::copy(row, row + T, per_trial + (s0 + s) * (int64_t)T);
+        }
+    }
+    return GH_OK;
+}
+
+// ---- reverse-reachable sets (header: "reverse influence sampling") ------------------------------------------------------
+// A chunk is ONE set of the level machinery with W words: bit b of word w is sample 64w + b of the chunk.  Round 0 sets one
+// bit per root; the levels run with the CSRs swapped (ic_run_levels<true>); then the touched list is turned into the CSR of
+// the chunk's sets: count per bit (ic_count_kernel), scan, scatter, segmented sort into the collection.
+namespace {
+
+// Words per chunk beyond the budget.  A touched entry costs W words in every pass over the lists while a sub-critical
+// search sets one or two bits of them, so more words only pay while they save launches: measured on random-regular graphs
+// of degree 8 at p = 0.1, 2^18 samples take 333 / 84 / 55 ms at W = 8 / 32 / 64 (n = 100 K) and 324 / 74 / 50 / 38 ms at
+// W = 8 / 32 / 64 / 128 (n = 1 M).  And round 0's frontier, up to 64 W roots, has to stay under the pull threshold n / 16
+// (half of it here), or every level scans the dense state: 210 ms at W = 128, n = 100 K.  Small graphs keep 16 words.
+#define RR_MAX_WORDS 128
+#define RR_MIN_WORDS_CAP 16
+
+// Round 0.  Several samples may share a root: its words take one atomicOr per sample, and the first to stamp the entry
+// (mark = -1, no round has that stamp) puts it into list 0 and the touched list, so both stay unique.
+__global__ __launch_bounds__(IC_BLOCK) void rr_root_kernel(const int32_t *__restrict__ roots, int32_t S, int32_t W, uint64_t *vis,
+                                                          uint64_t *cur, int32_t *mark, uint8_t *touched, int32_t *list0,
+                                                          int32_t *touch_list, int32_t *cnt) {
+    const int32_t j = blockIdx.x * IC_BLOCK + threadIdx.x;
+    if (j >= S) return;
+    const int32_t r = roots[j];
+    const int64_t x = (int64_t)r * W + (j >> 6);
+    const unsigned long long bit = 1ull << (j & 63);
+    atomicOr((unsigned long long *)&vis[x], bit);
+    atomicOr((unsigned long long *)&cur[x], bit);
+    if (atomicExch(&mark[r], -1) != -1) {
+        touched[r] = 1;
+        list0[atomicAdd(cnt, 1)] = r;
+        touch_list[atomicAdd(cnt + 3, 1)] = r;
+    }
+}
+
+// members of sample (w, b) -> scatter[off[64w + b] ..), in the order the atomics fall; the segmented sort orders them
+__global__ __launch_bounds__(IC_BLOCK) void rr_scatter_kernel(const int32_t *__restrict__ touch_list, const int32_t *touch_cnt,
+                                                             const uint64_t *__restrict__ vis, int32_t W,
+                                                             const int64_t *__restrict__ off, int32_t *cursor, int32_t *scatter) {
+    const int64_t items = (int64_t)*touch_cnt * W;
+    for (int64_t i = (int64_t)blockIdx.x * IC_BLOCK + threadIdx.x; i < items; i += (int64_t)gridDim.x * IC_BLOCK) {
+        const int32_t e = touch_list[i / W];
+        const int32_t w = (int32_t)(i % W);
+        uint64_t x = vis[(int64_t)e * W + w];
+        while (x) {
+            const int b = __ffsll((unsigned long long)x) - 1;
+            x &= x - 1;
+            scatter[off[64 * w + b] + atomicAdd(&cursor[64 * w + b], 1)] = e;
+        }
+    }
+}
+
+__global__ __launch_bounds__(IC_BLOCK) void rr_indptr_kernel(const int64_t *__restrict__ off, int32_t S, int64_t base, int64_t *indptr) {
+    const int32_t j = blockIdx.x * IC_BLOCK + threadIdx.x;
+    if (j < S) indptr[j + 1] = base + off[j + 1];
+}
+
+struct RrWiden {
+    __host__ __device__ int64_t operator()(int32_t x) const { return x; }
+};
+
+gh_status rr_scratch(gh_ic *h, int64_t bits) {
+    if (bits <= h->cap_rr_bits) return GH_OK;
+    h->cap_rr_bits = 0;
+    if (!h->d_rr_trials.alloc(8 * bits) || !h->d_rr_count.alloc(4 * (bits + 1)) || !h->d_rr_cursor.alloc(4 * bits) ||
+        !h->d_rr_off.alloc(8 * (bits + 1))) {
+        h->err = "hipMalloc failed for the sample tables of a chunk";
+        return GH_ERR_NOMEM;
+    }
+    h->cap_rr_bits = bits;
+    return GH_OK;
+}
+
+gh_status rr_tmp(gh_ic *h, size_t bytes) {
+    if (bytes <= h->d_rr_tmp.bytes) return GH_OK;
+    if (!h->d_rr_tmp.alloc(bytes)) { h->err = "hipMalloc failed for scan / sort scratch"; return GH_ERR_NOMEM; }
+    return GH_OK;
+}
+
+// One chunk of S samples (trials / roots on the host), appended to the collection at (rr->sets, rr->members).
+gh_status rr_run_chunk(gh_ic *h, gh_rr *rr, int32_t S, int32_t W, const uint64_t *trials, const int32_t *roots, uint64_t seed,
+                       uint32_t thr, int32_t max_hops, int64_t asked) {
+    const int64_t bits = 64 * (int64_t)W;
+    auto refuse = [&](int64_t total) {
+        const double mean = (double)(rr->members + total) / (double)(rr->sets + S);
+        h->err = "the collection would outgrow its memory budget of " + std::to_string(rr->budget) + " bytes: " +
+                 std::to_string(asked) + " samples asked, mean set size " + std::to_string(mean) + " over the first " +
+                 std::to_string(rr->sets + S) + " (reverse influence sampling is for sets that are small against n)";
+        return GH_ERR_NOMEM;
+    };
+    {
+        const gh_status st0 = rr_reserve(rr, rr->sets + S, rr->members, h->stream);
+        if (st0 == GH_ERR_NOMEM) return refuse(0);
+        if (st0 != GH_OK) return st0;
+    }
+    GH_HIP(hipMemsetAsync(h->d_rr_trials.p, 0, 8 * bits, h->stream));
+    GH_HIP(hipMemcpyAsync(h->d_rr_trials.p, trials, 8 * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemcpyAsync(rr->d_roots.p + rr->sets, roots, 4 * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_cnt.p, 0, 4 * 4, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_rr_count.p, 0, 4 * (bits + 1), h->stream));
+    GH_HIP(hipMemsetAsync(h->d_rr_cursor.p, 0, 4 * bits, h->stream));
+    rr_root_kernel<<<dim3((unsigned)((S + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
+        rr->d_roots.p + rr->sets, S, W, h->d_vis.p, h->d_fa.p, h->d_mark.p, h->d_touched.p, h->d_list0.p, h->d_touch.p, h->d_cnt.p);
+    GH_HIP(hipGetLastError());
+    GH_TRY_ST(ic_run_levels<true>(h, 1, W, S, seed, thr, max_hops, h->d_rr_trials.p));
+    const int grid_t = ic_blocks(h->n * W);
+    ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, h->n, W, S, h->d_rr_count.p);
+    GH_HIP(hipGetLastError());
+    hipcub::TransformInputIterator<int64_t, RrWiden, const int32_t *> wide(h->d_rr_count.p, RrWiden());
+    size_t temp = 0;
+    GH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, wide, h->d_rr_off.p, (int)(bits + 1), h->stream));
+    GH_TRY_ST(rr_tmp(h, temp));
+    GH_HIP(hipcub::DeviceScan::ExclusiveSum(h->d_rr_tmp.p, temp, wide, h->d_rr_off.p, (int)(bits + 1), h->stream));
+    int64_t total = 0;
+    GH_HIP(hipMemcpyAsync(&total, h->d_rr_off.p + bits, 8, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
+    // from here on a failure must still leave the chunk state zero
+    auto reset = [&]() {
+        ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, W, h->d_vis.p, h->d_fa.p, h->d_fb.p,
+                                                                       h->d_mark.p, h->d_touched.p);
+        return hipStreamSynchronize(h->stream);
+    };
+    gh_status st = total > INT32_MAX ? GH_ERR_NOMEM : rr_reserve(rr, rr->sets + S, rr->members + total, h->stream);
+    if (st == GH_OK && total > h->cap_rr_scatter) {
+        h->cap_rr_scatter = 0;
+        if (h->d_rr_scatter.alloc(4 * (size_t)total)) h->cap_rr_scatter = total;
+        else st = GH_ERR_NOMEM;
+    }
+    if (st == GH_ERR_NOMEM) (void)refuse(total);
+    if (st != GH_OK) { (void)reset(); return st; }
+    if (total > 0) {
+        rr_scatter_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, W, h->d_rr_off.p,
+                                                                         h->d_rr_cursor.p, h->d_rr_scatter.p);
+        GH_HIP(hipGetLastError());
+        int bits_n = 1;
+        while (((int64_t)1 << bits_n) < h->n) ++bits_n;
+        hipError_t e = hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, temp, h->d_rr_scatter.p, rr->d_members.p + rr->members, (int)total,
+                                                                  S, h->d_rr_off.p, h->d_rr_off.p + 1, 0, bits_n, h->stream);
+        if (e == hipSuccess && rr_tmp(h, temp) != GH_OK) { (void)reset(); return GH_ERR_NOMEM; }
+        if (e == hipSuccess)
+            e = hipcub::DeviceSegmentedRadixSort::SortKeys(h->d_rr_tmp.p, temp, h->d_rr_scatter.p, rr->d_members.p + rr->members, (int)total,
+                                                           S, h->d_rr_off.p, h->d_rr_off.p + 1, 0, bits_n, h->stream);
+        if (e != hipSuccess) {
+            h->err = std::string("segmented sort: ") + hipGetErrorString(e);
+            (void)reset();
+            return GH_ERR_HIP;
+        }
+    }
+    rr_indptr_kernel<<<dim3((unsigned)((S + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(h->d_rr_off.p, S, rr->members,
+                                                                                                       rr->d_indptr.p + rr->sets);
+    GH_HIP(hipGetLastError());
+    GH_HIP(reset());
+    rr->sets += S;
+    rr->members += total;
+    return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                                     const uint64_t *trials, const int32_t *roots) {
+    if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (!rr) return fail(GH_ERR_INVALID, "the collection handle is NULL");
+    if (rr->n != h->n || rr->device != h->device) return fail(GH_ERR_INVALID, "the collection was created for another n or device");
+    if (!(p >= 0.0 && p <= 1.0)) return fail(GH_ERR_INVALID, "p must be in [0, 1]");
+    if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
+    if (n_samples < 0) return fail(GH_ERR_INVALID, "n_samples must be >= 0");
+    if (rr->sets + n_samples > INT32_MAX) return fail(GH_ERR_INVALID, "a collection holds fewer than 2^31 sets");
+    if (roots)
+        for (int64_t j = 0; j < n_samples; ++j)
+            if (roots[j] < 0 || roots[j] >= h->n) return fail(GH_ERR_INVALID, "root vertex id outside [0, n)");
+    if (n_samples == 0) return GH_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    h->err.clear();
+    rr->err.clear();
+    const double tf = std::floor(p * 16777216.0 + 0.5);
+    const uint32_t thr = (uint32_t)std::min(16777216.0, tf);
+    // words per chunk: what the budget holds of one set's state, as gh_ic_spread sizes its seed sets
+    int64_t W = std::max<int64_t>(1, (h->budget / h->n - 17) / 24);
+    W = std::min<int64_t>({W, RR_MAX_WORDS, std::max<int64_t>(RR_MIN_WORDS_CAP, h->n / (2 * 64 * IC_PULL_DIV)), (n_samples + 63) / 64});
+    GH_TRY_ST(ic_reserve(h, 1, (int32_t)W, 1));
+    GH_TRY_ST(rr_scratch(h, 64 * W));
+    const int64_t sets0 = rr->sets, members0 = rr->members;
+    std::vector<uint64_t> tr((size_t)(64 * W));
+    std::vector<int32_t> ro((size_t)(64 * W));
+    for (int64_t j0 = 0; j0 < n_samples; j0 += 64 * W) {
+        const int32_t S = (int32_t)std::min<int64_t>(64 * W, n_samples - j0);
+        for (int32_t j = 0; j < S; ++j) {
+            tr[j] = trials ? trials[j0 + j] : (uint64_t)(sets0 + j0 + j);
+            ro[j] = roots ? roots[j0 + j]
+                          : (int32_t)(((ic_mix(ic_mix(seed + tr[j] * IC_GOLDEN) ^ ~0ull) >> 32) * (uint64_t)h->n) >> 32);
+        }
+        const gh_status st = rr_run_chunk(h, rr, S, (S + 63) / 64, tr.data(), ro.data(), seed, thr, max_hops, n_samples);
+        if (st != GH_OK) {   // all or nothing: the collection is what it was before the call
+            if (h->err.empty()) h->err = rr->err;   // the message of a failed copy while the collection grew
+            rr->err = h->err;
+            rr->sets = sets0;
+            rr->members = members0;
+            return st;
         }
     }
     return GH_OK;

@@ -4,8 +4,13 @@ The reference (graphem_rapids/influence.py, benchmark.py:246-379) scores seed se
 selects greedy seeds with k * n of them.  Here every cascade runs in csrc/influence.hip (gh_ic_spread), thousands of
 trials per call, with counter-based coins (include/graphem_hip.h): a result depends only on the arc set, the seed set,
 p, max_hops, the number of trials and the seed, and tests/ic_reference.py recomputes it bit for bit in numpy.
+
+Reverse influence sampling (RIS) draws reverse-reachable sets with the same coins (gh_ic_rr_sample) and selects seeds by
+greedy maximum coverage on the device (gh_rr_cover): a baseline whose cost follows the sizes of the sets, not
+n * trials * k, for the graph sizes CELF cannot reach (tests/ris_reference.py restates the rule in numpy).
 """
 import heapq
+import math
 import time
 
 import numpy as np
@@ -106,6 +111,7 @@ class InfluenceGraph:
     def __init__(self, graph, n=None, directed=None, device_id=0):
         self.n, self.arcs, self.directed, self.labels = _graph_arcs(graph, n, directed)
         self._index = None if self.labels is None else {v: i for i, v in enumerate(self.labels)}
+        self._device_id = int(device_id)
         self._ic = _native.ICGraph(max(self.n, 1), self.arcs, self.directed, device_id) if self.n > 0 else None
 
     def _ids(self, seeds):
@@ -154,9 +160,97 @@ class InfluenceGraph:
             seeds = [self.labels[s] for s in seeds]
         return seeds, evals
 
+    def rr_sets(self, n_samples, p=0.1, max_hops=None, seed=0, trials=None, roots=None):
+        """An RRCollection of n_samples reverse-reachable sets: sample j is the search backwards from roots[j] over the
+        live arcs of trial trials[j] (defaults: trial j, the root the header derives from the trial's word).  roots are
+        given as labels where the graph has labels."""
+        if self._ic is None:
+            raise ValueError("the graph has no vertices")
+        coll = RRCollection(_native.RRSets(self.n, self._device_id), self, p, self._hops(max_hops), seed)
+        try:
+            coll.extend(n_samples, trials, roots)
+        except Exception:
+            coll.close()
+            raise
+        return coll
+
     def close(self):
         if self._ic is not None:
             self._ic.close()
+
+
+class RRCollection:
+    """Reverse-reachable sets on the device (gh_rr_*): InfluenceGraph.rr_sets draws them, max_coverage uploads any set
+    system.  indptr (int64), members (int32 vertex ids, ascending within a set) and roots (int32 ids) are downloaded on
+    first use; cover and count_hit speak the graph's labels."""
+
+    def __init__(self, rr, graph=None, p=None, hops=-1, seed=0):
+        self._rr, self._graph, self._p, self._hops, self._seed = rr, graph, p, hops, seed
+        self._host = None
+
+    @property
+    def n_sets(self):
+        return self._rr.counts()[0]
+
+    @property
+    def n_members(self):
+        return self._rr.counts()[1]
+
+    def __len__(self):
+        return self.n_sets
+
+    def _download(self):
+        if self._host is None:
+            self._host = self._rr.download()
+        return self._host
+
+    indptr = property(lambda self: self._download()[0])
+    members = property(lambda self: self._download()[1])
+    roots = property(lambda self: self._download()[2])
+
+    def set_memory_budget(self, nbytes):
+        """Device bytes the collection may hold (0: the default, 4 GiB); a draw that would outgrow it raises MemoryError."""
+        self._rr.set_memory_budget(nbytes)
+
+    def extend(self, n_samples, trials=None, roots=None):
+        """Appends n_samples sets drawn with the collection's p, max_hops and seed; default trials continue at n_sets."""
+        if self._graph is None:
+            raise ValueError("an uploaded set system has no graph to sample from")
+        if roots is not None:
+            roots = self._graph._ids(roots)
+        self._host = None
+        self._graph._ic.rr_sample(self._rr, n_samples, self._p, self._seed, self._hops, trials, roots)
+        return self
+
+    def _labels(self):
+        return None if self._graph is None else self._graph.labels
+
+    def cover(self, k):
+        """Greedy maximum coverage: (seeds, gains) of min(k, n) rounds; gains int64, the newly covered sets per round."""
+        seeds, gains = self._rr.cover(k)
+        labels = self._labels()
+        seeds = [int(v) for v in seeds] if labels is None else [labels[v] for v in seeds]
+        return seeds, gains
+
+    def count_hit(self, vertices):
+        """Sets that contain at least one of the vertices."""
+        ids = self._graph._ids(vertices) if self._graph is not None else np.asarray(list(vertices), dtype=np.int64)
+        return self._rr.count_hit(ids)
+
+    def close(self):
+        self._rr.close()
+
+
+def max_coverage(indptr, members, n, k, device_id=0):
+    """Greedy maximum coverage of the set system (indptr, members) over the vertices 0 .. n-1 on the GPU: set s holds
+    members[indptr[s]:indptr[s + 1]], ascending.  Each of min(k, n) rounds takes the unchosen vertex in the most uncovered
+    sets, ties to the smallest id.  Returns (seeds, gains)."""
+    coll = RRCollection(_native.RRSets(int(n), device_id))
+    try:
+        coll._rr.upload(indptr, members)
+        return coll.cover(k)
+    finally:
+        coll.close()
 
 
 def influence_spread(graph, seeds, p=0.1, n_trials=1024, max_hops=None, seed=0, return_trials=False):
@@ -217,11 +311,111 @@ def greedy_seed_selection(G, k, p=0.1, iterations_count=200, *, n_trials=256, se
     return seeds, evals * int(iterations_count)
 
 
+_E1 = 1.0 - 1.0 / math.e
+
+
+def opim_sample_plan(n, k, epsilon, delta, max_samples=None):
+    """(theta_0, theta_max, i_max, a) of the OPIM-C stopping rule (Tang, Tang, Xiao, Yuan 2018)."""
+    ln6d = math.log(6.0 / delta)
+    ln_binom = math.lgamma(n + 1) - math.lgamma(k + 1) - math.lgamma(n - k + 1)
+    theta_max = math.ceil(2.0 * n * (_E1 * math.sqrt(ln6d) + math.sqrt(_E1 * (ln_binom + ln6d))) ** 2 / (epsilon ** 2 * k))
+    if max_samples is not None:
+        theta_max = min(theta_max, int(max_samples))
+    theta_max = max(1, theta_max)
+    theta_0 = max(1, math.ceil(theta_max * epsilon ** 2 * k / n))
+    i_max = max(1, math.ceil(math.log2(theta_max / theta_0)))
+    return theta_0, theta_max, i_max, math.log(3.0 * i_max / delta)
+
+
+def opim_bounds(gain_sum, hit2, theta, n, a):
+    """(lower bound of the spread of S, upper bound of the optimum) from Lambda1 = sets of R1 the greedy seeds cover and
+    Lambda2 = sets of R2 they hit, theta sets each."""
+    inner = math.sqrt(hit2 + 2.0 * a / 9.0) - math.sqrt(a / 2.0)
+    lower = 0.0 if inner < 0 else max(0.0, inner * inner - a / 18.0) * n / theta
+    upper = (math.sqrt(gain_sum / _E1 + a / 2.0) + math.sqrt(a / 2.0)) ** 2 * n / theta
+    return lower, upper
+
+
+def opim_c(sample, cover, count, n, k, epsilon, delta=None, max_samples=None):
+    """The OPIM-C driver over three callables, as celf_greedy is written over an evaluator:
+    sample(theta) grows both collections to theta sets each -- R1 on trials 0, 2, 4, .., R2 on trials 1, 3, 5, .., so a
+    doubling extends prefixes; cover(k) -> (seeds, gains) by greedy maximum coverage of R1; count(seeds) -> sets of R2 hit.
+    Stops when lower / upper >= 1 - 1/e - epsilon or after i_max doublings.  Returns (seeds, info)."""
+    k = min(int(k), n)
+    delta = 1.0 / n if delta is None else float(delta)
+    if not 0 < epsilon < 1 or not 0 < delta < 1:
+        raise ValueError("epsilon and delta must lie in (0, 1)")
+    if k <= 0:
+        return [], {"samples": 0, "covered": 0, "estimated_influence": 0.0, "rounds": 0, "lower": 0.0, "upper": 0.0, "ratio": 0.0}
+    theta, theta_max, i_max, a = opim_sample_plan(n, k, epsilon, delta, max_samples)
+    for i in range(1, i_max + 1):
+        sample(theta)
+        seeds, gains = cover(k)
+        covered = int(np.sum(gains))
+        lower, upper = opim_bounds(covered, int(count(seeds)), theta, n, a)
+        ratio = lower / upper
+        if ratio >= _E1 - epsilon or i == i_max:
+            break
+        theta *= 2
+    return list(seeds), {"samples": theta, "covered": covered, "estimated_influence": n * covered / theta, "rounds": i,
+                         "lower": lower, "upper": upper, "ratio": ratio}
+
+
+def ris_seed_selection(G, k, p=0.1, iterations_count=200, *, n_samples=None, epsilon=None, delta=None, max_samples=None,
+                       seed=None):
+    """Seeds by reverse influence sampling: (seeds, info), with greedy_seed_selection's conventions (hops =
+    iterations_count - 2, seed=None drawn from numpy's generator, G may be an InfluenceGraph).
+
+    n_samples = theta: one collection on trials 0 .. theta-1, then greedy maximum coverage.  epsilon (delta = 1/n by
+    default; epsilon = 0.1 when neither mode is named): OPIM-C, doubling two collections until the seeds are within
+    1 - 1/e - epsilon of the optimum with probability 1 - delta, at most max_samples sets each.
+    info: samples, covered, estimated_influence = n * covered / samples, rounds, and lower, upper, ratio with epsilon."""
+    if n_samples is not None and epsilon is not None:
+        raise ValueError("give n_samples (fixed mode) or epsilon (OPIM-C), not both")
+    if n_samples is None and epsilon is None:
+        epsilon = 0.1
+    if n_samples is not None and int(n_samples) < 1:
+        raise ValueError("n_samples must be >= 1")
+    if int(k) < 0:
+        raise ValueError("k must be >= 0")
+    seed = _draw_seed(seed)
+    g = G if isinstance(G, InfluenceGraph) else InfluenceGraph(G)
+    hops = _ndlib_hops(int(iterations_count))
+    k = min(int(k), g.n)
+    if hops is None or k == 0:   # nothing is ever removed: every gain is 0, the choice is 0, 1, 2, ...
+        seeds = list(range(k)) if g.labels is None else [g.labels[s] for s in range(k)]
+        info = {"samples": 0, "covered": 0, "estimated_influence": 0.0, "rounds": 0}
+        if epsilon is not None:
+            info.update(lower=0.0, upper=0.0, ratio=0.0)
+        return seeds, info
+    if n_samples is not None:
+        coll = g.rr_sets(int(n_samples), p, hops, seed)
+        try:
+            seeds, gains = coll.cover(k)
+        finally:
+            coll.close()
+        covered = int(gains.sum())
+        return seeds, {"samples": int(n_samples), "covered": covered, "estimated_influence": g.n * covered / int(n_samples),
+                       "rounds": 1}
+    r1, r2 = g.rr_sets(0, p, hops, seed), g.rr_sets(0, p, hops, seed)
+
+    def sample(theta):
+        have = len(r1)
+        r1.extend(theta - have, trials=2 * np.arange(have, theta, dtype=np.uint64))
+        r2.extend(theta - have, trials=2 * np.arange(have, theta, dtype=np.uint64) + np.uint64(1))
+    try:
+        return opim_c(sample, r1.cover, r2.count_hit, g.n, k, float(epsilon), delta, max_samples)
+    finally:
+        r1.close()
+        r2.close()
+
+
 def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iterations=200, dim=3, num_layout_iterations=20,
-                            layout_params=None, backend="hip"):
+                            layout_params=None, backend="hip", ris=False):
     """The reference's run_influence_benchmark (benchmark.py:246-379) on this package's embedder and the functions above:
     GraphEm seeds against greedy seeds and a random baseline, each scored with ndlib_estimated_influence.  The generator
-    may return an (E, 2) edge array or an adjacency matrix.  Returns the reference's result keys."""
+    may return an (E, 2) edge array or an adjacency matrix.  Returns the reference's result keys; ris=True adds
+    ris_seeds, ris_influence, ris_time and ris_samples from ris_seed_selection (epsilon = 0.1)."""
     from . import create_graphem, graphem_seed_selection, edges_to_adjacency
     start_time = time.time()
     out = graph_generator(**graph_params)
@@ -261,6 +455,12 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
         random_seeds = np.random.choice(n, k, replace=False)
         random_influences.append(ndlib_estimated_influence(graph, random_seeds, p, iterations)[0])
     random_influence = np.mean(random_influences)
+    ris_results = {}
+    if ris:
+        ris_start = time.time()
+        ris_seeds, ris_info = ris_seed_selection(graph, k, p, iterations)
+        ris_results = {"ris_seeds": ris_seeds, "ris_time": time.time() - ris_start, "ris_samples": ris_info["samples"],
+                       "ris_influence": ndlib_estimated_influence(graph, ris_seeds, p, iterations)[0]}
     graph.close()
 
     results = {
@@ -284,5 +484,6 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
     }
     results["graphem_efficiency"] = results["graphem_norm_influence"] / graphem_time if graphem_time > 0 else 0
     results["greedy_efficiency"] = results["greedy_norm_influence"] / greedy_time if greedy_time > 0 else 0
+    results.update(ris_results)
     results["total_time"] = time.time() - start_time
     return results

@@ -499,6 +499,54 @@ gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_tri
                        const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                        int64_t *totals, int32_t *per_trial);
 
+/* ---- reverse influence sampling (RIS; Borgs et al. 2014, TIM/IMM, OPIM-C; graphem-rapids_amd/influence.py) --------------
+ * A collection of reverse-reachable (RR) sets on the device behind its own handle, drawn by a gh_ic handle with the coins
+ * above.  Sample j of a collection is the pair (trial t_j, root r_j).
+ *
+ * RR set: RR(t, r) is the set of vertices u from which r is reached over the live arcs of trial t within max_hops hops
+ * (-1: no limit): a breadth-first search from r that walks every arc u -> v backwards, with the unchanged
+ * coin(seed, t, a, b) of that arc -- (a, b) = (u, v) for a directed arc u -> v, (min, max) for an undirected edge.  r
+ * always belongs to its set; members are reported in ascending id.
+ * Default root: from the trial's own word with a key no arc can have (all ones would be a self-loop on vertex 2^32 - 1,
+ * and self-loops are dropped):
+ *     w = mix( mix(seed + t * 0x9E3779B97F4A7C15) ^ 0xFFFFFFFFFFFFFFFF ),   r = ((w >> 32) * n) >> 32
+ * Default trials: the trial of a sample is its index in the collection, so an empty collection gets 0 .. theta - 1 and
+ * appending continues the sequence.  A caller may pass explicit trials (uint64) and / or roots (int32) instead.
+ * Maximum coverage: each of min(k, n) rounds takes the not yet chosen vertex contained in the most UNCOVERED sets, ties to
+ * the smallest id; the sets it hits become covered; a round with gain 0 still chooses (the smallest unchosen id).
+ * Estimate: the spread of S is estimated as n * (sets hit by S) / theta, one double division.
+ * Identity: for a fixed trial t and any seed set S,
+ *     sum over all roots r of [S meets RR(t, r)]  =  |R_t(S)|,
+ * the per-trial count gh_ic_spread returns for the same p, seed and max_hops (u reaches r forwards iff r reaches u
+ * backwards, and both searches cut at the same number of hops).
+ * Results depend only on (arc set, p, max_hops, seed, the samples): not on chunking or either memory budget. */
+typedef struct gh_rr *gh_rr_handle;
+
+/* An empty collection over vertex ids [0, n) on a device.  On failure *out = NULL, gh_rr_last_error(NULL) has the message. */
+gh_status gh_rr_create(gh_rr_handle *out, int device_id, int64_t n);
+void gh_rr_destroy(gh_rr_handle h);
+const char *gh_rr_last_error(gh_rr_handle h);
+/* Device bytes a collection may hold: 8 * (sets + 1) + 4 * sets + 4 * members.  0 restores the default, 4 GiB. */
+gh_status gh_rr_set_memory_budget(gh_rr_handle h, int64_t bytes);
+/* Appends n_samples RR sets drawn with ic's graph and coins; trials / roots: host arrays of n_samples, or NULL for the
+ * defaults above.  Samples are chunked to ic's memory budget as gh_ic_spread chunks seed sets (n * (24 * W + 17) bytes for
+ * 64 * W samples at once, W at most 128 and at most max(16, n / 2048)).  GH_ERR_INVALID for p outside [0, 1], max_hops < -1, a root outside [0, n), a collection of
+ * another n or device.  GH_ERR_NOMEM, with the mean set size so far in gh_ic_last_error(ic), when the collection would
+ * outgrow ITS budget: RIS is for sets that are small against n.  A failed call leaves the collection as it was.  Blocking. */
+gh_status gh_ic_rr_sample(gh_ic_handle ic, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                          const uint64_t *trials, const int32_t *roots);
+gh_status gh_rr_counts(gh_rr_handle h, int64_t *n_sets, int64_t *n_members);
+/* Host arrays (each may be NULL): indptr int64 (sets + 1), members int32, roots int32 (sets; -1 for an uploaded set
+ * without one).  Blocking. */
+gh_status gh_rr_download(gh_rr_handle h, int64_t *indptr, int32_t *members, int32_t *roots);
+/* Replaces the contents by a host CSR, so maximum coverage serves any set system: indptr[0] = 0, not decreasing; the
+ * members of a set in [0, n), strictly ascending; roots NULL or n_sets ids (-1: none).  Blocking. */
+gh_status gh_rr_upload(gh_rr_handle h, int64_t n_sets, const int64_t *indptr, const int32_t *members, const int32_t *roots);
+/* Greedy maximum coverage as above: seeds int32 and gains int64, host arrays of min(k, n).  Blocking. */
+gh_status gh_rr_cover(gh_rr_handle h, int64_t k, int32_t *seeds, int64_t *gains);
+/* *count = sets that contain at least one of the m vertices (duplicates allowed).  Blocking. */
+gh_status gh_rr_count_hit(gh_rr_handle h, const int32_t *vertices, int64_t m, int64_t *count);
+
 /* ---- centrality (reference benchmark.py: run_benchmark, benchmark_correlations; graphem-rapids_amd/centrality.py) ----
  * A handle over one undirected, unweighted graph, independent of the layout engine.  Self-loops are dropped and
  * duplicate edges merged.  Everything is fp64.
