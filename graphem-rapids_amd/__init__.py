@@ -16,7 +16,7 @@ from .generators import (erdos_renyi_graph, generate_random_regular, erdos_renyi
                          barabasi_albert_edges, caveman_edges, road_network_edges, balanced_tree_edges,
                          watts_strogatz_edges, powerlaw_cluster_edges, scale_free_edges, relaxed_caveman_edges)
 from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influence, greedy_seed_selection,
-                        run_influence_benchmark, RRCollection, max_coverage, ris_seed_selection)
+                        run_influence_benchmark, RRCollection, max_coverage, ris_seed_selection, kshell_seed_selection)
 from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
                          eigenvector_centrality_numpy, run_benchmark, benchmark_correlations)
 from . import graphstats
@@ -25,6 +25,8 @@ from .graphstats import (connected_components, number_connected_components, is_c
                          average_clustering, transitivity, graph_summary, print_graph_summary)
 from . import communities
 from .communities import (modularity, louvain_communities, louvain_partitions, community_labels, adjusted_rand_index)
+from . import cores
+from .cores import (core_number, onion_layers, degeneracy, k_core, k_shell, k_crust, k_corona, truss_number, k_truss)
 from . import quality
 from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
                       neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality)
@@ -78,7 +80,7 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "graphem_seed_selection", "MemoryManager", "cleanup_gpu_memory", "get_gpu_memory_info",
            "get_optimal_chunk_size", "monitor_memory_usage", "InfluenceGraph", "influence_spread",
            "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark", "RRCollection", "max_coverage",
-           "ris_seed_selection",
+           "ris_seed_selection", "kshell_seed_selection",
            "CentralityGraph", "betweenness_centrality", "load_centrality", "closeness_centrality", "pagerank",
            "eigenvector_centrality_numpy", "run_benchmark", "benchmark_correlations",
            "generate_sbm", "generate_ba", "generate_ws", "generate_power_cluster", "generate_scale_free",
@@ -93,6 +95,8 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "plot_radial_vs_centrality", "display_benchmark_results",
            "communities", "modularity", "louvain_communities", "louvain_partitions", "community_labels",
            "adjusted_rand_index",
+           "cores", "core_number", "onion_layers", "degeneracy", "k_core", "k_shell", "k_crust", "k_corona", "truss_number",
+           "k_truss",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
            "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",

@@ -154,6 +154,8 @@ SIGNATURES = {
     "gh_cent_components": (_int, [vp, vp, _P(i64)]),
     "gh_cent_distances": (_int, [vp, i64, vp, vp, vp, vp]),
     "gh_cent_triangles": (_int, [vp, vp]),
+    "gh_cent_cores": (_int, [vp, vp, vp, _P(i32)]),
+    "gh_cent_truss": (_int, [vp, vp, _P(i32)]),
     "gh_cent_modularity": (_int, [vp, vp, vp]),
     "gh_cent_louvain": (_int, [vp, u64, i32, i32, vp, _P(i32), vp, vp, vp]),
     "gh_gen_create": (_int, [_P(vp), _int]),
@@ -714,6 +716,22 @@ class CentGraph(BudgetHandle):
         tri = np.zeros(self.n, dtype=np.int64)
         self._raise(self.lib.gh_cent_triangles(self.handle, ptr(tri)))
         return tri
+
+    def cores(self):
+        """(core (n,) int32, layer (n,) int32, rounds): core numbers, onion layers and the number of peel rounds
+        (gh_cent_cores)."""
+        core = np.zeros(self.n, dtype=np.int32)
+        layer = np.zeros(self.n, dtype=np.int32)
+        rounds = ctypes.c_int32(0)
+        self._raise(self.lib.gh_cent_cores(self.handle, ptr(core), ptr(layer), ctypes.byref(rounds)))
+        return core, layer, int(rounds.value)
+
+    def truss(self):
+        """(truss (edges,) int32 in canonical edge order, rounds) (gh_cent_truss)."""
+        truss = np.zeros(self.edges, dtype=np.int32)
+        rounds = ctypes.c_int32(0)
+        self._raise(self.lib.gh_cent_truss(self.handle, ptr(truss), ctypes.byref(rounds)))
+        return truss, int(rounds.value)
 
     def modularity(self, labels):
         """(sum I, sum T^2, M) of a labelling with values in [0, n), as Python ints (gh_cent_modularity)."""

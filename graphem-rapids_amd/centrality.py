@@ -209,6 +209,19 @@ class CentralityGraph:
             return np.zeros(0, dtype=np.int64)
         return self._g.triangles()
 
+    def core_layers(self):
+        """(core (n,) int32, layer (n,) int32): networkx's core_number and onion_layers in vertex order, from one
+        synchronous peel (gh_cent_cores)."""
+        if self._g is None:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return self._g.cores()[:2]
+
+    def truss_numbers(self):
+        """(n_edges,) int32 aligned with self.edges: the largest k whose k-truss holds the edge (gh_cent_truss)."""
+        if self._g is None:
+            return np.zeros(0, dtype=np.int32)
+        return self._g.truss()[0]
+
     def louvain_levels(self, seed=0, max_levels=32, max_rounds=1000):
         """The Louvain levels of include/graphem_hip.h "communities" (gh_cent_louvain): (labels (L, n) int32, numerators
         [L] of Python ints, n_communities (L,) int64, rounds (L,) int32, M).  labels[l][v] = the smallest vertex id in v's
@@ -389,7 +402,7 @@ def _generate(graph_generator, graph_params):
 
 
 def run_benchmark(graph_generator, graph_params, dim=3, L_min=10.0, k_attr=0.5, k_inter=0.1, n_neighbors=15,
-                  sample_size=512, num_iterations=40, backend="hip", *, betweenness_k=None, **kwargs):
+                  sample_size=512, num_iterations=40, backend="hip", *, betweenness_k=None, cores=False, **kwargs):
     """The reference's run_benchmark (benchmark.py:18-160) with every centrality on the GPU and this package's embedder:
     the reference's result keys, plus 'centrality_time' (seconds spent on the six centralities) and 'betweenness_k'.
     The generator may return an (E, 2) edge array or an adjacency matrix.
@@ -398,7 +411,10 @@ def run_benchmark(graph_generator, graph_params, dim=3, L_min=10.0, k_attr=0.5, 
     networkx's sample of that many sources (random.Random(seed).sample over the nodes, seed = kwargs' 'seed' or 0),
     scaled by n / k.  Closeness stays exact: it comes from the same pass when betweenness_k is None, else from a
     distances-only pass over every vertex.  A disconnected graph has no eigenvector centrality; as in the reference, degree
-    centrality stands in for it."""
+    centrality stands in for it.
+
+    cores=True adds 'core_number' and 'onion_layer' (float arrays; CentralityGraph.core_layers), counted in
+    'centrality_time'."""
     from . import create_graphem, edges_to_adjacency
     start_time = time.time()
     n, edges, adjacency = _generate(graph_generator, graph_params)
@@ -421,6 +437,7 @@ def run_benchmark(graph_generator, graph_params, dim=3, L_min=10.0, k_attr=0.5, 
         logger.warning("Eigenvector centrality calculation failed: %s; using degree centrality", e)
         eigenvector = degree / (n - 1.0) if n > 1 else np.ones(n)
     pr = g.pagerank()
+    core_layers = g.core_layers() if cores else None
     g.close()
     centrality_time = time.time() - c0
 
@@ -452,35 +469,41 @@ def run_benchmark(graph_generator, graph_params, dim=3, L_min=10.0, k_attr=0.5, 
         "centrality_time": centrality_time,
         "betweenness_k": betweenness_k,
     }
+    if cores:
+        result["core_number"] = core_layers[0].astype(np.float64)
+        result["onion_layer"] = core_layers[1].astype(np.float64)
     result["total_time"] = time.time() - start_time
     return result
 
 
 CORRELATION_KEYS = ("degree", "betweenness", "eigenvector", "pagerank", "closeness", "node_load")
+CORE_KEYS = ("core_number", "onion_layer")
 
 
 def benchmark_correlations(graph_generator, graph_params, dim=2, L_min=10.0, k_attr=0.5, k_inter=0.1, n_neighbors=15,
                            sample_size=512, num_iterations=40, backend="hip", *, betweenness_k=None, bootstrap_reps=None,
-                           bootstrap_seed=0, **kwargs):
+                           bootstrap_seed=0, cores=False, **kwargs):
     """The reference's benchmark_correlations (benchmark.py:163-243): run_benchmark, then Spearman's rho (and p) between
     the radii and each centrality under results['correlations'][name] = {'rho', 'p'}.
 
     bootstrap_reps: None -- exactly that; an int -- every entry also gets 'ci_low' and 'ci_high', the 2.5 and 97.5
-    percentiles of that many bootstrap replicates (visualization.bootstrap_spearman with seed bootstrap_seed)."""
+    percentiles of that many bootstrap replicates (visualization.bootstrap_spearman with seed bootstrap_seed).
+    cores=True: run_benchmark's 'core_number' and 'onion_layer' arrays, correlated like the six centralities."""
     from scipy import stats
     results = run_benchmark(graph_generator, graph_params, dim=dim, L_min=L_min, k_attr=k_attr, k_inter=k_inter,
                             n_neighbors=n_neighbors, sample_size=sample_size, num_iterations=num_iterations,
-                            backend=backend, betweenness_k=betweenness_k, **kwargs)
+                            backend=backend, betweenness_k=betweenness_k, cores=cores, **kwargs)
+    names = CORRELATION_KEYS + (CORE_KEYS if cores else ())
     radii = results["radii"]
     correlations = {}
-    for name in CORRELATION_KEYS:
+    for name in names:
         rho, p = stats.spearmanr(radii, results[name])
         correlations[name] = {"rho": rho, "p": p}
     if bootstrap_reps is not None:
         from .visualization import bootstrap_spearman
-        _, _, ci_low, ci_high, _ = bootstrap_spearman(radii, [results[name] for name in CORRELATION_KEYS],
+        _, _, ci_low, ci_high, _ = bootstrap_spearman(radii, [results[name] for name in names],
                                                       reps=bootstrap_reps, seed=bootstrap_seed)
-        for j, name in enumerate(CORRELATION_KEYS):
+        for j, name in enumerate(names):
             correlations[name]["ci_low"] = float(ci_low[j])
             correlations[name]["ci_high"] = float(ci_high[j])
     results["correlations"] = correlations

@@ -32,19 +32,11 @@
 
 #include "../../include/graphem_hip.h"
 #include "cent_handle.h"
-
-#define GS_BLOCK 256
-#define GS_MAX_BLOCKS 4096
-#define GS_CHECK_EVERY 4   // component rounds / distance levels between two host reads of the flags
+#include "csr_core.h"
 
 namespace {
 
 typedef unsigned long long gs_u64;
-
-__device__ __forceinline__ int32_t gs_flag(const int32_t *f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-#define GS_GRID_LOOP(i, items) \
-    for (int64_t i = (int64_t)blockIdx.x * GS_BLOCK + threadIdx.x; i < (items); i += (int64_t)gridDim.x * GS_BLOCK)
 
 // ---- components -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GS_BLOCK) void gs_label_init_kernel(int64_t n, int32_t *label) {
@@ -152,27 +144,11 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(GsLevel a) {
 }
 
 // ---- triangles ------------------------------------------------------------------------------------------------------
-// first position in [lo, hi) whose entry is >= x
-__device__ __forceinline__ int64_t gs_lower_bound(const int32_t *__restrict__ a, int64_t lo, int64_t hi, int32_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(GS_BLOCK) void gs_triangle_kernel(int64_t n, int64_t arcs, const int64_t *__restrict__ ptr,
                                                                const int32_t *__restrict__ adj, gs_u64 *tri) {
     GS_GRID_LOOP(e, arcs) {
         const int32_t v = adj[e];
-        int64_t lo = 0, hi = n;   // the row of arc e: the last u with ptr[u] <= e
-        while (hi - lo > 1) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (ptr[mid] <= e) lo = mid;
-            else hi = mid;
-        }
-        const int32_t u = (int32_t)lo;
+        const int32_t u = gs_arc_row(ptr, n, e);
         if (v <= u) continue;
         const int64_t ub = ptr[u], ue = ptr[u + 1], vb = ptr[v], ve = ptr[v + 1];
         const bool u_short = ue - ub <= ve - vb;
@@ -194,10 +170,6 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_triangle_kernel(int64_t n, int64_
             atomicAdd(&tri[v], c);
         }
     }
-}
-
-inline int gs_blocks(int64_t items) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(GS_MAX_BLOCKS, (items + GS_BLOCK - 1) / GS_BLOCK));
 }
 
 gh_status gs_components(gh_cent *h, int32_t *labels) {

@@ -410,12 +410,40 @@ def ris_seed_selection(G, k, p=0.1, iterations_count=200, *, n_samples=None, eps
         r2.close()
 
 
+def kshell_seed_selection(G, k):
+    """The k-shell baseline for influential spreaders (Kitsak et al. 2010): the k vertices first in the order (core number
+    descending, onion layer descending, degree descending, vertex id ascending), as nodes.  A pure function of the graph:
+    no coins, one peel on the GPU (gh_cent_cores).  G: what CentralityGraph takes, a CentralityGraph, or an undirected
+    InfluenceGraph.  ValueError for k outside [0, n]."""
+    from .centrality import CentralityGraph   # centrality imports this module
+    if isinstance(G, InfluenceGraph):
+        if G.directed:
+            raise NotImplementedError("k-shell seeds are for undirected graphs")
+        g, own, labels = CentralityGraph(G.arcs, n=G.n), True, G.labels
+    elif isinstance(G, CentralityGraph):
+        g, own, labels = G, False, G.labels
+    else:
+        g, own = CentralityGraph(G), True
+        labels = g.labels
+    try:
+        k = int(k)
+        if k < 0 or k > g.n:
+            raise ValueError(f"k must lie in [0, {g.n}]")
+        core, layer = g.core_layers()
+        order = np.lexsort((np.arange(g.n), -g.degree(), -layer.astype(np.int64), -core.astype(np.int64)))[:k]
+        return order.tolist() if labels is None else [labels[i] for i in order]
+    finally:
+        if own:
+            g.close()
+
+
 def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iterations=200, dim=3, num_layout_iterations=20,
-                            layout_params=None, backend="hip", ris=False):
+                            layout_params=None, backend="hip", ris=False, kshell=False):
     """The reference's run_influence_benchmark (benchmark.py:246-379) on this package's embedder and the functions above:
     GraphEm seeds against greedy seeds and a random baseline, each scored with ndlib_estimated_influence.  The generator
     may return an (E, 2) edge array or an adjacency matrix.  Returns the reference's result keys; ris=True adds
-    ris_seeds, ris_influence, ris_time and ris_samples from ris_seed_selection (epsilon = 0.1)."""
+    ris_seeds, ris_influence, ris_time and ris_samples from ris_seed_selection (epsilon = 0.1); kshell=True adds
+    kshell_seeds, kshell_influence and kshell_time from kshell_seed_selection."""
     from . import create_graphem, graphem_seed_selection, edges_to_adjacency
     start_time = time.time()
     out = graph_generator(**graph_params)
@@ -461,6 +489,12 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
         ris_seeds, ris_info = ris_seed_selection(graph, k, p, iterations)
         ris_results = {"ris_seeds": ris_seeds, "ris_time": time.time() - ris_start, "ris_samples": ris_info["samples"],
                        "ris_influence": ndlib_estimated_influence(graph, ris_seeds, p, iterations)[0]}
+    kshell_results = {}
+    if kshell:
+        kshell_start = time.time()
+        kshell_seeds = kshell_seed_selection(graph, k)
+        kshell_results = {"kshell_seeds": kshell_seeds, "kshell_time": time.time() - kshell_start,
+                          "kshell_influence": ndlib_estimated_influence(graph, kshell_seeds, p, iterations)[0]}
     graph.close()
 
     results = {
@@ -485,5 +519,6 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
     results["graphem_efficiency"] = results["graphem_norm_influence"] / graphem_time if graphem_time > 0 else 0
     results["greedy_efficiency"] = results["greedy_norm_influence"] / greedy_time if greedy_time > 0 else 0
     results.update(ris_results)
+    results.update(kshell_results)
     results["total_time"] = time.time() - start_time
     return results

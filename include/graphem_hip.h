@@ -621,6 +621,41 @@ gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, const int32_t *
  * searched in the longer one, so an edge costs min(deg) log(max deg); counts are 64-bit throughout. */
 gh_status gh_cent_triangles(gh_cent_handle h, int64_t *triangles);
 
+/* ---- cores and trusses (graphem-rapids_amd/cores.py) ----------------------------------------------------------------
+ * The k-core and k-truss decompositions of a gh_cent handle's graph, under the preamble of "graph statistics":
+ * undirected, unweighted, self-loops dropped, duplicate edges merged, every output an integer, blocking calls that
+ * report through gh_cent_last_error(h), GH_ERR_INVALID for a NULL handle.  Each result is a pure function of the edge
+ * set: not of edge order, duplicate edges, scheduling, nor of earlier calls on the handle.  Both are synchronous peels.
+ *
+ * Vertex peel (core number and onion layer).  State: deg[v], alive[v], threshold k = 0, round r = 0.  While a vertex is
+ * alive:
+ *     r += 1;  k = max(k, min over alive v of deg[v]);  S = {alive v : deg[v] <= k};
+ *     every v in S gets core[v] = k and layer[v] = r and dies;
+ *     every surviving vertex loses one degree per neighbour in S.
+ * Isolated vertices leave in round 1 with core 0.  core is networkx.core_number, layer is networkx.onion_layers.
+ *
+ * Edge peel (truss number).  Edge ids are the positions in the canonical edge list: u < v, sorted by (u, v) -- the order
+ * of the CSR's upper arcs.  sup[e] = the triangles through e whose three edges are alive.  State: j = 0, r = 0.  While an
+ * edge is alive:
+ *     r += 1;  j = max(j, min over alive e of sup[e]);  S = {alive e : sup[e] <= j};
+ *     every e in S gets truss[e] = j + 2 and dies;
+ *     every triangle that was alive at the start of the round and has an edge in S is destroyed, and each of its edges
+ *     outside S loses exactly one support (on the device the triangle is charged to its smallest-id edge in S).
+ * {e : truss[e] >= k} is the edge set of networkx.k_truss(G, k) for every k >= 2.
+ *
+ * A round is a fixed sequence of launches: select S, let S take what it owes from the survivors with integer atomicSub,
+ * and a one-thread step that moves k (or j), r and the alive count on.  A selection that finds S empty only raises the
+ * threshold to the minimum it saw and has no round number.  The host reads the device's "nobody alive" flag every 4
+ * steps.  *n_rounds (may be NULL) = r at the end: the largest onion layer for the vertex peel.  More than 2^31 - 1 arcs
+ * (twice the edges) give GH_ERR_INVALID; a peel that outlives its bound (items + 1 rounds) GH_ERR_RUNTIME. */
+
+/* core, layer: host int32[n] each; either may be NULL.  n = 0: GH_OK with *n_rounds = 0.  Device state: 8 n bytes. */
+gh_status gh_cent_cores(gh_cent_handle h, int32_t *core, int32_t *layer, int32_t *n_rounds);
+/* truss: host int32[edges] in canonical edge order (gh_cent_edge_count).  No edges: GH_OK with *n_rounds = 0.  Device
+ * state: 12 bytes per arc (edge id per arc; endpoint, arc position, support and removal round per edge), and 16 n bytes
+ * plus a scan's work space while the edge ids are built. */
+gh_status gh_cent_truss(gh_cent_handle h, int32_t *truss, int32_t *n_rounds);
+
 /* ---- communities: Louvain levels and exact modularity (graphem-rapids_amd/communities.py) -------------------------------
  * Over a gh_cent handle's graph: undirected, unweighted, self-loops dropped and duplicate edges merged.  Every quantity
  * is an exact integer and no floating-point number is ever compared, so the result is a pure function of (edge set, n,
