@@ -447,7 +447,12 @@ gh_status gh_spmv_symnorm(void *hip_stream, int64_t n, const int64_t *indptr, co
  * matvec, classical Gram-Schmidt twice against the nl locked vectors and the basis so far, coefficients into column j of
  * Td, beta[j] = |w|, hmax[j] = max |coefficient|, next basis vector -- seven launches per step on hip_stream, no host
  * synchronisation.  V (nl + m + 1, n), Td (m, m) row-major, work: n + 2 (nl + m + 1) + ceil(n / 512) (nl + m + 1)
- * doubles, beta / hmax (m); all DEVICE pointers; nl + m + 1 <= 256. */
+ * doubles, beta / hmax (m); all DEVICE pointers; nl + m + 1 <= 256.
+ * Layout of work, with R = nl + j + 1 and as the LAST step j of the call left it: w at 0 (n doubles: B V[nl + j] after
+ * both passes, before the division by beta[j]); h1 at n (the R coefficients of the first pass, row by row of V); h2 at
+ * n + (nl + m + 1) (those of the second pass, taken on w after the first); the chunk partials from n + 2 (nl + m + 1)
+ * on.  Td[r - nl][j] = h1[r] + h2[r] for nl <= r < R; no other entry of Td, beta or hmax is written, nor any row of V
+ * but nl + j + 1.  k == m is an empty sweep: GH_OK, nothing written. */
 gh_status gh_trlan_sweep(void *hip_stream, int64_t n, const int64_t *indptr, const int32_t *indices,
                          const double *inv_sqrt_deg, double *V, int32_t nl, int32_t m, int32_t k, double *Td,
                          double *work, double *beta, double *hmax);

@@ -140,15 +140,30 @@ def test_spans_the_references_own_eigsh_start_at_100k():
 @pytest.mark.gpu
 def test_sweep_kernels_equal_the_torch_steps():
     """gh_trlan_sweep (csrc/spectral.hip: matvec + classical Gram-Schmidt twice as kernels) against the same solver with
-    torch GEMVs: same eigenvalues and subspace on a graph with isolated vertices and a degenerate spectrum."""
+    torch GEMVs: same eigenvalues on a graph with isolated vertices and a degenerate spectrum (all five wanted eigenvalues
+    are 0 there, whatever the solver does) and on a connected one, where they are not.  Every returned column x_j of
+    either method is an eigenvector to its eigenvalue: |L x_j - lambda_j x_j| <= 4 tol |x_j| -- tol bounds the Ritz
+    estimate |B y - theta y| / theta, theta <= 2 on B, and 2 for the gap between the estimate and the true residual."""
     import graphem_rapids_amd as gra
     from graphem_rapids_amd.spectral import laplacian_embedding_hip
-    n = 30000
-    edges = gra.erdos_renyi_edges(n, 4.0 / n, seed=5)     # mean degree 4: isolated vertices, small components
-    adj = gra.edges_to_adjacency(n, edges)
-    out = {}
-    for method in ("trlan", "trlan_torch"):
-        emb, info = laplacian_embedding_hip(adj, 4, return_info=True, tol=1e-9, method=method)
-        assert info["converged"]
-        out[method] = (np.sort(np.asarray(info["eigenvalues"])[:5]), emb.astype(np.float64))
-    np.testing.assert_allclose(out["trlan"][0], out["trlan_torch"][0], atol=1e-8)
+    n, tol = 30000, 1e-9
+    graphs = {"er": gra.edges_to_adjacency(n, gra.erdos_renyi_edges(n, 4.0 / n, seed=5)),   # mean degree 4: isolated
+              "rr": gra.generate_random_regular(n, 6, seed=5)}                              # vertices, small components
+    for name, adj in graphs.items():
+        sym = sp.csr_matrix(adj + adj.transpose())
+        sym.data = np.ones_like(sym.data)
+        L = laplacian(sym, normed=True)                   # as _reference_eig, but sparse
+        out = {}
+        for method in ("trlan", "trlan_torch"):
+            emb, info = laplacian_embedding_hip(adj, 4, return_info=True, tol=tol, method=method)
+            assert info["converged"]
+            lam, X = np.asarray(info["eigenvalues"])[:5], info["vectors_all"]
+            assert emb.shape == (n, 4) and X.shape == (n, 5)
+            resid = np.linalg.norm(L @ X - X * lam, axis=0) / np.linalg.norm(X, axis=0)
+            print(f"\n{name} {method}: eigenvalues {lam}, residuals {resid}")
+            assert np.all(resid <= 4 * tol), (name, method, resid)
+            out[method] = np.sort(lam)
+        np.testing.assert_allclose(out["trlan"], out["trlan_torch"], atol=1e-8)
+        if name == "rr":                                  # connected: one zero eigenvalue, then the spectral gap
+            for lam in out.values():
+                assert lam[0] < 1e-8 < lam[1]
