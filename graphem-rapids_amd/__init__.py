@@ -29,7 +29,8 @@ from . import cores
 from .cores import (core_number, onion_layers, degeneracy, k_core, k_shell, k_crust, k_corona, truss_number, k_truss)
 from . import quality
 from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
-                      neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality)
+                      neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality,
+                      hop_profile, layout_stress, hop_distance_correlation, distance_quality)
 from . import datasets
 from .datasets import (read_edge_list, parse_edge_list, load_dataset, load_dataset_as_networkx, load_dataset_adjacency,
                        list_available_datasets, get_data_directory, SNAPDataset, NetworkRepositoryDataset,
@@ -99,6 +100,7 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "k_truss",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
            "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
+           "hop_profile", "layout_stress", "hop_distance_correlation", "distance_quality",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",
            "load_dataset_adjacency", "list_available_datasets", "get_data_directory", "SNAPDataset",
            "NetworkRepositoryDataset", "SemanticScholarDataset"]

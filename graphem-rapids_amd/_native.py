@@ -183,6 +183,7 @@ SIGNATURES = {
     "gh_qual_edge_lengths": (_int, [vp, vp]),
     "gh_qual_neighbor_sizes": (_int, [vp, i64, vp, vp]),
     "gh_qual_neighbor_ranks": (_int, [vp, i64, vp, vp, vp, vp, vp]),
+    "gh_qual_hop_profile": (_int, [vp, i64, vp, i64, _P(i64), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gh_ingest_create": (_int, [_P(vp), _int]),
     "gh_ingest_destroy": (None, [vp]),
     "gh_ingest_last_error": (_str, [vp]),
@@ -924,7 +925,8 @@ def corr_rho(sxy, sxx, syy):
 class LayoutQuality(Handle):
     """Thin RAII wrapper over a gh_qual_handle: exact edge-crossing counts under the engine's float32 test and edge-length
     statistics of one layout (include/graphem_hip.h "layout quality"), and the exact neighbour ranks on the simple graph of
-    the same edge list ("embedding quality").  edges: (E, 2) int32, ids kept as given.
+    the same edge list ("embedding quality"), and the hop profile on that graph ("distance preservation").  edges: (E, 2)
+    int32, ids kept as given.
     device_id < 0 is the library's host path, which touches no device and returns the same integers."""
     _destroy, _last_error = "gh_qual_destroy", "gh_qual_last_error"
 
@@ -990,6 +992,26 @@ class LayoutQuality(Handle):
         below, equal = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.int32)
         self._raise(self.lib.gh_qual_neighbor_ranks(self.handle, n_rows, ptr(rows), ptr(neighbors), ptr(dist2), ptr(below), ptr(equal)))
         return indptr, neighbors, dist2, below, equal
+
+    def hop_profile(self, sources=None):
+        """The sums of include/graphem_hip.h "distance preservation" over the source vertex ids `sources`, any order, repeats
+        allowed; None = all vertices in order (gh_qual_hop_profile).  dict: per hop h = 1 .. H, at entry h - 1, pairs (int64),
+        sum_d, sum_d2 (float64), min_d2, max_d2 (float32); per source reach (int64), eccentricity (int32), sum_d_over_h and
+        sum_d2_over_h2 (float64)."""
+        if sources is not None:
+            sources = np.ascontiguousarray(sources, dtype=np.int32).ravel()
+            if len(sources) == 0:
+                sources = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean all vertices)
+        S = self.n if sources is None else len(sources)
+        cap = max(self.n, 1)   # H <= n - 1
+        hop = {"pairs": np.zeros(cap, dtype=np.int64), "sum_d": np.zeros(cap, dtype=np.float64), "sum_d2": np.zeros(cap, dtype=np.float64),
+               "min_d2": np.zeros(cap, dtype=np.float32), "max_d2": np.zeros(cap, dtype=np.float32)}
+        out = {"reach": np.zeros(S, dtype=np.int64), "eccentricity": np.zeros(S, dtype=np.int32),
+               "sum_d_over_h": np.zeros(S, dtype=np.float64), "sum_d2_over_h2": np.zeros(S, dtype=np.float64)}
+        H = ctypes.c_int64()
+        self._raise(self.lib.gh_qual_hop_profile(self.handle, S, ptr(sources), cap, ctypes.byref(H), *(ptr(a) for a in hop.values()),
+                                                 *(ptr(a) for a in out.values())))
+        return {**{key: a[:H.value].copy() for key, a in hop.items()}, **out}
 
 
 class EdgeListParser(BudgetHandle):

@@ -14,6 +14,11 @@
 //   qual_length_kernel     per-edge length in double; min / max / sum / sum of squares by wave shuffles and one LDS step,
 //                          one partial per workgroup, combined on the host in workgroup order (deterministic, no atomics)
 //
+//   qual_hop_level_kernel  distance preservation ("distance preservation" in the header): one level of a breadth-first search
+//                          from 64 sources to a machine word; where a source first reaches a vertex the pair's distance goes
+//                          onto lane-local sums for the hop and LDS sums for the source; one slab of partials per workgroup.
+//                          qual_hop_reduce_kernel adds the slabs in a fixed order: no float atomic touches global memory.
+//
 //   qual_rank_kernel       neighbour ranks ("embedding quality" in the header): a wave owns up to 64 (source, neighbour) slots
 //                          of one source, lane i keeps threshold i and its two counts in registers, the workgroup walks the
 //                          position tiles through LDS, and per 64 columns each threshold costs two compares, two ballots and
@@ -32,10 +37,13 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <map>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "csr_core.h"
 #include "host_util.h"
 #include "intersect_core.h"
 
@@ -52,6 +60,10 @@
 #define QUAL_RANK_TILE 1024                 // columns of a tile at most; fewer when D * 1024 floats do not fit
 #define QUAL_RANK_LAUNCH_PAIRS (1ll << 40)  // (piece, column) pairs per launch: pieces are taken in batches of about a second
 #define QUAL_RANK_LAUNCH_ITEMS (1ll << 22)
+#define QUAL_HOP_SRC_LDS 8192               // floats of a group's 64 staged source rows: 32 KiB, D <= 128
+#define QUAL_HOP_MAX_BLOCKS 2048            // workgroups of one level launch, over all groups of the batch
+#define QUAL_HOP_STATE_BYTES (1ll << 30)    // visited, frontier and next frontier of the groups in flight: 24 n bytes a group
+#define QUAL_HOP_CHECK_EVERY 4              // levels between two host reads of the flags
 
 namespace {
 
@@ -278,6 +290,218 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_rank_sum_kernel(int64_t slots
     out[s] = a;
 }
 
+// ---- distance preservation ------------------------------------------------------------------------------------------
+typedef unsigned long long qual_u64;
+
+// What the pairs of one hop add up to.  mn and mx are the float's bit pattern, which orders the floats d2 can be without a
+// NaN (+0 .. +inf) as the values do.
+struct qual_hop {
+    qual_u64 pairs;
+    double sd, sq;
+    uint32_t mn, mx;
+};
+
+__host__ __device__ __forceinline__ qual_hop qual_hop_empty() { return {0, 0.0, 0.0, 0xFFFFFFFFu, 0u}; }
+
+__host__ __device__ __forceinline__ void qual_hop_join(qual_hop &a, const qual_hop &b) {
+    a.pairs += b.pairs;
+    a.sd += b.sd;
+    a.sq += b.sq;
+    a.mn = b.mn < a.mn ? b.mn : a.mn;
+    a.mx = b.mx > a.mx ? b.mx : a.mx;
+}
+
+// One pair at squared distance d2: q = (double)d2 and d = sqrt(q), an IEEE double square root; *d_out = d.
+__host__ __device__ __forceinline__ void qual_hop_pair(qual_hop &a, float d2, double *d_out) {
+    union { float f; uint32_t u; } bits = {d2};
+    const double q = (double)d2, d = sqrt(q);
+    const qual_hop one = {1, d, q, bits.u, bits.u};
+    qual_hop_join(a, one);
+    *d_out = d;
+}
+
+// vis = the unused bits of the batch's last group, 0 elsewhere; cur = 0
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_fill_kernel(int64_t n, int64_t G, uint64_t unused_last, uint64_t *vis, uint64_t *cur) {
+    for (int64_t i = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x; i < G * n; i += (int64_t)gridDim.x * QUAL_BLOCK) {
+        vis[i] = i >= (G - 1) * n ? unused_last : 0;
+        cur[i] = 0;
+    }
+}
+
+// source j of the batch: bit j & 63 of group j >> 6, at its own vertex; a repeated id is a source of its own
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_seed_kernel(int64_t n, int64_t n_src, const int32_t *__restrict__ src, qual_u64 *vis, qual_u64 *cur) {
+    const int64_t j = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x;
+    if (j >= n_src) return;
+    const int64_t w = (j >> 6) * n + src[j];
+    atomicOr(&vis[w], 1ull << (j & 63));
+    atomicOr(&cur[w], 1ull << (j & 63));
+}
+
+struct QualHopLevel {
+    const int64_t *ptr; const int32_t *idx;   // the simple graph
+    const float *pos;
+    const int32_t *src;                       // the batch's source ids, 64 per group; the unused slots of the last group hold 0
+    uint64_t *vis; const uint64_t *cur; uint64_t *nxt;
+    int32_t *flags;                           // flags[L] = 1: level L reached something
+    double *lvl_f; qual_u64 *lvl_i;           // per workgroup: (sum d, sum q) and (pairs, min bits, max bits) of this level
+    double *src_f; uint32_t *src_c;           // per workgroup: 2 x 64 sums and 64 counts, one per source of the group
+    int64_t n;
+    int32_t D, level;
+};
+
+// One level of the bit-parallel search, grid (x, G): the waves of row g stride over the vertices, 64 at a time, lane =
+// vertex.  nxt[v] = (OR of cur over the neighbours) & ~vis[v], always stored, so the ping-pong buffers need no clearing.  A
+// lane whose word of new bits is not empty walks them: bit b is the pair (source 64 g + b, v) at hop `level`, met here and
+// never again.  Per hop the lane keeps the five accumulators in registers; per source the workgroup adds in LDS.  Both
+// leave the workgroup as one slab of partials -- every workgroup writes its slab, zeros included -- and
+// qual_hop_reduce_kernel adds the slabs in a fixed order.  STAGED: the group's 64 source rows are read from LDS.
+template <bool STAGED>
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_level_kernel(QualHopLevel a) {
+    __shared__ float s_src[STAGED ? QUAL_HOP_SRC_LDS : 1];
+    __shared__ double s_sum[2][64];
+    __shared__ uint32_t s_cnt[64];
+    __shared__ int32_t s_id[64];
+    __shared__ qual_hop s_w[QUAL_BLOCK / 64];
+    if (gs_flag(&a.flags[a.level - 1]) == 0) return;   // the search ended before this level: the same for every thread
+    const int lane = threadIdx.x & 63, D = a.D;
+    const int64_t g = blockIdx.y, off = g * a.n;
+    uint64_t *vis = a.vis + off, *nxt = a.nxt + off;
+    const uint64_t *cur = a.cur + off;
+    if (threadIdx.x < 64) {
+        s_sum[0][threadIdx.x] = 0.0;
+        s_sum[1][threadIdx.x] = 0.0;
+        s_cnt[threadIdx.x] = 0;
+        s_id[threadIdx.x] = a.src[g * 64 + threadIdx.x];
+    }
+    if (STAGED)
+        for (int i = threadIdx.x; i < 64 * D; i += QUAL_BLOCK) s_src[i] = a.pos[(int64_t)a.src[g * 64 + i / D] * D + i % D];
+    __syncthreads();
+    qual_hop acc = qual_hop_empty();
+    const int64_t stride = (int64_t)gridDim.x * QUAL_BLOCK;
+    for (int64_t base = (int64_t)blockIdx.x * QUAL_BLOCK + (threadIdx.x & ~63); base < a.n; base += stride) {
+        const int64_t v = base + lane;
+        uint64_t w = 0;
+        if (v < a.n) {
+            const uint64_t need = ~vis[v];
+            if (need) {
+                uint64_t reach = 0;
+                const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
+                for (int64_t k = beg; k < end; ++k) reach |= cur[a.idx[k]];
+                w = reach & need;
+                if (w) vis[v] = ~need | w;
+            }
+            nxt[v] = w;
+        }
+        if (w == 0) continue;
+        const float *xv = a.pos + v * D;
+        // lane l starts its walk at bit l: where the words are dense the lanes of a wave add to 64 different LDS words
+        uint64_t rot = (w >> lane) | (w << ((64 - lane) & 63));
+        while (rot) {
+            const int b = (__ffsll((long long)rot) - 1 + lane) & 63;
+            rot &= rot - 1;
+            const float *xs = STAGED ? s_src + b * D : a.pos + (int64_t)s_id[b] * D;
+            const float d2 = qual_d2(xs, xv, 1, D);
+            double d;
+            qual_hop_pair(acc, d2, &d);
+            atomicAdd(&s_sum[0][b], d);
+            atomicAdd(&s_sum[1][b], (double)d2);
+            atomicAdd(&s_cnt[b], 1u);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const qual_hop other = {__shfl_down(acc.pairs, o, 64), __shfl_down(acc.sd, o, 64), __shfl_down(acc.sq, o, 64),
+                                __shfl_down(acc.mn, o, 64), __shfl_down(acc.mx, o, 64)};
+        qual_hop_join(acc, other);
+    }
+    if (lane == 0) s_w[threadIdx.x >> 6] = acc;
+    __syncthreads();   // the wave partials and every wave's LDS adds
+    const int64_t slab = g * gridDim.x + blockIdx.x;
+    if (threadIdx.x == 0) {
+        for (int wv = 1; wv < QUAL_BLOCK / 64; ++wv) qual_hop_join(acc, s_w[wv]);
+        a.lvl_f[2 * slab] = acc.sd;
+        a.lvl_f[2 * slab + 1] = acc.sq;
+        a.lvl_i[3 * slab] = acc.pairs;
+        a.lvl_i[3 * slab + 1] = acc.mn;
+        a.lvl_i[3 * slab + 2] = acc.mx;
+        if (acc.pairs && gs_flag(&a.flags[a.level]) == 0) a.flags[a.level] = 1;
+    }
+    if (threadIdx.x < 64) {
+        a.src_f[(2 * slab) * 64 + threadIdx.x] = s_sum[0][threadIdx.x];
+        a.src_f[(2 * slab + 1) * 64 + threadIdx.x] = s_sum[1][threadIdx.x];
+        a.src_c[slab * 64 + threadIdx.x] = s_cnt[threadIdx.x];
+    }
+}
+
+struct QualHopReduce {
+    const int32_t *flags;
+    const double *lvl_f; const qual_u64 *lvl_i; const double *src_f; const uint32_t *src_c;   // the slabs of G rows of X workgroups
+    double *hop_f; qual_u64 *hop_i;           // per hop L, over all batches: (sum d, sum q) at 2 L, (pairs, min bits, max bits) at 3 L
+    qual_u64 *reach; int32_t *ecc;            // per source of the batch
+    double *over_h, *over_h2;
+    int64_t X, G;
+    int32_t level;
+};
+
+// Adds the slabs of one level in a fixed order.  Workgroup g < G: the 64 sources of group g, the X slabs taken by four
+// stripes of threads and the stripes joined in order, then sum d / L and sum q / L^2 go onto the source's totals.
+// Workgroup G: the level's five values over all G X slabs, strided over the threads and joined in thread order.
+__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_reduce_kernel(QualHopReduce a) {
+    __shared__ double s_f[2][QUAL_BLOCK];
+    __shared__ qual_u64 s_c[QUAL_BLOCK];
+    __shared__ qual_hop s_h[QUAL_BLOCK];
+    if (gs_flag(&a.flags[a.level]) == 0) return;   // nothing was reached at this level, or its launch returned at once
+    const int t = threadIdx.x;
+    if ((int64_t)blockIdx.x < a.G) {
+        const int64_t g = blockIdx.x;
+        const int b = t & 63;
+        double fa = 0.0, fb = 0.0;
+        qual_u64 c = 0;
+        for (int64_t x = t >> 6; x < a.X; x += QUAL_BLOCK / 64) {
+            const int64_t slab = g * a.X + x;
+            fa += a.src_f[(2 * slab) * 64 + b];
+            fb += a.src_f[(2 * slab + 1) * 64 + b];
+            c += a.src_c[slab * 64 + b];
+        }
+        s_f[0][t] = fa;
+        s_f[1][t] = fb;
+        s_c[t] = c;
+        __syncthreads();
+        if (t >= 64) return;
+        for (int q = 1; q < QUAL_BLOCK / 64; ++q) {
+            fa += s_f[0][64 * q + t];
+            fb += s_f[1][64 * q + t];
+            c += s_c[64 * q + t];
+        }
+        if (c == 0) return;
+        const int64_t j = g * 64 + t;
+        const double L = (double)a.level;
+        a.reach[j] += c;
+        a.ecc[j] = a.level;   // levels ascend
+        a.over_h[j] += fa / L;
+        a.over_h2[j] += fb / (L * L);
+        return;
+    }
+    qual_hop v = qual_hop_empty();
+    for (int64_t slab = t; slab < a.G * a.X; slab += QUAL_BLOCK) {
+        const qual_hop one = {a.lvl_i[3 * slab], a.lvl_f[2 * slab], a.lvl_f[2 * slab + 1], (uint32_t)a.lvl_i[3 * slab + 1],
+                              (uint32_t)a.lvl_i[3 * slab + 2]};
+        qual_hop_join(v, one);
+    }
+    s_h[t] = v;
+    __syncthreads();
+    if (t != 0) return;
+    for (int k = 1; k < QUAL_BLOCK; ++k) qual_hop_join(v, s_h[k]);
+    // an earlier batch may have been here: its entry joins; an entry nobody reached yet is all zeros
+    const int64_t L = a.level;
+    const qual_hop old = {a.hop_i[3 * L], a.hop_f[2 * L], a.hop_f[2 * L + 1], (uint32_t)a.hop_i[3 * L + 1], (uint32_t)a.hop_i[3 * L + 2]};
+    if (old.pairs) qual_hop_join(v, old);
+    a.hop_f[2 * L] = v.sd;
+    a.hop_f[2 * L + 1] = v.sq;
+    a.hop_i[3 * L] = v.pairs;
+    a.hop_i[3 * L + 1] = v.mn;
+    a.hop_i[3 * L + 2] = v.mx;
+}
+
 unsigned qual_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + QUAL_BLOCK - 1) / QUAL_BLOCK); }
 
 }  // namespace
@@ -297,6 +521,8 @@ struct gh_qual : gh_host {          // device < 0: host path
     bool g_built = false;
     std::vector<int64_t> g_ptr;
     std::vector<int32_t> g_idx;
+    gh_dev<int64_t> d_gptr;         // the same on the device, uploaded by the first hop profile
+    gh_dev<int32_t> d_gidx;
 };
 
 static thread_local std::string g_qual_error;
@@ -494,6 +720,173 @@ gh_status qual_ranks_device(gh_qual *h, int64_t n_rows, const int32_t *rows, con
     for (int64_t s = 0; s < slots; ++s) {
         below[s] = cnt[s].x;
         equal[s] = cnt[s].y;
+    }
+    return GH_OK;
+}
+
+// What both paths of the hop profile fill: hops[h - 1] for h = 1 .. H, and one entry per source.
+struct qual_hop_result {
+    std::vector<qual_hop> hops;
+    std::vector<int64_t> reach;
+    std::vector<int32_t> ecc;
+    std::vector<double> over_h, over_h2;
+};
+
+// One breadth-first search per source; a thread keeps the sums of its sources per hop, and the threads join in order.
+void qual_hops_host(const gh_qual *h, int64_t S, const int32_t *src, qual_hop_result *out) {
+    const int64_t n = h->n;
+    const int D = h->D;
+    const float *pos = h->h_pos.data();
+    const int64_t *ptr = h->g_ptr.data();
+    const int32_t *idx = h->g_idx.data();
+    std::mutex mu;
+    std::map<int64_t, std::vector<qual_hop>> parts;   // by the thread's first source: thread order
+    qual_host_parallel(S, 1, [&, n, D, pos, ptr, idx, src, out](int64_t first, int64_t last) {
+        std::vector<qual_hop> mine;
+        std::vector<int32_t> dist((size_t)n), queue;
+        for (int64_t j = first; j < last; ++j) {
+            const int32_t s = src[j];
+            const float *xs = pos + (int64_t)s * D;
+            std::fill(dist.begin(), dist.end(), -1);
+            dist[s] = 0;
+            queue.assign(1, s);
+            double over_h = 0.0, over_h2 = 0.0;
+            int64_t reach = 0;
+            int32_t level = 0;
+            for (size_t head = 0; head < queue.size();) {
+                const size_t tail = queue.size();   // queue[head .. tail) is the frontier at `level`
+                ++level;
+                qual_hop acc = qual_hop_empty();
+                for (; head < tail; ++head) {
+                    const int32_t u = queue[head];
+                    for (int64_t k = ptr[u]; k < ptr[u + 1]; ++k) {
+                        const int32_t v = idx[k];
+                        if (dist[v] >= 0) continue;
+                        dist[v] = level;
+                        queue.push_back(v);
+                        double d;
+                        qual_hop_pair(acc, qual_d2(xs, pos + (int64_t)v * D, 1, D), &d);
+                    }
+                }
+                if (acc.pairs == 0) { --level; break; }
+                if (mine.size() < (size_t)level) mine.resize((size_t)level, qual_hop_empty());
+                qual_hop_join(mine[(size_t)level - 1], acc);
+                const double L = (double)level;
+                over_h += acc.sd / L;
+                over_h2 += acc.sq / (L * L);
+                reach += (int64_t)acc.pairs;
+            }
+            out->reach[j] = reach;
+            out->ecc[j] = level;
+            out->over_h[j] = over_h;
+            out->over_h2[j] = over_h2;
+        }
+        std::lock_guard<std::mutex> lock(mu);
+        parts[first] = std::move(mine);
+    });
+    for (auto &part : parts) {
+        if (out->hops.size() < part.second.size()) out->hops.resize(part.second.size(), qual_hop_empty());
+        for (size_t l = 0; l < part.second.size(); ++l) qual_hop_join(out->hops[l], part.second[l]);
+    }
+}
+
+gh_status qual_hops_device(gh_qual *h, int64_t S, const int32_t *src, qual_hop_result *out) {
+    const int64_t n = h->n, groups = (S + 63) / 64;
+    GH_HIP(hipSetDevice(h->device));
+    if (!h->d_gptr.p) {   // once per handle
+        if (!h->d_gptr.alloc(8 * (size_t)(n + 1)) || !h->d_gidx.alloc(4 * h->g_idx.size())) {
+            h->d_gptr.reset();
+            h->err = "hipMalloc failed for " + std::to_string(8 * (n + 1) + 4 * (int64_t)h->g_idx.size()) + " bytes of graph";
+            return GH_ERR_NOMEM;
+        }
+        GH_HIP(hipMemcpyAsync(h->d_gptr.p, h->g_ptr.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
+        if (!h->g_idx.empty()) GH_HIP(hipMemcpyAsync(h->d_gidx.p, h->g_idx.data(), 4 * h->g_idx.size(), hipMemcpyHostToDevice, h->stream));
+        GH_HIP(hipStreamSynchronize(h->stream));
+    }
+    // G groups in flight, X workgroups to a group
+    const int64_t G = std::max<int64_t>(1, std::min<int64_t>({QUAL_HOP_STATE_BYTES / (24 * n), groups, (int64_t)65535}));   // 65535: grid.y
+    const int64_t X = std::max<int64_t>(1, std::min<int64_t>((n + QUAL_BLOCK - 1) / QUAL_BLOCK, QUAL_HOP_MAX_BLOCKS / G));
+    std::vector<int32_t> padded(64 * (size_t)groups, 0);   // the unused slots of the last group name vertex 0: a row that exists
+    std::copy(src, src + S, padded.begin());
+    gh_dev<uint64_t> d_vis, d_fa, d_fb;
+    gh_dev<int32_t> d_flags, d_src, d_ecc;
+    gh_dev<double> d_lvl_f, d_src_f, d_hop_f, d_over;
+    gh_dev<qual_u64> d_lvl_i, d_hop_i, d_reach;
+    gh_dev<uint32_t> d_src_c;
+    const size_t state = 8 * (size_t)(G * n), slabs = (size_t)(G * X), per_src = 64 * (size_t)groups;
+    if (!d_vis.alloc(state) || !d_fa.alloc(state) || !d_fb.alloc(state) || !d_flags.alloc(4 * (size_t)(n + 2)) || !d_src.alloc(4 * per_src) ||
+        !d_lvl_f.alloc(16 * slabs) || !d_lvl_i.alloc(24 * slabs) || !d_src_f.alloc(1024 * slabs) || !d_src_c.alloc(256 * slabs) ||
+        !d_hop_f.alloc(16 * (size_t)n) || !d_hop_i.alloc(24 * (size_t)n) || !d_reach.alloc(8 * per_src) || !d_ecc.alloc(4 * per_src) ||
+        !d_over.alloc(16 * per_src)) {
+        h->err = "hipMalloc failed for " + std::to_string(G) + " source groups of search state";
+        return GH_ERR_NOMEM;
+    }
+    GH_HIP(hipMemcpyAsync(d_src.p, padded.data(), 4 * per_src, hipMemcpyHostToDevice, h->stream));
+    GH_HIP(hipMemsetAsync(d_hop_f.p, 0, 16 * (size_t)n, h->stream));
+    GH_HIP(hipMemsetAsync(d_hop_i.p, 0, 24 * (size_t)n, h->stream));
+    GH_HIP(hipMemsetAsync(d_reach.p, 0, 8 * per_src, h->stream));
+    GH_HIP(hipMemsetAsync(d_ecc.p, 0, 4 * per_src, h->stream));
+    GH_HIP(hipMemsetAsync(d_over.p, 0, 16 * per_src, h->stream));
+    const bool staged = 64 * (int64_t)h->D <= QUAL_HOP_SRC_LDS;
+    QualHopLevel lv{};
+    lv.ptr = h->d_gptr.p; lv.idx = h->d_gidx.p; lv.pos = h->d_pos.p;
+    lv.vis = d_vis.p; lv.flags = d_flags.p;
+    lv.lvl_f = d_lvl_f.p; lv.lvl_i = d_lvl_i.p; lv.src_f = d_src_f.p; lv.src_c = d_src_c.p;
+    lv.n = n; lv.D = h->D;
+    QualHopReduce rd{};
+    rd.flags = d_flags.p;
+    rd.lvl_f = d_lvl_f.p; rd.lvl_i = d_lvl_i.p; rd.src_f = d_src_f.p; rd.src_c = d_src_c.p;
+    rd.hop_f = d_hop_f.p; rd.hop_i = d_hop_i.p;
+    rd.X = X;
+    const unsigned fill_blocks = (unsigned)std::min<int64_t>(QUAL_HOP_MAX_BLOCKS, qual_grid(G * n));
+    int32_t H = 0;
+    for (int64_t g0 = 0; g0 < groups; g0 += G) {
+        const int64_t gb = std::min(G, groups - g0), ns = std::min<int64_t>(64 * gb, S - 64 * g0);
+        const int64_t in_last = ns - 64 * (gb - 1);
+        const uint64_t unused_last = in_last < 64 ? ~0ull << in_last : 0;
+        GH_HIP(hipMemsetAsync(d_flags.p, 0, 4 * (size_t)(n + 2), h->stream));
+        const int32_t one = 1;
+        GH_HIP(hipMemcpyAsync(d_flags.p, &one, 4, hipMemcpyHostToDevice, h->stream));
+        qual_hop_fill_kernel<<<dim3(fill_blocks), dim3(QUAL_BLOCK), 0, h->stream>>>(n, gb, unused_last, d_vis.p, d_fa.p);
+        GH_LAUNCH_CHECK();
+        qual_hop_seed_kernel<<<dim3(qual_grid(ns)), dim3(QUAL_BLOCK), 0, h->stream>>>(n, ns, d_src.p + 64 * g0, (qual_u64 *)d_vis.p, (qual_u64 *)d_fa.p);
+        GH_LAUNCH_CHECK();
+        lv.src = d_src.p + 64 * g0;
+        rd.G = gb;
+        rd.reach = d_reach.p + 64 * g0; rd.ecc = d_ecc.p + 64 * g0;
+        rd.over_h = d_over.p + 64 * g0; rd.over_h2 = d_over.p + per_src + 64 * g0;
+        const dim3 grid((unsigned)X, (unsigned)gb);
+        int32_t last = 0;
+        GH_TRY_ST(gh_level_loop(h, n, d_flags.p, QUAL_HOP_CHECK_EVERY, &last, [&](int32_t L) -> gh_status {
+            lv.level = rd.level = L;
+            lv.cur = (L & 1) ? d_fa.p : d_fb.p;
+            lv.nxt = (L & 1) ? d_fb.p : d_fa.p;
+            if (staged) qual_hop_level_kernel<true><<<grid, dim3(QUAL_BLOCK), 0, h->stream>>>(lv);
+            else qual_hop_level_kernel<false><<<grid, dim3(QUAL_BLOCK), 0, h->stream>>>(lv);
+            GH_LAUNCH_CHECK();
+            qual_hop_reduce_kernel<<<dim3((unsigned)gb + 1), dim3(QUAL_BLOCK), 0, h->stream>>>(rd);
+            GH_LAUNCH_CHECK();
+            return GH_OK;
+        }));
+        H = std::max(H, last);
+    }
+    std::vector<double> hop_f(2 * (size_t)H + 2), over(2 * per_src);
+    std::vector<qual_u64> hop_i(3 * (size_t)H + 3), reach(per_src);
+    if (H > 0) {   // entry L of the device arrays is hop L; entry 0 is unused
+        GH_HIP(hipMemcpyAsync(hop_f.data(), d_hop_f.p, 16 * ((size_t)H + 1), hipMemcpyDeviceToHost, h->stream));
+        GH_HIP(hipMemcpyAsync(hop_i.data(), d_hop_i.p, 24 * ((size_t)H + 1), hipMemcpyDeviceToHost, h->stream));
+    }
+    GH_HIP(hipMemcpyAsync(reach.data(), d_reach.p, 8 * per_src, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(out->ecc.data(), d_ecc.p, 4 * (size_t)S, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipMemcpyAsync(over.data(), d_over.p, 16 * per_src, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
+    out->hops.resize((size_t)H);
+    for (int64_t L = 1; L <= H; ++L)
+        out->hops[(size_t)L - 1] = {hop_i[3 * L], hop_f[2 * L], hop_f[2 * L + 1], (uint32_t)hop_i[3 * L + 1], (uint32_t)hop_i[3 * L + 2]};
+    for (int64_t j = 0; j < S; ++j) {
+        out->reach[j] = (int64_t)reach[j];
+        out->over_h[j] = over[j];
+        out->over_h2[j] = over[per_src + j];
     }
     return GH_OK;
 }
@@ -709,5 +1102,51 @@ extern "C" gh_status gh_qual_neighbor_ranks(gh_qual_handle h, int64_t n_rows, co
     }
     if (h->device < 0) qual_ranks_host(h, n_rows, rows, indptr.data(), neighbors, d2, below, equal);
     else GH_TRY_ST(qual_ranks_device(h, n_rows, rows, indptr.data(), neighbors, d2, below, equal));
+    return GH_OK;
+}
+
+extern "C" gh_status gh_qual_hop_profile(gh_qual_handle h, int64_t n_sources, const int32_t *sources, int64_t hop_cap, int64_t *n_hops,
+                                         int64_t *pairs, double *sum_d, double *sum_d2, float *min_d2, float *max_d2, int64_t *reach,
+                                         int32_t *eccentricity, double *sum_d_over_h, double *sum_d2_over_h2) {
+    if (!h) { g_qual_error = "handle is NULL"; return GH_ERR_INVALID; }
+    if (h->D < 1) return qual_invalid(h, "no positions were set");
+    if (!sources) n_sources = h->n;
+    if (n_sources < 0) return qual_invalid(h, "n_sources must be >= 0, got " + std::to_string(n_sources));
+    if (hop_cap < 0) return qual_invalid(h, "hop_cap must be >= 0, got " + std::to_string(hop_cap));
+    for (int64_t j = 0; sources && j < n_sources; ++j)
+        if (sources[j] < 0 || sources[j] >= h->n) return qual_invalid(h, "source " + std::to_string(j) + " has a vertex id outside [0, n)");
+    GH_TRY_ST(qual_build_graph(h));
+    const int64_t S = n_sources;
+    std::vector<int32_t> all;
+    if (!sources) {
+        all.resize((size_t)S);
+        for (int64_t j = 0; j < S; ++j) all[j] = (int32_t)j;
+        sources = all.data();
+    }
+    qual_hop_result r;
+    r.reach.assign((size_t)S, 0);
+    r.ecc.assign((size_t)S, 0);
+    r.over_h.assign((size_t)S, 0.0);
+    r.over_h2.assign((size_t)S, 0.0);
+    if (S > 0) {
+        if (h->device < 0) qual_hops_host(h, S, sources, &r);
+        else GH_TRY_ST(qual_hops_device(h, S, sources, &r));
+    }
+    const int64_t H = (int64_t)r.hops.size();
+    if (n_hops) *n_hops = H;
+    if ((pairs || sum_d || sum_d2 || min_d2 || max_d2) && hop_cap < H)
+        return qual_invalid(h, "hop_cap = " + std::to_string(hop_cap) + " is below the greatest hop " + std::to_string(H));
+    for (int64_t l = 0; l < H; ++l) {
+        union { uint32_t u; float f; } mn = {r.hops[l].mn}, mx = {r.hops[l].mx};
+        if (pairs) pairs[l] = (int64_t)r.hops[l].pairs;
+        if (sum_d) sum_d[l] = r.hops[l].sd;
+        if (sum_d2) sum_d2[l] = r.hops[l].sq;
+        if (min_d2) min_d2[l] = mn.f;
+        if (max_d2) max_d2[l] = mx.f;
+    }
+    if (reach) std::copy(r.reach.begin(), r.reach.end(), reach);
+    if (eccentricity) std::copy(r.ecc.begin(), r.ecc.end(), eccentricity);
+    if (sum_d_over_h) std::copy(r.over_h.begin(), r.over_h.end(), sum_d_over_h);
+    if (sum_d2_over_h2) std::copy(r.over_h2.begin(), r.over_h2.end(), sum_d2_over_h2);
     return GH_OK;
 }

@@ -16,7 +16,15 @@ neighbor_ranks returns, for every (source, neighbour), how many other vertices l
 as near -- exact integers under the float32 distance of include/graphem_hip.h "embedding quality", over ALL D coordinates
 and on the SIMPLE graph of the edge list (self-loops dropped, repeats and both directions merged) -- and link_auc,
 neighborhood_preservation and embedding_quality are a few divisions of sums of those integers.
+
+Distance preservation asks about the layout as a whole: does embedding distance follow graph distance?  hop_profile returns,
+per hop and per source, the sums of the embedding distance over every (source, vertex) pair the graph joins (include/
+graphem_hip.h "distance preservation": a breadth-first search from 64 sources to a machine word that evaluates the pair's
+distance where the source first reaches the vertex), and layout_stress, hop_distance_correlation and distance_quality --
+Kamada-Kawai stress, the Shepard curve, Pearson's r between hops and distance -- are a few operations on those sums.
 """
+import math
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -42,6 +50,18 @@ EXACT_MAX_VERTICES = 500_000
 # threads of the same machine's host, 4.2e9 and 4.6e9 pairs per second; all sources were not run there, and at that rate
 # they take a second at 66 000 vertices.
 HOST_EXACT_MAX_VERTICES = 60_000
+# distance_quality(exact=None) takes every vertex as a source up to this many vertices and samples sources above it.
+# Measured on one MI355X (2026-10-19, tools/distance_quality.py --n 100000 --iters 20 --time --host --all and --n 1000000
+# --iters 20 --time --host; random-regular d = 8, D = 3, the layout after 20 iterations, 8 and 9 hops):
+# the hop profile over all sources takes 0.159 s at 100 K vertices, 6.3e10 (source, vertex) pairs per second, and the time
+# grows with the square of n: 1.59e-11 n^2 is a second at 250 000 vertices (all sources were not run above 100 K).  1024
+# sampled sources take 2.33 ms at 100 K and 20.8 ms at a million, 4.4e10 and 4.9e10 pairs per second; the whole
+# distance_quality call on them takes 14 ms and 99 ms (graph, upload, numpy).
+EXACT_MAX_DISTANCE_VERTICES = 250_000
+# The same for the library's host path (no device): 1024 sources take 0.141 s at 100 K and 11.1 s at a million on 16
+# threads of the same machine's host, 7.3e8 and 9.2e7 pairs per second (a search's distance array leaves the caches); all
+# sources were not run there, and at the 100 K rate they take a second at 27 000 vertices.
+HOST_EXACT_MAX_DISTANCE_VERTICES = 25_000
 
 
 def _edges_from_adjacency(adjacency):
@@ -126,6 +146,27 @@ class _Snapshot:
         n = self.q.n
         if exact is None:
             exact = n <= (EXACT_MAX_VERTICES if self.q.device_id >= 0 else HOST_EXACT_MAX_VERTICES)
+        S = min(int(sample_size), n)
+        if exact or S >= n:
+            return None
+        return np.sort(np.random.default_rng(seed).choice(n, S, replace=False))
+
+    def hops(self, sources=None):
+        """hop_profile's dict for the source ids `sources` (None: all vertices)."""
+        n = self.q.n
+        p = self.q.hop_profile(sources)
+        ids = np.arange(n, dtype=np.int64) if sources is None else np.array(sources, dtype=np.int64).ravel()
+        mean_d = p["sum_d"] / p["pairs"]   # every hop up to H has a pair
+        return {"sources": ids, "hops": np.arange(1, len(p["pairs"]) + 1, dtype=np.int64), "pairs": p["pairs"],
+                "sum_d": p["sum_d"], "sum_d2": p["sum_d2"], "min_d2": p["min_d2"], "max_d2": p["max_d2"], "mean_d": mean_d,
+                "reach": p["reach"], "eccentricity": p["eccentricity"], "sum_d_over_h": p["sum_d_over_h"],
+                "sum_d2_over_h2": p["sum_d2_over_h2"], "n_unreachable": len(ids) * (n - 1) - int(p["reach"].sum())}
+
+    def distance_sample(self, exact, sample_size, seed):
+        """The source ids distance_quality uses: None (all vertices) or the sorted sample."""
+        n = self.q.n
+        if exact is None:
+            exact = n <= (EXACT_MAX_DISTANCE_VERTICES if self.q.device_id >= 0 else HOST_EXACT_MAX_DISTANCE_VERTICES)
         S = min(int(sample_size), n)
         if exact or S >= n:
             return None
@@ -288,3 +329,85 @@ def embedding_quality(x, edges=None, exact=None, sample_size=4096, seed=0, devic
                 "link_auc": _link_auc(counts, n), "neighborhood_precision": pres["precision"],
                 "neighborhood_jaccard": pres["jaccard"],
                 "mean_rank": int(b_bar.sum()) / len(b_bar) if len(b_bar) else float("nan")}
+
+
+# ---- distance preservation: the hop profile and what is computed from it ---------------------------------------------------
+def hop_profile(x, edges=None, sources=None, device_id=None):
+    """The sums of include/graphem_hip.h "distance preservation" over the source vertex ids `sources` (any order, repeats
+    allowed; None = all vertices in order) on the SIMPLE graph of the edge list: dict of sources (int64), hops =
+    arange(1, H + 1), and per hop pairs (int64: the (source, vertex) pairs at that hop), sum_d and sum_d2 (float64: the sums
+    of the embedding distance and of its square over them), min_d2 and max_d2 (float32, exact), mean_d = sum_d / pairs (the
+    Shepard curve); per source reach (int64: the vertices it reaches, itself not counted), eccentricity (int32),
+    sum_d_over_h and sum_d2_over_h2 (float64: the sums over the vertices it reaches of d / hop and d^2 / hop^2); and
+    n_unreachable = S (n - 1) - sum(reach)."""
+    with _Snapshot(x, edges, device_id) as s:
+        return s.hops(sources)
+
+
+def _stress(p, scale=None):
+    """layout_stress's dict from a hop profile: stress(s) = (s^2 B - 2 s A + N) / N."""
+    a, b, c = p["sum_d_over_h"], p["sum_d2_over_h2"], p["reach"]
+    A, B, N = math.fsum(a), math.fsum(b), int(c.sum())
+    if scale is None:
+        scale = A / B if B > 0 else 1.0
+    s = float(scale)
+    t = s * s * b - 2 * s * a + c
+    with np.errstate(invalid="ignore", divide="ignore"):
+        vertex = np.where(c > 0, t / c, np.nan)
+    return {"stress": (s * s * B - 2 * s * A + N) / N if N else float("nan"), "scale": s, "pairs": N,
+            "n_unreachable": p["n_unreachable"], "sources": p["sources"], "vertex_stress": vertex}, t
+
+
+def layout_stress(x, edges=None, sources=None, scale=None, device_id=None):
+    """Kamada-Kawai stress of the layout against hop distance with the weights 1 / hop^2, over the pairs P of hop_profile:
+    stress(s) = sum over P of (s d - hop)^2 / hop^2, divided by |P| = (s^2 B - 2 s A + N) / N with A = sum of sum_d_over_h,
+    B = sum of sum_d2_over_h2, N = sum of reach.  scale=None takes the minimiser s* = A / B (1.0 when B = 0).  dict: stress
+    (nan when N = 0), scale, pairs = N, n_unreachable, sources, and vertex_stress, the same quotient over one source's pairs
+    (nan for a source that reaches nothing): which vertices are badly placed."""
+    with _Snapshot(x, edges, device_id) as s:
+        return _stress(s.hops(sources), scale)[0]
+
+
+def _hop_correlation(p):
+    h = p["hops"].astype(np.float64)
+    n = int(p["pairs"].sum())
+    if n == 0:
+        return float("nan")
+    sh, shh = math.fsum(h * p["pairs"]), math.fsum(h * h * p["pairs"])
+    shd, sd, sdd = math.fsum(h * p["sum_d"]), math.fsum(p["sum_d"]), math.fsum(p["sum_d2"])
+    var_h, var_d = n * shh - sh * sh, n * sdd - sd * sd
+    if not (var_h > 0 and var_d > 0):
+        return float("nan")
+    return (n * shd - sh * sd) / math.sqrt(var_h * var_d)
+
+
+def hop_distance_correlation(x, edges=None, sources=None, device_id=None):
+    """Pearson's r between hop distance and embedding distance over the pairs P of hop_profile, from the per-hop table:
+    sum h = sum h pairs[h], sum h^2 = sum h^2 pairs[h], sum h d = sum h sum_d[h], sum d = sum sum_d[h], sum d^2 = sum sum_d2[h].
+    nan when either variance is 0 (no pairs, one hop only, all distances equal)."""
+    with _Snapshot(x, edges, device_id) as s:
+        return _hop_correlation(s.hops(sources))
+
+
+def distance_quality(x, edges=None, exact=None, sample_size=1024, seed=0, device_id=None):
+    """dict: n_sources, exact (every vertex was a source), pairs, n_unreachable, stress and scale (layout_stress at its
+    minimiser), stress_stderr, correlation (hop_distance_correlation), hops, mean_d (the Shepard curve) and max_hop.
+
+    exact=True takes every vertex as a source; exact=False takes S = min(sample_size, n) of them, sources =
+    sort(default_rng(seed).choice(n, S, replace=False)); exact=None takes all up to EXACT_MAX_DISTANCE_VERTICES vertices
+    (HOST_EXACT_MAX_DISTANCE_VERTICES on the host path) and samples above.  stress_stderr is 0.0 when exact or S < 2, else
+    the ratio estimator's error: with t_j = s^2 b_j - 2 s a_j + c_j and c_j = reach[j],
+    sqrt(S / (S - 1) * sum_j (t_j - stress c_j)^2) / sum_j c_j * sqrt(1 - S / n)."""
+    with _Snapshot(x, edges, device_id) as s:
+        n = s.q.n
+        sources = s.distance_sample(exact, sample_size, seed)
+        p = s.hops(sources)
+        st, t = _stress(p)
+        S = len(p["sources"])
+        stderr = 0.0
+        if sources is not None and S >= 2 and st["pairs"] > 0:
+            resid = t - st["stress"] * p["reach"]
+            stderr = math.sqrt(S / (S - 1) * math.fsum(resid * resid)) / st["pairs"] * math.sqrt(1 - S / n)
+        return {"n_sources": S, "exact": sources is None, "pairs": st["pairs"], "n_unreachable": p["n_unreachable"],
+                "stress": st["stress"], "scale": st["scale"], "stress_stderr": stderr, "correlation": _hop_correlation(p),
+                "hops": p["hops"], "mean_d": p["mean_d"], "max_hop": len(p["hops"])}

@@ -905,6 +905,46 @@ gh_status gh_qual_neighbor_sizes(gh_qual_handle h, int64_t n_rows, const int32_t
 gh_status gh_qual_neighbor_ranks(gh_qual_handle h, int64_t n_rows, const int32_t *rows, int32_t *neighbors, float *d2,
                                  int32_t *below, int32_t *equal);
 
+/* ---- distance preservation: hop profile, stress, Shepard curve (graphem-rapids_amd/quality.py: hop_profile, layout_stress,
+ * hop_distance_correlation, distance_quality) -- the same gh_qual handle -----------------------------------------------------
+ * Does the embedding preserve graph distance as a whole?  Under stress, the Shepard curve and the correlation of embedding
+ * distance with hop distance lie the same sums: per hop and per source, over every (source, vertex) pair the graph joins.
+ *
+ * Graph.  The simple undirected graph of the handle's edge list, exactly as for the neighbour ranks: self-loops dropped,
+ * repeats and both directions merged.  hop(s, v) = the breadth-first distance.
+ * Distance.  d2(s, v) is the float32 chain above over all D coordinates.  A pair contributes d = sqrt((double)d2), an IEEE
+ * double square root, and q = (double)d2.
+ * Sources.  sources[0 .. S), ids in [0, n) in any order; a repeat is a source of its own.  NULL = all n vertices in order
+ * (n_sources is ignored).
+ * Pairs.  P = {(j, v) : v != sources[j], v reachable from sources[j]}.  With all vertices as sources every unordered pair
+ * appears twice -- d2 is symmetric bit for bit.
+ * Per hop h = 1 .. H, H = the greatest hop in P (0 when P is empty), at entry h - 1 of each array:
+ *     pairs   (int64)   the number of pairs at hop h
+ *     sum_d, sum_d2     (double)  sum of d, sum of q over them
+ *     min_d2, max_d2    (float32) the exact least and greatest d2 among them
+ * Per source j:
+ *     reach[j]          (int64)   the number of pairs (j, v) in P: the source itself is not counted
+ *     eccentricity[j]   (int32)   the greatest finite hop; 0 when nothing is reached
+ *     sum_d_over_h[j]   (double)  sum over v of d / hop
+ *     sum_d2_over_h2[j] (double)  sum over v of q / hop^2
+ * Exactness.  The integers and the bits of min_d2 / max_d2 are pure functions of (edges, positions, sources): they do not
+ * depend on launch geometry, on how sources are batched into 64-bit groups, on edge order or duplicates, or on whether the
+ * device or the host path ran.  The four kinds of double sums are sums of non-negative, individually well-defined terms;
+ * only the order of summation, and where the division by h or h^2 is applied (both paths divide a source's sum over one hop),
+ * is the path's own -- as for the two length sums of gh_qual_edge_lengths.  A sum of N terms is within (N + 2) 2^-53 of the
+ * true sum, relatively.  On the device the order within a workgroup is that of its LDS adds, so two runs can differ there.
+ * Non-finite positions.  Rows with a NaN or an infinity leave the integer outputs exact; the float outputs are then
+ * unspecified.
+ *
+ * hop_cap: the length of the per-hop arrays; n always suffices.  *n_hops (may be NULL) = H.  Every output array may be NULL.
+ * GH_ERR_INVALID for a source id outside [0, n) ("source <j> has a vertex id outside [0, n)"), for a query before any
+ * positions were set, and for hop_cap < H with a per-hop array given (*n_hops is set, so the call can be repeated).
+ * S = 0 is a no-op with H = 0.  The device path keeps as many 64-source groups in flight as 1 GiB of search state allows
+ * (24 n bytes a group), at least one.  Blocking. */
+gh_status gh_qual_hop_profile(gh_qual_handle h, int64_t n_sources, const int32_t *sources, int64_t hop_cap, int64_t *n_hops,
+                              int64_t *pairs, double *sum_d, double *sum_d2, float *min_d2, float *max_d2, int64_t *reach,
+                              int32_t *eccentricity, double *sum_d_over_h, double *sum_d2_over_h2);
+
 /* ---- edge-list ingestion: text -> (vertices, edges) (reference datasets.py: SNAPDataset.load, _load_mtx_file,
  * _load_edges_file; graphem-rapids_amd/datasets.py) ------------------------------------------------------------------
  * The reference reads a file in text mode line by line, tests line.startswith(c), takes line.strip().split() and calls
