@@ -24,13 +24,16 @@ from .graphstats import (connected_components, number_connected_components, is_c
                          eccentricity, diameter, radius, average_shortest_path_length, triangles, clustering,
                          average_clustering, transitivity, graph_summary, print_graph_summary)
 from . import communities
-from .communities import (modularity, louvain_communities, louvain_partitions, community_labels, adjusted_rand_index)
+from .communities import (modularity, louvain_communities, louvain_partitions, community_labels, adjusted_rand_index,
+                          normalized_mutual_info)
 from . import cores
 from .cores import (core_number, onion_layers, degeneracy, k_core, k_shell, k_crust, k_corona, truss_number, k_truss)
 from . import quality
 from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
                       neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality,
                       hop_profile, layout_stress, hop_distance_correlation, distance_quality)
+from . import clusters
+from .clusters import (kmeans, kmeans_plusplus, nearest_center, silhouette_samples, silhouette_score, cluster_recovery)
 from . import datasets
 from .datasets import (read_edge_list, parse_edge_list, load_dataset, load_dataset_as_networkx, load_dataset_adjacency,
                        list_available_datasets, get_data_directory, SNAPDataset, NetworkRepositoryDataset,
@@ -95,12 +98,14 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "spearman_matrix", "bootstrap_spearman", "report_corr", "report_full_correlation_matrix",
            "plot_radial_vs_centrality", "display_benchmark_results",
            "communities", "modularity", "louvain_communities", "louvain_partitions", "community_labels",
-           "adjusted_rand_index",
+           "adjusted_rand_index", "normalized_mutual_info",
            "cores", "core_number", "onion_layers", "degeneracy", "k_core", "k_shell", "k_crust", "k_corona", "truss_number",
            "k_truss",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
            "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
            "hop_profile", "layout_stress", "hop_distance_correlation", "distance_quality",
+           "clusters", "kmeans", "kmeans_plusplus", "nearest_center", "silhouette_samples", "silhouette_score",
+           "cluster_recovery",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",
            "load_dataset_adjacency", "list_available_datasets", "get_data_directory", "SNAPDataset",
            "NetworkRepositoryDataset", "SemanticScholarDataset"]

@@ -184,6 +184,11 @@ SIGNATURES = {
     "gh_qual_neighbor_sizes": (_int, [vp, i64, vp, vp]),
     "gh_qual_neighbor_ranks": (_int, [vp, i64, vp, vp, vp, vp, vp]),
     "gh_qual_hop_profile": (_int, [vp, i64, vp, i64, _P(i64), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gh_qual_position_rows": (_int, [vp, i64, vp, vp]),
+    "gh_qual_kmeans_assign": (_int, [vp, i32, vp, vp, vp]),
+    "gh_qual_kmeans": (_int, [vp, i32, vp, i32, vp, vp, vp, _P(i32), _P(i32)]),
+    "gh_qual_kmeans_seed_step": (_int, [vp, i64, i32, vp]),
+    "gh_qual_cluster_distance_sums": (_int, [vp, i32, vp, i64, vp, vp]),
     "gh_ingest_create": (_int, [_P(vp), _int]),
     "gh_ingest_destroy": (None, [vp]),
     "gh_ingest_last_error": (_str, [vp]),
@@ -934,6 +939,7 @@ class LayoutQuality(Handle):
         self.device_id = int(device_id)
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
         self.n, self.E = int(n), int(edges.shape[0])
+        self.D = 0   # of the snapshot; 0: no positions yet
         self._create("gh_qual_create", self.device_id, self.n, self.E, ptr(edges))
 
     def set_positions(self, pos, D=None, ld=None):
@@ -947,11 +953,13 @@ class LayoutQuality(Handle):
         elif pos.size < self.n * int(ld):
             raise ValueError(f"a buffer of {pos.size} floats is smaller than n * ld = {self.n * int(ld)}")
         self._raise(self.lib.gh_qual_set_positions(self.handle, ptr(pos), int(D), int(ld), 0))
+        self.D = int(D)
 
     def set_positions_device(self, dev_ptr, D, ld=None):
         """Snapshot of (n, D) float32 rows at a device pointer on the handle's device, row stride ld floats (default D)."""
         self._raise(self.lib.gh_qual_set_positions(self.handle, ctypes.c_void_p(int(dev_ptr)), int(D),
                                                    int(D if ld is None else ld), 1))
+        self.D = int(D)
 
     def crossings(self, rows=None):
         """(counts int32, their int sum) for the edge ids `rows`, any order, repeats allowed; None = all edges in order."""
@@ -1012,6 +1020,66 @@ class LayoutQuality(Handle):
         self._raise(self.lib.gh_qual_hop_profile(self.handle, S, ptr(sources), cap, ctypes.byref(H), *(ptr(a) for a in hop.values()),
                                                  *(ptr(a) for a in out.values())))
         return {**{key: a[:H.value].copy() for key, a in hop.items()}, **out}
+
+    def _centres(self, centres):
+        centres = np.array(centres, dtype=np.float32, order="C")   # a copy: gh_qual_kmeans writes it
+        if centres.ndim != 2 or centres.shape[0] < 1:
+            raise ValueError(f"centres must be (k, D) with k >= 1, got {centres.shape}")
+        if self.D and centres.shape[1] != self.D:
+            raise ValueError(f"centres of dimension {centres.shape[1]} for positions of dimension {self.D}")
+        return centres
+
+    def position_rows(self, rows):
+        """float32 (len(rows), D): the snapshot's rows at the vertex ids `rows` (gh_qual_position_rows)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        out = np.zeros((len(rows), self.D), dtype=np.float32)
+        if len(rows):
+            self._raise(self.lib.gh_qual_position_rows(self.handle, len(rows), ptr(rows), ptr(out)))
+        return out
+
+    def kmeans_assign(self, centres):
+        """(labels int32, d2 float32) of every vertex under the (k, D) centres: the least nearest centre and the float32
+        squared distance to it (include/graphem_hip.h "embedding clusters", gh_qual_kmeans_assign)."""
+        centres = self._centres(centres)
+        labels, d2 = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.float32)
+        self._raise(self.lib.gh_qual_kmeans_assign(self.handle, len(centres), ptr(centres), ptr(labels), ptr(d2)))
+        return labels, d2
+
+    def kmeans(self, centres, max_iter=300):
+        """The Lloyd loop from the (k, D) start centres with exact centre updates (gh_qual_kmeans).  dict: labels (int32),
+        centers (float32 (k, D)), d2 (float32), counts (int64), n_iter (the number of updates) and converged."""
+        centres = self._centres(centres)
+        k = len(centres)
+        labels, d2 = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.float32)
+        counts = np.zeros(k, dtype=np.int64)
+        n_iter, converged = ctypes.c_int32(), ctypes.c_int32()
+        self._raise(self.lib.gh_qual_kmeans(self.handle, k, ptr(centres), int(max_iter), ptr(labels), ptr(d2), ptr(counts),
+                                            ctypes.byref(n_iter), ctypes.byref(converged)))
+        return {"labels": labels, "centers": centres, "d2": d2, "counts": counts, "n_iter": int(n_iter.value),
+                "converged": bool(converged.value)}
+
+    def kmeans_seed_step(self, vertex, first):
+        """float32 (n,): the handle's running minimum of d2(x_w, x_vertex) over the steps since the last one with `first`
+        set (gh_qual_kmeans_seed_step)."""
+        min_d2 = np.zeros(self.n, dtype=np.float32)
+        self._raise(self.lib.gh_qual_kmeans_seed_step(self.handle, int(vertex), int(bool(first)), ptr(min_d2)))
+        return min_d2
+
+    def cluster_distance_sums(self, labels, k, rows=None):
+        """float64 (len(rows), k): per row vertex and cluster the sum of the distances to the cluster's other members
+        (gh_qual_cluster_distance_sums).  labels: n ids in [0, k); rows: vertex ids, any order, repeats allowed; None = all
+        vertices in order."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if len(labels) != self.n:
+            raise ValueError(f"{len(labels)} labels for {self.n} vertices")
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            if len(rows) == 0:
+                rows = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean all vertices)
+        n_rows = self.n if rows is None else len(rows)
+        sums = np.zeros((n_rows, max(int(k), 0)), dtype=np.float64)
+        self._raise(self.lib.gh_qual_cluster_distance_sums(self.handle, int(k), ptr(labels), n_rows, ptr(rows), ptr(sums)))
+        return sums
 
 
 class EdgeListParser(BudgetHandle):

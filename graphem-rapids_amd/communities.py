@@ -11,6 +11,8 @@ Every function takes what CentralityGraph takes -- a networkx Graph, a scipy spa
 an (E, 2) edge array or a CentralityGraph.  Undirected, unweighted graphs only.  Self-loops are dropped and duplicate
 edges merged.
 """
+import math
+
 import numpy as np
 
 from .graphstats import _components_of, _unweighted, _with_graph
@@ -139,3 +141,33 @@ def adjusted_rand_index(a, b):
     P = n * (n - 1) // 2
     den = (A + B) * P - 2 * A * B
     return 1.0 if den == 0 else 2 * (S * P - A * B) / den
+
+
+def normalized_mutual_info(a, b):
+    """The normalised mutual information of two labellings of the same items (any integer or hashable labels), on the host,
+    in natural logarithms with the arithmetic mean of the entropies: NMI = MI / ((H(a) + H(b)) / 2).  The integer contingency
+    cells n_ij come from the sorted label pairs, as for adjusted_rand_index; with the row and column totals a_i and b_j,
+    MI = fsum over the cells of (n_ij / n) log((n n_ij) / (a_i b_j)) and H(a) = fsum of (a_i / n) log(n / a_i), the products
+    in integers and every sum a math.fsum.  Identical labellings give the same terms on both sides, so exactly 1.0; two
+    trivial labellings (both entropies 0; also n = 0) give 1.0; one trivial labelling gives 0.0."""
+    a, b = np.asarray(a).ravel(), np.asarray(b).ravel()
+    if len(a) != len(b):
+        raise ValueError("the two labellings must have the same length")
+    n = len(a)
+    if n == 0:
+        return 1.0
+    ia = np.unique(a, return_inverse=True)[1].astype(np.int64).reshape(n)
+    ib = np.unique(b, return_inverse=True)[1].astype(np.int64).reshape(n)
+    kb = int(ib.max()) + 1
+    pair = np.sort(ia * kb + ib)
+    first = np.flatnonzero(np.r_[True, pair[1:] != pair[:-1], True])
+    cells, key = np.diff(first), pair[first[:-1]]
+    ra, rb = np.bincount(ia), np.bincount(ib)
+
+    def entropy(t):
+        return math.fsum((t / n * np.log(n / t)).tolist())
+    ha, hb = entropy(ra), entropy(rb)
+    if ha == 0.0 and hb == 0.0:
+        return 1.0
+    mi = math.fsum((cells / n * np.log((n * cells) / (ra[key // kb] * rb[key % kb]))).tolist())
+    return mi / ((ha + hb) / 2)

@@ -46,14 +46,13 @@
 #include "csr_core.h"
 #include "host_util.h"
 #include "intersect_core.h"
+#include "qual_handle.h"   // struct gh_qual, QUAL_BLOCK, qual_d2, qual_host_parallel: shared with clusters.hip
 
-#define QUAL_BLOCK 256
 #define QUAL_TILE 1024                      // column segments staged at once: 24 KiB of LDS
 #define QUAL_LAUNCH_PAIRS (1ll << 36)       // pair tests per launch: rows are taken in batches of about a second
 #define QUAL_LAUNCH_ROWS (1ll << 22)
 #define QUAL_MIN_BLOCKS 2048                // fewer row blocks than this: the column tiles are split over gridDim.y
 #define QUAL_LEN_BLOCKS 1024
-#define QUAL_HOST_THREADS 16
 #define QUAL_RANK_PIECE 64                  // slots of one source that one wave owns: lane i keeps threshold i (at most 64)
 #define QUAL_RANK_WAVES (QUAL_BLOCK / 64)   // pieces per workgroup: they share the staged position tile
 #define QUAL_RANK_LDS 8192                  // floats of the position tile, D rows of tile_cols columns: 32 KiB
@@ -185,17 +184,7 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_length_kernel(int64_t E, cons
 }
 
 // ---- neighbour ranks -------------------------------------------------------------------------------------------------
-// The exact-difference chain of the header: (((0 + t_0 t_0) + t_1 t_1) + ...), t_d = a[d] - b[d * sb], every operation a
-// separate float32 operation (the Makefile's -ffp-contract=off keeps the product and the sum apart).  a is a packed row; b
-// has stride sb, which is 1 for a packed row and the tile's column count for a column of the staged tile.
-__host__ __device__ __forceinline__ float qual_d2(const float *a, const float *b, int64_t sb, int D) {
-    float s = 0.0f;
-    for (int d = 0; d < D; ++d) {
-        const float t = a[d] - b[d * sb];
-        s = s + t * t;
-    }
-    return s;
-}
+// The distance is qual_d2 (qual_handle.h), the exact-difference chain of the header.
 
 // What one column at distance d adds to the two counts of a threshold t: IEEE comparisons, so a NaN on either side adds
 // nothing and +inf equals +inf.
@@ -502,47 +491,13 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_reduce_kernel(QualHopRedu
     a.hop_i[3 * L + 2] = v.mx;
 }
 
-unsigned qual_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + QUAL_BLOCK - 1) / QUAL_BLOCK); }
-
 }  // namespace
-
-struct gh_qual : gh_host {          // device < 0: host path
-    int64_t n = 0, E = 0;
-    int32_t D = 0;                  // 0: no positions yet
-    size_t pos_bytes = 0;
-    gh_dev<int2> d_edges;
-    gh_dev<float> d_pos;            // the snapshot, packed (n, D)
-    gh_dev<float4> d_seg;
-    std::vector<int2> h_edges;
-    std::vector<float> h_pos;
-    std::vector<float4> h_seg;
-    // the simple graph of the edge list (self-loops dropped, repeats and both directions merged), built by the first
-    // neighbour query: neighbours of u = g_idx[g_ptr[u] .. g_ptr[u + 1]), ids ascending
-    bool g_built = false;
-    std::vector<int64_t> g_ptr;
-    std::vector<int32_t> g_idx;
-    gh_dev<int64_t> d_gptr;         // the same on the device, uploaded by the first hop profile
-    gh_dev<int32_t> d_gidx;
-};
 
 static thread_local std::string g_qual_error;
 
+void qual_set_create_error(const std::string &msg) { g_qual_error = msg; }
+
 namespace {
-
-gh_status qual_invalid(gh_qual *h, const std::string &msg) {
-    h->err = msg;
-    return GH_ERR_INVALID;
-}
-
-// fn(first, last) over [0, count) on up to QUAL_HOST_THREADS threads
-template <class Fn> void qual_host_parallel(int64_t count, int64_t grain, Fn fn) {
-    const int64_t want = std::min<int64_t>(QUAL_HOST_THREADS, std::max<unsigned>(1, std::thread::hardware_concurrency()));
-    const int64_t nt = std::max<int64_t>(1, std::min(want, count / std::max<int64_t>(1, grain)));
-    if (nt == 1) { fn(0, count); return; }
-    std::vector<std::thread> pool;
-    for (int64_t t = 0; t < nt; ++t) pool.emplace_back(fn, count * t / nt, count * (t + 1) / nt);
-    for (auto &th : pool) th.join();
-}
 
 gh_status qual_crossings_device(gh_qual *h, int64_t n_rows, const int32_t *rows, int32_t *counts) {
     GH_HIP(hipSetDevice(h->device));
@@ -949,6 +904,7 @@ extern "C" gh_status gh_qual_set_positions(gh_qual_handle h, const float *pos, i
     if (!pos && h->n > 0) return qual_invalid(h, "pos is NULL");
     if (on_device && h->device < 0) return qual_invalid(h, "a host-path handle takes host positions only");
     const int64_t n = h->n, total = n * D;
+    h->epoch += 1;   // what clusters.hip keeps about the old snapshot is void
     if (h->device < 0) {
         h->h_pos.resize((size_t)total);
         for (int64_t i = 0; i < n; ++i) std::copy(pos + i * ld, pos + i * ld + D, h->h_pos.begin() + i * D);

@@ -945,6 +945,54 @@ gh_status gh_qual_hop_profile(gh_qual_handle h, int64_t n_sources, const int32_t
                               int64_t *pairs, double *sum_d, double *sum_d2, float *min_d2, float *max_d2, int64_t *reach,
                               int32_t *eccentricity, double *sum_d_over_h, double *sum_d2_over_h2);
 
+/* ---- embedding clusters: exact k-means, k-means++ minima, silhouette sums (graphem-rapids_amd/clusters.py: kmeans,
+ * kmeans_plusplus, nearest_center, silhouette_samples, silhouette_score, cluster_recovery) -- the same gh_qual handle ------
+ * Do the clusters of the embedding equal the communities of the graph?  k-means on the position snapshot, with integer
+ * results that are a pure function of the input, and the sums the silhouette is a few divisions of.
+ *
+ * Distance.  d2(x, c) is the float32 chain of "embedding quality" over all D coordinates, between a snapshot row x and a
+ * centre row c: t_d = x[d] - c[d].
+ * Assignment.  label(v) = the least c in [0, k) that minimises d2(x_v, centre_c): with best = +inf and label = 0, c is walked
+ * upwards and taken when d2 < best, strictly.  A +inf or NaN distance is never taken: a row whose distances all overflow
+ * keeps label 0 and best = +inf.  The returned d2[v] is best.
+ * Centre update, exact.  M = the greatest |x| of the snapshot; s = 38 - ilogb(M), or 0 when M = 0;
+ *     q(x) = llrint(ldexp((double)x, s)), ties to even      (|q| <= 2^39)
+ *     S[c][d] = sum of q(x_v[d]) over the members v of c, in int64; count[c] = the number of members
+ *     centre[c][d] = (float) ldexp((double)S[c][d] / (double)count[c], -s)
+ * and a cluster without members keeps its centre.  n <= 2^24 cannot overflow S; a larger n is refused.  Integer adds commute,
+ * so labels, d2, counts and the centres' bits depend only on (positions, start centres, max_iter): not on launch geometry,
+ * the order of atomic adds, or whether the device or the host path ran; and a permuted vertex order gives the same centres.
+ * Lloyd loop.  it = 0, no prev.  (1) assign; (2) if it > 0 and the labels equal prev: converged, stop; (3) if it == max_iter:
+ * not converged, stop; (4) update the centres, prev = labels, it += 1; (5) repeat.  The returned labels and d2 always belong
+ * to the returned centres; n_iter = the number of updates; max_iter = 0 is a plain assignment.
+ * Seeding.  The handle keeps min_d2[w] = min(min_d2[w], d2(x_w, x_vertex)) over the seed steps since the last one with
+ * `first` set, which starts it at d2(x_w, x_vertex); the draw itself is the caller's.
+ * Distance sums.  sums[r][c] = the sum over w with labels[w] == c, w != rows[r], of sqrt((double)d2(rows[r], w)): non-negative
+ * double terms whose order of summation is the path's own, within (N + 2) 2^-53 of the true sum relatively, as for the hop
+ * profile's sums.
+ *
+ * 1 <= k <= min(n, 4096).  centres: host float32 (k, D), packed.  GH_ERR_INVALID for a k outside that range, for a query
+ * before any positions were set, for a snapshot row that holds a NaN or an infinity ("position row <v> is not finite"), for
+ * such a centre ("centre <c> is not finite"), for a label outside [0, k) ("label <w> is outside [0, k)") and for a row id
+ * outside [0, n) ("row <r> has a vertex id outside [0, n)").  All calls are blocking. */
+/* out: host float32 (n_rows, D): the snapshot's rows rows[0 .. n_rows), ids in any order, repeats allowed -- the start
+ * centres of a run that begins at chosen vertices, without a download of the layout. */
+gh_status gh_qual_position_rows(gh_qual_handle h, int64_t n_rows, const int32_t *rows, float *out);
+/* labels: host int32, n; d2: host float32, n. */
+gh_status gh_qual_kmeans_assign(gh_qual_handle h, int32_t k, const float *centres, int32_t *labels, float *d2);
+/* centres: the start centres in, the last centres out.  counts: host int64, k members per cluster of the returned labels;
+ * counts, n_iter and converged may be NULL.  GH_ERR_INVALID for max_iter < 0 and for n > 2^24. */
+gh_status gh_qual_kmeans(gh_qual_handle h, int32_t k, float *centres, int32_t max_iter, int32_t *labels, float *d2, int64_t *counts,
+                         int32_t *n_iter, int32_t *converged);
+/* min_d2: host float32, n: the handle's running minimum after this step.  GH_ERR_INVALID for a vertex outside [0, n) and
+ * for a step without `first` when none with it came before on these positions. */
+gh_status gh_qual_kmeans_seed_step(gh_qual_handle h, int64_t vertex, int32_t first, float *min_d2);
+/* labels: host int32, n, every one in [0, k).  rows: host int32, n_rows vertex ids in any order, repeats allowed; NULL = all
+ * n vertices in order (n_rows is ignored).  sums: host float64 (n_rows, k).  The device path takes the rows in batches, so
+ * its working memory is bounded: 4 n D bytes of sorted columns and at most 256 MiB of partial sums. */
+gh_status gh_qual_cluster_distance_sums(gh_qual_handle h, int32_t k, const int32_t *labels, int64_t n_rows, const int32_t *rows,
+                                        double *sums);
+
 /* ---- edge-list ingestion: text -> (vertices, edges) (reference datasets.py: SNAPDataset.load, _load_mtx_file,
  * _load_edges_file; graphem-rapids_amd/datasets.py) ------------------------------------------------------------------
  * The reference reads a file in text mode line by line, tests line.startswith(c), takes line.strip().split() and calls
