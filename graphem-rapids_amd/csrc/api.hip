@@ -130,6 +130,8 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     const bool scan_path = gh_knn_scan_path(h);
     GH_A(d_gmin, (size_t)gh_gmin_floats(h), true);
     GH_A(d_sub_uv, (size_t)h->thr_M1 * 2, false);
+    // (a whole-graph engine's stats_fix launch stages the rows of the next set-up's queries: forces.hip)
+    if (h->thr_M1 > 0 && h->rows == n) GH_A(d_setup_rows, 2 * S * h->LD, true);
     if (hashed) GH_A(d_own_eids, g.own_eids.size() + 1, true);
     if (h->nlong) {
         GH_A(d_long_rows, g.long_rows.size(), false);
@@ -440,20 +442,24 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
     return gh_knn_local(h, fuse_intersect);
 }
 
-static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world) {
+// next: the ids step_finish will set the next iteration up from (presetup_ids), when the caller knows them by now.
+static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world, const gh_ids *next = nullptr) {
     GH_TRY_ST(gh_knn_merge(h, gathered, world));
     if (!h->intersect_done) GH_TRY_ST(gh_launch_intersect(h));
-    GH_TRY_ST(gh_launch_integrate(h));
+    GH_TRY_ST(gh_launch_integrate(h, next));
     return GH_OK;
 }
 
 // next: the source of the next iteration's ids, or null.  The normalise launch of a single-rank step on the fused path
 // then also runs that iteration's KNN set-up (gh_launch_normalise); gh_knn_prepare falls back to its own kernel when the
-// next step turns out different.
-static gh_status step_finish(gh_engine *h, const gh_ids *next) {
+// next step turns out different.  presetup_ids: `next` where that applies, else null.
+static const gh_ids *presetup_ids(const gh_engine *h, const gh_ids *next) {
     const bool presetup = next && h->rows == h->n && h->layout != GH_LAYOUT_GATHERED && gh_knn_scan_path(h) &&
                           (h->fused_scan || gh_grid_path(h) || gh_ivf_path(h)) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
-    GH_TRY_ST(gh_launch_normalise(h, true, presetup ? next : nullptr));  // also zeroes what the intersection phase touched
+    return presetup ? next : nullptr;
+}
+static gh_status step_finish(gh_engine *h, const gh_ids *next) {
+    GH_TRY_ST(gh_launch_normalise(h, true, presetup_ids(h, next)));  // also zeroes what the intersection phase touched
     h->iter += 1;
     return GH_OK;
 }
@@ -469,9 +475,11 @@ static gh_status run_iterations(gh_engine *h, int32_t iters, bool draws_own, Src
             GH_TRY_ST(before_row(t));
             h->sample = src_of_row(t);
             GH_TRY_ST(step_begin(h, true));
-            GH_TRY_ST(step_merge(h, h->d_partial.p, 1));
+            // (named before the statistics launch, which stages the rows of that set-up: before_row(t) has made row t + 1 available)
             const gh_ids next = t + 1 < iters ? src_of_row(t + 1) : own;
-            GH_TRY_ST(step_finish(h, t + 1 < iters || draws_own ? &next : nullptr));
+            const gh_ids *next_ids = t + 1 < iters || draws_own ? &next : nullptr;
+            GH_TRY_ST(step_merge(h, h->d_partial.p, 1, presetup_ids(h, next_ids)));
+            GH_TRY_ST(step_finish(h, next_ids));
         }
         return GH_OK;
     };

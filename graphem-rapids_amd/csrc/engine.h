@@ -151,7 +151,11 @@ struct gh_engine {
         bool valid = false;       // the last normalise launch also ran the KNN set-up of iteration `iter` from `src`
         gh_ids src{};             //   (gh_knn_prepare then skips its kernel); written by gh_set_lookahead only
         uint64_t iter = 0;
+        bool rows = false;        // (not yet valid) the last stats_fix launch staged the queries' raw endpoint rows of that
+                                  //   set-up in d_setup_rows, for the normalise launch right behind it; gh_set_lookahead_rows
     } lookahead;
+    gh_dev<float> d_setup_rows;   // (2 S, LD) un-normalised rows of the next queries' endpoints, rows 2s, 2s + 1 for query s
+                                  // (setup_core.h gh_setup_gather); whole-graph engines with threshold tiles only
     bool last_step_own_ids = false;     // gh_step_begin was called without ids (device sampler / arange)
     bool tcount_reset_pending = false;  // this step's threshold kernel must reset d_tcount
     gh_dev<float> d_iscratch;     // (S * k, LD) per-pair scratch of the intersection kernel
@@ -256,9 +260,23 @@ template <class T> gh_status gh_alloc(gh_engine *h, gh_dev<T> &buf, size_t count
 // device sampler.
 inline gh_ids gh_own_ids(const gh_engine *h) { return gh_ids{h->S >= h->E ? GH_IDS_ARANGE : GH_IDS_SAMPLER, h->d_sampled.p}; }
 // The normalise launch just enqueued also set up iteration iter + 1 from *next; null: nothing is set up ahead (any more).
+// Either way the rows a stats_fix launch staged are spent: they belong to the one normalise launch behind it.
 inline void gh_set_lookahead(gh_engine *h, const gh_ids *next) {
     h->lookahead.valid = next != nullptr;
+    h->lookahead.rows = false;
     if (next) { h->lookahead.src = *next; h->lookahead.iter = h->iter + 1; }
+}
+// The stats_fix launch just enqueued also gathered, into d_setup_rows, the rows the set-up of iteration iter + 1 from
+// `next` reads.
+inline void gh_set_lookahead_rows(gh_engine *h, const gh_ids &next) {
+    h->lookahead.valid = false;
+    h->lookahead.rows = true;
+    h->lookahead.src = next;
+    h->lookahead.iter = h->iter + 1;
+}
+inline bool gh_lookahead_rows_for(const gh_engine *h, const gh_ids *next) {
+    return next && h->lookahead.rows && h->lookahead.iter == h->iter + 1 && h->lookahead.src.mode == next->mode &&
+           h->lookahead.src.ids == next->ids;
 }
 
 // RAII-free helper: records start/stop events around a launch when timing is on.
@@ -346,7 +364,9 @@ gh_status gh_launch_intersect(gh_engine *h);               // d_sampled, d_keys_
 gh_status gh_launch_inter_cleanup(gh_engine *h);
 gh_status gh_launch_spring_mid(gh_engine *h);              // -> d_Fs, d_mid
 gh_status gh_launch_mid_only(gh_engine *h);                // -> d_mid
-gh_status gh_launch_integrate(gh_engine *h);               // d_Fs, d_acc -> d_new, d_stats
+// d_Fs, d_acc -> d_new, d_stats.  next: the ids the normalise launch behind this one will set the next iteration up from
+// (null: none, or not known yet): after a fused step the stats_fix launch then also stages that set-up's rows
+gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next = nullptr);
 gh_status gh_launch_spring_only(gh_engine *h, float *d_F); // F (n, LD), own rows
 gh_status gh_launch_inter_to_dense(gh_engine *h, float *d_F);
 gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float *d_Fi);

@@ -279,7 +279,8 @@ __global__ __launch_bounds__(256) void stats_reduce_kernel(const double *__restr
 // fixed order; every workgroup also takes a slice of the touched list, stores the corrected rows
 // and leaves its column sums of (new - new0) and (new^2 - new0^2) in its own row pair of the
 // statistics buffer (rows 2.. of d_stats); normalise_kernel adds all rows up.  new0 is recomputed
-// from pos and Fs, never read back.
+// from pos and Fs, never read back.  Workgroups past the 2*LD-th, if any, gather the rows of the next
+// iteration's queries for the normalise launch that follows (setup_core.h gh_setup_gather).
 template <int LD>
 __global__ __launch_bounds__(256) void stats_fix_kernel(const double *__restrict__ blockstats, int nblocks,
                                                        const float *__restrict__ pos, const float *__restrict__ Fs,
@@ -291,11 +292,23 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const double *__restrict
                                                        int32_t *__restrict__ patch_count = nullptr /* form D of a partitioned step
                                                        (gh_overlap_layout): new0 is already travelling to the other ranks; the corrected
                                                        rows go into the rank's patch list instead of out_new */,
-                                                       float *__restrict__ patch_rows = nullptr, int patch_cap = 0) {
+                                                       float *__restrict__ patch_rows = nullptr, int patch_cap = 0,
+                                                       gh_setup_args sa = gh_setup_args{} /* with gather workgroups behind the
+                                                       2 * LD fixing ones (single-rank steps that set up ahead): the NEXT
+                                                       iteration's set-up arguments; the launch has 8 workgroups of its own and
+                                                       nothing beside it, and everything gh_setup_gather reads is final */,
+                                                       const int32_t *__restrict__ tflag = nullptr, float *__restrict__ setup_rows = nullptr) {
+    constexpr int NFIX = 2 * LD;   // = gh_fix_blocks(LD)
+    if ((int)blockIdx.x >= NFIX) {
+        // (rows == n, row_lo == 0: a row of Fs / out_new is a vertex.  out_new is read for unflagged rows only: the fixing
+        // workgroups of this launch store the flagged ones)
+        gh_setup_gather<LD>(sa, gh_gather_src{pos, Fs, out_new, acc, tflag, setup_rows}, (int)blockIdx.x - NFIX);
+        return;
+    }
     __shared__ double red[4][2 * LD];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (!skip_reduce) {  // (the select launch of a single-rank step has done this part already)
-        const int c = blockIdx.x;  // gridDim.x == 2 * LD
+        const int c = blockIdx.x;  // one of the 2 * LD fixing workgroups
         double s = 0.0;
         // four independent partial sums per thread (loads in flight), combined in a fixed order
         double s4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -317,7 +330,7 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const double *__restrict
 #pragma unroll
     for (int d = 0; d < LD; ++d) { dx[d] = 0.0; dxx[d] = 0.0; }
     const int nt = *tcount;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += gridDim.x * blockDim.x) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += NFIX * blockDim.x) {
         const int64_t x = touched[t];
         const int64_t i = x - row_lo;
         if (i < 0 || i >= rows) continue;
@@ -387,7 +400,10 @@ struct gh_norm_src {
 // LDT: the row stride as a compile-time constant for the set-up part (4, 8, 16; 0 = any stride, no tiles): one kernel for
 // all strides carried the 16-wide set-up's 127 VGPRs -- 4 workgroups per CU, so that at 1 M vertices half of the 2048
 // streaming workgroups queued behind the first 1024 (tools/stamp_probe.py: median start 8 us into the launch).
-template <int LDT>
+// STAGED: the rows of the set-up's queries come from sa.rows, staged by the stats_fix launch in front (setup_core.h); a
+// kernel of its own, so that neither form carries the other's address arithmetic (VGPRs at strides 4 / 8 / 16: 67 / 105 /
+// 127 staged, 68 / 105 / 128 gathering, 7 / 4 / 4 waves per SIMD either way).
+template <int LDT, bool STAGED>
 __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, int LD, int64_t n, float *__restrict__ pos,
                                                        double *__restrict__ acc /* null: no clean-up */,
                                                        int32_t *__restrict__ tflag,
@@ -425,7 +441,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, 
         }
     };
     if constexpr (early_fetch)
-        if (setup_block && sa.tiles > 0) gh_setup_fetch<LDS_>(sa, (int)blockIdx.x, raw_row, srows);
+        if (setup_block && sa.tiles > 0) gh_setup_fetch<LDS_, STAGED>(sa, (int)blockIdx.x, raw_row, srows);
     extern __shared__ float ms[];  // mean[LD], std[LD], then one rank's (2 + 2 nfix, LD) statistics rows as doubles,
                                    // then (world > 1) the (2, LD) totals of the ranks before it
     // a rank's statistics rows with one load per thread and round, then summed from LDS in the fixed order: a thread adding
@@ -475,8 +491,8 @@ __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, 
         if constexpr (LDT > 0) {
             if (sa.tiles > 0) {
                 auto norm = [=](float x, int d) { return (x - ms[d]) / ms[LD + d]; };
-                if constexpr (!early_fetch) gh_setup_fetch<LDS_>(sa, (int)blockIdx.x, raw_row, srows);
-                gh_setup_finish<LDS_>(sa, (int)blockIdx.x, raw_row, norm, srows, setup_lds, stamps);
+                if constexpr (!early_fetch) gh_setup_fetch<LDS_, STAGED>(sa, (int)blockIdx.x, raw_row, srows);
+                gh_setup_finish<LDS_, STAGED>(sa, (int)blockIdx.x, raw_row, norm, srows, setup_lds, stamps);
             } else {
                 gh_setup_item(sa, t, getp);
             }
@@ -815,22 +831,33 @@ gh_status gh_launch_spring_mid(gh_engine *h) {
 gh_status gh_launch_mid_only(gh_engine *h) { return launch_mid_gather(h); }
 
 // new = pos + (Fs + Fi) for the own rows -> d_new, column statistics -> d_stats.
-gh_status gh_launch_integrate(gh_engine *h) {
+gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next) {
+    h->lookahead.rows = false;
     if (h->new0_ready && h->rows > 0) {  // the fused kernel already wrote pos + Fs and its partial sums
         h->new0_ready = false;
         gh_scope t(h, "stats_fix");
         const struct reset_flag { gh_engine *e; ~reset_flag() { e->stats_reduced = false; } } reset{h};
+        // next: the normalise launch behind this one will run the next iteration's set-up (whole graph on this rank); with
+        // threshold tiles, workgroups appended to this launch gather the raw rows it needs (setup_core.h gh_setup_gather)
+        gh_setup_args sa{};
+        unsigned gather = 0;
+        if (next && h->d_setup_rows.p && h->rows == h->n && h->part.row_lo == 0 && h->layout == GH_LAYOUT_NONE) {
+            sa = gh_make_setup_args(h, *next, h->iter + 1);
+            if (sa.tiles > 0) gather = gh_gather_blocks(sa.S);
+        }
         if (!gh_dispatch_stride(h->LD, [&](auto ld) {
-                stats_fix_kernel<ld()><<<dim3(gh_fix_blocks(ld())), dim3(256), 0, h->stream>>>(
+                stats_fix_kernel<ld()><<<dim3(gh_fix_blocks(ld()) + gather), dim3(256), 0, h->stream>>>(
                     h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo,
                     h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0,
                     h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr,
-                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap);
+                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap, sa, h->d_tflag.p,
+                    h->d_setup_rows.p);
             })) {   // unreachable: only gh_launch_spring_scan sets new0_ready, and it needs one of these strides
             h->err = "stats_fix: the fused step left its sums for a row stride other than 4, 8 or 16";
             return GH_ERR_RUNTIME;
         }
         GH_LAUNCH_CHECK();
+        if (gather) gh_set_lookahead_rows(h, *next);
         return GH_OK;
     }
     h->new0_ready = false;
@@ -927,6 +954,8 @@ gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float
 // next: also run the next iteration's KNN set-up in this launch (single-rank fused steps, forms B and D), for the sample
 // source the caller expects then.
 gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next, bool gathered, const double *stats_all) {
+    // the stats_fix launch in front of this one staged the rows of exactly this set-up (single-rank steps only)
+    const bool staged = !gathered && !stats_all && gh_lookahead_rows_for(h, next);
     gh_set_lookahead(h, nullptr);  // positions change: whatever set-up was done ahead is stale
     const int R = 2 + 2 * gh_fix_blocks(h->LD);
     gh_norm_src src{h->d_new, std::max<int64_t>(h->rows, 1), 0, h->LD, h->part.row_lo, h->rows, h->d_stats, 1, 0};
@@ -958,15 +987,22 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
     if (next) {
         sa = gh_make_setup_args(h, *next, h->iter + 1);
         extra = gh_setup_blocks(sa);
+        if (staged && sa.tiles > 0) sa.rows = h->d_setup_rows.p;
     }
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
     float *packed = stats_all && h->packed_exchange ? h->d_rows_packed.p + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
     const int ldt = stats_all ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
     const auto normalise = [&](auto ld) {   // 0: any row stride, no set-up tiles
-        normalise_kernel<ld()><<<dim3(grid + extra), dim3(256), smem, h->stream>>>(
-            src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p,
-            gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,
-            h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed);
+        const auto launch = [&](auto kernel) {
+            kernel<<<dim3(grid + extra), dim3(256), smem, h->stream>>>(
+                src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p,
+                gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,
+                h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed);
+        };
+        if constexpr (ld() > 0) {
+            if (sa.rows) return launch(normalise_kernel<ld(), true>);
+        }
+        launch(normalise_kernel<ld(), false>);
     };
     if (!gh_dispatch_stride(ldt, normalise)) {
         if (sa.tiles > 0) { h->err = "KNN set-up tiles need a row stride of 4, 8 or 16"; return GH_ERR_RUNTIME; }

@@ -573,7 +573,8 @@ gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter) 
     const int tiles = (int)((h->thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
     return gh_setup_args{h->d_edges.p, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q.p, h->d_cnt.p,
                          h->d_ovf.p, h->part.edge_lo, h->d_own_eids.p, reinterpret_cast<const int2 *>(h->d_sub_uv.p), h->thr_M1, h->thr_stride, h->d_gmin.p,
-                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag.p : nullptr};
+                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag.p : nullptr,
+                         nullptr /* rows: only a normalise launch behind a gathering stats_fix launch reads staged rows (forces.hip) */};
 }
 
 // Workgroups of 256 threads a set-up takes (knn_setup_kernel, or the head of a normalise launch).

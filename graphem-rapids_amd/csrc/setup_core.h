@@ -41,6 +41,7 @@ struct gh_setup_args {
     int64_t Gpad;            // row stride of gmin = 16 * tiles
     int tiles;               // ceil(M1 / 256): workgroups of gh_setup_block
     unsigned *tau_flag;      // thresholds inside the fused launch (tau_core.h): the published-queries counter, zeroed here
+    const float *rows;       // (2 S, LD) raw endpoint rows of the queries, staged by gh_setup_gather beside stats_fix, or null
 };
 
 #define GH_THR_TILE 128    /* subset edges per set-up workgroup */
@@ -97,7 +98,21 @@ struct gh_setup_rows {
     float qa[LD], qb[LD], ma[LD], mb[LD];   // endpoint rows of the lane's query / of its subset edge
     int32_t e32;
 };
-template <int LD, class RAW /* void(int64_t vertex, float (&row)[LD]) */>
+//
+// STAGED QUERY ROWS (a.rows): every set-up workgroup needs the same S queries, so inside a normalise launch each of its
+// M1 / 128 workgroups used to repeat the same 3 S requests (id -> edge -> two rows): two thirds of the launch's random
+// requests, beside a 32 MB stream.  The stats_fix launch in front of it (8 workgroups on an otherwise idle device) has
+// everything those gathers need but the statistics, which they do not need: gh_setup_gather, in workgroups appended to that
+// launch, gathers the raw endpoint rows ONCE into a.rows -- rows 2s, 2s + 1 of query s -- and the queries' fetch becomes
+// one level of coalesced row loads.  The values are the ones RAW would return, bit for bit.  (The TILES' rows staged the
+// same way, 2 M1 more rows, were measured and left out: 250 K random requests and three dependent levels in the stats_fix
+// launch cost it 2.5 us and saved the normalise launch 1.35: NOTES.md "Set-up rows gathered beside stats_fix".)
+__device__ __forceinline__ int32_t gh_setup_id(const gh_setup_args &a, int64_t s) {
+    if (a.mode == 1) return gh_sample_id(a.E, a.seed, a.iter, s);
+    if (a.mode == 2) return (int32_t)s;
+    return a.sampled[s];
+}
+template <int LD, bool STAGED /* the queries' rows from a.rows instead of through RAW */, class RAW /* void(int64_t vertex, float (&row)[LD]) */>
 __device__ __forceinline__ void gh_setup_fetch(const gh_setup_args &a, int blk, RAW raw, gh_setup_rows<LD> &st) {
     const int t = threadIdx.x;
     __builtin_amdgcn_s_setprio(3);  // inside a normalise launch these waves sit among streaming ones: their chains go first
@@ -108,12 +123,16 @@ __device__ __forceinline__ void gh_setup_fetch(const gh_setup_args &a, int blk, 
     // this lane's first query (every workgroup needs all of them; issued before the tile so that both chains of
     // dependent loads -- id -> edge -> rows here, endpoints -> rows below -- are in flight together)
     if (t < a.S) {
-        if (a.mode == 1) st.e32 = gh_sample_id(a.E, a.seed, a.iter, t);
-        else if (a.mode == 2) st.e32 = (int32_t)t;
-        else st.e32 = a.sampled[t];
-        const int2 uv = reinterpret_cast<const int2 *>(a.edges)[st.e32];
-        raw(uv.x, st.qa);
-        raw(uv.y, st.qb);
+        if constexpr (STAGED) {   // the id only where it is stored (workgroup 0, gh_setup_finish)
+            if (blk == 0) st.e32 = gh_setup_id(a, t);
+            gh_load_row<LD>(a.rows, 2 * (int64_t)t, st.qa);
+            gh_load_row<LD>(a.rows, 2 * (int64_t)t + 1, st.qb);
+        } else {
+            st.e32 = gh_setup_id(a, t);
+            const int2 uv = reinterpret_cast<const int2 *>(a.edges)[st.e32];
+            raw(uv.x, st.qa);
+            raw(uv.y, st.qb);
+        }
     }
     if (t < GH_THR_TILE) {
         const int64_t j = (int64_t)blk * GH_THR_TILE + t;
@@ -125,7 +144,40 @@ __device__ __forceinline__ void gh_setup_fetch(const gh_setup_args &a, int blk, 
     }
 }
 
-template <int LD, class RAW, class NORM /* float(float raw value, int d) */>
+// What stats_fix_kernel's gather workgroups read beside the set-up arguments (forces.hip): the un-normalised new position
+// of vertex x is new0[x] when the intersection phase left x alone, and pos + (Fs + Fi) -- stats_fix_kernel's expression,
+// recomputed here because its fixing workgroups are storing that row in this very launch -- when tflag[x] is set.
+struct gh_gather_src {
+    const float *pos, *Fs, *new0;
+    const double *acc;
+    const int32_t *tflag;
+    float *rows;    // -> gh_setup_args::rows of the normalise launch that follows
+};
+// Workgroup `blk` of gh_gather_blocks(S): a lane owns one row of the buffer (id -> vertex -> flag -> row, 16-byte loads and
+// coalesced 16-byte stores).
+inline unsigned gh_gather_blocks(int64_t S) { return (unsigned)((2 * S + 255) / 256); }
+template <int LD>
+__device__ __forceinline__ void gh_setup_gather(const gh_setup_args &a, const gh_gather_src &g, int blk) {
+    const int64_t r = (int64_t)blk * 256 + threadIdx.x;
+    if (r >= 2 * a.S) return;
+    const int64_t x = a.edges[2 * (int64_t)gh_setup_id(a, r >> 1) + (r & 1)];
+    float row[LD];
+    if (g.tflag[x] == 0) {
+        gh_load_row<LD>(g.new0, x, row);
+    } else {
+        float p[LD], f[LD];
+        gh_load_row<LD>(g.pos, x, p);
+        gh_load_row<LD>(g.Fs, x, f);
+#pragma unroll
+        for (int d = 0; d < LD; ++d) {
+            const float tot = f[d] + (float)g.acc[x * LD + d];
+            row[d] = p[d] + tot;
+        }
+    }
+    gh_store_row<LD>(g.rows, r, row);
+}
+
+template <int LD, bool STAGED, class RAW, class NORM /* float(float raw value, int d) */>
 __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk, RAW raw, NORM norm, const gh_setup_rows<LD> &st,
                                                 unsigned char *lds, unsigned long long *stamps = nullptr /* diagnostic */) {
     // the tile in LDS as PAIRS of subset edges, component-interleaved: pair p, coordinate d -> (m_2p[d], m_2p+1[d]),
@@ -133,13 +185,17 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
     gh_f2 *rsh = reinterpret_cast<gh_f2 *>(lds);     // [GH_THR_TILE / 2][LD]
     const int t = threadIdx.x;
     auto query = [&](int64_t s, int32_t &e32, float (&q)[LD]) {   // (queries past the first 256)
-        if (a.mode == 1) e32 = gh_sample_id(a.E, a.seed, a.iter, s);
-        else if (a.mode == 2) e32 = (int32_t)s;
-        else e32 = a.sampled[s];
-        const int2 uv = reinterpret_cast<const int2 *>(a.edges)[e32];
         float ra[LD], rb[LD];
-        raw(uv.x, ra);
-        raw(uv.y, rb);
+        if constexpr (STAGED) {
+            if (blk == 0) e32 = gh_setup_id(a, s);
+            gh_load_row<LD>(a.rows, 2 * s, ra);
+            gh_load_row<LD>(a.rows, 2 * s + 1, rb);
+        } else {
+            e32 = gh_setup_id(a, s);
+            const int2 uv = reinterpret_cast<const int2 *>(a.edges)[e32];
+            raw(uv.x, ra);
+            raw(uv.y, rb);
+        }
 #pragma unroll
         for (int d = 0; d < LD; ++d) q[d] = d < a.D ? (norm(ra[d], d) + norm(rb[d], d)) / 2.0f : 0.0f;
     };
@@ -226,8 +282,8 @@ __device__ __forceinline__ void gh_setup_block(const gh_setup_args &a, int blk, 
     };
     auto norm = [](float x, int) { return x; };
     gh_setup_rows<LD> st;
-    gh_setup_fetch<LD>(a, blk, raw, st);
-    gh_setup_finish<LD>(a, blk, raw, norm, st, lds, stamps);
+    gh_setup_fetch<LD, false>(a, blk, raw, st);
+    gh_setup_finish<LD, false>(a, blk, raw, norm, st, lds, stamps);
 }
 
 // Runtime row stride -> the instantiation (the scan path has LD in {4, 8, 16}).
