@@ -28,6 +28,10 @@ from .communities import (modularity, louvain_communities, louvain_partitions, c
                           normalized_mutual_info)
 from . import cores
 from .cores import (core_number, onion_layers, degeneracy, k_core, k_shell, k_crust, k_corona, truss_number, k_truss)
+from . import links
+from .links import (link_scores, jaccard_coefficient, adamic_adar_index, resource_allocation_index, preferential_attachment,
+                    link_candidates, top_links, split_edges, embedding_link_scores, ranking_auc, average_precision,
+                    link_prediction_benchmark)
 from . import quality
 from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossings, edge_length_stats, layout_quality,
                       neighbor_ranks, link_auc, neighborhood_preservation, embedding_quality,
@@ -101,6 +105,9 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "adjusted_rand_index", "normalized_mutual_info",
            "cores", "core_number", "onion_layers", "degeneracy", "k_core", "k_shell", "k_crust", "k_corona", "truss_number",
            "k_truss",
+           "links", "link_scores", "jaccard_coefficient", "adamic_adar_index", "resource_allocation_index",
+           "preferential_attachment", "link_candidates", "top_links", "split_edges", "embedding_link_scores", "ranking_auc",
+           "average_precision", "link_prediction_benchmark",
            "quality", "edge_crossing_counts", "edge_crossings", "estimate_edge_crossings", "edge_length_stats",
            "layout_quality", "neighbor_ranks", "link_auc", "neighborhood_preservation", "embedding_quality",
            "hop_profile", "layout_stress", "hop_distance_correlation", "distance_quality",

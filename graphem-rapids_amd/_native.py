@@ -35,6 +35,9 @@ EDGES_RANGE, EDGES_HASHED = 0, 1  # gh_partition.edge_rule (include/graphem_hip.
 
 
 SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphem_hip.h)
+LINK_KINDS = {"common_neighbors": 0, "jaccard": 1, "adamic_adar": 2, "resource_allocation": 3,
+              "preferential_attachment": 4}  # GH_LINK_* (include/graphem_hip.h)
+LINK_MAX_K = 128
 
 
 # Every symbol include/graphem_hip.h declares: name -> (restype, argtypes).  load() applies the table, so a symbol cannot be
@@ -158,6 +161,9 @@ SIGNATURES = {
     "gh_cent_truss": (_int, [vp, vp, _P(i32)]),
     "gh_cent_modularity": (_int, [vp, vp, vp]),
     "gh_cent_louvain": (_int, [vp, u64, i32, i32, vp, _P(i32), vp, vp, vp]),
+    "gh_link_weight": (i64, [i32, i64]),
+    "gh_cent_link_scores": (_int, [vp, i64, vp, vp, vp, vp]),
+    "gh_cent_link_candidates": (_int, [vp, i32, i32, i64, vp, vp, vp, vp]),
     "gh_gen_create": (_int, [_P(vp), _int]),
     "gh_gen_destroy": (None, [vp]),
     "gh_gen_last_error": (_str, [vp]),
@@ -739,6 +745,35 @@ class CentGraph(BudgetHandle):
         self._raise(self.lib.gh_cent_truss(self.handle, ptr(truss), ctypes.byref(rounds)))
         return truss, int(rounds.value)
 
+    def link_scores(self, pairs, cn=True, aa=True, ra=True):
+        """(cn, aa, ra), (P,) int64 each, of the vertex pairs `pairs` ((P, 2) ids; gh_cent_link_scores): common
+        neighbours and the fixed-point Adamic-Adar and resource-allocation sums (scale 2^32); a part not asked for is None."""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= self.n):
+            raise ValueError(f"vertex ids must lie in [0, {self.n})")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        out = [np.zeros(len(pairs), dtype=np.int64) if want else None for want in (cn, aa, ra)]
+        self._raise(self.lib.gh_cent_link_scores(self.handle, len(pairs), ptr(pairs), ptr(out[0]), ptr(out[1]), ptr(out[2])))
+        return tuple(out)
+
+    def link_candidates(self, kind, k, rows):
+        """(ids (R, k) int32, num (R, k) int64, den (R, k) int64): the k best two-hop candidates of every source in `rows`
+        under score kind `kind` (a LINK_KINDS name or code), best first; unused slots hold -1, 0, 1
+        (gh_cent_link_candidates)."""
+        kind = LINK_KINDS[kind] if isinstance(kind, str) else int(kind)
+        k = int(k)
+        if not 1 <= k <= LINK_MAX_K:
+            raise ValueError(f"k must lie in [1, {LINK_MAX_K}]")
+        rows = np.asarray(rows, dtype=np.int64).ravel()
+        if len(rows) and (rows.min() < 0 or rows.max() >= self.n):
+            raise ValueError(f"vertex ids must lie in [0, {self.n})")
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        ids = np.full((len(rows), k), -1, dtype=np.int32)
+        num = np.zeros((len(rows), k), dtype=np.int64)
+        den = np.ones((len(rows), k), dtype=np.int64)
+        self._raise(self.lib.gh_cent_link_candidates(self.handle, kind, k, len(rows), ptr(rows), ptr(ids), ptr(num), ptr(den)))
+        return ids, num, den
+
     def modularity(self, labels):
         """(sum I, sum T^2, M) of a labelling with values in [0, n), as Python ints (gh_cent_modularity)."""
         labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
@@ -778,6 +813,16 @@ class CentGraph(BudgetHandle):
         if st != GH_OK:
             msg = self.lib.gh_cent_last_error(None)
             raise RuntimeError(msg.decode() if msg else f"gh_status {st}")
+
+
+def link_weight(kind, degree):
+    """The fixed-point weight (scale 2^32) a common neighbour of that degree adds to the sum of score `kind` (a LINK_KINDS
+    name or code; gh_link_weight, no device)."""
+    kind = LINK_KINDS[kind] if isinstance(kind, str) else int(kind)
+    w = int(load().gh_link_weight(kind, int(degree)))
+    if w < 0:
+        raise ValueError(f"no link weight for kind {kind} and degree {degree}")
+    return w
 
 
 def knn_points(query, reference, k, device_id=0):

@@ -222,6 +222,28 @@ class CentralityGraph:
             return np.zeros(0, dtype=np.int32)
         return self._g.truss()[0]
 
+    def link_scores(self, pairs):
+        """(cn, aa, ra), (P,) int64 each, of the vertex-id pairs `pairs` ((P, 2)): common neighbours and the fixed-point
+        Adamic-Adar and resource-allocation sums of include/graphem_hip.h "link scores" (gh_cent_link_scores)."""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        if self._g is None:
+            if len(pairs):
+                raise ValueError("vertex ids must lie in [0, 0)")
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+        return self._g.link_scores(pairs)
+
+    def link_candidates(self, kind, k, rows=None):
+        """(ids (R, k) int32, num (R, k) int64, den (R, k) int64): the k best vertices at hop distance two of every source
+        in `rows` (vertex ids; None: every vertex) under score kind `kind`, best first; unused slots hold -1, 0, 1
+        (gh_cent_link_candidates)."""
+        rows = np.arange(self.n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).ravel()
+        if self._g is None:
+            if len(rows):
+                raise ValueError("vertex ids must lie in [0, 0)")
+            k = int(k)
+            return np.zeros((0, k), np.int32), np.zeros((0, k), np.int64), np.zeros((0, k), np.int64)
+        return self._g.link_candidates(kind, k, rows)
+
     def louvain_levels(self, seed=0, max_levels=32, max_rounds=1000):
         """The Louvain levels of include/graphem_hip.h "communities" (gh_cent_louvain): (labels (L, n) int32, numerators
         [L] of Python ints, n_communities (L,) int64, rounds (L,) int32, M).  labels[l][v] = the smallest vertex id in v's

@@ -1,5 +1,6 @@
 // The centrality handle (include/graphem_hip.h "centrality"), shared by centrality.hip, which owns its life cycle, and
-// graphstats.hip and communities.hip, which read the CSR, the stream and the budget and report through err.
+// graphstats.hip, communities.hip, cores.hip and links.hip, which read the CSR, the stream and the budget and report
+// through err.
 #pragma once
 #include "host_util.h"
 
@@ -14,7 +15,7 @@ struct cent_level_graph {
 };
 
 struct gh_cent : gh_host {
-    int64_t n = 0, edges = 0;
+    int64_t n = 0, edges = 0, max_degree = 0;
     gh_dev<int64_t> d_ptr;
     gh_dev<int32_t> d_adj;
     gh_dev<double> d_inv_deg;
@@ -26,6 +27,8 @@ struct gh_cent : gh_host {
     gh_dev<int2> d_range;
     // the current and the next level graph of a gh_cent_louvain call; released when the call returns
     cent_level_graph lv[2];
+    // links.hip: W_aa over 0 .. max_degree, built by the first link call and kept
+    gh_dev<int64_t> d_link_aa;
 };
 
 // (centrality.hip) the message gh_cent_last_error(NULL) returns on this thread

@@ -398,14 +398,17 @@ extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t 
         for (int64_t i = 0; i < n; ++i) std::sort(adj.begin() + ptr[i], adj.begin() + ptr[i + 1]);
     }
     std::vector<double> inv_deg((size_t)n);
+    int64_t max_degree = 0;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t d = ptr[i + 1] - ptr[i];
         inv_deg[i] = d ? 1.0 / (double)d : 0.0;
+        max_degree = std::max(max_degree, d);
     }
     gh_cent *h = new gh_cent();
     h->budget = CENT_DEFAULT_BUDGET;
     h->n = n;
     h->edges = (int64_t)key.size();
+    h->max_degree = max_degree;
     auto bail = [&](gh_status st, const std::string &msg) { gh_cent_destroy(h); return fail(st, msg); };
     const gh_status st = gh_host_open(h, device_id, &g_cent_error);
     if (st != GH_OK) { gh_cent_destroy(h); return st; }

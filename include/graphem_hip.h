@@ -1057,6 +1057,52 @@ gh_status gh_ingest_chunking(gh_ingest_handle h, int64_t *chunk_bytes, int64_t *
 gh_status gh_ingest_copy_vertices(gh_ingest_handle h, int64_t *vertices);
 gh_status gh_ingest_copy_edges(gh_ingest_handle h, int32_t relabel, int64_t *edges);
 
+/* ---- link scores (graphem-rapids_amd/links.py) --------------------------------------------------------------------------
+ * The classical neighbourhood predictors of link prediction over a gh_cent handle's graph: undirected, unweighted,
+ * self-loops dropped, duplicate edges merged.  N(v) is row v of the handle's CSR and deg(v) its length.  Every device
+ * quantity is an integer, so every result is a pure function of the edge set and the arguments: not of the memory
+ * budget, edge order, duplicate edges, scheduling, nor of earlier calls on the handle.  Both calls are blocking and
+ * report through gh_cent_last_error(h); a NULL handle gives GH_ERR_INVALID.
+ *
+ * Fixed-point weights, scale 2^32:
+ *     W_ra(d) = (2^33 + d) / (2 d) in integer division: 2^32 / d rounded half up;  W_ra(0) = 0
+ *     W_aa(d) = nearbyint(2^32 / log(d)) for d >= 2, else 0: computed on the host in double, once per handle, as a table
+ *               over 0 .. the largest degree, and uploaded -- the device never evaluates a logarithm.
+ * For a pair (u, v), over the common neighbours w in N(u) & N(v):
+ *     cn = |N(u) & N(v)|     aa = sum W_aa(deg w)     ra = sum W_ra(deg w)     uni = deg u + deg v - cn     pa = deg u * deg v
+ * all int64.  u = v is allowed and gives cn = deg u.  A graph whose largest degree is >= 2^30 gives GH_ERR_INVALID (the
+ * sums would leave int64).
+ *
+ * A score kind ranks by the rational key num / den:
+ *     GH_LINK_CN cn / 1     GH_LINK_JACCARD cn / uni     GH_LINK_AA aa / 1     GH_LINK_RA ra / 1     GH_LINK_PA pa / 1
+ * Two keys are compared by cross-multiplication in integers (both products fit in 64 bits); the larger key ranks first,
+ * equal keys rank the smaller vertex id first: a strict total order, so a top-k is unique.
+ * The candidates of a source u are C(u) = {v : v != u, v not in N(u), N(u) & N(v) not empty}: the vertices at hop distance
+ * exactly two. */
+enum { GH_LINK_CN = 0, GH_LINK_JACCARD = 1, GH_LINK_AA = 2, GH_LINK_RA = 3, GH_LINK_PA = 4 };
+
+/* The weight a common neighbour of that degree adds to the sum of `kind`: W_aa for GH_LINK_AA, W_ra for GH_LINK_RA, 1 for
+ * the three kinds that count; -1 for another kind or a degree outside [0, 2^30).  Host only, no device. */
+int64_t gh_link_weight(int32_t kind, int64_t degree);
+/* pairs: host int32 (n_pairs, 2), ids in [0, n) (GH_ERR_INVALID otherwise: "pair <i> has a vertex id outside [0, n)"), in
+ * any order, repeats allowed; n_pairs = 0 is a no-op.  cn, aa, ra: host int64[n_pairs], each may be NULL.  A group of
+ * lanes takes one pair: its lanes stride over the shorter row, each bisects the longer one, and the group adds up its
+ * three integer sums with shuffles.  The group is 4 .. 64 lanes wide, the power of two at or above the mean degree.
+ * Device state: 32 bytes per pair, as many pairs at once as gh_cent_set_memory_budget allows, at least one. */
+gh_status gh_cent_link_scores(gh_cent_handle h, int64_t n_pairs, const int32_t *pairs, int64_t *cn, int64_t *aa,
+                              int64_t *ra);
+/* For each of rows[0 .. n_rows) (ids in [0, n), any order, repeats allowed; GH_ERR_INVALID otherwise: "row <r> has a
+ * vertex id outside [0, n)") the k best members of C(rows[r]) under the order of `kind`, best first: ids int32, num and
+ * den int64, (n_rows, k) each, host.  Unused slots hold id -1, num 0, den 1.  1 <= k <= 128 (GH_ERR_INVALID otherwise,
+ * and for another kind).  Persistent workgroups take the rows off a counter; each owns a slab of n int64 sums, zero
+ * between two rows, and a candidate buffer, 20 n bytes together, as many workgroups as gh_cent_set_memory_budget allows,
+ * at least one and at most 1024.  Per row: (a) every wedge u-w-v adds the weight of deg w to slab[v] with integer
+ * atomics; (b) the wedges are walked again and slab[v] is exchanged for 0 -- the one lane that gets a non-zero value
+ * owns v, drops it when v = u or v is in row u, and appends it to the buffer otherwise; (c) k passes over the buffer take
+ * the best entry below the one before.  The outputs of up to 2^22 / k rows at once (20 k bytes a row) come on top. */
+gh_status gh_cent_link_candidates(gh_cent_handle h, int32_t kind, int32_t k, int64_t n_rows, const int32_t *rows,
+                                  int32_t *ids, int64_t *num, int64_t *den);
+
 /* Device / build facts for the host mirror's get_backend_info(). */
 int32_t gh_device_count(void);
 const char *gh_version(void);
