@@ -38,6 +38,9 @@ from .quality import (edge_crossing_counts, edge_crossings, estimate_edge_crossi
                       hop_profile, layout_stress, hop_distance_correlation, distance_quality)
 from . import clusters
 from .clusters import (kmeans, kmeans_plusplus, nearest_center, silhouette_samples, silhouette_score, cluster_recovery)
+from . import classify
+from .classify import (knn_neighbors, knn_classify, label_propagation, split_labels, accuracy, confusion_matrix, macro_f1,
+                       node_classification_benchmark, CLASSIFY_METHODS)
 from . import datasets
 from .datasets import (read_edge_list, parse_edge_list, load_dataset, load_dataset_as_networkx, load_dataset_adjacency,
                        list_available_datasets, get_data_directory, SNAPDataset, NetworkRepositoryDataset,
@@ -113,6 +116,8 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "hop_profile", "layout_stress", "hop_distance_correlation", "distance_quality",
            "clusters", "kmeans", "kmeans_plusplus", "nearest_center", "silhouette_samples", "silhouette_score",
            "cluster_recovery",
+           "classify", "knn_neighbors", "knn_classify", "label_propagation", "split_labels", "accuracy", "confusion_matrix",
+           "macro_f1", "node_classification_benchmark", "CLASSIFY_METHODS",
            "datasets", "read_edge_list", "parse_edge_list", "load_dataset", "load_dataset_as_networkx",
            "load_dataset_adjacency", "list_available_datasets", "get_data_directory", "SNAPDataset",
            "NetworkRepositoryDataset", "SemanticScholarDataset"]

@@ -38,6 +38,8 @@ SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphe
 LINK_KINDS = {"common_neighbors": 0, "jaccard": 1, "adamic_adar": 2, "resource_allocation": 3,
               "preferential_attachment": 4}  # GH_LINK_* (include/graphem_hip.h)
 LINK_MAX_K = 128
+KNN_MAX_K = 128             # gh_qual_knn_vote's bound on k
+LABEL_MAX_CLASSES = 1024    # gh_cent_label_propagation's bound on n_classes
 
 
 # Every symbol include/graphem_hip.h declares: name -> (restype, argtypes).  load() applies the table, so a symbol cannot be
@@ -164,6 +166,7 @@ SIGNATURES = {
     "gh_link_weight": (i64, [i32, i64]),
     "gh_cent_link_scores": (_int, [vp, i64, vp, vp, vp, vp]),
     "gh_cent_link_candidates": (_int, [vp, i32, i32, i64, vp, vp, vp, vp]),
+    "gh_cent_label_propagation": (_int, [vp, i32, vp, i32, vp, _P(i32), _P(i32)]),
     "gh_gen_create": (_int, [_P(vp), _int]),
     "gh_gen_destroy": (None, [vp]),
     "gh_gen_last_error": (_str, [vp]),
@@ -195,6 +198,7 @@ SIGNATURES = {
     "gh_qual_kmeans": (_int, [vp, i32, vp, i32, vp, vp, vp, _P(i32), _P(i32)]),
     "gh_qual_kmeans_seed_step": (_int, [vp, i64, i32, vp]),
     "gh_qual_cluster_distance_sums": (_int, [vp, i32, vp, i64, vp, vp]),
+    "gh_qual_knn_vote": (_int, [vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp]),
     "gh_ingest_create": (_int, [_P(vp), _int]),
     "gh_ingest_destroy": (None, [vp]),
     "gh_ingest_last_error": (_str, [vp]),
@@ -774,6 +778,19 @@ class CentGraph(BudgetHandle):
         self._raise(self.lib.gh_cent_link_candidates(self.handle, kind, k, len(rows), ptr(rows), ptr(ids), ptr(num), ptr(den)))
         return ids, num, den
 
+    def label_propagation(self, seed_labels, n_classes, max_rounds=100):
+        """(labels (n,) int32, rounds, converged): synchronous label propagation from the seeds (gh_cent_label_propagation).
+        seed_labels: n entries, -1 = unlabelled, else a class in [0, n_classes); seeds never change."""
+        seed_labels = np.asarray(seed_labels).ravel()
+        if len(seed_labels) != self.n:
+            raise ValueError(f"{len(seed_labels)} seed labels for {self.n} vertices")
+        seed_labels = np.ascontiguousarray(np.clip(seed_labels, -2, LABEL_MAX_CLASSES), dtype=np.int32)   # out of range stays so
+        labels = np.zeros(self.n, dtype=np.int32)
+        rounds, converged = ctypes.c_int32(), ctypes.c_int32()
+        self._raise(self.lib.gh_cent_label_propagation(self.handle, int(n_classes), ptr(seed_labels), int(max_rounds), ptr(labels),
+                                                       ctypes.byref(rounds), ctypes.byref(converged)))
+        return labels, int(rounds.value), bool(converged.value)
+
     def modularity(self, labels):
         """(sum I, sum T^2, M) of a labelling with values in [0, n), as Python ints (gh_cent_modularity)."""
         labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
@@ -1125,6 +1142,34 @@ class LayoutQuality(Handle):
         sums = np.zeros((n_rows, max(int(k), 0)), dtype=np.float64)
         self._raise(self.lib.gh_qual_cluster_distance_sums(self.handle, int(k), ptr(labels), n_rows, ptr(rows), ptr(sums)))
         return sums
+
+    def knn_vote(self, k, train, train_labels=None, rows=None, neighbors=True, d2=True, pred=True, votes=True):
+        """(neighbors (R, k) int32, d2 (R, k) float32, pred (R,) int32, votes (R,) int32): the k nearest training vertices
+        of every query row under (d2, vertex id), unused slots -1 and +inf, and the vote of their classes
+        (include/graphem_hip.h "node classification", gh_qual_knn_vote).  train: distinct vertex ids; train_labels: their
+        classes, >= 0, or None (then pred and votes are None); rows: vertex ids, any order, repeats allowed; None = all
+        vertices in order.  A part not asked for is None."""
+        k = int(k)
+        train = np.ascontiguousarray(train, dtype=np.int32).ravel()
+        if train_labels is not None:
+            train_labels = np.ascontiguousarray(train_labels, dtype=np.int32).ravel()
+            if len(train_labels) != len(train):
+                raise ValueError(f"{len(train_labels)} labels for {len(train)} training vertices")
+            if len(train) == 0:
+                train_labels = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean no labels)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            if len(rows) == 0:
+                rows = np.zeros(1, dtype=np.int32)[:0]   # (a NULL pointer would mean all vertices)
+        n_rows = self.n if rows is None else len(rows)
+        slots = (n_rows, max(k, 0))
+        out_i = np.zeros(slots, dtype=np.int32) if neighbors else None
+        out_d = np.zeros(slots, dtype=np.float32) if d2 else None
+        out_p = np.zeros(n_rows, dtype=np.int32) if pred and train_labels is not None else None
+        out_v = np.zeros(n_rows, dtype=np.int32) if votes and train_labels is not None else None
+        self._raise(self.lib.gh_qual_knn_vote(self.handle, k, len(train), ptr(train), ptr(train_labels), n_rows, ptr(rows),
+                                              ptr(out_i), ptr(out_d), ptr(out_p), ptr(out_v)))
+        return out_i, out_d, out_p, out_v
 
 
 class EdgeListParser(BudgetHandle):

@@ -244,6 +244,21 @@ class CentralityGraph:
             return np.zeros((0, k), np.int32), np.zeros((0, k), np.int64), np.zeros((0, k), np.int64)
         return self._g.link_candidates(kind, k, rows)
 
+    def label_propagation(self, seed_labels, n_classes, max_rounds=100):
+        """(labels (n,) int32, rounds, converged): synchronous label propagation with clamped seeds, the rule of
+        include/graphem_hip.h "label propagation" (gh_cent_label_propagation).  seed_labels: (n,) ints, -1 = unlabelled,
+        else a class in [0, n_classes)."""
+        seed_labels = np.asarray(seed_labels).ravel()
+        if len(seed_labels) != self.n:
+            raise ValueError(f"{len(seed_labels)} seed labels for {self.n} vertices")
+        if not 1 <= int(n_classes) <= _native.LABEL_MAX_CLASSES:
+            raise ValueError(f"n_classes must lie in [1, {_native.LABEL_MAX_CLASSES}], got {n_classes}")
+        if int(max_rounds) < 0:
+            raise ValueError(f"max_rounds must be >= 0, got {max_rounds}")
+        if self._g is None:
+            return np.zeros(0, dtype=np.int32), 0, int(max_rounds) > 0
+        return self._g.label_propagation(seed_labels, n_classes, max_rounds)
+
     def louvain_levels(self, seed=0, max_levels=32, max_rounds=1000):
         """The Louvain levels of include/graphem_hip.h "communities" (gh_cent_louvain): (labels (L, n) int32, numerators
         [L] of Python ints, n_communities (L,) int64, rounds (L,) int32, M).  labels[l][v] = the smallest vertex id in v's

@@ -267,7 +267,10 @@ gh_status cl_check_k(gh_qual *h, int64_t k) {
     return GH_OK;
 }
 
-// The scan of the snapshot, once per epoch; a row with a NaN or an infinity is refused.
+}  // namespace
+
+// The scan of the snapshot, once per epoch; a row with a NaN or an infinity is refused.  Declared in qual_handle.h:
+// classify.hip refuses the same rows with the same message.
 gh_status cl_scan(gh_qual *h) {
     if (h->scan_epoch != h->epoch) {
         const int64_t n = h->n, total = n * h->D;
@@ -302,6 +305,8 @@ gh_status cl_scan(gh_qual *h) {
     if (h->bad_row >= 0) return qual_invalid(h, "position row " + std::to_string(h->bad_row) + " is not finite");
     return GH_OK;
 }
+
+namespace {
 
 gh_status cl_check_centres(gh_qual *h, int64_t k, const float *centres) {
     if (!centres) return qual_invalid(h, "centres is NULL");

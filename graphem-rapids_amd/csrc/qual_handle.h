@@ -1,6 +1,6 @@
 // The layout-quality handle (include/graphem_hip.h "layout quality"), shared by quality.hip, which owns its life cycle and
-// the position snapshot, and clusters.hip, which reads the snapshot, the stream and the device and reports through err.
-// With it: the float32 distance chain both files evaluate, and the host thread pool of their host paths.
+// the position snapshot, and clusters.hip and classify.hip, which read the snapshot, the stream and the device and report
+// through err.  With it: the float32 distance chain all of them evaluate, and the host thread pool of their host paths.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,6 +66,10 @@ struct gh_qual : gh_host {          // device < 0: host path
 
 // (quality.hip) the message gh_qual_last_error(NULL) returns on this thread
 void qual_set_create_error(const std::string &msg);
+
+// (clusters.hip) the scan of the snapshot, once per epoch: GH_ERR_INVALID "position row <v> is not finite" for a row with a NaN
+// or an infinity
+gh_status cl_scan(gh_qual *h);
 
 inline gh_status qual_invalid(gh_qual *h, const std::string &msg) {
     h->err = msg;

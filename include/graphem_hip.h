@@ -711,6 +711,24 @@ gh_status gh_cent_modularity(gh_cent_handle h, const int32_t *labels, int64_t ou
 gh_status gh_cent_louvain(gh_cent_handle h, uint64_t seed, int32_t max_levels, int32_t max_rounds, int32_t *labels,
                           int32_t *n_levels, int64_t *numerators, int64_t *n_communities, int32_t *rounds);
 
+/* ---- label propagation: synchronous, with clamped seeds (graphem-rapids_amd/classify.py: label_propagation) ---------------
+ * The graph-side baseline of node classification, over a gh_cent handle's graph (undirected, self-loops dropped, duplicate
+ * edges merged).  Every quantity is an integer; the result is a pure function of (graph, seed_labels, max_rounds).
+ *
+ * Input.  seed_labels: host int32[n]; -1 = unlabelled, any other value a class in [0, n_classes).  A labelled vertex is a
+ * seed and never changes.  L_0 = seed_labels.
+ * Round.  L_{i+1} is computed from L_i alone (two buffers).  For every non-seed v: count the classes of its neighbours w
+ * with L_i[w] >= 0.  With no such neighbour v keeps L_i[v].  Otherwise best = the greatest count; v keeps L_i[v] if that is
+ * >= 0 and its count equals best; else v takes the least class id whose count equals best.
+ * Loop.  it = 0.  (1) if it == max_rounds: stop, converged = 0; (2) run a round, it += 1; (3) if no label changed in it:
+ * stop, converged = 1; (4) repeat.  rounds = it.  max_rounds = 0 returns the input.
+ *
+ * 1 <= n_classes <= 1024.  labels: host int32[n], -1 where no label arrived; rounds and converged may be NULL.
+ * GH_ERR_INVALID for an n_classes outside that range, for max_rounds < 0 and for "seed label <v> is outside [-1, n_classes)".
+ * Device state: 12 n bytes of labels.  The host reads one flag per round.  Blocking. */
+gh_status gh_cent_label_propagation(gh_cent_handle h, int32_t n_classes, const int32_t *seed_labels, int32_t max_rounds,
+                                    int32_t *labels, int32_t *rounds, int32_t *converged);
+
 /* ---- graph generators (reference generators.py: generate_sbm / generate_bipartite_graph, generate_geometric,
  * generate_ba; graphem-rapids_amd/generators.py) ------------------------------------------------------------------
  * Three random graph families whose every random decision is a counter-based word, so an edge list is a pure function
@@ -992,6 +1010,39 @@ gh_status gh_qual_kmeans_seed_step(gh_qual_handle h, int64_t vertex, int32_t fir
  * its working memory is bounded: 4 n D bytes of sorted columns and at most 256 MiB of partial sums. */
 gh_status gh_qual_cluster_distance_sums(gh_qual_handle h, int32_t k, const int32_t *labels, int64_t n_rows, const int32_t *rows,
                                         double *sums);
+
+/* ---- node classification: exact k nearest labelled vertices and their vote (graphem-rapids_amd/classify.py: knn_neighbors,
+ * knn_classify, node_classification_benchmark) -- the same gh_qual handle ----------------------------------------------------
+ * Given the classes of a few vertices, which class does the embedding give the others?  The k nearest of a SUBSET of the
+ * snapshot's rows under a total order, and the vote of their classes: integers and float32 bits that are a pure function of
+ * the input.
+ *
+ * Training set.  train[0 .. n_train) are distinct vertex ids in [0, n), in any order; train_labels[i] >= 0 is the class of
+ * train[i].  A class id has no bound and there is no class count: ids may be sparse (0 and 1 000 000).  train_labels == NULL
+ * is allowed; pred and votes must then be NULL too.
+ * Queries.  rows[0 .. n_rows) are vertex ids in any order, repeats allowed; NULL = all n vertices in order (n_rows is ignored).
+ * Distance.  d2(u, t) is the float32 chain of "embedding quality" over all D coordinates between the snapshot rows u and t.
+ * Candidates of a query u: every training vertex t != u.  A query that is itself a training vertex never votes for itself, so
+ * train = rows = all vertices is leave-one-out in one call.
+ * Order.  (d2(u, t), t) ascending: the float distance by IEEE comparison, then the smaller vertex id.  A snapshot with a row
+ * that is not finite is refused, so no NaN arises; +inf distances (an overflowing difference) are legal, tie, and are ordered
+ * by id.
+ * Taken.  The first m = min(k, number of candidates) candidates in that order: neighbors[r][j] and d2[r][j] hold the j-th;
+ * the slots j >= m hold -1 and +inf.
+ * Vote.  votes[r] = the greatest number of taken neighbours that share one class; pred[r] = the least class id that reaches
+ * it.  m = 0 gives pred = -1 and votes = 0.
+ * Results depend only on (positions, train, train_labels, rows, k): not on the order of train, on launch geometry, on how the
+ * training set is cut into tiles and pieces, or on whether the device or the host path ran.
+ *
+ * 1 <= k <= 128.  neighbors (int32) and d2 (float32) are host arrays of shape (n_rows, k); pred and votes host int32,
+ * n_rows; each of the four may be NULL.  n_train = 0 is valid.  GH_ERR_INVALID for a k outside that range, for a query before
+ * any positions were set, for "training row <i> has a vertex id outside [0, n)", "training row <i> repeats vertex <v>" (i walks
+ * upwards, the id is tested first), "label <i> is negative", "row <r> has a vertex id outside [0, n)" and "position row <v> is
+ * not finite".  Blocking.  The device path takes the rows in batches of at most 2^22 list entries, so its working memory is
+ * bounded: 4 T (D + 2) bytes of gathered training rows, 4 n bytes of training ranks, 4 n_rows of row ids, at most 128 MiB of
+ * per-piece lists and 48 MiB of results. */
+gh_status gh_qual_knn_vote(gh_qual_handle h, int32_t k, int64_t n_train, const int32_t *train, const int32_t *train_labels,
+                           int64_t n_rows, const int32_t *rows, int32_t *neighbors, float *d2, int32_t *pred, int32_t *votes);
 
 /* ---- edge-list ingestion: text -> (vertices, edges) (reference datasets.py: SNAPDataset.load, _load_mtx_file,
  * _load_edges_file; graphem-rapids_amd/datasets.py) ------------------------------------------------------------------
