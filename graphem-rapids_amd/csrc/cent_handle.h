@@ -1,6 +1,6 @@
 // The centrality handle (include/graphem_hip.h "centrality"), shared by centrality.hip, which owns its life cycle, and
 // graphstats.hip, communities.hip, cores.hip and links.hip, which read the CSR, the stream and the budget and report
-// through err.
+// through err.  The CSR is gh_csr_from_keys' (csr_build.h): symmetric, deduplicated, rows ascending.
 #pragma once
 #include "host_util.h"
 

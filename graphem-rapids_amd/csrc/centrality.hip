@@ -386,17 +386,9 @@ extern "C" gh_status gh_cent_create(gh_cent_handle *out, int device_id, int64_t 
     if (n_edges < 0 || (n_edges > 0 && !edges)) return fail(GH_ERR_INVALID, "bad edge list");
     std::vector<uint64_t> key;
     GH_TRY_ST(gh_canonical_edge_keys(n, n_edges, edges, false, "edge", &key, &g_cent_error));
-    // symmetric CSR, neighbours ascending
-    std::vector<int64_t> ptr((size_t)n + 1, 0);
-    for (uint64_t k : key) { ++ptr[(k >> 32) + 1]; ++ptr[(k & 0xFFFFFFFFu) + 1]; }
-    for (int64_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int32_t> adj((size_t)ptr[n]);
-    {
-        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
-        for (uint64_t k : key) adj[fill[k >> 32]++] = (int32_t)(k & 0xFFFFFFFFu);
-        for (uint64_t k : key) adj[fill[k & 0xFFFFFFFFu]++] = (int32_t)(k >> 32);
-        for (int64_t i = 0; i < n; ++i) std::sort(adj.begin() + ptr[i], adj.begin() + ptr[i + 1]);
-    }
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> adj;
+    gh_csr_from_keys(n, key, GH_CSR_SYMMETRIC, &ptr, &adj);   // neighbours ascending
     std::vector<double> inv_deg((size_t)n);
     int64_t max_degree = 0;
     for (int64_t i = 0; i < n; ++i) {

@@ -21,7 +21,8 @@
 // Edge set-up: up[u] = the entries of row u above u, scanned to base[]; the upper arc at position a of row u is edge
 // base[u] + (a - first upper position of u), the canonical id, and a lower arc (u, v) finds its twin by one bisection of
 // row v.  eid[arc] = that id, eu[e] / ea[e] = the lower endpoint and the upper arc's position.  sup[e] = the common
-// neighbours of e's endpoints (the shorter row searched in the longer one, as gs_triangle_kernel does).
+// neighbours of e's endpoints (the shorter row searched in the longer one: gs_common_walk of csr_core.h, as in
+// gs_triangle_kernel).
 // Edge push (cr_edge_push_kernel): a leaver e = (u, v) intersects the two rows again.  For a common neighbour w the stamps
 // of (u, w) and (v, w) say: dead before this round -- the triangle was; leaving now with a smaller id than e -- that edge
 // accounts for the triangle; otherwise e takes 1 from the support of each of the two that stays.
@@ -140,32 +141,12 @@ __global__ __launch_bounds__(GS_BLOCK) void cr_edge_id_kernel(int64_t n, int64_t
     }
 }
 
-// The rows of an edge's endpoints, the shorter one first, for a walk over their common entries.
-struct CrRows {
-    int64_t sb, se, lb, le;
-    bool u_short;
-};
-
-__device__ __forceinline__ CrRows cr_rows(const int64_t *__restrict__ ptr, int32_t u, int32_t v) {
-    const int64_t ub = ptr[u], ue = ptr[u + 1], vb = ptr[v], ve = ptr[v + 1];
-    CrRows w;
-    w.u_short = ue - ub <= ve - vb;
-    w.sb = w.u_short ? ub : vb; w.se = w.u_short ? ue : ve;
-    w.lb = w.u_short ? vb : ub; w.le = w.u_short ? ve : ue;
-    return w;
-}
-
 __global__ __launch_bounds__(GS_BLOCK) void cr_support_kernel(int64_t edges, const int64_t *__restrict__ ptr, const int32_t *__restrict__ adj,
                                                               const int32_t *__restrict__ eu, const int32_t *__restrict__ ea, int32_t *sup) {
     GS_GRID_LOOP(e, edges) {
-        const CrRows w = cr_rows(ptr, eu[e], adj[ea[e]]);
-        int64_t lb = w.lb;
+        const GsRows w = gs_rows(ptr, eu[e], adj[ea[e]]);
         int32_t c = 0;
-        for (int64_t k = w.sb; k < w.se && lb < w.le; ++k) {
-            const int32_t x = adj[k];
-            lb = gs_lower_bound(adj, lb, w.le, x);
-            if (lb < w.le && adj[lb] == x) ++c;
-        }
+        gs_common_walk(adj, w.sb, w.se, w.lb, w.le, [&](int64_t, int64_t) { ++c; });
         sup[e] = c;
     }
 }
@@ -178,19 +159,15 @@ __global__ __launch_bounds__(GS_BLOCK) void cr_edge_push_kernel(int64_t edges, c
     const int32_t r = c->r;
     GS_GRID_LOOP(e, edges) {
         if (stamp[e] != r) continue;
-        const CrRows w = cr_rows(ptr, eu[e], adj[ea[e]]);
-        int64_t lb = w.lb;
-        for (int64_t k = w.sb; k < w.se && lb < w.le; ++k) {
-            const int32_t x = adj[k];
-            lb = gs_lower_bound(adj, lb, w.le, x);
-            if (lb >= w.le || adj[lb] != x) continue;
-            const int32_t e1 = eid[k], e2 = eid[lb];   // the triangle's other two edges
+        const GsRows w = gs_rows(ptr, eu[e], adj[ea[e]]);
+        gs_common_walk(adj, w.sb, w.se, w.lb, w.le, [&](int64_t k, int64_t at) {
+            const int32_t e1 = eid[k], e2 = eid[at];   // the triangle's other two edges
             const int32_t g1 = stamp[e1], g2 = stamp[e2];
-            if ((g1 != 0 && g1 != r) || (g2 != 0 && g2 != r)) continue;   // dead before this round
-            if ((g1 == r && e1 < e) || (g2 == r && e2 < e)) continue;     // charged to a leaver of smaller id
+            if ((g1 != 0 && g1 != r) || (g2 != 0 && g2 != r)) return;   // dead before this round
+            if ((g1 == r && e1 < e) || (g2 == r && e2 < e)) return;     // charged to a leaver of smaller id
             if (g1 == 0) atomicSub(&sup[e1], 1);
             if (g2 == 0) atomicSub(&sup[e2], 1);
-        }
+        });
     }
 }
 

@@ -11,17 +11,17 @@
 //   since label[x] <= x stays inside the component, that root is the component's smallest id.  Round r runs only when
 //   round r - 1 set its flag; the host reads the flags every GS_CHECK_EVERY rounds.
 //
-// Distances.  64 sources to a group; bit b of a word belongs to source 64 g + b.  Per (group, vertex) three words,
-// [group][vertex]: vis (sources that reached v; the unused bits of a short last group preset), cur and nxt (sources
-// whose frontier holds v at the previous / this level).  Lane = vertex, so the 64 words a wave holds are one group's.
-//   gs_level_kernel (L)   nxt[v] = (OR of cur over the neighbours) & ~vis[v], always stored, so the ping-pong buffers need
-//                         no clearing.  The wave transposes its 64 new words with 64 ballots: lane b adds the population
-//                         count of bit b to a register, over a grid-stride loop; then, per source, integer atomics:
+// Distances.  The bit-parallel search of frontier_core.h: its state, its fill and seed kernels and the pull step of one
+// vertex, shared with quality.hip's hop profile.  Lane = vertex, so the 64 words a wave holds are one group's.
+//   gs_level_kernel (L)   gs_frontier_pull gives every lane its word of new bits.  The wave transposes its 64 new words
+//                         with 64 ballots: lane b adds the population count of bit b to a register, over a grid-stride
+//                         loop; then, per source, integer atomics onto counters that start at zero:
 //                         reached += count, dist_sum += L count, eccentricity = max(., L).  Sets flags[L] when anything
 //                         was reached; a launch after the last level sees flags[L - 1] == 0 and returns.
 //
 // Triangles.  One thread per arc (u, v) with u < v: the shorter of the two rows, from its first entry above v, is searched
-// in the longer one by bisection (the window shrinks as both ascend), so an arc costs min(deg) log(max deg).  Every
+// in the longer one by bisection (gs_common_walk of csr_core.h: the window shrinks as both ascend), so an arc costs
+// min(deg) log(max deg).  Every
 // triangle u < v < w is found once, at its arc (u, v), and credited to its three vertices with 64-bit integer atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +33,7 @@
 #include "../../include/graphem_hip.h"
 #include "cent_handle.h"
 #include "csr_core.h"
+#include "frontier_core.h"
 
 namespace {
 
@@ -83,27 +84,6 @@ struct GsLevel {
     int32_t level;
 };
 
-// vis = the unused bits of the batch's last group, 0 elsewhere; cur = 0
-__global__ __launch_bounds__(GS_BLOCK) void gs_dist_fill_kernel(int64_t n, int64_t G, uint64_t unused_last, uint64_t *vis, uint64_t *cur) {
-    GS_GRID_LOOP(i, G * n) {
-        vis[i] = i >= (G - 1) * n ? unused_last : 0;
-        cur[i] = 0;
-    }
-}
-
-__global__ __launch_bounds__(GS_BLOCK) void gs_dist_seed_kernel(int64_t n, int64_t n_src, const int32_t *__restrict__ sources, gs_u64 *vis,
-                                                                gs_u64 *cur, gs_u64 *reached, gs_u64 *dist_sum, int32_t *ecc) {
-    GS_GRID_LOOP(j, n_src) {
-        const int64_t w = (j >> 6) * n + sources[j];
-        const gs_u64 bit = 1ull << (j & 63);
-        atomicOr(&vis[w], bit);
-        atomicOr(&cur[w], bit);
-        reached[j] = 1;
-        dist_sum[j] = 0;
-        ecc[j] = 0;
-    }
-}
-
 // grid (x, G): the waves of row g stride over the vertices, 64 at a time
 __global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(GsLevel a) {
     if (gs_flag(&a.flags[a.level - 1]) == 0) return;
@@ -115,18 +95,7 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(GsLevel a) {
     uint32_t cnt = 0;   // lane b: vertices that source 64 g + b reached at this level (< 2^31)
     for (int64_t base = (int64_t)blockIdx.x * GS_BLOCK + (threadIdx.x & ~63); base < a.n; base += stride) {
         const int64_t v = base + lane;
-        uint64_t w = 0;
-        if (v < a.n) {
-            const uint64_t need = ~vis[v];
-            if (need) {
-                uint64_t acc = 0;
-                const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
-                for (int64_t k = beg; k < end; ++k) acc |= cur[a.adj[k]];
-                w = acc & need;
-                if (w) vis[v] = ~need | w;
-            }
-            nxt[v] = w;
-        }
+        const uint64_t w = v < a.n ? gs_frontier_pull(a.ptr, a.adj, vis, cur, nxt, v) : 0;
         if (__ballot(w != 0) == 0) continue;
 #pragma unroll 8
         for (int b = 0; b < 64; ++b) {
@@ -150,21 +119,14 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_triangle_kernel(int64_t n, int64_
         const int32_t v = adj[e];
         const int32_t u = gs_arc_row(ptr, n, e);
         if (v <= u) continue;
-        const int64_t ub = ptr[u], ue = ptr[u + 1], vb = ptr[v], ve = ptr[v + 1];
-        const bool u_short = ue - ub <= ve - vb;
-        int64_t sb = u_short ? ub : vb, lb = u_short ? vb : ub;
-        const int64_t se = u_short ? ue : ve, le = u_short ? ve : ue;
-        sb = gs_lower_bound(adj, sb, se, v + 1);
-        lb = gs_lower_bound(adj, lb, le, v + 1);
+        const GsRows r = gs_rows(ptr, u, v);
+        // both rows from their first entry above v
+        const int64_t sb = gs_lower_bound(adj, r.sb, r.se, v + 1), lb = gs_lower_bound(adj, r.lb, r.le, v + 1);
         gs_u64 c = 0;
-        for (int64_t k = sb; k < se && lb < le; ++k) {
-            const int32_t w = adj[k];
-            lb = gs_lower_bound(adj, lb, le, w);
-            if (lb < le && adj[lb] == w) {
-                ++c;
-                atomicAdd(&tri[w], 1ull);
-            }
-        }
+        gs_common_walk(adj, sb, r.se, lb, r.le, [&](int64_t k, int64_t) {
+            ++c;
+            atomicAdd(&tri[adj[k]], 1ull);
+        });
         if (c) {
             atomicAdd(&tri[u], c);
             atomicAdd(&tri[v], c);
@@ -203,32 +165,25 @@ gh_status gs_components(gh_cent *h, int32_t *labels) {
     return GH_OK;
 }
 
-// One batch of G groups holding ns <= 64 G sources; d_out: reached, dist_sum, eccentricity of the batch's sources.
-gh_status gs_distance_batch(gh_cent *h, int64_t G, const int32_t *src, int64_t ns, uint64_t *d_vis, uint64_t *d_fa, uint64_t *d_fb,
-                            int32_t *d_flags, int32_t *d_src, gs_u64 *d_reached, gs_u64 *d_dsum, int32_t *d_ecc) {
+// One batch of G groups holding ns <= 64 G sources; the level kernel adds to reached, dist_sum and eccentricity of the
+// batch's sources, which start at zero.
+gh_status gs_distance_batch(gh_cent *h, gs_frontier &f, int64_t G, const int32_t *src, int64_t ns, int32_t *d_src, gs_u64 *d_reached,
+                            gs_u64 *d_dsum, int32_t *d_ecc) {
     const int64_t n = h->n;
     GH_HIP(hipMemcpyAsync(d_src, src, 4 * ns, hipMemcpyHostToDevice, h->stream));
-    GH_HIP(hipMemsetAsync(d_flags, 0, 4 * (n + 2), h->stream));
-    const int32_t one = 1;
-    GH_HIP(hipMemcpyAsync(d_flags, &one, 4, hipMemcpyHostToDevice, h->stream));
-    const int64_t in_last = ns - 64 * (G - 1);
-    const uint64_t unused_last = in_last < 64 ? ~0ull << in_last : 0;
-    gs_dist_fill_kernel<<<dim3(gs_blocks(G * n)), dim3(GS_BLOCK), 0, h->stream>>>(n, G, unused_last, d_vis, d_fa);
-    gs_dist_seed_kernel<<<dim3(gs_blocks(ns)), dim3(GS_BLOCK), 0, h->stream>>>(n, ns, d_src, (gs_u64 *)d_vis, (gs_u64 *)d_fa, d_reached,
-                                                                              d_dsum, d_ecc);
-    GH_HIP(hipGetLastError());
+    GH_TRY_ST(f.begin(h, G, ns, d_src, GS_MAX_BLOCKS));
     GsLevel a{};
     a.ptr = h->d_ptr.p; a.adj = h->d_adj.p;
-    a.vis = d_vis; a.flags = d_flags;
+    a.vis = f.vis.p; a.flags = f.flags.p;
     a.reached = d_reached; a.dist_sum = d_dsum; a.ecc = d_ecc;
     a.n = n;
     const int64_t per_row = std::max<int64_t>(1, GS_MAX_BLOCKS / G);
     const dim3 grid((unsigned)std::min<int64_t>(per_row, (n + GS_BLOCK - 1) / GS_BLOCK), (unsigned)G);
     int32_t last_level = 0;   // the kernel keeps the eccentricities itself
-    return gh_level_loop(h, n, d_flags, GS_CHECK_EVERY, &last_level, [&](int32_t L) -> gh_status {
+    return gh_level_loop(h, n, f.flags.p, GS_CHECK_EVERY, &last_level, [&](int32_t L) -> gh_status {
         a.level = L;
-        a.cur = (L & 1) ? d_fa : d_fb;
-        a.nxt = (L & 1) ? d_fb : d_fa;
+        a.cur = f.cur(L);
+        a.nxt = f.nxt(L);
         gs_level_kernel<<<grid, dim3(GS_BLOCK), 0, h->stream>>>(a);
         GH_HIP(hipGetLastError());
         return GH_OK;
@@ -265,23 +220,25 @@ extern "C" gh_status gh_cent_distances(gh_cent_handle h, int64_t n_sources, cons
     const int64_t n = h->n, groups = (n_sources + 63) / 64;
     int64_t G = std::max<int64_t>(1, h->budget / (24 * n));   // 3 words per (group, vertex)
     G = std::min<int64_t>({G, groups, (int64_t)65535});       // 65535: grid.y
-    gh_dev<uint64_t> d_vis, d_fa, d_fb;
-    gh_dev<int32_t> d_flags, d_src, d_ecc;
-    gh_dev<gs_u64> d_cnt;
-    if (!d_vis.alloc(8 * G * n) || !d_fa.alloc(8 * G * n) || !d_fb.alloc(8 * G * n) || !d_flags.alloc(4 * (n + 2)) ||
-        !d_src.alloc(4 * 64 * G) || !d_cnt.alloc(16 * 64 * groups) || !d_ecc.alloc(4 * 64 * groups))
+    gs_frontier f;
+    gh_dev<int32_t> d_src, d_ecc;
+    gh_dev<gs_u64> d_cnt;   // reached beyond the source itself, then dist_sum
+    if (!f.alloc(G, n) || !d_src.alloc(4 * 64 * G) || !d_cnt.alloc(16 * 64 * groups) || !d_ecc.alloc(4 * 64 * groups))
         return fail(GH_ERR_NOMEM, "hipMalloc failed for " + std::to_string(G) + " source groups of distance state");
     auto run = [&]() -> gh_status {
+        GH_HIP(hipMemsetAsync(d_cnt.p, 0, 16 * 64 * groups, h->stream));
+        GH_HIP(hipMemsetAsync(d_ecc.p, 0, 4 * 64 * groups, h->stream));
         for (int64_t g0 = 0; g0 < groups; g0 += G) {
             const int64_t gb = std::min(G, groups - g0);
             const int64_t ns = std::min<int64_t>(64 * gb, n_sources - 64 * g0);
-            GH_TRY_ST(gs_distance_batch(h, gb, sources + 64 * g0, ns, d_vis.p, d_fa.p, d_fb.p, d_flags.p, d_src.p, d_cnt.p + 64 * g0,
-                                        d_cnt.p + 64 * groups + 64 * g0, d_ecc.p + 64 * g0));
+            GH_TRY_ST(gs_distance_batch(h, f, gb, sources + 64 * g0, ns, d_src.p, d_cnt.p + 64 * g0, d_cnt.p + 64 * groups + 64 * g0,
+                                        d_ecc.p + 64 * g0));
         }
         if (reached) GH_HIP(hipMemcpyAsync(reached, d_cnt.p, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
         if (dist_sum) GH_HIP(hipMemcpyAsync(dist_sum, d_cnt.p + 64 * groups, 8 * n_sources, hipMemcpyDeviceToHost, h->stream));
         if (eccentricity) GH_HIP(hipMemcpyAsync(eccentricity, d_ecc.p, 4 * n_sources, hipMemcpyDeviceToHost, h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; reached && i < n_sources; ++i) reached[i] += 1;   // the source itself
         return GH_OK;
     };
     const gh_status st = run();

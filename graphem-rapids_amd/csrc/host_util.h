@@ -1,7 +1,7 @@
 // Host plumbing shared by every handle behind the C ABI, the layout engine included: the HIP-call checks, gh_dev -- a device
 // allocation that frees itself, the type of every buffer a handle owns -- with the process-wide count of the live ones, the
-// life cycle of an analysis handle (device, stream, budget, message), the canonical edge set, and the level loop of a
-// breadth-first pass.  No kernel and no policy lives here.
+// life cycle of an analysis handle (device, stream, budget, message), the canonical edge set and its CSR (csr_build.h),
+// and the level loop of a breadth-first pass.  No kernel and no policy lives here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/graphem_hip.h"
+#include "csr_build.h"   // gh_canonical_edge_keys and the CSR builder: host-only code, kept where a host compiler reads it alone
 
 // The checks need a handle `h` in scope whose `err` takes the message "<call>: <hip error string>".
 #define GH_HIP(call)                                                                        \
@@ -115,27 +116,6 @@ inline gh_status gh_host_set_budget(gh_host *h, int64_t bytes, int64_t dflt, std
     if (!h) { *null_msg = "handle is NULL"; return GH_ERR_INVALID; }
     if (bytes < 0) { h->err = "budget must be >= 0 (0: the default)"; return GH_ERR_INVALID; }
     h->budget = bytes ? bytes : dflt;
-    return GH_OK;
-}
-
-// The canonical edge set of `count` vertex pairs on n vertices: ids validated, self-loops dropped, duplicates merged, as
-// ascending keys (a << 32) | b -- (u, v) as given when directed, else (min, max).  `noun` names a pair in the message.
-inline gh_status gh_canonical_edge_keys(int64_t n, int64_t count, const int32_t *pairs, bool directed, const char *noun,
-                                        std::vector<uint64_t> *keys, std::string *err) {
-    keys->clear();
-    keys->reserve((size_t)count);
-    for (int64_t i = 0; i < count; ++i) {
-        const int64_t u = pairs[2 * i], v = pairs[2 * i + 1];
-        if (u < 0 || u >= n || v < 0 || v >= n) {
-            *err = std::string(noun) + " " + std::to_string(i) + " has a vertex id outside [0, n)";
-            return GH_ERR_INVALID;
-        }
-        if (u == v) continue;
-        const uint64_t a = directed ? u : std::min(u, v), b = directed ? v : std::max(u, v);
-        keys->push_back((a << 32) | b);
-    }
-    std::sort(keys->begin(), keys->end());
-    keys->erase(std::unique(keys->begin(), keys->end()), keys->end());
     return GH_OK;
 }
 

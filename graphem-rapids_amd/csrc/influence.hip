@@ -403,23 +403,6 @@ extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, i
     if (n_arcs < 0 || (n_arcs > 0 && !arcs)) return fail(GH_ERR_INVALID, "bad arc list");
     std::vector<uint64_t> key;
     GH_TRY_ST(gh_canonical_edge_keys(n, n_arcs, arcs, directed != 0, "arc", &key, &g_ic_error));
-    // CSR of arcs by source (push) and by target (pull); undirected: both directions, and the two are the same CSR
-    auto build = [&](bool by_target, std::vector<int64_t> &ptr, std::vector<int32_t> &adj) {
-        ptr.assign((size_t)n + 1, 0);
-        for (uint64_t k : key) {
-            const int32_t a = (int32_t)(k >> 32), b = (int32_t)(k & 0xFFFFFFFFu);
-            if (directed) ++ptr[(by_target ? b : a) + 1];
-            else { ++ptr[a + 1]; ++ptr[b + 1]; }
-        }
-        for (int64_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
-        adj.resize((size_t)ptr[n]);
-        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
-        for (uint64_t k : key) {
-            const int32_t a = (int32_t)(k >> 32), b = (int32_t)(k & 0xFFFFFFFFu);
-            if (directed) { if (by_target) adj[fill[b]++] = a; else adj[fill[a]++] = b; }
-            else { adj[fill[a]++] = b; adj[fill[b]++] = a; }
-        }
-    };
     gh_ic *h = new gh_ic();
     h->budget = IC_DEFAULT_BUDGET;
     h->n = n;
@@ -428,10 +411,11 @@ extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, i
     auto bail = [&](gh_status st, const std::string &msg) { gh_ic_destroy(h); return fail(st, msg); };
     const gh_status st = gh_host_open(h, device_id, &g_ic_error);
     if (st != GH_OK) { gh_ic_destroy(h); return st; }
+    // CSR of arcs by source (push) and by target (pull); undirected: both directions, and the two are the same CSR
     for (int pass = 0; pass < (directed ? 2 : 1); ++pass) {
         std::vector<int64_t> ptr;
         std::vector<int32_t> adj;
-        build(pass == 1, ptr, adj);
+        gh_csr_from_keys(n, key, !directed ? GH_CSR_SYMMETRIC : pass ? GH_CSR_BY_TARGET : GH_CSR_BY_SOURCE, &ptr, &adj);
         gh_dev<int64_t> &dp = pass ? h->d_in_own_ptr : h->d_out_ptr;
         gh_dev<int32_t> &da = pass ? h->d_in_own_adj : h->d_out_adj;
         if (!dp.alloc(8 * ptr.size()) || !da.alloc(4 * adj.size())) return bail(GH_ERR_NOMEM, "hipMalloc failed");

@@ -4,7 +4,8 @@
 // the host computes once per handle).  No result depends on the order of an atomic or on the number of workgroups.
 //
 // lk_pair_kernel        a group of G lanes (G = 4 .. 64, one value per launch) takes one pair: the lanes stride over the
-//                       shorter row, each bisects the longer one, and xor-shuffles inside the group add up cn, aa and ra.
+//                       shorter row (gs_rows of csr_core.h picks it), each bisects the longer one, and xor-shuffles inside
+//                       the group add up cn, aa and ra.
 // lk_candidate_kernel   persistent workgroups take source rows off a ticket counter.  Each owns a slab of n 64-bit sums in
 //                       global memory, zero on entry, and a buffer of n (id, value) entries; no word of either is touched
 //                       by another workgroup.  Per source u:
@@ -50,15 +51,13 @@ __global__ __launch_bounds__(GS_BLOCK) void lk_pair_kernel(int64_t n_pairs, int 
     const int lane = threadIdx.x & (G - 1);
     const int64_t per_block = GS_BLOCK / G;
     for (int64_t p = (int64_t)blockIdx.x * per_block + threadIdx.x / G; p < n_pairs; p += (int64_t)gridDim.x * per_block) {
-        const int32_t u = pairs[2 * p], v = pairs[2 * p + 1];
-        const int64_t ub = ptr[u], ue = ptr[u + 1], vb = ptr[v], ve = ptr[v + 1];
-        const bool u_short = ue - ub <= ve - vb;
-        const int64_t sb = u_short ? ub : vb, se = u_short ? ue : ve, lb = u_short ? vb : ub, le = u_short ? ve : ue;
+        const GsRows rows = gs_rows(ptr, pairs[2 * p], pairs[2 * p + 1]);
         int64_t c = 0, a = 0, r = 0;
-        for (int64_t k = sb + lane; k < se; k += G) {
+        // the lanes stride over the short row and each bisects the whole long row: no window to carry, so not gs_common_walk
+        for (int64_t k = rows.sb + lane; k < rows.se; k += G) {
             const int32_t w = adj[k];
-            const int64_t at = gs_lower_bound(adj, lb, le, w);
-            if (at < le && adj[at] == w) {
+            const int64_t at = gs_lower_bound(adj, rows.lb, rows.le, w);
+            if (at < rows.le && adj[at] == w) {
                 const int64_t d = ptr[w + 1] - ptr[w];
                 c += 1;
                 a += w_aa[d];

@@ -43,7 +43,7 @@
 #include <thread>
 #include <vector>
 
-#include "csr_core.h"
+#include "frontier_core.h"   // with csr_core.h: gs_flag, GS_GRID_LOOP
 #include "host_util.h"
 #include "intersect_core.h"
 #include "qual_handle.h"   // struct gh_qual, QUAL_BLOCK, qual_d2, qual_host_parallel: shared with clusters.hip
@@ -63,6 +63,8 @@
 #define QUAL_HOP_MAX_BLOCKS 2048            // workgroups of one level launch, over all groups of the batch
 #define QUAL_HOP_STATE_BYTES (1ll << 30)    // visited, frontier and next frontier of the groups in flight: 24 n bytes a group
 #define QUAL_HOP_CHECK_EVERY 4              // levels between two host reads of the flags
+
+static_assert(QUAL_BLOCK == GS_BLOCK, "GS_GRID_LOOP and the frontier kernels stride by GS_BLOCK");
 
 namespace {
 
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_length_kernel(int64_t E, cons
                                                                  int D, double *__restrict__ part) {
     __shared__ qual_len s_w[QUAL_BLOCK / 64];
     qual_len v = {INFINITY, -INFINITY, 0.0, 0.0};
-    for (int64_t e = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * QUAL_BLOCK) {
+    GS_GRID_LOOP(e, E) {
         const double L = qual_length(pos, D, D, edges[e]);
         const qual_len one = {L, L, L, L * L};
         qual_len_join(v, one);
@@ -309,23 +311,6 @@ __host__ __device__ __forceinline__ void qual_hop_pair(qual_hop &a, float d2, do
     *d_out = d;
 }
 
-// vis = the unused bits of the batch's last group, 0 elsewhere; cur = 0
-__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_fill_kernel(int64_t n, int64_t G, uint64_t unused_last, uint64_t *vis, uint64_t *cur) {
-    for (int64_t i = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x; i < G * n; i += (int64_t)gridDim.x * QUAL_BLOCK) {
-        vis[i] = i >= (G - 1) * n ? unused_last : 0;
-        cur[i] = 0;
-    }
-}
-
-// source j of the batch: bit j & 63 of group j >> 6, at its own vertex; a repeated id is a source of its own
-__global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_seed_kernel(int64_t n, int64_t n_src, const int32_t *__restrict__ src, qual_u64 *vis, qual_u64 *cur) {
-    const int64_t j = (int64_t)blockIdx.x * QUAL_BLOCK + threadIdx.x;
-    if (j >= n_src) return;
-    const int64_t w = (j >> 6) * n + src[j];
-    atomicOr(&vis[w], 1ull << (j & 63));
-    atomicOr(&cur[w], 1ull << (j & 63));
-}
-
 struct QualHopLevel {
     const int64_t *ptr; const int32_t *idx;   // the simple graph
     const float *pos;
@@ -338,9 +323,9 @@ struct QualHopLevel {
     int32_t D, level;
 };
 
-// One level of the bit-parallel search, grid (x, G): the waves of row g stride over the vertices, 64 at a time, lane =
-// vertex.  nxt[v] = (OR of cur over the neighbours) & ~vis[v], always stored, so the ping-pong buffers need no clearing.  A
-// lane whose word of new bits is not empty walks them: bit b is the pair (source 64 g + b, v) at hop `level`, met here and
+// One level of the bit-parallel search (frontier_core.h), grid (x, G): the waves of row g stride over the vertices, 64 at a
+// time, lane = vertex; gs_frontier_pull gives the vertex's word of new bits.  A lane whose word is not empty walks them:
+// bit b is the pair (source 64 g + b, v) at hop `level`, met here and
 // never again.  Per hop the lane keeps the five accumulators in registers; per source the workgroup adds in LDS.  Both
 // leave the workgroup as one slab of partials -- every workgroup writes its slab, zeros included -- and
 // qual_hop_reduce_kernel adds the slabs in a fixed order.  STAGED: the group's 64 source rows are read from LDS.
@@ -369,18 +354,7 @@ __global__ __launch_bounds__(QUAL_BLOCK) void qual_hop_level_kernel(QualHopLevel
     const int64_t stride = (int64_t)gridDim.x * QUAL_BLOCK;
     for (int64_t base = (int64_t)blockIdx.x * QUAL_BLOCK + (threadIdx.x & ~63); base < a.n; base += stride) {
         const int64_t v = base + lane;
-        uint64_t w = 0;
-        if (v < a.n) {
-            const uint64_t need = ~vis[v];
-            if (need) {
-                uint64_t reach = 0;
-                const int64_t beg = a.ptr[v], end = a.ptr[v + 1];
-                for (int64_t k = beg; k < end; ++k) reach |= cur[a.idx[k]];
-                w = reach & need;
-                if (w) vis[v] = ~need | w;
-            }
-            nxt[v] = w;
-        }
+        const uint64_t w = v < a.n ? gs_frontier_pull(a.ptr, a.idx, vis, cur, nxt, v) : 0;
         if (w == 0) continue;
         const float *xv = a.pos + v * D;
         // lane l starts its walk at bit l: where the words are dense the lanes of a wave add to 64 different LDS words
@@ -565,18 +539,7 @@ gh_status qual_build_graph(gh_qual *h) {
     }
     std::vector<uint64_t> keys;
     GH_TRY_ST(gh_canonical_edge_keys(h->n, h->E, (const int32_t *)edges, false, "edge", &keys, &h->err));
-    h->g_ptr.assign((size_t)h->n + 1, 0);
-    for (uint64_t k : keys) {
-        h->g_ptr[(size_t)(k >> 32) + 1] += 1;
-        h->g_ptr[(size_t)(k & 0xFFFFFFFFu) + 1] += 1;
-    }
-    for (int64_t u = 0; u < h->n; ++u) h->g_ptr[u + 1] += h->g_ptr[u];
-    h->g_idx.resize(2 * keys.size());
-    std::vector<int64_t> fill(h->g_ptr.begin(), h->g_ptr.end() - 1);
-    // keys ascend by (a, b) with a < b: row b takes its smaller neighbours a in ascending order first, then row a its
-    // larger neighbours b in ascending order, so every row ends up ascending
-    for (uint64_t k : keys) h->g_idx[(size_t)fill[k & 0xFFFFFFFFu]++] = (int32_t)(k >> 32);
-    for (uint64_t k : keys) h->g_idx[(size_t)fill[k >> 32]++] = (int32_t)(k & 0xFFFFFFFFu);
+    gh_csr_from_keys(h->n, keys, GH_CSR_SYMMETRIC, &h->g_ptr, &h->g_idx);
     h->g_built = true;
     return GH_OK;
 }
@@ -763,13 +726,13 @@ gh_status qual_hops_device(gh_qual *h, int64_t S, const int32_t *src, qual_hop_r
     const int64_t X = std::max<int64_t>(1, std::min<int64_t>((n + QUAL_BLOCK - 1) / QUAL_BLOCK, QUAL_HOP_MAX_BLOCKS / G));
     std::vector<int32_t> padded(64 * (size_t)groups, 0);   // the unused slots of the last group name vertex 0: a row that exists
     std::copy(src, src + S, padded.begin());
-    gh_dev<uint64_t> d_vis, d_fa, d_fb;
-    gh_dev<int32_t> d_flags, d_src, d_ecc;
+    gs_frontier f;
+    gh_dev<int32_t> d_src, d_ecc;
     gh_dev<double> d_lvl_f, d_src_f, d_hop_f, d_over;
     gh_dev<qual_u64> d_lvl_i, d_hop_i, d_reach;
     gh_dev<uint32_t> d_src_c;
-    const size_t state = 8 * (size_t)(G * n), slabs = (size_t)(G * X), per_src = 64 * (size_t)groups;
-    if (!d_vis.alloc(state) || !d_fa.alloc(state) || !d_fb.alloc(state) || !d_flags.alloc(4 * (size_t)(n + 2)) || !d_src.alloc(4 * per_src) ||
+    const size_t slabs = (size_t)(G * X), per_src = 64 * (size_t)groups;
+    if (!f.alloc(G, n) || !d_src.alloc(4 * per_src) ||
         !d_lvl_f.alloc(16 * slabs) || !d_lvl_i.alloc(24 * slabs) || !d_src_f.alloc(1024 * slabs) || !d_src_c.alloc(256 * slabs) ||
         !d_hop_f.alloc(16 * (size_t)n) || !d_hop_i.alloc(24 * (size_t)n) || !d_reach.alloc(8 * per_src) || !d_ecc.alloc(4 * per_src) ||
         !d_over.alloc(16 * per_src)) {
@@ -785,37 +748,28 @@ gh_status qual_hops_device(gh_qual *h, int64_t S, const int32_t *src, qual_hop_r
     const bool staged = 64 * (int64_t)h->D <= QUAL_HOP_SRC_LDS;
     QualHopLevel lv{};
     lv.ptr = h->d_gptr.p; lv.idx = h->d_gidx.p; lv.pos = h->d_pos.p;
-    lv.vis = d_vis.p; lv.flags = d_flags.p;
+    lv.vis = f.vis.p; lv.flags = f.flags.p;
     lv.lvl_f = d_lvl_f.p; lv.lvl_i = d_lvl_i.p; lv.src_f = d_src_f.p; lv.src_c = d_src_c.p;
     lv.n = n; lv.D = h->D;
     QualHopReduce rd{};
-    rd.flags = d_flags.p;
+    rd.flags = f.flags.p;
     rd.lvl_f = d_lvl_f.p; rd.lvl_i = d_lvl_i.p; rd.src_f = d_src_f.p; rd.src_c = d_src_c.p;
     rd.hop_f = d_hop_f.p; rd.hop_i = d_hop_i.p;
     rd.X = X;
-    const unsigned fill_blocks = (unsigned)std::min<int64_t>(QUAL_HOP_MAX_BLOCKS, qual_grid(G * n));
     int32_t H = 0;
     for (int64_t g0 = 0; g0 < groups; g0 += G) {
         const int64_t gb = std::min(G, groups - g0), ns = std::min<int64_t>(64 * gb, S - 64 * g0);
-        const int64_t in_last = ns - 64 * (gb - 1);
-        const uint64_t unused_last = in_last < 64 ? ~0ull << in_last : 0;
-        GH_HIP(hipMemsetAsync(d_flags.p, 0, 4 * (size_t)(n + 2), h->stream));
-        const int32_t one = 1;
-        GH_HIP(hipMemcpyAsync(d_flags.p, &one, 4, hipMemcpyHostToDevice, h->stream));
-        qual_hop_fill_kernel<<<dim3(fill_blocks), dim3(QUAL_BLOCK), 0, h->stream>>>(n, gb, unused_last, d_vis.p, d_fa.p);
-        GH_LAUNCH_CHECK();
-        qual_hop_seed_kernel<<<dim3(qual_grid(ns)), dim3(QUAL_BLOCK), 0, h->stream>>>(n, ns, d_src.p + 64 * g0, (qual_u64 *)d_vis.p, (qual_u64 *)d_fa.p);
-        GH_LAUNCH_CHECK();
+        GH_TRY_ST(f.begin(h, gb, ns, d_src.p + 64 * g0, QUAL_HOP_MAX_BLOCKS));
         lv.src = d_src.p + 64 * g0;
         rd.G = gb;
         rd.reach = d_reach.p + 64 * g0; rd.ecc = d_ecc.p + 64 * g0;
         rd.over_h = d_over.p + 64 * g0; rd.over_h2 = d_over.p + per_src + 64 * g0;
         const dim3 grid((unsigned)X, (unsigned)gb);
         int32_t last = 0;
-        GH_TRY_ST(gh_level_loop(h, n, d_flags.p, QUAL_HOP_CHECK_EVERY, &last, [&](int32_t L) -> gh_status {
+        GH_TRY_ST(gh_level_loop(h, n, f.flags.p, QUAL_HOP_CHECK_EVERY, &last, [&](int32_t L) -> gh_status {
             lv.level = rd.level = L;
-            lv.cur = (L & 1) ? d_fa.p : d_fb.p;
-            lv.nxt = (L & 1) ? d_fb.p : d_fa.p;
+            lv.cur = f.cur(L);
+            lv.nxt = f.nxt(L);
             if (staged) qual_hop_level_kernel<true><<<grid, dim3(QUAL_BLOCK), 0, h->stream>>>(lv);
             else qual_hop_level_kernel<false><<<grid, dim3(QUAL_BLOCK), 0, h->stream>>>(lv);
             GH_LAUNCH_CHECK();

@@ -89,6 +89,26 @@ def test_two_handles_and_two_calls_agree():
     assert _native.live_allocations() == start
 
 
+def test_hop_profile_and_cent_distances_share_one_search():
+    """gh_qual_hop_profile and gh_cent_distances run the same frontier step (csrc/frontier_core.h).  n = 130: a path of 66, a
+    star whose hub 66 has 62 leaves, and the isolated vertex 129; 65 sources -- two groups, the last one of one source --
+    with the hub twice and the isolated vertex.  The hop profile counts the pairs at hop >= 1, gh_cent_distances the source
+    too (tests/hops_reference.py, tests/graphstats_reference.py): reach = reached - 1, and the eccentricities are equal."""
+    n = 130
+    edges = np.array([(v, v + 1) for v in range(65)] + [(66, v) for v in range(67, 129)], dtype=np.int32)
+    src = np.r_[np.arange(0, 124, 2), 129, 66, 5]
+    assert len(src) == 65 and len(edges) == 65 + 62
+    hops = gr.hop_profile(cloud(n, 2), edges, sources=src, device_id=0)
+    g = _native.CentGraph(n, edges, 0)
+    reached, _, ecc = g.distances(src)
+    g.close()
+    assert hops["reach"].dtype == reached.dtype == np.int64 and hops["eccentricity"].dtype == ecc.dtype == np.int32
+    assert np.array_equal(hops["reach"], reached - 1) and np.array_equal(hops["eccentricity"], ecc)
+    on_path = src < 66
+    assert np.array_equal(reached[on_path], np.full(on_path.sum(), 66)) and np.array_equal(ecc[on_path], np.maximum(src, 65 - src)[on_path])
+    assert reached[62] == 1 and ecc[62] == 0 and reached[63] == reached[33] == 63 and ecc[63] == ecc[33] == 1 and src[33] == 66
+
+
 def live_engine(**kw):
     n = 300
     e = gr.random_regular_edges(n, 4, seed=3)
