@@ -74,8 +74,9 @@ def paths(n, edges, sources, batch=256):
     return bc, ld, reached, dsum
 
 
-def pagerank(n, edges, alpha=0.85, max_iter=100, tol=1e-6):
-    """networkx _pagerank_scipy restated: (x, iterations); iterations = -1 when max_iter iterations did not converge."""
+def pagerank(n, edges, alpha=0.85, max_iter=100, tol=1e-6, changes=None):
+    """networkx _pagerank_scipy restated: (x, iterations); iterations = -1 when max_iter iterations did not converge.
+    changes (a list) receives every iteration's L1 change, the number that is held against n tol."""
     A = adjacency(n, edges)
     S = np.asarray(A.sum(axis=1)).ravel()
     inv = np.zeros(n)
@@ -87,6 +88,9 @@ def pagerank(n, edges, alpha=0.85, max_iter=100, tol=1e-6):
     for it in range(1, max_iter + 1):
         xlast = x
         x = alpha * (x @ M + sum(x[dangling]) * p) + (1 - alpha) * p
-        if np.absolute(x - xlast).sum() < n * tol:
+        err = np.absolute(x - xlast).sum()
+        if changes is not None:
+            changes.append(float(err))
+        if err < n * tol:
             return x, it
     return x, -1

@@ -81,7 +81,15 @@ def _path5000():
     return G
 
 
+def _plc_gnp_caveman():
+    """The base that tests/tiled_graphs.py tiles to a million vertices: cores 0 .. 9 without 5 and 6, trusses 2 .. 9, 28
+    components and 5467 triangles on 2360 vertices and 7952 edges."""
+    return nx.disjoint_union_all([nx.powerlaw_cluster_graph(1000, 4, 0.3, seed=5), nx.gnp_random_graph(1000, 0.004, seed=1),
+                                  nx.relaxed_caveman_graph(30, 12, 0.15, seed=3)])
+
+
 GRAPHS = {
+    "plc_gnp_caveman": _plc_gnp_caveman,
     "path5000": _path5000,
     "lollipop": lambda: nx.lollipop_graph(40, 700),
     "wheel5001": gsr.TRIANGLE_GRAPHS["wheel5001"],
