@@ -35,6 +35,8 @@ EDGES_RANGE, EDGES_HASHED = 0, 1  # gh_partition.edge_rule (include/graphem_hip.
 
 
 SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphem_hip.h)
+COARSE_TAU = {"auto": 0, "off": 1, "on": 2}        # GH_COARSE_*
+COARSE_GROUPS = 64                                 # GH_CT_M (csrc/engine.h)
 LINK_KINDS = {"common_neighbors": 0, "jaccard": 1, "adamic_adar": 2, "resource_allocation": 3,
               "preferential_attachment": 4}  # GH_LINK_* (include/graphem_hip.h)
 LINK_MAX_K = 128
@@ -121,6 +123,9 @@ SIGNATURES = {
     "gh_set_cdist_replay": (_int, [vp, i32]),
     "gh_set_scan_filter": (_int, [vp, i32]),
     "gh_get_scan_filter": (_int, [vp, _P(i32)]),
+    "gh_set_coarse_tau": (_int, [vp, i32]),
+    "gh_get_coarse_tau": (_int, [vp, _P(i32)]),
+    "gh_debug_coarse_table": (_int, [vp, vp, i64]),
     "gh_qcell_probe": (_int, [vp, i32, vp, vp, vp, i64, vp, vp]),
     "gh_sampler_stats": (_int, [vp, vp]),
     "gh_overlap_layout": (_int, [vp, i32, i32, i64]),
@@ -556,6 +561,23 @@ class Engine(Handle):
         v = ctypes.c_int32(0)
         self._chk(self.lib.gh_get_scan_filter(self.handle, ctypes.byref(v)))
         return {b: a for a, b in SCAN_FILTERS.items()}[v.value]
+
+    def set_coarse_tau(self, mode):
+        """Thresholds of the query-cell filter: 'on' = from 64 coarse group minima inside the fused launch, 'off' = a launch
+        of their own, 'auto' (same results either way)."""
+        self._chk(self.lib.gh_set_coarse_tau(self.handle, COARSE_TAU[mode]))
+
+    def coarse_tau(self):
+        """True when the fused launch computes the thresholds itself from the coarse table."""
+        v = ctypes.c_int32(0)
+        self._chk(self.lib.gh_get_coarse_tau(self.handle, ctypes.byref(v)))
+        return bool(v.value)
+
+    def coarse_table(self):
+        """Both copies of the coarse table as (2, 64, sample_size) uint32 float bits; 0xFFFFFFFF = empty (diagnostic)."""
+        out = np.empty((2, COARSE_GROUPS, self.S), dtype=np.uint32)
+        self._chk(self.lib.gh_debug_coarse_table(self.handle, out.ctypes.data_as(ctypes.c_void_p), out.size))
+        return out
 
     def knn_ivf_config(self):
         """(lists, probes per query) of a knn_method='ivf' engine; (0, 0) otherwise."""

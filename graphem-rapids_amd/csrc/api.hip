@@ -102,6 +102,8 @@ struct create_switches {
     const char *reorder = nullptr;   // GRAPHEM_HIP_REORDER=1 | 2 overrides gh_params.reorder (tests / A-B runs: off, breadth-first)
     int tau_separate = -1;      // GRAPHEM_HIP_TAU_SEPARATE=1 | 0: thresholds in a launch of their own | in the fused one; -1: by size
     bool stamps = false;        // GRAPHEM_HIP_STAMPS: wall-clock stamps of the fused launch's workgroups
+    int coarse_tau = -1;        // GRAPHEM_HIP_COARSE_TAU=1 | 0: the query-cell launch takes its thresholds from coarse group minima | a
+                                // threshold launch of its own from the fine ones; -1: wherever the coarse form can serve
 };
 static create_switches read_switches() {
     create_switches sw;
@@ -109,6 +111,7 @@ static create_switches read_switches() {
     sw.reorder = getenv("GRAPHEM_HIP_REORDER");
     if (const char *e = getenv("GRAPHEM_HIP_TAU_SEPARATE")) sw.tau_separate = atoi(e) != 0;
     sw.stamps = getenv("GRAPHEM_HIP_STAMPS") != nullptr;
+    if (const char *e = getenv("GRAPHEM_HIP_COARSE_TAU")) sw.coarse_tau = atoi(e) != 0;
     return sw;
 }
 
@@ -199,6 +202,11 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_wait_failed, 1, true);
     GH_A(d_qcell, GH_QC_WORDS, true);
     GH_A(d_qc_flag, 1, true);
+    {   // the coarse table, every entry empty (also where AUTO does not take it: gh_set_scan_filter / gh_set_coarse_tau may)
+        const size_t words = gh_coarse_tau_ok(h) ? 2 * (size_t)GH_CT_M * S : 1;
+        GH_A(d_cmin, words, false);
+        GH_HIP(hipMemsetAsync(h->d_cmin.p, 0xFF, sizeof(uint32_t) * words, h->stream));
+    }
     if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
 #undef GH_A
     if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv.p, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -263,7 +271,8 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     // 64.9 -> 60.6 us).  A large graph gains nothing (1 M vertices: 175.7 -> 176.7 us, the first round of workgroups waits
     // ~3 us for producers that share their CUs with gathers) and keeps the launch of its own.
     h->tau_embedded_plan = sw.tau_separate >= 0 ? sw.tau_separate == 0 : h->n_vblocks <= 2048;
-    gh_choose_scan_filter(h);                 // (fused.hip) sets tau_embedded
+    h->coarse_mode = sw.coarse_tau < 0 ? GH_COARSE_AUTO : sw.coarse_tau ? GH_COARSE_ON : GH_COARSE_OFF;
+    gh_choose_scan_filter(h);                 // (fused.hip) sets tau_embedded and coarse_tau
 
     const gh_status st = allocate_and_upload(h, g, sw);
     if (st != GH_OK) return fail(st, h->err);
@@ -434,7 +443,8 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
     }
     if (h->fused_scan && gh_knn_scan_path(h)) {
         GH_TRY_ST(gh_knn_prepare(h));
-        if (!h->tau_embedded) GH_TRY_ST(gh_knn_thresholds(h));   // else: the first workgroups of the fused launch (tau_core.h)
+        // (else: the first workgroups of the fused launch, tau_core.h, or the first one of its query-cell form, qcell_core.h)
+        if (!h->tau_embedded && !h->coarse_tau) GH_TRY_ST(gh_knn_thresholds(h));
         GH_TRY_ST(gh_launch_spring_scan(h));
         return gh_knn_finish(h, false, fuse_intersect);
     }
@@ -558,10 +568,42 @@ extern "C" gh_status gh_set_scan_filter(gh_handle h, int32_t mode) {
         return GH_ERR_INVALID;
     }
     h->scan_filter = mode;
-    const bool was_embedded = h->tau_embedded;
+    const bool was_embedded = h->tau_embedded, was_coarse = h->coarse_tau;
     gh_choose_scan_filter(h);
-    // a set-up done ahead for the other threshold placement would not have zeroed the producers' counter: done again
-    if (h->tau_embedded != was_embedded) h->lookahead.valid = false;
+    // a set-up done ahead for the other threshold placement would not have zeroed the producers' counter, one for the other
+    // form of the group minima has left the wrong ones: done again
+    if (h->tau_embedded != was_embedded || h->coarse_tau != was_coarse) h->lookahead.valid = false;
+    return GH_OK;
+}
+
+extern "C" gh_status gh_set_coarse_tau(gh_handle h, int32_t mode) {
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_set_coarse_tau"));
+    if (mode != GH_COARSE_AUTO && mode != GH_COARSE_OFF && mode != GH_COARSE_ON) {
+        h->err = "gh_set_coarse_tau: mode must be GH_COARSE_AUTO, GH_COARSE_OFF or GH_COARSE_ON";
+        return GH_ERR_INVALID;
+    }
+    h->coarse_mode = mode;
+    const bool was_coarse = h->coarse_tau;
+    gh_choose_scan_filter(h);
+    if (h->coarse_tau != was_coarse) h->lookahead.valid = false;   // the set-up done ahead left the other form of the minima
+    return GH_OK;
+}
+extern "C" gh_status gh_get_coarse_tau(gh_handle h, int32_t *in_use) {
+    GH_TRY_ST(check_handle(h));
+    if (!in_use) { h->err = "in_use is NULL"; return GH_ERR_INVALID; }
+    *in_use = !h->f64 && h->coarse_tau ? 1 : 0;
+    return GH_OK;
+}
+extern "C" gh_status gh_debug_coarse_table(gh_handle h, uint32_t *out, int64_t count) {
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_debug_coarse_table"));
+    if (!out || count != 2 * (int64_t)GH_CT_M * h->S || !gh_coarse_tau_ok(h)) {
+        h->err = "gh_debug_coarse_table: needs an engine the coarse thresholds can serve and room for 2 * 64 * sample_size words";
+        return GH_ERR_INVALID;
+    }
+    GH_HIP(hipMemcpyAsync(out, h->d_cmin.p, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }
 

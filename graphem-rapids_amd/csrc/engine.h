@@ -22,6 +22,11 @@
 inline int gh_fix_blocks(int LD) { return LD <= 16 ? 2 * LD : 0; }
 // Below this many reference edges the per-query block kernel scans everything itself.
 #define GH_SCAN_MIN_EDGES 16384
+// Coarse form of the threshold group minima (setup_core.h "COARSE FORM"): groups per query, the value of an empty entry,
+// and the most keys a threshold may stand for (registers of the selecting thread, qcell_core.h gh_ct_tau).
+#define GH_CT_M 64
+#define GH_CT_EMPTY 0xFFFFFFFFu
+#define GH_CT_KMAX 32
 
 struct gh_timer_slot {
     std::string name;
@@ -232,6 +237,13 @@ struct gh_engine {
     gh_dev<unsigned> d_qc_flag;          // launch number whose table is complete
     unsigned qc_epoch = 0;               // number of the last launch on the query-cell path
     gh_dev<int32_t> d_wait_failed;       // a consumer gave up waiting: reported by gh_sync / gh_get_positions
+    // thresholds by workgroup 0 of the query-cell launch, from coarse group minima (setup_core.h "COARSE FORM")
+    int coarse_mode = 0;                 // GH_COARSE_AUTO | _OFF | _ON, as set by gh_set_coarse_tau / GRAPHEM_HIP_COARSE_TAU
+    bool coarse_tau = false;             // in use: no d_gmin, no knn_tau_kernel launch (gh_choose_scan_filter)
+    gh_dev<uint32_t> d_cmin;             // (2, GH_CT_M, S) float bits, GH_CT_EMPTY where no set-up workgroup has written: copy
+                                         // (iter & 1) is filled by the set-up of iteration iter and consumed, and reset, by its fused launch
+    bool cmin_dirty[2] = {false, false}; // a set-up has written the copy and no fused launch has consumed it yet (a set-up done
+                                         // ahead that turned out stale): the next set-up into it fills it with GH_CT_EMPTY first
 
 #define GH_STAMP_EXTRA 8192
     gh_dev<unsigned long long> d_stamps;      // GRAPHEM_HIP_STAMPS: (n_vblocks, 8) wall-clock stamps of the last fused launch
@@ -356,7 +368,9 @@ int gh_fused_mfma_kb(const gh_engine *h);          // operand rows the threshold
 bool gh_fused_uses_mfma(const gh_engine *h);       // the fused kernel's pre-filter runs on the matrix pipe
 int gh_fused_tile(const gh_engine *h);              // edges per fused workgroup
 bool gh_fused_cells_ok(const gh_engine *h);         // the query-cell pre-filter can serve this engine (fused.hip)
-void gh_choose_scan_filter(gh_engine *h);           // qcells and tau_embedded from scan_filter and tau_embedded_plan
+bool gh_coarse_tau_ok(const gh_engine *h);          // ... and its first workgroup can compute the thresholds (coarse form)
+gh_status gh_cmin_claim(gh_engine *h, uint64_t iter);   // before enqueueing a coarse set-up of iteration iter: its table copy is empty
+void gh_choose_scan_filter(gh_engine *h);           // qcells, tau_embedded and coarse_tau from scan_filter, tau_embedded_plan and coarse_mode
 gh_status gh_launch_spring_scan(gh_engine *h);             // d_Fs + final-level candidates in one kernel
 gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world);  // -> d_keys_cur
 // forces.hip

@@ -403,7 +403,8 @@ struct gh_norm_src {
 // STAGED: the rows of the set-up's queries come from sa.rows, staged by the stats_fix launch in front (setup_core.h); a
 // kernel of its own, so that neither form carries the other's address arithmetic (VGPRs at strides 4 / 8 / 16: 67 / 105 /
 // 127 staged, 68 / 105 / 128 gathering, 7 / 4 / 4 waves per SIMD either way).
-template <int LDT, bool STAGED>
+// COARSE: the set-up leaves the coarse form of the group minima (sa.cmin; setup_core.h), again a kernel of its own.
+template <int LDT, bool STAGED, bool COARSE = false>
 __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, int LD, int64_t n, float *__restrict__ pos,
                                                        double *__restrict__ acc /* null: no clean-up */,
                                                        int32_t *__restrict__ tflag,
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, 
             if (sa.tiles > 0) {
                 auto norm = [=](float x, int d) { return (x - ms[d]) / ms[LD + d]; };
                 if constexpr (!early_fetch) gh_setup_fetch<LDS_, STAGED>(sa, (int)blockIdx.x, raw_row, srows);
-                gh_setup_finish<LDS_, STAGED>(sa, (int)blockIdx.x, raw_row, norm, srows, setup_lds, stamps);
+                gh_setup_finish<LDS_, STAGED, COARSE>(sa, (int)blockIdx.x, raw_row, norm, srows, setup_lds, stamps);
             } else {
                 gh_setup_item(sa, t, getp);
             }
@@ -988,6 +989,7 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
         sa = gh_make_setup_args(h, *next, h->iter + 1);
         extra = gh_setup_blocks(sa);
         if (staged && sa.tiles > 0) sa.rows = h->d_setup_rows.p;
+        if (sa.cmin) GH_TRY_ST(gh_cmin_claim(h, h->iter + 1));
     }
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
     float *packed = stats_all && h->packed_exchange ? h->d_rows_packed.p + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
@@ -999,6 +1001,9 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
                 gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,
                 h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed);
         };
+        if constexpr (ld() == 4) {   // (the coarse form serves the query-cell path: up to 3 components)
+            if (sa.cmin) return sa.rows ? launch(normalise_kernel<4, true, true>) : launch(normalise_kernel<4, false, true>);
+        }
         if constexpr (ld() > 0) {
             if (sa.rows) return launch(normalise_kernel<ld(), true>);
         }

@@ -57,10 +57,29 @@ int gh_fused_mfma_kb(const gh_engine *h) { return h->fused_scan && !h->qcells ? 
 bool gh_fused_cells_ok(const gh_engine *h) {
     return h->fused_scan && fused_mfma(h->LD, h->D, h->S) && h->D <= 3 && h->S >= 1 && h->S <= GH_QC_SMAX;
 }
+// The first workgroup of the query-cell launch can take the thresholds from coarse group minima itself (setup_core.h
+// "COARSE FORM", qcell_core.h gh_ct_tau): a whole-graph engine with a threshold subset and at most GH_CT_KMAX keys to bound.
+bool gh_coarse_tau_ok(const gh_engine *h) {
+    return gh_fused_cells_ok(h) && h->thr_M1 > 0 && h->rows == h->n && h->Ksel <= GH_CT_KMAX;
+}
 void gh_choose_scan_filter(gh_engine *h) {
     const bool want = h->scan_filter == GH_FILTER_CELLS || (h->scan_filter == GH_FILTER_AUTO && !h->tau_embedded_plan);
     h->qcells = want && gh_fused_cells_ok(h);
-    h->tau_embedded = h->tau_embedded_plan && !h->qcells;   // the cell table is built from thresholds already in memory
+    h->tau_embedded = h->tau_embedded_plan && !h->qcells;   // the cell table is built from thresholds already in memory ...
+    // ... or from coarse group minima.  AUTO takes them where they were measured ahead -- three components, up to a dozen
+    // keys: rr1m 153.8 -> 149.9 us per iteration, er1m 191.2 -> 186.1, pp1m 182.6 -> 177.3 (NOTES.md "Coarse thresholds") --
+    // and leaves the two-dimensional and the 32-key kernels, whose smaller batches were not measured at scale, to a request
+    const bool want_coarse = h->coarse_mode == GH_COARSE_ON || (h->coarse_mode == GH_COARSE_AUTO && h->D == 3 && h->Ksel <= 12);
+    h->coarse_tau = h->qcells && want_coarse && gh_coarse_tau_ok(h);
+}
+// The copy of the coarse table that the set-up of iteration `iter` fills must be empty: it is, unless a set-up done ahead
+// was discarded (other ids, positions set, another threshold form in between) after it had written.
+gh_status gh_cmin_claim(gh_engine *h, uint64_t iter) {
+    const int p = (int)(iter & 1);
+    if (h->cmin_dirty[p])
+        GH_HIP(hipMemsetAsync(h->d_cmin.p + (size_t)p * GH_CT_M * (size_t)h->S, 0xFF, sizeof(uint32_t) * GH_CT_M * (size_t)h->S, h->stream));
+    h->cmin_dirty[p] = true;
+    return GH_OK;
 }
 int gh_fused_tile(const gh_engine *h) {
     int nt, r;
@@ -350,30 +369,70 @@ __global__ __launch_bounds__(256) void spring_scan_mfma_kernel(
 // -> 16.1; the gathers of phase A take 8.1 -> 9.1 us, with more workgroups in phase A at a time.  Kernel 129.5 -> 114.1
 // us.  88 VGPRs (77 for D = 2), 24.2 KB of LDS: five workgroups per CU, as for the MFMA form (91 VGPRs, 30 KB); six
 // would need 80 VGPRs, which the compiler reaches only by spilling (36 bytes per lane; not measured).
-template <int D>
+// KC > 0: no threshold launch has run.  Workgroup 0 first takes every query's tau from its coarse group minima (thread s:
+// gh_ct_tau<KC>, K <= KC keys; setup_core.h "COARSE FORM"), stores it into the query record for the launches behind this
+// one, builds the table from the records at hand and publishes the S records behind the table, under the same flag; the
+// other workgroups stage the records from there, after the poll, instead of from qt before it.
+template <int D, int KC>
 __global__ __launch_bounds__(256) void spring_scan_cells_kernel(
     const float *__restrict__ pos, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ adj,
     const int32_t *__restrict__ first_edge, const int32_t *__restrict__ own_eids,
     const int32_t *__restrict__ vblock, int64_t row_lo, float L_min, float neg_k, float *__restrict__ Fs,
-    float *__restrict__ out_new, double *__restrict__ blockstats, const float *__restrict__ qt, int S,
+    float *__restrict__ out_new, double *__restrict__ blockstats, float *__restrict__ qt, int S,
     uint32_t *__restrict__ qcell, unsigned *__restrict__ qc_flag, unsigned epoch, int32_t *__restrict__ wait_failed,
-    uint64_t *__restrict__ cand, int32_t *__restrict__ cnt, gh_long_args la, int cdist, unsigned long long *__restrict__ stamps) {
+    uint64_t *__restrict__ cand, int32_t *__restrict__ cnt, gh_long_args la, int cdist, unsigned long long *__restrict__ stamps,
+    uint32_t *__restrict__ cmin /* KC > 0: this iteration's copy of the coarse table */, int K,
+    int32_t *__restrict__ tcount_reset /* KC > 0: the touched-list counter to reset (the threshold launch did), or null */) {
     constexpr int LD = 4, NT = 256, R = 2, TILE = NT * R, HITBUF = 512;
     static_assert(D <= 3, "query records of one 16-byte load");
     __shared__ float4 tile[TILE];               // fp32 midpoints of the owned edges (x, y, z, 0)
     __shared__ float4 qrec[GH_QC_SMAX];         // (q_0, q_1, q_2, tau)
-    __shared__ uint32_t tab[GH_QC_WORDS];       // the cell table (qcell_core.h)
+    __shared__ uint32_t tab[GH_QC_TAB_WORDS];   // the cell table (qcell_core.h)
     __shared__ uint64_t hkey[HITBUF];
     __shared__ int hq[HITBUF];
     __shared__ uint32_t ids[TILE];
     __shared__ int hcount;
     if (blockIdx.x == 0) {   // the table of this launch (scratch counters in the hit buffer)
-        gh_qc_build<D, NT>(reinterpret_cast<const float4 *>(qt), S, tab, qrec, reinterpret_cast<uint32_t *>(hkey));
-        for (int i = threadIdx.x; i < GH_QC_WORDS; i += NT)
+        // diagnostic stamps of this workgroup: the last record of the buffer (start, thresholds, table built, flag set)
+        unsigned long long *st0 = stamps && threadIdx.x == 0 ? stamps + ((int64_t)gridDim.x - 1 + GH_STAMP_EXTRA - 1) * 8 : nullptr;
+        if (st0) st0[0] = wall_clock64();
+        float4 r = make_float4(0.f, 0.f, 0.f, -1.f);
+        if ((int)threadIdx.x < S) r = reinterpret_cast<const float4 *>(qt)[threadIdx.x];
+        unsigned long long *stb = st0 ? st0 - 8 : nullptr;   // (the record before: the stages of the table build)
+        if constexpr (KC > 0) {
+            // up to a dozen keys in three dimensions the batch is the whole row -- one memory round trip (qcell_core.h) -- at 90
+            // VGPRs instead of 88, still five workgroups per CU; the two-dimensional kernel would go from 77 to 88 and from
+            // six to five, the 32-key one past its budget too
+            constexpr int B = KC <= 12 ? (D == 3 ? GH_CT_M : 16) : (D == 3 ? 8 : 4);
+            // first of all: this workgroup starts before the gathers of the others fill the memory system's queues
+            if (threadIdx.x == 0 && tcount_reset) *tcount_reset = 0;
+            if ((int)threadIdx.x < S) {
+                r.w = gh_ct_tau<KC, B>(cmin, threadIdx.x, (uint32_t)S, K);
+                qt[threadIdx.x * 4 + 3] = r.w;   // read by the launches behind this one (cdist.hip)
+            }
+            if (st0) st0[1] = wall_clock64();
+            gh_qc_frame<D, NT>(r, S, tab, qrec, reinterpret_cast<uint32_t *>(hkey), stb);
+            gh_qc_fill<D, NT>(r, S, tab, qrec, reinterpret_cast<uint32_t *>(hkey), stb);
+        } else {
+            if (st0) st0[1] = wall_clock64();
+            gh_qc_build<D, NT>(r, S, tab, qrec, reinterpret_cast<uint32_t *>(hkey), stb);
+        }
+        if (st0) st0[2] = wall_clock64();
+        for (int i = threadIdx.x; i < GH_QC_TAB_WORDS; i += NT)
             __hip_atomic_store(qcell + i, tab[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (KC > 0) {
+            if ((int)threadIdx.x < S) {
+                uint32_t *dst = qcell + GH_QC_OFF_REC + 4 * threadIdx.x;
+                __hip_atomic_store(dst + 0, __float_as_uint(r.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst + 1, __float_as_uint(r.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst + 2, __float_as_uint(r.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst + 3, __float_as_uint(r.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's write-through stores have left ...
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(qc_flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the flag
+        if (st0) st0[3] = wall_clock64();
         return;
     }
     const int nbx = (int)gridDim.x - 1;
@@ -394,15 +453,19 @@ __global__ __launch_bounds__(256) void spring_scan_cells_kernel(
     // and the barrier in gh_block_stats publishes it.  A workgroup whose rows take every wave stages after phase A.
     const int t_idle = min(NT, (v1 - v0 + 63) / 64 * 64);   // first thread of the first wave without rows
     auto stage = [&](int t0) {   // by threads t0 .. NT - 1
-        for (int i = (int)threadIdx.x - t0; i < S; i += NT - t0) qrec[i] = reinterpret_cast<const float4 *>(qt)[i];
+        if constexpr (KC == 0)
+            for (int i = (int)threadIdx.x - t0; i < S; i += NT - t0) qrec[i] = reinterpret_cast<const float4 *>(qt)[i];
         unsigned spins = 0;
         while ((int)(__hip_atomic_load(qc_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0) {
             __builtin_amdgcn_s_sleep(32);
             if (++spins > (1u << 20)) { *wait_failed = 1; break; }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // orders the loads below after the poll; no cache invalidate
-        for (int i = (int)threadIdx.x - t0; i < GH_QC_WORDS / 4; i += NT - t0)
+        for (int i = (int)threadIdx.x - t0; i < GH_QC_TAB_WORDS / 4; i += NT - t0)
             reinterpret_cast<float4 *>(tab)[i] = gh_ld_f4(reinterpret_cast<const float4 *>(qcell) + i, true);
+        if constexpr (KC > 0)   // the records with this launch's thresholds, published behind the table
+            for (int i = (int)threadIdx.x - t0; i < S; i += NT - t0)
+                qrec[i] = gh_ld_f4(reinterpret_cast<const float4 *>(qcell + GH_QC_OFF_REC) + i, true);
     };
     if (t_idle < NT && (int)threadIdx.x >= t_idle) stage(t_idle);
 
@@ -746,13 +809,26 @@ void launch_mfma_d(gh_engine *h) {
         -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, reinterpret_cast<const gh_h8 *>(h->d_qA.p),
         h->d_qexact.p, (int)h->S, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), ta, h->d_stamps.p);
 }
-template <int D>
-void launch_cells(gh_engine *h) {
+template <int D, int KC>
+void launch_cells_k(gh_engine *h) {
     if (++h->qc_epoch == 0) h->qc_epoch = 1;   // (0 is the flag's value before the first launch)
-    spring_scan_cells_kernel<D><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
+    const int p = (int)(h->iter & 1);   // the copy this iteration's set-up filled (gh_make_setup_args)
+    spring_scan_cells_kernel<D, KC><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
         h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min,
         -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, (int)h->S, h->d_qcell.p, h->d_qc_flag.p, h->qc_epoch,
-        h->d_wait_failed.p, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps.p);
+        h->d_wait_failed.p, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps.p,
+        KC > 0 ? h->d_cmin.p + (size_t)p * GH_CT_M * (size_t)h->S : nullptr, h->Ksel,
+        KC > 0 && h->tcount_reset_pending ? h->d_tcount.p : nullptr);
+    if (KC > 0) h->cmin_dirty[p] = false;   // consumed, and reset entry by entry
+}
+// The thresholds: in memory (a launch of their own has run), or taken by workgroup 0 from the coarse table -- the usual
+// dozen keys in as many registers per thread, up to GH_CT_KMAX in a kernel of its own.
+template <int D>
+void launch_cells(gh_engine *h) {
+    static_assert(GH_CT_KMAX == 32, "the instantiations below");
+    if (!h->coarse_tau) launch_cells_k<D, 0>(h);
+    else if (h->Ksel <= 12) launch_cells_k<D, 12>(h);
+    else launch_cells_k<D, 32>(h);
 }
 template <int D, int R>
 void launch_mfma(gh_engine *h) {

@@ -36,13 +36,16 @@ namespace {
 // One launch sets a KNN search up from the CURRENT positions (setup_core.h): sample ids, query
 // records, list reset and -- on the scan path, a.tiles > 0 -- the group minima of the threshold
 // subset.  (In a run the same work rides in the previous iteration's normalise launch instead.)
+// COARSE: the coarse form of the group minima (a.cmin; row stride 4, a.tiles > 0), a kernel of its own.
+template <bool COARSE>
 __global__ __launch_bounds__(256) void knn_setup_kernel(const float *__restrict__ pos, gh_setup_args a,
                                                        int32_t *__restrict__ tcount, int32_t *__restrict__ qexact) {
     __shared__ __align__(16) unsigned char lds[GH_SETUP_LDS_BYTES];
     if (blockIdx.x == 0 && threadIdx.x == 0) { *tcount = 0; qexact[0] = 0; }  // the previous iteration's normalise kernel has consumed it
     const int LD = a.LD;
     auto getp = [=](int64_t v, int d) { return pos[v * LD + d]; };
-    if (a.tiles > 0) gh_setup_block_any(a, (int)blockIdx.x, getp, lds);
+    if constexpr (COARSE) gh_setup_block<4, true>(a, (int)blockIdx.x, getp, lds);
+    else if (a.tiles > 0) gh_setup_block_any(a, (int)blockIdx.x, getp, lds);
     else gh_setup_item(a, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, getp);
 }
 
@@ -574,7 +577,9 @@ gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter) 
     return gh_setup_args{h->d_edges.p, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q.p, h->d_cnt.p,
                          h->d_ovf.p, h->part.edge_lo, h->d_own_eids.p, reinterpret_cast<const int2 *>(h->d_sub_uv.p), h->thr_M1, h->thr_stride, h->d_gmin.p,
                          (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag.p : nullptr,
-                         nullptr /* rows: only a normalise launch behind a gathering stats_fix launch reads staged rows (forces.hip) */};
+                         nullptr /* rows: only a normalise launch behind a gathering stats_fix launch reads staged rows (forces.hip) */,
+                         // the coarse form: copy iter & 1 of the table (the launcher calls gh_cmin_claim first)
+                         h->coarse_tau && tiles > 0 ? h->d_cmin.p + (size_t)(iter & 1) * GH_CT_M * (size_t)h->S : nullptr};
 }
 
 // Workgroups of 256 threads a set-up takes (knn_setup_kernel, or the head of a normalise launch).
@@ -598,8 +603,10 @@ gh_status gh_knn_prepare(gh_engine *h) {
     h->tcount_reset_pending = done;  // the stand-alone kernel resets d_tcount; else the threshold kernel does
     if (done) return GH_OK;
     const gh_setup_args a = gh_make_setup_args(h, src, h->iter);
+    if (a.cmin) GH_TRY_ST(gh_cmin_claim(h, h->iter));
     gh_scope t(h, "knn_setup");
-    knn_setup_kernel<<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos.p, a, h->d_tcount.p, h->d_qexact.p);
+    if (a.cmin) knn_setup_kernel<true><<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos.p, a, h->d_tcount.p, h->d_qexact.p);
+    else knn_setup_kernel<false><<<dim3(gh_setup_blocks(a)), dim3(256), 0, h->stream>>>(h->d_pos.p, a, h->d_tcount.p, h->d_qexact.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }

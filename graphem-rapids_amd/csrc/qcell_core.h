@@ -33,6 +33,7 @@
 // a box (two per query, one of returning atomics) published the table so late that a tenth of the workgroups waited
 // ~10 us for it (tools/stamp_probe.py).
 #include "common.h"
+#include "engine.h"   // GH_CT_M
 
 #define GH_QC_G 8                                 // cells per axis
 #define GH_QC_CAP 27                              // cells a query's box may cover before it goes on the wide list
@@ -46,10 +47,14 @@
 #define GH_QC_OFF_PTR 28                          // GH_QC_CELLS + 1 uint16 offsets into the entries
 #define GH_QC_OFF_ENT 288                         // GH_QC_ENT uint8 query indices, by cell
 #define GH_QC_OFF_WIDE (GH_QC_OFF_ENT + GH_QC_ENT / 4)                 // GH_QC_SMAX uint8 query indices
-#define GH_QC_WORDS (GH_QC_OFF_WIDE + GH_QC_SMAX / 4)                  // 864 words = 216 x 16 bytes
+#define GH_QC_TAB_WORDS (GH_QC_OFF_WIDE + GH_QC_SMAX / 4)              // 864 words = 216 x 16 bytes: the table proper
+// behind the table in the device buffer (not in a workgroup's LDS copy of it): the S query records (x, y, z|0, tau) that
+// workgroup 0 publishes with it when it computes the thresholds itself (gh_ct_tau)
+#define GH_QC_OFF_REC GH_QC_TAB_WORDS
+#define GH_QC_WORDS (GH_QC_OFF_REC + 4 * GH_QC_SMAX)
 static_assert(GH_QC_OFF_B + 3 * 8 <= GH_QC_OFF_PTR, "blob layout");
 static_assert(GH_QC_OFF_PTR + (GH_QC_CELLS + 2) / 2 <= GH_QC_OFF_ENT, "blob layout");
-static_assert(GH_QC_WORDS % 4 == 0, "the blob moves in 16-byte pieces");
+static_assert(GH_QC_TAB_WORDS % 4 == 0 && GH_QC_WORDS % 4 == 0, "the blob moves in 16-byte pieces");
 
 __host__ __device__ inline int gh_qc_axis_cell(const float *b, float x) {
     int c = 0;
@@ -93,19 +98,72 @@ __device__ __forceinline__ uint32_t gh_qc_block_scan(uint32_t v, uint32_t *wsum 
     return base + incl - v;
 }
 
-// Built by ONE workgroup of NT >= 256 threads (the first of the fused launch) from the query records qt (x, y, z|0, tau),
-// S <= GH_QC_SMAX, in the LDS blob `tab`; scratch: 4 KB of records, GH_QC_CELLS counters.  Ends with the blob complete
-// in `tab` (after a barrier).
+// tau of one query from its GH_CT_M coarse group minima (setup_core.h "COARSE FORM"), by ONE thread: the K-th smallest of
+// them AS A MULTISET (copies count, see gh_tau_kth), K <= KC, kept as KC ascending registers that every value is passed
+// through (a min and a max per register and value).  Fewer than K occupied groups: +inf -- the query goes on the wide list
+// and, should its candidate list overflow, to the exact fallback.  The loads are independent of one another and plain (the
+// launch in front wrote the table); the consumed entries are reset for the set-up after the next.
+// The values pass in batches of B in a loop that is NOT unrolled, the loads of a batch issued while the batch before it is
+// sorted in; B is the caller's: what its register budget allows (fused.hip).  Written without the loop, the compiler keeps
+// every ADDRESS in registers too (160 - 250 VGPRs for the fused kernel: three or two workgroups per CU instead of five, for
+// the sake of the launch's first one).
+// Measured on rr1m (tools/stamp_probe.py, workgroup 0 of the fused launch, which shares its CU with four gathering
+// workgroups): B = 16: 6.0 us, B = 64: 3.8 - 4.2 us.  Not faster, each tried on top of B = 64: the first batch fetched before
+// the cell frame and sorted in behind it (5.3 us behind a 3 us frame), one v_med3_u32 per register and value instead of
+// min + max, reading the lower neighbour's old value so that no step waits for another (5.2 - 6.3 us), the same in a loop
+// over slices of 8 registers, for its code size (5.9 - 7.8 us), s_setprio 3 (4.9 us with the median form).
+template <int KC, int B /* values per batch */>
+__device__ __forceinline__ float gh_ct_tau(uint32_t *cmin, uint32_t q /* the query */, uint32_t S, int K) {
+    static_assert(GH_CT_M % B == 0, "whole batches");
+    uint32_t a[KC], cur[B], nxt[B];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) a[i] = 0x7F800000u;
+#pragma unroll
+    for (int j = 0; j < B; ++j) cur[j] = cmin[q + (uint32_t)j * S];
+#pragma unroll 1
+    for (uint32_t b = 0; b < GH_CT_M / B; ++b) {
+        uint32_t *row = cmin + q + b * B * S;   // (entry j of this batch; the next batch starts B rows on)
+        if (b + 1 < GH_CT_M / B) {
+#pragma unroll
+            for (int j = 0; j < B; ++j) nxt[j] = row[(uint32_t)(B + j) * S];
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) row[(uint32_t)j * S] = GH_CT_EMPTY;
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            uint32_t x = cur[j];   // (an empty entry, 0xFFFFFFFF, or the bits of a NaN: sinks through, every register stays <= +inf)
+#pragma unroll
+            for (int i = 0; i < KC; ++i) {
+                const uint32_t lo = min(a[i], x);
+                x = max(a[i], x);
+                a[i] = lo;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) cur[j] = nxt[j];
+    }
+    uint32_t kth = 0x7F800000u;   // K > KC cannot be (the launcher checks): +inf all the same
+#pragma unroll
+    for (int i = 0; i < KC; ++i) kth = i == K - 1 ? a[i] : kth;
+    return __uint_as_float(kth);
+}
+
+// Built by ONE workgroup of NT >= 256 threads (the first of the fused launch) from the query records (x, y, z|0, tau) --
+// thread t < S hands in record t -- S <= GH_QC_SMAX, in the LDS blob `tab`; scratch: 4 KB of records, GH_QC_CELLS
+// counters.  Ends with the blob complete in `tab` and the records in `rec` (after a barrier).
+// Two halves: gh_qc_frame -- records to LDS, the cell frame -- needs the coordinates only; gh_qc_fill, which takes the
+// thresholds (r.w), does the rest.
 template <int D, int NT>
-__device__ __forceinline__ void gh_qc_build(const float4 *__restrict__ qt, int S, uint32_t *tab, float4 *rec, uint32_t *cnt) {
+__device__ __forceinline__ void gh_qc_frame(float4 r, int S, uint32_t *tab, float4 *rec, uint32_t *cnt,
+                                            unsigned long long *st = nullptr /* diagnostic: thread 0's stamps of the stages */) {
     static_assert(NT >= GH_QC_SMAX, "one query per thread");
     constexpr int NC = D == 3 ? GH_QC_CELLS : GH_QC_G * GH_QC_G;
     const int t = threadIdx.x;
-    float4 r = make_float4(0.f, 0.f, 0.f, -1.f);
-    if (t < S) { r = qt[t]; rec[t] = r; }
+    if (t < S) rec[t] = r;
     for (int c = t; c < NC; c += NT) cnt[c] = 0;
     if (t == 0) tab[GH_QC_OFF_NWIDE] = 0;
     __syncthreads();
+    if (st) st[0] = wall_clock64();
     // boundaries: wave d < D ranks an evenly spaced sample of the coordinates of axis d (ties by lane), lane of rank
     // floor(i * n / G) supplies boundary i - 1
     float *bnd = reinterpret_cast<float *>(tab + GH_QC_OFF_B);
@@ -116,8 +174,11 @@ __device__ __forceinline__ void gh_qc_build(const float4 *__restrict__ qt, int S
         const float x = w == 0 ? sr.x : w == 1 ? sr.y : sr.z;
         const uint32_t u = __float_as_uint(x);
         const uint32_t key = lane < n ? ((u & 0x80000000u) ? ~u : (u | 0x80000000u)) : 0xFFFFFFFFu;   // total order
+        // (all GH_QC_SAMPLE lanes, unrolled: the lanes past n hold the largest key and are never counted by a lane below n;
+        // a loop over the first n with the lane in a register took 3.8 us of this workgroup's critical path)
         int rank = 0;
-        for (int p = 0; p < n; ++p) {
+#pragma unroll
+        for (int p = 0; p < GH_QC_SAMPLE; ++p) {
             const uint32_t kp = (uint32_t)__builtin_amdgcn_readlane((int)key, p);
             rank += (kp < key || (kp == key && p < lane)) ? 1 : 0;
         }
@@ -128,6 +189,15 @@ __device__ __forceinline__ void gh_qc_build(const float4 *__restrict__ qt, int S
         }
     }
     __syncthreads();
+    if (st) st[1] = wall_clock64();
+}
+template <int D, int NT>
+__device__ __forceinline__ void gh_qc_fill(float4 r, int S, uint32_t *tab, float4 *rec, uint32_t *cnt, unsigned long long *st = nullptr) {
+    constexpr int NC = D == 3 ? GH_QC_CELLS : GH_QC_G * GH_QC_G;
+    const int t = threadIdx.x;
+    if (t < S) rec[t].w = r.w;   // (own slot; nobody reads a threshold from LDS before the barriers below)
+    else r = make_float4(0.f, 0.f, 0.f, -1.f);
+    const float *bnd = reinterpret_cast<const float *>(tab + GH_QC_OFF_B);
     // boxes: counted per cell, or the query goes on the wide list
     __shared__ uint32_t wsum[NT / 64];
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
@@ -152,14 +222,25 @@ __device__ __forceinline__ void gh_qc_build(const float4 *__restrict__ qt, int S
         listed = listed && before + (uint32_t)ncell <= GH_QC_ENT;
     }
     if (t < S && !listed) wide[atomicAdd(&tab[GH_QC_OFF_NWIDE], 1u)] = (uint8_t)t;
+    if (st) st[2] = wall_clock64();
+    // The cells of a box, x fastest, by three counters.  (The k-th cell by division -- k % wx, (k / wx) % wy, k / (wx wy),
+    // four integer divisions per cell and loop -- made the build 10.4 us of this workgroup's 11.5: unnoticed while the
+    // thresholds came from a launch of their own and the table was ready before the first workgroups asked for it.)
     const int wx = hi[0] - lo[0] + 1, wy = hi[1] - lo[1] + 1;
-    auto cell_of = [&](int k) {   // k-th cell of the box, k < ncell (x fastest)
-        const int x = k % wx, y = (k / wx) % wy, z = k / (wx * wy);
-        return (lo[0] + x) + GH_QC_G * ((lo[1] + y) + GH_QC_G * (lo[2] + z));
+    struct box_walk {
+        int x = 0, y = 0, z = 0;
+        __device__ __forceinline__ int next(const int (&lo)[3], int wx, int wy) {   // the current cell; moves on
+            const int c = (lo[0] + x) + GH_QC_G * ((lo[1] + y) + GH_QC_G * (lo[2] + z));
+            if (++x == wx) { x = 0; if (++y == wy) { y = 0; ++z; } }
+            return c;
+        }
     };
-    if (listed)
-        for (int k = 0; k < ncell; ++k) atomicAdd(&cnt[cell_of(k)], 1u);   // (no return value: nothing to wait for)
+    if (listed) {
+        box_walk wk;
+        for (int k = 0; k < ncell; ++k) atomicAdd(&cnt[wk.next(lo, wx, wy)], 1u);   // (no return value: nothing to wait for)
+    }
     __syncthreads();
+    if (st) st[3] = wall_clock64();
     // offsets: exclusive sum of the counters (thread t owns cells 2t, 2t + 1; NC <= 2 NT), then cnt = fill cursors
     uint16_t *ptr = reinterpret_cast<uint16_t *>(tab + GH_QC_OFF_PTR);
     {
@@ -172,16 +253,27 @@ __device__ __forceinline__ void gh_qc_build(const float4 *__restrict__ qt, int S
         if (t == 0) ptr[NC] = (uint16_t)total;
     }
     __syncthreads();
+    if (st) st[4] = wall_clock64();
     uint8_t *ent = reinterpret_cast<uint8_t *>(tab + GH_QC_OFF_ENT);
     // four returning atomics in flight at a time (the loops over a box are what made the table late at a cap of 64)
-    if (listed)
+    if (listed) {
+        box_walk wk;
         for (int k0 = 0; k0 < ncell; k0 += 4) {
             uint32_t at[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) at[u] = k0 + u < ncell ? atomicAdd(&cnt[cell_of(k0 + u)], 1u) : 0u;
+            for (int u = 0; u < 4; ++u) {
+                const int c = wk.next(lo, wx, wy);   // (past the box's last cell: not used)
+                at[u] = k0 + u < ncell ? atomicAdd(&cnt[c], 1u) : 0u;
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if (k0 + u < ncell) ent[at[u]] = (uint8_t)t;
         }
+    }
     __syncthreads();
+}
+template <int D, int NT>
+__device__ __forceinline__ void gh_qc_build(float4 r, int S, uint32_t *tab, float4 *rec, uint32_t *cnt, unsigned long long *st = nullptr) {
+    gh_qc_frame<D, NT>(r, S, tab, rec, cnt, st);
+    gh_qc_fill<D, NT>(r, S, tab, rec, cnt, st);
 }

@@ -42,11 +42,23 @@ struct gh_setup_args {
     int tiles;               // ceil(M1 / 256): workgroups of gh_setup_block
     unsigned *tau_flag;      // thresholds inside the fused launch (tau_core.h): the published-queries counter, zeroed here
     const float *rows;       // (2 S, LD) raw endpoint rows of the queries, staged by gh_setup_gather beside stats_fix, or null
+    uint32_t *cmin;          // coarse form (below): this iteration's copy of the coarse table, (GH_CT_M, S) float bits; null: gmin
 };
 
 #define GH_THR_TILE 128    /* subset edges per set-up workgroup */
 #define GH_THR_GSIZE 64    /* subset edges per group */
 #define GH_THR_GROUPS (GH_THR_TILE / GH_THR_GSIZE)   /* group minima per tile and query */
+
+// COARSE FORM of the group minima (the query-cell path of the fused kernel, thresholds not embedded: fused.hip).  tau only
+// has to be an upper bound of the K-th distance, so the groups may be as coarse as one likes: with GH_CT_M groups in all --
+// workgroup b of n belongs to group b * GH_CT_M / n -- a set-up workgroup reduces each query's distances to ONE minimum over
+// its whole tile and folds it into cmin[group][query] with a relaxed no-return atomic min on the float bits (non-negative
+// floats order like unsigned integers).  64 values per query are then a job for one thread: workgroup 0 of the fused launch
+// takes their K-th smallest itself (gh_ct_tau, qcell_core.h) and the threshold launch is gone.  The K-th smallest of M group
+// minima has expected subset rank ln(1 - K/M) / ln(1 - 1/M): 12.0 instead of 11.06 at K = 11, i.e. ~9 % more candidates.
+// An empty entry is 0xFFFFFFFF (above every float; a reader takes anything >= 0x7F800000 for +inf): the table is filled
+// with it at creation and the fused launch that consumes a copy resets it.  Two copies, chosen by iteration parity.
+// (GH_CT_M, GH_CT_EMPTY: engine.h)
 
 // Sample id, query record and list reset of query t (every query exactly once per iteration).
 template <class P /* float(int64_t vertex, int d) */>
@@ -177,7 +189,8 @@ __device__ __forceinline__ void gh_setup_gather(const gh_setup_args &a, const gh
     gh_store_row<LD>(g.rows, r, row);
 }
 
-template <int LD, bool STAGED, class RAW, class NORM /* float(float raw value, int d) */>
+template <int LD, bool STAGED, bool COARSE = false /* one minimum per tile into a.cmin instead of group minima into a.gmin */,
+          class RAW, class NORM /* float(float raw value, int d) */>
 __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk, RAW raw, NORM norm, const gh_setup_rows<LD> &st,
                                                 unsigned char *lds, unsigned long long *stamps = nullptr /* diagnostic */) {
     // the tile in LDS as PAIRS of subset edges, component-interleaved: pair p, coordinate d -> (m_2p[d], m_2p+1[d]),
@@ -236,7 +249,7 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
             a.cnt[s * GH_CNT_STRIDE] = 0;
             a.ovf[s] = 0;
         }
-        uint32_t *dst = reinterpret_cast<uint32_t *>(a.gmin) + s * a.Gpad + (int64_t)blk * GH_THR_GROUPS;
+        [[maybe_unused]] uint32_t *dst = reinterpret_cast<uint32_t *>(a.gmin) + s * a.Gpad + (int64_t)blk * GH_THR_GROUPS;
         // a few pairs in flight per lane only: fully unrolled, the compiler hoists every LDS read of the tile
         // (512 registers and scratch spills, which also cost the normalising workgroups of the same kernel their occupancy)
         constexpr int UNR = LD == 4 ? 4 : LD == 8 ? 4 : 2;  // (LD = 4: 8 in flight ran the distance loop ~1 us faster, at 90 VGPRs for the whole normalise launch instead of 58)
@@ -262,7 +275,13 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
             mn[gg] = best;
         }
         static_assert(GH_THR_GROUPS == 2 || GH_THR_GROUPS % 4 == 0, "vector stores of the group minima");
-        if constexpr (GH_THR_GROUPS == 2) {
+        if constexpr (COARSE) {
+            uint32_t all = mn[0];
+#pragma unroll
+            for (int gg = 1; gg < GH_THR_GROUPS; ++gg) all = min(all, mn[gg]);
+            const int64_t g = (int64_t)blk * GH_CT_M / a.tiles;   // consecutive lanes, consecutive words of one group's row
+            (void)__hip_atomic_fetch_min(a.cmin + g * a.S + s, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if constexpr (GH_THR_GROUPS == 2) {
             *reinterpret_cast<uint2 *>(dst) = make_uint2(mn[0], mn[1]);
         } else {
 #pragma unroll
@@ -273,7 +292,7 @@ __device__ __forceinline__ void gh_setup_finish(const gh_setup_args &a, int blk,
 }
 
 // Both halves at once, positions read through getp(vertex, d) (knn_setup_kernel).
-template <int LD, class P>
+template <int LD, bool COARSE = false, class P>
 __device__ __forceinline__ void gh_setup_block(const gh_setup_args &a, int blk, P getp, unsigned char *lds,
                                                unsigned long long *stamps = nullptr /* diagnostic */) {
     auto raw = [&](int64_t v, float (&row)[LD]) {
@@ -283,7 +302,7 @@ __device__ __forceinline__ void gh_setup_block(const gh_setup_args &a, int blk, 
     auto norm = [](float x, int) { return x; };
     gh_setup_rows<LD> st;
     gh_setup_fetch<LD, false>(a, blk, raw, st);
-    gh_setup_finish<LD, false>(a, blk, raw, norm, st, lds, stamps);
+    gh_setup_finish<LD, false, COARSE>(a, blk, raw, norm, st, lds, stamps);
 }
 
 // Runtime row stride -> the instantiation (the scan path has LD in {4, 8, 16}).

@@ -362,6 +362,7 @@ gh_status gh_timing_get(gh_handle h, int32_t i, const char **name, double *total
 /* Environment variables the library reads -- diagnostics only, all of them at gh_create, none needed in production:
  *   GRAPHEM_HIP_TAU_SEPARATE=1|0  thresholds always in a launch of their own / always by the first workgroups of the fused
  *                                 launch (default: inside for <= 2048 fused workgroups);
+ *   GRAPHEM_HIP_COARSE_TAU=1|0    GH_COARSE_ON | GH_COARSE_OFF instead of GH_COARSE_AUTO (gh_set_coarse_tau);
  *   GRAPHEM_HIP_NO_PRESETUP=1     the next iteration's KNN set-up as a launch of its own instead of inside the normalise
  *                                 launch (the per-query flags of gh_knn_last_counts then survive a step);
  *   GRAPHEM_HIP_REORDER=1|2       overrides gh_params.reorder (1 off, 2 breadth-first);
@@ -406,6 +407,22 @@ gh_status gh_set_cdist_replay(gh_handle h, int32_t all_ties);
 #define GH_FILTER_CELLS 2
 gh_status gh_set_scan_filter(gh_handle h, int32_t mode);
 gh_status gh_get_scan_filter(gh_handle h, int32_t *mode);
+/* Where the thresholds of a GH_FILTER_CELLS engine come from (whole-graph engines, n_neighbors + 1 -- + 2 with
+ * GH_DIST_CDIST -- up to 32; results are the same bit for bit either way):
+ *   GH_COARSE_ON    the set-up reduces each query's subset distances to 64 coarse group minima and the first workgroup
+ *                   of the fused launch takes their K-th smallest itself: no threshold launch.  Also on graphs that AUTO
+ *                   would give embedded thresholds, once gh_set_scan_filter(GH_FILTER_CELLS) is in force.
+ *   GH_COARSE_OFF   group minima of 64 subset edges and a threshold launch of their own.
+ *   GH_COARSE_AUTO  (default; GRAPHEM_HIP_COARSE_TAU=1|0 at creation sets ON | OFF) ON for three components and up to 12 keys,
+ *                   where it was measured ahead (1 M vertices: 153.8 -> 149.9 us per iteration), else OFF.
+ * Forcing ON where it cannot serve is not an error: gh_get_coarse_tau reports what is in use, 1 or 0. */
+#define GH_COARSE_AUTO 0
+#define GH_COARSE_OFF 1
+#define GH_COARSE_ON 2
+gh_status gh_set_coarse_tau(gh_handle h, int32_t mode);
+gh_status gh_get_coarse_tau(gh_handle h, int32_t *in_use);
+/* Both copies of the coarse table, (2, 64, sample_size) float bits, 0xFFFFFFFF = empty (diagnostic; count words).  Blocking. */
+gh_status gh_debug_coarse_table(gh_handle h, uint32_t *out, int64_t count);
 /* Host copy of the query-cell box (test support): for each of n (q, tau, m) triples of D <= 3 coordinates -- boundaries
  * (D, 7) per axis -- writes the fp32 chain d2(q, m) of the exact test to d2[i], and per axis the cell of m and q's box
  * [lo, hi] to cells[(i * D + d) * 3 + {0, 1, 2}]. */

@@ -43,6 +43,20 @@ for i in idx:
 if not embedded:
     print("  rows per workgroup: median", np.median(t[:, 6]), "max", t[:, 6].max(), "; owned edges median", np.median(t[:, 7]))
 
+# ---- the first round of workgroups (five per CU start at once) and the table they wait for (query-cell form)
+first = t[:5 * 256]
+for a, b, nm in ((1, 2, "block sums + barrier (idle waves stage the table inside it)"), (2, 3, "staging after the barrier")):
+    d = (first[:, b] - first[:, a]) / 100.0
+    print("  first round, %-60s median %5.2f us  p90 %5.2f  max %5.2f" % (nm, np.median(d), np.quantile(d, 0.9), d.max()))
+wg0 = norm[-1]   # the last record of the buffer: the launch's first workgroup, which builds the table
+if not embedded and wg0[0] > 0 and wg0[3] > 0:
+    sb = norm[-2]   # the record before it: the stages of the table build
+    print("  workgroup 0: starts %.2f us after the first stamp, flag set %.2f us after it" % ((wg0[0] - t0) / 100.0, (wg0[3] - t0) / 100.0))
+    for nm, a, b in (("thresholds from the coarse table", wg0[0], wg0[1]), ("records to LDS", wg0[1], sb[0]), ("cell frame (boundaries)", sb[0], sb[1]),
+                     ("boxes, wide list", sb[1], sb[2]), ("cell counts", sb[2], sb[3]), ("offsets", sb[3], sb[4]), ("entries", sb[4], wg0[2]),
+                     ("stores, wait, flag", wg0[2], wg0[3])):
+        print("    %-34s %5.2f us" % (nm, (b - a) / 100.0))
+
 # ---- the normalise launch that followed: set-up workgroups (next iteration's queries and group minima) first
 for kind, nm in ((1, "set-up"), (2, "normalising")):
     w = norm[norm[:, 6] == kind]
@@ -63,7 +77,7 @@ for kind, nm in ((1, "set-up"), (2, "normalising")):
 # ---- thresholds inside the fused launch (tau_core.h): the producers' stamps sit in the last records of the buffer
 prod = norm[-64:]
 prod = prod[prod[:, 0] > 0]
-if len(prod):
+if embedded and len(prod):
     names2 = ["group minima loaded", "K-th smallest", "records stored (issued)", "stores acknowledged", "counter moved"]
     print("threshold producers: %d workgroups, start %.1f us after the first workgroup, counter complete at %.1f us" % (
         len(prod), (prod[:, 0].min() - t0) / 100.0, (prod[:, 5].max() - t0) / 100.0))
