@@ -130,11 +130,10 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_mid, (size_t)h->own_count * h->LD, true);
     GH_A(d_Fs, (size_t)h->rows * h->LD, true);
     // candidate lists and the threshold subset exist only for the filtered scan (64 KiB per query)
-    const bool scan_path = gh_knn_scan_path(h);
     GH_A(d_gmin, (size_t)gh_gmin_floats(h), true);
-    GH_A(d_sub_uv, (size_t)h->thr_M1 * 2, false);
+    GH_A(d_sub_uv, (size_t)h->plan.thr_M1 * 2, false);
     // (a whole-graph engine's stats_fix launch stages the rows of the next set-up's queries: forces.hip)
-    if (h->thr_M1 > 0 && h->rows == n) GH_A(d_setup_rows, 2 * S * h->LD, true);
+    if (h->plan.stage_rows) GH_A(d_setup_rows, 2 * S * h->LD, true);
     if (hashed) GH_A(d_own_eids, g.own_eids.size() + 1, true);
     if (h->nlong) {
         GH_A(d_long_rows, g.long_rows.size(), false);
@@ -161,7 +160,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_qscan, S * (size_t)(h->LD + 4), true);
     GH_A(d_qA, S * 16, true);
     GH_A(d_qexact, S + 1, true);
-    if ((st = gh_alloc(h, h->d_cand, scan_path ? S * GH_CAND_CAP : 1, false)) != GH_OK) {
+    if ((st = gh_alloc(h, h->d_cand, h->plan.lists() ? S * GH_CAND_CAP : 1, false)) != GH_OK) {
         h->err = "hipMalloc of the KNN candidate lists failed: sample_size = " + std::to_string(h->S) + " needs " +
                  std::to_string((S * GH_CAND_CAP * sizeof(uint64_t)) >> 20) + " MiB (128 KiB per sampled midpoint)";
         return st;
@@ -203,13 +202,13 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_qcell, GH_QC_WORDS, true);
     GH_A(d_qc_flag, 1, true);
     {   // the coarse table, every entry empty (also where AUTO does not take it: gh_set_scan_filter / gh_set_coarse_tau may)
-        const size_t words = gh_coarse_tau_ok(h) ? 2 * (size_t)GH_CT_M * S : 1;
+        const size_t words = h->plan.coarse_ok ? 2 * (size_t)GH_CT_M * S : 1;
         GH_A(d_cmin, words, false);
         GH_HIP(hipMemsetAsync(h->d_cmin.p, 0xFF, sizeof(uint32_t) * words, h->stream));
     }
     if (sw.stamps) GH_A(d_stamps, ((size_t)std::max(h->n_vblocks, 1) + GH_STAMP_EXTRA) * 8, true);
 #undef GH_A
-    if (h->thr_M1 > 0 && hipMemcpy(h->d_sub_uv.p, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (h->plan.thr_M1 > 0 && hipMemcpy(h->d_sub_uv.p, g.sub_uv.data(), sizeof(int32_t) * g.sub_uv.size(), hipMemcpyHostToDevice) != hipSuccess) {
         h->err = "upload of the threshold subset failed";
         return GH_ERR_HIP;
     }
@@ -259,20 +258,15 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     h->stream = h->own_stream;
     h->pos_rows = n + GH_POS_PAD_ROWS;
     const create_switches sw = read_switches();
-    h->opt_no_presetup = sw.no_presetup;
+    h->requests.no_presetup = sw.no_presetup;
+    h->requests.tau_place = sw.tau_separate < 0 ? GH_TAU_BY_SIZE : sw.tau_separate ? GH_TAU_SEPARATE : GH_TAU_EMBEDDED;
+    h->requests.coarse_mode = sw.coarse_tau < 0 ? GH_COARSE_AUTO : sw.coarse_tau ? GH_COARSE_ON : GH_COARSE_OFF;
 
     gh_graph_plan g;   // vertex order, ownership, pull lists, owned edges, fused blocks (graph_plan.hip)
     gh_plan_graph(h, edges, part != nullptr, sw.reorder ? atoi(sw.reorder) : params->reorder, &g);
     if (auto_method) gh_auto_knn_method(h);   // on the edges this engine searches: known only now
-    gh_choose_threshold_subset(h);            // (knn.hip) the method, own_count, fused_scan, Ksel and S are final here
+    gh_replan(h);                             // (step_plan.h) the method, own_count, fused_scan, Ksel and S are final here
     gh_plan_threshold_subset(h, &g);
-    // Thresholds by the first workgroups of the fused launch (tau_core.h) where that launch is a single round of
-    // workgroups or little more: there the iteration is a chain of launch latencies and this removes one (100 K vertices:
-    // 64.9 -> 60.6 us).  A large graph gains nothing (1 M vertices: 175.7 -> 176.7 us, the first round of workgroups waits
-    // ~3 us for producers that share their CUs with gathers) and keeps the launch of its own.
-    h->tau_embedded_plan = sw.tau_separate >= 0 ? sw.tau_separate == 0 : h->n_vblocks <= 2048;
-    h->coarse_mode = sw.coarse_tau < 0 ? GH_COARSE_AUTO : sw.coarse_tau ? GH_COARSE_ON : GH_COARSE_OFF;
-    gh_choose_scan_filter(h);                 // (fused.hip) sets tau_embedded and coarse_tau
 
     const gh_status st = allocate_and_upload(h, g, sw);
     if (st != GH_OK) return fail(st, h->err);
@@ -313,29 +307,52 @@ static gh_status download_padded(gh_engine *h, const float *d_src, float *host) 
     return GH_OK;
 }
 
-// A workgroup of a fused launch gave up waiting for that launch's thresholds (tau_core.h): whatever was computed since
-// is not to be trusted.  Cannot happen while workgroups are started in index order; checked where the host synchronises.
+static gh_plan_input plan_input_of(const gh_engine *h) {
+    gh_plan_input in;
+    in.n = h->n; in.rows = h->rows; in.E = h->E; in.own_count = h->own_count; in.S = h->S;
+    in.D = h->D; in.LD = h->LD; in.k = h->k; in.K = h->K; in.Ksel = h->Ksel;
+    in.knn_method = h->prm.knn_method;
+    in.cdist = h->cdist; in.cd_part = h->cd_part;
+    in.fused_scan = h->fused_scan; in.n_vblocks = h->n_vblocks;
+    in.layout = h->layout;
+    return in;
+}
+void gh_replan(gh_engine *h) {
+    const gh_tau_form was = h->plan.tau;
+    h->plan = gh_make_step_plan(plan_input_of(h), h->requests);
+    // a set-up done ahead for the other threshold placement would not have zeroed the producers' counter, one for the other
+    // form of the group minima has left the wrong ones: done again
+    if (h->plan.tau != was) gh_drop_lookahead(h);
+}
+
+// A workgroup of a fused launch gave up waiting for that launch's thresholds (tau_core.h) or query-cell table (fused.hip):
+// whatever was computed since is not to be trusted.  Cannot happen while workgroups are started in index order; checked
+// where the host synchronises.
 static gh_status check_device_waits(gh_engine *h) {
-    if (!(h->tau_embedded || h->qcells) || !h->d_wait_failed.p) return GH_OK;
+    const bool cells = h->plan.prefilter == GH_PRE_CELLS;
+    if (h->plan.search != GH_SEARCH_FUSED || !(h->plan.tau == GH_TAUF_EMBEDDED || cells) || !h->d_wait_failed.p) return GH_OK;
     int32_t failed = 0;
     GH_HIP(hipMemcpyAsync(&failed, h->d_wait_failed.p, sizeof(failed), hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipStreamSynchronize(h->stream));
     if (failed) {
-        // reported once: the flag is cleared and the engine goes on with the thresholds as a launch of their own (no
-        // workgroup waits for another any more)
+        // reported once: the flag is cleared and the engine goes on without the form whose wait failed.  A failed table wait
+        // leaves the split-f16 filter, with the thresholds wherever the creation-time placement puts them (inside the fused
+        // launch on small graphs: its first workgroups are waited for).  A failed threshold wait leaves a threshold launch
+        // of its own, and with the filter on AUTO that brings the query-cell table with it -- whose workgroups wait for the
+        // launch's first one -- exactly the state GRAPHEM_HIP_TAU_SEPARATE=1 creates (NOTES.md "Recovery after a failed wait").
+        // Either way whatever was set up ahead is dropped: the caller has to set the positions again.
         GH_HIP(hipMemsetAsync(h->d_wait_failed.p, 0, sizeof(int32_t), h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
-        if (h->qcells) {   // the wait was for the query-cell table (fused.hip): back to the split-f16 filter
-            h->scan_filter = GH_FILTER_MFMA;
-            gh_choose_scan_filter(h);
-            h->lookahead.valid = false;
+        if (cells) h->requests.scan_filter = GH_FILTER_MFMA;
+        else h->requests.tau_place = GH_TAU_SEPARATE;
+        gh_replan(h);
+        gh_drop_lookahead(h);
+        if (cells) {
             h->err = "a workgroup of the fused spring+scan launch timed out waiting for the query-cell table of its own "
                      "launch; results since the last successful gh_sync / gh_get_positions are invalid -- set the positions "
                      "again.  The engine now uses the split-f16 pre-filter (GH_FILTER_MFMA); please report this";
             return GH_ERR_RUNTIME;
         }
-        h->tau_embedded_plan = false;
-        gh_choose_scan_filter(h);
         h->err = "a workgroup of the fused spring+scan launch timed out waiting for the thresholds of its own launch; "
                  "results since the last successful gh_sync / gh_get_positions are invalid -- set the positions again. "
                  "The engine now computes the thresholds in a launch of their own (as GRAPHEM_HIP_TAU_SEPARATE=1 does); "
@@ -409,44 +426,42 @@ static gh_status caller_ids(gh_engine *h, const int32_t *host_ids, gh_ids *src) 
 // fuse_intersect: single-rank step, the KNN kernels also run the intersection phase.
 static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect);
 static gh_status step_begin(gh_engine *h, bool fuse_intersect) {
-    h->rows_early = false;
+    gh_step_reset(h);
     GH_TRY_ST(step_begin_launches(h, fuse_intersect));
     // form D: new0 = pos + Fs of the own rows is in their block -- written by the fused kernel, or (a rank too small for it;
     // every rank must send at the same point of the iteration) by a launch of its own -- and may travel now
     if (h->layout == GH_LAYOUT_OVERLAP) {
-        if (!h->new0_ready) GH_TRY_ST(gh_launch_new0(h));
-        h->rows_early = true;
+        if (!h->step.new0_ready) GH_TRY_ST(gh_launch_new0(h));
+        gh_step_set_rows_early(h, true);
     }
     return GH_OK;
 }
 static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
-    h->intersect_done = false;
-    h->stats_reduced = false;
-    h->new0_ready = false;
-    if (h->S == 0 || h->k == 0) {  // nothing sampled / no neighbours asked for: spring forces only
+    switch (h->plan.search) {
+    case GH_SEARCH_NONE:   // nothing sampled / no neighbours asked for: spring forces only
         h->sample.mode = GH_IDS_GIVEN;
-        h->intersect_done = true;
+        gh_step_intersect_done(h);
         GH_HIP(hipMemsetAsync(h->d_tcount.p, 0, sizeof(int32_t), h->stream));
         return gh_launch_spring_mid(h);
-    }
-    if (gh_grid_path(h)) {  // sub-quadratic search: thresholds, own midpoints to memory, grid build + cell search
+    case GH_SEARCH_GRID:   // sub-quadratic search: thresholds, own midpoints to memory, grid build + cell search
         GH_TRY_ST(gh_knn_prepare(h));          // query records only: the thresholds come from the grid itself
         GH_TRY_ST(gh_launch_spring_mid(h));
         GH_TRY_ST(gh_grid_search(h));
         return gh_knn_finish(h, true, fuse_intersect);
-    }
-    if (gh_ivf_path(h)) {   // inverted-file search (approximate: probed lists only; ivf.hip)
+    case GH_SEARCH_IVF:    // inverted-file search (approximate: probed lists only; ivf.hip)
         GH_TRY_ST(gh_knn_prepare(h));          // query records only
         GH_TRY_ST(gh_launch_spring_mid(h));
         GH_TRY_ST(gh_ivf_search(h));
         return gh_knn_finish(h, true, fuse_intersect);
-    }
-    if (h->fused_scan && gh_knn_scan_path(h)) {
+    case GH_SEARCH_FUSED:
         GH_TRY_ST(gh_knn_prepare(h));
         // (else: the first workgroups of the fused launch, tau_core.h, or the first one of its query-cell form, qcell_core.h)
-        if (!h->tau_embedded && !h->coarse_tau) GH_TRY_ST(gh_knn_thresholds(h));
+        if (h->plan.tau == GH_TAUF_LAUNCH) GH_TRY_ST(gh_knn_thresholds(h));
         GH_TRY_ST(gh_launch_spring_scan(h));
         return gh_knn_finish(h, false, fuse_intersect);
+    case GH_SEARCH_SCAN:
+    case GH_SEARCH_BLOCK:
+        break;
     }
     GH_TRY_ST(gh_launch_spring_mid(h));
     return gh_knn_local(h, fuse_intersect);
@@ -454,8 +469,8 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
 
 // next: the ids step_finish will set the next iteration up from (presetup_ids), when the caller knows them by now.
 static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world, const gh_ids *next = nullptr) {
-    GH_TRY_ST(gh_knn_merge(h, gathered, world));
-    if (!h->intersect_done) GH_TRY_ST(gh_launch_intersect(h));
+    GH_TRY_ST(gh_knn_merge(h, gathered, world, !h->step.intersect_done));
+    if (!h->step.intersect_done) GH_TRY_ST(gh_launch_intersect(h));
     GH_TRY_ST(gh_launch_integrate(h, next));
     return GH_OK;
 }
@@ -464,9 +479,7 @@ static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world, c
 // then also runs that iteration's KNN set-up (gh_launch_normalise); gh_knn_prepare falls back to its own kernel when the
 // next step turns out different.  presetup_ids: `next` where that applies, else null.
 static const gh_ids *presetup_ids(const gh_engine *h, const gh_ids *next) {
-    const bool presetup = next && h->rows == h->n && h->layout != GH_LAYOUT_GATHERED && gh_knn_scan_path(h) &&
-                          (h->fused_scan || gh_grid_path(h) || gh_ivf_path(h)) && h->S > 0 && h->k > 0 && !h->opt_no_presetup;
-    return presetup ? next : nullptr;
+    return h->plan.presetup ? next : nullptr;
 }
 static gh_status step_finish(gh_engine *h, const gh_ids *next) {
     GH_TRY_ST(gh_launch_normalise(h, true, presetup_ids(h, next)));  // also zeroes what the intersection phase touched
@@ -562,17 +575,13 @@ extern "C" gh_status gh_set_scan_filter(gh_handle h, int32_t mode) {
         h->err = "gh_set_scan_filter: mode must be GH_FILTER_AUTO, GH_FILTER_MFMA or GH_FILTER_CELLS";
         return GH_ERR_INVALID;
     }
-    if (mode == GH_FILTER_CELLS && !gh_fused_cells_ok(h)) {
+    if (mode == GH_FILTER_CELLS && !h->plan.cells_ok) {
         h->err = "gh_set_scan_filter: the query-cell filter needs a fused engine with n_components <= 3 and 1 <= sample_size <= " +
                  std::to_string(GH_QC_SMAX);
         return GH_ERR_INVALID;
     }
-    h->scan_filter = mode;
-    const bool was_embedded = h->tau_embedded, was_coarse = h->coarse_tau;
-    gh_choose_scan_filter(h);
-    // a set-up done ahead for the other threshold placement would not have zeroed the producers' counter, one for the other
-    // form of the group minima has left the wrong ones: done again
-    if (h->tau_embedded != was_embedded || h->coarse_tau != was_coarse) h->lookahead.valid = false;
+    h->requests.scan_filter = mode;
+    gh_replan(h);
     return GH_OK;
 }
 
@@ -583,22 +592,20 @@ extern "C" gh_status gh_set_coarse_tau(gh_handle h, int32_t mode) {
         h->err = "gh_set_coarse_tau: mode must be GH_COARSE_AUTO, GH_COARSE_OFF or GH_COARSE_ON";
         return GH_ERR_INVALID;
     }
-    h->coarse_mode = mode;
-    const bool was_coarse = h->coarse_tau;
-    gh_choose_scan_filter(h);
-    if (h->coarse_tau != was_coarse) h->lookahead.valid = false;   // the set-up done ahead left the other form of the minima
+    h->requests.coarse_mode = mode;
+    gh_replan(h);
     return GH_OK;
 }
 extern "C" gh_status gh_get_coarse_tau(gh_handle h, int32_t *in_use) {
     GH_TRY_ST(check_handle(h));
     if (!in_use) { h->err = "in_use is NULL"; return GH_ERR_INVALID; }
-    *in_use = !h->f64 && h->coarse_tau ? 1 : 0;
+    *in_use = !h->f64 && h->plan.tau == GH_TAUF_COARSE ? 1 : 0;
     return GH_OK;
 }
 extern "C" gh_status gh_debug_coarse_table(gh_handle h, uint32_t *out, int64_t count) {
     GH_TRY_ST(check_handle(h));
     GH_TRY_ST(reject_f64(h, "gh_debug_coarse_table"));
-    if (!out || count != 2 * (int64_t)GH_CT_M * h->S || !gh_coarse_tau_ok(h)) {
+    if (!out || count != 2 * (int64_t)GH_CT_M * h->S || !h->plan.coarse_ok) {
         h->err = "gh_debug_coarse_table: needs an engine the coarse thresholds can serve and room for 2 * 64 * sample_size words";
         return GH_ERR_INVALID;
     }
@@ -610,7 +617,8 @@ extern "C" gh_status gh_debug_coarse_table(gh_handle h, uint32_t *out, int64_t c
 extern "C" gh_status gh_get_scan_filter(gh_handle h, int32_t *mode) {
     GH_TRY_ST(check_handle(h));
     if (!mode) { h->err = "mode is NULL"; return GH_ERR_INVALID; }
-    *mode = h->f64 || !gh_fused_uses_mfma(h) || h->D > 3 ? GH_FILTER_AUTO : h->qcells ? GH_FILTER_CELLS : GH_FILTER_MFMA;
+    const gh_prefilter f = h->f64 ? GH_PRE_NONE : h->plan.prefilter;
+    *mode = f == GH_PRE_CELLS ? GH_FILTER_CELLS : f == GH_PRE_SPLIT_F16 ? GH_FILTER_MFMA : GH_FILTER_AUTO;
     return GH_OK;
 }
 
@@ -789,7 +797,7 @@ extern "C" gh_status gh_step_begin(gh_handle h, const int32_t *sampled) {
     GH_TRY_ST(check_handle(h));
     GH_TRY_ST(reject_f64(h, "gh_step_begin"));
     GH_TRY_ST(check_k(h));
-    h->last_step_own_ids = sampled == nullptr;
+    gh_step_own_ids(h, sampled == nullptr);
     GH_TRY_ST(caller_ids(h, sampled, &h->sample));
     return step_begin(h, false);
 }
@@ -797,7 +805,7 @@ extern "C" gh_status gh_step_begin(gh_handle h, const int32_t *sampled) {
 // engine draws them itself, identically on every rank (comm.hip gh_run_partitioned).
 gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids) {
     GH_TRY_ST(check_k(h));
-    h->last_step_own_ids = dev_ids == nullptr;
+    gh_step_own_ids(h, dev_ids == nullptr);
     h->sample = dev_ids ? gh_ids{GH_IDS_GIVEN, dev_ids} : gh_own_ids(h);   // (gh_upload_sample_stream gives none when S >= E)
     return step_begin(h, false);
 }
@@ -852,6 +860,7 @@ extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, 
     h->d_stats = reinterpret_cast<double *>(h->d_gbuf.p + rank * slot + chunk * h->LD * (int64_t)sizeof(float));
     h->g_slot = slot; h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
     h->layout = GH_LAYOUT_GATHERED;
+    gh_replan(h);
     return GH_OK;
 }
 extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
@@ -863,6 +872,7 @@ extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, in
     }
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
     h->layout = GH_LAYOUT_RANK;
+    gh_replan(h);
     return GH_OK;
 }
 // Form D: form B's finish (every rank normalises all n rows from the gathered un-normalised rows) with the big collective
@@ -884,13 +894,14 @@ extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank,
     h->d_stats = h->d_stats_all.p + (size_t)rank * (size_t)h->stats_block;
     h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
     h->layout = GH_LAYOUT_OVERLAP;
+    gh_replan(h);
     return GH_OK;
 }
 extern "C" float *gh_rows_all_device(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? nullptr : h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p; }
 extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? 0 : h->d_rows_pk.p ? h->D : h->LD; }
 extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->d_stats_all.p : nullptr; }
 extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->stats_block : 0; }
-extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP && h->rows_early ? 1 : 0; }
+extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP && h->step.rows_early ? 1 : 0; }
 extern "C" gh_status gh_step_pack_rows(gh_handle h, void *hip_stream, int32_t use_engine_stream) {
     GH_TRY_ST(check_handle(h));
     if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
@@ -902,8 +913,8 @@ extern "C" gh_status gh_step_finish_overlap(gh_handle h) {
     GH_TRY_ST(gh_launch_patch_rows(h));
     const gh_ids own = gh_own_ids(h);
     // (the patch launch has zeroed the accumulators of a step whose rows went early)
-    GH_TRY_ST(gh_launch_normalise(h, !h->rows_early, h->last_step_own_ids ? &own : nullptr, true));
-    h->rows_early = false;
+    GH_TRY_ST(gh_launch_normalise(h, !h->step.rows_early, h->step.own_ids ? &own : nullptr, true));
+    gh_step_set_rows_early(h, false);
     h->iter += 1;
     return GH_OK;
 }
@@ -936,7 +947,7 @@ extern "C" gh_status gh_step_finish_gathered(gh_handle h) {
     if (h->layout != GH_LAYOUT_GATHERED) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
     // a rank that drew this step's ids on the device will do so again: prepare them in the same launch
     const gh_ids own = gh_own_ids(h);
-    GH_TRY_ST(gh_launch_normalise(h, true, h->last_step_own_ids ? &own : nullptr, true));
+    GH_TRY_ST(gh_launch_normalise(h, true, h->step.own_ids ? &own : nullptr, true));
     h->iter += 1;
     return GH_OK;
 }
@@ -982,9 +993,7 @@ extern "C" gh_status gh_knn_midpoints(gh_handle h, const int32_t *sampled, int32
     GH_TRY_ST(step_begin(h, false));  // the same kernels a step runs (spring forces are a by-product)
     const uint64_t *d_keys = h->d_partial.p;
     if (h->cd_part) {   // a GH_DIST_CDIST engine created with a (whole-graph) partition: its rows are decided at the merge
-        h->intersect_done = true;   // (no intersection phase here)
-        GH_TRY_ST(gh_knn_merge(h, h->d_partial.p, 1));
-        h->intersect_done = false;
+        GH_TRY_ST(gh_knn_merge(h, h->d_partial.p, 1, false));   // (no intersection phase here)
         d_keys = h->d_merged.p;
     }
     std::vector<uint64_t> keys((size_t)h->S * h->K);
@@ -1101,7 +1110,7 @@ extern "C" gh_status gh_knn_cdist_stats(gh_handle h, int32_t *full_pass_rows, in
         GH_HIP(hipMemcpyAsync(&rare, hdr, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         GH_HIP(hipMemcpyAsync(&stat, hdr + 1, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         GH_HIP(hipStreamSynchronize(h->stream));
-        if (!gh_knn_scan_path(h)) rare = (int32_t)h->S;   // a graph too small for the filtered scan: every row
+        if (!h->plan.lists()) rare = (int32_t)h->S;   // a graph too small for the filtered scan: every row
     }
     if (full_pass_rows) *full_pass_rows = rare;
     if (unresolved_tie_rows) *unresolved_tie_rows = stat;

@@ -1179,15 +1179,13 @@ static gh_status cdist_replay_rounds(gh_engine *h, const cdist_args &a, const cd
 // all_rows: the graph is too small for the filtered scan -- every query is replayed over all edges.  Otherwise the
 // candidate lists of the scan are in place.  -> d_partial (S, K): the reference's rows, column 0 included.
 // fuse_intersect (single-rank steps, K <= 64): the same launches run the intersection phase of every query they finish
-// and reduce the fused kernel's column sums (h->intersect_done / h->stats_reduced tell the caller).
+// and reduce the fused kernel's column sums (gh_step_intersect_done / gh_step_stats_reduced tell the caller).
 // A row-partitioned engine (h->cd_part) stops after its own candidates: -> d_partial (S, K + 2): this rank's K + 1 best cdist
 // keys of every query and 1 where they are provably its K + 1 best; gh_knn_merge_cdist finishes after the ranks' all-gather.
 gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) {
     const cdist_args a = make_cdist_args(h);
     if (h->cd_part && all_rows) {   // too few own edges for the scan: nothing proven, every row is replayed after the merge
         GH_HIP(hipMemsetAsync(h->d_partial.p, 0xFF, sizeof(uint64_t) * (size_t)h->S * (h->K + 2), h->stream));
-        h->intersect_done = false;
-        h->stats_reduced = false;
         return GH_OK;
     }
     const int set = h->cd_part ? h->cd_set ^ 1 : h->cd_set;   // (a partitioned engine's search takes its counter set at the merge)
@@ -1197,7 +1195,7 @@ gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) 
     bool reduce = false;
     if (!all_rows) {
         // the column sums of the fused kernel's workgroup partials ride along (stats_fix_kernel then skips them)
-        reduce = h->new0_ready && h->rows > 0 && h->LD <= 16 && h->S < 2048;
+        reduce = gh_sums_ride_along(h->plan, h->step);
         gh_scope t(h, fuse ? "knn_select_cdist_intersect" : "knn_select_cdist");
         const inter_args ia = make_inter_args(h, fuse);
         const int part_mode = h->cd_part ? 1 : 0;
@@ -1205,27 +1203,27 @@ gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect) 
                 knn_select_cdist_kernel<d()><<<dim3((unsigned)h->S + (reduce ? 2u * (unsigned)h->LD : 0u)), dim3(256), 0, h->stream>>>(
                     h->d_cand.p, h->d_cnt.p, h->K, a, h->d_partial.p, h->d_ovf.p, h->d_dbg_cnt.p + h->S, rr, ia, (int)h->S, h->d_blockstats.p,
                     h->n_vblocks, h->d_stats, part_mode, (fuse && !h->cd_all_ties) ? 1 : 0);
-            })) {   // (the candidate lists come from the scan path, which gh_knn_scan_path opens for these dimensions only)
+            })) {   // (the candidate lists come from the scan path, which gh_plan_built opens for these dimensions only)
             h->err = "GH_DIST_CDIST: the candidate selection needs 2..16 components";
             return GH_ERR_RUNTIME;
         }
         GH_LAUNCH_CHECK();
     }
     if (!h->cd_part) GH_TRY_ST(cdist_replay_rounds(h, a, rr, all_rows, fuse, h->d_partial.p));
-    h->intersect_done = fuse;
-    h->stats_reduced = reduce;
+    if (fuse) gh_step_intersect_done(h);
+    if (reduce) gh_step_stats_reduced(h);
     return GH_OK;
 }
 
 // Row partitions, after the all-gather of the ranks' keys: gathered (world, S, K + 2) -> d_merged (S, K), the reference's rows
 // (knn_merge_cdist_kernel; the listed rows replayed over all edges), with the intersection phase of every query when
-// K <= 64 and 2..16 components (h->intersect_done).
-gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) {
+// with_intersect, K <= 64 and 2..16 components (gh_step_intersect_done).
+gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world, bool with_intersect) {
     const cdist_args a = make_cdist_args(h);
     const int set = h->cd_set;
     h->cd_set ^= 1;
     const cdist_rows rr{h->d_rare.p, h->d_cd_rows.p, h->d_cd_rows.p + h->S, h->d_cd_stat.p + 4 * set, h->d_cd_stat.p + 4 * (set ^ 1)};
-    const bool fuse = !h->intersect_done && h->K <= 64 && gh_dim_templated(h->D);
+    const bool fuse = with_intersect && h->K <= 64 && gh_dim_templated(h->D);
     const int total = world * (h->K + 1);
     int n2 = 2;
     while (n2 < total) n2 <<= 1;
@@ -1247,6 +1245,6 @@ gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world) 
     }
     GH_TRY_ST(cdist_replay_rounds(h, a, rr, false, fuse, h->d_merged.p));
     h->d_keys_cur = h->d_merged.p;
-    if (fuse) h->intersect_done = true;
+    if (fuse) gh_step_intersect_done(h);
     return GH_OK;
 }

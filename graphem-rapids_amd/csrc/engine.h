@@ -8,6 +8,7 @@
 
 #include "../../include/graphem_hip.h"
 #include "host_util.h"   // GH_HIP, GH_TRY_ST, GH_LAUNCH_CHECK
+#include "step_plan.h"   // gh_step_plan, gh_step_state and the sizes the choice of path depends on
 
 // Candidate-list capacity per query in the filtered KNN scan, and the LDS sort size.
 #define GH_CAND_CAP 16384   /* (8192 until round 3: one query of a 16 M-vertex run reached 8777 candidates and its exhaustive fallback cost 0.5 s) */
@@ -20,13 +21,10 @@
 #define GH_POS_PAD_ROWS 1024
 // Row pairs of corrections behind the (2, LD) column statistics: one per stats_fix workgroup.
 inline int gh_fix_blocks(int LD) { return LD <= 16 ? 2 * LD : 0; }
-// Below this many reference edges the per-query block kernel scans everything itself.
-#define GH_SCAN_MIN_EDGES 16384
-// Coarse form of the threshold group minima (setup_core.h "COARSE FORM"): groups per query, the value of an empty entry,
-// and the most keys a threshold may stand for (registers of the selecting thread, qcell_core.h gh_ct_tau).
+// Coarse form of the threshold group minima (setup_core.h "COARSE FORM"): groups per query and the value of an empty entry
+// (the most keys a threshold may stand for, GH_CT_KMAX, is in step_plan.h).
 #define GH_CT_M 64
 #define GH_CT_EMPTY 0xFFFFFFFFu
-#define GH_CT_KMAX 32
 
 struct gh_timer_slot {
     std::string name;
@@ -41,10 +39,6 @@ struct gh_ids {
     int mode;       // GH_IDS_GIVEN: the ids are at `ids`; GH_IDS_SAMPLER / GH_IDS_ARANGE: produced into `ids` (d_sampled)
     int32_t *ids;   // a view (mutable: the set-up writes the ids it draws)
 };
-
-// How a partitioned engine finishes a step (include/graphem_hip.h): set by gh_gather_layout (form B), gh_rank_layout
-// (form C), gh_overlap_layout (form D).
-enum { GH_LAYOUT_NONE = 0, GH_LAYOUT_GATHERED, GH_LAYOUT_RANK, GH_LAYOUT_OVERLAP };
 
 // Parts of the engine whose types are complete only in their own translation units: each defines its gh_delete there.
 struct gh_comm;   // comm.hip: collective backend of the native partitioned loop
@@ -121,10 +115,8 @@ struct gh_engine {
     gh_dev<float> d_Fs;           // (rows, LD) spring forces of the own rows
     gh_dev<float> d_gmin;         // (S, Gpad) group minima of the threshold subset (setup_core.h), float bits
     gh_dev<int32_t> d_sub_uv;     // (thr_M1, 2) endpoints of the subset edges
-    int64_t thr_stride = 0, thr_M1 = 0;  // the subset: every thr_stride-th own edge, thr_M1 of them (gh_choose_threshold_subset)
     gh_dev<int32_t> d_vblock;     // (n_vblocks + 1) vertex ranges of the fused spring+scan workgroups
     int n_vblocks = 0;
-    bool opt_no_presetup = false; // GRAPHEM_HIP_NO_PRESETUP (read at gh_create)
     bool fused_scan = false;      // fused spring+scan kernel usable for this graph / partition
 
     // state
@@ -149,20 +141,19 @@ struct gh_engine {
     size_t stream_ids_cap = 0;
     gh_ring ring;                     // gh_run_torch_sampled
     double sampler_stats[4] = {0, 0, 0, 0};   // last gh_run_torch_sampled, host ms: producer drawing, caller waiting for a pinned slot, caller waiting for ids, the call
-    bool new0_ready = false;      // the fused kernel of this step wrote d_new = pos + Fs and its block sums
-    bool intersect_done = false;  // the KNN kernels of this step already ran the intersection phase
-    bool stats_reduced = false;   // ... and reduced the fused kernel's workgroup sums into d_stats (knn_select_kernel)
+    // The protocol of a step: which launches make it up, where it stands, and what was done ahead for the next one.
+    gh_plan_requests requests;    // what the caller / the environment asked for (gh_create, gh_set_scan_filter, gh_set_coarse_tau)
+    gh_step_plan plan;            // what follows from them and the sizes above: written by gh_replan only
+    gh_step_state step;           // written through the gh_step_* functions below only (the table there)
     struct {
         bool valid = false;       // the last normalise launch also ran the KNN set-up of iteration `iter` from `src`
-        gh_ids src{};             //   (gh_knn_prepare then skips its kernel); written by gh_set_lookahead only
+        gh_ids src{};             //   (gh_knn_prepare then skips its kernel)
         uint64_t iter = 0;
         bool rows = false;        // (not yet valid) the last stats_fix launch staged the queries' raw endpoint rows of that
-                                  //   set-up in d_setup_rows, for the normalise launch right behind it; gh_set_lookahead_rows
-    } lookahead;
+                                  //   set-up in d_setup_rows, for the normalise launch right behind it
+    } lookahead;                  // read and written through the gh_*lookahead* functions below only
     gh_dev<float> d_setup_rows;   // (2 S, LD) un-normalised rows of the next queries' endpoints, rows 2s, 2s + 1 for query s
                                   // (setup_core.h gh_setup_gather); whole-graph engines with threshold tiles only
-    bool last_step_own_ids = false;     // gh_step_begin was called without ids (device sampler / arange)
-    bool tcount_reset_pending = false;  // this step's threshold kernel must reset d_tcount
     gh_dev<float> d_iscratch;     // (S * k, LD) per-pair scratch of the intersection kernel
     gh_dev<float> d_q;            // (S, QS) query records: midpoint coordinates + tau (knn.hip gh_qs)
     gh_dev<float> d_qscan;        // (S, QS) pre-filter records (-2q, t) written by the threshold kernel
@@ -178,7 +169,6 @@ struct gh_engine {
     bool packed_exchange = false;     // ... in use (gh_set_packed_rows; default: from 2 M vertices on, where the saved quarter of
                                       // the all-gather outweighs the expansion kernel -- 30 us at 4 M vertices, 14 at 1 M)
     // form D (gh_overlap_layout): the ranks' un-normalised rows new0 = pos + Fs are all-gathered EARLY, beside the KNN tail
-    bool rows_early = false;          // this step: new0 of the own rows is in its block (the rows may travel right after step_begin)
     gh_dev<float> d_rows_all;         // (world, chunk, LD): d_new is block g_rank of it
     gh_dev<float> d_rows_pk;          // (world, chunk, D): the same without pad columns -- what travels when D < LD -- or null
     gh_dev<double> d_stats_all;       // (world, stats_block) doubles: per rank its statistics rows, then its PATCH LIST -- two int32 counters used by alternate iterations (16 bytes
@@ -225,25 +215,22 @@ struct gh_engine {
                                     // summed elementwise over the ranks by the caller when partitioned.  A view: d_stats_buf,
                                     // or the own block of d_gbuf (form B) / d_stats_all (form D)
 
-    // timing
-    // thresholds inside the fused launch (tau_core.h)
-    bool tau_embedded = false;
-    bool tau_embedded_plan = false;      // the creation-time choice; the query-cell filter overrides it (gh_choose_scan_filter)
+    // thresholds inside the fused launch (tau_core.h; plan.tau == GH_TAUF_EMBEDDED)
     gh_dev<unsigned> d_tau_flag;         // queries published so far by the current fused launch
-    // pre-filter of the D <= 3 fused kernel's phase B (fused.hip): query-cell table or split-f16 MFMA
-    int scan_filter = 0;                 // GH_FILTER_AUTO | _MFMA | _CELLS, as set by gh_set_scan_filter
-    bool qcells = false;                 // in use: the query-cell table (qcell_core.h)
+    // the query-cell table of the D <= 3 fused kernel's phase B (qcell_core.h; plan.prefilter == GH_PRE_CELLS)
     gh_dev<uint32_t> d_qcell;            // (GH_QC_WORDS) the table of the current launch, built by its first workgroup
     gh_dev<unsigned> d_qc_flag;          // launch number whose table is complete
     unsigned qc_epoch = 0;               // number of the last launch on the query-cell path
     gh_dev<int32_t> d_wait_failed;       // a consumer gave up waiting: reported by gh_sync / gh_get_positions
-    // thresholds by workgroup 0 of the query-cell launch, from coarse group minima (setup_core.h "COARSE FORM")
-    int coarse_mode = 0;                 // GH_COARSE_AUTO | _OFF | _ON, as set by gh_set_coarse_tau / GRAPHEM_HIP_COARSE_TAU
-    bool coarse_tau = false;             // in use: no d_gmin, no knn_tau_kernel launch (gh_choose_scan_filter)
+    // thresholds by workgroup 0 of the query-cell launch, from coarse group minima (setup_core.h "COARSE FORM";
+    // plan.tau == GH_TAUF_COARSE: no d_gmin, no knn_tau_kernel launch)
     gh_dev<uint32_t> d_cmin;             // (2, GH_CT_M, S) float bits, GH_CT_EMPTY where no set-up workgroup has written: copy
                                          // (iter & 1) is filled by the set-up of iteration iter and consumed, and reset, by its fused launch
     bool cmin_dirty[2] = {false, false}; // a set-up has written the copy and no fused launch has consumed it yet (a set-up done
-                                         // ahead that turned out stale): the next set-up into it fills it with GH_CT_EMPTY first
+                                         // ahead that turned out stale): the next set-up into it fills it with GH_CT_EMPTY first.
+                                         // gh_cmin_claim / gh_cmin_release only
+
+    // timing
 
 #define GH_STAMP_EXTRA 8192
     gh_dev<unsigned long long> d_stamps;      // GRAPHEM_HIP_STAMPS: (n_vblocks, 8) wall-clock stamps of the last fused launch
@@ -290,6 +277,40 @@ inline bool gh_lookahead_rows_for(const gh_engine *h, const gh_ids *next) {
     return next && h->lookahead.rows && h->lookahead.iter == h->iter + 1 && h->lookahead.src.mode == next->mode &&
            h->lookahead.src.ids == next->ids;
 }
+// The rows a stats_fix launch staged are spent (or no longer wanted); a set-up done ahead stays.
+inline void gh_drop_lookahead_rows(gh_engine *h) { h->lookahead.rows = false; }
+// The set-up of the current iteration was done ahead, from these ids (gh_knn_prepare then skips its kernel).
+inline bool gh_lookahead_done_for(const gh_engine *h, const gh_ids &src) {
+    return h->lookahead.valid && h->lookahead.iter == h->iter && h->lookahead.src.mode == src.mode && h->lookahead.src.ids == src.ids;
+}
+// A set-up done ahead is stale (another threshold form, a failed wait); rows staged for one stay.
+inline void gh_drop_lookahead(gh_engine *h) { h->lookahead.valid = false; }
+
+// gh_step_state (step_plan.h), field by field: who sets it, who reads it, where it is cleared.
+//   new0_ready            set: gh_launch_spring_scan (the fused kernel wrote d_new = pos + Fs and its block sums).
+//                         read: step_begin (form D: else a launch of its own), the final selection (gh_sums_ride_along),
+//                         gh_launch_integrate.  cleared: gh_step_sums_spent in gh_launch_integrate, their one consumer; a search
+//                         without a step (gh_knn_midpoints) leaves it to the gh_step_reset of the next step.
+//   stats_reduced         set: the final selection launch (launch_select, gh_knn_finish_cdist) when the sums rode along.
+//                         read: gh_launch_integrate (stats_fix_kernel skips them).  cleared: as new0_ready.
+//   intersect_done        set: whatever launch ran the intersection phase of this step (the final selection, the exhaustive
+//                         search, the merges; a step without queries has none to run).  read: step_merge.  cleared: gh_step_reset.
+//   tcount_reset_pending  written: gh_knn_prepare, every step (the set-up was done ahead: a later launch of this step must
+//                         reset d_tcount).  read: the threshold launch, the grid build, the coarse query-cell launch.
+//   rows_early            set: step_begin under form D (new0 of the own rows is in its block: the rows may travel).
+//                         read: gh_step_rows_early, gh_step_finish_overlap, which clears it; gh_step_reset.
+//   own_ids               written: gh_step_begin / gh_step_begin_device_ids, every split step (called without ids: device
+//                         sampler / arange).  read: the gathered finishes (they set the next draw up).
+inline void gh_step_reset(gh_engine *h) {   // the start of a step's launches
+    h->step.new0_ready = h->step.stats_reduced = h->step.intersect_done = h->step.rows_early = false;
+}
+inline void gh_step_new0_ready(gh_engine *h) { h->step.new0_ready = true; }
+inline void gh_step_stats_reduced(gh_engine *h) { h->step.stats_reduced = true; }
+inline void gh_step_sums_spent(gh_engine *h) { h->step.new0_ready = h->step.stats_reduced = false; }
+inline void gh_step_intersect_done(gh_engine *h) { h->step.intersect_done = true; }
+inline void gh_step_tcount_reset_pending(gh_engine *h, bool pending) { h->step.tcount_reset_pending = pending; }
+inline void gh_step_set_rows_early(gh_engine *h, bool early) { h->step.rows_early = early; }
+inline void gh_step_own_ids(gh_engine *h, bool own) { h->step.own_ids = own; }
 
 // RAII-free helper: records start/stop events around a launch when timing is on.
 struct gh_scope {
@@ -318,6 +339,8 @@ void gh_auto_knn_method(gh_engine *h);   // GH_KNN_AUTO -> prm.knn_method (and t
 void gh_plan_threshold_subset(const gh_engine *h, gh_graph_plan *g);   // needs thr_stride / thr_M1
 // pull lists of all n rows without ownership bits (the float64 engine)
 void gh_pull_lists(int64_t n, int64_t E, const int32_t *edges, std::vector<int32_t> &rowptr, std::vector<int32_t> &adj);
+// api.hip
+void gh_replan(gh_engine *h);   // plan from the engine's sizes and requests: the only writer of it.  Drops a set-up done ahead when the threshold form changed
 // api.hip / comm.hip
 extern "C" float *gh_rows_all_device(gh_handle h);
 extern "C" int32_t gh_rows_all_row_floats(gh_handle h);
@@ -337,9 +360,7 @@ gh_status gh_f64_run(gh_engine *h, int32_t iters, const int32_t *sample_stream);
 gh_status gh_f64_knn_midpoints(gh_engine *h, const int32_t *sampled, int32_t *knn);
 // knn.hip
 gh_status gh_knn_local(gh_engine *h, bool fuse_intersect);  // d_sampled, d_mid -> d_partial (unfused)
-bool gh_knn_scan_path(const gh_engine *h);
 struct gh_setup_args;
-void gh_choose_threshold_subset(gh_engine *h);   // thr_stride, thr_M1: once knn_method, own_count, fused_scan, Ksel and S are final
 gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter);  // setup_core.h
 unsigned gh_setup_blocks(const gh_setup_args &a);
 int64_t gh_gmin_floats(const gh_engine *h);   // size of d_gmin
@@ -352,27 +373,21 @@ gh_status gh_knn_points_device(hipStream_t stream, const float *d_q, int64_t nq,
                                int D, int K, uint64_t *d_keys, std::string *err);
 // cdist.hip
 gh_status gh_cdist_alloc(gh_engine *h);
-gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world);   // row partitions: the ranks' (S, K + 2) records -> d_merged, the reference's rows
+gh_status gh_knn_merge_cdist(gh_engine *h, const uint64_t *gathered, int world, bool with_intersect);   // row partitions: the ranks' (S, K + 2) records -> d_merged, the reference's rows
 gh_status gh_knn_finish_cdist(gh_engine *h, bool all_rows, bool fuse_intersect);   // candidate lists (or nothing) -> d_partial, the reference's rows
 // grid_core.h
-bool gh_grid_path(const gh_engine *h);
 gh_status gh_grid_alloc(gh_engine *h);
 gh_status gh_grid_search(gh_engine *h);            // d_mid + tau -> candidate lists
 // ivf.hip
-bool gh_ivf_path(const gh_engine *h);
 gh_status gh_ivf_alloc(gh_engine *h);
 gh_status gh_ivf_search(gh_engine *h);             // d_mid + query records -> tau and candidate lists (probed lists only)
 // fused.hip
 gh_status gh_radial_topk_device(gh_engine *h, int K, uint64_t *d_part, int nparts, int32_t *d_ids);
-int gh_fused_mfma_kb(const gh_engine *h);          // operand rows the thresholds must write: 0 = split-f16 MFMA form (D <= 3), -1 = none
-bool gh_fused_uses_mfma(const gh_engine *h);       // the fused kernel's pre-filter runs on the matrix pipe
-int gh_fused_tile(const gh_engine *h);              // edges per fused workgroup
-bool gh_fused_cells_ok(const gh_engine *h);         // the query-cell pre-filter can serve this engine (fused.hip)
-bool gh_coarse_tau_ok(const gh_engine *h);          // ... and its first workgroup can compute the thresholds (coarse form)
 gh_status gh_cmin_claim(gh_engine *h, uint64_t iter);   // before enqueueing a coarse set-up of iteration iter: its table copy is empty
-void gh_choose_scan_filter(gh_engine *h);           // qcells, tau_embedded and coarse_tau from scan_filter, tau_embedded_plan and coarse_mode
+inline void gh_cmin_release(gh_engine *h, uint64_t iter) { h->cmin_dirty[iter & 1] = false; }   // its fused launch consumed the copy, and reset it entry by entry
 gh_status gh_launch_spring_scan(gh_engine *h);             // d_Fs + final-level candidates in one kernel
-gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world);  // -> d_keys_cur
+// -> d_keys_cur; with_intersect: the merge launch (more than one rank, or a partitioned GH_DIST_CDIST engine) also runs the intersection phase
+gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world, bool with_intersect);
 // forces.hip
 gh_status gh_launch_intersect(gh_engine *h);               // d_sampled, d_keys_cur -> d_acc/d_touched
 gh_status gh_launch_inter_cleanup(gh_engine *h);

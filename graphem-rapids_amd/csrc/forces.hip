@@ -833,23 +833,23 @@ gh_status gh_launch_mid_only(gh_engine *h) { return launch_mid_gather(h); }
 
 // new = pos + (Fs + Fi) for the own rows -> d_new, column statistics -> d_stats.
 gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next) {
-    h->lookahead.rows = false;
-    if (h->new0_ready && h->rows > 0) {  // the fused kernel already wrote pos + Fs and its partial sums
-        h->new0_ready = false;
+    gh_drop_lookahead_rows(h);
+    const bool fused_sums = h->step.new0_ready && h->rows > 0, reduced = h->step.stats_reduced;
+    gh_step_sums_spent(h);   // (read above: this launch is their one consumer)
+    if (fused_sums) {  // the fused kernel already wrote pos + Fs and its partial sums
         gh_scope t(h, "stats_fix");
-        const struct reset_flag { gh_engine *e; ~reset_flag() { e->stats_reduced = false; } } reset{h};
         // next: the normalise launch behind this one will run the next iteration's set-up (whole graph on this rank); with
         // threshold tiles, workgroups appended to this launch gather the raw rows it needs (setup_core.h gh_setup_gather)
         gh_setup_args sa{};
         unsigned gather = 0;
-        if (next && h->d_setup_rows.p && h->rows == h->n && h->part.row_lo == 0 && h->layout == GH_LAYOUT_NONE) {
+        if (next && h->plan.stage_rows) {
             sa = gh_make_setup_args(h, *next, h->iter + 1);
             if (sa.tiles > 0) gather = gh_gather_blocks(sa.S);
         }
         if (!gh_dispatch_stride(h->LD, [&](auto ld) {
                 stats_fix_kernel<ld()><<<dim3(gh_fix_blocks(ld()) + gather), dim3(256), 0, h->stream>>>(
                     h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo,
-                    h->rows, h->d_new, h->d_stats, h->stats_reduced ? 1 : 0,
+                    h->rows, h->d_new, h->d_stats, reduced ? 1 : 0,
                     h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr,
                     h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap, sa, h->d_tflag.p,
                     h->d_setup_rows.p);
@@ -861,7 +861,6 @@ gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next) {
         if (gather) gh_set_lookahead_rows(h, *next);
         return GH_OK;
     }
-    h->new0_ready = false;
     // unfused path: no correction rows
     GH_HIP(hipMemsetAsync(h->d_stats + 2 * h->LD, 0, sizeof(double) * 2 * gh_fix_blocks(h->LD) * h->LD, h->stream));
     if (h->rows == 0) {
@@ -977,7 +976,7 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
         src.stats = overlap ? h->d_stats_all.p : reinterpret_cast<const double *>(h->d_gbuf.p + h->g_chunk * h->LD * (int64_t)sizeof(float));
         src.world = h->g_world;
         src.stats_block = overlap ? h->stats_block : h->g_slot / (int64_t)sizeof(double);
-        if (!(h->fused_scan && gh_knn_scan_path(h) && h->S > 0 && h->k > 0 && !h->opt_no_presetup)) next = nullptr;
+        if (!h->plan.presetup_gathered) next = nullptr;
     }
     if (src.out_rows == 0) return with_cleanup ? gh_launch_inter_cleanup(h) : GH_OK;
     gh_scope t(h, gathered ? "normalise_gathered" : stats_all ? "normalise_own" : "normalise");

@@ -34,44 +34,19 @@
 // replaced (rounds 1-2; removed in round 4 together with its GRAPHEM_HIP_MFMA / _FUSED_CFG switches): 1M vertices, 256
 // queries: 4700 vs 4440 it/s in the steady state of a long run; 100K vertices 10760 vs 9730; 1024 queries 433 vs 566 us per
 // iteration, 4096 queries 640 vs 1434 us for the kernel; D = 12: 818 -> 508 us per iteration.
-static bool fused_mfma(int LD, int D, int64_t S) {
-    (void)S;
-    return D <= 16 && (LD == 4 || LD == 8 || LD == 16);   // D <= 3: split form; 4..16: wide form (scan_core.h)
-}
-// operand rows the threshold computation writes: only the split form has any (the wide form builds its rows at staging)
-static int fused_mfma_kb(int LD, int D, int64_t S) { return fused_mfma(LD, D, S) && D <= 3 ? 0 : -1; }
+// (gh_plan_mfma, GH_FUSED_NT / _R / _TILE: step_plan.h)
+//
 // Workgroups of 256 threads, R = 2 references per thread: tiles of 512 owned edges (95 VGPRs / 27 KB of LDS for the split
 // form; the wide form keeps the fp32 tile in LDS for the exact checks).
 // (Round 5, for graphs whose launch is one under-filled round of workgroups -- 100 K vertices: 782 workgroups on 256 CUs --
 // tiles of 256 edges, R = 1, twice the workgroups: 59.1 us per iteration against 54.5, the fused kernel 32.4 against 28.0.)
-static void fused_cfg(int LD, int D, int64_t S, int64_t own_edges, int *nt, int *r) {
-    (void)LD; (void)D; (void)S; (void)own_edges;
-    *nt = 256;
-    *r = 2;
-}
-bool gh_fused_uses_mfma(const gh_engine *h) { return h->fused_scan && fused_mfma(h->LD, h->D, h->S); }
-int gh_fused_mfma_kb(const gh_engine *h) { return h->fused_scan && !h->qcells ? fused_mfma_kb(h->LD, h->D, h->S) : -1; }
+//
 // The query-cell pre-filter (spring_scan_cells_kernel) serves D <= 3 with up to GH_QC_SMAX queries: one staged group of
 // query records and one uint8 index per table entry.  AUTO takes it wherever the thresholds have a launch of their own
 // (graphs of more than 2048 fused workgroups); where they are computed inside the fused launch the split-f16 form stays.
-bool gh_fused_cells_ok(const gh_engine *h) {
-    return h->fused_scan && fused_mfma(h->LD, h->D, h->S) && h->D <= 3 && h->S >= 1 && h->S <= GH_QC_SMAX;
-}
 // The first workgroup of the query-cell launch can take the thresholds from coarse group minima itself (setup_core.h
-// "COARSE FORM", qcell_core.h gh_ct_tau): a whole-graph engine with a threshold subset and at most GH_CT_KMAX keys to bound.
-bool gh_coarse_tau_ok(const gh_engine *h) {
-    return gh_fused_cells_ok(h) && h->thr_M1 > 0 && h->rows == h->n && h->Ksel <= GH_CT_KMAX;
-}
-void gh_choose_scan_filter(gh_engine *h) {
-    const bool want = h->scan_filter == GH_FILTER_CELLS || (h->scan_filter == GH_FILTER_AUTO && !h->tau_embedded_plan);
-    h->qcells = want && gh_fused_cells_ok(h);
-    h->tau_embedded = h->tau_embedded_plan && !h->qcells;   // the cell table is built from thresholds already in memory ...
-    // ... or from coarse group minima.  AUTO takes them where they were measured ahead -- three components, up to a dozen
-    // keys: rr1m 153.8 -> 149.9 us per iteration, er1m 191.2 -> 186.1, pp1m 182.6 -> 177.3 (NOTES.md "Coarse thresholds") --
-    // and leaves the two-dimensional and the 32-key kernels, whose smaller batches were not measured at scale, to a request
-    const bool want_coarse = h->coarse_mode == GH_COARSE_ON || (h->coarse_mode == GH_COARSE_AUTO && h->D == 3 && h->Ksel <= 12);
-    h->coarse_tau = h->qcells && want_coarse && gh_coarse_tau_ok(h);
-}
+// "COARSE FORM", qcell_core.h gh_ct_tau).  Which of these an engine runs: gh_make_step_plan (step_plan.h).
+
 // The copy of the coarse table that the set-up of iteration `iter` fills must be empty: it is, unless a set-up done ahead
 // was discarded (other ids, positions set, another threshold form in between) after it had written.
 gh_status gh_cmin_claim(gh_engine *h, uint64_t iter) {
@@ -81,12 +56,6 @@ gh_status gh_cmin_claim(gh_engine *h, uint64_t iter) {
     h->cmin_dirty[p] = true;
     return GH_OK;
 }
-int gh_fused_tile(const gh_engine *h) {
-    int nt, r;
-    fused_cfg(h->LD, h->D, h->S, h->own_count, &nt, &r);
-    return nt * r;
-}
-
 namespace {
 
 // Phase A of both fused kernels for one workgroup: spring forces of the vertices v0..v1 -> Fs,
@@ -783,7 +752,7 @@ __global__ __launch_bounds__(256) void spring_scan_mfmaw_kernel(
 #undef GH_STAMP
 }
 
-// The thresholds of this iteration: computed by the first workgroups of the fused launch itself (h->tau_embedded), or
+// The thresholds of this iteration: computed by the first workgroups of the fused launch itself (GH_TAUF_EMBEDDED), or
 // already in place (knn_tau_kernel ran; nblocks = 0).
 static unsigned fused_grid(const gh_engine *h, const gh_tau_args &ta) {
     return (unsigned)(h->n_vblocks + ta.nblocks);
@@ -791,7 +760,7 @@ static unsigned fused_grid(const gh_engine *h, const gh_tau_args &ta) {
 gh_tau_args fused_tau_args(gh_engine *h, int nt) {
     gh_tau_args ta{};
     ta.cdist = h->cdist ? 1 : 0;
-    if (!h->tau_embedded) return ta;
+    if (h->plan.tau != GH_TAUF_EMBEDDED) return ta;
     ta = gh_make_tau_args(h);
     ta.cdist = h->cdist ? 1 : 0;
     ta.flag = h->d_tau_flag.p;        // zeroed by this iteration's set-up (setup_core.h), S once the producers are through
@@ -818,15 +787,15 @@ void launch_cells_k(gh_engine *h) {
         -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, (int)h->S, h->d_qcell.p, h->d_qc_flag.p, h->qc_epoch,
         h->d_wait_failed.p, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps.p,
         KC > 0 ? h->d_cmin.p + (size_t)p * GH_CT_M * (size_t)h->S : nullptr, h->Ksel,
-        KC > 0 && h->tcount_reset_pending ? h->d_tcount.p : nullptr);
-    if (KC > 0) h->cmin_dirty[p] = false;   // consumed, and reset entry by entry
+        KC > 0 && h->step.tcount_reset_pending ? h->d_tcount.p : nullptr);
+    if (KC > 0) gh_cmin_release(h, h->iter);
 }
 // The thresholds: in memory (a launch of their own has run), or taken by workgroup 0 from the coarse table -- the usual
 // dozen keys in as many registers per thread, up to GH_CT_KMAX in a kernel of its own.
 template <int D>
 void launch_cells(gh_engine *h) {
     static_assert(GH_CT_KMAX == 32, "the instantiations below");
-    if (!h->coarse_tau) launch_cells_k<D, 0>(h);
+    if (h->plan.tau != GH_TAUF_COARSE) launch_cells_k<D, 0>(h);
     else if (h->Ksel <= 12) launch_cells_k<D, 12>(h);
     else launch_cells_k<D, 32>(h);
 }
@@ -872,20 +841,26 @@ gh_status gh_launch_spring_scan(gh_engine *h) {
     GH_TRY_ST(gh_launch_spring_long(h, h->d_Fs.p, 0));  // hubs first: their rows' forces are read back in phase A
     gh_scope t(h, "spring_scan");
     bool launched = false;
-    if (fused_mfma(h->LD, h->D, h->S) && h->D > 3) {   // the wide form: 4..16
+    switch (h->plan.prefilter) {
+    case GH_PRE_WIDE_F16:   // 4..16 components
         launched = gh_dispatch_dim(h->D, [&](auto d, auto ld) {
             if constexpr (d() > 3) launch_mfmaw<d(), ld()>(h);
         });
-    } else if (h->qcells) {
+        break;
+    case GH_PRE_CELLS:
         launched = gh_dispatch_value<2, 3>(h->D, [&](auto d) { launch_cells<d()>(h); });
-    } else if (fused_mfma(h->LD, h->D, h->S)) {
-        launched = gh_dispatch_value<2, 3>(h->D, [&](auto d) { launch_mfma<d(), 2>(h); });
+        break;
+    case GH_PRE_SPLIT_F16:
+        launched = gh_dispatch_value<2, 3>(h->D, [&](auto d) { launch_mfma<d(), GH_FUSED_R>(h); });
+        break;
+    case GH_PRE_NONE:
+        break;
     }
-    if (!launched) {   // unreachable: fused_scan needs gh_dim_templated(D) (graph_plan.hip), fused_mfma() a row stride of 4, 8 or 16
+    if (!launched) {   // unreachable: fused_scan needs gh_dim_templated(D) (graph_plan.hip), gh_plan_mfma() a row stride of 4, 8 or 16
         h->err = "fused spring+scan launched for an unsupported dimension";
         return GH_ERR_RUNTIME;
     }
     GH_LAUNCH_CHECK();
-    h->new0_ready = true;  // d_new = pos + Fs and d_blockstats[n_vblocks] are in place
+    gh_step_new0_ready(h);  // d_new = pos + Fs and d_blockstats[n_vblocks] are in place
     return GH_OK;
 }

@@ -194,7 +194,7 @@ void long_rows(gh_engine *h, gh_graph_plan *g) {
 // Vertex ranges of the fused spring+scan workgroups: as many consecutive own rows as hold at most TILE owned edges (and at
 // most 1024 rows, 4 per thread).
 void fused_blocks(gh_engine *h, gh_graph_plan *g) {
-    const int tile = gh_fused_tile(h);
+    const int tile = GH_FUSED_TILE;
     bool ok = h->fused_mid && gh_dim_templated(h->D);
     std::vector<int32_t> &vblock = g->vblock;
     if (ok) {
@@ -268,10 +268,10 @@ void gh_auto_knn_method(gh_engine *h) {
 }
 
 void gh_plan_threshold_subset(const gh_engine *h, gh_graph_plan *g) {
-    g->sub_uv.resize((size_t)h->thr_M1 * 2);
+    g->sub_uv.resize((size_t)h->plan.thr_M1 * 2);
     const bool hashed = h->part.edge_rule == GH_EDGES_HASHED;
-    for (int64_t j = 0; j < h->thr_M1; ++j) {   // every thr_stride-th own edge
-        const int64_t e = hashed ? (int64_t)g->own_eids[(size_t)(j * h->thr_stride)] : h->part.edge_lo + j * h->thr_stride;
+    for (int64_t j = 0; j < h->plan.thr_M1; ++j) {   // every thr_stride-th own edge
+        const int64_t e = hashed ? (int64_t)g->own_eids[(size_t)(j * h->plan.thr_stride)] : h->part.edge_lo + j * h->plan.thr_stride;
         g->sub_uv[(size_t)(2 * j)] = g->edges[2 * e];
         g->sub_uv[(size_t)(2 * j + 1)] = g->edges[2 * e + 1];
     }

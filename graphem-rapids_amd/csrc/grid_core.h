@@ -6,7 +6,7 @@
 // the final decision are always taken in all D coordinates); what the projection costs is selectivity, and it costs
 // everything: on the 1 M-vertex bench state the shadow of the threshold ball holds more than the 8192 candidates a list
 // takes and every query falls back to the exhaustive search -- 85 ms per iteration at D = 6, S = 4096 against 1.6 ms for
-// the scan (profiles/r03/knn_method_sweep.log).  Hence the grid is for D <= 3 only (gh_grid_path; the wide form and its
+// the scan (profiles/r03/knn_method_sweep.log).  Hence the grid is for D <= 3 only (gh_plan_built; the wide form and its
 // switch were removed in round 4);
 // the matrix-pipe scan is the search for wide rows at every S tried (up to 65536).  Included at the end of knn.hip (it
 // uses that file's K-smallest extraction).
@@ -319,15 +319,11 @@ __global__ __launch_bounds__(256) void grid_scan_kernel(const float4 *__restrict
 
 }  // namespace
 
-bool gh_grid_path(const gh_engine *h) {
-    // 2 or 3 components only.  (Round 2 also ran it over the first three of 4..16 coordinates: exact, but measured 50-80x SLOWER
-    // than the scan on the 1 M-vertex graph, profiles/r03/knn_method_sweep.log -- the three-coordinate shadow of a 6- or
-    // 16-dimensional threshold ball holds more midpoints than a candidate list takes; removed in round 4.)
-    return h->prm.knn_method == GH_KNN_GRID && h->D >= 2 && h->D <= 3 && gh_knn_scan_path(h);
-}
-
+// 2 or 3 components only (gh_plan_built).  (Round 2 also ran it over the first three of 4..16 coordinates: exact, but measured
+// 50-80x SLOWER than the scan on the 1 M-vertex graph, profiles/r03/knn_method_sweep.log -- the three-coordinate shadow of a 6-
+// or 16-dimensional threshold ball holds more midpoints than a candidate list takes; removed in round 4.)
 gh_status gh_grid_alloc(gh_engine *h) {
-    if (!gh_grid_path(h)) return GH_OK;
+    if (h->plan.built != GH_SEARCH_GRID) return GH_OK;
     // cells per binade and axis: 16 (3-D: a central cell holds ~60 of 4M midpoints of a Gaussian core) / 128 (2-D)
     const int P = h->D >= 3 ? 16 : 128;
     const int G = 2 * P * GH_GRID_OCTAVES;
@@ -364,7 +360,7 @@ gh_status gh_grid_search(gh_engine *h) {
     {
         gh_scope t(h, "grid_build");
         grid_frame_kernel<<<dim3(1), dim3(256), 0, h->stream>>>(h->d_q.p, QS, h->S, std::min(h->D, 3), h->grid_G / 2, h->D >= 3 ? 23 - 4 : 23 - 7, frame,
-                                                                  h->tcount_reset_pending ? h->d_tcount.p : nullptr);
+                                                                  h->step.tcount_reset_pending ? h->d_tcount.p : nullptr);
         gh_dispatch_value<2, 3>(h->D, [&](auto d) {   // (any other dimension: the error below)
             grid_cell_kernel<d()><<<dim3(gridM), dim3(256), 0, h->stream>>>(h->d_mid.p, h->LD, M, frame, keys, rows);
         });
@@ -377,7 +373,7 @@ gh_status gh_grid_search(gh_engine *h) {
     gh_scope t(h, "grid_tau_scan");
     const int64_t fb_stride = M >= 8 * 64 * (int64_t)h->K ? 8 : 1;   // sparse queries only: a tight bound keeps their boxes small
     const dim3 sgrid((unsigned)h->S, h->S <= 2048 ? 32 : h->S <= 16384 ? 16 : 4);   // an outlier's box can hold the whole bulk: its runs over several workgroups
-    // 2 or 3 components only (gh_grid_path)
+    // 2 or 3 components only (gh_plan_built)
     if (!gh_dispatch_value<2, 3>(h->D, [&](auto d) {
             constexpr int LD = gh_ld(d());
             grid_tau_kernel<d(), LD><<<dim3((unsigned)h->S), dim3(256), 0, h->stream>>>(smid, skeys, (int)M, frame, h->d_q.p, h->K);

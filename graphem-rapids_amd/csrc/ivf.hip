@@ -30,8 +30,7 @@
 #include "engine.h"
 #include "scan_core.h"
 
-#define GH_IVF_TILE 512          /* members per scan workgroup (R = 2 references per thread) */
-#define GH_IVF_MAX_LISTS 2048
+// (GH_IVF_TILE, members per scan workgroup -- R = 2 references per thread -- and GH_IVF_MAX_LISTS: step_plan.h)
 #define GH_IVF_GROUPS 256        /* group minima per query the threshold is taken from */
 #define GH_IVF_MB 4              /* member blocks of 32 a wave of the assignment holds */
 // Counters that many workgroups bump with returning atomics sit one per 128-byte line (adjacent counters serialise on
@@ -799,15 +798,10 @@ size_t ivf_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
-bool gh_ivf_path(const gh_engine *h) {
-    return h->prm.knn_method == GH_KNN_IVF && !h->cdist && h->D >= 2 && h->LD <= 16 && gh_knn_scan_path(h) &&
-           h->own_count >= 64 * 64 && h->own_count < ((int64_t)1 << 31) - (int64_t)GH_IVF_MAX_LISTS * GH_IVF_TILE;
-}
-
 void gh_delete(gh_ivf *v) { delete v; }
 
 gh_status gh_ivf_alloc(gh_engine *h) {
-    if (!gh_ivf_path(h)) return GH_OK;
+    if (h->plan.built != GH_SEARCH_IVF) return GH_OK;
     gh_ivf *v = new gh_ivf();
     h->ivf.reset(v);
     const int64_t M = h->own_count;
@@ -941,7 +935,7 @@ static gh_status ivf_build_and_probe(gh_engine *h) {
 // d_mid (this iteration's own midpoints) + the query records -> tau of every query and its candidate list.
 gh_status gh_ivf_search(gh_engine *h) {
     gh_ivf *v = h->ivf.get();
-    // gh_ivf_path: 2 <= D and a row stride of at most 16, so both dispatchers below find their kernels
+    // gh_plan_built: 2 <= D and a row stride of at most 16, so both dispatchers below find their kernels
     gh_status st = GH_ERR_RUNTIME;
     if (!gh_dispatch_stride(h->LD, [&](auto ld) { st = ivf_build_and_probe<ld()>(h); })) h->err = "ivf_search: row stride other than 4, 8 or 16";
     GH_TRY_ST(st);

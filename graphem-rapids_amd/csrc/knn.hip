@@ -451,7 +451,7 @@ void launch_scan(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, 
 }
 
 // D <= 4: the dimension's own kernel; above, one kernel per row stride (the whole padded row is compared), with fewer
-// references per thread.  false: neither (gh_knn_scan_path admits no such engine).
+// references per thread.  false: neither (gh_plan_built admits no such engine to the filtered scan).
 template <int R>
 bool launch_scan_d(gh_engine *h, const float *mid, int64_t M, int64_t mem_stride, int64_t id_stride) {
     if (h->D <= 4) return gh_dispatch_value<2, 3, 4>(h->D, [&](auto d) { launch_scan<d(), R>(h, mid, M, mem_stride, id_stride); });
@@ -488,36 +488,10 @@ void launch_block_select(gh_engine *h, const float *mid, int64_t M, int64_t mem_
     }
 }
 
-// Stride of the threshold subset.  The set-up evaluates M/stride subset edges against every query (inside the
-// normalise launch: ~0.1 us per 1000 rows at 256 queries beyond what the streaming part hides), the final pass then
-// meets ~K*stride candidates per query, each a divergent exact re-check + LDS append in the scan and a key in the
-// selection.  Measured optimum (rr1m, M = 4M, S*K = 2816): 64 (178 us per iteration; 40: 182, 100: 181); M = 400K: 20.
-// That is sqrt(c * M / (S*K)) with c = 3 for the MFMA form of the scan (its hits cost less than half as much as the
-// packed-VALU form's, whose balance sits lower).  Bounds: the list holds GH_CAND_CAP candidates (mean K*stride kept
-// <= 4096), a workgroup parks its hits in LDS (mean min(S,256)*K*stride*tile/M per query group kept near 300 for a buffer of >= 512), and the
-// subset must keep well over K groups of GH_THR_GSIZE rows.
-int64_t subset_stride(int64_t Mtot, int K, int64_t S, int tile, bool mfma) {
-    // beyond 256 queries the threshold kernel's workgroups no longer run all at once and its cost grows
-    // with S like the hits do, so the balance point stops moving
-    // (the MFMA form's hits cost less than half as much -- ~0.1 us per unit of stride -- so its balance sits higher)
-    int64_t r = (int64_t)sqrt((mfma ? 3.0 : 2.0) * (double)Mtot / ((double)(S < 256 ? S : 256) * K));
-    const int64_t by_list = 4096 / K;
-    if (r > by_list) r = by_list;
-    if (r > 256) r = 256;
-    // (per query GROUP: the fused kernels empty the buffer between groups once it is a quarter full)
-    const int64_t by_hits = (int64_t)(300.0 * (double)Mtot / ((double)(S < 256 ? S : 256) * K * tile));
-    if (r > by_hits) r = by_hits;
-    if (r < 2) r = 2;
-    while (r > 2 && Mtot / r < 8 * (int64_t)K * GH_THR_GSIZE) r /= 2;  // at least 8 K groups: tau stays close to the subset's K-th smallest
-    return r;
-}
-
 // fb_mid: midpoint rows for the exact search of overflowed queries, or null (gather the endpoints).
 gh_status launch_select(gh_engine *h, bool final_level, bool with_intersect, const float *fb_mid) {
     // the column sums of the fused kernel's workgroup partials ride along (stats_fix_kernel then skips them)
-    // (not with thousands of queries: there the wave-per-query form below is worth more than the ride, and stats_fix_kernel
-    // adds the column sums up itself)
-    const bool reduce = final_level && h->new0_ready && h->rows > 0 && h->LD <= 16 && h->S < 2048;
+    const bool reduce = final_level && gh_sums_ride_along(h->plan, h->step);
     gh_scope t(h, with_intersect ? "knn_select_intersect" : "knn_select");
     // thousands of queries, no column sums riding along: a wave per query first, the workgroup form for what it leaves
     const bool wave = final_level && !reduce && h->S >= 2048;
@@ -548,38 +522,22 @@ gh_status launch_select(gh_engine *h, bool final_level, bool with_intersect, con
         GH_HIP(hipMemsetAsync(h->d_tq_count.p, 0, sizeof(int32_t) * (size_t)h->S, h->stream));
     }
     GH_LAUNCH_CHECK();
-    h->stats_reduced = reduce;
+    if (reduce) gh_step_stats_reduced(h);
     return GH_OK;
 }
 
 }  // namespace
 
-// Edges this rank searches: the range [edge_lo, edge_hi), or the list d_own_eids (hashed ownership).
-static int64_t own_edges(const gh_engine *h) { return h->own_count; }
-
-bool gh_knn_scan_path(const gh_engine *h) {
-    const int64_t Mtot = own_edges(h);
-    return Mtot >= GH_SCAN_MIN_EDGES && h->LD <= 16 && h->D >= 2 && h->Ksel <= GH_EXTRACT_MAX_K && h->S <= 0x7FFFFFFF;
-}
-
-// The threshold subset of the filtered scan: every thr_stride-th own edge, thr_M1 of them (none on the other paths).
-void gh_choose_threshold_subset(gh_engine *h) {
-    const int64_t Mtot = own_edges(h);
-    const bool scan = gh_knn_scan_path(h) && !gh_grid_path(h) && !gh_ivf_path(h);   // the grid / IVF searches take their thresholds from their own structures
-    h->thr_stride = scan ? subset_stride(Mtot, h->Ksel, h->S, gh_fused_tile(h), gh_fused_uses_mfma(h)) : 1;
-    h->thr_M1 = scan ? (Mtot + h->thr_stride - 1) / h->thr_stride : 0;
-}
-
 // Sample ids (if still pending), query records, list reset and -- on the scan path -- the compact
 // threshold subset: one launch.
 gh_setup_args gh_make_setup_args(const gh_engine *h, gh_ids src, uint64_t iter) {
-    const int tiles = (int)((h->thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
+    const int tiles = (int)((h->plan.thr_M1 + GH_THR_TILE - 1) / GH_THR_TILE);
     return gh_setup_args{h->d_edges.p, src.ids, src.mode, h->E, h->prm.seed, iter, h->S, h->D, h->LD, h->d_q.p, h->d_cnt.p,
-                         h->d_ovf.p, h->part.edge_lo, h->d_own_eids.p, reinterpret_cast<const int2 *>(h->d_sub_uv.p), h->thr_M1, h->thr_stride, h->d_gmin.p,
-                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->tau_embedded ? h->d_tau_flag.p : nullptr,
+                         h->d_ovf.p, h->part.edge_lo, h->d_own_eids.p, reinterpret_cast<const int2 *>(h->d_sub_uv.p), h->plan.thr_M1, h->plan.thr_stride, h->d_gmin.p,
+                         (int64_t)tiles * GH_THR_GROUPS, tiles, h->plan.tau == GH_TAUF_EMBEDDED ? h->d_tau_flag.p : nullptr,
                          nullptr /* rows: only a normalise launch behind a gathering stats_fix launch reads staged rows (forces.hip) */,
                          // the coarse form: copy iter & 1 of the table (the launcher calls gh_cmin_claim first)
-                         h->coarse_tau && tiles > 0 ? h->d_cmin.p + (size_t)(iter & 1) * GH_CT_M * (size_t)h->S : nullptr};
+                         h->plan.tau == GH_TAUF_COARSE && tiles > 0 ? h->d_cmin.p + (size_t)(iter & 1) * GH_CT_M * (size_t)h->S : nullptr};
 }
 
 // Workgroups of 256 threads a set-up takes (knn_setup_kernel, or the head of a normalise launch).
@@ -588,7 +546,7 @@ unsigned gh_setup_blocks(const gh_setup_args &a) {
 }
 int64_t gh_gmin_floats(const gh_engine *h) {
     const gh_setup_args a = gh_make_setup_args(h, gh_ids{GH_IDS_GIVEN, nullptr}, 0);
-    if (gh_ivf_path(h)) return h->S * 256 + 4;   // GH_IVF_GROUPS minima per query, written by ivf_probe_kernel
+    if (h->plan.built == GH_SEARCH_IVF) return h->S * 256 + 4;   // GH_IVF_GROUPS minima per query, written by ivf_probe_kernel
     if (a.tiles == 0) return 4;
     return h->S * a.Gpad + 4;
 }
@@ -597,10 +555,9 @@ gh_status gh_knn_prepare(gh_engine *h) {
     const gh_ids src = h->sample;
     h->sample.mode = GH_IDS_GIVEN;   // produced by the set-up, here or done ahead
     // the previous normalise launch may already have done this iteration's set-up (forces.hip)
-    const bool done = h->lookahead.valid && h->lookahead.iter == h->iter && h->lookahead.src.mode == src.mode &&
-                      h->lookahead.src.ids == src.ids;
+    const bool done = gh_lookahead_done_for(h, src);
     gh_set_lookahead(h, nullptr);
-    h->tcount_reset_pending = done;  // the stand-alone kernel resets d_tcount; else the threshold kernel does
+    gh_step_tcount_reset_pending(h, done);  // the stand-alone kernel resets d_tcount; else the threshold kernel does
     if (done) return GH_OK;
     const gh_setup_args a = gh_make_setup_args(h, src, h->iter);
     if (a.cmin) GH_TRY_ST(gh_cmin_claim(h, h->iter));
@@ -625,13 +582,13 @@ gh_tau_args gh_make_tau_args(gh_engine *h) {
     t.qt = h->d_q.p;
     t.qscan = h->d_qscan.p;
     t.qA = reinterpret_cast<_Float16 *>(h->d_qA.p);
-    t.qA_kb = gh_fused_mfma_kb(h);   // -1: no MFMA form in use
+    t.qA_kb = h->plan.prefilter == GH_PRE_SPLIT_F16 ? 0 : -1;   // operand rows the thresholds must write: 0 = the split-f16 form (D <= 3), -1 = none
     t.qexact = h->d_qexact.p;
-    t.tcount_reset = h->tcount_reset_pending ? h->d_tcount.p : nullptr;
+    t.tcount_reset = h->step.tcount_reset_pending ? h->d_tcount.p : nullptr;
     return t;
 }
 
-// tau of every query from the group minima the set-up left in d_gmin.  Needs gh_knn_scan_path(h).
+// tau of every query from the group minima the set-up left in d_gmin.  Needs candidate lists (plan.lists()).
 gh_status gh_knn_thresholds(gh_engine *h, int64_t groups) {
     gh_scope t(h, "knn_tau");
     gh_tau_args a = gh_make_tau_args(h);
@@ -650,26 +607,26 @@ gh_status gh_knn_thresholds(gh_engine *h, int64_t groups) {
 // redone exactly over all own edges in the same launch (from d_mid when have_mid, else by
 // gathering endpoints).
 // fuse_intersect (single-rank steps): the same launches also run the intersection phase of each
-// query they finish (h->intersect_done tells the caller).
+// query they finish (gh_step_intersect_done tells the caller).
 gh_status gh_knn_finish(gh_engine *h, bool have_mid, bool fuse_intersect) {
     if (h->cdist) return gh_knn_finish_cdist(h, false, fuse_intersect);   // the reference's cdist + topk rows (cdist.hip)
     const bool fuse = fuse_intersect && h->K <= GH_EXTRACT_MAX_K;
     GH_TRY_ST(launch_select(h, true, fuse, have_mid ? h->d_mid.p : nullptr));
-    h->intersect_done = fuse;
+    if (fuse) gh_step_intersect_done(h);
     return GH_OK;
 }
 
 // Unfused search over the materialised midpoints d_mid -> d_partial.
 gh_status gh_knn_local(gh_engine *h, bool fuse_intersect) {
-    const int64_t Mtot = own_edges(h);
+    const int64_t Mtot = h->own_count;
     GH_TRY_ST(gh_knn_prepare(h));
-    if (!gh_knn_scan_path(h)) {
+    if (!h->plan.lists()) {
         if (h->cdist) return gh_knn_finish_cdist(h, true, false);   // every query against all edges (cdist.hip)
         const bool fuse = fuse_intersect && h->K <= GH_EXTRACT_MAX_K;
         gh_scope t(h, "knn_block_select");
         launch_block_select(h, h->d_mid.p, Mtot, 1, 1, nullptr, h->d_partial.p, false, fuse);
         GH_LAUNCH_CHECK();
-        h->intersect_done = fuse;
+        if (fuse) gh_step_intersect_done(h);
         return GH_OK;
     }
     GH_TRY_ST(gh_knn_thresholds(h));
@@ -684,8 +641,8 @@ gh_status gh_knn_local(gh_engine *h, bool fuse_intersect) {
     return gh_knn_finish(h, true, fuse_intersect);
 }
 
-gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world) {
-    if (h->cd_part) return gh_knn_merge_cdist(h, gathered, world);   // (S, K + 2) records per rank: the rows are decided now (cdist.hip)
+gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world, bool with_intersect) {
+    if (h->cd_part) return gh_knn_merge_cdist(h, gathered, world, with_intersect);   // (S, K + 2) records per rank: the rows are decided now (cdist.hip)
     if (world == 1) {  // nothing to merge: the intersection phase reads this rank's keys directly
         h->d_keys_cur = gathered;
         return GH_OK;
@@ -700,12 +657,12 @@ gh_status gh_knn_merge(gh_engine *h, const uint64_t *gathered, int world) {
     gh_scope t(h, "knn_merge_intersect");
     const auto merge = [&](auto d) {
         knn_merge_kernel<d()><<<dim3((unsigned)h->S), dim3(256), sizeof(uint64_t) * (size_t)n2, h->stream>>>(
-            gathered, world, h->S, h->K, h->d_merged.p, make_inter_args(h, !h->intersect_done));
+            gathered, world, h->S, h->K, h->d_merged.p, make_inter_args(h, with_intersect));
     };
-    if (!(!h->intersect_done && gh_dispatch_dim(h->D, [&](auto d, auto) { merge(d); }))) merge(gh_int<0>{});
+    if (!(with_intersect && gh_dispatch_dim(h->D, [&](auto d, auto) { merge(d); }))) merge(gh_int<0>{});
     GH_LAUNCH_CHECK();
     h->d_keys_cur = h->d_merged.p;
-    h->intersect_done = true;
+    if (with_intersect) gh_step_intersect_done(h);
     return GH_OK;
 }
 

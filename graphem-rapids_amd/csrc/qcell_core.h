@@ -33,12 +33,12 @@
 // a box (two per query, one of returning atomics) published the table so late that a tenth of the workgroups waited
 // ~10 us for it (tools/stamp_probe.py).
 #include "common.h"
-#include "engine.h"   // GH_CT_M
+#include "engine.h"   // GH_CT_M; GH_QC_SMAX, GH_CT_KMAX (step_plan.h)
 
 #define GH_QC_G 8                                 // cells per axis
 #define GH_QC_CAP 27                              // cells a query's box may cover before it goes on the wide list
 #define GH_QC_ENT 2048                            // entries of the CSR
-#define GH_QC_SMAX 256                            // queries: one staged group, one uint8 index
+// (GH_QC_SMAX, the queries -- one staged group, one uint8 index: step_plan.h)
 #define GH_QC_CELLS (GH_QC_G * GH_QC_G * GH_QC_G)  // D = 3 (D = 2 uses the first G * G)
 #define GH_QC_SAMPLE 64                           // queries whose coordinates place the boundaries (one wave)
 // blob layout, in u32 words

@@ -104,7 +104,7 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
                    min_u64(readlane_u64(v, 32), readlane_u64(v, 48)));
 }
 
-#define GH_EXTRACT_MAX_K 128
+// (GH_EXTRACT_MAX_K, the keys the register extraction takes: step_plan.h)
 
 // K smallest of the keys an NT-thread workgroup holds in registers (NPT per thread, unused
 // slots = GH_KEY_INF), written ascending to out[0..K) in LDS.  Each of the NT/64 waves extracts

@@ -45,8 +45,7 @@ struct gh_setup_args {
     uint32_t *cmin;          // coarse form (below): this iteration's copy of the coarse table, (GH_CT_M, S) float bits; null: gmin
 };
 
-#define GH_THR_TILE 128    /* subset edges per set-up workgroup */
-#define GH_THR_GSIZE 64    /* subset edges per group */
+// (GH_THR_TILE, subset edges per set-up workgroup, and GH_THR_GSIZE, subset edges per group: step_plan.h)
 #define GH_THR_GROUPS (GH_THR_TILE / GH_THR_GSIZE)   /* group minima per tile and query */
 
 // COARSE FORM of the group minima (the query-cell path of the fused kernel, thresholds not embedded: fused.hip).  tau only
