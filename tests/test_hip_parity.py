@@ -253,6 +253,14 @@ def test_device_sampler():
     assert np.array_equal(a, b)          # same seed -> same trajectory
     assert not np.array_equal(a, c)      # different seed -> different samples
     assert np.isfinite(a).all()
+    # ... and the samples are the documented permutation's (tests/sampler_reference.py; every route of the step plan:
+    # test_hip_device_sampler.py): the same run on the restated ids ends with the same bits
+    import sampler_reference
+    eng = _native.Engine(5000, 3, edges, 1.0, 0.2, 0.5, 10, 256, seed=1)
+    eng.set_positions(pos)
+    eng.run(3, sampler_reference.stream(E, 256, 1, 0, 3))
+    assert eng.get_positions().tobytes() == a.tobytes()
+    eng.close()
 
 
 @pytest.mark.parametrize("world,rule,n,D", [(2, "range", 30011, 3), (3, "range", 30011, 3),
