@@ -143,6 +143,9 @@ SIGNATURES = {
     "gh_ic_set_memory_budget": (_int, [vp, i64]),
     "gh_ic_spread": (_int, [vp, f64, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
     "gh_ic_rr_sample": (_int, [vp, vp, f64, i32, u64, i64, vp, vp]),
+    "gh_ic_set_arc_probabilities": (_int, [vp, i64, vp, vp]),
+    "gh_ic_spread_arcs": (_int, [vp, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
+    "gh_ic_rr_sample_arcs": (_int, [vp, vp, i32, u64, i64, vp, vp]),
     "gh_rr_create": (_int, [_P(vp), _int, i64]),
     "gh_rr_destroy": (None, [vp]),
     "gh_rr_last_error": (_str, [vp]),
@@ -619,9 +622,22 @@ class ICGraph(BudgetHandle):
         self._create("gh_ic_create", int(device_id), self.n, arcs.shape[0], ptr(arcs), 1 if self.directed else 0)
         self.arcs = int(self.lib.gh_ic_arc_count(self.handle))
 
+    def set_arc_probabilities(self, pairs, prob):
+        """The handle's per-arc table (gh_ic_set_arc_probabilities): pairs (m, 2) directed u -> v, prob (m,) float64.  Arcs
+        that are not listed get probability 0; a failed call keeps the previous table."""
+        pairs = np.asarray(pairs).reshape(-1, 2)
+        prob = np.ascontiguousarray(np.asarray(prob).ravel(), dtype=np.float64)
+        if len(prob) != len(pairs):
+            raise ValueError(f"{len(pairs)} pairs but {len(prob)} probabilities")
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= self.n):   # before the cast to int32 can wrap an id
+            raise ValueError(f"pair endpoints must lie in [0, {self.n})")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        self._raise(self.lib.gh_ic_set_arc_probabilities(self.handle, len(pairs), ptr(pairs), ptr(prob)))
+
     def spread(self, sets, p, n_trials, seed=0, max_hops=-1, base=None, per_trial=False):
         """sets: a list of vertex-id sequences.  Returns totals (n_sets,) int64 and, with per_trial, the (n_sets, n_trials)
-        int32 counts; with a base set both are marginal over it (gh_ic_spread)."""
+        int32 counts; with a base set both are marginal over it (gh_ic_spread; p=None: the handle's per-arc table,
+        gh_ic_spread_arcs)."""
         sets = [np.asarray(s, dtype=np.int64).ravel() for s in sets]
         offsets = np.zeros(len(sets) + 1, dtype=np.int64)
         offsets[1:] = np.cumsum([len(s) for s in sets])
@@ -629,14 +645,16 @@ class ICGraph(BudgetHandle):
         base = np.ascontiguousarray(np.zeros(0) if base is None else np.asarray(base).ravel(), dtype=np.int32)
         totals = np.zeros(len(sets), dtype=np.int64)
         trials = np.zeros((len(sets), int(n_trials)), dtype=np.int32) if per_trial else None
-        self._raise(self.lib.gh_ic_spread(self.handle, float(p), int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                          len(sets), ptr(offsets), ptr(verts), ptr(base), len(base), ptr(totals), ptr(trials)))
+        rest = (int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF, len(sets), ptr(offsets), ptr(verts), ptr(base),
+                len(base), ptr(totals), ptr(trials))
+        self._raise(self.lib.gh_ic_spread_arcs(self.handle, *rest) if p is None else
+                    self.lib.gh_ic_spread(self.handle, float(p), *rest))
         return (totals, trials) if per_trial else totals
 
 
     def rr_sample(self, rr, n_samples, p, seed=0, max_hops=-1, trials=None, roots=None):
         """Appends n_samples reverse-reachable sets to the RRSets `rr` (gh_ic_rr_sample); trials uint64 / roots int32 of
-        n_samples, or None for the header's defaults."""
+        n_samples, or None for the header's defaults.  p=None: the handle's per-arc table (gh_ic_rr_sample_arcs)."""
         n_samples = int(n_samples)
         if trials is not None:
             trials = np.ascontiguousarray(np.asarray(trials).ravel(), dtype=np.uint64)
@@ -645,8 +663,9 @@ class ICGraph(BudgetHandle):
         for a in (trials, roots):
             if a is not None and len(a) != n_samples:
                 raise ValueError(f"trials and roots must have n_samples = {n_samples} entries")
-        self._raise(self.lib.gh_ic_rr_sample(self.handle, rr.handle, float(p), int(max_hops), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                             n_samples, ptr(trials), ptr(roots)))
+        rest = (int(max_hops), int(seed) & 0xFFFFFFFFFFFFFFFF, n_samples, ptr(trials), ptr(roots))
+        self._raise(self.lib.gh_ic_rr_sample_arcs(self.handle, rr.handle, *rest) if p is None else
+                    self.lib.gh_ic_rr_sample(self.handle, rr.handle, float(p), *rest))
 
 
 class RRSets(BudgetHandle):

@@ -17,6 +17,10 @@
 //                                    clears the old frontier's words, zeroes the third counter of the ring of three.
 // The host reads the frontier count back every IC_CHECK_EVERY levels only.  Counting (ic_count_kernel) and clearing
 // (ic_reset_kernel) walk the touched list, never the dense state, so a chunk costs what its cascades reach.
+//
+// Probabilities: one threshold for the whole graph (gh_ic_spread, gh_ic_rr_sample), or one per arc from two arrays aligned
+// with the CSR slots (gh_ic_set_arc_probabilities; gh_ic_spread_arcs, gh_ic_rr_sample_arcs run the ARC instantiations of
+// push and pull).  The coin and its key are the same in both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -75,6 +79,9 @@ struct IcLevel {
     const uint64_t *trial_tab;                        // REV: the trial of bit b of word w at [64 * w + b]
     uint32_t thr;
     int32_t W, T, directed, round;
+    // ARC: the threshold of the arc in each slot of out_adj / in_adj.  Last, so that the scalar instantiations read every
+    // other member where they always did.
+    const uint32_t *out_thr, *in_thr;
 };
 
 // REV (reverse-reachable sets, gh_ic_rr_sample): the host swaps the two CSRs, so a level walks every arc backwards; the
@@ -93,7 +100,9 @@ __device__ __forceinline__ void ic_append(const IcLevel &a, int32_t e) {   // on
     if (atomicExch(&a.mark[e], a.round) != a.round) a.nxt_list[atomicAdd(a.nxt_cnt, 1)] = e;
 }
 
-template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
+// ARC (per-arc probabilities, gh_ic_set_arc_probabilities): the threshold of an arc comes from the array aligned with the
+// CSR slots -- loaded beside the neighbour id, broadcast with it -- instead of the one a.thr.
+template <bool REV, bool ARC> __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(IcLevel a) {
     const int64_t cnt = *a.cur_cnt;
     if (cnt == 0 || cnt >= a.pull_min) return;
     const int lane = threadIdx.x & 63;
@@ -122,11 +131,14 @@ template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(I
             // memory work (visited load, atomicOr, append) in parallel instead of one lane arc after arc
             for (int64_t k0 = beg; k0 < end; k0 += 64) {
                 const int32_t vk = k0 + lane < end ? a.out_adj[k0 + lane] : 0;
+                uint32_t tk = 0;
+                if constexpr (ARC) tk = k0 + lane < end ? a.out_thr[k0 + lane] : 0;
                 const int m = (int)min((int64_t)64, end - k0);
                 uint64_t mine = 0;
                 for (int q = 0; q < m; ++q) {
                     const int32_t v = __builtin_amdgcn_readlane(vk, q);
-                    const uint64_t live = __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < a.thr) & fj;
+                    const uint32_t thr = ARC ? (uint32_t)__builtin_amdgcn_readlane((int32_t)tk, q) : a.thr;
+                    const uint64_t live = __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < thr) & fj;
                     if (lane == q) mine = live;
                 }
                 if (mine) {
@@ -142,7 +154,7 @@ template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_push_kernel(I
     }
 }
 
-template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
+template <bool REV, bool ARC> __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(IcLevel a) {
     const int64_t cnt = *a.cur_cnt;
     if (cnt == 0 || cnt < a.pull_min) return;
     const int lane = threadIdx.x & 63;
@@ -167,9 +179,11 @@ template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(I
             // 64 in-arcs at a time: lane q loads the frontier word of arc q's source, coins only for the nonzero ones
             for (int64_t k0 = beg; k0 < end && acc != uj; k0 += 64) {
                 int32_t uk = 0;
+                uint32_t tk = 0;
                 uint64_t fk = 0;
                 if (k0 + lane < end) {
                     uk = a.in_adj[k0 + lane];
+                    if constexpr (ARC) tk = a.in_thr[k0 + lane];
                     fk = cw[(int64_t)uk * a.W] & uj;
                 }
                 uint64_t arcs = __ballot(fk != 0);
@@ -180,7 +194,8 @@ template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void ic_pull_kernel(I
                     const uint64_t f = uni64(__shfl(fk, q)) & ~acc;
                     if (f == 0) continue;
                     if (!have_h) { h = ic_lane_word<REV>(a, wj, lane); have_h = true; }
-                    acc |= __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < a.thr) & f;
+                    const uint32_t thr = ARC ? (uint32_t)__builtin_amdgcn_readlane((int32_t)tk, q) : a.thr;
+                    acc |= __ballot((uint32_t)(ic_mix(h ^ ic_arc_key<REV>(u, v, a.directed)) >> 40) < thr) & f;
                 }
             }
             if (acc && lane == 0) {
@@ -282,6 +297,10 @@ struct gh_ic : gh_host {
     gh_dev<int32_t> d_out_adj, d_in_own_adj;
     const int64_t *d_in_ptr = nullptr;          // not owned: d_in_own_*, or d_out_* for an undirected graph
     const int32_t *d_in_adj = nullptr;
+    // per-arc thresholds (gh_ic_set_arc_probabilities): one per slot of d_out_adj / of the in-CSR; graph state, not budgeted
+    std::vector<uint64_t> keys;                 // the canonical arc keys, ascending: what the setter resolves pairs against
+    bool has_table = false;
+    gh_dev<uint32_t> d_out_thr, d_in_thr;
     // chunk state, grown on demand
     int64_t cap_words = 0, cap_ents = 0, cap_counts = 0;
     gh_dev<uint64_t> d_vis, d_fa, d_fb;
@@ -332,14 +351,41 @@ gh_status ic_reserve(gh_ic *h, int64_t sets, int32_t W, int32_t T) {
 
 // The levels of one chunk whose round 0 is in place (list 0, the touched list, their counts): push / pull / advance until
 // the frontier is empty or max_hops levels have run.  REV: the CSRs swapped and the per-bit trial table (gh_ic_rr_sample).
+template <bool REV, bool ARC> void ic_launch_level(const gh_ic *h, const IcLevel &a, int grid) {
+    ic_push_kernel<REV, ARC><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+    ic_pull_kernel<REV, ARC><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+    ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+}
+
+// The probability model of a call: the one threshold of p, or the handle's per-arc table.
+struct IcProb {
+    bool arc;
+    uint32_t thr;   // !arc
+};
+
+inline uint32_t ic_threshold(double p) { return (uint32_t)std::min(16777216.0, std::floor(p * 16777216.0 + 0.5)); }
+
+// What the scalar and the per-arc entry points check of their probability argument.
+gh_status ic_prob(gh_ic *h, const double *p, IcProb *out) {
+    if (p) {
+        if (!(*p >= 0.0 && *p <= 1.0)) { h->err = "p must be in [0, 1]"; return GH_ERR_INVALID; }
+        *out = IcProb{false, ic_threshold(*p)};
+    } else {
+        if (!h->has_table) { h->err = "no arc probabilities have been set (gh_ic_set_arc_probabilities)"; return GH_ERR_INVALID; }
+        *out = IcProb{true, 0};
+    }
+    return GH_OK;
+}
+
 template <bool REV>
-gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t seed, uint32_t thr, int32_t max_hops,
+gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t seed, IcProb prob, int32_t max_hops,
                         const uint64_t *trial_tab) {
     IcLevel a{};
     a.out_ptr = REV ? h->d_in_ptr : h->d_out_ptr.p; a.out_adj = REV ? h->d_in_adj : h->d_out_adj.p;
     a.in_ptr = REV ? h->d_out_ptr.p : h->d_in_ptr; a.in_adj = REV ? h->d_out_adj.p : h->d_in_adj;
+    if (prob.arc) { a.out_thr = REV ? h->d_in_thr.p : h->d_out_thr.p; a.in_thr = REV ? h->d_out_thr.p : h->d_in_thr.p; }
     a.vis = h->d_vis.p; a.mark = h->d_mark.p; a.touched = h->d_touched.p; a.touch_list = h->d_touch.p; a.touch_cnt = h->d_cnt.p + 3;
-    a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = thr; a.directed = h->directed; a.trial_tab = trial_tab;
+    a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = prob.thr; a.directed = h->directed; a.trial_tab = trial_tab;
     a.dense = sets * h->n * W;
     a.pull_min = std::max<int64_t>(1, sets * h->n / IC_PULL_DIV);
     const int grid = ic_blocks(a.dense);   // a wave per 64 items; no level has more than `dense` items
@@ -354,9 +400,8 @@ gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t s
         a.cur_cnt = h->d_cnt.p + (r - 1) % 3;
         a.nxt_cnt = h->d_cnt.p + r % 3;
         a.zero_cnt = h->d_cnt.p + (r + 1) % 3;
-        ic_push_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-        ic_pull_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
-        ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+        if (prob.arc) ic_launch_level<REV, true>(h, a, grid);
+        else ic_launch_level<REV, false>(h, a, grid);
         GH_HIP(hipGetLastError());
         if (r % IC_CHECK_EVERY == 0 && r < last) {
             int32_t alive = 0;
@@ -370,7 +415,7 @@ gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t s
 
 // One chunk: `sets` seed sets given as unique entry ids (s * n + v) in `seeds`; counts -> out (sets, T).
 gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds, int32_t W, int32_t T, uint64_t seed,
-                       uint32_t thr, int32_t max_hops, int32_t *out) {
+                       IcProb prob, int32_t max_hops, int32_t *out) {
     GH_HIP(hipMemsetAsync(h->d_counts.p, 0, sizeof(int32_t) * sets * T, h->stream));
     const int32_t c0[4] = {(int32_t)seeds.size(), 0, 0, (int32_t)seeds.size()};   // ring of three + touched count
     if (!seeds.empty()) {
@@ -381,7 +426,7 @@ gh_status ic_run_chunk(gh_ic *h, int64_t sets, const std::vector<int32_t> &seeds
         ic_seed_kernel<<<dim3((unsigned)((si + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
             h->d_list0.p, (int64_t)seeds.size(), W, T, h->d_vis.p, h->d_fa.p, h->d_touched.p);
         GH_HIP(hipGetLastError());
-        GH_TRY_ST(ic_run_levels<false>(h, sets, W, T, seed, thr, max_hops, nullptr));
+        GH_TRY_ST(ic_run_levels<false>(h, sets, W, T, seed, prob, max_hops, nullptr));
         const int grid_t = ic_blocks(sets * h->n * W);
         ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, h->n, W, T, h->d_counts.p);
         ic_reset_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, W, h->d_vis.p, h->d_fa.p, h->d_fb.p,
@@ -425,7 +470,62 @@ extern "C" gh_status gh_ic_create(gh_ic_handle *out, int device_id, int64_t n, i
     }
     h->d_in_ptr = directed ? h->d_in_own_ptr.p : h->d_out_ptr.p;
     h->d_in_adj = directed ? h->d_in_own_adj.p : h->d_out_adj.p;
+    h->keys = std::move(key);
     *out = h;
+    return GH_OK;
+}
+
+// The threshold arrays are built on the host from the canonical keys, as the CSRs were: the listed pairs become a sorted
+// table (u << 32 | v) -> thr, and every slot of a CSR row looks its own arc up in it (an arc that is not listed: 0).
+extern "C" gh_status gh_ic_set_arc_probabilities(gh_ic_handle h, int64_t m, const int32_t *arcs, const double *prob) {
+    if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (m < 0 || (m > 0 && (!arcs || !prob))) return fail(GH_ERR_INVALID, "bad arc probability arguments");
+    std::vector<std::pair<uint64_t, uint32_t>> tab((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t u = arcs[2 * i], v = arcs[2 * i + 1];
+        const std::string pair = "pair " + std::to_string(i) + " (" + std::to_string(u) + ", " + std::to_string(v) + ")";
+        bool is_arc = u >= 0 && u < h->n && v >= 0 && v < h->n && u != v;
+        if (is_arc) {
+            const uint64_t a = h->directed ? u : std::min(u, v), b = h->directed ? v : std::max(u, v);
+            is_arc = std::binary_search(h->keys.begin(), h->keys.end(), (a << 32) | b);
+        }
+        if (!is_arc) return fail(GH_ERR_INVALID, pair + " is not an arc of the graph");
+        if (!(prob[i] >= 0.0 && prob[i] <= 1.0)) return fail(GH_ERR_INVALID, "the probability of " + pair + " is not in [0, 1]");
+        tab[(size_t)i] = {((uint64_t)u << 32) | (uint64_t)v, ic_threshold(prob[i])};
+    }
+    std::sort(tab.begin(), tab.end());
+    for (int64_t i = 1; i < m; ++i)
+        if (tab[(size_t)i].first == tab[(size_t)i - 1].first)
+            return fail(GH_ERR_INVALID, "the pair (" + std::to_string(tab[(size_t)i].first >> 32) + ", " +
+                                            std::to_string(tab[(size_t)i].first & 0xFFFFFFFFu) + ") is listed twice");
+    auto thr_of = [&](int64_t u, int64_t v) -> uint32_t {
+        const uint64_t k = ((uint64_t)u << 32) | (uint64_t)v;
+        auto it = std::lower_bound(tab.begin(), tab.end(), std::make_pair(k, (uint32_t)0));
+        return it != tab.end() && it->first == k ? it->second : 0;
+    };
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    // row x, neighbour y: out_thr holds x -> y in the slots of the out-CSR, in_thr holds y -> x in the slots of the in-CSR
+    // (for an undirected graph both are over the one symmetric CSR)
+    gh_dev<uint32_t> fresh[2];
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> adj;
+    std::vector<uint32_t> thr;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (h->directed || pass == 0)
+            gh_csr_from_keys(h->n, h->keys, !h->directed ? GH_CSR_SYMMETRIC : pass ? GH_CSR_BY_TARGET : GH_CSR_BY_SOURCE, &ptr, &adj);
+        thr.resize(adj.size());
+        for (int64_t x = 0; x < h->n; ++x)
+            for (int64_t k = ptr[(size_t)x]; k < ptr[(size_t)x + 1]; ++k)
+                thr[(size_t)k] = pass ? thr_of(adj[(size_t)k], x) : thr_of(x, adj[(size_t)k]);
+        if (!fresh[pass].alloc(4 * thr.size())) return fail(GH_ERR_NOMEM, "hipMalloc failed for the arc thresholds");
+        if (!thr.empty() && hipMemcpy(fresh[pass].p, thr.data(), 4 * thr.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GH_ERR_HIP, "upload of the arc thresholds failed");
+    }
+    // nothing failed: the new table replaces the old one (no call of this handle is in flight, every entry point blocks)
+    h->d_out_thr = std::move(fresh[0]);
+    h->d_in_thr = std::move(fresh[1]);
+    h->has_table = true;
     return GH_OK;
 }
 
@@ -443,12 +543,14 @@ extern "C" gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes) {
 
 extern "C" int64_t gh_ic_arc_count(gh_ic_handle h) { return h ? h->arcs : -1; }
 
-extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
-                                  const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
-                                  int64_t *totals, int32_t *per_trial) {
+// gh_ic_spread (p: the scalar) and gh_ic_spread_arcs (p = NULL: the handle's table)
+static gh_status ic_spread(gh_ic_handle h, const double *p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                           const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                           int64_t *totals, int32_t *per_trial) {
     if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
     auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
-    if (!(p >= 0.0 && p <= 1.0)) return fail(GH_ERR_INVALID, "p must be in [0, 1]");
+    IcProb prob;
+    GH_TRY_ST(ic_prob(h, p, &prob));
     if (n_trials < 1) return fail(GH_ERR_INVALID, "n_trials must be >= 1");
     if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
     if (n_sets < 0 || (n_sets > 0 && (!set_offsets || !totals))) return fail(GH_ERR_INVALID, "bad seed-set arguments");
@@ -464,8 +566,6 @@ extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, in
         if (base[i] < 0 || base[i] >= h->n) return fail(GH_ERR_INVALID, "base vertex id outside [0, n)");
     if (n_sets == 0) return GH_OK;
     if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
-    const double tf = std::floor(p * 16777216.0 + 0.5);
-    const uint32_t thr = (uint32_t)std::min(16777216.0, tf);
     const int32_t T = n_trials, W = (n_trials + 63) / 64;
     const int64_t per_set = ic_bytes_per_set(h->n, W);
     int64_t chunk = std::max<int64_t>(1, h->budget / per_set);
@@ -478,7 +578,7 @@ extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, in
     std::vector<int32_t> base_counts;
     if (!base_u.empty()) {   // |R(base)| per trial, with the same coins
         base_counts.resize(T);
-        st = ic_run_chunk(h, 1, base_u, W, T, seed, thr, max_hops, base_counts.data());
+        st = ic_run_chunk(h, 1, base_u, W, T, seed, prob, max_hops, base_counts.data());
         if (st != GH_OK) return st;
     }
     std::vector<int32_t> counts((size_t)chunk * T), one;
@@ -493,7 +593,7 @@ extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, in
             one.erase(std::unique(one.begin(), one.end()), one.end());
             for (int32_t v : one) seeds.push_back((int32_t)(s * h->n + v));
         }
-        st = ic_run_chunk(h, ns, seeds, W, T, seed, thr, max_hops, counts.data());
+        st = ic_run_chunk(h, ns, seeds, W, T, seed, prob, max_hops, counts.data());
         if (st != GH_OK) return st;
         for (int64_t s = 0; s < ns; ++s) {
             int64_t tot = 0;
@@ -507,6 +607,18 @@ extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, in
         }
     }
     return GH_OK;
+}
+
+extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                                  const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                                  int64_t *totals, int32_t *per_trial) {
+    return ic_spread(h, &p, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals, per_trial);
+}
+
+extern "C" gh_status gh_ic_spread_arcs(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                                       const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base,
+                                       int64_t n_base, int64_t *totals, int32_t *per_trial) {
+    return ic_spread(h, nullptr, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals, per_trial);
 }
 
 // ---- reverse-reachable sets (header: "reverse influence sampling") ------------------------------------------------------
@@ -588,7 +700,7 @@ gh_status rr_tmp(gh_ic *h, size_t bytes) {
 
 // One chunk of S samples (trials / roots on the host), appended to the collection at (rr->sets, rr->members).
 gh_status rr_run_chunk(gh_ic *h, gh_rr *rr, int32_t S, int32_t W, const uint64_t *trials, const int32_t *roots, uint64_t seed,
-                       uint32_t thr, int32_t max_hops, int64_t asked) {
+                       IcProb prob, int32_t max_hops, int64_t asked) {
     const int64_t bits = 64 * (int64_t)W;
     auto refuse = [&](int64_t total) {
         const double mean = (double)(rr->members + total) / (double)(rr->sets + S);
@@ -611,7 +723,7 @@ gh_status rr_run_chunk(gh_ic *h, gh_rr *rr, int32_t S, int32_t W, const uint64_t
     rr_root_kernel<<<dim3((unsigned)((S + IC_BLOCK - 1) / IC_BLOCK)), dim3(IC_BLOCK), 0, h->stream>>>(
         rr->d_roots.p + rr->sets, S, W, h->d_vis.p, h->d_fa.p, h->d_mark.p, h->d_touched.p, h->d_list0.p, h->d_touch.p, h->d_cnt.p);
     GH_HIP(hipGetLastError());
-    GH_TRY_ST(ic_run_levels<true>(h, 1, W, S, seed, thr, max_hops, h->d_rr_trials.p));
+    GH_TRY_ST(ic_run_levels<true>(h, 1, W, S, seed, prob, max_hops, h->d_rr_trials.p));
     const int grid_t = ic_blocks(h->n * W);
     ic_count_kernel<<<dim3(grid_t), dim3(IC_BLOCK), 0, h->stream>>>(h->d_touch.p, h->d_cnt.p + 3, h->d_vis.p, h->n, W, S, h->d_rr_count.p);
     GH_HIP(hipGetLastError());
@@ -666,13 +778,15 @@ gh_status rr_run_chunk(gh_ic *h, gh_rr *rr, int32_t S, int32_t W, const uint64_t
 
 }  // namespace
 
-extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
-                                     const uint64_t *trials, const int32_t *roots) {
+// gh_ic_rr_sample (p: the scalar) and gh_ic_rr_sample_arcs (p = NULL: the handle's table)
+static gh_status ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, const double *p, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                              const uint64_t *trials, const int32_t *roots) {
     if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
     auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
     if (!rr) return fail(GH_ERR_INVALID, "the collection handle is NULL");
     if (rr->n != h->n || rr->device != h->device) return fail(GH_ERR_INVALID, "the collection was created for another n or device");
-    if (!(p >= 0.0 && p <= 1.0)) return fail(GH_ERR_INVALID, "p must be in [0, 1]");
+    IcProb prob;
+    GH_TRY_ST(ic_prob(h, p, &prob));
     if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
     if (n_samples < 0) return fail(GH_ERR_INVALID, "n_samples must be >= 0");
     if (rr->sets + n_samples > INT32_MAX) return fail(GH_ERR_INVALID, "a collection holds fewer than 2^31 sets");
@@ -683,8 +797,6 @@ extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, 
     if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
     h->err.clear();
     rr->err.clear();
-    const double tf = std::floor(p * 16777216.0 + 0.5);
-    const uint32_t thr = (uint32_t)std::min(16777216.0, tf);
     // words per chunk: what the budget holds of one set's state, as gh_ic_spread sizes its seed sets
     int64_t W = std::max<int64_t>(1, (h->budget / h->n - 17) / 24);
     W = std::min<int64_t>({W, RR_MAX_WORDS, std::max<int64_t>(RR_MIN_WORDS_CAP, h->n / (2 * 64 * IC_PULL_DIV)), (n_samples + 63) / 64});
@@ -700,7 +812,7 @@ extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, 
             ro[j] = roots ? roots[j0 + j]
                           : (int32_t)(((ic_mix(ic_mix(seed + tr[j] * IC_GOLDEN) ^ ~0ull) >> 32) * (uint64_t)h->n) >> 32);
         }
-        const gh_status st = rr_run_chunk(h, rr, S, (S + 63) / 64, tr.data(), ro.data(), seed, thr, max_hops, n_samples);
+        const gh_status st = rr_run_chunk(h, rr, S, (S + 63) / 64, tr.data(), ro.data(), seed, prob, max_hops, n_samples);
         if (st != GH_OK) {   // all or nothing: the collection is what it was before the call
             if (h->err.empty()) h->err = rr->err;   // the message of a failed copy while the collection grew
             rr->err = h->err;
@@ -710,4 +822,14 @@ extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, 
         }
     }
     return GH_OK;
+}
+
+extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                                     const uint64_t *trials, const int32_t *roots) {
+    return ic_rr_sample(h, rr, &p, max_hops, seed, n_samples, trials, roots);
+}
+
+extern "C" gh_status gh_ic_rr_sample_arcs(gh_ic_handle h, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                                          const uint64_t *trials, const int32_t *roots) {
+    return ic_rr_sample(h, rr, nullptr, max_hops, seed, n_samples, trials, roots);
 }

@@ -8,9 +8,19 @@ p, max_hops, the number of trials and the seed, and tests/ic_reference.py recomp
 Reverse influence sampling (RIS) draws reverse-reachable sets with the same coins (gh_ic_rr_sample) and selects seeds by
 greedy maximum coverage on the device (gh_rr_cover): a baseline whose cost follows the sizes of the sets, not
 n * trials * k, for the graph sizes CELF cannot reach (tests/ris_reference.py restates the rule in numpy).
+
+Per-arc probabilities.  Wherever p is accepted it may be, instead of one float for the whole graph, a specification that
+arc_probabilities resolves to one probability per directed arc: "wc" (weighted cascade, p(u -> v) = 1 / indeg(v)), an
+array aligned with InfluenceGraph.arcs, or a sparse matrix P[u, v].  The coin of an arc and its key do not change; only
+the threshold it is compared with becomes the arc's own (include/graphem_hip.h), so the two directions of an undirected
+edge share a coin but may differ in probability.  A float takes gh_ic_spread / gh_ic_rr_sample as before; a table is
+uploaded once per distinct specification (gh_ic_set_arc_probabilities) and read by gh_ic_spread_arcs /
+gh_ic_rr_sample_arcs, and tests/arc_ic_reference.py recomputes every result bit for bit.
 """
+import hashlib
 import heapq
 import math
+import numbers
 import time
 
 import numpy as np
@@ -57,6 +67,85 @@ def _graph_arcs(graph, n=None, directed=None):
         arcs = np.sort(arcs, axis=1)
     arcs = np.unique(arcs, axis=0) if len(arcs) else arcs.reshape(0, 2)
     return n, arcs, directed, labels
+
+
+def _checked_probabilities(prob):
+    if prob.size and not (np.all(prob >= 0.0) and np.all(prob <= 1.0)):   # a NaN fails both comparisons
+        raise ValueError("arc probabilities must lie in [0, 1] and must not be NaN")
+    return prob
+
+
+def arc_probabilities(arcs, n, directed, p):
+    """One probability per directed arc from the specification p, against the canonical (A, 2) arc array of _graph_arcs
+    (unique rows in ascending order, no self-loops, an undirected edge as (a, b) with a < b).  Host only.
+
+    Returns float64 (A,) for a directed graph, (A, 2) for an undirected one: column 0 is a -> b, column 1 is b -> a.
+    p: "wc" / "weighted_cascade" -- p(u -> v) = 1 / indeg(v), for an undirected graph 1 / deg(v);
+       an (A,) array aligned with arcs (both directions of an undirected edge get the value);
+       an (A, 2) array, undirected graphs only: the a -> b and b -> a probabilities;
+       a scipy sparse (n, n) matrix, P[u, v] = p(u -> v): an absent entry is 0, a stored entry on a pair that is not an
+       arc raises.
+    ValueError for anything else: a float (that is the uniform model, which needs no table), a wrong shape, NaN, values
+    outside [0, 1]."""
+    arcs = np.asarray(arcs, dtype=np.int64).reshape(-1, 2)
+    n, directed, A = int(n), bool(directed), len(arcs)
+    a, b = arcs[:, 0], arcs[:, 1]
+    if isinstance(p, str):
+        if p not in ("wc", "weighted_cascade"):
+            raise ValueError(f"unknown probability model {p!r}: 'wc' / 'weighted_cascade' is the one with a name")
+        if directed:
+            return 1.0 / np.bincount(b, minlength=n)[b].astype(np.float64)
+        deg = np.bincount(arcs.ravel(), minlength=n).astype(np.float64)
+        return np.column_stack([1.0 / deg[b], 1.0 / deg[a]])
+    if sp.issparse(p):
+        if p.shape != (n, n):
+            raise ValueError(f"a probability matrix must have shape ({n}, {n}), got {p.shape}")
+        coo = sp.coo_matrix(p)
+        coo.sum_duplicates()
+        u, v, val = coo.row.astype(np.int64), coo.col.astype(np.int64), _checked_probabilities(coo.data.astype(np.float64))
+        lo, hi = (u, v) if directed else (np.minimum(u, v), np.maximum(u, v))
+        slot = np.searchsorted(a * n + b, lo * n + hi)   # the canonical rows ascend, so their keys do
+        hit = slot < A
+        hit[hit] = (a[slot[hit]] == lo[hit]) & (b[slot[hit]] == hi[hit])
+        if not hit.all():
+            i = int(np.flatnonzero(~hit)[0])
+            raise ValueError(f"the probability matrix stores an entry at ({u[i]}, {v[i]}), which is not an arc of the graph")
+        out = np.zeros(A if directed else (A, 2), dtype=np.float64)
+        if directed:
+            out[slot] = val
+        else:
+            out[slot, (u > v).astype(np.int64)] = val
+        return out
+    if isinstance(p, numbers.Number) or p is None:
+        raise ValueError("a per-arc specification is 'wc', an array aligned with the arcs or a sparse matrix")
+    try:
+        prob = np.array(p, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"not a per-arc probability specification: {exc}") from None
+    if prob.shape == (A,):
+        _checked_probabilities(prob)
+        return prob if directed else np.column_stack([prob, prob])
+    if prob.shape == (A, 2) and not directed:
+        return _checked_probabilities(prob)
+    want = f"({A},)" if directed else f"({A},) or ({A}, 2)"
+    raise ValueError(f"a probability array must have shape {want}, got {prob.shape}")
+
+
+def trivalency_probabilities(arcs, directed, seed=0, values=(0.1, 0.01, 0.001)):
+    """The trivalency model: every directed arc draws its probability from `values`,
+    np.random.default_rng(seed).choice(values, size=...), in arc_probabilities' shape for the canonical arc array."""
+    A = len(np.asarray(arcs).reshape(-1, 2))
+    return np.random.default_rng(seed).choice(np.asarray(values, dtype=np.float64), size=A if directed else (A, 2))
+
+
+class _ArcTable:
+    """A resolved specification: its own copy of the host array, and the digest an InfluenceGraph compares with the
+    table its handle holds, so one specification is uploaded once however many calls name it."""
+
+    def __init__(self, prob):
+        self.prob = np.ascontiguousarray(prob, dtype=np.float64)
+        self.prob.setflags(write=False)
+        self.key = hashlib.blake2b(self.prob.tobytes(), digest_size=16).digest()
 
 
 def celf_greedy(evaluate, n, k, celf=True, batch=64):
@@ -106,13 +195,45 @@ class InfluenceGraph:
     graph: a networkx Graph / DiGraph, a scipy sparse adjacency (this package's graph type; undirected unless
     directed=True) or an (E, 2) edge array (undirected unless directed=True; n = largest id + 1 unless given).
     Self-loops are dropped and duplicate edges merged.  networkx node labels that are not 0 .. n-1 are mapped in node
-    order; seeds are given and returned as labels."""
+    order; seeds are given and returned as labels.
+
+    p, wherever a method takes it, is one float for the whole graph or a per-arc specification (arc_probabilities):
+    "wc", an array aligned with self.arcs, a sparse matrix.  The handle keeps the table of the last specification used, so
+    repeated calls with one specification upload it once; a float never touches it."""
 
     def __init__(self, graph, n=None, directed=None, device_id=0):
         self.n, self.arcs, self.directed, self.labels = _graph_arcs(graph, n, directed)
         self._index = None if self.labels is None else {v: i for i, v in enumerate(self.labels)}
         self._device_id = int(device_id)
         self._ic = _native.ICGraph(max(self.n, 1), self.arcs, self.directed, device_id) if self.n > 0 else None
+        self._table_key = None   # digest of the table the handle holds
+
+    def arc_probabilities(self, p):
+        """The host array a per-arc specification resolves to on this graph (arc_probabilities): float64 (A,) aligned
+        with self.arcs for a directed graph, (A, 2) -- a -> b, b -> a -- for an undirected one."""
+        return np.array(self._resolve_table(p).prob)
+
+    def _resolve_table(self, p):
+        return p if isinstance(p, _ArcTable) else _ArcTable(arc_probabilities(self.arcs, self.n, self.directed, p))
+
+    def _resolve(self, p):
+        """A float stays a float (the uniform path); anything else becomes an _ArcTable, resolved once per public call."""
+        if isinstance(p, numbers.Real) and not isinstance(p, bool):
+            return float(p)
+        return self._resolve_table(p)
+
+    def _native_p(self, p):
+        """What _native.ICGraph takes for a resolved p: the float, or None once the handle holds p's table."""
+        if not isinstance(p, _ArcTable):
+            return p
+        if self._table_key != p.key:
+            if self.directed:
+                pairs, prob = self.arcs, p.prob
+            else:
+                pairs, prob = np.concatenate([self.arcs, self.arcs[:, ::-1]]), np.concatenate([p.prob[:, 0], p.prob[:, 1]])
+            self._ic.set_arc_probabilities(pairs, prob)
+            self._table_key = p.key
+        return None
 
     def _ids(self, seeds):
         seeds = list(seeds)
@@ -134,10 +255,11 @@ class InfluenceGraph:
     def spread(self, seeds, p=0.1, n_trials=1024, max_hops=None, seed=0, return_trials=False):
         """Mean spread of the seed set over n_trials cascades (and the (n_trials,) per-trial counts with return_trials)."""
         ids = self._ids(seeds)
+        p = self._resolve(p)
         if self._ic is None:
             trials = np.zeros(int(n_trials), dtype=np.int32)
         else:
-            _, trials = self._ic.spread([ids], p, n_trials, seed, self._hops(max_hops), per_trial=True)
+            _, trials = self._ic.spread([ids], self._native_p(p), n_trials, seed, self._hops(max_hops), per_trial=True)
             trials = trials[0]
         mean = float(trials.sum(dtype=np.int64)) / int(n_trials)
         return (mean, trials) if return_trials else mean
@@ -145,14 +267,17 @@ class InfluenceGraph:
     def marginal_totals(self, base, candidates, p, n_trials, max_hops=None, seed=0):
         """(len(candidates),) int64: sum over trials of |R(base + c)| - |R(base)|, the same coins for every candidate."""
         cand = np.asarray(candidates, dtype=np.int64).ravel()
+        p = self._resolve(p)
         if self._ic is None or len(cand) == 0:
             return np.zeros(len(cand), dtype=np.int64)
-        return self._ic.spread(cand.reshape(-1, 1), p, n_trials, seed, self._hops(max_hops),
+        return self._ic.spread(cand.reshape(-1, 1), self._native_p(p), n_trials, seed, self._hops(max_hops),
                                base=np.asarray(base, dtype=np.int64))
 
     def greedy(self, k, p=0.1, n_trials=256, max_hops=None, seed=0, celf=True):
         """Greedy seeds maximising the sample-average spread over ONE fixed set of n_trials coin draws (common random
         numbers): (seeds, candidate evaluations)."""
+        p = self._resolve(p)   # once: every evaluation then finds the handle's table in place
+
         def evaluate(base, cand):
             return self.marginal_totals(base, cand, p, n_trials, max_hops, seed)
         seeds, evals = celf_greedy(evaluate, self.n, k, celf=celf)
@@ -166,6 +291,7 @@ class InfluenceGraph:
         given as labels where the graph has labels."""
         if self._ic is None:
             raise ValueError("the graph has no vertices")
+        p = self._resolve(p)
         coll = RRCollection(_native.RRSets(self.n, self._device_id), self, p, self._hops(max_hops), seed)
         try:
             coll.extend(n_samples, trials, roots)
@@ -219,7 +345,7 @@ class RRCollection:
         if roots is not None:
             roots = self._graph._ids(roots)
         self._host = None
-        self._graph._ic.rr_sample(self._rr, n_samples, self._p, self._seed, self._hops, trials, roots)
+        self._graph._ic.rr_sample(self._rr, n_samples, self._graph._native_p(self._p), self._seed, self._hops, trials, roots)
         return self
 
     def _labels(self):
@@ -380,6 +506,7 @@ def ris_seed_selection(G, k, p=0.1, iterations_count=200, *, n_samples=None, eps
         raise ValueError("k must be >= 0")
     seed = _draw_seed(seed)
     g = G if isinstance(G, InfluenceGraph) else InfluenceGraph(G)
+    p = g._resolve(p)   # once: both collections and every doubling then find the handle's table in place
     hops = _ndlib_hops(int(iterations_count))
     k = min(int(k), g.n)
     if hops is None or k == 0:   # nothing is ever removed: every gain is 0, the choice is 0, 1, 2, ...
@@ -443,7 +570,8 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
     GraphEm seeds against greedy seeds and a random baseline, each scored with ndlib_estimated_influence.  The generator
     may return an (E, 2) edge array or an adjacency matrix.  Returns the reference's result keys; ris=True adds
     ris_seeds, ris_influence, ris_time and ris_samples from ris_seed_selection (epsilon = 0.1); kshell=True adds
-    kshell_seeds, kshell_influence and kshell_time from kshell_seed_selection."""
+    kshell_seeds, kshell_influence and kshell_time from kshell_seed_selection.  p may be a per-arc specification
+    (arc_probabilities), e.g. p="wc" for the weighted cascade."""
     from . import create_graphem, graphem_seed_selection, edges_to_adjacency
     start_time = time.time()
     out = graph_generator(**graph_params)
@@ -460,6 +588,7 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
         layout_params = {"L_min": 10.0, "k_attr": 0.5, "k_inter": 0.1, "n_neighbors": 15, "sample_size": 512,
                          "batch_size": 1024}
     graph = InfluenceGraph(edges, n=n)
+    p = graph._resolve(p)   # a per-arc specification ("wc", ..) is resolved once for all the calls below
     embedder = create_graphem(adjacency, n_components=dim, backend=backend, verbose=False, **layout_params)
 
     graphem_start = time.time()

@@ -498,7 +498,23 @@ gh_status gh_selftest_arith(int device_id, uint64_t seed, int64_t samples, int64
  * of a separate coin per direction -- and (u, v) per arc u -> v for a directed graph.  The reached set of trial t is
  * exactly the breadth-first search over the live arcs from the seeds, cut at max_hops.  Results therefore depend only on
  * (arc set, seed set, p, max_hops, n_trials, seed): not on arc order, duplicate arcs, self-loops, how trials are packed,
- * how seed sets are batched or chunked. */
+ * how seed sets are batched or chunked.
+ *
+ * Per-arc probabilities (gh_ic_set_arc_probabilities, gh_ic_spread_arcs, gh_ic_rr_sample_arcs): arc u -> v has its own
+ * probability p_uv in [0, 1] and its own threshold, computed once on the host in double:
+ *     thr_uv = min(2^24, floor(p_uv * 2^24 + 0.5))
+ * In trial t the arc u -> v is live iff  coin(seed, t, a, b) < thr_uv.  coin, mix and the key (a, b) are unchanged: (u, v)
+ * for a directed graph, (min, max) for an undirected one, whose two directions therefore share a coin but may have
+ * different thresholds.  Trial t so defines ONE live digraph; a cascade is the breadth-first search over it from the
+ * seeds, cut at max_hops, and an RR set is the search over it backwards from the root.  Two consequences:
+ *   1. One forward (or one backward) search looks at an undirected edge in at most one direction -- from the endpoint it
+ *      reaches first -- so by deferred decisions its result has the distribution of independent coins per direction, as
+ *      argued above for the uniform p.
+ *   2. The identity  sum over all roots r of [S meets RR(t, r)] = |R_t(S)|  (RIS section) holds exactly, because both
+ *      searches walk the same live digraph.
+ * Results depend only on (arc set, probability table, seed set or samples, max_hops, n_trials, seed).  The table is graph
+ * state on the device, 4 bytes per CSR slot in each of two arrays (a slot per arc and array for a directed graph, two
+ * slots per edge and array for an undirected one); gh_ic_set_memory_budget does not count it. */
 typedef struct gh_ic *gh_ic_handle;
 
 /* arcs: (n_arcs, 2) int32 host array, vertex ids in [0, n).  directed = 0: each row is an undirected edge.  Self-loops
@@ -520,6 +536,17 @@ gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes);
 gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
                        const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                        int64_t *totals, int32_t *per_trial);
+/* The handle's per-arc table: arcs is an (m, 2) int32 host array of DIRECTED pairs u -> v, prob[i] the probability of
+ * pair i.  For an undirected graph (u, v) and (v, u) are the two directions of one edge; each may be listed once.  An arc
+ * of the graph that is not listed gets threshold 0.  GH_ERR_INVALID, with the pair in gh_ic_last_error(h), for a pair
+ * that is not an arc of the graph, a pair listed twice, a probability that is NaN or outside [0, 1].  A call replaces
+ * the previous table; a failed call leaves it in place.  Calls with a scalar p are not affected by it.  Blocking. */
+gh_status gh_ic_set_arc_probabilities(gh_ic_handle h, int64_t m, const int32_t *arcs, const double *prob);
+/* gh_ic_spread with the table in place of p: the same arguments, checks, chunking and budget.  GH_ERR_INVALID when no
+ * table has been set. */
+gh_status gh_ic_spread_arcs(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                            const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                            int64_t *totals, int32_t *per_trial);
 
 /* ---- reverse influence sampling (RIS; Borgs et al. 2014, TIM/IMM, OPIM-C; graphem-rapids_amd/influence.py) --------------
  * A collection of reverse-reachable (RR) sets on the device behind its own handle, drawn by a gh_ic handle with the coins
@@ -557,6 +584,10 @@ gh_status gh_rr_set_memory_budget(gh_rr_handle h, int64_t bytes);
  * outgrow ITS budget: RIS is for sets that are small against n.  A failed call leaves the collection as it was.  Blocking. */
 gh_status gh_ic_rr_sample(gh_ic_handle ic, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
                           const uint64_t *trials, const int32_t *roots);
+/* gh_ic_rr_sample with ic's per-arc table (gh_ic_set_arc_probabilities) in place of p: the same arguments, checks,
+ * chunking and budgets.  GH_ERR_INVALID when no table has been set. */
+gh_status gh_ic_rr_sample_arcs(gh_ic_handle ic, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                               const uint64_t *trials, const int32_t *roots);
 gh_status gh_rr_counts(gh_rr_handle h, int64_t *n_sets, int64_t *n_members);
 /* Host arrays (each may be NULL): indptr int64 (sets + 1), members int32, roots int32 (sets; -1 for an uploaded set
  * without one).  Blocking. */
