@@ -20,6 +20,7 @@
 
 #define RR_BLOCK 256
 #define RR_MAX_BLOCKS 1024
+#define RR_COVER_BLOCKS 256         // rr_cover_kernel: a wave per set of the chosen vertex
 
 static thread_local std::string g_rr_error;
 
@@ -234,7 +235,7 @@ extern "C" gh_status gh_rr_cover(gh_rr_handle h, int64_t k, int32_t *seeds, int6
                                                                                         d_cursor.p, d_vsets.p);
         GH_LAUNCH_CHECK();
     }
-    const int grid_n = rr_blocks(n), grid_c = 256;
+    const int grid_n = rr_blocks(n), grid_c = RR_COVER_BLOCKS;
     for (int64_t r = 0; r < rounds; ++r) {
         rr_argmax_kernel<<<dim3(grid_n), dim3(RR_BLOCK), 0, h->stream>>>(d_cnt.p, d_chosen.p, n, d_best.p + r);
         rr_cover_kernel<<<dim3(grid_c), dim3(RR_BLOCK), 0, h->stream>>>(d_best.p + r, h->d_indptr.p, h->d_members.p, d_vptr.p, d_vsets.p,

@@ -12,6 +12,16 @@ from ic_reference import G, canonical_arcs, mix, threshold
 from ris_reference import default_roots
 
 
+def mixed_probabilities(rng, shape, scale=1.0):
+    """Random probabilities with exact 0, exact 1, 1e-9 (threshold 0) and 1 - 1e-9 (threshold 2^24) mixed in."""
+    prob = rng.random(shape) * scale
+    kind = rng.integers(0, 20, shape)
+    for k, value in enumerate((0.0, 1.0, 1e-9, 1.0 - 1e-9)):
+        prob[kind == k] = value
+    assert all((prob == v).any() for v in (0.0, 1.0, 1e-9, 1.0 - 1e-9))
+    return prob
+
+
 def _live_arcs(n, pairs, directed, prob):
     """(src, dst, key, thr) of every directed arc, for canonical `pairs`."""
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -27,7 +37,7 @@ def _live_arcs(n, pairs, directed, prob):
     return src, dst, key, thr
 
 
-def spread_trials_arcs(n, pairs, directed, prob, seeds, n_trials, seed=0, max_hops=None):
+def spread_trials_arcs(n, pairs, directed, prob, seeds, n_trials, seed=0, max_hops=None, frontiers=None):
     """(n_trials,) int64: the spread of every trial (ic_reference.spread_trials with a threshold per arc)."""
     src, dst, key, thr = _live_arcs(n, pairs, directed, prob)
     order = np.argsort(dst, kind="stable")
@@ -47,21 +57,25 @@ def spread_trials_arcs(n, pairs, directed, prob, seeds, n_trials, seed=0, max_ho
         vis = np.zeros(n, dtype=np.uint64)
         vis[seeds] = valid
         front = vis.copy()
-        for _ in range(hops):
+        for level in range(hops):
             if not front.any() or len(key) == 0:
                 break
+            if frontiers is not None:
+                frontiers.level(w, level, front)
             contrib = front[src] & live
             nxt = np.zeros(n, dtype=np.uint64)
             nxt[dst[starts]] = np.bitwise_or.reduceat(contrib, starts)
             nxt &= ~vis
             vis |= nxt
             front = nxt
+        if frontiers is not None:
+            frontiers.done(w, vis)
         for j in range(len(t)):
             out[64 * w + j] = int(np.count_nonzero(vis & bits[j]))
     return out
 
 
-def rr_sets_arcs(n, pairs, directed, prob, n_samples=None, seed=0, max_hops=None, trials=None, roots=None):
+def rr_sets_arcs(n, pairs, directed, prob, n_samples=None, seed=0, max_hops=None, trials=None, roots=None, frontiers=None):
     """(indptr int64, members int32, roots int32): ris_reference.rr_sets with a threshold per arc."""
     if trials is None:
         trials = np.arange(n_samples, dtype=np.uint64)
@@ -85,17 +99,23 @@ def rr_sets_arcs(n, pairs, directed, prob, n_samples=None, seed=0, max_hops=None
         vis = np.zeros(n, dtype=np.uint64)
         np.bitwise_or.at(vis, r, bits[:len(t)])
         front = vis.copy()
-        for _ in range(hops):
+        for level in range(hops):
             if not front.any() or len(key) == 0:
                 break
+            if frontiers is not None:
+                frontiers.level(w, level, front)
             contrib = front[dst] & live
             nxt = np.zeros(n, dtype=np.uint64)
             nxt[src[starts]] = np.bitwise_or.reduceat(contrib, starts)
             nxt &= ~vis
             vis |= nxt
             front = nxt
+        if frontiers is not None:
+            frontiers.done(w, vis)
+        reached = np.flatnonzero(vis)   # ascending, so every set's members are
+        words = vis[reached]
         for j in range(len(t)):
-            sets.append(np.flatnonzero(vis & bits[j]).astype(np.int32))
+            sets.append(reached[(words & bits[j]) != 0].astype(np.int32))
     indptr = np.zeros(S + 1, dtype=np.int64)
     indptr[1:] = np.cumsum([len(s) for s in sets])
     members = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int32)

@@ -30,8 +30,38 @@ def canonical_arcs(n, arcs, directed):
     return np.unique(arcs, axis=0) if len(arcs) else arcs
 
 
-def spread_trials(n, arcs, directed, seeds, p, n_trials, seed=0, max_hops=None):
-    """(n_trials,) int64: the spread of every trial."""
+class Frontiers:
+    """What the restatements see of the level machinery's work lists, for tests/launch_caps.py: per chunk of
+    `words_per_chunk` words (None: one chunk) and level r, the vertices whose frontier word of round r + 1 is non-zero in
+    any word, and the vertices that are visited in any word at the end (the touched list)."""
+
+    def __init__(self, words_per_chunk=None):
+        self.words_per_chunk = words_per_chunk
+        self.levels, self.touched = {}, {}
+
+    def _chunk(self, w):
+        return 0 if self.words_per_chunk is None else w // self.words_per_chunk
+
+    def level(self, w, r, front):
+        rows = self.levels.setdefault(self._chunk(w), [])
+        if r == len(rows):
+            rows.append(np.zeros(len(front), dtype=bool))
+        rows[r] |= front != 0
+
+    def done(self, w, vis):
+        c = self._chunk(w)
+        self.touched[c] = (vis != 0) | self.touched.get(c, False)
+
+    def entries(self, chunk=0):
+        """Frontier entries of every level that had any: what *cur_cnt holds in round 1, 2, ..."""
+        return [int(x.sum()) for x in self.levels.get(chunk, [])]
+
+    def touched_entries(self, chunk=0):
+        return int(np.sum(self.touched.get(chunk, 0)))
+
+
+def spread_trials(n, arcs, directed, seeds, p, n_trials, seed=0, max_hops=None, frontiers=None):
+    """(n_trials,) int64: the spread of every trial.  frontiers: a Frontiers that records the levels on the way."""
     pairs = canonical_arcs(n, arcs, directed)
     src, dst = pairs[:, 0], pairs[:, 1]
     if not directed:   # both directions share the pair's coin
@@ -55,15 +85,19 @@ def spread_trials(n, arcs, directed, seeds, p, n_trials, seed=0, max_hops=None):
         vis = np.zeros(n, dtype=np.uint64)
         vis[seeds] = valid
         front = vis.copy()
-        for _ in range(hops):
+        for r in range(hops):
             if not front.any() or len(key) == 0:
                 break
+            if frontiers is not None:
+                frontiers.level(w, r, front)
             contrib = front[src] & live
             nxt = np.zeros(n, dtype=np.uint64)
             nxt[dst[starts]] = np.bitwise_or.reduceat(contrib, starts)
             nxt &= ~vis
             vis |= nxt
             front = nxt
+        if frontiers is not None:
+            frontiers.done(w, vis)
         for j in range(len(t)):
             out[64 * w + j] = int(np.count_nonzero(vis & bits[j]))
     return out

@@ -1,5 +1,6 @@
-"""The capped launches of the graph analyses on the shared CSR handle, and the shapes at which
-tests/test_hip_launch_caps.py takes each of them past its cap: one table.  The caps are read out of the csrc files, so the
+"""The capped launches of the graph analyses on the shared CSR handle, of the cascade and RR-set kernels (influence.hip,
+ris.hip) and of the block-model generator, and the shapes at which tests/test_hip_launch_caps.py,
+tests/test_hip_cascade_caps.py and tests/test_hip_generators.py take each of them past its cap: one table.  The caps are read out of the csrc files, so the
 CPU test over this table (tests/test_launch_caps_cpu.py) fails when somebody raises a cap and a shape stops passing it,
 instead of a GPU test that silently covers nothing any more.  Nothing here touches the library under test."""
 import functools
@@ -19,6 +20,10 @@ DEFINES = {
     "PR_BLOCK": "centrality.hip", "PR_MAX_BLOCKS": "centrality.hip",
     "QUAL_BLOCK": "qual_handle.h", "QUAL_HOP_MAX_BLOCKS": "quality.hip", "QUAL_HOP_STATE_BYTES": "quality.hip",
     "CENT_DEFAULT_BUDGET": "cent_handle.h",   # the default budget of the centrality handle
+    "IC_BLOCK": "influence.hip", "IC_MAX_BLOCKS": "influence.hip", "IC_PULL_DIV": "influence.hip", "IC_DEFAULT_BUDGET": "influence.hip",
+    "RR_MAX_WORDS": "influence.hip", "RR_MIN_WORDS_CAP": "influence.hip",
+    "RR_BLOCK": "ris.hip", "RR_MAX_BLOCKS": "ris.hip", "RR_COVER_BLOCKS": "ris.hip",
+    "GEN_BLOCK": "generators.hip", "GEN_MAX_BLOCKS": "generators.hip", "GEN_DEFAULT_BUDGET": "generators.hip",
 }
 
 
@@ -51,6 +56,36 @@ def groups_in_flight(state_bytes, n, n_sources):
     return max(1, min(state_bytes // (24 * n), ceil_div(n_sources, 64), 65535))
 
 
+def ic_sets_per_chunk(budget, n, W, n_sets):
+    """The seed sets of one chunk of gh_ic_spread: ic_bytes_per_set of csrc/influence.hip -- three (n, W) word arrays, the
+    round stamp, the touched byte and three lists -- into the budget, at most the sets there are and 2^31 entries."""
+    return min(max(1, budget // (n * (3 * 8 * W + 4 + 1 + 3 * 4))), n_sets, (2 ** 31 - 1) // n)
+
+
+def ic_pull_min(d, sets_in_chunk, n):
+    """pull_min of ic_run_levels: a level pulls from this many frontier entries on, and pushes below."""
+    return max(1, sets_in_chunk * n // d.IC_PULL_DIV)
+
+
+def rr_words_per_chunk(d, n, n_samples, budget=None):
+    """W of ic_rr_sample: what the budget holds of one set's state, at most RR_MAX_WORDS, at most half the pull threshold in
+    roots (RR_MIN_WORDS_CAP for small graphs), at most the words the samples fill."""
+    W = max(1, ((d.IC_DEFAULT_BUDGET if budget is None else budget) // n - 17) // 24)
+    return min(W, d.RR_MAX_WORDS, max(d.RR_MIN_WORDS_CAP, n // (2 * 64 * d.IC_PULL_DIV)), ceil_div(n_samples, 64))
+
+
+def sbm_segments(sizes, segment):
+    """(first segment, segments) of every block pair a <= b in the order gh_gen_sbm numbers them: a pair space of N index
+    pairs is cut into ceil(N / segment) segments whatever its probability."""
+    out, seg0 = [], 0
+    for a, sa in enumerate(sizes):
+        for b in range(a, len(sizes)):
+            count = ceil_div(sa * (sa - 1) // 2 if a == b else sa * sizes[b], segment)
+            out.append((seg0, count))
+            seg0 += count
+    return out
+
+
 def pair_group_width(n, m):
     """lk_group_width of csrc/links.hip: the power of two at or above the mean degree, 4 .. 64."""
     mean = ceil_div(2 * m, n) if n else 0
@@ -72,6 +107,21 @@ PAIRS = {"dense130": dict(n=130, width=64, pairs=20_000, extra=3), "ba300": dict
 RING = dict(n=140_001)
 LONG_ROWS = dict(n=4650, hubs=150, hub_degree=1500, base_degree=40)
 
+# influence.hip and ris.hip: the shapes A - E of tests/test_hip_cascade_caps.py (graphs and expectations: tests/cascade_caps.py)
+# Whether a level pushes or pulls, and how long the lists are that advance, count, reset and scatter walk, depends on the
+# frontier, which only the restatement knows: `peak` is the largest number of frontier entries (vertices whose frontier
+# word is non-zero in any word, over the sets of the chunk) that any level has, `touched` the entries visited in the end.
+# tests/test_launch_caps_cpu.py measures both with the restatements and holds these figures to them.
+FWD_PULL = dict(n=2003, sets=17, set_size=3, p=0.3, T=1000, arc_scale=0.6,            # A: er2000, no hop limit
+                measured={"p": dict(peak=33_916, touched=33_967), "arcs": dict(peak=33_782, touched=33_967)})
+FWD_PUSH = dict(n=17_503, out_degree=3, sets=8, set_size=1060, p=0.3, T=4033, arc_scale=0.6)   # B: one hop
+REV_PULL = dict(n=40_003, degree=6, p=0.4, hops=5, samples=1250, measured=dict(words=19, peak=17_733, touched=35_970))   # C: first chunk
+REV_PUSH = dict(n=262_147, in_degree=3, samples=8192, distinct_roots=8000, p=0.5, arc_scale=1.0)   # D: one hop
+COVER = dict(n=300_001, sets=9003, sizes=(0, 1, 2, 63, 64, 65, 200), heavy=290_000, heavy_sets=3001, tie_low=1234,   # E
+             tie_high=280_000, tie_sets=40, members=514_140)
+# generators.hip: two blocks joined by p = 1e-6 and empty inside; `segment` is GH_GEN_SBM_SEGMENT of include/graphem_hip.h
+SBM = dict(sizes=(550_000, 550_000), p=1e-6, segment=16_384)
+
 
 # Capped launches that an older test already takes past the cap; they have no row below.
 COVERED_ELSEWHERE = {
@@ -81,8 +131,9 @@ COVERED_ELSEWHERE = {
     "cm_best_spill_kernel, one slice": "test_hip_communities.py::test_invariance_bit_for_bit[ladder] under set_memory_budget(1)",
 }
 # Not covered: the per-vertex loops of a Louvain level above 1 048 576 vertices and cm_run_count / cm_run_place past a
-# million runs (a Louvain restatement at that size takes minutes); influence.hip, ris.hip, clusters.hip, generators.hip and
-# the engine are not on this handle.
+# million runs (a Louvain restatement at that size takes minutes), and the engine.  influence.hip, ris.hip and gen_sbm_kernel
+# of generators.hip are not on the shared handle but have rows below; clusters.hip is passed by
+# test_hip_clusters.py::test_device_equals_host_when_workgroups_stride.
 
 
 def long_row_graph(seed=0):
@@ -152,4 +203,84 @@ def rows(d=None):
     for name, p in PAIRS.items():
         out.append(dict(launch=f"lk_pair_kernel, {p['width']} lanes a pair ({name})", cap="GS_MAX_BLOCKS", per_trip=gs_trip // p["width"],
                         items=p["pairs"] + p["extra"], block=d.GS_BLOCK // p["width"], kernels="lk_pair", test=f"test_pair_scores[{name}]"))
+    out.append(dict(launch="gen_sbm_kernel, a thread per segment", cap="GEN_MAX_BLOCKS", per_trip=d.GEN_MAX_BLOCKS * d.GEN_BLOCK,
+                    items=sum(count for _, count in sbm_segments(SBM["sizes"], SBM["segment"])), block=d.GEN_BLOCK,
+                    kernels="gen_sbm<false> gen_sbm<true>", test="test_hip_generators.py::test_sbm_device_equals_host_past_the_cap"))
+    return out + cascade_rows(d)
+
+
+def cascade_rows(d):
+    """The rows of influence.hip and ris.hip.  A level kernel only works on the side of pull_min its frontier is on, so a
+    row's items are 0 -- and the row fails -- when the sizing rules as the sources now state them no longer send the shape's
+    frontier through the kernel the row names, or no longer give the chunk the measured figures were taken for.  Push takes
+    a wave per 64 (entry, word) items and both push shapes have W a multiple of 64, so those rows have no ragged block;
+    `second_trip` is what is left for the last trip, which tests/test_launch_caps_cpu.py holds to be a partial one."""
+    here = "test_hip_cascade_caps.py::"
+    ic_trip = d.IC_MAX_BLOCKS * d.IC_BLOCK      # (entry, word) items: a thread each, or a lane each of a wave's 64
+    ic_waves = ic_trip // 64                    # ic_count_kernel: a wave per (64 touched entries, word)
+    rr_trip = d.RR_MAX_BLOCKS * d.RR_BLOCK
+    out = []
+
+    a = FWD_PULL
+    W = ceil_div(a["T"], 64)
+    chunk = ic_sets_per_chunk(d.IC_DEFAULT_BUDGET, a["n"], W, a["sets"])
+    pull_min = ic_pull_min(d, chunk, a["n"])
+    peak, touched = (min(m[key] for m in a["measured"].values()) for key in ("peak", "touched"))
+    whole = chunk == a["sets"]                  # the figures were measured over all the sets in one chunk
+    out += [
+        dict(launch="ic_pull_kernel, forward", cap="IC_MAX_BLOCKS", per_trip=ic_trip, block=d.IC_BLOCK, W=W, pull_min=pull_min,
+             items=chunk * a["n"] * W if whole and peak >= pull_min else 0, kernels="ic_pull<false, false> ic_pull<false, true>",
+             test=here + "test_forward_pull_past_the_cap"),
+        dict(launch="ic_advance_kernel, ic_reset_kernel, forward", cap="IC_MAX_BLOCKS", per_trip=ic_trip, block=d.IC_BLOCK,
+             items=peak * W if whole else 0, kernels="ic_advance ic_reset", test=here + "test_forward_pull_past_the_cap"),
+        dict(launch="ic_count_kernel, forward", cap="IC_MAX_BLOCKS", per_trip=ic_waves, items=ceil_div(touched, 64) * W if whole else 0,
+             kernels="ic_count", test=here + "test_forward_pull_past_the_cap"),
+    ]
+
+    b = FWD_PUSH
+    W = ceil_div(b["T"], 64)
+    chunk = ic_sets_per_chunk(d.IC_DEFAULT_BUDGET, b["n"], W, b["sets"])
+    pull_min = ic_pull_min(d, chunk, b["n"])
+    entries = b["sets"] * b["set_size"]         # round 1's frontier is the seed list
+    items = entries * W if chunk == b["sets"] and entries < pull_min else 0
+    out.append(dict(launch="ic_push_kernel, forward", cap="IC_MAX_BLOCKS", per_trip=ic_trip, items=items, W=W, pull_min=pull_min,
+                    second_trip=items - ic_trip, kernels="ic_push<false, false> ic_push<false, true>",
+                    test=here + "test_forward_push_past_the_cap"))
+
+    c = REV_PULL
+    W = rr_words_per_chunk(d, c["n"], c["samples"])
+    pull_min = ic_pull_min(d, 1, c["n"])
+    peak, touched = c["measured"]["peak"], c["measured"]["touched"]
+    whole = W == c["measured"]["words"]         # the figures are those of the first chunk at this many words
+    out += [
+        dict(launch="ic_pull_kernel, reverse", cap="IC_MAX_BLOCKS", per_trip=ic_trip, block=d.IC_BLOCK, W=W, pull_min=pull_min,
+             items=c["n"] * W if whole and peak >= pull_min else 0, kernels="ic_pull<true, false>",
+             test=here + "test_reverse_pull_past_the_cap"),
+        dict(launch="rr_scatter_kernel, ic_reset_kernel, reverse", cap="IC_MAX_BLOCKS", per_trip=ic_trip, block=d.IC_BLOCK,
+             items=touched * W if whole else 0, kernels="rr_scatter ic_reset", test=here + "test_reverse_pull_past_the_cap"),
+        dict(launch="ic_count_kernel, reverse", cap="IC_MAX_BLOCKS", per_trip=ic_waves, items=ceil_div(touched, 64) * W if whole else 0,
+             kernels="ic_count", test=here + "test_reverse_pull_past_the_cap"),
+    ]
+
+    r = REV_PUSH
+    W = rr_words_per_chunk(d, r["n"], r["samples"])
+    pull_min = ic_pull_min(d, 1, r["n"])
+    entries = r["distinct_roots"]               # round 1's frontier is the root list
+    items = entries * W if 64 * W >= r["samples"] and entries < pull_min else 0
+    out.append(dict(launch="ic_push_kernel, reverse", cap="IC_MAX_BLOCKS", per_trip=ic_trip, items=items, W=W, pull_min=pull_min,
+                    second_trip=items - ic_trip, kernels="ic_push<true, false> ic_push<true, true>",
+                    test=here + "test_reverse_push_past_the_cap"))
+
+    e = COVER
+    test = here + "test_coverage_kernels_past_their_caps"
+    out += [
+        dict(launch="rr_vscatter_kernel, rr_hit_kernel, a wave per set", cap="RR_MAX_BLOCKS", per_trip=rr_trip // 64, items=e["sets"],
+             block=d.RR_BLOCK // 64, kernels="rr_vscatter rr_hit", test=test),
+        dict(launch="rr_argmax_kernel", cap="RR_MAX_BLOCKS", per_trip=rr_trip, items=e["n"], block=d.RR_BLOCK, kernels="rr_argmax",
+             test=test),
+        dict(launch="rr_cover_kernel, a wave per set of the chosen vertex", cap="RR_COVER_BLOCKS", per_trip=d.RR_COVER_BLOCKS * d.RR_BLOCK // 64,
+             items=e["heavy_sets"], block=d.RR_BLOCK // 64, kernels="rr_cover", test=test),
+        dict(launch="rr_vcount_kernel", cap="RR_MAX_BLOCKS", per_trip=rr_trip, items=e["members"], block=d.RR_BLOCK, kernels="rr_vcount",
+             test=test),
+    ]
     return out

@@ -20,7 +20,7 @@ def default_roots(n, seed, trials):
     return (((w >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
 
 
-def rr_sets(n, arcs, directed, p, n_samples=None, seed=0, max_hops=None, trials=None, roots=None):
+def rr_sets(n, arcs, directed, p, n_samples=None, seed=0, max_hops=None, trials=None, roots=None, frontiers=None):
     """(indptr int64, members int32, roots int32): the RR sets of the samples, members ascending within a set."""
     if trials is None:
         trials = np.arange(n_samples, dtype=np.uint64)
@@ -49,17 +49,23 @@ def rr_sets(n, arcs, directed, p, n_samples=None, seed=0, max_hops=None, trials=
         vis = np.zeros(n, dtype=np.uint64)
         np.bitwise_or.at(vis, r, bits[:len(t)])
         front = vis.copy()
-        for _ in range(hops):
+        for level in range(hops):
             if not front.any() or len(key) == 0:
                 break
+            if frontiers is not None:
+                frontiers.level(w, level, front)
             contrib = front[dst] & live
             nxt = np.zeros(n, dtype=np.uint64)
             nxt[src[starts]] = np.bitwise_or.reduceat(contrib, starts)
             nxt &= ~vis
             vis |= nxt
             front = nxt
+        if frontiers is not None:
+            frontiers.done(w, vis)
+        reached = np.flatnonzero(vis)   # ascending, so every set's members are
+        words = vis[reached]
         for j in range(len(t)):
-            sets.append(np.flatnonzero(vis & bits[j]).astype(np.int32))
+            sets.append(reached[(words & bits[j]) != 0].astype(np.int32))
     indptr = np.zeros(S + 1, dtype=np.int64)
     indptr[1:] = np.cumsum([len(s) for s in sets])
     members = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int32)

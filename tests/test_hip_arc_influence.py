@@ -21,14 +21,7 @@ SEED = 7
 EXTRA = 3   # isolated vertices n .. n + 2 behind every graph, as tests/test_hip_influence.py adds them
 
 
-def _mixed(rng, shape, scale=1.0):
-    """Random probabilities with exact 0, exact 1, 1e-9 (threshold 0) and 1 - 1e-9 (threshold 2^24) mixed in."""
-    prob = rng.random(shape) * scale
-    kind = rng.integers(0, 20, shape)
-    for k, value in enumerate((0.0, 1.0, 1e-9, 1.0 - 1e-9)):
-        prob[kind == k] = value
-    assert all((prob == v).any() for v in (0.0, 1.0, 1e-9, 1.0 - 1e-9))
-    return prob
+_mixed = arc.mixed_probabilities   # exact 0, exact 1, 1e-9 and 1 - 1e-9 mixed in; tests/test_hip_cascade_caps.py shares it
 
 
 @functools.lru_cache(maxsize=None)

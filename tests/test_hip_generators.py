@@ -7,6 +7,7 @@ import pytest
 import graphem_rapids_amd as gr
 from graphem_rapids_amd import _native
 import generators_reference as ref
+import launch_caps as lc
 from test_generators_cpu import BA_GRID, GEOMETRIC_GRID, SBM_GRID
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +63,18 @@ def test_sbm_device_equals_host_200k(device, host):
     h = host.sbm(sizes, P, 11)
     print(f"sbm 200 K vertices, 50 blocks: {len(d)} edges")
     assert len(d) > 1_000_000
+    assert np.array_equal(d, h)
+
+
+def test_sbm_device_equals_host_past_the_cap(device, host):
+    """Two blocks of 550 000 vertices, empty inside and joined by p = 1e-6: 36.9 M segments against the 65 536 * 256 that
+    gen_sbm_kernel takes a trip, the live block pair across the end of the first (tests/launch_caps.py, SBM)."""
+    sizes, p = list(lc.SBM["sizes"]), lc.SBM["p"]
+    P = [[0.0, p], [p, 0.0]]
+    d = device.sbm(sizes, P, 11)
+    h = host.sbm(sizes, P, 11)
+    assert 290_000 < len(d) < 315_000   # p * 550 000^2 = 302 500, standard deviation 550
+    assert (d[:, 0] < sizes[0]).all() and (d[:, 1] >= sizes[0]).all()
     assert np.array_equal(d, h)
 
 
