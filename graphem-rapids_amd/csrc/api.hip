@@ -177,7 +177,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     GH_A(d_iscratch, S * (size_t)h->k * h->LD, false);
     h->nblocks_update = (int)((h->rows + 255) / 256);
     GH_A(d_blockstats, (size_t)std::max(std::max(h->nblocks_update, h->n_vblocks), 1) * 2 * h->LD, true);
-    GH_A(d_stats_buf, (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD, true);
+    GH_A(d_stats_buf, (size_t)gh_stats_rows(h->LD) * h->LD, true);
     h->d_stats = h->d_stats_buf.p;
     h->sample = gh_ids{GH_IDS_GIVEN, h->d_sampled.p};
     auto up = [&](void *dst, const void *src, size_t bytes) {
@@ -314,7 +314,7 @@ static gh_plan_input plan_input_of(const gh_engine *h) {
     in.knn_method = h->prm.knn_method;
     in.cdist = h->cdist; in.cd_part = h->cd_part;
     in.fused_scan = h->fused_scan; in.n_vblocks = h->n_vblocks;
-    in.layout = h->layout;
+    in.layout = h->xch.lay.form;
     return in;
 }
 void gh_replan(gh_engine *h) {
@@ -393,7 +393,7 @@ static bool whole_graph(gh_engine *h) {
 // gh_step / gh_run / the per-phase entry points merge with world = 1 and normalise with the own rows'
 // statistics: on a row partition that would silently corrupt the positions.
 static gh_status check_whole(gh_engine *h, const char *what) {
-    if (whole_graph(h) && h->layout == GH_LAYOUT_NONE) return GH_OK;
+    if (whole_graph(h) && h->xch.is(GH_LAYOUT_NONE)) return GH_OK;
     h->err = std::string(what) + " needs the whole graph on one rank; a partitioned engine runs gh_step_begin / "
              "gh_step_merge / gh_step_finish_gathered (or gh_run_partitioned)";
     return GH_ERR_INVALID;
@@ -430,7 +430,7 @@ static gh_status step_begin(gh_engine *h, bool fuse_intersect) {
     GH_TRY_ST(step_begin_launches(h, fuse_intersect));
     // form D: new0 = pos + Fs of the own rows is in their block -- written by the fused kernel, or (a rank too small for it;
     // every rank must send at the same point of the iteration) by a launch of its own -- and may travel now
-    if (h->layout == GH_LAYOUT_OVERLAP) {
+    if (h->xch.is(GH_LAYOUT_OVERLAP)) {
         if (!h->step.new0_ready) GH_TRY_ST(gh_launch_new0(h));
         gh_step_set_rows_early(h, true);
     }
@@ -467,8 +467,8 @@ static gh_status step_begin_launches(gh_engine *h, bool fuse_intersect) {
     return gh_knn_local(h, fuse_intersect);
 }
 
-// next: the ids step_finish will set the next iteration up from (presetup_ids), when the caller knows them by now.
-static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world, const gh_ids *next = nullptr) {
+// next: the ids the finish will set the next iteration up from (presetup_ids), when the caller knows them by now.
+gh_status gh_step_merge_keys(gh_engine *h, const uint64_t *gathered, int world, const gh_ids *next) {
     GH_TRY_ST(gh_knn_merge(h, gathered, world, !h->step.intersect_done));
     if (!h->step.intersect_done) GH_TRY_ST(gh_launch_intersect(h));
     GH_TRY_ST(gh_launch_integrate(h, next));
@@ -481,8 +481,20 @@ static gh_status step_merge(gh_engine *h, const uint64_t *gathered, int world, c
 static const gh_ids *presetup_ids(const gh_engine *h, const gh_ids *next) {
     return h->plan.presetup ? next : nullptr;
 }
-static gh_status step_finish(gh_engine *h, const gh_ids *next) {
-    GH_TRY_ST(gh_launch_normalise(h, true, presetup_ids(h, next)));  // also zeroes what the intersection phase touched
+// The finish of every step.  The next iteration's set-up rides in the normalise launch where the plan allows: from `next`
+// after a single-rank finish; after an all-rows finish, from the engine's own draw when this step drew its own ids (a rank
+// that drew this step's ids on the device will do so again); never under form C.
+gh_status gh_step_finish_as(gh_engine *h, gh_finish_kind kind, const gh_ids *next, const double *stats_all) {
+    const gh_ids own = gh_own_ids(h);
+    bool with_cleanup = true;   // the normalise launch also zeroes what the intersection phase touched
+    if (kind == GH_FINISH_OWN) next = presetup_ids(h, next);
+    else next = kind == GH_FINISH_ALL_ROWS && h->step.own_ids && h->plan.presetup_gathered ? &own : nullptr;
+    if (kind == GH_FINISH_ALL_ROWS && h->xch.is(GH_LAYOUT_OVERLAP)) {
+        GH_TRY_ST(gh_launch_patch_rows(h));
+        with_cleanup = !h->step.rows_early;   // (the patch launch has zeroed the accumulators of a step whose rows went early)
+    }
+    GH_TRY_ST(gh_launch_normalise(h, kind, with_cleanup, next, stats_all));
+    gh_step_set_rows_early(h, false);
     h->iter += 1;
     return GH_OK;
 }
@@ -501,8 +513,8 @@ static gh_status run_iterations(gh_engine *h, int32_t iters, bool draws_own, Src
             // (named before the statistics launch, which stages the rows of that set-up: before_row(t) has made row t + 1 available)
             const gh_ids next = t + 1 < iters ? src_of_row(t + 1) : own;
             const gh_ids *next_ids = t + 1 < iters || draws_own ? &next : nullptr;
-            GH_TRY_ST(step_merge(h, h->d_partial.p, 1, presetup_ids(h, next_ids)));
-            GH_TRY_ST(step_finish(h, next_ids));
+            GH_TRY_ST(gh_step_merge_keys(h, h->d_partial.p, 1, presetup_ids(h, next_ids)));
+            GH_TRY_ST(gh_step_finish_as(h, GH_FINISH_OWN, next_ids));
         }
         return GH_OK;
     };
@@ -825,131 +837,86 @@ extern "C" gh_status gh_step_merge(gh_handle h, const uint64_t *gathered, int32_
     GH_TRY_ST(check_handle(h));
     GH_TRY_ST(reject_f64(h, "gh_step_merge"));
     if (!gathered || world < 1) { h->err = "bad gathered buffer / world size"; return GH_ERR_INVALID; }
-    return step_merge(h, gathered, world);
+    return gh_step_merge_keys(h, gathered, world);
 }
 extern "C" double *gh_stats_partial_device(gh_handle h) { return h ? h->d_stats : nullptr; }
-extern "C" int32_t gh_stats_rows(gh_handle h) { return h ? 2 + 2 * gh_fix_blocks(h->LD) : 0; }
+extern "C" int32_t gh_stats_rows(gh_handle h) { return h ? gh_stats_rows(h->LD) : 0; }
 extern "C" gh_status gh_step_finish(gh_handle h) {
     GH_TRY_ST(check_handle(h));
     GH_TRY_ST(reject_f64(h, "gh_step_finish"));
-    return step_finish(h, nullptr);
+    return gh_step_finish_as(h, GH_FINISH_OWN);
 }
 
-// Checks of the layout calls (name: the call, what: its layout in the message): world blocks of chunk rows, block `rank`
-// the engine's row partition, the blocks within d_pos if within_pos; no layout set yet.
-static gh_status check_layout(gh_engine *h, const char *name, const char *what, int32_t world, int32_t rank, int64_t chunk,
-                              bool within_pos = false) {
+// The one layout setter (name: the call, for the messages): the value from exchange_layout.h, the buffers it sizes, and the
+// views d_new / d_stats moved to the engine's own block (forms B and D).
+static gh_status set_layout(gh_engine *h, const char *name, int form, int32_t world, int32_t rank, int64_t chunk) {
     GH_TRY_ST(check_handle(h));
     GH_TRY_ST(reject_f64(h, name));
-    if (world < 1 || rank < 0 || rank >= world || chunk < 1 || chunk * world < h->n || (within_pos && chunk * world > h->pos_rows) ||
-        h->part.row_lo != std::min<int64_t>(h->n, rank * chunk) || h->part.row_hi != std::min<int64_t>(h->n, (rank + 1) * chunk)) {
-        h->err = std::string(what) + " does not match the engine's row partition";
-        return GH_ERR_INVALID;
+    gh_exchange &x = h->xch;
+    gh_exchange_layout l;
+    GH_TRY_ST(gh_make_exchange_layout({h->n, h->pos_rows, h->D, h->LD, h->S, h->k, h->part.row_lo, h->part.row_hi}, x.lay.form, form,
+                                      world, rank, chunk, &l, &h->err));
+    const bool views_move = form != GH_LAYOUT_RANK;
+    if (views_move) GH_HIP(hipStreamSynchronize(h->stream));
+    if (l.rows_floats) GH_TRY_ST(gh_alloc(h, x.d_rows, (size_t)l.rows_floats, true));
+    if (l.late_all_doubles) GH_TRY_ST(gh_alloc(h, x.d_late, (size_t)l.late_all_doubles, true));
+    if (l.packed_floats) GH_TRY_ST(gh_alloc(h, x.d_packed, (size_t)l.packed_floats, true));
+    if (form == GH_LAYOUT_OVERLAP) GH_HIP(hipStreamSynchronize(h->stream));   // (a side stream will read them)
+    x.lay = l;
+    x.packed_exchange = l.packed_default;
+    if (views_move) {
+        h->d_new = x.d_rows.p + l.own_rows;
+        h->d_stats = x.stats_buffer() + l.own_stats;
     }
-    if (h->layout != GH_LAYOUT_NONE) { h->err = "rank / gather layout already set"; return GH_ERR_INVALID; }
-    return GH_OK;
-}
-
-extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY_ST(check_layout(h, "gh_gather_layout", "gather layout", world, rank, chunk));
-    const int64_t stats_bytes = (int64_t)sizeof(double) * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
-    const int64_t slot = (chunk * h->LD * (int64_t)sizeof(float) + stats_bytes + 15) / 16 * 16;
-    GH_HIP(hipStreamSynchronize(h->stream));
-    GH_TRY_ST(gh_alloc(h, h->d_gbuf, (size_t)(slot * world), true));
-    h->d_new = reinterpret_cast<float *>(h->d_gbuf.p + rank * slot);
-    h->d_stats = reinterpret_cast<double *>(h->d_gbuf.p + rank * slot + chunk * h->LD * (int64_t)sizeof(float));
-    h->g_slot = slot; h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
-    h->layout = GH_LAYOUT_GATHERED;
     gh_replan(h);
     return GH_OK;
 }
-extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY_ST(check_layout(h, "gh_rank_layout", "rank layout", world, rank, chunk, true));
-    // fewer components than the row stride (3 of 4, 5..7 of 8, 9..15 of 16): the finished blocks travel unpadded
-    if (h->D < h->LD && world > 1) {
-        GH_TRY_ST(gh_alloc(h, h->d_rows_packed, (size_t)world * chunk * h->D, true));
-        h->packed_exchange = h->n >= ((int64_t)1 << 21);
-    }
-    h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
-    h->layout = GH_LAYOUT_RANK;
-    gh_replan(h);
-    return GH_OK;
-}
+extern "C" gh_status gh_gather_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) { return set_layout(h, "gh_gather_layout", GH_LAYOUT_GATHERED, world, rank, chunk); }
+extern "C" gh_status gh_rank_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) { return set_layout(h, "gh_rank_layout", GH_LAYOUT_RANK, world, rank, chunk); }
 // Form D: form B's finish (every rank normalises all n rows from the gathered un-normalised rows) with the big collective
 // moved to the front of the KNN tail -- see include/graphem_hip.h.
-extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) {
-    GH_TRY_ST(check_layout(h, "gh_overlap_layout", "overlap layout", world, rank, chunk));
-    if (h->LD > 16) { h->err = "gh_overlap_layout: up to 16 components (use gh_rank_layout / gh_gather_layout beyond)"; return GH_ERR_INVALID; }
-    const size_t R = (size_t)(2 + 2 * gh_fix_blocks(h->LD));
-    // a rank's block of the late all-gather: statistics rows, 16 bytes for the patch count, the patch records
-    h->patch_cap = std::max<int64_t>(1, std::min<int64_t>(4 * h->S * h->k, chunk));
-    h->stats_block = (int64_t)(R * h->LD) + 2 + ((int64_t)h->patch_cap * (1 + h->LD) * 4 + 7) / 8;
-    h->stats_block = (h->stats_block + 1) / 2 * 2;   // 16-byte multiples
-    GH_HIP(hipStreamSynchronize(h->stream));
-    GH_TRY_ST(gh_alloc(h, h->d_rows_all, (size_t)world * chunk * h->LD, true));
-    GH_TRY_ST(gh_alloc(h, h->d_stats_all, (size_t)world * (size_t)h->stats_block, true));
-    if (h->D < h->LD && world > 1) GH_TRY_ST(gh_alloc(h, h->d_rows_pk, (size_t)world * chunk * h->D, true));
-    GH_HIP(hipStreamSynchronize(h->stream));
-    h->d_new = h->d_rows_all.p + (size_t)rank * chunk * h->LD;
-    h->d_stats = h->d_stats_all.p + (size_t)rank * (size_t)h->stats_block;
-    h->g_chunk = chunk; h->g_world = world; h->g_rank = rank;
-    h->layout = GH_LAYOUT_OVERLAP;
-    gh_replan(h);
-    return GH_OK;
-}
-extern "C" float *gh_rows_all_device(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? nullptr : h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p; }
-extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return !h || h->layout != GH_LAYOUT_OVERLAP ? 0 : h->d_rows_pk.p ? h->D : h->LD; }
-extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->d_stats_all.p : nullptr; }
-extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP ? h->stats_block : 0; }
-extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->layout == GH_LAYOUT_OVERLAP && h->step.rows_early ? 1 : 0; }
+extern "C" gh_status gh_overlap_layout(gh_handle h, int32_t world, int32_t rank, int64_t chunk) { return set_layout(h, "gh_overlap_layout", GH_LAYOUT_OVERLAP, world, rank, chunk); }
+extern "C" float *gh_rows_all_device(gh_handle h) { return h && h->xch.is(GH_LAYOUT_OVERLAP) ? h->xch.travelling_rows() : nullptr; }
+extern "C" int32_t gh_rows_all_row_floats(gh_handle h) { return h && h->xch.is(GH_LAYOUT_OVERLAP) ? h->xch.lay.row_floats : 0; }
+extern "C" double *gh_stats_all_device(gh_handle h) { return h && h->xch.is(GH_LAYOUT_OVERLAP) ? h->xch.d_late.p : nullptr; }
+extern "C" int64_t gh_stats_all_block_doubles(gh_handle h) { return h && h->xch.is(GH_LAYOUT_OVERLAP) ? h->xch.lay.late_doubles : 0; }
+extern "C" int32_t gh_step_rows_early(gh_handle h) { return h && h->xch.is(GH_LAYOUT_OVERLAP) && h->step.rows_early ? 1 : 0; }
 extern "C" gh_status gh_step_pack_rows(gh_handle h, void *hip_stream, int32_t use_engine_stream) {
     GH_TRY_ST(check_handle(h));
-    if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
+    if (!h->xch.is(GH_LAYOUT_OVERLAP)) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
     return gh_launch_pack_rows(h, use_engine_stream ? h->stream : reinterpret_cast<hipStream_t>(hip_stream));
 }
 extern "C" gh_status gh_step_finish_overlap(gh_handle h) {
     GH_TRY_ST(check_handle(h));
-    if (h->layout != GH_LAYOUT_OVERLAP) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
-    GH_TRY_ST(gh_launch_patch_rows(h));
-    const gh_ids own = gh_own_ids(h);
-    // (the patch launch has zeroed the accumulators of a step whose rows went early)
-    GH_TRY_ST(gh_launch_normalise(h, !h->step.rows_early, h->step.own_ids ? &own : nullptr, true));
-    gh_step_set_rows_early(h, false);
-    h->iter += 1;
-    return GH_OK;
+    if (!h->xch.is(GH_LAYOUT_OVERLAP)) { h->err = "gh_overlap_layout has not been called"; return GH_ERR_INVALID; }
+    return gh_step_finish_as(h, GH_FINISH_ALL_ROWS);
 }
 
 extern "C" gh_status gh_set_packed_rows(gh_handle h, int32_t on) {
     GH_TRY_ST(check_handle(h));
-    if (on && !h->d_rows_packed.p) { h->err = "no packed block exchange for this engine (needs gh_rank_layout with world > 1 and fewer components than the row stride)"; return GH_ERR_INVALID; }
-    h->packed_exchange = on != 0;
+    if (on && !(h->xch.is(GH_LAYOUT_RANK) && h->xch.d_packed.p)) { h->err = "no packed block exchange for this engine (needs gh_rank_layout with world > 1 and fewer components than the row stride)"; return GH_ERR_INVALID; }
+    h->xch.packed_exchange = on != 0;
     return GH_OK;
 }
-extern "C" float *gh_rows_packed_device(gh_handle h) { return h && h->packed_exchange ? h->d_rows_packed.p : nullptr; }
+extern "C" float *gh_rows_packed_device(gh_handle h) { return h && h->xch.packed_exchange ? h->xch.d_packed.p : nullptr; }
 extern "C" gh_status gh_step_unpack_rows(gh_handle h) {
     GH_TRY_ST(check_handle(h));
-    if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
-    if (!h->packed_exchange) { h->err = "the packed block exchange is not in use (gh_set_packed_rows)"; return GH_ERR_INVALID; }
+    if (!h->xch.is(GH_LAYOUT_RANK)) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
+    if (!h->xch.packed_exchange) { h->err = "the packed block exchange is not in use (gh_set_packed_rows)"; return GH_ERR_INVALID; }
     return gh_launch_unpack_rows(h);
 }
 extern "C" gh_status gh_step_finish_own(gh_handle h, const double *stats_all, int32_t world) {
     GH_TRY_ST(check_handle(h));
-    if (h->layout != GH_LAYOUT_RANK) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
-    if (!stats_all || world != h->g_world) { h->err = "bad statistics buffer / world size"; return GH_ERR_INVALID; }
-    GH_TRY_ST(gh_launch_normalise(h, true, nullptr, false, stats_all));
-    h->iter += 1;
-    return GH_OK;
+    if (!h->xch.is(GH_LAYOUT_RANK)) { h->err = "gh_rank_layout has not been called"; return GH_ERR_INVALID; }
+    if (!stats_all || world != h->xch.lay.world) { h->err = "bad statistics buffer / world size"; return GH_ERR_INVALID; }
+    return gh_step_finish_as(h, GH_FINISH_OWN_ALL_STATS, nullptr, stats_all);
 }
-extern "C" void *gh_gather_buffer_device(gh_handle h) { return h ? h->d_gbuf.p : nullptr; }
-extern "C" int64_t gh_gather_slot_bytes(gh_handle h) { return h ? h->g_slot : 0; }
+extern "C" void *gh_gather_buffer_device(gh_handle h) { return h && h->xch.is(GH_LAYOUT_GATHERED) ? h->xch.d_rows.p : nullptr; }
+extern "C" int64_t gh_gather_slot_bytes(gh_handle h) { return h ? h->xch.lay.slot_bytes : 0; }
 extern "C" gh_status gh_step_finish_gathered(gh_handle h) {
     GH_TRY_ST(check_handle(h));
-    if (h->layout != GH_LAYOUT_GATHERED) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
-    // a rank that drew this step's ids on the device will do so again: prepare them in the same launch
-    const gh_ids own = gh_own_ids(h);
-    GH_TRY_ST(gh_launch_normalise(h, true, h->step.own_ids ? &own : nullptr, true));
-    h->iter += 1;
-    return GH_OK;
+    if (!h->xch.is(GH_LAYOUT_GATHERED)) { h->err = "gh_gather_layout has not been called"; return GH_ERR_INVALID; }
+    return gh_step_finish_as(h, GH_FINISH_ALL_ROWS);
 }
 
 extern "C" gh_status gh_radial_topk(gh_handle h, int32_t k, int32_t *ids) {
@@ -1041,7 +1008,7 @@ extern "C" gh_status gh_integrate_normalise(gh_handle h, const float *Fs, const 
     GH_TRY_ST(gh_launch_integrate_given(h, h->d_tmpF.p, h->d_tmpF2.p));
     // normalise into scratch so the current positions stay unchanged
     GH_HIP(hipMemcpyAsync(h->d_tmpF.p, h->d_pos.p, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
-    GH_TRY_ST(gh_launch_normalise(h, false));
+    GH_TRY_ST(gh_launch_normalise(h, GH_FINISH_OWN, false));
     GH_TRY_ST(gh_launch_unpad(h, h->d_pos.p, h->d_io.p));
     GH_HIP(hipMemcpyAsync(out, h->d_io.p, bytes, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipMemcpyAsync(h->d_pos.p, h->d_tmpF.p, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));

@@ -108,7 +108,7 @@ struct gh_comm {
     ncclComm_t nccl = nullptr;          // RCCL backend
     gh_loop_group *loop = nullptr;      // loopback backend
     gh_dev<uint64_t> d_gathered;        // (world, S, K) keys of all ranks
-    gh_dev<double> d_stats_all;         // (world, stats rows, LD) statistics of all ranks (form C)
+    gh_dev<double> d_stats_gathered;    // (world, stats rows, LD) statistics of all ranks (form C)
     // form D: the all-gather of the new0 blocks runs beside the KNN tail, on a stream and a communicator of its own
     ncclComm_t nccl_b = nullptr;        // ncclCommSplit of `nccl` (same ranks); null: the loopback backend, or no overlap
     hipStream_t stream_b = nullptr;
@@ -173,7 +173,7 @@ extern "C" gh_status gh_comm_unique_id(void *out128) {
 
 static gh_status comm_common(gh_engine *h, int world, int rank) {
     if (h->comm) { h->err = "a communicator is already attached"; return GH_ERR_INVALID; }
-    if (h->g_world != world || h->g_rank != rank) {
+    if (h->xch.lay.world != world || h->xch.lay.rank != rank) {
         h->err = "call gh_rank_layout (or gh_gather_layout) with the same world and rank first";
         return GH_ERR_INVALID;
     }
@@ -181,12 +181,11 @@ static gh_status comm_common(gh_engine *h, int world, int rank) {
     if (!h->comm) { h->err = "out of host memory"; return GH_ERR_NOMEM; }
     h->comm->world = world;
     h->comm->rank = rank;
-    const size_t stats_doubles = (size_t)world * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
     // (16 spare bytes behind each)
     gh_status st = gh_alloc(h, h->comm->d_gathered, (size_t)world * h->S * (h->K + (h->cd_part ? 2 : 0)) + 2, false);
-    if (st == GH_OK) st = gh_alloc(h, h->comm->d_stats_all, stats_doubles + 2, false);
+    if (st == GH_OK) st = gh_alloc(h, h->comm->d_stats_gathered, (size_t)world * h->xch.lay.stats_doubles + 2, false);
     if (st != GH_OK) { h->comm.reset(); return st; }
-    if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: a second stream for the early all-gather of the rows, ordered against the engine's by two events
+    if (h->xch.is(GH_LAYOUT_OVERLAP)) {   // form D: a second stream for the early all-gather of the rows, ordered against the engine's by two events
         if (hipStreamCreateWithFlags(&h->comm->stream_b, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_fused, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->comm->ev_rows, hipEventDisableTiming) != hipSuccess) {
@@ -216,7 +215,7 @@ extern "C" gh_status gh_comm_init_rccl(gh_handle h, int32_t world, int32_t rank,
     // form D: the early all-gather needs a communicator of its own to be in flight beside the keys' and the statistics'.
     // Without ncclCommSplit (or if it fails -- on every rank alike: it is a collective call) the rows go out on the engine's
     // stream after the merge, form B's order: correct, nothing hidden.
-    if (h->layout == GH_LAYOUT_OVERLAP && api->CommSplit) {   // (also at world 1: the rehearsal of the N > 1 path on a one-GPU box takes the same route)
+    if (h->xch.is(GH_LAYOUT_OVERLAP) && api->CommSplit) {   // (also at world 1: the rehearsal of the N > 1 path on a one-GPU box takes the same route)
         if (api->CommSplit(h->comm->nccl, 0, rank, &h->comm->nccl_b, nullptr) != ncclSuccess) h->comm->nccl_b = nullptr;
     }
     return GH_OK;
@@ -260,20 +259,23 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
     GH_TRY_ST(gh_upload_sample_stream(h, iters, sample_stream, &d_ids));   // nullptr: device sampler / arange on every rank
     // a rank that fails leaves the loop: the loopback group must not wait for it (RCCL has its own abort paths)
     auto run = [&]() -> gh_status {
-        const size_t stats_bytes = sizeof(double) * (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
+        const gh_exchange &x = h->xch;
+        const gh_exchange_layout &l = x.lay;
+        // a (world, block) array to every rank, each sending its own block from where it will be received
+        auto gather_in_place = [&](void *blocks, size_t block, const char *what, bool side = false) {
+            return comm_all_gather(h, static_cast<unsigned char *>(blocks) + (size_t)c->rank * block, blocks, block, what, side);
+        };
         // form D: the own block of new0, packed to its travelling form, to every rank -- on the side stream or the engine's
         auto send_rows = [&](bool side) -> gh_status {
-            const size_t block = sizeof(float) * (size_t)h->g_chunk * gh_rows_all_row_floats(h);
-            unsigned char *rows = reinterpret_cast<unsigned char *>(gh_rows_all_device(h));
             GH_TRY_ST(gh_launch_pack_rows(h, side ? c->stream_b : h->stream));
-            return comm_all_gather(h, rows + (size_t)c->rank * block, rows, block, "allgather_rows", side);
+            return gather_in_place(x.travelling_rows(), l.rows_block_bytes(l.packed_rows()), "allgather_rows", side);
         };
         for (int32_t t = 0; t < iters; ++t) {
             GH_TRY_ST(gh_step_begin_device_ids(h, d_ids ? d_ids + (size_t)t * h->S : nullptr));
             // form D: new0 = pos + Fs of the own rows is complete -- its all-gather starts here, on the side stream when there
             // is a second communicator (RCCL) or on the engine's (loopback: the host rendezvous blocks either way), and runs
             // beside select -> keys -> merge + intersection -> statistics
-            const bool early = h->layout == GH_LAYOUT_OVERLAP && gh_step_rows_early(h);
+            const bool early = x.is(GH_LAYOUT_OVERLAP) && h->step.rows_early;
             const bool side = early && c->stream_b && (c->nccl_b || c->loop);
             const bool rows_sent = early && (side || c->loop);
             if (rows_sent) {
@@ -285,33 +287,28 @@ extern "C" gh_status gh_run_partitioned(gh_handle h, int32_t iters, const int32_
             }
             if (h->S > 0 && h->k > 0) {
                 GH_TRY_ST(comm_all_gather(h, h->d_partial.p, c->d_gathered.p, key_bytes, "allgather_keys"));
-                GH_TRY_ST(gh_step_merge(h, c->d_gathered.p, c->world));
+                GH_TRY_ST(gh_step_merge_keys(h, c->d_gathered.p, c->world));
             } else {
-                GH_TRY_ST(gh_step_merge(h, h->d_partial.p, 1));  // spring forces only: nothing to merge
+                GH_TRY_ST(gh_step_merge_keys(h, h->d_partial.p, 1));  // spring forces only: nothing to merge
             }
-            if (h->layout == GH_LAYOUT_OVERLAP) {   // form D: (the rows went out above, or go now)
+            if (x.is(GH_LAYOUT_OVERLAP)) {   // form D: (the rows went out above, or go now)
                 // a step without new0 (no fused kernel), or RCCL without a second communicator: form B's order
                 if (!rows_sent) GH_TRY_ST(send_rows(false));
-                GH_TRY_ST(comm_all_gather(h, h->d_stats, h->d_stats_all.p, sizeof(double) * (size_t)h->stats_block, "allgather_stats"));  // statistics + patch list
+                GH_TRY_ST(comm_all_gather(h, h->d_stats, x.d_late.p, l.late_bytes(), "allgather_stats"));  // statistics + patch list
                 if (early && side) {   // what of the early all-gather is still outstanding is this iteration's EXPOSED collective time
                     gh_scope t(h, "allgather_rows_exposed");
                     if (hipStreamWaitEvent(h->stream, c->ev_rows, 0) != hipSuccess) { h->err = "hipStreamWaitEvent failed"; return GH_ERR_HIP; }
                 }
-                GH_TRY_ST(gh_step_finish_overlap(h));
-            } else if (h->layout == GH_LAYOUT_GATHERED) {   // form B
-                GH_TRY_ST(comm_all_gather(h, h->d_gbuf.p + (size_t)c->rank * h->g_slot, h->d_gbuf.p, (size_t)h->g_slot, "allgather_slots"));
-                GH_TRY_ST(gh_step_finish_gathered(h));
+                GH_TRY_ST(gh_step_finish_as(h, GH_FINISH_ALL_ROWS));
+            } else if (x.is(GH_LAYOUT_GATHERED)) {   // form B
+                GH_TRY_ST(gather_in_place(x.d_rows.p, (size_t)l.slot_bytes, "allgather_slots"));
+                GH_TRY_ST(gh_step_finish_as(h, GH_FINISH_ALL_ROWS));
             } else {           // form C
-                GH_TRY_ST(comm_all_gather(h, h->d_stats, c->d_stats_all.p, stats_bytes, "allgather_stats"));
-                GH_TRY_ST(gh_step_finish_own(h, c->d_stats_all.p, c->world));
-                if (h->packed_exchange) {   // the blocks travel without their pad columns (12 instead of 16 bytes per row at D = 3)
-                    const size_t block = sizeof(float) * (size_t)h->g_chunk * h->D;
-                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_rows_packed.p) + (size_t)c->rank * block, h->d_rows_packed.p, block, "allgather_rows"));
-                    GH_TRY_ST(gh_launch_unpack_rows(h));
-                } else {
-                    const size_t block = sizeof(float) * (size_t)h->g_chunk * h->LD;
-                    GH_TRY_ST(comm_all_gather(h, reinterpret_cast<unsigned char *>(h->d_pos.p) + (size_t)c->rank * block, h->d_pos.p, block, "allgather_rows"));
-                }
+                GH_TRY_ST(comm_all_gather(h, h->d_stats, c->d_stats_gathered.p, l.late_bytes(), "allgather_stats"));
+                GH_TRY_ST(gh_step_finish_as(h, GH_FINISH_OWN_ALL_STATS, nullptr, c->d_stats_gathered.p));
+                // the finished blocks: without their pad columns (12 instead of 16 bytes per row at D = 3) and then expanded, or in place
+                GH_TRY_ST(gather_in_place(x.packed_exchange ? x.d_packed.p : h->d_pos.p, l.rows_block_bytes(x.packed_exchange), "allgather_rows"));
+                GH_TRY_ST(gh_launch_unpack_rows(h));   // (nothing unless packed)
             }
         }
         return GH_OK;

@@ -9,6 +9,7 @@
 #include "../../include/graphem_hip.h"
 #include "host_util.h"   // GH_HIP, GH_TRY_ST, GH_LAUNCH_CHECK
 #include "step_plan.h"   // gh_step_plan, gh_step_state and the sizes the choice of path depends on
+#include "exchange_layout.h"   // gh_exchange_layout, gh_stats_rows
 
 // Candidate-list capacity per query in the filtered KNN scan, and the LDS sort size.
 #define GH_CAND_CAP 16384   /* (8192 until round 3: one query of a 16 M-vertex run reached 8777 candidates and its exhaustive fallback cost 0.5 s) */
@@ -19,8 +20,6 @@
 #define GH_CNT_STRIDE 32
 // Spare rows behind the n positions so equal all-gather chunks fit for any world size <= this.
 #define GH_POS_PAD_ROWS 1024
-// Row pairs of corrections behind the (2, LD) column statistics: one per stats_fix workgroup.
-inline int gh_fix_blocks(int LD) { return LD <= 16 ? 2 * LD : 0; }
 // Coarse form of the threshold group minima (setup_core.h "COARSE FORM"): groups per query and the value of an empty entry
 // (the most keys a threshold may stand for, GH_CT_KMAX, is in step_plan.h).
 #define GH_CT_M 64
@@ -68,6 +67,20 @@ struct gh_ring {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
+};
+
+// The exchange of a row-partitioned step: the layout value and the buffers it sizes (exchange_layout.h describes both, and
+// alone knows how a slot or a late block is laid out).  Written by the layout setter (api.hip set_layout) only;
+// packed_exchange also by gh_set_packed_rows.
+struct gh_exchange {
+    gh_exchange_layout lay;
+    gh_dev<float> d_rows, d_packed;   // lay.rows_floats, lay.packed_floats
+    gh_dev<double> d_late;            // lay.late_all_doubles
+    bool packed_exchange = false;     // form C: the finished blocks travel packed (default: lay.packed_default)
+    bool is(int form) const { return lay.form == form; }
+    float *travelling_rows() const { return d_packed.p ? d_packed.p : d_rows.p; }   // forms B, D: what the rows' all-gather fills
+    // forms B, D: the buffer the ranks' statistics lie in (rank r's rows at lay.first_stats + r * lay.late_doubles)
+    double *stats_buffer() const { return is(GH_LAYOUT_GATHERED) ? reinterpret_cast<double *>(d_rows.p) : d_late.p; }
 };
 
 // Ownership is stated by type: a gh_dev member owns its device memory, a raw pointer is a view into memory owned
@@ -122,7 +135,7 @@ struct gh_engine {
     // state
     gh_dev<float> d_pos;          // (n, LD)
     gh_dev<float> d_new_buf;      // (rows, LD) the engine's own storage for ...
-    float *d_new = nullptr;       // ... the un-normalised update of own rows.  A view: d_new_buf, or block g_rank of d_gbuf (form B) / d_rows_all (form D)
+    float *d_new = nullptr;       // ... the un-normalised update of own rows.  A view: d_new_buf, or the own block of xch.d_rows (forms B, D)
     gh_dev<float> d_tmpF;         // (n, LD) scratch for the per-phase entry points
     gh_dev<float> d_tmpF2;
     gh_dev<float> d_io;           // (n, D) staging for unpadded host copies
@@ -160,22 +173,7 @@ struct gh_engine {
     gh_dev<uint16_t> d_qA;        // (S, 16) f16 A-operand rows of the split-f16 MFMA pre-filter (D <= 3), same kernel
     gh_dev<int32_t> d_order;          // internal row of every vertex (BFS reordering), or null: identity
     std::vector<int32_t> order_host;  // the same on the host (empty: identity)
-    gh_dev<unsigned char> d_gbuf;     // gather buffer of the one-collective finish (gh_gather_layout), or null
-    int64_t g_slot = 0, g_chunk = 0;  // slot bytes, rows per rank
-    int g_world = 0, g_rank = 0;
-    int layout = GH_LAYOUT_NONE;
-    gh_dev<float> d_rows_packed;      // form C, D < LD: (world, chunk, D) the finished blocks WITHOUT the pad columns -- what travels
-                                      // (12 instead of 16 bytes per row at 3 components); gh_step_unpack_rows expands it into d_pos
-    bool packed_exchange = false;     // ... in use (gh_set_packed_rows; default: from 2 M vertices on, where the saved quarter of
-                                      // the all-gather outweighs the expansion kernel -- 30 us at 4 M vertices, 14 at 1 M)
-    // form D (gh_overlap_layout): the ranks' un-normalised rows new0 = pos + Fs are all-gathered EARLY, beside the KNN tail
-    gh_dev<float> d_rows_all;         // (world, chunk, LD): d_new is block g_rank of it
-    gh_dev<float> d_rows_pk;          // (world, chunk, D): the same without pad columns -- what travels when D < LD -- or null
-    gh_dev<double> d_stats_all;       // (world, stats_block) doubles: per rank its statistics rows, then its PATCH LIST -- two int32 counters used by alternate iterations (16 bytes
-                                      // reserved) and patch_cap records (row as int32 bits, LD floats): the own rows the intersection phase touched, as
-                                      // finished by their owner, pos + (Fs + Fi); d_stats is block g_rank of it
-    int64_t stats_block = 0;          // doubles per rank in d_stats_all
-    int64_t patch_cap = 0;            // records per rank: min(4 S k, chunk)
+    gh_exchange xch;              // what a row partition exchanges to finish a step; d_new and d_stats may be views into it
     gh_dev<int32_t> d_qexact;     // [0] = count, [1..] = queries outside the f16 range (scanned exactly)
     gh_dev<uint64_t> d_cand;      // (S, GH_CAND_CAP)
     gh_dev<int32_t> d_cnt;        // (S * GH_CNT_STRIDE) one counter per 128-byte line
@@ -211,9 +209,9 @@ struct gh_engine {
     gh_dev<double> d_blockstats;    // (nblocks, 2, LD)
     int nblocks_update = 0;
     gh_dev<double> d_stats_buf;     // the engine's own storage for ...
-    double *d_stats = nullptr;      // ... (2 + 2*gh_fix_blocks(LD), LD): sum, sum of squares, then correction row pairs;
+    double *d_stats = nullptr;      // ... (gh_stats_rows(LD), LD): sum, sum of squares, then correction row pairs;
                                     // summed elementwise over the ranks by the caller when partitioned.  A view: d_stats_buf,
-                                    // or the own block of d_gbuf (form B) / d_stats_all (form D)
+                                    // or the own statistics in xch.d_rows (form B) / xch.d_late (form D)
 
     // thresholds inside the fused launch (tau_core.h; plan.tau == GH_TAUF_EMBEDDED)
     gh_dev<unsigned> d_tau_flag;         // queries published so far by the current fused launch
@@ -298,7 +296,7 @@ inline void gh_drop_lookahead(gh_engine *h) { h->lookahead.valid = false; }
 //   tcount_reset_pending  written: gh_knn_prepare, every step (the set-up was done ahead: a later launch of this step must
 //                         reset d_tcount).  read: the threshold launch, the grid build, the coarse query-cell launch.
 //   rows_early            set: step_begin under form D (new0 of the own rows is in its block: the rows may travel).
-//                         read: gh_step_rows_early, gh_step_finish_overlap, which clears it; gh_step_reset.
+//                         read: gh_step_rows_early, gh_step_finish_as, which clears it; gh_step_reset.
 //   own_ids               written: gh_step_begin / gh_step_begin_device_ids, every split step (called without ids: device
 //                         sampler / arange).  read: the gathered finishes (they set the next draw up).
 inline void gh_step_reset(gh_engine *h) {   // the start of a step's launches
@@ -311,6 +309,10 @@ inline void gh_step_intersect_done(gh_engine *h) { h->step.intersect_done = true
 inline void gh_step_tcount_reset_pending(gh_engine *h, bool pending) { h->step.tcount_reset_pending = pending; }
 inline void gh_step_set_rows_early(gh_engine *h, bool early) { h->step.rows_early = early; }
 inline void gh_step_own_ids(gh_engine *h, bool own) { h->step.own_ids = own; }
+
+// What a finish normalises, and from what: the own rows from the own statistics (single-rank steps, per-phase entry
+// points), the own rows from every rank's statistics (form C), all n rows from the gathered blocks (forms B and D).
+enum gh_finish_kind { GH_FINISH_OWN, GH_FINISH_OWN_ALL_STATS, GH_FINISH_ALL_ROWS };
 
 // RAII-free helper: records start/stop events around a launch when timing is on.
 struct gh_scope {
@@ -342,10 +344,12 @@ void gh_pull_lists(int64_t n, int64_t E, const int32_t *edges, std::vector<int32
 // api.hip
 void gh_replan(gh_engine *h);   // plan from the engine's sizes and requests: the only writer of it.  Drops a set-up done ahead when the threshold form changed
 // api.hip / comm.hip
-extern "C" float *gh_rows_all_device(gh_handle h);
-extern "C" int32_t gh_rows_all_row_floats(gh_handle h);
-extern "C" int32_t gh_step_rows_early(gh_handle h);
-extern "C" gh_status gh_step_finish_overlap(gh_handle h);
+// keys of all ranks -> merge, intersection forces, own rows integrated (gh_step_merge).  next: the ids the finish will set
+// the next iteration up from, when the caller knows them by now
+gh_status gh_step_merge_keys(gh_engine *h, const uint64_t *gathered, int world, const gh_ids *next = nullptr);
+// the one finish behind gh_step_finish / _gathered / _own / _overlap.  next: GH_FINISH_OWN, the ids of the next iteration
+// where known; stats_all: GH_FINISH_OWN_ALL_STATS, the (world, gh_stats_rows, LD) statistics of every rank
+gh_status gh_step_finish_as(gh_engine *h, gh_finish_kind kind, const gh_ids *next = nullptr, const double *stats_all = nullptr);
 gh_status gh_upload_sample_stream(gh_engine *h, int32_t iters, const int32_t *sample_stream, int32_t **d_ids);
 gh_status gh_step_begin_device_ids(gh_engine *h, int32_t *dev_ids);
 // f64.hip
@@ -399,17 +403,18 @@ gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next = nullptr);
 gh_status gh_launch_spring_only(gh_engine *h, float *d_F); // F (n, LD), own rows
 gh_status gh_launch_inter_to_dense(gh_engine *h, float *d_F);
 gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float *d_Fi);
-// d_new -> d_pos (pt.py:802-804).  The own rows from the own statistics; stats_all: form C, the own rows from every rank's
-// statistics; gathered: forms B / D, all n rows from every rank's rows and statistics where the layout holds them.
+// d_new -> d_pos (pt.py:802-804), rows and statistics from where `kind` says (gh_make_norm_src; stats_all: GH_FINISH_OWN_ALL_STATS).
 // next: also the KNN set-up of the next iteration from these ids, in the same launch (null: none)
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next = nullptr, bool gathered = false,
+gh_status gh_launch_normalise(gh_engine *h, gh_finish_kind kind, bool with_cleanup, const gh_ids *next = nullptr,
                               const double *stats_all = nullptr);
 gh_status gh_launch_unpack_rows(gh_engine *h);   // form C: the gathered packed blocks of the OTHER ranks -> their rows of d_pos
 struct gh_long_args;
 gh_long_args gh_make_long_args(const gh_engine *h, bool coop_mid = false);   // common.h; coop_mid: fused kernels
 gh_status gh_launch_spring_long(gh_engine *h, float *outF, int64_t f_row0);  // spring forces of the hub rows
-inline int32_t *gh_patch_count(gh_engine *h) { return reinterpret_cast<int32_t *>(h->d_stats + (size_t)(2 + 2 * gh_fix_blocks(h->LD)) * h->LD); }
-inline float *gh_patch_records(gh_engine *h) { return reinterpret_cast<float *>(gh_patch_count(h) + 4); }
+// form D: the counter this iteration's patch list is appended through (two, used by alternate iterations: patch_rows_kernel)
+// and its records; null under the other forms
+inline int32_t *gh_patch_count(gh_engine *h) { return h->xch.is(GH_LAYOUT_OVERLAP) ? reinterpret_cast<int32_t *>(h->d_stats + h->xch.lay.patch_counters) + (h->iter & 1) : nullptr; }
+inline float *gh_patch_records(gh_engine *h) { return h->xch.is(GH_LAYOUT_OVERLAP) ? reinterpret_cast<float *>(h->d_stats + h->xch.lay.patch_records) : nullptr; }
 gh_status gh_launch_new0(gh_engine *h);                            // form D without the fused kernel: d_new = pos + Fs of the own rows
 gh_status gh_launch_pack_rows(gh_engine *h, hipStream_t stream);   // form D: own block of new0 -> its packed slot (on the given stream)
 gh_status gh_launch_patch_rows(gh_engine *h);                      // form D: touched rows of the gathered array += Fi; accumulators zeroed

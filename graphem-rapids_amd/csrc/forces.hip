@@ -372,7 +372,7 @@ __device__ __forceinline__ void gh_clear_touched(double *__restrict__ acc, int32
     }
 }
 
-// Where a normalise launch reads (gh_launch_normalise builds it from the engine's layout).  Row j of the destination range
+// Where a normalise launch reads (gh_make_norm_src fills it from the exchange layout).  Row j of the destination range
 // [out_lo, out_lo + out_rows) of pos is row j % chunk of rank block j / chunk of the un-normalised rows; rank r's statistics
 // rows (sum, sum of squares, then the gh_fix_blocks correction pairs) start at stats + r * stats_block.
 struct gh_norm_src {
@@ -390,6 +390,24 @@ struct gh_norm_src {
         return p + j * RS;                           // 130 for the launch, one wave per SIMD less)
     }
 };
+// Every field from the engine and its exchange layout (exchange_layout.h): no arithmetic of its own.
+gh_norm_src gh_make_norm_src(const gh_engine *h, gh_finish_kind kind, const double *stats_all) {
+    const gh_exchange_layout &l = h->xch.lay;
+    gh_norm_src src{h->d_new, std::max<int64_t>(h->rows, 1), 0, h->LD, h->part.row_lo, h->rows, h->d_stats, 1, 0};
+    if (kind == GH_FINISH_OWN) return src;
+    src.world = l.world;
+    src.stats_block = l.late_doubles;
+    src.stats = stats_all;   // form C: the statistics rows of every rank, all-gathered in rank order
+    if (kind == GH_FINISH_OWN_ALL_STATS) return src;
+    // form B: both halves of the gathered slots; form D: the early-gathered rows (packed or not), the late-gathered statistics
+    src.rows = h->xch.travelling_rows();
+    src.RS = l.row_floats;
+    src.chunk = std::min(l.chunk, h->n);
+    src.block = l.block_floats;
+    src.out_lo = 0; src.out_rows = h->n;
+    src.stats = h->xch.stats_buffer() + l.first_stats;
+    return src;
+}
 
 // pt.py:802-804: centre by the column mean, divide by (unbiased std + 1e-6), into rows [out_lo, out_lo + out_rows) of pos:
 // the own rows (single-rank steps, per-phase entry points, form C) or all n rows (forms B and D, include/graphem_hip.h).
@@ -850,9 +868,7 @@ gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next) {
                 stats_fix_kernel<ld()><<<dim3(gh_fix_blocks(ld()) + gather), dim3(256), 0, h->stream>>>(
                     h->d_blockstats.p, h->n_vblocks, h->d_pos.p, h->d_Fs.p, h->d_acc.p, h->d_touched.p, h->d_tcount.p, h->part.row_lo,
                     h->rows, h->d_new, h->d_stats, reduced ? 1 : 0,
-                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr,
-                    h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr, (int)h->patch_cap, sa, h->d_tflag.p,
-                    h->d_setup_rows.p);
+                    gh_patch_count(h), gh_patch_records(h), (int)h->xch.lay.patch_cap, sa, h->d_tflag.p, h->d_setup_rows.p);
             })) {   // unreachable: only gh_launch_spring_scan sets new0_ready, and it needs one of these strides
             h->err = "stats_fix: the fused step left its sums for a row stride other than 4, 8 or 16";
             return GH_ERR_RUNTIME;
@@ -870,9 +886,9 @@ gh_status gh_launch_integrate(gh_engine *h, const gh_ids *next) {
     const unsigned grid = grid_for(h->rows, 256);
     // form D: the own block (d_new) holds new0 and is on its way to the other ranks: statistics as always, the touched rows'
     // values into the patch list (row strides of 4, 8, 16 floats: gh_overlap_layout refuses the others)
-    int32_t *pc = h->layout == GH_LAYOUT_OVERLAP ? gh_patch_count(h) + (h->iter & 1) : nullptr;   // (two counters, alternate iterations: patch_rows_kernel)
-    float *pr = h->layout == GH_LAYOUT_OVERLAP ? gh_patch_records(h) : nullptr;
-    const int pcap = (int)h->patch_cap;
+    int32_t *pc = gh_patch_count(h);
+    float *pr = gh_patch_records(h);
+    const int pcap = (int)h->xch.lay.patch_cap;
     float *wide_out = h->d_new;
     {
         gh_scope t(h, "integrate");
@@ -941,7 +957,7 @@ gh_status gh_launch_inter_cleanup(gh_engine *h) {
 }
 
 gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float *d_Fi) {
-    GH_HIP(hipMemsetAsync(h->d_stats, 0, sizeof(double) * (2 + 2 * gh_fix_blocks(h->LD)) * h->LD, h->stream));
+    GH_HIP(hipMemsetAsync(h->d_stats, 0, sizeof(double) * gh_stats_rows(h->LD) * h->LD, h->stream));
     // whole graph on one rank only (per-phase entry point)
     const int64_t total = h->n * h->LD;
     integrate_given_kernel<<<dim3(grid_for(total, 256)), dim3(256), 0, h->stream>>>(h->d_pos.p, d_Fs, d_Fi, total,
@@ -953,33 +969,13 @@ gh_status gh_launch_integrate_given(gh_engine *h, const float *d_Fs, const float
 
 // next: also run the next iteration's KNN set-up in this launch (single-rank fused steps, forms B and D), for the sample
 // source the caller expects then.
-gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *next, bool gathered, const double *stats_all) {
+gh_status gh_launch_normalise(gh_engine *h, gh_finish_kind kind, bool with_cleanup, const gh_ids *next, const double *stats_all) {
     // the stats_fix launch in front of this one staged the rows of exactly this set-up (single-rank steps only)
-    const bool staged = !gathered && !stats_all && gh_lookahead_rows_for(h, next);
+    const bool staged = kind == GH_FINISH_OWN && gh_lookahead_rows_for(h, next);
     gh_set_lookahead(h, nullptr);  // positions change: whatever set-up was done ahead is stale
-    const int R = 2 + 2 * gh_fix_blocks(h->LD);
-    gh_norm_src src{h->d_new, std::max<int64_t>(h->rows, 1), 0, h->LD, h->part.row_lo, h->rows, h->d_stats, 1, 0};
-    if (stats_all) {   // form C: the statistics rows of every rank, all-gathered in rank order
-        src.stats = stats_all;
-        src.world = h->g_world;
-        src.stats_block = (int64_t)R * h->LD;
-    }
-    if (gathered) {   // form B: both halves of the gathered slots; form D: the early-gathered rows (packed or not) and the
-                      // late-gathered statistics
-        const bool overlap = h->layout == GH_LAYOUT_OVERLAP;
-        src.RS = overlap && h->d_rows_pk.p ? h->D : h->LD;
-        src.rows = overlap ? (h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p) : reinterpret_cast<const float *>(h->d_gbuf.p);
-        src.chunk = std::min(h->g_chunk, h->n);
-        src.block = overlap ? h->g_chunk * src.RS : h->g_slot / (int64_t)sizeof(float);
-        src.out_lo = 0;
-        src.out_rows = h->n;
-        src.stats = overlap ? h->d_stats_all.p : reinterpret_cast<const double *>(h->d_gbuf.p + h->g_chunk * h->LD * (int64_t)sizeof(float));
-        src.world = h->g_world;
-        src.stats_block = overlap ? h->stats_block : h->g_slot / (int64_t)sizeof(double);
-        if (!h->plan.presetup_gathered) next = nullptr;
-    }
+    const gh_norm_src src = gh_make_norm_src(h, kind, stats_all);
     if (src.out_rows == 0) return with_cleanup ? gh_launch_inter_cleanup(h) : GH_OK;
-    gh_scope t(h, gathered ? "normalise_gathered" : stats_all ? "normalise_own" : "normalise");
+    gh_scope t(h, kind == GH_FINISH_ALL_ROWS ? "normalise_gathered" : kind == GH_FINISH_OWN_ALL_STATS ? "normalise_own" : "normalise");
     unsigned grid = grid_for(src.out_rows * h->LD / 4, 1024);  // four float4 elements per thread and round (normalise_kernel)
     if (grid > 2048) grid = 2048;
     gh_setup_args sa{};
@@ -990,9 +986,10 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
         if (staged && sa.tiles > 0) sa.rows = h->d_setup_rows.p;
         if (sa.cmin) GH_TRY_ST(gh_cmin_claim(h, h->iter + 1));
     }
-    const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(R + (src.world > 1 ? 2 : 0)) * h->LD;
-    float *packed = stats_all && h->packed_exchange ? h->d_rows_packed.p + (size_t)h->g_rank * h->g_chunk * h->D : nullptr;
-    const int ldt = stats_all ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
+    const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(gh_stats_rows(h->LD) + (src.world > 1 ? 2 : 0)) * h->LD;
+    const bool form_c = kind == GH_FINISH_OWN_ALL_STATS;
+    float *packed = form_c && h->xch.packed_exchange ? h->xch.d_packed.p + h->xch.lay.own_packed : nullptr;
+    const int ldt = form_c ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
     const auto normalise = [&](auto ld) {   // 0: any row stride, no set-up tiles
         const auto launch = [&](auto kernel) {
             kernel<<<dim3(grid + extra), dim3(256), smem, h->stream>>>(
@@ -1018,7 +1015,7 @@ gh_status gh_launch_normalise(gh_engine *h, bool with_cleanup, const gh_ids *nex
 }
 
 // Form C with fewer components than the row stride: the blocks travel without their pad columns.  After the all-gather of
-// d_rows_packed (world, chunk, D): the other ranks' rows -> d_pos (the own block was written in place by the normalise launch).
+// xch.d_packed (world, chunk, D): the other ranks' rows -> d_pos (the own block was written in place by the normalise launch).
 __global__ __launch_bounds__(256) void unpack_rows_kernel(const float *__restrict__ packed, int64_t n, int D, int LD, int64_t own_lo,
                                                          int64_t own_hi, float *__restrict__ pos) {
     const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;   // element (row, d) of the padded array
@@ -1029,9 +1026,9 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const float *__restric
     pos[t] = d < D ? packed[row * D + d] : 0.0f;
 }
 gh_status gh_launch_unpack_rows(gh_engine *h) {
-    if (!h->packed_exchange) return GH_OK;
+    if (!h->xch.packed_exchange) return GH_OK;
     gh_scope t(h, "unpack_rows");
-    unpack_rows_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(h->d_rows_packed.p, h->n, h->D, h->LD, h->part.row_lo,
+    unpack_rows_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(h->xch.d_packed.p, h->n, h->D, h->LD, h->part.row_lo,
                                                                                        h->part.row_hi, h->d_pos.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
@@ -1053,11 +1050,11 @@ gh_status gh_launch_new0(gh_engine *h) {
     return GH_OK;
 }
 gh_status gh_launch_pack_rows(gh_engine *h, hipStream_t stream) {
-    if (!h->d_rows_pk.p || h->rows == 0) return GH_OK;
+    if (!h->xch.d_packed.p || h->rows == 0) return GH_OK;
     gh_scope t(h, "pack_rows", stream);
     // (chunk rows, not only the real ones: the block of a rank with fewer rows must not travel with stale bytes)
-    pack_rows_kernel<<<dim3(grid_for(h->g_chunk * h->D, 256)), dim3(256), 0, stream>>>(h->d_new, h->g_chunk, h->D, h->LD,
-                                                                                        h->d_rows_pk.p + (size_t)h->g_rank * h->g_chunk * h->D);
+    const gh_exchange_layout &l = h->xch.lay;
+    pack_rows_kernel<<<dim3(grid_for(l.chunk * h->D, 256)), dim3(256), 0, stream>>>(h->d_new, l.chunk, h->D, h->LD, h->xch.d_packed.p + l.own_packed);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }
@@ -1091,10 +1088,10 @@ gh_status gh_launch_patch_rows(gh_engine *h) {
     const int64_t maxT = std::max<int64_t>(4 * h->S * h->k * h->LD, 256);
     unsigned grid = grid_for(maxT, 256);
     if (grid > 64) grid = 64;
-    const int stat_doubles = (2 + 2 * gh_fix_blocks(h->LD)) * h->LD;
-    patch_rows_kernel<<<dim3(grid, (unsigned)h->g_world), dim3(256), 0, h->stream>>>(
-        h->d_rows_pk.p ? h->d_rows_pk.p : h->d_rows_all.p, h->d_rows_pk.p ? h->D : h->LD, h->D, h->LD, h->d_stats_all.p, h->stats_block, stat_doubles,
-        h->g_rank, (int)h->patch_cap, (int)(h->iter & 1), h->d_acc.p, h->d_tflag.p, h->d_touched.p, h->d_tcount.p);
+    const gh_exchange_layout &l = h->xch.lay;
+    patch_rows_kernel<<<dim3(grid, (unsigned)l.world), dim3(256), 0, h->stream>>>(
+        h->xch.travelling_rows(), l.row_floats, h->D, h->LD, h->xch.d_late.p, l.late_doubles, (int)l.patch_counters,
+        l.rank, (int)l.patch_cap, (int)(h->iter & 1), h->d_acc.p, h->d_tflag.p, h->d_touched.p, h->d_tcount.p);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }

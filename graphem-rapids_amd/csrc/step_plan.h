@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/graphem_hip.h"   // GH_KNN_*, GH_FILTER_*, GH_COARSE_*
+#include "exchange_layout.h"             // GH_LAYOUT_*: how a partitioned engine finishes a step
 
 // ---- sizes the choice depends on (the device headers take them from here) ----------------------------------------------
 #define GH_SCAN_MIN_EDGES 16384   /* below this many searched edges the per-query block kernel scans everything itself */
@@ -23,10 +24,6 @@
 #define GH_FUSED_TILE (GH_FUSED_NT * GH_FUSED_R)
 // A fused launch of at most this many workgroups is a single round or little more: thresholds inside it (gh_tau_place)
 #define GH_TAU_EMBED_MAX_VBLOCKS 2048
-
-// How a partitioned engine finishes a step (include/graphem_hip.h): set by gh_gather_layout (form B), gh_rank_layout
-// (form C), gh_overlap_layout (form D).
-enum { GH_LAYOUT_NONE = 0, GH_LAYOUT_GATHERED, GH_LAYOUT_RANK, GH_LAYOUT_OVERLAP };
 
 // ---- input: what the engine is ---------------------------------------------------------------------------------------
 struct gh_plan_input {

@@ -42,6 +42,9 @@ REMOVED_FUNCTIONS = ["gh_knn_scan_path", "gh_grid_path", "gh_ivf_path", "gh_fuse
                      "fused_mfma", "fused_mfma_kb", "subset_stride"]
 REMOVED_MEMBERS = ["qcells", "tau_embedded", "tau_embedded_plan", "coarse_tau", "coarse_mode", "scan_filter", "opt_no_presetup",
                    "thr_stride", "thr_M1", "last_step_own_ids",
+                   # the exchange of a partitioned step: now h->xch, its layout value made by csrc/exchange_layout.h
+                   "d_gbuf", "g_slot", "g_chunk", "g_world", "g_rank", "layout", "d_rows_packed", "packed_exchange", "d_rows_all",
+                   "d_rows_pk", "d_stats_all", "stats_block", "patch_cap",
                    # the step flags: now in h->step, written through the gh_step_* functions of engine.h
                    "new0_ready", "intersect_done", "stats_reduced", "tcount_reset_pending", "rows_early"]
 STEP_FLAGS = REMOVED_MEMBERS[-5:] + ["own_ids"]
