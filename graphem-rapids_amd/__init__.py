@@ -17,7 +17,7 @@ from .generators import (erdos_renyi_graph, generate_random_regular, erdos_renyi
                          watts_strogatz_edges, powerlaw_cluster_edges, scale_free_edges, relaxed_caveman_edges)
 from .influence import (InfluenceGraph, influence_spread, ndlib_estimated_influence, greedy_seed_selection,
                         run_influence_benchmark, RRCollection, max_coverage, ris_seed_selection, kshell_seed_selection,
-                        arc_probabilities, trivalency_probabilities)
+                        arc_probabilities, trivalency_probabilities, lt_weights, linear_threshold)
 from .centrality import (CentralityGraph, betweenness_centrality, load_centrality, closeness_centrality, pagerank,
                          eigenvector_centrality_numpy, run_benchmark, benchmark_correlations)
 from . import graphstats
@@ -93,6 +93,7 @@ __all__ = ["create_graphem", "get_backend_info", "GraphEmbedderHIP", "BackendCon
            "get_optimal_chunk_size", "monitor_memory_usage", "InfluenceGraph", "influence_spread",
            "ndlib_estimated_influence", "greedy_seed_selection", "run_influence_benchmark", "RRCollection", "max_coverage",
            "ris_seed_selection", "kshell_seed_selection", "arc_probabilities", "trivalency_probabilities",
+           "lt_weights", "linear_threshold",
            "CentralityGraph", "betweenness_centrality", "load_centrality", "closeness_centrality", "pagerank",
            "eigenvector_centrality_numpy", "run_benchmark", "benchmark_correlations",
            "generate_sbm", "generate_ba", "generate_ws", "generate_power_cluster", "generate_scale_free",

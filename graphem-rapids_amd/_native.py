@@ -146,6 +146,9 @@ SIGNATURES = {
     "gh_ic_set_arc_probabilities": (_int, [vp, i64, vp, vp]),
     "gh_ic_spread_arcs": (_int, [vp, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
     "gh_ic_rr_sample_arcs": (_int, [vp, vp, i32, u64, i64, vp, vp]),
+    "gh_ic_set_lt_weights": (_int, [vp, i64, vp, vp]),
+    "gh_ic_spread_lt": (_int, [vp, i32, i32, u64, i64, vp, vp, vp, i64, vp, vp]),
+    "gh_ic_rr_sample_lt": (_int, [vp, vp, i32, u64, i64, vp, vp]),
     "gh_rr_create": (_int, [_P(vp), _int, i64]),
     "gh_rr_destroy": (None, [vp]),
     "gh_rr_last_error": (_str, [vp]),
@@ -611,6 +614,9 @@ class Engine(Handle):
         return out
 
 
+LT = "lt"   # what ICGraph.spread / rr_sample take as p for the handle's Linear Threshold table
+
+
 class ICGraph(BudgetHandle):
     """Thin RAII wrapper over a gh_ic_handle: Monte Carlo Independent Cascade on one graph (include/graphem_hip.h).
     Memory budget: device bytes of chunk state a spread call may hold, 1 GiB by default."""
@@ -634,10 +640,22 @@ class ICGraph(BudgetHandle):
         pairs = np.ascontiguousarray(pairs, dtype=np.int32)
         self._raise(self.lib.gh_ic_set_arc_probabilities(self.handle, len(pairs), ptr(pairs), ptr(prob)))
 
+    def set_lt_weights(self, pairs, weight):
+        """The handle's Linear Threshold table (gh_ic_set_lt_weights): pairs (m, 2) directed u -> v, weight (m,) float64.
+        Arcs that are not listed get weight 0; a failed call keeps the previous table.  The per-arc table is another one."""
+        pairs = np.asarray(pairs).reshape(-1, 2)
+        weight = np.ascontiguousarray(np.asarray(weight).ravel(), dtype=np.float64)
+        if len(weight) != len(pairs):
+            raise ValueError(f"{len(pairs)} pairs but {len(weight)} weights")
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= self.n):   # before the cast to int32 can wrap an id
+            raise ValueError(f"pair endpoints must lie in [0, {self.n})")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        self._raise(self.lib.gh_ic_set_lt_weights(self.handle, len(pairs), ptr(pairs), ptr(weight)))
+
     def spread(self, sets, p, n_trials, seed=0, max_hops=-1, base=None, per_trial=False):
         """sets: a list of vertex-id sequences.  Returns totals (n_sets,) int64 and, with per_trial, the (n_sets, n_trials)
         int32 counts; with a base set both are marginal over it (gh_ic_spread; p=None: the handle's per-arc table,
-        gh_ic_spread_arcs)."""
+        gh_ic_spread_arcs; p=LT: its Linear Threshold table, gh_ic_spread_lt)."""
         sets = [np.asarray(s, dtype=np.int64).ravel() for s in sets]
         offsets = np.zeros(len(sets) + 1, dtype=np.int64)
         offsets[1:] = np.cumsum([len(s) for s in sets])
@@ -647,14 +665,16 @@ class ICGraph(BudgetHandle):
         trials = np.zeros((len(sets), int(n_trials)), dtype=np.int32) if per_trial else None
         rest = (int(max_hops), int(n_trials), int(seed) & 0xFFFFFFFFFFFFFFFF, len(sets), ptr(offsets), ptr(verts), ptr(base),
                 len(base), ptr(totals), ptr(trials))
-        self._raise(self.lib.gh_ic_spread_arcs(self.handle, *rest) if p is None else
+        self._raise(self.lib.gh_ic_spread_lt(self.handle, *rest) if (isinstance(p, str) and p == LT) else
+                    self.lib.gh_ic_spread_arcs(self.handle, *rest) if p is None else
                     self.lib.gh_ic_spread(self.handle, float(p), *rest))
         return (totals, trials) if per_trial else totals
 
 
     def rr_sample(self, rr, n_samples, p, seed=0, max_hops=-1, trials=None, roots=None):
         """Appends n_samples reverse-reachable sets to the RRSets `rr` (gh_ic_rr_sample); trials uint64 / roots int32 of
-        n_samples, or None for the header's defaults.  p=None: the handle's per-arc table (gh_ic_rr_sample_arcs)."""
+        n_samples, or None for the header's defaults.  p=None: the handle's per-arc table (gh_ic_rr_sample_arcs); p=LT: its
+        Linear Threshold table (gh_ic_rr_sample_lt)."""
         n_samples = int(n_samples)
         if trials is not None:
             trials = np.ascontiguousarray(np.asarray(trials).ravel(), dtype=np.uint64)
@@ -664,7 +684,8 @@ class ICGraph(BudgetHandle):
             if a is not None and len(a) != n_samples:
                 raise ValueError(f"trials and roots must have n_samples = {n_samples} entries")
         rest = (int(max_hops), int(seed) & 0xFFFFFFFFFFFFFFFF, n_samples, ptr(trials), ptr(roots))
-        self._raise(self.lib.gh_ic_rr_sample_arcs(self.handle, rr.handle, *rest) if p is None else
+        self._raise(self.lib.gh_ic_rr_sample_lt(self.handle, rr.handle, *rest) if (isinstance(p, str) and p == LT) else
+                    self.lib.gh_ic_rr_sample_arcs(self.handle, rr.handle, *rest) if p is None else
                     self.lib.gh_ic_rr_sample(self.handle, rr.handle, float(p), *rest))
 
 

@@ -21,6 +21,11 @@
 // Probabilities: one threshold for the whole graph (gh_ic_spread, gh_ic_rr_sample), or one per arc from two arrays aligned
 // with the CSR slots (gh_ic_set_arc_probabilities; gh_ic_spread_arcs, gh_ic_rr_sample_arcs run the ARC instantiations of
 // push and pull).  The coin and its key are the same in both.
+//
+// Linear Threshold (gh_ic_set_lt_weights; gh_ic_spread_lt, gh_ic_rr_sample_lt): the same levels with lt_push_kernel /
+// lt_pull_kernel as the next-word launches.  In a trial every vertex selects at most one in-arc: the arc whose fixed-point
+// interval [lo, hi) of the target's row holds the 32-bit pick of (trial, target).  Every CSR slot carries the (lo, hi) of
+// its arc, in both CSRs, so a launch never looks into another row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -82,6 +87,8 @@ struct IcLevel {
     // ARC: the threshold of the arc in each slot of out_adj / in_adj.  Last, so that the scalar instantiations read every
     // other member where they always did.
     const uint32_t *out_thr, *in_thr;
+    // LT: the interval (lo, hi) of the arc in each slot of out_adj / in_adj, within the row of the arc's original target
+    const uint2 *out_iv, *in_iv;
 };
 
 // REV (reverse-reachable sets, gh_ic_rr_sample): the host swaps the two CSRs, so a level walks every arc backwards; the
@@ -206,6 +213,142 @@ template <bool REV, bool ARC> __global__ __launch_bounds__(IC_BLOCK) void ic_pul
     }
 }
 
+// ---- Linear Threshold ----------------------------------------------------------------------------------------------------
+// pick(seed, t, v): the trial's word mixed with the self-loop key (v, v), which no arc coin has; the top 32 bits.
+__device__ __forceinline__ uint32_t lt_pick(uint64_t h, int32_t v) {
+    return (uint32_t)(ic_mix(h ^ (((uint64_t)(uint32_t)v << 32) | (uint32_t)v)) >> 32);
+}
+
+// The pick belongs to the arc's ORIGINAL target.  Forward push walks u's out-arcs, so the target is the neighbour: one mix
+// per arc and lane, as the IC coin costs (a slot with an empty interval costs nothing).  Reverse push walks the arcs INTO u
+// backwards, so the target is u itself: one pick per (entry, word), and a slot costs two compares against its (lo, hi),
+// broadcast beside the neighbour id.
+template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void lt_push_kernel(IcLevel a) {
+    const int64_t cnt = *a.cur_cnt;
+    if (cnt == 0 || cnt >= a.pull_min) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t items = cnt * a.W;
+    const int64_t nwaves = (int64_t)gridDim.x * (IC_BLOCK / 64);
+    for (int64_t i0 = ((int64_t)blockIdx.x * (IC_BLOCK / 64) + (threadIdx.x >> 6)) * 64; i0 < items; i0 += nwaves * 64) {
+        const int64_t i = i0 + lane;
+        int32_t e = 0, w = 0;
+        uint64_t f = 0;
+        if (i < items) {
+            e = a.cur_list[i / a.W];
+            w = (int32_t)(i % a.W);
+            f = a.cur[(int64_t)e * a.W + w];
+        }
+        uint64_t todo = __ballot(f != 0);
+        while (todo) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const int32_t ej = uni(__shfl(e, j)), wj = uni(__shfl(w, j));
+            const uint64_t fj = uni64(__shfl(f, j));
+            const int64_t s = ej / a.n;
+            const int32_t u = (int32_t)(ej - s * a.n);
+            const uint64_t h = ic_lane_word<REV>(a, wj, lane);
+            uint32_t pk = 0;
+            if constexpr (REV) pk = lt_pick(h, u);
+            const int64_t beg = a.out_ptr[u], end = a.out_ptr[u + 1];
+            for (int64_t k0 = beg; k0 < end; k0 += 64) {
+                int32_t vk = 0;
+                uint2 ck = make_uint2(0, 0);
+                if (k0 + lane < end) {
+                    vk = a.out_adj[k0 + lane];
+                    ck = a.out_iv[k0 + lane];
+                }
+                const int m = (int)min((int64_t)64, end - k0);
+                uint64_t mine = 0;
+                for (int q = 0; q < m; ++q) {
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)ck.x, q);
+                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)ck.y, q);
+                    if (lo == hi) continue;   // a zero-weight arc: nobody selects it
+                    if constexpr (!REV) pk = lt_pick(h, __builtin_amdgcn_readlane(vk, q));
+                    const uint64_t live = __ballot(pk >= lo && pk < hi) & fj;
+                    if (lane == q) mine = live;
+                }
+                if (mine) {
+                    const int64_t ev = s * a.n + vk;
+                    const uint64_t nw = mine & ~a.vis[ev * a.W + wj];
+                    if (nw) {
+                        atomicOr((unsigned long long *)&a.nxt[ev * a.W + wj], (unsigned long long)nw);
+                        ic_append(a, (int32_t)ev);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Forward pull walks the arcs into v, so v is the target: one pick per (entry, word), two compares per slot whose source is
+// in the frontier.  The slots of v's row ascend in cumulative weight (the row IS the target's row), so after a batch whose
+// last bound is c every trial with pick < c has had its one selected source looked at, and the row stops once no unvisited
+// trial is left beyond that.  Reverse pull walks v's out-arcs backwards: the target is the neighbour, one mix per arc whose
+// target is in the frontier.
+template <bool REV> __global__ __launch_bounds__(IC_BLOCK) void lt_pull_kernel(IcLevel a) {
+    const int64_t cnt = *a.cur_cnt;
+    if (cnt == 0 || cnt < a.pull_min) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * (IC_BLOCK / 64);
+    for (int64_t i0 = ((int64_t)blockIdx.x * (IC_BLOCK / 64) + (threadIdx.x >> 6)) * 64; i0 < a.dense; i0 += nwaves * 64) {
+        const int64_t i = i0 + lane;   // word index: entry i / W, word i % W
+        uint64_t unv = 0;
+        if (i < a.dense) unv = ~a.vis[i] & ic_valid((int)(i % a.W), a.W, a.T);
+        uint64_t todo = __ballot(unv != 0);
+        while (todo) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const int64_t ij = (int64_t)uni64((uint64_t)(i0 + j));
+            const uint64_t uj = uni64(__shfl(unv, j));
+            const int32_t e = uni((int32_t)(ij / a.W)), wj = uni((int32_t)(ij % a.W));
+            const int64_t s = e / a.n;
+            const int32_t v = (int32_t)(e - s * a.n);
+            const uint64_t *cw = a.cur + s * a.n * a.W + wj;
+            uint64_t acc = 0, h = 0;
+            uint32_t pk = 0;
+            bool have_h = false;
+            const int64_t beg = a.in_ptr[v], end = a.in_ptr[v + 1];
+            for (int64_t k0 = beg; k0 < end && acc != uj; k0 += 64) {
+                int32_t uk = 0;
+                uint2 ck = make_uint2(0, 0);
+                uint64_t fk = 0;
+                if (k0 + lane < end) {
+                    uk = a.in_adj[k0 + lane];
+                    ck = a.in_iv[k0 + lane];
+                    if (ck.x != ck.y) fk = cw[(int64_t)uk * a.W] & uj;
+                }
+                uint64_t arcs = __ballot(fk != 0);
+                while (arcs && acc != uj) {
+                    const int q = __ffsll((unsigned long long)arcs) - 1;
+                    arcs &= arcs - 1;
+                    const uint64_t f = uni64(__shfl(fk, q)) & ~acc;
+                    if (f == 0) continue;
+                    if (!have_h) {
+                        h = ic_lane_word<REV>(a, wj, lane);
+                        if constexpr (!REV) pk = lt_pick(h, v);
+                        have_h = true;
+                    }
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)ck.x, q);
+                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)ck.y, q);
+                    if constexpr (REV) pk = lt_pick(h, __builtin_amdgcn_readlane(uk, q));
+                    acc |= __ballot(pk >= lo && pk < hi) & f;
+                }
+                if constexpr (!REV) {
+                    if (have_h) {
+                        const int last = uni((int32_t)min((int64_t)64, end - k0)) - 1;
+                        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int32_t)ck.y, last);
+                        if ((uj & ~acc & ~__ballot(pk < c)) == 0) break;
+                    }
+                }
+            }
+            if (acc && lane == 0) {
+                a.nxt[ij] = acc;
+                ic_append(a, e);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(IC_BLOCK) void ic_advance_kernel(IcLevel a) {
     const int64_t ncur = (int64_t)*a.cur_cnt * a.W, nnew = (int64_t)*a.nxt_cnt * a.W;
     const int64_t stride = (int64_t)gridDim.x * IC_BLOCK;
@@ -301,6 +444,10 @@ struct gh_ic : gh_host {
     std::vector<uint64_t> keys;                 // the canonical arc keys, ascending: what the setter resolves pairs against
     bool has_table = false;
     gh_dev<uint32_t> d_out_thr, d_in_thr;
+    // Linear Threshold intervals (gh_ic_set_lt_weights): (lo, hi) per slot of d_out_adj / of the in-CSR; graph state of its
+    // own beside the per-arc table, not budgeted
+    bool has_lt = false;
+    gh_dev<uint2> d_out_iv, d_in_iv;
     // chunk state, grown on demand
     int64_t cap_words = 0, cap_ents = 0, cap_counts = 0;
     gh_dev<uint64_t> d_vis, d_fa, d_fb;
@@ -356,20 +503,32 @@ template <bool REV, bool ARC> void ic_launch_level(const gh_ic *h, const IcLevel
     ic_pull_kernel<REV, ARC><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
     ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
 }
+template <bool REV> void lt_launch_level(const gh_ic *h, const IcLevel &a, int grid) {
+    lt_push_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+    lt_pull_kernel<REV><<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+    ic_advance_kernel<<<dim3(grid), dim3(IC_BLOCK), 0, h->stream>>>(a);
+}
 
-// The probability model of a call: the one threshold of p, or the handle's per-arc table.
+// The diffusion model of a call: the one threshold of p, the handle's per-arc table, or its Linear Threshold intervals.
 struct IcProb {
     bool arc;
     uint32_t thr;   // !arc
+    bool lt = false;
 };
+
+// What picks the model at an entry point: p for the scalar, and for p = NULL the table named here.
+enum IcTable { IC_TABLE_ARCS, IC_TABLE_LT };
 
 inline uint32_t ic_threshold(double p) { return (uint32_t)std::min(16777216.0, std::floor(p * 16777216.0 + 0.5)); }
 
 // What the scalar and the per-arc entry points check of their probability argument.
-gh_status ic_prob(gh_ic *h, const double *p, IcProb *out) {
+gh_status ic_prob(gh_ic *h, const double *p, IcTable table, IcProb *out) {
     if (p) {
         if (!(*p >= 0.0 && *p <= 1.0)) { h->err = "p must be in [0, 1]"; return GH_ERR_INVALID; }
         *out = IcProb{false, ic_threshold(*p)};
+    } else if (table == IC_TABLE_LT) {
+        if (!h->has_lt) { h->err = "no Linear Threshold weights have been set (gh_ic_set_lt_weights)"; return GH_ERR_INVALID; }
+        *out = IcProb{false, 0, true};
     } else {
         if (!h->has_table) { h->err = "no arc probabilities have been set (gh_ic_set_arc_probabilities)"; return GH_ERR_INVALID; }
         *out = IcProb{true, 0};
@@ -384,6 +543,7 @@ gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t s
     a.out_ptr = REV ? h->d_in_ptr : h->d_out_ptr.p; a.out_adj = REV ? h->d_in_adj : h->d_out_adj.p;
     a.in_ptr = REV ? h->d_out_ptr.p : h->d_in_ptr; a.in_adj = REV ? h->d_out_adj.p : h->d_in_adj;
     if (prob.arc) { a.out_thr = REV ? h->d_in_thr.p : h->d_out_thr.p; a.in_thr = REV ? h->d_out_thr.p : h->d_in_thr.p; }
+    if (prob.lt) { a.out_iv = REV ? h->d_in_iv.p : h->d_out_iv.p; a.in_iv = REV ? h->d_out_iv.p : h->d_in_iv.p; }
     a.vis = h->d_vis.p; a.mark = h->d_mark.p; a.touched = h->d_touched.p; a.touch_list = h->d_touch.p; a.touch_cnt = h->d_cnt.p + 3;
     a.n = h->n; a.W = W; a.T = T; a.seed = seed; a.thr = prob.thr; a.directed = h->directed; a.trial_tab = trial_tab;
     a.dense = sets * h->n * W;
@@ -400,7 +560,8 @@ gh_status ic_run_levels(gh_ic *h, int64_t sets, int32_t W, int32_t T, uint64_t s
         a.cur_cnt = h->d_cnt.p + (r - 1) % 3;
         a.nxt_cnt = h->d_cnt.p + r % 3;
         a.zero_cnt = h->d_cnt.p + (r + 1) % 3;
-        if (prob.arc) ic_launch_level<REV, true>(h, a, grid);
+        if (prob.lt) lt_launch_level<REV>(h, a, grid);
+        else if (prob.arc) ic_launch_level<REV, true>(h, a, grid);
         else ic_launch_level<REV, false>(h, a, grid);
         GH_HIP(hipGetLastError());
         if (r % IC_CHECK_EVERY == 0 && r < last) {
@@ -529,6 +690,83 @@ extern "C" gh_status gh_ic_set_arc_probabilities(gh_ic_handle h, int64_t m, cons
     return GH_OK;
 }
 
+// The intervals are built on the host in the target's row of the by-target CSR, whose slots ascend in source id: S is the
+// sequential double sum of the row's weights and a slot's (lo, hi) = (c_{k-1}, c_k), c_k = min(2^32 - 1, floor(S_k 2^32 + .5)).
+// The by-source CSR gets, for its slot (x, y), the interval of arc x -> y out of y's row.
+extern "C" gh_status gh_ic_set_lt_weights(gh_ic_handle h, int64_t m, const int32_t *arcs, const double *weight) {
+    if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
+    auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
+    if (m < 0 || (m > 0 && (!arcs || !weight))) return fail(GH_ERR_INVALID, "bad arc weight arguments");
+    std::vector<std::pair<uint64_t, double>> tab((size_t)m);   // keyed (target, source): a row's weights lie together
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t u = arcs[2 * i], v = arcs[2 * i + 1];
+        const std::string pair = "pair " + std::to_string(i) + " (" + std::to_string(u) + ", " + std::to_string(v) + ")";
+        bool is_arc = u >= 0 && u < h->n && v >= 0 && v < h->n && u != v;
+        if (is_arc) {
+            const uint64_t a = h->directed ? u : std::min(u, v), b = h->directed ? v : std::max(u, v);
+            is_arc = std::binary_search(h->keys.begin(), h->keys.end(), (a << 32) | b);
+        }
+        if (!is_arc) return fail(GH_ERR_INVALID, pair + " into vertex " + std::to_string(v) + " is not an arc of the graph");
+        if (!(weight[i] >= 0.0 && weight[i] <= 1.0))
+            return fail(GH_ERR_INVALID, "the weight of " + pair + " into vertex " + std::to_string(v) + " is not in [0, 1]");
+        tab[(size_t)i] = {((uint64_t)v << 32) | (uint64_t)u, weight[i]};
+    }
+    std::sort(tab.begin(), tab.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    for (int64_t i = 1; i < m; ++i)
+        if (tab[(size_t)i].first == tab[(size_t)i - 1].first)
+            return fail(GH_ERR_INVALID, "the pair (" + std::to_string(tab[(size_t)i].first & 0xFFFFFFFFu) + ", " +
+                                            std::to_string(tab[(size_t)i].first >> 32) + ") into vertex " +
+                                            std::to_string(tab[(size_t)i].first >> 32) + " is listed twice");
+    // the target's rows: in_ptr / in_adj, slot k of row v = arc in_adj[k] -> v
+    std::vector<int64_t> in_ptr, out_ptr;
+    std::vector<int32_t> in_adj, out_adj;
+    gh_csr_from_keys(h->n, h->keys, h->directed ? GH_CSR_BY_TARGET : GH_CSR_SYMMETRIC, &in_ptr, &in_adj);
+    std::vector<uint2> in_iv(in_adj.size()), out_iv;
+    size_t t = 0;
+    for (int64_t v = 0; v < h->n; ++v) {
+        double S = 0.0;
+        uint32_t c = 0;
+        for (int64_t k = in_ptr[(size_t)v]; k < in_ptr[(size_t)v + 1]; ++k) {
+            const uint64_t key = ((uint64_t)v << 32) | (uint64_t)(uint32_t)in_adj[(size_t)k];
+            while (t < tab.size() && tab[t].first < key) ++t;   // both ascend by (target, source)
+            if (t < tab.size() && tab[t].first == key) S += tab[t].second;
+            const uint32_t c1 = (uint32_t)std::min(4294967295.0, std::floor(S * 4294967296.0 + 0.5));
+            in_iv[(size_t)k] = make_uint2(c, c1);
+            c = c1;
+        }
+        if (S > 1.0 + 1.0 / 1048576.0)
+            return fail(GH_ERR_INVALID, "the weights into vertex " + std::to_string(v) + " sum to " + std::to_string(S) +
+                                            ", above 1 + 2^-20");
+    }
+    const std::vector<int64_t> *optr = &in_ptr;
+    const std::vector<int32_t> *oadj = &in_adj;
+    if (h->directed) {
+        gh_csr_from_keys(h->n, h->keys, GH_CSR_BY_SOURCE, &out_ptr, &out_adj);
+        optr = &out_ptr;
+        oadj = &out_adj;
+    }
+    out_iv.resize(oadj->size());
+    for (int64_t x = 0; x < h->n; ++x)
+        for (int64_t k = (*optr)[(size_t)x]; k < (*optr)[(size_t)x + 1]; ++k) {   // arc x -> y: x's place in y's row, which ascends
+            const int64_t y = (*oadj)[(size_t)k];
+            const auto rb = in_adj.begin() + in_ptr[(size_t)y], re = in_adj.begin() + in_ptr[(size_t)y + 1];
+            out_iv[(size_t)k] = in_iv[(size_t)(std::lower_bound(rb, re, (int32_t)x) - in_adj.begin())];
+        }
+    if (hipSetDevice(h->device) != hipSuccess) return fail(GH_ERR_RUNTIME, "hipSetDevice failed");
+    gh_dev<uint2> fresh[2];
+    for (int pass = 0; pass < 2; ++pass) {
+        const std::vector<uint2> &iv = pass ? in_iv : out_iv;
+        if (!fresh[pass].alloc(sizeof(uint2) * iv.size())) return fail(GH_ERR_NOMEM, "hipMalloc failed for the arc intervals");
+        if (!iv.empty() && hipMemcpy(fresh[pass].p, iv.data(), sizeof(uint2) * iv.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GH_ERR_HIP, "upload of the arc intervals failed");
+    }
+    // nothing failed: the new table replaces the old one (no call of this handle is in flight, every entry point blocks)
+    h->d_out_iv = std::move(fresh[0]);
+    h->d_in_iv = std::move(fresh[1]);
+    h->has_lt = true;
+    return GH_OK;
+}
+
 extern "C" void gh_ic_destroy(gh_ic_handle h) {
     if (!h) return;
     gh_host_close(h);
@@ -543,14 +781,14 @@ extern "C" gh_status gh_ic_set_memory_budget(gh_ic_handle h, int64_t bytes) {
 
 extern "C" int64_t gh_ic_arc_count(gh_ic_handle h) { return h ? h->arcs : -1; }
 
-// gh_ic_spread (p: the scalar) and gh_ic_spread_arcs (p = NULL: the handle's table)
-static gh_status ic_spread(gh_ic_handle h, const double *p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+// gh_ic_spread (p: the scalar), gh_ic_spread_arcs and gh_ic_spread_lt (p = NULL: the handle's table of that kind)
+static gh_status ic_spread(gh_ic_handle h, const double *p, IcTable table, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
                            const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                            int64_t *totals, int32_t *per_trial) {
     if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
     auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
     IcProb prob;
-    GH_TRY_ST(ic_prob(h, p, &prob));
+    GH_TRY_ST(ic_prob(h, p, table, &prob));
     if (n_trials < 1) return fail(GH_ERR_INVALID, "n_trials must be >= 1");
     if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
     if (n_sets < 0 || (n_sets > 0 && (!set_offsets || !totals))) return fail(GH_ERR_INVALID, "bad seed-set arguments");
@@ -612,13 +850,21 @@ static gh_status ic_spread(gh_ic_handle h, const double *p, int32_t max_hops, in
 extern "C" gh_status gh_ic_spread(gh_ic_handle h, double p, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
                                   const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                                   int64_t *totals, int32_t *per_trial) {
-    return ic_spread(h, &p, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals, per_trial);
+    return ic_spread(h, &p, IC_TABLE_ARCS, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals, per_trial);
 }
 
 extern "C" gh_status gh_ic_spread_arcs(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
                                        const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base,
                                        int64_t n_base, int64_t *totals, int32_t *per_trial) {
-    return ic_spread(h, nullptr, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals, per_trial);
+    return ic_spread(h, nullptr, IC_TABLE_ARCS, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals,
+                     per_trial);
+}
+
+extern "C" gh_status gh_ic_spread_lt(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                                     const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base,
+                                     int64_t n_base, int64_t *totals, int32_t *per_trial) {
+    return ic_spread(h, nullptr, IC_TABLE_LT, max_hops, n_trials, seed, n_sets, set_offsets, set_vertices, base, n_base, totals,
+                     per_trial);
 }
 
 // ---- reverse-reachable sets (header: "reverse influence sampling") ------------------------------------------------------
@@ -778,15 +1024,15 @@ gh_status rr_run_chunk(gh_ic *h, gh_rr *rr, int32_t S, int32_t W, const uint64_t
 
 }  // namespace
 
-// gh_ic_rr_sample (p: the scalar) and gh_ic_rr_sample_arcs (p = NULL: the handle's table)
-static gh_status ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, const double *p, int32_t max_hops, uint64_t seed, int64_t n_samples,
+// gh_ic_rr_sample (p: the scalar), gh_ic_rr_sample_arcs and gh_ic_rr_sample_lt (p = NULL: the handle's table of that kind)
+static gh_status ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, const double *p, IcTable table, int32_t max_hops, uint64_t seed, int64_t n_samples,
                               const uint64_t *trials, const int32_t *roots) {
     if (!h) { g_ic_error = "handle is NULL"; return GH_ERR_INVALID; }
     auto fail = [&](gh_status st, const std::string &msg) { h->err = msg; return st; };
     if (!rr) return fail(GH_ERR_INVALID, "the collection handle is NULL");
     if (rr->n != h->n || rr->device != h->device) return fail(GH_ERR_INVALID, "the collection was created for another n or device");
     IcProb prob;
-    GH_TRY_ST(ic_prob(h, p, &prob));
+    GH_TRY_ST(ic_prob(h, p, table, &prob));
     if (max_hops < -1) return fail(GH_ERR_INVALID, "max_hops must be >= 0, or -1 for no limit");
     if (n_samples < 0) return fail(GH_ERR_INVALID, "n_samples must be >= 0");
     if (rr->sets + n_samples > INT32_MAX) return fail(GH_ERR_INVALID, "a collection holds fewer than 2^31 sets");
@@ -826,10 +1072,15 @@ static gh_status ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, const double *p, 
 
 extern "C" gh_status gh_ic_rr_sample(gh_ic_handle h, gh_rr_handle rr, double p, int32_t max_hops, uint64_t seed, int64_t n_samples,
                                      const uint64_t *trials, const int32_t *roots) {
-    return ic_rr_sample(h, rr, &p, max_hops, seed, n_samples, trials, roots);
+    return ic_rr_sample(h, rr, &p, IC_TABLE_ARCS, max_hops, seed, n_samples, trials, roots);
 }
 
 extern "C" gh_status gh_ic_rr_sample_arcs(gh_ic_handle h, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
                                           const uint64_t *trials, const int32_t *roots) {
-    return ic_rr_sample(h, rr, nullptr, max_hops, seed, n_samples, trials, roots);
+    return ic_rr_sample(h, rr, nullptr, IC_TABLE_ARCS, max_hops, seed, n_samples, trials, roots);
+}
+
+extern "C" gh_status gh_ic_rr_sample_lt(gh_ic_handle h, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                                        const uint64_t *trials, const int32_t *roots) {
+    return ic_rr_sample(h, rr, nullptr, IC_TABLE_LT, max_hops, seed, n_samples, trials, roots);
 }

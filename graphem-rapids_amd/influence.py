@@ -16,6 +16,13 @@ the threshold it is compared with becomes the arc's own (include/graphem_hip.h),
 edge share a coin but may differ in probability.  A float takes gh_ic_spread / gh_ic_rr_sample as before; a table is
 uploaded once per distinct specification (gh_ic_set_arc_probabilities) and read by gh_ic_spread_arcs /
 gh_ic_rr_sample_arcs, and tests/arc_ic_reference.py recomputes every result bit for bit.
+
+Linear Threshold.  p may also be linear_threshold(w): the other canonical diffusion model (Kempe, Kleinberg, Tardos 2003),
+in its live-edge form -- in a trial every vertex selects at most one in-arc, arc u -> v with probability w_uv, by one
+32-bit pick per (trial, vertex) against fixed-point intervals of the vertex's in-arcs (include/graphem_hip.h).  lt_weights
+resolves w to one weight per directed arc; the table is uploaded once per distinct specification (gh_ic_set_lt_weights)
+beside the per-arc table, gh_ic_spread_lt / gh_ic_rr_sample_lt read it, and tests/lt_reference.py recomputes every result
+bit for bit.  max_hops counts rounds of the threshold process.
 """
 import hashlib
 import heapq
@@ -138,6 +145,78 @@ def trivalency_probabilities(arcs, directed, seed=0, values=(0.1, 0.01, 0.001)):
     return np.random.default_rng(seed).choice(np.asarray(values, dtype=np.float64), size=A if directed else (A, 2))
 
 
+_LT_ROW_MARGIN = 1.0 + 2.0 ** -20   # include/graphem_hip.h: what the sequential double sum of a row may reach
+
+
+def _lt_rows(arcs, directed, weight):
+    """(src, dst, w) of every directed arc of canonical arcs and lt_weights' array, by (target, source) ascending: the
+    order in which the header sums a row."""
+    a, b = arcs[:, 0], arcs[:, 1]
+    if directed:
+        src, dst, w = a, b, weight
+    else:
+        src, dst, w = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([weight[:, 0], weight[:, 1]])
+    order = np.lexsort((src, dst))
+    return src[order], dst[order], w[order]
+
+
+def lt_weights(arcs, n, directed, w="uniform"):
+    """One Linear Threshold weight per directed arc from the specification w, against the canonical (A, 2) arc array of
+    _graph_arcs.  Host only.  Returns arc_probabilities' shapes: float64 (A,) for a directed graph, (A, 2) -- a -> b,
+    b -> a -- for an undirected one, whose two arcs of an edge are weighted separately.
+    w: "uniform" -- w_uv = 1 / indeg(v), for an undirected graph 1 / deg(v): ndlib's ThresholdModel, which compares the
+       fraction of active neighbours with the threshold;
+       an (A,) array aligned with arcs (both arcs of an undirected edge get the value), or an (A, 2) array;
+       a scipy sparse (n, n) matrix, W[u, v] = w_uv: an absent entry is 0.
+    ValueError for NaN, a weight outside [0, 1], a wrong shape, a stored entry on a pair that is not an arc, and a vertex
+    whose in-weights, summed in ascending source id, exceed 1 + 2^-20 (the header derives the margin)."""
+    arcs = np.asarray(arcs, dtype=np.int64).reshape(-1, 2)
+    n, directed = int(n), bool(directed)
+    if isinstance(w, str):
+        if w != "uniform":
+            raise ValueError(f"unknown Linear Threshold weighting {w!r}: 'uniform' is the one with a name")
+        return arc_probabilities(arcs, n, directed, "wc")
+    try:
+        weight = arc_probabilities(arcs, n, directed, w)
+    except ValueError as exc:
+        raise ValueError(f"Linear Threshold weights: {exc}") from None
+    _, dst, ws = _lt_rows(arcs, directed, weight)
+    total = np.bincount(dst, weights=ws, minlength=n)   # adds in array order: the sequential sum of every row
+    if len(total) and total.max() > _LT_ROW_MARGIN:
+        v = int(np.argmax(total > _LT_ROW_MARGIN))
+        raise ValueError(f"the Linear Threshold weights into vertex {v} sum to {total[v]!r}, above 1 + 2^-20")
+    return weight
+
+
+class LinearThreshold:
+    """What linear_threshold returns: a diffusion-model specification that every p parameter accepts."""
+
+    def __init__(self, w="uniform"):
+        self.w = w
+
+    def __repr__(self):
+        return f"linear_threshold({self.w!r})" if isinstance(self.w, str) else "linear_threshold(<weights>)"
+
+
+def linear_threshold(w="uniform"):
+    """The Linear Threshold model as a value for p: InfluenceGraph.spread / marginal_totals / greedy / rr_sets,
+    RRCollection.extend, influence_spread, ndlib_estimated_influence, greedy_seed_selection, ris_seed_selection and
+    run_influence_benchmark take it wherever they take a probability.  w: what lt_weights takes.  The specification is
+    resolved against the graph when a call first meets it, and its table is uploaded once (a digest of the resolved
+    weights tells).  Hops keep the package's iterations_count - 2 convention, which is the package's own here: ndlib's
+    threshold model has no "removed" state, so nothing in ndlib lags the active set by two iterations."""
+    return LinearThreshold(w)
+
+
+class _LTTable:
+    """A resolved Linear Threshold specification: the host weights and their digest, as _ArcTable is for probabilities."""
+
+    def __init__(self, weight):
+        self.weight = np.ascontiguousarray(weight, dtype=np.float64)
+        self.weight.setflags(write=False)
+        self.key = hashlib.blake2b(self.weight.tobytes(), digest_size=16).digest()
+
+
 class _ArcTable:
     """A resolved specification: its own copy of the host array, and the digest an InfluenceGraph compares with the
     table its handle holds, so one specification is uploaded once however many calls name it."""
@@ -197,8 +276,8 @@ class InfluenceGraph:
     Self-loops are dropped and duplicate edges merged.  networkx node labels that are not 0 .. n-1 are mapped in node
     order; seeds are given and returned as labels.
 
-    p, wherever a method takes it, is one float for the whole graph or a per-arc specification (arc_probabilities):
-    "wc", an array aligned with self.arcs, a sparse matrix.  The handle keeps the table of the last specification used, so
+    p, wherever a method takes it, is one float for the whole graph, linear_threshold(w) for the Linear Threshold model,
+    or a per-arc specification (arc_probabilities): "wc", an array aligned with self.arcs, a sparse matrix.  The handle keeps the table of the last specification used, so
     repeated calls with one specification upload it once; a float never touches it."""
 
     def __init__(self, graph, n=None, directed=None, device_id=0):
@@ -207,11 +286,16 @@ class InfluenceGraph:
         self._device_id = int(device_id)
         self._ic = _native.ICGraph(max(self.n, 1), self.arcs, self.directed, device_id) if self.n > 0 else None
         self._table_key = None   # digest of the table the handle holds
+        self._lt_key = None      # and of its Linear Threshold table
 
     def arc_probabilities(self, p):
         """The host array a per-arc specification resolves to on this graph (arc_probabilities): float64 (A,) aligned
         with self.arcs for a directed graph, (A, 2) -- a -> b, b -> a -- for an undirected one."""
         return np.array(self._resolve_table(p).prob)
+
+    def lt_weights(self, w="uniform"):
+        """The host array a Linear Threshold specification resolves to on this graph (lt_weights)."""
+        return lt_weights(self.arcs, self.n, self.directed, w.w if isinstance(w, LinearThreshold) else w)
 
     def _resolve_table(self, p):
         return p if isinstance(p, _ArcTable) else _ArcTable(arc_probabilities(self.arcs, self.n, self.directed, p))
@@ -220,10 +304,24 @@ class InfluenceGraph:
         """A float stays a float (the uniform path); anything else becomes an _ArcTable, resolved once per public call."""
         if isinstance(p, numbers.Real) and not isinstance(p, bool):
             return float(p)
+        if isinstance(p, _LTTable):
+            return p
+        if isinstance(p, LinearThreshold):
+            return _LTTable(lt_weights(self.arcs, self.n, self.directed, p.w))
         return self._resolve_table(p)
 
     def _native_p(self, p):
-        """What _native.ICGraph takes for a resolved p: the float, or None once the handle holds p's table."""
+        """What _native.ICGraph takes for a resolved p: the float, or None / _native.LT once the handle holds p's table."""
+        if isinstance(p, _LTTable):
+            if self._lt_key != p.key:
+                if self.directed:
+                    pairs, weight = self.arcs, p.weight
+                else:
+                    pairs = np.concatenate([self.arcs, self.arcs[:, ::-1]])
+                    weight = np.concatenate([p.weight[:, 0], p.weight[:, 1]])
+                self._ic.set_lt_weights(pairs, weight)
+                self._lt_key = p.key
+            return _native.LT
         if not isinstance(p, _ArcTable):
             return p
         if self._table_key != p.key:
@@ -571,7 +669,8 @@ def run_influence_benchmark(graph_generator, graph_params, k=10, p=0.1, iteratio
     may return an (E, 2) edge array or an adjacency matrix.  Returns the reference's result keys; ris=True adds
     ris_seeds, ris_influence, ris_time and ris_samples from ris_seed_selection (epsilon = 0.1); kshell=True adds
     kshell_seeds, kshell_influence and kshell_time from kshell_seed_selection.  p may be a per-arc specification
-    (arc_probabilities), e.g. p="wc" for the weighted cascade."""
+    (arc_probabilities), e.g. p="wc" for the weighted cascade, or linear_threshold() to run every selection and every
+    score under the Linear Threshold model."""
     from . import create_graphem, graphem_seed_selection, edges_to_adjacency
     start_time = time.time()
     out = graph_generator(**graph_params)

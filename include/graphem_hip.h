@@ -514,7 +514,37 @@ gh_status gh_selftest_arith(int device_id, uint64_t seed, int64_t samples, int64
  *      searches walk the same live digraph.
  * Results depend only on (arc set, probability table, seed set or samples, max_hops, n_trials, seed).  The table is graph
  * state on the device, 4 bytes per CSR slot in each of two arrays (a slot per arc and array for a directed graph, two
- * slots per edge and array for an undirected one); gh_ic_set_memory_budget does not count it. */
+ * slots per edge and array for an undirected one); gh_ic_set_memory_budget does not count it.
+ *
+ * Linear Threshold (gh_ic_set_lt_weights, gh_ic_spread_lt, gh_ic_rr_sample_lt; Kempe, Kleinberg, Tardos 2003), in its
+ * live-edge form.  Every vertex v has weights w_uv >= 0 on its in-arcs with  sum over u of w_uv <= 1.  In one trial v
+ * selects AT MOST ONE in-arc: arc u -> v with probability w_uv, none with probability 1 - sum w_uv, independently across
+ * vertices.  The selected arcs are the live digraph of the trial; a cascade is the breadth-first search over it from the
+ * seeds, cut at max_hops, and an RR set is the search over it backwards from the root.  By Kempe et al., Claim 2.6 (an
+ * induction over rounds), the active set after every round of the threshold process -- theta_v uniform on [0, 1], v
+ * becomes active once the weights of its active in-neighbours reach theta_v -- has the distribution of the set reached
+ * within that many hops over the live arcs: max_hops counts rounds, as for Independent Cascade.
+ *     pick(seed, t, v) = mix( mix(seed + t * 0x9E3779B97F4A7C15) ^ ((uint64)v << 32 | v) ) >> 32           (32 bits)
+ * The key (v, v) is a self-loop key: no arc coin has it (self-loops are dropped), and it is not the all-ones root key.
+ * Intervals, computed once on the host in double: the in-arcs of v in ascending source id, after self-loops and
+ * duplicates went; an arc that is not listed has weight 0;
+ *     S_k = the sequential double sum of the first k weights,  c_0 = 0,  c_k = min(2^32 - 1, floor(S_k * 2^32 + 0.5))
+ * as uint32.  The k-th in-arc of v is live in trial t iff  c_{k-1} <= pick(seed, t, v) < c_k.  S is monotone, so c is: the
+ * intervals are disjoint, and a zero-weight arc has an empty one.  Because of the clamp a vertex whose weights sum to 1
+ * selects nobody with probability 2^-32.
+ * A row may sum to at most 1 + 2^-20.  The margin is derived: a sequential sum of d <= 2^31 doubles has a relative error
+ * of at most d * 2^-53 <= 2^-22, so a row whose exact sum is 1 (d copies of fl(1 / d)) always passes, and the clamp
+ * absorbs the excess.
+ * Undirected graphs: the edge {a, b} is the two arcs a -> b and b -> a, each in its own target's row with its own weight
+ * and selected by its own target's pick.  Nothing is shared between the two -- unlike the Independent Cascade coin, which
+ * the two directions of an edge share.
+ * The identity  sum over all roots r of [S meets RR(t, r)] = |R_t(S)|  holds exactly (one digraph, two searches), and
+ * under fixed picks the spread is reachability in a fixed digraph, so it is monotone and submodular.
+ * Results depend only on (arc set, weight table, seed set or samples, max_hops, n_trials, seed): not on arc order,
+ * duplicates, loops, batching, chunking or either memory budget.  The table is graph state of its own beside the per-arc
+ * table -- a handle may hold both, and setting one never touches the other or the scalar p: the pair (c_{k-1}, c_k) of
+ * every CSR slot in each of two arrays, 8 bytes per slot and array (16 bytes per arc of a directed graph, 32 per edge of
+ * an undirected one), so that no launch looks into another vertex's row; gh_ic_set_memory_budget does not count it. */
 typedef struct gh_ic *gh_ic_handle;
 
 /* arcs: (n_arcs, 2) int32 host array, vertex ids in [0, n).  directed = 0: each row is an undirected edge.  Self-loops
@@ -547,6 +577,18 @@ gh_status gh_ic_set_arc_probabilities(gh_ic_handle h, int64_t m, const int32_t *
 gh_status gh_ic_spread_arcs(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
                             const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
                             int64_t *totals, int32_t *per_trial);
+/* The handle's Linear Threshold table: arcs is an (m, 2) int32 host array of DIRECTED pairs u -> v, weight[i] = w_uv of
+ * pair i.  For an undirected graph (u, v) and (v, u) are two arcs; each may be listed once.  An arc of the graph that is
+ * not listed gets weight 0.  GH_ERR_INVALID, with the target vertex in gh_ic_last_error(h), for a pair that is not an arc
+ * of the graph, a pair listed twice, a weight that is NaN or outside [0, 1], a row whose sequential sum is above
+ * 1 + 2^-20.  A call replaces the previous Linear Threshold table; a failed call leaves it in place.  The per-arc
+ * probability table and calls with a scalar p are not affected.  Blocking. */
+gh_status gh_ic_set_lt_weights(gh_ic_handle h, int64_t m, const int32_t *arcs, const double *weight);
+/* gh_ic_spread under Linear Threshold with the table above: the same arguments, checks, chunking, marginal mode and
+ * budget.  GH_ERR_INVALID when no Linear Threshold table has been set. */
+gh_status gh_ic_spread_lt(gh_ic_handle h, int32_t max_hops, int32_t n_trials, uint64_t seed, int64_t n_sets,
+                          const int64_t *set_offsets, const int32_t *set_vertices, const int32_t *base, int64_t n_base,
+                          int64_t *totals, int32_t *per_trial);
 
 /* ---- reverse influence sampling (RIS; Borgs et al. 2014, TIM/IMM, OPIM-C; graphem-rapids_amd/influence.py) --------------
  * A collection of reverse-reachable (RR) sets on the device behind its own handle, drawn by a gh_ic handle with the coins
@@ -588,6 +630,11 @@ gh_status gh_ic_rr_sample(gh_ic_handle ic, gh_rr_handle rr, double p, int32_t ma
  * chunking and budgets.  GH_ERR_INVALID when no table has been set. */
 gh_status gh_ic_rr_sample_arcs(gh_ic_handle ic, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
                                const uint64_t *trials, const int32_t *roots);
+/* gh_ic_rr_sample under Linear Threshold with ic's table (gh_ic_set_lt_weights): the same arguments, checks, chunking,
+ * default trials and roots, and budgets; an RR set is then a simple path backwards from the root.  GH_ERR_INVALID when no
+ * Linear Threshold table has been set. */
+gh_status gh_ic_rr_sample_lt(gh_ic_handle ic, gh_rr_handle rr, int32_t max_hops, uint64_t seed, int64_t n_samples,
+                             const uint64_t *trials, const int32_t *roots);
 gh_status gh_rr_counts(gh_rr_handle h, int64_t *n_sets, int64_t *n_members);
 /* Host arrays (each may be NULL): indptr int64 (sets + 1), members int32, roots int32 (sets; -1 for an uploaded set
  * without one).  Blocking. */
