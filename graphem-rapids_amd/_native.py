@@ -36,6 +36,7 @@ EDGES_RANGE, EDGES_HASHED = 0, 1  # gh_partition.edge_rule (include/graphem_hip.
 
 SCAN_FILTERS = {"auto": 0, "mfma": 1, "cells": 2}  # GH_FILTER_* (include/graphem_hip.h)
 COARSE_TAU = {"auto": 0, "off": 1, "on": 2}        # GH_COARSE_*
+COMPACT_GATHER = {"off": 0, "on": 1, "auto": 2}    # GH_COMPACT_*
 COARSE_GROUPS = 64                                 # GH_CT_M (csrc/engine.h)
 LINK_KINDS = {"common_neighbors": 0, "jaccard": 1, "adamic_adar": 2, "resource_allocation": 3,
               "preferential_attachment": 4}  # GH_LINK_* (include/graphem_hip.h)
@@ -126,6 +127,12 @@ SIGNATURES = {
     "gh_set_coarse_tau": (_int, [vp, i32]),
     "gh_get_coarse_tau": (_int, [vp, _P(i32)]),
     "gh_debug_coarse_table": (_int, [vp, vp, i64]),
+    "gh_set_compact_gather": (_int, [vp, i32]),
+    "gh_get_compact_gather": (_int, [vp, _P(i32)]),
+    "gh_compact_gather_launches": (_int, [vp, _P(i64)]),
+    "gh_compact_slot": (i64, [i64]),
+    "gh_compact_slots": (_int, [i64, i64, vp]),
+    "gh_compact_bytes": (i64, [i64]),
     "gh_qcell_probe": (_int, [vp, i32, vp, vp, vp, i64, vp, vp]),
     "gh_sampler_stats": (_int, [vp, vp]),
     "gh_overlap_layout": (_int, [vp, i32, i32, i64]),
@@ -578,6 +585,23 @@ class Engine(Handle):
         v = ctypes.c_int32(0)
         self._chk(self.lib.gh_get_coarse_tau(self.handle, ctypes.byref(v)))
         return bool(v.value)
+
+    def set_compact_gather(self, mode):
+        """Position rows of the three-component fused kernel: 'on' = from the table of 12-byte rows packed five to a 64-byte
+        sector, 'off' = from the padded positions, 'auto' (same results either way)."""
+        self._chk(self.lib.gh_set_compact_gather(self.handle, COMPACT_GATHER[mode]))
+
+    def compact_gather(self):
+        """True when the engine keeps the sector-packed table and its fused kernel reads it."""
+        v = ctypes.c_int32(0)
+        self._chk(self.lib.gh_get_compact_gather(self.handle, ctypes.byref(v)))
+        return bool(v.value)
+
+    def compact_gather_launches(self):
+        """Fused launches of this engine so far that read the sector-packed table (the others read the padded positions)."""
+        v = ctypes.c_int64(0)
+        self._chk(self.lib.gh_compact_gather_launches(self.handle, ctypes.byref(v)))
+        return v.value
 
     def coarse_table(self):
         """Both copies of the coarse table as (2, 64, sample_size) uint32 float bits; 0xFFFFFFFF = empty (diagnostic)."""

@@ -102,6 +102,8 @@ struct create_switches {
     const char *reorder = nullptr;   // GRAPHEM_HIP_REORDER=1 | 2 overrides gh_params.reorder (tests / A-B runs: off, breadth-first)
     int tau_separate = -1;      // GRAPHEM_HIP_TAU_SEPARATE=1 | 0: thresholds in a launch of their own | in the fused one; -1: by size
     bool stamps = false;        // GRAPHEM_HIP_STAMPS: wall-clock stamps of the fused launch's workgroups
+    int compact_gather = -1;    // GRAPHEM_HIP_COMPACT_GATHER=1 | 0: the fused kernel reads position rows from the sector-packed table |
+                                // from the padded positions; -1: where the packed form was measured ahead
     int coarse_tau = -1;        // GRAPHEM_HIP_COARSE_TAU=1 | 0: the query-cell launch takes its thresholds from coarse group minima | a
                                 // threshold launch of its own from the fine ones; -1: wherever the coarse form can serve
 };
@@ -112,6 +114,7 @@ static create_switches read_switches() {
     if (const char *e = getenv("GRAPHEM_HIP_TAU_SEPARATE")) sw.tau_separate = atoi(e) != 0;
     sw.stamps = getenv("GRAPHEM_HIP_STAMPS") != nullptr;
     if (const char *e = getenv("GRAPHEM_HIP_COARSE_TAU")) sw.coarse_tau = atoi(e) != 0;
+    if (const char *e = getenv("GRAPHEM_HIP_COMPACT_GATHER")) sw.compact_gather = atoi(e) != 0;
     return sw;
 }
 
@@ -146,6 +149,7 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     }
     GH_A(d_vblock, g.vblock.size(), false);
     GH_A(d_pos, (size_t)h->pos_rows * h->LD, true);
+    GH_TRY_ST(gh_ensure_compact_table(h));
     GH_A(d_new_buf, (size_t)h->rows * h->LD, true);
     h->d_new = h->d_new_buf.p;
     GH_A(d_tmpF, nLD, true);
@@ -222,6 +226,14 @@ static gh_status allocate_and_upload(gh_engine *h, const gh_graph_plan &g, const
     return GH_OK;
 }
 
+// The sector-packed gather table exists where the plan asks for it (common.h gh_cg_slot), zeroed once: its pad dwords and
+// the rows behind the n-th are never written.  A new table holds no positions yet.
+gh_status gh_ensure_compact_table(gh_engine *h) {
+    if (!h->plan.compact_gather || h->d_cg.p) return GH_OK;
+    gh_step_compact_valid(h, false);
+    return gh_alloc(h, h->d_cg, (size_t)gh_cg_bytes(h->n) / sizeof(float), true);
+}
+
 extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t D, int64_t E, const int32_t *edges,
                                const gh_params *params, const gh_partition *part) {
     if (!out) return GH_ERR_INVALID;
@@ -261,6 +273,7 @@ extern "C" gh_status gh_create(gh_handle *out, int device_id, int64_t n, int32_t
     h->requests.no_presetup = sw.no_presetup;
     h->requests.tau_place = sw.tau_separate < 0 ? GH_TAU_BY_SIZE : sw.tau_separate ? GH_TAU_SEPARATE : GH_TAU_EMBEDDED;
     h->requests.coarse_mode = sw.coarse_tau < 0 ? GH_COARSE_AUTO : sw.coarse_tau ? GH_COARSE_ON : GH_COARSE_OFF;
+    h->requests.compact_gather = sw.compact_gather < 0 ? GH_COMPACT_AUTO : sw.compact_gather ? GH_COMPACT_ON : GH_COMPACT_OFF;
 
     gh_graph_plan g;   // vertex order, ownership, pull lists, owned edges, fused blocks (graph_plan.hip)
     gh_plan_graph(h, edges, part != nullptr, sw.reorder ? atoi(sw.reorder) : params->reorder, &g);
@@ -295,7 +308,10 @@ extern "C" gh_status gh_set_positions(gh_handle h, const float *pos) {
     if (!pos) { h->err = "positions is NULL"; return GH_ERR_INVALID; }
     gh_set_lookahead(h, nullptr);
     GH_HIP(hipMemcpyAsync(h->d_io.p, pos, sizeof(float) * (size_t)h->n * h->D, hipMemcpyHostToDevice, h->stream));
-    GH_TRY_ST(gh_launch_pad(h, h->d_io.p, h->d_pos.p));
+    float *cg = h->plan.compact_gather ? h->d_cg.p : nullptr;
+    gh_step_compact_valid(h, false);
+    GH_TRY_ST(gh_launch_pad(h, h->d_io.p, h->d_pos.p, cg));
+    gh_step_compact_valid(h, cg != nullptr);
     GH_HIP(hipStreamSynchronize(h->stream));  // the host buffer may be released by the caller
     return GH_OK;
 }
@@ -347,6 +363,7 @@ static gh_status check_device_waits(gh_engine *h) {
         else h->requests.tau_place = GH_TAU_SEPARATE;
         gh_replan(h);
         gh_drop_lookahead(h);
+        gh_step_compact_valid(h, false);
         if (cells) {
             h->err = "a workgroup of the fused spring+scan launch timed out waiting for the query-cell table of its own "
                      "launch; results since the last successful gh_sync / gh_get_positions are invalid -- set the positions "
@@ -370,7 +387,11 @@ extern "C" gh_status gh_get_positions(gh_handle h, float *pos) {
     return download_padded(h, h->d_pos.p, pos);
 }
 
-extern "C" float *gh_positions_device(gh_handle h) { return h && !h->f64 ? h->d_pos.p : nullptr; }
+extern "C" float *gh_positions_device(gh_handle h) {
+    if (!h || h->f64) return nullptr;
+    gh_step_pos_shared(h);   // the caller may write the rows whenever it likes: the sector-packed copy is not read again
+    return h->d_pos.p;
+}
 extern "C" gh_status gh_vertex_order(gh_handle h, int32_t *order) {
     GH_TRY_ST(check_handle(h));
     if (!order) { h->err = "order is NULL"; return GH_ERR_INVALID; }
@@ -608,6 +629,38 @@ extern "C" gh_status gh_set_coarse_tau(gh_handle h, int32_t mode) {
     gh_replan(h);
     return GH_OK;
 }
+extern "C" gh_status gh_set_compact_gather(gh_handle h, int32_t mode) {
+    GH_TRY_ST(check_handle(h));
+    GH_TRY_ST(reject_f64(h, "gh_set_compact_gather"));
+    if (mode != GH_COMPACT_AUTO && mode != GH_COMPACT_OFF && mode != GH_COMPACT_ON) {
+        h->err = "gh_set_compact_gather: mode must be GH_COMPACT_AUTO, GH_COMPACT_OFF or GH_COMPACT_ON";
+        return GH_ERR_INVALID;
+    }
+    h->requests.compact_gather = mode;
+    gh_replan(h);
+    // a table that was out of use did not follow the positions: the next finish (or gh_set_positions) fills it
+    gh_step_compact_valid(h, false);
+    return gh_ensure_compact_table(h);
+}
+extern "C" gh_status gh_get_compact_gather(gh_handle h, int32_t *in_use) {
+    GH_TRY_ST(check_handle(h));
+    if (!in_use) { h->err = "in_use is NULL"; return GH_ERR_INVALID; }
+    *in_use = !h->f64 && h->plan.compact_gather && !h->step.pos_shared ? 1 : 0;
+    return GH_OK;
+}
+extern "C" gh_status gh_compact_gather_launches(gh_handle h, int64_t *packed) {
+    GH_TRY_ST(check_handle(h));
+    if (!packed) { h->err = "packed is NULL"; return GH_ERR_INVALID; }
+    *packed = h->f64 ? 0 : h->compact_launches;
+    return GH_OK;
+}
+extern "C" gh_status gh_compact_slots(int64_t v0, int64_t count, int64_t *out) {
+    if (!out || v0 < 0 || count < 0 || v0 + count > 0x100000000ll) return GH_ERR_INVALID;
+    for (int64_t i = 0; i < count; ++i) out[i] = (int64_t)gh_cg_slot((uint32_t)(v0 + i));
+    return GH_OK;
+}
+extern "C" int64_t gh_compact_slot(int64_t v) { return v < 0 || v > 0xFFFFFFFFll ? -1 : (int64_t)gh_cg_slot((uint32_t)v); }
+extern "C" int64_t gh_compact_bytes(int64_t n) { return n < 0 ? -1 : gh_cg_bytes(n); }
 extern "C" gh_status gh_get_coarse_tau(gh_handle h, int32_t *in_use) {
     GH_TRY_ST(check_handle(h));
     if (!in_use) { h->err = "in_use is NULL"; return GH_ERR_INVALID; }
@@ -1012,6 +1065,7 @@ extern "C" gh_status gh_integrate_normalise(gh_handle h, const float *Fs, const 
     GH_TRY_ST(gh_launch_unpad(h, h->d_pos.p, h->d_io.p));
     GH_HIP(hipMemcpyAsync(out, h->d_io.p, bytes, hipMemcpyDeviceToHost, h->stream));
     GH_HIP(hipMemcpyAsync(h->d_pos.p, h->d_tmpF.p, sizeof(float) * (size_t)h->n * h->LD, hipMemcpyDeviceToDevice, h->stream));
+    gh_step_compact_valid(h, false);   // (the normalise launch wrote the scratch result into the sector-packed table as well)
     GH_HIP(hipStreamSynchronize(h->stream));
     return GH_OK;
 }

@@ -81,6 +81,36 @@ __device__ __forceinline__ void gh_store_row(float *__restrict__ dst, int64_t v,
     for (int i = 0; i < LD / 4; ++i) p[i] = make_float4(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]);
 }
 
+// ---------------------------------------------------------------------------------
+// The sector-packed gather table of three-component engines (plan.compact_gather): the rows of pos without their pad
+// column, five to a 64-byte sector -- 60 bytes of rows, one dword unused -- so that no row crosses a sector (plain
+// 12-byte rows: two in sixteen would, and such a gather makes two requests) and the table a launch gathers from
+// is 4/5 the size: a larger share of it stays in the L2s.  gh_cg_slot: the dword offset of vertex v's row (v / 5 by
+// multiply-high: exact for every 32-bit v); the table of n vertices covers the spare rows behind them too.
+__host__ __device__ __forceinline__ uint32_t gh_cg_slot(uint32_t v) {
+    const uint32_t q = (uint32_t)(((uint64_t)v * 0xCCCCCCCDull) >> 34);   // v / 5
+    return v * 3u + q;   // = q * 16 + (v - 5 q) * 3: three dwords per row and one more per full sector before it
+}
+__host__ __device__ inline int64_t gh_cg_bytes(int64_t n) { return (n + 1024 + 4) / 5 * 64; }
+typedef float gh_f3 __attribute__((ext_vector_type(3)));
+typedef gh_f3 gh_f3u __attribute__((aligned(4)));   // a row of the table: one global_load_dwordx3 / global_store_dwordx3
+// The row of vertex v as the padded table holds it: (x, y, z, 0).  The byte offset is 32 bits wide (GH_CG_MAX_N).
+__device__ __forceinline__ void gh_cg_load_row(const float *__restrict__ cg, uint32_t v, float *out) {
+    const gh_f3 t = *reinterpret_cast<const gh_f3u *>(reinterpret_cast<const char *>(cg) + gh_cg_slot(v) * 4u);
+    out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = 0.0f;
+}
+__device__ __forceinline__ void gh_cg_store_row(float *__restrict__ cg, uint32_t v, float x, float y, float z) {
+    gh_f3 t;
+    t.x = x; t.y = y; t.z = z;
+    *reinterpret_cast<gh_f3u *>(reinterpret_cast<char *>(cg) + gh_cg_slot(v) * 4u) = t;
+}
+// A position row for the spring phase of a fused kernel: CG = from the table above (LD == 4), else from the padded rows.
+template <int LD, bool CG>
+__device__ __forceinline__ void gh_gather_row(const float *__restrict__ src, int64_t v, float *out) {
+    if constexpr (CG) gh_cg_load_row(src, (uint32_t)v, out);
+    else gh_load_row<LD>(src, v, out);
+}
+
 // (dist2, edge id) packed so that unsigned comparison orders by distance, then id.
 // dist2 >= +0 always (fma chain from +0), so its bit pattern is monotone.
 __device__ __forceinline__ uint64_t gh_key(float d2, uint32_t id) {
@@ -150,7 +180,8 @@ __device__ __forceinline__ void gh_div_by(const float (&n)[D], float d, float (&
 //   diff = p_y - p_x,  dist = |diff| + 1e-6,  f = (-k_attr * (dist - L_min)) * (diff / dist)
 // which equals +f of pt.py:629 when x is the first endpoint and -f when it is the second,
 // bit for bit (negation commutes with every rounding involved).
-template <int D, int LD, bool WRITE_MID>
+// CG: `pos` is the sector-packed table (gh_cg_slot) and the neighbour rows come from it; same values, same bits.
+template <int D, int LD, bool WRITE_MID, bool CG = false>
 __device__ __forceinline__ void spring_pull(const float *__restrict__ pos, const int32_t *__restrict__ adj,
                                             int beg, int end, int64_t self, const float *px, float L_min,
                                             float neg_k, float *F, float *__restrict__ mid, int64_t mid_row0) {
@@ -175,7 +206,7 @@ __device__ __forceinline__ void spring_pull(const float *__restrict__ pos, const
         }
         float py[C][LD];
 #pragma unroll
-        for (int j = 0; j < C; ++j) gh_load_row<LD>(pos, ys[j], py[j]);
+        for (int j = 0; j < C; ++j) gh_gather_row<LD, CG>(pos, ys[j], py[j]);
 #pragma unroll
         for (int j = 0; j < C; ++j) {
             if (base + j < end) {
@@ -248,11 +279,12 @@ __device__ __forceinline__ void gh_long_midpoints(const float *__restrict__ pos,
 
 // One row of the spring phase: short rows pull, long rows take the force spring_long_kernel left
 // in Fpre and only emit the midpoints of the edges they own.
-template <int D, int LD, bool WRITE_MID>
+// CG: short rows pull from the sector-packed table `cg`; the long rows' own path keeps reading pos.
+template <int D, int LD, bool WRITE_MID, bool CG = false>
 __device__ __forceinline__ void spring_row(const float *__restrict__ pos, const int32_t *__restrict__ adj, int beg,
                                            int end, int64_t self, const float *px, float L_min, float neg_k, float *F,
                                            float *__restrict__ mid, int64_t mid_row0, const gh_long_args &la,
-                                           int i_local, const float *__restrict__ Fpre) {
+                                           int i_local, const float *__restrict__ Fpre, const float *__restrict__ cg = nullptr) {
     if (la.n > 0 && end - beg > la.deg) {
         gh_load_row<LD>(Fpre, 0, F);
         if (WRITE_MID && !la.own_long) {
@@ -280,7 +312,7 @@ __device__ __forceinline__ void spring_row(const float *__restrict__ pos, const 
         }
         return;
     }
-    spring_pull<D, LD, WRITE_MID>(pos, adj, beg, end, self, px, L_min, neg_k, F, mid, mid_row0);
+    spring_pull<D, LD, WRITE_MID, CG>(CG ? cg : pos, adj, beg, end, self, px, L_min, neg_k, F, mid, mid_row0);
 }
 
 // ---------------------------------------------------------------------------------

@@ -134,6 +134,10 @@ struct gh_engine {
 
     // state
     gh_dev<float> d_pos;          // (n, LD)
+    gh_dev<float> d_cg;           // (gh_cg_bytes(n)) the rows of d_pos without pad columns, five to a 64-byte sector (common.h
+                                  // gh_cg_slot): what the fused kernel gathers from while step.compact_valid.  Allocated only
+                                  // where plan.compact_gather asks for it (gh_ensure_compact_table)
+    int64_t compact_launches = 0; // fused launches so far that ran the sector-packed instantiation (gh_compact_gather_launches)
     gh_dev<float> d_new_buf;      // (rows, LD) the engine's own storage for ...
     float *d_new = nullptr;       // ... the un-normalised update of own rows.  A view: d_new_buf, or the own block of xch.d_rows (forms B, D)
     gh_dev<float> d_tmpF;         // (n, LD) scratch for the per-phase entry points
@@ -299,6 +303,17 @@ inline void gh_drop_lookahead(gh_engine *h) { h->lookahead.valid = false; }
 //                         read: gh_step_rows_early, gh_step_finish_as, which clears it; gh_step_reset.
 //   own_ids               written: gh_step_begin / gh_step_begin_device_ids, every split step (called without ids: device
 //                         sampler / arange).  read: the gathered finishes (they set the next draw up).
+//   compact_valid         set: the two launches that write every row of d_cg beside d_pos -- pad_kernel (gh_set_positions) and
+//                         the normalise launch of a whole-graph single-rank finish (gh_launch_normalise) -- when the plan
+//                         asks for the table.  read: the fused launch (fused.hip fused_compact: else the padded instantiation).
+//                         cleared: by everything else that can change d_pos or leave d_cg behind it -- every other normalise
+//                         launch, gh_integrate_normalise, a failed device wait, gh_set_compact_gather; and it stays clear once
+//                         pos_shared is set.  Not by gh_step_reset: it outlives the step.
+//   pos_shared            set: gh_positions_device, for good -- a caller that holds the pointer may write the rows between any two
+//                         steps, so from then on no launch of this engine trusts the copy.  read: gh_step_compact_valid,
+//                         gh_get_compact_gather.  never cleared.
+inline void gh_step_compact_valid(gh_engine *h, bool valid) { h->step.compact_valid = valid && !h->step.pos_shared; }
+inline void gh_step_pos_shared(gh_engine *h) { h->step.pos_shared = true; h->step.compact_valid = false; }
 inline void gh_step_reset(gh_engine *h) {   // the start of a step's launches
     h->step.new0_ready = h->step.stats_reduced = h->step.intersect_done = h->step.rows_early = false;
 }
@@ -418,7 +433,9 @@ inline float *gh_patch_records(gh_engine *h) { return h->xch.is(GH_LAYOUT_OVERLA
 gh_status gh_launch_new0(gh_engine *h);                            // form D without the fused kernel: d_new = pos + Fs of the own rows
 gh_status gh_launch_pack_rows(gh_engine *h, hipStream_t stream);   // form D: own block of new0 -> its packed slot (on the given stream)
 gh_status gh_launch_patch_rows(gh_engine *h);                      // form D: touched rows of the gathered array += Fi; accumulators zeroed
-gh_status gh_launch_pad(gh_engine *h, const float *d_src_nD, float *d_dst_nLD);
+// cg: also the sector-packed copy of the same rows (d_cg; null: none)
+gh_status gh_launch_pad(gh_engine *h, const float *d_src_nD, float *d_dst_nLD, float *cg = nullptr);
+gh_status gh_ensure_compact_table(gh_engine *h);   // (api.hip) d_cg exists, zeroed, where the plan asks for it; a new one is not valid
 gh_status gh_launch_unpad(gh_engine *h, const float *d_src_nLD, float *d_dst_nD);
 gh_status gh_launch_sample(gh_engine *h);                  // device sampler -> d_sampled
 gh_status gh_launch_arange(gh_engine *h);

@@ -422,7 +422,10 @@ gh_norm_src gh_make_norm_src(const gh_engine *h, gh_finish_kind kind, const doub
 // kernel of its own, so that neither form carries the other's address arithmetic (VGPRs at strides 4 / 8 / 16: 67 / 105 /
 // 127 staged, 68 / 105 / 128 gathering, 7 / 4 / 4 waves per SIMD either way).
 // COARSE: the set-up leaves the coarse form of the group minima (sa.cmin; setup_core.h), again a kernel of its own.
-template <int LDT, bool STAGED, bool COARSE = false>
+// CG: the streaming threads also store the rows into the sector-packed table `cg` (common.h gh_cg_slot; LDT = 4, D = 3, the
+// whole-graph single-rank finish).  A compile-time choice: carried by every instantiation, the slot arithmetic of the four
+// elements in flight took the stride-4 kernels from 67 / 68 to 78 / 80 VGPRs and from 7 to 6 waves per SIMD.
+template <int LDT, bool STAGED, bool COARSE = false, bool CG = false>
 __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, int LD, int64_t n, float *__restrict__ pos,
                                                        double *__restrict__ acc /* null: no clean-up */,
                                                        int32_t *__restrict__ tflag,
@@ -430,7 +433,8 @@ __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, 
                                                        const int32_t *__restrict__ tcount, int nfix, int g_norm,
                                                        int n_setup, gh_setup_args sa, int32_t *__restrict__ qexact,
                                                        unsigned long long *__restrict__ stamps /* diagnostic, or null */,
-                                                       float *__restrict__ packed = nullptr /* form C: the same rows without pad columns, (rows, D) */) {
+                                                       float *__restrict__ packed = nullptr /* form C: the same rows without pad columns, (rows, D) */,
+                                                       float *__restrict__ cg = nullptr /* CG: the sector-packed table */) {
     if (stamps && (blockIdx.x >= GH_STAMP_EXTRA)) stamps = nullptr;
     if (stamps) stamps += (int64_t)blockIdx.x * 8;
 #define GH_STAMP(k) do { if (stamps && threadIdx.x == 0) stamps[k] = wall_clock64(); } while (0)
@@ -539,6 +543,7 @@ __global__ __launch_bounds__(256) void normalise_kernel(gh_norm_src src, int D, 
             o.z = d0 + 2 < D ? (v.z - ms[d0 + 2]) / ms[LD + d0 + 2] : 0.0f;
             o.w = d0 + 3 < D ? (v.w - ms[d0 + 3]) / ms[LD + d0 + 3] : 0.0f;
             dst[t] = o;
+            if constexpr (CG) gh_cg_store_row(cg, (uint32_t)t, o.x, o.y, o.z);   // (LD = 4, one block from row 0: element t is row t)
             if (packed) {   // the copy that travels (gh_step_unpack_rows on the receiving ranks; form C has one block)
                 float *pk = packed + (t * 4 / LD) * D + d0;
                 if (d0 + 0 < D) pk[0] = o.x;
@@ -638,14 +643,17 @@ __global__ void reset_counter_kernel(int32_t *c) { *c = 0; }
 // (n, D) <-> (n, LD) copies for the host boundary.
 // Vertex arrays cross the API as (n, D) in the caller's vertex order; on the device they are
 // (n, LD) rows in the internal order (order[v] = row of vertex v; null = identity).
+// cg: also into the sector-packed table (common.h gh_cg_slot; D = 3, LD = 4), or null.
 __global__ void pad_kernel(const float *__restrict__ src, int64_t n, int D, int LD, const int32_t *__restrict__ order,
-                           float *__restrict__ dst) {
+                           float *__restrict__ dst, float *__restrict__ cg) {
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (t >= n * LD) return;
     const int64_t i = t / LD;
     const int d = (int)(t % LD);
     const int64_t row = order ? order[i] : i;
-    dst[row * LD + d] = d < D ? src[i * D + d] : 0.0f;
+    const float v = d < D ? src[i * D + d] : 0.0f;
+    dst[row * LD + d] = v;
+    if (cg && d < D) cg[gh_cg_slot((uint32_t)row) + d] = v;
 }
 __global__ void unpad_kernel(const float *__restrict__ src, int64_t n, int D, int LD, const int32_t *__restrict__ order,
                              float *__restrict__ dst) {
@@ -989,15 +997,22 @@ gh_status gh_launch_normalise(gh_engine *h, gh_finish_kind kind, bool with_clean
     const size_t smem = sizeof(float) * 2 * h->LD + sizeof(double) * (size_t)(gh_stats_rows(h->LD) + (src.world > 1 ? 2 : 0)) * h->LD;
     const bool form_c = kind == GH_FINISH_OWN_ALL_STATS;
     float *packed = form_c && h->xch.packed_exchange ? h->xch.d_packed.p + h->xch.lay.own_packed : nullptr;
+    // the whole-graph single-rank finish writes every row of d_pos: the sector-packed table beside it, where the plan has one
+    float *cg = h->plan.compact_gather && kind == GH_FINISH_OWN && src.out_lo == 0 && src.out_rows == h->n ? h->d_cg.p : nullptr;
+    gh_step_compact_valid(h, false);
     const int ldt = form_c ? 0 : h->LD;   // (form C runs no set-up: the kernel without the set-up's registers)
     const auto normalise = [&](auto ld) {   // 0: any row stride, no set-up tiles
         const auto launch = [&](auto kernel) {
             kernel<<<dim3(grid + extra), dim3(256), smem, h->stream>>>(
                 src, h->D, h->LD, h->n, h->d_pos.p, with_cleanup ? h->d_acc.p : nullptr, h->d_tflag.p, h->d_touched.p, h->d_tcount.p,
                 gh_fix_blocks(h->LD), (int)grid, (int)extra, sa, h->d_qexact.p,
-                h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed);
+                h->d_stamps.p ? h->d_stamps.p + (int64_t)std::max(h->n_vblocks, 1) * 8 : nullptr, packed, cg);
         };
         if constexpr (ld() == 4) {   // (the coarse form serves the query-cell path: up to 3 components)
+            if (cg) {   // the instantiations that also write the sector-packed table
+                if (sa.cmin) return sa.rows ? launch(normalise_kernel<4, true, true, true>) : launch(normalise_kernel<4, false, true, true>);
+                return sa.rows ? launch(normalise_kernel<4, true, false, true>) : launch(normalise_kernel<4, false, false, true>);
+            }
             if (sa.cmin) return sa.rows ? launch(normalise_kernel<4, true, true>) : launch(normalise_kernel<4, false, true>);
         }
         if constexpr (ld() > 0) {
@@ -1011,6 +1026,7 @@ gh_status gh_launch_normalise(gh_engine *h, gh_finish_kind kind, bool with_clean
     }
     GH_LAUNCH_CHECK();
     gh_set_lookahead(h, next);
+    gh_step_compact_valid(h, cg != nullptr);
     return GH_OK;
 }
 
@@ -1096,8 +1112,8 @@ gh_status gh_launch_patch_rows(gh_engine *h) {
     return GH_OK;
 }
 
-gh_status gh_launch_pad(gh_engine *h, const float *d_src_nD, float *d_dst_nLD) {
-    pad_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(d_src_nD, h->n, h->D, h->LD, h->d_order.p, d_dst_nLD);
+gh_status gh_launch_pad(gh_engine *h, const float *d_src_nD, float *d_dst_nLD, float *cg) {
+    pad_kernel<<<dim3(grid_for(h->n * h->LD, 256)), dim3(256), 0, h->stream>>>(d_src_nD, h->n, h->D, h->LD, h->d_order.p, d_dst_nLD, cg);
     GH_LAUNCH_CHECK();
     return GH_OK;
 }

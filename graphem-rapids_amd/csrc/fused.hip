@@ -62,27 +62,30 @@ namespace {
 // midpoints of their owned edges -> LDS, and new0 = pos + Fs -> out_new (pt.py:796-799 for every
 // vertex the intersection phase does not touch: Fs + 0 == Fs exactly; the few touched vertices are
 // redone by stats_fix_kernel).  Returns this thread's column sums of new0 for the fp64 statistics.
-template <int D, int LD, int NT, bool LONG>
+// CG: own rows and neighbour rows come from the sector-packed table `cg` (common.h gh_cg_slot) and pos is read only for
+// the hub rows' midpoints: the own-row stream then warms the very lines the gathers hit.
+template <int D, int LD, int NT, bool LONG, bool CG = false>
 __device__ __forceinline__ void gh_phase_a(const float *__restrict__ pos, const int32_t *__restrict__ rowptr,
                                            const int32_t *__restrict__ adj, const int32_t *__restrict__ first_edge,
                                            int v0, int v1, int fe0, int nedges, int64_t row_lo, float L_min, float neg_k,
                                            float *__restrict__ Fs, float *__restrict__ out_new, float *mids,
                                            double (&sx)[LD], double (&sxx)[LD], const gh_long_args &la,
-                                           const float *__restrict__ Fpre = nullptr /* hub forces (the Fs array) */) {
+                                           const float *__restrict__ Fpre = nullptr /* hub forces (the Fs array) */,
+                                           const float *__restrict__ cg = nullptr) {
     if (!Fpre) Fpre = Fs;
 #pragma unroll
     for (int d = 0; d < LD; ++d) { sx[d] = 0.0; sxx[d] = 0.0; }
     for (int i = v0 + threadIdx.x; i < v1; i += NT) {
         const int64_t x = row_lo + i;
         float px[LD], F[LD], nw[LD];
-        gh_load_row<LD>(pos, x, px);
+        gh_gather_row<LD, CG>(CG ? cg : pos, x, px);
         // LONG: the graph has hub rows (their forces come from spring_long_kernel); kept out of the
         // common instantiation, where the extra path costs 8 VGPRs and with them a wave of occupancy
         if constexpr (LONG)
-            spring_row<D, LD, true>(pos, adj, rowptr[i], rowptr[i + 1], x, px, L_min, neg_k, F, mids, first_edge[i] - fe0,
-                                    la, i, Fpre + (int64_t)i * LD);
+            spring_row<D, LD, true, CG>(pos, adj, rowptr[i], rowptr[i + 1], x, px, L_min, neg_k, F, mids, first_edge[i] - fe0,
+                                        la, i, Fpre + (int64_t)i * LD, cg);
         else
-            spring_pull<D, LD, true>(pos, adj, rowptr[i], rowptr[i + 1], x, px, L_min, neg_k, F, mids, first_edge[i] - fe0);
+            spring_pull<D, LD, true, CG>(CG ? cg : pos, adj, rowptr[i], rowptr[i + 1], x, px, L_min, neg_k, F, mids, first_edge[i] - fe0);
         if (Fs) gh_store_row<LD>(Fs, i, F);
 #pragma unroll
         for (int d = 0; d < LD; ++d) {
@@ -134,14 +137,16 @@ __device__ __forceinline__ void gh_block_stats(const double (&sx)[LD], const dou
 // (as in spring_scan_mfmaw_kernel) instead of on the spot by the lane that found them.  Pays where a workgroup meets many
 // of them -- a graph of 100 K vertices, ~70 per workgroup: 59.4 -> 58.2 us per iteration -- and costs three VGPRs, i.e. a wave
 // of occupancy: the launcher takes it for graphs whose workgroups all run at once anyway (1 M vertices with it: 173 -> 189 us).
-template <int D, int R, bool DEFER = false>
+// CG: phase A reads position rows from the sector-packed table `cg` (gh_phase_a).
+template <int D, int R, bool DEFER = false, bool CG = false>
 __global__ __launch_bounds__(256) void spring_scan_mfma_kernel(
     const float *__restrict__ pos, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ adj,
     const int32_t *__restrict__ first_edge, const int32_t *__restrict__ own_eids,
     const int32_t *__restrict__ vblock, int64_t row_lo, float L_min, float neg_k, float *__restrict__ Fs,
     float *__restrict__ out_new, double *__restrict__ blockstats, const float *__restrict__ qt,
     const gh_h8 *__restrict__ qA, const int32_t *__restrict__ qexact, int S, uint64_t *__restrict__ cand,
-    int32_t *__restrict__ cnt, gh_long_args la, gh_tau_args ta, unsigned long long *__restrict__ stamps) {
+    int32_t *__restrict__ cnt, gh_long_args la, gh_tau_args ta, unsigned long long *__restrict__ stamps,
+    const float *__restrict__ cg) {
     constexpr int LD = 4, NT = 256, TILE = NT * R, NB = 2 * R, HITBUF = 512;
     if ((int)blockIdx.x < ta.nblocks) {  // thresholds of this launch (tau_core.h); diagnostic stamps: the last records of the buffer
         gh_tau_produce<NT, 0>(ta, stamps ? stamps + ((int64_t)gridDim.x - 2 * ta.nblocks + GH_STAMP_EXTRA + blockIdx.x) * 8 : nullptr);
@@ -194,7 +199,8 @@ __global__ __launch_bounds__(256) void spring_scan_mfma_kernel(
     __shared__ double red[(NT / 64) * 2 * LD];
     {
         double sx[LD], sxx[LD];
-        gh_phase_a<D, LD, NT, true>(pos, rowptr, adj, first_edge, v0, v1, fe0, nedges, row_lo, L_min, neg_k, Fs, out_new, mids, sx, sxx, la);
+        gh_phase_a<D, LD, NT, true, CG>(pos, rowptr, adj, first_edge, v0, v1, fe0, nedges, row_lo, L_min, neg_k, Fs, out_new, mids, sx, sxx, la,
+                                        nullptr, cg);
         GH_STAMP(1);
         gh_block_stats<LD, NT>(sx, sxx, red, blockstats, bx, nbx, v1 - v0);  // contains the barrier that ends phase A
     }
@@ -342,7 +348,8 @@ __global__ __launch_bounds__(256) void spring_scan_mfma_kernel(
 // gh_ct_tau<KC>, K <= KC keys; setup_core.h "COARSE FORM"), stores it into the query record for the launches behind this
 // one, builds the table from the records at hand and publishes the S records behind the table, under the same flag; the
 // other workgroups stage the records from there, after the poll, instead of from qt before it.
-template <int D, int KC>
+// CG: phase A reads position rows from the sector-packed table `cg` (gh_phase_a).
+template <int D, int KC, bool CG = false>
 __global__ __launch_bounds__(256) void spring_scan_cells_kernel(
     const float *__restrict__ pos, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ adj,
     const int32_t *__restrict__ first_edge, const int32_t *__restrict__ own_eids,
@@ -351,7 +358,8 @@ __global__ __launch_bounds__(256) void spring_scan_cells_kernel(
     uint32_t *__restrict__ qcell, unsigned *__restrict__ qc_flag, unsigned epoch, int32_t *__restrict__ wait_failed,
     uint64_t *__restrict__ cand, int32_t *__restrict__ cnt, gh_long_args la, int cdist, unsigned long long *__restrict__ stamps,
     uint32_t *__restrict__ cmin /* KC > 0: this iteration's copy of the coarse table */, int K,
-    int32_t *__restrict__ tcount_reset /* KC > 0: the touched-list counter to reset (the threshold launch did), or null */) {
+    int32_t *__restrict__ tcount_reset /* KC > 0: the touched-list counter to reset (the threshold launch did), or null */,
+    const float *__restrict__ cg) {
     constexpr int LD = 4, NT = 256, R = 2, TILE = NT * R, HITBUF = 512;
     static_assert(D <= 3, "query records of one 16-byte load");
     __shared__ float4 tile[TILE];               // fp32 midpoints of the owned edges (x, y, z, 0)
@@ -441,7 +449,8 @@ __global__ __launch_bounds__(256) void spring_scan_cells_kernel(
     __shared__ double red[(NT / 64) * 2 * LD];
     {
         double sx[LD], sxx[LD];
-        gh_phase_a<D, LD, NT, true>(pos, rowptr, adj, first_edge, v0, v1, fe0, nedges, row_lo, L_min, neg_k, Fs, out_new, mids, sx, sxx, la);
+        gh_phase_a<D, LD, NT, true, CG>(pos, rowptr, adj, first_edge, v0, v1, fe0, nedges, row_lo, L_min, neg_k, Fs, out_new, mids, sx, sxx, la,
+                                        nullptr, cg);
         GH_STAMP(1);
         gh_block_stats<LD, NT>(sx, sxx, red, blockstats, bx, nbx, v1 - v0);  // contains the barrier that ends phase A
     }
@@ -770,25 +779,43 @@ gh_tau_args fused_tau_args(gh_engine *h, int nt) {
     return ta;
 }
 
-template <int D, int R, bool DEFER>
-void launch_mfma_d(gh_engine *h) {
+// The sector-packed table serves this launch: the plan asks for it and its rows are those of d_pos (engine.h
+// gh_step_compact_valid).  Else the padded instantiation -- never a packing launch.
+static bool fused_compact(const gh_engine *h) { return h->plan.compact_gather && h->step.compact_valid && h->d_cg.p; }
+
+template <int D, int R, bool DEFER, bool CG>
+void launch_mfma_c(gh_engine *h) {
     const gh_tau_args ta = fused_tau_args(h, 256);
-    spring_scan_mfma_kernel<D, R, DEFER><<<dim3(fused_grid(h, ta)), dim3(256), 0, h->stream>>>(
+    spring_scan_mfma_kernel<D, R, DEFER, CG><<<dim3(fused_grid(h, ta)), dim3(256), 0, h->stream>>>(
         h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min,
         -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, reinterpret_cast<const gh_h8 *>(h->d_qA.p),
-        h->d_qexact.p, (int)h->S, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), ta, h->d_stamps.p);
+        h->d_qexact.p, (int)h->S, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), ta, h->d_stamps.p, h->d_cg.p);
 }
-template <int D, int KC>
-void launch_cells_k(gh_engine *h) {
+template <int D, int R, bool DEFER>
+void launch_mfma_d(gh_engine *h) {
+    if constexpr (D == 3) {
+        if (fused_compact(h)) { ++h->compact_launches; return launch_mfma_c<D, R, DEFER, true>(h); }
+    }
+    launch_mfma_c<D, R, DEFER, false>(h);
+}
+template <int D, int KC, bool CG>
+void launch_cells_c(gh_engine *h) {
     if (++h->qc_epoch == 0) h->qc_epoch = 1;   // (0 is the flag's value before the first launch)
     const int p = (int)(h->iter & 1);   // the copy this iteration's set-up filled (gh_make_setup_args)
-    spring_scan_cells_kernel<D, KC><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
+    spring_scan_cells_kernel<D, KC, CG><<<dim3((unsigned)h->n_vblocks + 1), dim3(256), 0, h->stream>>>(
         h->d_pos.p, h->d_rowptr.p, h->d_adj.p, h->d_first_edge.p, h->d_own_eids.p, h->d_vblock.p, h->part.row_lo, h->prm.L_min,
         -h->prm.k_attr, h->d_Fs.p, h->d_new, h->d_blockstats.p, h->d_q.p, (int)h->S, h->d_qcell.p, h->d_qc_flag.p, h->qc_epoch,
         h->d_wait_failed.p, h->d_cand.p, h->d_cnt.p, gh_make_long_args(h, true), h->cdist ? 1 : 0, h->d_stamps.p,
         KC > 0 ? h->d_cmin.p + (size_t)p * GH_CT_M * (size_t)h->S : nullptr, h->Ksel,
-        KC > 0 && h->step.tcount_reset_pending ? h->d_tcount.p : nullptr);
+        KC > 0 && h->step.tcount_reset_pending ? h->d_tcount.p : nullptr, h->d_cg.p);
     if (KC > 0) gh_cmin_release(h, h->iter);
+}
+template <int D, int KC>
+void launch_cells_k(gh_engine *h) {
+    if constexpr (D == 3) {
+        if (fused_compact(h)) { ++h->compact_launches; return launch_cells_c<D, KC, true>(h); }
+    }
+    launch_cells_c<D, KC, false>(h);
 }
 // The thresholds: in memory (a launch of their own has run), or taken by workgroup 0 from the coarse table -- the usual
 // dozen keys in as many registers per thread, up to GH_CT_KMAX in a kernel of its own.

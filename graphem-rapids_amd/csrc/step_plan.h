@@ -24,6 +24,10 @@
 #define GH_FUSED_TILE (GH_FUSED_NT * GH_FUSED_R)
 // A fused launch of at most this many workgroups is a single round or little more: thresholds inside it (gh_tau_place)
 #define GH_TAU_EMBED_MAX_VBLOCKS 2048
+// The sector-packed gather table (common.h gh_cg_slot): most vertices it is built for, and where GH_COMPACT_AUTO takes it
+#define GH_CG_MAX_N ((int64_t)1 << 27)
+#define GH_CG_AUTO_MIN_N 400000
+#define GH_CG_AUTO_MAX_N 2000000
 
 // ---- input: what the engine is ---------------------------------------------------------------------------------------
 struct gh_plan_input {
@@ -44,6 +48,7 @@ struct gh_plan_requests {
     int coarse_mode = GH_COARSE_AUTO;      // gh_set_coarse_tau / GRAPHEM_HIP_COARSE_TAU
     gh_tau_place tau_place = GH_TAU_BY_SIZE;
     bool no_presetup = false;              // GRAPHEM_HIP_NO_PRESETUP
+    int compact_gather = GH_COMPACT_OFF;   // gh_set_compact_gather / GRAPHEM_HIP_COMPACT_GATHER (gh_create asks for GH_COMPACT_AUTO)
 };
 
 // ---- output ----------------------------------------------------------------------------------------------------------
@@ -74,6 +79,8 @@ struct gh_step_plan {
     bool presetup_gathered = false;        // the same for the gathered finishes (forms B and D)
     bool stage_rows = false;               // the stats_fix launch may stage that set-up's rows (d_setup_rows)
     bool ride_along = false;               // the final selection can reduce the fused kernel's column sums (gh_sums_ride_along)
+    bool compact_gather = false;           // the fused kernel reads position rows from the sector-packed 12-byte table (common.h
+                                           // gh_cg_slot) whenever that table is up to date (gh_step_state::compact_valid)
     bool lists() const { return built != GH_SEARCH_BLOCK; }   // candidate lists exist (a filtered search)
 };
 
@@ -86,6 +93,8 @@ struct gh_step_state {
     bool tcount_reset_pending = false;
     bool rows_early = false;
     bool own_ids = false;
+    bool compact_valid = false;
+    bool pos_shared = false;
 };
 
 // The pre-filter of the fused kernels runs on the matrix pipe for every row stride they are built for: split-f16
@@ -173,6 +182,14 @@ inline gh_step_plan gh_make_step_plan(const gh_plan_input &in, const gh_plan_req
     // (not with thousands of queries: there the wave-per-query selection is worth more than the ride, and stats_fix_kernel
     // adds the column sums up itself)
     p.ride_along = in.rows > 0 && in.LD <= 16 && in.S < 2048;
+    // Position rows of the fused D <= 3 kernels from the sector-packed table: three components in rows of four floats, the
+    // whole graph on one rank (its normalise launch writes every row of the table beside the positions), and byte offsets
+    // into the table that fit 32 bits.  AUTO: GH_CG_AUTO_MIN_N .. GH_CG_AUTO_MAX_N vertices, where it was measured ahead
+    // (NOTES.md "The sector-packed gather table"): below, both tables fit the L2s; above, neither does to any extent.
+    const bool cg_ok = p.search == GH_SEARCH_FUSED && in.D == 3 && in.LD == 4 && in.whole() && in.layout == GH_LAYOUT_NONE &&
+                       in.n <= GH_CG_MAX_N;
+    p.compact_gather = cg_ok && (rq.compact_gather == GH_COMPACT_ON ||
+                                 (rq.compact_gather == GH_COMPACT_AUTO && in.n >= GH_CG_AUTO_MIN_N && in.n <= GH_CG_AUTO_MAX_N));
     return p;
 }
 

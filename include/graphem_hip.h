@@ -174,7 +174,9 @@ gh_status gh_intersection_forces_f64(gh_handle h, const int32_t *sampled, const 
 gh_status gh_set_positions(gh_handle h, const float *pos /* (n, D) host */);
 gh_status gh_get_positions(gh_handle h, float *pos /* (n, D) host, blocking */);
 /* Device view for callers that keep data on the GPU (RCCL all-gather, torch tensors):
- * (n, ld) float32 rows, ld = gh_row_stride(h) >= D floats, columns >= D are zero. */
+ * (n, ld) float32 rows, ld = gh_row_stride(h) >= D floats, columns >= D are zero.
+ * The caller may write the rows between steps; from this call on the engine reads no copy it keeps of them
+ * (gh_set_compact_gather). */
 float *gh_positions_device(gh_handle h);
 /* order[v] = row of vertex v in the device position array (identity without reordering). */
 gh_status gh_vertex_order(gh_handle h, int32_t *order);
@@ -363,6 +365,7 @@ gh_status gh_timing_get(gh_handle h, int32_t i, const char **name, double *total
  *   GRAPHEM_HIP_TAU_SEPARATE=1|0  thresholds always in a launch of their own / always by the first workgroups of the fused
  *                                 launch (default: inside for <= 2048 fused workgroups);
  *   GRAPHEM_HIP_COARSE_TAU=1|0    GH_COARSE_ON | GH_COARSE_OFF instead of GH_COARSE_AUTO (gh_set_coarse_tau);
+ *   GRAPHEM_HIP_COMPACT_GATHER=1|0  GH_COMPACT_ON | GH_COMPACT_OFF instead of GH_COMPACT_AUTO (gh_set_compact_gather);
  *   GRAPHEM_HIP_NO_PRESETUP=1     the next iteration's KNN set-up as a launch of its own instead of inside the normalise
  *                                 launch (the per-query flags of gh_knn_last_counts then survive a step);
  *   GRAPHEM_HIP_REORDER=1|2       overrides gh_params.reorder (1 off, 2 breadth-first);
@@ -423,6 +426,30 @@ gh_status gh_set_coarse_tau(gh_handle h, int32_t mode);
 gh_status gh_get_coarse_tau(gh_handle h, int32_t *in_use);
 /* Both copies of the coarse table, (2, 64, sample_size) float bits, 0xFFFFFFFF = empty (diagnostic; count words).  Blocking. */
 gh_status gh_debug_coarse_table(gh_handle h, uint32_t *out, int64_t count);
+/* Where the fused spring+scan kernel of a three-component engine takes position rows from (its own rows and the rows it
+ * gathers; same values, so the same results bit for bit either way):
+ *   GH_COMPACT_ON    a second table of 12-byte rows, five to a 64-byte sector (no row crosses a sector), written beside the
+ *                    positions by the launches that write them.  Whole-graph single-rank fused engines with n_components
+ *                    = 3 only; a step that finds the table out of date (the positions were changed by another entry
+ *                    point) reads the padded positions and the next finish brings it up to date.  Once
+ *                    gh_positions_device has handed the rows out the table is not read again: the caller may write them
+ *                    between any two steps.
+ *   GH_COMPACT_OFF   the padded 16-byte rows of gh_positions_device.
+ *   GH_COMPACT_AUTO  (default; GRAPHEM_HIP_COMPACT_GATHER=1|0 at creation sets ON | OFF) ON where it was measured ahead.
+ * Forcing ON where it cannot serve is not an error: gh_get_compact_gather reports what is in use, 1 or 0 (0 also once the
+ * rows were handed out), and gh_compact_gather_launches how many fused launches of this engine have read the table so far
+ * (a step that found it out of date does not count). */
+#define GH_COMPACT_OFF 0
+#define GH_COMPACT_ON 1
+#define GH_COMPACT_AUTO 2
+gh_status gh_set_compact_gather(gh_handle h, int32_t mode);
+gh_status gh_get_compact_gather(gh_handle h, int32_t *in_use);
+gh_status gh_compact_gather_launches(gh_handle h, int64_t *packed);
+/* The layout of that table on the host (test support): the dword offset of vertex v's row -- of the count vertices from v0
+ * on into out[] -- and the bytes a table for n vertices takes. */
+int64_t gh_compact_slot(int64_t v);
+gh_status gh_compact_slots(int64_t v0, int64_t count, int64_t *out);
+int64_t gh_compact_bytes(int64_t n);
 /* Host copy of the query-cell box (test support): for each of n (q, tau, m) triples of D <= 3 coordinates -- boundaries
  * (D, 7) per axis -- writes the fp32 chain d2(q, m) of the exact test to d2[i], and per axis the cell of m and q's box
  * [lo, hi] to cells[(i * D + d) * 3 + {0, 1, 2}]. */
